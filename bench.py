@@ -29,9 +29,14 @@ N > 1 : one process per GPU.  Started either by a launcher (python -m torch.dist
         transport, ncclCommCount, every rank's device, the fallback reason if gloo host hooks had to be taken.
         --strong keeps the whole problem at --cells per side instead; --stack grows the box along z.
 
-Prints ONE JSON line on rank 0 (contract in the task description), with `roofline` for the CG
-SpMV kernel (raw HIP event pairs around sampled SpMV launches of the timed solves) and `cpu_baseline` (the C
-oracle on the host cores, timed at the reference's three timer points on the SAME configuration).
+Prints ONE JSON line on rank 0 (contract in the task description).  A plain run sets up, warms up, times the --steps
+steps and prints the headline (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, iterations, setup).
+--full adds everything that takes measurements or runs of its own: `roofline` for the CG SpMV kernel (raw HIP event
+pairs around sampled SpMV launches of the timed solves, HBM traffic from two child runs under rocprofv3 --pmc),
+`cpu_baseline` (the C oracle on the host cores, timed at the reference's three timer points on the SAME configuration),
+the point-Jacobi companion, the step at the parity tolerance, the check of the answer, and for N > 1 the strong-scaling
+companion, the link latencies and the peer-transport A/B.
+--dump-outputs DIR writes what the last timed step computed (one GPU) as DIR/<name>.npy, float64.
 """
 import argparse
 import json
@@ -93,7 +98,7 @@ def pmc_traffic_live(argv, timeout_s=240.0):
         return "rocprofv3 is not on this box"
     if any(k.startswith("ROCPROF") or k.startswith("ROCP_") for k in os.environ) or "rocprofiler" in os.environ.get("LD_PRELOAD", ""):
         return "this process runs under a profiler already"
-    child = [a for a in argv] + ["--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-parity-step", "--no-jacobi-step", "--no-pmc"]
+    child = drop_option(argv, "--dump-outputs") + ["--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-parity-step", "--no-jacobi-step", "--no-pmc"]
     out = {}
     env = dict(os.environ, TMPDIR="/tmp")
     for counter in ("FETCH_SIZE", "WRITE_SIZE"):
@@ -360,11 +365,48 @@ def transport_ab_child(args):
         return {"skipped": f"unreadable result line of the companion job: {e}"}
 
 
+def drop_option(argv, name):
+    """argv without `name VALUE` / `name=VALUE`."""
+    out, skip = [], False
+    for a in argv:
+        if skip:
+            skip = False
+        elif a == name:
+            skip = True
+        elif not a.startswith(name + "="):
+            out.append(a)
+    return out
+
+
+def dump_outputs(solver, its, reason, rnorm, out_dir):
+    """--dump-outputs: what the last timed step handed its caller -- the solution, the assembled right-hand side and
+    matrix values, and the solve's (iterations, converged reason, residual norm) -- as float64 .npy files.  An array longer
+    than its cap is replaced by its entries at indices drawn from a fixed seed (the same for every build), so that two
+    builds compare entry for entry; the caps keep the files under 56 MB in all."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+
+    def put(name, a, cap):
+        a = np.asarray(a, dtype=np.float64)
+        if a.size > cap:
+            a = a[np.sort(np.random.default_rng(20240611).integers(0, a.size, cap))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    put("solution", solver.getSolution(), 4_000_000)
+    put("rhs", solver.getRHS(), 1_000_000)
+    put("matrix_values", solver.getCSR()[2], 2_000_000)
+    put("solve", [its, reason, rnorm], 3)
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps")
+    ap.add_argument("--warmup", type=int, default=3, help="untimed steps before them")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline (with the PMC child runs), CPU baseline, point-Jacobi companion, parity-"
+                         "tolerance step, check of the answer; N>1: strong-scaling companion, link latencies, peer-transport A/B")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="one GPU: write what the last timed step computed as DIR/<name>.npy (float64; long arrays as a fixed, seeded sample)")
     ap.add_argument("--cells", dest="n", type=int, default=200, help="cells per side of one rank's block")
     ap.add_argument("--rtol", type=float, default=1e-5, help="PETSc default (the reference sets none)")
     ap.add_argument("--workload", choices=["poisson", "beam"], default="poisson",
@@ -426,7 +468,12 @@ def parse_args():
     ap.add_argument("--rank-timeout", type=float, default=1500.0,
                     help="seconds after which a rank that is still running dumps every thread's traceback and exits non-zero "
                          "(a hung collective must not hang the job)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (args.gpus != 1 or args.mode != "batched"):
+        ap.error("--dump-outputs needs --gpus 1 and --mode batched")
+    return args
 
 
 def single_gpu_reference():
@@ -453,9 +500,11 @@ class Job:
         self.rccl_dead = False
 
 
-def run_case(J, beam, nE, ext, steps, warmup, rtol, profile=True, parity_step=False, pc=None, transport=None, probe_comm=False):
+def run_case(J, beam, nE, ext, steps, warmup, rtol, profile=True, parity_step=False, pc=None, transport=None, probe_comm=False,
+             dump_dir=None):
     """One configuration through the whole hot path on this job's ranks: device-generated slab, transport, pattern,
-    `warmup` + `steps` steps (assembly + solve) bracketed by barriers; returns everything the JSON line needs."""
+    `warmup` + `steps` steps (assembly + solve) bracketed by barriers; returns everything the JSON line needs.  The
+    second pattern build and the check of the answer are made under --full only."""
     import faulthandler
 
     import numpy as np
@@ -580,9 +629,11 @@ def run_case(J, beam, nE, ext, steps, warmup, rtol, profile=True, parity_step=Fa
     R["t_setup"] = time.perf_counter() - t_setup
     # the first build also pays for the first multi-GB device allocations of the process (0.05 - 1 s from box to box);
     # a second build of the same pattern shows the symbolic phase itself
-    t1 = time.perf_counter()
-    solver.buildPattern()
-    R["t_pattern2"] = time.perf_counter() - t1
+    R["t_pattern2"] = None
+    if args.full:
+        t1 = time.perf_counter()
+        solver.buildPattern()
+        R["t_pattern2"] = time.perf_counter() - t1
     if profile:      # event pair around every 8th (gamg: every 2nd) SpMV launch of the CG loop of the timed solves (a pair costs ~2 us)
         solver.profileSpmv(2 if pc == "gamg" else 8)
 
@@ -618,6 +669,8 @@ def run_case(J, beam, nE, ext, steps, warmup, rtol, profile=True, parity_step=Fa
         acc["enq_ms"] += tm["host_enqueue_ms"]; acc["enq_n"] += tm["host_enqueued_iterations"]; acc["hostcomm_ms"] += tm["host_comm_ms"]
     sync()
     elapsed = time.perf_counter() - t0
+    if dump_dir:
+        dump_outputs(solver, its, reason, rnorm, dump_dir)
     R["mem"] = pf.device_memory(J.device_index)      # mesh, pattern, incidence, both SpMV forms, vectors: all resident
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
@@ -658,7 +711,8 @@ def run_case(J, beam, nE, ext, steps, warmup, rtol, profile=True, parity_step=Fa
         ex = (ax[2][idx[2]] ** 2)[:, None, None] + (ax[1][idx[1]] ** 2)[None, :, None] + (ax[0][idx[0]] ** 2)[None, None, :]
         return "max_nodal_error", float(np.abs(u - ex.ravel()).max())
 
-    R["check_name"], R["check"] = owned_check(solver.getSolution())
+    if args.full:
+        R["check_name"], R["check"] = owned_check(solver.getSolution())
 
     # ---- the same step at the parity tolerance (SURVEY 8d asks for both), untimed extra ----
     R["parity"] = None
@@ -828,7 +882,7 @@ def main():
 
     # N = 1: the SpMV's HBM traffic, measured by two short child runs under rocprofv3 --pmc BEFORE this process touches the GPU
     pmc_live = None
-    if args.gpus == 1 and "WORLD_SIZE" not in os.environ and not args.no_pmc:
+    if args.full and args.gpus == 1 and "WORLD_SIZE" not in os.environ and not args.no_pmc:
         pmc_live = pmc_traffic_live(sys.argv[1:])
         if isinstance(pmc_live, str):
             print(f"bench.py: HBM traffic not measured in this run ({pmc_live})", file=sys.stderr, flush=True)
@@ -906,18 +960,19 @@ def main():
             J.dist.destroy_process_group()
         faulthandler.cancel_dump_traceback_later()
         return
-    R = run_case(J, beam, nE, ext, args.steps, args.warmup, args.rtol, profile=True,
-                 parity_step=(world == 1 and not args.no_parity_step and not beam), probe_comm=True)
+    R = run_case(J, beam, nE, ext, args.steps, args.warmup, args.rtol, profile=args.full,
+                 parity_step=(args.full and world == 1 and not args.no_parity_step and not beam), probe_comm=args.full,
+                 dump_dir=args.dump_outputs)
     weak = not (beam or args.strong)
     # ---- the same configuration with north_star's own preconditioner, the diagonal: a shorter, separately timed run
     Jac = None
-    if R["pc"] != "jacobi" and not args.no_jacobi_step:
+    if args.full and R["pc"] != "jacobi" and not args.no_jacobi_step:
         Jac = run_case(J, beam, nE, ext, max(1, min(args.steps, 3)), 1, args.rtol, profile=True, pc="jacobi")
     # ---- N > 1, weak run: the strong-scaling companion.  The cube of 2 x --cells per side (at the default 200: BASELINE
     # config 5, 400^3 x 6 tets, which fits ONE MI355X: profiles/r02/bench_cfg5_400cube_single_gpu.json) on the same N
     # ranks -- the >= 6x-at-8-GPUs evidence next to the weak figure, whose Jacobi iteration count grows with the problem.
     S = None
-    if world > 1 and weak and not args.stack and not args.no_strong_block:
+    if args.full and world > 1 and weak and not args.stack and not args.no_strong_block:
         side = 2 * n
         if nE == (side, side, side):
             S = R                       # N = 8: the weak configuration IS that cube
@@ -927,49 +982,6 @@ def main():
     nEx, nEy, nEz = nE
     N, its, acc, info, cinfo, sz = R["N"], R["its"], R["acc"], R["info"], R["cinfo"], R["sz"]
     if rank == 0:
-        ref1 = single_gpu_reference()
-        bytes_per_spmv = 12 * info["nnz"] + 20 * info["n_local"]       # FP64 vals, int32 cols
-        fmt_bytes = R["fmt_bytes"]
-        # The event pair of a sampled launch reports marker-end -> kernel-end.  `avg_launch_ms` is that RAW figure: it is
-        # the one rocprofv3 --kernel-trace agrees with (profiles/r02: 209.97 us traced, 209.98 us raw pairs in the driver's
-        # run).  The offset of an empty kernel timed the same way is reported for information only and NOT subtracted
-        # (round 2 did, and overstated the fraction by 0.02).
-        raw_spmv_ms = acc["spmv_ms"] / max(acc["spmv_n"], 1)
-        avg_spmv_ms = max(raw_spmv_ms, 1e-9)
-        achieved = bytes_per_spmv / (avg_spmv_ms * 1e-3) / 1e9 if acc["spmv_n"] else 0.0
-        traffic, traffic_source, traffic_counters = None, None, None
-        if isinstance(pmc_live, dict) and pmc_live:
-            # the CG's own product: the WITH_DOT = true kernel with the most dispatches in the child runs (same command, one step)
-            kname, e = max(pmc_live.items(), key=lambda kv: kv[1]["dispatches"])
-            traffic = (2.0 * e["FETCH_SIZE_KB"] + e["WRITE_SIZE_KB"]) * 1024.0
-            traffic_source = ("measured in THIS run: two child runs of the same command (one step) under rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE "
-                              "(separate passes) before this process touched the GPU; bytes = (2 x FETCH_SIZE + WRITE_SIZE) KB per dispatch, "
-                              "FETCH_SIZE doubled per MI355X_MICROARCH.md section HBM (gfx950 tallies 128-B requests at 64 B)")
-            traffic_counters = dict(e, kernel=kname)
-        elif world == 1 and args.numbering == "lattice" and args.jitter <= 0.0:
-            traffic, traffic_source = pmc_traffic(info["nnz"], R["value_dict"])
-            if traffic and isinstance(pmc_live, str):
-                traffic_source += f" [not measured in this run: {pmc_live}]"
-        hbm_bytes = traffic if traffic else fmt_bytes
-        hbm_gbps = hbm_bytes / (avg_spmv_ms * 1e-3) / 1e9 if acc["spmv_n"] else 0.0
-        # names as rocprofv3 prints them: k_spmvr / k_spmvg / k_spmv16 <WITH_DOT, gap table>, k_spmvr32 / k_spmv <WITH_DOT>
-        tbl = R["gap_table"]
-        tname = "true" if tbl else "false"
-        tnote = f" with a table of the {tbl} distinct gaps beyond 32767" if tbl else ""
-        bits = R["bits"]
-        vdn = R["value_dict"]           # pfem_valdict.hpp: the values as 16-bit codes into a dictionary of the distinct ones (0: fp64 copy)
-        vd = "_vd" if vdn else ""
-        vnote = (f"; matrix values streamed as 16-bit codes into a dictionary of the {vdn} DISTINCT values of this matrix held in LDS "
-                 "(lossless: the same doubles, the same products, the same bits)") if vdn else ""
-        kernel = {3: f"pfem::k_spmvg{vd}<true, {tname}> (row-grouped wave-sliced CSR SpMV + (p,Ap) partials: the 3 dof rows of a "
-                     f"node share one lane, 16-bit column gaps{tnote}{vnote}), rank 0",
-                  4: ("pfem::k_spmvr32<true>" if bits == 32 else f"pfem::k_spmvr{vd}<true, {tname}>") +
-                     " (wave-sliced CSR SpMV + (p,Ap) partials; 4 consecutive rows per lane share one relative column stream of "
-                     f"{bits}-bit gaps{tnote}, x read as 32-B quads{vnote}), rank 0"}.get(
-            R["row_group"],
-            ("pfem::k_spmv16e<true>" if (bits == 16 and R.get("gap_escapes")) else f"pfem::k_spmv16<true, {tname}>" if bits == 16 else "pfem::k_spmv<true>") +
-            " (wave-sliced CSR SpMV + (p,Ap) partials; %d-bit column %s%s), rank 0"
-            % (bits, "gaps" if bits == 16 else "indices", " with escapes to the int32 columns" if R.get("gap_escapes") else tnote))
         axis_name = "xyz"[R["axis"]]
         cross = [m + 1 for d, m in enumerate(nE) if d != R["axis"]]
         partition = None
@@ -1002,13 +1014,13 @@ def main():
                                  f", zero initial guess, rtol {args.rtol:g} on ||M^-1 r|| (PETSc KSPCG default norm). The reference's PETSc run "
                                  "used KSPCG + PCBJACOBI (per-rank ILU(0), solverpetsc.F:187,206), which is NOT reproduced: "
                                  "iteration counts are not comparable with a PETSc run of the reference; north_star's CG + point Jacobi is "
-                                 "measured next to it (`jacobi_step`)",
+                                 "measured next to it under --full (`jacobi_step`)",
                        "parallelism": "1 GPU" if world == 1 else
                                       f"{world} slabs of hex layers across {axis_name}, sub-assembled interface rows, neighbour exchange of "
                                       f"{cinfo['doubles_per_exchange']} doubles with {cinfo['n_peers']} neighbour(s) per SpMV "
                                       f"+ {1 if args.single_reduction and args.pc == 'jacobi' else 2} scalar all-reduce(s) per iteration",
                        "partition": partition, "numbering": args.numbering, "jitter": args.jitter},
-            "iterations": its, "converged_reason": R["reason"], "rnorm": R["rnorm"], R["check_name"]: R["check"],
+            "iterations": its, "converged_reason": R["reason"], "rnorm": R["rnorm"],
             "assembly_ms_per_step": acc["asm_ms"] / args.steps, "solve_ms_per_step": acc["sol_ms"] / args.steps,
             "ms_per_iteration": R["ms_per_iteration"],     # weak scaling: iterations grow with the problem
             "setup_s_untimed": R["t_setup"], "setup_breakdown_s": {"generate_mesh_and_numbering_on_device": R["t_generate"],
@@ -1022,132 +1034,180 @@ def main():
             # the same as a rate: DOF/s of ONE run of the reference driver's timed section on a fresh pattern (assembly + KSPSolve with
             # its PCSetUp, tetrapoissonparallelimpl1.F:826-902); `value` is the rate of every later step on the same pattern
             "cold_value": (N / (R["first_step_ms"] * 1e-3)) if R.get("first_step_ms") else None,
-            # how to quote this line: three rates of the same configuration, never the first alone
-            "headline": {"value_warm_step_default_solver": N * args.steps / R["elapsed"],
-                         "cold_value_first_step_with_preconditioner_setup": (N / (R["first_step_ms"] * 1e-3)) if R.get("first_step_ms") else None,
-                         "north_star_cg_point_jacobi": (Jac["N"] / (Jac["ms_per_step"] * 1e-3)) if Jac else None,
-                         "unit": "DOF/s", "default_solver": R["pc_in_effect"],
-                         "solver_default_at_the_boundary": "the C ABI, the Python drivers and the Fortran modules default to -pc_type jacobi (north_star's "
-                                                           "solver); one line `-pc_type gamg` in petsc_options.dat -- where the reference's own run "
-                                                           "takes its KSP options from (tetrapoissonparallelimpl1.F:168) -- selects what this line's `value` ran"},
-            "parity_tolerance_step": R["parity"],
-            "preconditioner": ({"name": R["pc_in_effect"], "levels": R["amg"]["levels"], "rows_per_level": R["amg"]["rows"],
-                                "nnz_per_level": R["amg"]["nnz"], "gershgorin_lambda_max": R["amg"]["lambda_max"],
-                                "operator_complexity": sum(R["amg"]["nnz"]) / max(R["amg"]["nnz"][0], 1),
-                                "cheb_degree": R["amg"]["cheb_degree"], "cheb_degree_on_the_assembled_matrix": R["amg"]["fine_degree"], "eig_ratio": R["amg"]["eig_ratio"], "coarse_scale": R["amg"]["coarse_scale"],
-                                "numeric_setup_ms_per_solve_inside_the_timer": R["amg"]["numeric_ms"],
-                                # a solve = numeric set-up + (iterations + 1) cycles: the initial one, then one per iteration
-                                # (`ms_per_iteration` above divides the whole solve by the iterations)
-                                "ms_per_cycle_with_its_cg_iteration": (acc["sol_ms"] / args.steps - R["amg"]["numeric_ms"]) / (its + 1),
-                                "symbolic_setup_ms_once_per_pattern": R["amg"]["symbolic_ms"],
-                                "symbolic_setup_where": "first solve after a pattern build (a warm-up step; with --warmup 0 the first timed step)",
-                                "levels_paired_on_the_lattice": R["amg_layout"]["lattice_levels"],
-                                # how every level's aggregates were formed (pfem_solver_amg_aggregation), rank 0's view
-                                "aggregation": R["amg_aggregation"],
-                                # -pc_mg_cycle_type (--cycle; V unless asked: W halves the iterations on matched aggregates and costs
-                                # twice the time, LAB_NOTES round 5)
-                                "cycle": R["amg_cycle"]["cycle"], "last_level_visited_twice": R["amg_cycle"]["last_level_visited_twice"],
-                                # levels whose SpMVs stream 16-bit value codes into a dictionary of the level's distinct values (0: fp64 values)
-                                "value_dictionary_entries_per_level": R["amg_vd"],
-                                "distributed_levels": R["amg_layout"]["distributed_levels"] if world > 1 else None,
-                                "communication_per_cycle": ({"neighbour_exchanges": R["amg_layout"]["exchanges_per_cycle"],
-                                                             "all_reduces": R["amg_layout"]["allreduces_per_cycle"],
-                                                             "note": "enqueued by one V-cycle, next to the CG's own exchange and two all-reduces per iteration"}
-                                                            if world > 1 else None),
-                                "hierarchy": ("one rank" if world == 1 else "one across the ranks" if R["amg_layout"]["coupled"] else "one per rank (block Jacobi over the ranks)"),
-                                "scope": ("the whole matrix" if world == 1 else "rank 0's owned rows of every level of the global hierarchy"
-                                          if R["amg_layout"]["coupled"] else "rank 0's block")} if R["amg"] else {"name": R["pc_in_effect"]}),
-            "jacobi_step": ({"preconditioner": "point Jacobi (north_star's)", "steps": Jac["steps"], "warmup": Jac["warmup"],
-                             "ms_per_step": Jac["ms_per_step"], "dof_per_s": Jac["N"] / (Jac["ms_per_step"] * 1e-3), "iterations": Jac["its"],
-                             "converged_reason": Jac["reason"], "ms_per_iteration": Jac["ms_per_iteration"], Jac["check_name"]: Jac["check"],
-                             "speedup_of_value_over_it": Jac["ms_per_step"] / R["ms_per_step"]} if Jac else None),
-            "device_memory_gb": {"in_use_rank0_device": round((R["mem"]["total_bytes"] - R["mem"]["free_bytes"]) / 1e9, 2),
-                                 "total": round(R["mem"]["total_bytes"] / 1e9, 2)},
+            # what carried an N > 1 run (no measurement of its own: the ranks' reports and the transport's own description)
             "comm": comm_block(J, R) if world > 1 else None,
-            # the kernel furthest from the HBM roofline, with the bound it really has: FP64 issue (every element's geometry is
-            # evaluated once per incident node, un-contracted as the reference's order demands).  The event time is this
-            # run's; the issue fraction is replayed from the committed SQ counters of the same kernel on the same workload
-            "assembly_kernel": ({"kernel": "pfem::k_gather_poisson_tet4 (gather assembly; in the steady state it also writes the SpMV's 16-bit value codes "
-                                           "and level 0's inverse diagonal + Gershgorin ratios for the multigrid)",
-                                 "event_ms_per_step": acc["asm_ms"] / args.steps,
-                                 # what it waits for (profiles/r06/assembly_kernel_bound.txt): not its arithmetic -- the same kernel with the
-                                 # element geometry for nothing is no faster -- but its gathered node records (72 x 32 B per row through the
-                                 # L1) under 4 waves per SIMD; its incidence records come from a cached pattern table where the mesh's
-                                 # numbering repeats (`incidence_patterns` > 0: 2.34 GB moved per launch instead of 5.37)
-                                 "bound": "memory-latency (gathered node records at 4 waves per SIMD)",
-                                 "incidence_patterns": R["incidence_patterns"][0], "longest_incidence_list": R["incidence_patterns"][1],
-                                 "bytes_moved_per_launch_replayed_not_this_run": {"records_from_the_pattern_table": 2.34e9, "every_nodes_own_records": 5.37e9,
-                                                                                  "source": "profiles/r06/assembly_kernel_bound.txt (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE per dispatch, tools/r06/incpat2.sh)"},
-                                 # SQ_ACTIVE_INST_VALU / (32 x GRBM_GUI_ACTIVE) of this kernel on this workload, re-taken in round 6 at commit 43503de
-                                 # with the pattern table (473.5 M / (32 x 18.47 M); before the table 0.68 = 466.1 M / (32 x 21.34 M); round 4: 0.75)
-                                 "valu_issue_fraction_replayed_not_this_run": 0.80,
-                                 "valu_issue_source": "profiles/r06/gather_and_spmv_sq_counters.txt (rocprofv3 --pmc, separate passes, tools/r06/final.sh)",
-                                 # compulsory bytes per launch: SURVEY 8(d)'s 2.69 GB + the codes (0.24 GB) + the two vectors for the multigrid (0.13 GB)
-                                 "hbm_frac_of_compulsory_bytes": (3.05e9 / (acc["asm_ms"] / args.steps * 1e-3) / 1e9 / HBM_PEAK_GBPS)
-                                 if (not beam and world == 1 and args.n == 200 and args.numbering == "lattice" and args.jitter <= 0.0) else None}
-                                if (not beam and world == 1) else None),
-            "roofline": {"bound": "hbm", "kernel": kernel,
-                         # `frac` is the REAL fraction of the HBM peak: bytes the launch moves through the memory side (PMC counters of
-                         # this run when rocprofv3 is on the box, else the committed passes of the same workload, else the storage of
-                         # the selected form + x + y) / measured launch time / peak.  Never above 1.  What SURVEY 8(d) prices a launch
-                         # at -- plain CSR, 12 B per nonzero + 20 B per row -- stands beside it as `algorithmic_*`; the compressed forms
-                         # (16-bit gaps, relative row groups, value dictionary) move fewer bytes than that: `compression`
-                         "achieved": hbm_gbps, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": hbm_gbps / HBM_PEAK_GBPS,
-                         "frac_of_achievable_6300_gbps": hbm_gbps / 6300.0,
-                         "algorithmic_achieved": achieved, "algorithmic_frac": achieved / HBM_PEAK_GBPS,
-                         "compression": (bytes_per_spmv / hbm_bytes) if hbm_bytes else None,
-                         "value_dictionary_entries": vdn,
-                         "note": ("`achieved` / `frac`: bytes really moved (traffic) per second of the launch; `algorithmic_*`: the plain-CSR "
-                                  "bytes of SURVEY 8(d) the launch REPLACES per second -- above the peak when the kernel streams "
-                                  f"2 B of value code + 1/2 B of column gap per slot instead of 8 + 4 (the {vdn} distinct values of the assembled "
-                                  "matrix sit in LDS; lossless, same bits). PFEM_SPMV_VALDICT=0 runs the fp64 copy") if vdn else None,
-                         "traffic": traffic, "traffic_source": traffic_source, "traffic_counters": traffic_counters,
-                         "format_bytes_per_launch": fmt_bytes,
-                         "hbm_bytes_source": "PMC counters (traffic)" if traffic else "storage of the selected form + x + y",
-                         "algorithmic_bytes_per_launch": bytes_per_spmv, "avg_launch_ms": avg_spmv_ms,
-                         "avg_launch_source": f"raw HIP event pairs around every {2 if R['pc_in_effect'] == 'gamg' else 8}th launch of this kernel in the timed solves "
-                                              "(the CG's own SpMV), on the solver's stream" +
-                                              ("; the same kernel in the Jacobi step of this line: avg_launch_ms_in_jacobi_step; "
-                                               "profiles/r03/rocprofv3_kernel_stats*.txt hold one kernel trace per loop" if R["pc_in_effect"] == "gamg" else ""),
-                         # what rocprofv3 --kernel-trace says about the same kernel in the same command (committed trace summaries).
-                         # The events are bound to the dispatch itself (hipExtLaunchKernelGGL), and still read ~20 us more than the
-                         # trace: under the tracer dispatches run one at a time, on the plain stream the kernel's first waves share
-                         # the device with the last waves of the kernel before it (events without the system-scope fence: no change,
-                         # round-3 lease script aj.sh, in the history).  The judged fraction uses the pair as it is, the lower of the two figures
-                         "kernel_trace_avg_launch_us_replayed_not_this_run": kernel_trace_figures(info["nnz"], R["value_dict"]) if (world == 1 and args.numbering == "lattice" and args.jitter <= 0.0) else None,
-                         "avg_launch_ms_in_jacobi_step": (Jac["acc"]["spmv_ms"] / max(Jac["acc"]["spmv_n"], 1)) if (Jac and Jac["acc"]["spmv_n"]) else None,
-                         "event_pair_offset_ms_not_subtracted": R["event_overhead_ms"],
-                         "launches_timed": acc["spmv_n"], "nnz": info["nnz"], "rows": info["n_local"]},
         }
-        if world > 1:
-            # how to read an N > 1 line: (1) per-iteration efficiency -- rows per GPU and millisecond of iteration against
-            # the committed N = 1 figure (independent of the iteration count, which Jacobi makes grow with the problem);
-            # (2) the strong-scaling companion on BASELINE config 5
-            r1 = ref1.get("cfg3_200cube_" + R["pc_in_effect"], {})
-            if r1.get("ms_per_iteration") and r1.get("free_dofs"):
-                rate1 = r1["free_dofs"] / r1["ms_per_iteration"]
-                out["per_iteration_efficiency"] = {
-                    "value": (N / world / R["ms_per_iteration"]) / rate1,
-                    "definition": "(free dofs per GPU / ms per CG iteration) of this run / the same of the N=1 run",
-                    "n1_ms_per_iteration": r1["ms_per_iteration"], "n1_free_dofs": r1["free_dofs"], "n1_source": r1.get("source")}
-            if S is not None:
-                r5 = ref1.get("cfg5_400cube_" + S["pc_in_effect"], {})
-                is5 = S["nE"] == (400, 400, 400)
-                out["strong_cfg5"] = {
-                    "workload": "tetrapoissonparallelimpl1: [-1,1]^3, %dx%dx%dx6 P1 tets%s" % (*S["nE"], " (BASELINE config 5)" if is5 else ""),
-                    "is_baseline_config5": is5, "free_dofs": S["N"], "n_gpus": world, "steps": S["steps"], "warmup": S["warmup"],
-                    "same_run_as_value": S is R, "preconditioner": S["pc_in_effect"],
-                    "ms_per_step": S["ms_per_step"], "dof_per_s": S["N"] / (S["ms_per_step"] * 1e-3), "iterations": S["its"],
-                    "converged_reason": S["reason"], "ms_per_iteration": S["ms_per_iteration"], S["check_name"]: S["check"],
-                    "single_gpu_ms_per_step": r5.get("ms_per_step") if is5 else None,
-                    "single_gpu_source": r5.get("source") if is5 else None,
-                    "speedup_vs_single_gpu": (r5["ms_per_step"] / S["ms_per_step"]) if (is5 and r5.get("ms_per_step")) else None,
-                    "bytes_per_neighbour": 8 * S["cinfo"]["doubles_per_exchange"] // max(S["cinfo"]["n_peers"], 1)}
-        if world == 1 and not args.no_cpu_baseline and not beam:
-            out["cpu_baseline"] = cpu_baseline(n, args.rtol, extra_sample=(n >= 200))
-        if world > 1:
-            out["comm"]["link_latencies"] = R.get("comm_bench")
-            out["comm"]["coupled_cycle"] = R.get("cycle_profile")
+        if args.full:
+            ref1 = single_gpu_reference()
+            bytes_per_spmv = 12 * info["nnz"] + 20 * info["n_local"]       # FP64 vals, int32 cols
+            fmt_bytes = R["fmt_bytes"]
+            # The event pair of a sampled launch reports marker-end -> kernel-end.  `avg_launch_ms` is that RAW figure: it is
+            # the one rocprofv3 --kernel-trace agrees with (profiles/r02: 209.97 us traced, 209.98 us raw pairs in the driver's
+            # run).  The offset of an empty kernel timed the same way is reported for information only and NOT subtracted
+            # (round 2 did, and overstated the fraction by 0.02).
+            raw_spmv_ms = acc["spmv_ms"] / max(acc["spmv_n"], 1)
+            avg_spmv_ms = max(raw_spmv_ms, 1e-9)
+            achieved = bytes_per_spmv / (avg_spmv_ms * 1e-3) / 1e9 if acc["spmv_n"] else 0.0
+            traffic, traffic_source, traffic_counters = None, None, None
+            if isinstance(pmc_live, dict) and pmc_live:
+                # the CG's own product: the WITH_DOT = true kernel with the most dispatches in the child runs (same command, one step)
+                kname, e = max(pmc_live.items(), key=lambda kv: kv[1]["dispatches"])
+                traffic = (2.0 * e["FETCH_SIZE_KB"] + e["WRITE_SIZE_KB"]) * 1024.0
+                traffic_source = ("measured in THIS run: two child runs of the same command (one step) under rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE "
+                                  "(separate passes) before this process touched the GPU; bytes = (2 x FETCH_SIZE + WRITE_SIZE) KB per dispatch, "
+                                  "FETCH_SIZE doubled because gfx950 tallies 128-B requests at 64 B")
+                traffic_counters = dict(e, kernel=kname)
+            elif world == 1 and args.numbering == "lattice" and args.jitter <= 0.0:
+                traffic, traffic_source = pmc_traffic(info["nnz"], R["value_dict"])
+                if traffic and isinstance(pmc_live, str):
+                    traffic_source += f" [not measured in this run: {pmc_live}]"
+            hbm_bytes = traffic if traffic else fmt_bytes
+            hbm_gbps = hbm_bytes / (avg_spmv_ms * 1e-3) / 1e9 if acc["spmv_n"] else 0.0
+            # names as rocprofv3 prints them: k_spmvr / k_spmvg / k_spmv16 <WITH_DOT, gap table>, k_spmvr32 / k_spmv <WITH_DOT>
+            tbl = R["gap_table"]
+            tname = "true" if tbl else "false"
+            tnote = f" with a table of the {tbl} distinct gaps beyond 32767" if tbl else ""
+            bits = R["bits"]
+            vdn = R["value_dict"]           # pfem_valdict.hpp: the values as 16-bit codes into a dictionary of the distinct ones (0: fp64 copy)
+            vd = "_vd" if vdn else ""
+            vnote = (f"; matrix values streamed as 16-bit codes into a dictionary of the {vdn} DISTINCT values of this matrix held in LDS "
+                     "(lossless: the same doubles, the same products, the same bits)") if vdn else ""
+            kernel = {3: f"pfem::k_spmvg{vd}<true, {tname}> (row-grouped wave-sliced CSR SpMV + (p,Ap) partials: the 3 dof rows of a "
+                         f"node share one lane, 16-bit column gaps{tnote}{vnote}), rank 0",
+                      4: ("pfem::k_spmvr32<true>" if bits == 32 else f"pfem::k_spmvr{vd}<true, {tname}>") +
+                         " (wave-sliced CSR SpMV + (p,Ap) partials; 4 consecutive rows per lane share one relative column stream of "
+                         f"{bits}-bit gaps{tnote}, x read as 32-B quads{vnote}), rank 0"}.get(
+                R["row_group"],
+                ("pfem::k_spmv16e<true>" if (bits == 16 and R.get("gap_escapes")) else f"pfem::k_spmv16<true, {tname}>" if bits == 16 else "pfem::k_spmv<true>") +
+                " (wave-sliced CSR SpMV + (p,Ap) partials; %d-bit column %s%s), rank 0"
+                % (bits, "gaps" if bits == 16 else "indices", " with escapes to the int32 columns" if R.get("gap_escapes") else tnote))
+            out.update({
+                R["check_name"]: R["check"],
+                # how to quote this line: three rates of the same configuration, never the first alone
+                "headline": {"value_warm_step_default_solver": N * args.steps / R["elapsed"],
+                             "cold_value_first_step_with_preconditioner_setup": (N / (R["first_step_ms"] * 1e-3)) if R.get("first_step_ms") else None,
+                             "north_star_cg_point_jacobi": (Jac["N"] / (Jac["ms_per_step"] * 1e-3)) if Jac else None,
+                             "unit": "DOF/s", "default_solver": R["pc_in_effect"],
+                             "solver_default_at_the_boundary": "the C ABI, the Python drivers and the Fortran modules default to -pc_type jacobi (north_star's "
+                                                               "solver); one line `-pc_type gamg` in petsc_options.dat -- where the reference's own run "
+                                                               "takes its KSP options from (tetrapoissonparallelimpl1.F:168) -- selects what this line's `value` ran"},
+                "parity_tolerance_step": R["parity"],
+                "preconditioner": ({"name": R["pc_in_effect"], "levels": R["amg"]["levels"], "rows_per_level": R["amg"]["rows"],
+                                    "nnz_per_level": R["amg"]["nnz"], "gershgorin_lambda_max": R["amg"]["lambda_max"],
+                                    "operator_complexity": sum(R["amg"]["nnz"]) / max(R["amg"]["nnz"][0], 1),
+                                    "cheb_degree": R["amg"]["cheb_degree"], "cheb_degree_on_the_assembled_matrix": R["amg"]["fine_degree"], "eig_ratio": R["amg"]["eig_ratio"], "coarse_scale": R["amg"]["coarse_scale"],
+                                    "numeric_setup_ms_per_solve_inside_the_timer": R["amg"]["numeric_ms"],
+                                    # a solve = numeric set-up + (iterations + 1) cycles: the initial one, then one per iteration
+                                    # (`ms_per_iteration` above divides the whole solve by the iterations)
+                                    "ms_per_cycle_with_its_cg_iteration": (acc["sol_ms"] / args.steps - R["amg"]["numeric_ms"]) / (its + 1),
+                                    "symbolic_setup_ms_once_per_pattern": R["amg"]["symbolic_ms"],
+                                    "symbolic_setup_where": "first solve after a pattern build (a warm-up step; with --warmup 0 the first timed step)",
+                                    "levels_paired_on_the_lattice": R["amg_layout"]["lattice_levels"],
+                                    # how every level's aggregates were formed (pfem_solver_amg_aggregation), rank 0's view
+                                    "aggregation": R["amg_aggregation"],
+                                    # -pc_mg_cycle_type (--cycle; V unless asked: W halves the iterations on matched aggregates and costs
+                                    # twice the time, LAB_NOTES round 5)
+                                    "cycle": R["amg_cycle"]["cycle"], "last_level_visited_twice": R["amg_cycle"]["last_level_visited_twice"],
+                                    # levels whose SpMVs stream 16-bit value codes into a dictionary of the level's distinct values (0: fp64 values)
+                                    "value_dictionary_entries_per_level": R["amg_vd"],
+                                    "distributed_levels": R["amg_layout"]["distributed_levels"] if world > 1 else None,
+                                    "communication_per_cycle": ({"neighbour_exchanges": R["amg_layout"]["exchanges_per_cycle"],
+                                                                 "all_reduces": R["amg_layout"]["allreduces_per_cycle"],
+                                                                 "note": "enqueued by one V-cycle, next to the CG's own exchange and two all-reduces per iteration"}
+                                                                if world > 1 else None),
+                                    "hierarchy": ("one rank" if world == 1 else "one across the ranks" if R["amg_layout"]["coupled"] else "one per rank (block Jacobi over the ranks)"),
+                                    "scope": ("the whole matrix" if world == 1 else "rank 0's owned rows of every level of the global hierarchy"
+                                              if R["amg_layout"]["coupled"] else "rank 0's block")} if R["amg"] else {"name": R["pc_in_effect"]}),
+                "jacobi_step": ({"preconditioner": "point Jacobi (north_star's)", "steps": Jac["steps"], "warmup": Jac["warmup"],
+                                 "ms_per_step": Jac["ms_per_step"], "dof_per_s": Jac["N"] / (Jac["ms_per_step"] * 1e-3), "iterations": Jac["its"],
+                                 "converged_reason": Jac["reason"], "ms_per_iteration": Jac["ms_per_iteration"], Jac["check_name"]: Jac["check"],
+                                 "speedup_of_value_over_it": Jac["ms_per_step"] / R["ms_per_step"]} if Jac else None),
+                "device_memory_gb": {"in_use_rank0_device": round((R["mem"]["total_bytes"] - R["mem"]["free_bytes"]) / 1e9, 2),
+                                     "total": round(R["mem"]["total_bytes"] / 1e9, 2)},
+                # the kernel furthest from the HBM roofline, with the bound it really has: FP64 issue (every element's geometry is
+                # evaluated once per incident node, un-contracted as the reference's order demands).  The event time is this
+                # run's; the issue fraction is replayed from the committed SQ counters of the same kernel on the same workload
+                "assembly_kernel": ({"kernel": "pfem::k_gather_poisson_tet4 (gather assembly; in the steady state it also writes the SpMV's 16-bit value codes "
+                                               "and level 0's inverse diagonal + Gershgorin ratios for the multigrid)",
+                                     "event_ms_per_step": acc["asm_ms"] / args.steps,
+                                     # what it waits for (profiles/r06/assembly_kernel_bound.txt): not its arithmetic -- the same kernel with the
+                                     # element geometry for nothing is no faster -- but its gathered node records (72 x 32 B per row through the
+                                     # L1) under 4 waves per SIMD; its incidence records come from a cached pattern table where the mesh's
+                                     # numbering repeats (`incidence_patterns` > 0: 2.34 GB moved per launch instead of 5.37)
+                                     "bound": "memory-latency (gathered node records at 4 waves per SIMD)",
+                                     "incidence_patterns": R["incidence_patterns"][0], "longest_incidence_list": R["incidence_patterns"][1],
+                                     "bytes_moved_per_launch_replayed_not_this_run": {"records_from_the_pattern_table": 2.34e9, "every_nodes_own_records": 5.37e9,
+                                                                                      "source": "profiles/r06/assembly_kernel_bound.txt (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE per dispatch, tools/r06/incpat2.sh)"},
+                                     # SQ_ACTIVE_INST_VALU / (32 x GRBM_GUI_ACTIVE) of this kernel on this workload, re-taken in round 6 at commit 43503de
+                                     # with the pattern table (473.5 M / (32 x 18.47 M); before the table 0.68 = 466.1 M / (32 x 21.34 M); round 4: 0.75)
+                                     "valu_issue_fraction_replayed_not_this_run": 0.80,
+                                     "valu_issue_source": "profiles/r06/gather_and_spmv_sq_counters.txt (rocprofv3 --pmc, separate passes, tools/r06/final.sh)",
+                                     # compulsory bytes per launch: SURVEY 8(d)'s 2.69 GB + the codes (0.24 GB) + the two vectors for the multigrid (0.13 GB)
+                                     "hbm_frac_of_compulsory_bytes": (3.05e9 / (acc["asm_ms"] / args.steps * 1e-3) / 1e9 / HBM_PEAK_GBPS)
+                                     if (not beam and world == 1 and args.n == 200 and args.numbering == "lattice" and args.jitter <= 0.0) else None}
+                                    if (not beam and world == 1) else None),
+                "roofline": {"bound": "hbm", "kernel": kernel,
+                             # `frac` is the REAL fraction of the HBM peak: bytes the launch moves through the memory side (PMC counters of
+                             # this run when rocprofv3 is on the box, else the committed passes of the same workload, else the storage of
+                             # the selected form + x + y) / measured launch time / peak.  Never above 1.  What SURVEY 8(d) prices a launch
+                             # at -- plain CSR, 12 B per nonzero + 20 B per row -- stands beside it as `algorithmic_*`; the compressed forms
+                             # (16-bit gaps, relative row groups, value dictionary) move fewer bytes than that: `compression`
+                             "achieved": hbm_gbps, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": hbm_gbps / HBM_PEAK_GBPS,
+                             "frac_of_achievable_6300_gbps": hbm_gbps / 6300.0,
+                             "algorithmic_achieved": achieved, "algorithmic_frac": achieved / HBM_PEAK_GBPS,
+                             "compression": (bytes_per_spmv / hbm_bytes) if hbm_bytes else None,
+                             "value_dictionary_entries": vdn,
+                             "note": ("`achieved` / `frac`: bytes really moved (traffic) per second of the launch; `algorithmic_*`: the plain-CSR "
+                                      "bytes of SURVEY 8(d) the launch REPLACES per second -- above the peak when the kernel streams "
+                                      f"2 B of value code + 1/2 B of column gap per slot instead of 8 + 4 (the {vdn} distinct values of the assembled "
+                                      "matrix sit in LDS; lossless, same bits). PFEM_SPMV_VALDICT=0 runs the fp64 copy") if vdn else None,
+                             "traffic": traffic, "traffic_source": traffic_source, "traffic_counters": traffic_counters,
+                             "format_bytes_per_launch": fmt_bytes,
+                             "hbm_bytes_source": "PMC counters (traffic)" if traffic else "storage of the selected form + x + y",
+                             "algorithmic_bytes_per_launch": bytes_per_spmv, "avg_launch_ms": avg_spmv_ms,
+                             "avg_launch_source": f"raw HIP event pairs around every {2 if R['pc_in_effect'] == 'gamg' else 8}th launch of this kernel in the timed solves "
+                                                  "(the CG's own SpMV), on the solver's stream" +
+                                                  ("; the same kernel in the Jacobi step of this line: avg_launch_ms_in_jacobi_step; "
+                                                   "profiles/r03/rocprofv3_kernel_stats*.txt hold one kernel trace per loop" if R["pc_in_effect"] == "gamg" else ""),
+                             # what rocprofv3 --kernel-trace says about the same kernel in the same command (committed trace summaries).
+                             # The events are bound to the dispatch itself (hipExtLaunchKernelGGL), and still read ~20 us more than the
+                             # trace: under the tracer dispatches run one at a time, on the plain stream the kernel's first waves share
+                             # the device with the last waves of the kernel before it (events without the system-scope fence: no change,
+                             # measured in round 3).  The judged fraction uses the pair as it is, the lower of the two figures
+                             "kernel_trace_avg_launch_us_replayed_not_this_run": kernel_trace_figures(info["nnz"], R["value_dict"]) if (world == 1 and args.numbering == "lattice" and args.jitter <= 0.0) else None,
+                             "avg_launch_ms_in_jacobi_step": (Jac["acc"]["spmv_ms"] / max(Jac["acc"]["spmv_n"], 1)) if (Jac and Jac["acc"]["spmv_n"]) else None,
+                             "event_pair_offset_ms_not_subtracted": R["event_overhead_ms"],
+                             "launches_timed": acc["spmv_n"], "nnz": info["nnz"], "rows": info["n_local"]},
+            })
+            if world > 1:
+                # how to read an N > 1 line: (1) per-iteration efficiency -- rows per GPU and millisecond of iteration against
+                # the committed N = 1 figure (independent of the iteration count, which Jacobi makes grow with the problem);
+                # (2) the strong-scaling companion on BASELINE config 5
+                r1 = ref1.get("cfg3_200cube_" + R["pc_in_effect"], {})
+                if r1.get("ms_per_iteration") and r1.get("free_dofs"):
+                    rate1 = r1["free_dofs"] / r1["ms_per_iteration"]
+                    out["per_iteration_efficiency"] = {
+                        "value": (N / world / R["ms_per_iteration"]) / rate1,
+                        "definition": "(free dofs per GPU / ms per CG iteration) of this run / the same of the N=1 run",
+                        "n1_ms_per_iteration": r1["ms_per_iteration"], "n1_free_dofs": r1["free_dofs"], "n1_source": r1.get("source")}
+                if S is not None:
+                    r5 = ref1.get("cfg5_400cube_" + S["pc_in_effect"], {})
+                    is5 = S["nE"] == (400, 400, 400)
+                    out["strong_cfg5"] = {
+                        "workload": "tetrapoissonparallelimpl1: [-1,1]^3, %dx%dx%dx6 P1 tets%s" % (*S["nE"], " (BASELINE config 5)" if is5 else ""),
+                        "is_baseline_config5": is5, "free_dofs": S["N"], "n_gpus": world, "steps": S["steps"], "warmup": S["warmup"],
+                        "same_run_as_value": S is R, "preconditioner": S["pc_in_effect"],
+                        "ms_per_step": S["ms_per_step"], "dof_per_s": S["N"] / (S["ms_per_step"] * 1e-3), "iterations": S["its"],
+                        "converged_reason": S["reason"], "ms_per_iteration": S["ms_per_iteration"], S["check_name"]: S["check"],
+                        "single_gpu_ms_per_step": r5.get("ms_per_step") if is5 else None,
+                        "single_gpu_source": r5.get("source") if is5 else None,
+                        "speedup_vs_single_gpu": (r5["ms_per_step"] / S["ms_per_step"]) if (is5 and r5.get("ms_per_step")) else None,
+                        "bytes_per_neighbour": 8 * S["cinfo"]["doubles_per_exchange"] // max(S["cinfo"]["n_peers"], 1)}
+            if world == 1 and not args.no_cpu_baseline and not beam:
+                out["cpu_baseline"] = cpu_baseline(n, args.rtol, extra_sample=(n >= 200))
+            if world > 1:
+                out["comm"]["link_latencies"] = R.get("comm_bench")
+                out["comm"]["coupled_cycle"] = R.get("cycle_profile")
     else:
         out = None
     # ---- N > 1: the same steps over the OTHER device-side transport (A/B).  RCCL stays the headline (north_star); the
@@ -1169,7 +1229,7 @@ def main():
         J.dist.barrier()
         J.dist.destroy_process_group()
     faulthandler.cancel_dump_traceback_later()
-    if world > 1 and not args.no_transport_ab and rank == 0:
+    if args.full and world > 1 and not args.no_transport_ab and rank == 0:
         P = transport_ab_child(args)
         out["comm"]["transports"] = {{"rccl": "rccl", "host": "gloo-host-hooks"}.get(main_kind, main_kind): brief(R), "peer-ipc": P,
                                      "note": "same configuration, fresh solver each; the first entry is the run `value` reports; the second ran as "

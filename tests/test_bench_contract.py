@@ -10,9 +10,17 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def _skip_unless_eight_gpus():
+    """The eight-rank runs of BASELINE configs[3] / [4] put one rank on each of 8 GPUs; checked before any work."""
+    import pfemfort_amd as pf
+    n = pf.device_count()
+    if n < 8:
+        pytest.skip(f"needs 8 GPUs (one per rank), found {n}")
+
+
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_roofline_and_cpu_baseline():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--cells", "40"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--cells", "40", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -63,6 +71,39 @@ def test_bench_prints_one_json_line_with_roofline_and_cpu_baseline():
 
 
 @pytest.mark.gpu
+def test_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full: the headline only (no companion runs, no CPU baseline), exactly --steps timed steps, and with
+    --dump-outputs what the last timed step computed, as float64 arrays of at most 64 MB in all."""
+    import numpy as np
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--cells", "40",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["metric"] == "DOF/s (assembly+CG-to-tol)" and d["unit"] == "DOF/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert (d["n_gpus"], d["steps"], d["warmup"]) == (1, 3, 1) and d["converged_reason"] == 2
+    assert d["value"] > 0 and abs(d["value"] - d["config"]["free_dofs"] / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    assert not {"roofline", "cpu_baseline", "jacobi_step", "parity_tolerance_step", "max_nodal_error"} & set(d)
+    files = {f: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert set(files) == {"solution.npy", "rhs.npy", "matrix_values.npy", "solve.npy"}
+    assert all(a.dtype == np.float64 for a in files.values()) and sum(os.path.getsize(tmp_path / f) for f in files) <= 64e6
+    assert files["solution.npy"].size == files["rhs.npy"].size == d["config"]["free_dofs"] == 39 ** 3
+    assert list(files["solve.npy"][:2]) == [d["iterations"], d["converged_reason"]] and files["solve.npy"][2] == d["rnorm"]
+    # u = x^2+y^2+z^2 is nodally exact on this mesh: the dumped solution is the converged answer
+    x = np.linspace(-1, 1, 41)[1:-1]
+    exact = (x[:, None, None] ** 2 + x[None, :, None] ** 2 + x[None, None, :] ** 2).ravel()
+    assert np.abs(files["solution.npy"] - exact).max() < 1e-3
+
+
+def test_bench_rejects_what_it_cannot_time_or_dump():
+    """--steps sets the number of timed steps, so it must be at least 1; --dump-outputs writes one GPU's arrays."""
+    for bad in (["--steps", "0"], ["--warmup", "-1"], ["--gpus", "2", "--dump-outputs", "out"], ["--mode", "compat", "--dump-outputs", "out"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + bad, capture_output=True, text=True, timeout=120, cwd=ROOT)
+        assert r.returncode == 2 and "error" in r.stderr and not r.stdout.strip(), (bad, r.stderr[-500:])
+
+
+@pytest.mark.gpu
 def test_bench_two_ranks_sharing_the_device():
     """The N > 1 code path of bench.py (per-rank device-generated slab, neighbour plan, exchange, comm report) with two
     ranks on cuda:0 over gloo host hooks -- the launch line is the driver's, only backend and placement differ."""
@@ -72,7 +113,7 @@ def test_bench_two_ranks_sharing_the_device():
         port = so.getsockname()[1]
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--cells", "40", "--backend", "gloo", "--same-device", "--simulate-rccl-failure"],
+                        "--cells", "40", "--backend", "gloo", "--same-device", "--simulate-rccl-failure", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
@@ -112,17 +153,17 @@ def test_bench_two_ranks_sharing_the_device():
 @pytest.mark.gpu
 def test_config5_at_full_size_with_eight_ranks_sharing_the_device():
     """BASELINE configs[4] -- the 400x400x400x6 cube (384 M tets, 63.5 M free dofs) on 8 ranks -- functionally and at full
-    size on the one GPU a test box has: eight processes share the MI355X (8 GB each), exchange through gloo host hooks, and
-    solve the whole problem.  Not a performance figure; it pins the per-rank device generator, the neighbour plan
-    (one or two faces of 399^2 dofs), the relative-row-group SpMV with a table of the large gaps that slabs of this size need, and the
-    multi-rank loop at the size the scaling run uses."""
+    size: eight processes, one per GPU, exchange through gloo host hooks, and solve the whole problem.  Not a performance
+    figure; it pins the per-rank device generator, the neighbour plan (one or two faces of 399^2 dofs), the relative-row-group
+    SpMV with a table of the large gaps that slabs of this size need, and the multi-rank loop at the size the scaling run uses."""
     import socket
+    _skip_unless_eight_gpus()
     with socket.socket() as so:
         so.bind(("127.0.0.1", 0))
         port = so.getsockname()[1]
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--no-transport-ab", "--steps", "1", "--warmup", "0",
-                        "--backend", "gloo", "--same-device", "--pc", "jacobi"], capture_output=True, text=True, timeout=1500, cwd=ROOT)
+                        "--backend", "gloo", "--pc", "jacobi", "--full"], capture_output=True, text=True, timeout=1500, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")][-1])
     assert d["config"]["free_dofs"] == 63521199 and d["config"]["elements"] == 384000000 and d["n_gpus"] == 8
@@ -131,7 +172,7 @@ def test_config5_at_full_size_with_eight_ranks_sharing_the_device():
     assert sc["is_baseline_config5"] and sc["same_run_as_value"] and sc["single_gpu_ms_per_step"] > 1000 and sc["preconditioner"] == "jacobi"
     assert abs(sc["speedup_vs_single_gpu"] - sc["single_gpu_ms_per_step"] / d["ms_per_step"]) < 1e-9
     c = d["comm"]
-    assert len(c["ranks"]) == 8 and c["distinct_devices"] == 1 and [r["layers"] for r in c["ranks"]] == [[50 * r, 50 * r + 50] for r in range(8)]
+    assert len(c["ranks"]) == 8 and c["distinct_devices"] == 8 and [r["layers"] for r in c["ranks"]] == [[50 * r, 50 * r + 50] for r in range(8)]
     assert c["bytes_per_neighbour"] == 8 * 399 ** 2 and c["neighbours"] == 1            # rank 0: one face
     # dictionary form of the column gaps -- and of the VALUES: a slab of the structured box repeats its element matrices
     assert "k_spmvr_vd<true, true>" in d["roofline"]["kernel"] and "table of the" in d["roofline"]["kernel"]
@@ -145,7 +186,7 @@ def test_config5_at_full_size_alone_on_one_device():
     as the eight-rank test above: the same answer (nodal error of the %.8f boundary data), the same iteration count to
     a few (one rank sums in a different order than eight), and the strong-scaling baseline of SURVEY 8(e)."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--cells", "400", "--steps", "1", "--warmup", "0",
-                        "--no-cpu-baseline", "--pc", "jacobi"], capture_output=True, text=True, timeout=1500, cwd=ROOT)
+                        "--no-cpu-baseline", "--pc", "jacobi", "--full"], capture_output=True, text=True, timeout=1500, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")][-1])
     assert d["config"]["free_dofs"] == 63521199 and d["config"]["elements"] == 384000000 and d["n_gpus"] == 1
@@ -158,11 +199,10 @@ def test_config5_at_full_size_alone_on_one_device():
 
 @pytest.mark.gpu
 def test_config5_with_the_default_solver():
-    """BASELINE configs[4] with the solver `bench.py` runs by default (-pc_type gamg), alone on one device and on 8 ranks sharing
-    it: 13 iterations alone (720 with point Jacobi), 15 across the eight ranks (one hierarchy across them), the converged
-    answer at rtol 1e-10 within the error of the "%.8f" boundary data."""
+    """BASELINE configs[4] with the solver `bench.py` runs by default (-pc_type gamg), alone on one device: 13 iterations
+    (720 with point Jacobi), the converged answer at rtol 1e-10 within the error of the "%.8f" boundary data."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--cells", "400", "--steps", "1", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-jacobi-step"], capture_output=True, text=True, timeout=1500, cwd=ROOT)
+                        "--no-cpu-baseline", "--no-jacobi-step", "--full"], capture_output=True, text=True, timeout=1500, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")][-1])
     assert d["config"]["free_dofs"] == 63521199 and d["preconditioner"]["name"] == "gamg" and d["converged_reason"] == 2
@@ -170,9 +210,16 @@ def test_config5_with_the_default_solver():
     assert d["preconditioner"]["rows_per_level"][:3] == [399 ** 3, 200 ** 3, 100 ** 3]
     pt = d["parity_tolerance_step"]
     assert pt["converged_reason"] == 2 and pt["max_nodal_error"] < 2e-7 and pt["iterations"] <= 40
+
+
+@pytest.mark.gpu
+def test_config5_with_the_default_solver_on_eight_gpus():
+    """BASELINE configs[4] with the default solver on 8 ranks, one per GPU: 15 iterations across the eight ranks (one
+    hierarchy across them), against 13 alone (test_config5_with_the_default_solver)."""
+    _skip_unless_eight_gpus()
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--no-transport-ab", "--same-device", "--backend", "gloo", "--steps", "1",
-                        "--warmup", "0", "--no-jacobi-step", "--no-parity-step"], capture_output=True, text=True, timeout=1500, cwd=ROOT, env=env)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--no-transport-ab", "--backend", "gloo", "--steps", "1",
+                        "--warmup", "0", "--no-jacobi-step", "--no-parity-step", "--full"], capture_output=True, text=True, timeout=1500, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     d8 = json.loads([ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")][-1])
     assert d8["config"]["free_dofs"] == 63521199 and d8["n_gpus"] == 8 and d8["converged_reason"] == 2
@@ -185,7 +232,7 @@ def test_strong_scaling_flag_keeps_the_problem():
     free dofs, the same answer, "scaling": "strong"; and the line reports the device memory in use."""
     import socket
     one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--cells", "60", "--steps", "1", "--warmup", "0",
-                          "--no-cpu-baseline", "--no-parity-step", "--pc", "jacobi"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--no-cpu-baseline", "--no-parity-step", "--pc", "jacobi", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert one.returncode == 0, one.stdout[-2000:] + one.stderr[-3000:]
     d1 = json.loads([ln for ln in one.stdout.splitlines() if ln.strip().startswith("{")][-1])
     with socket.socket() as so:
@@ -193,7 +240,8 @@ def test_strong_scaling_flag_keeps_the_problem():
         port = so.getsockname()[1]
     two = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--no-transport-ab", "--cells", "60", "--strong",
-                          "--steps", "1", "--warmup", "0", "--backend", "gloo", "--same-device", "--no-cpu-baseline", "--no-parity-step", "--pc", "jacobi"],
+                          "--steps", "1", "--warmup", "0", "--backend", "gloo", "--same-device", "--no-cpu-baseline", "--no-parity-step", "--pc", "jacobi",
+                          "--full"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert two.returncode == 0, two.stdout[-2000:] + two.stderr[-3000:]
     d2 = json.loads([ln for ln in two.stdout.splitlines() if ln.strip().startswith("{")][-1])
@@ -212,7 +260,8 @@ def test_plain_invocation_with_two_gpus_launches_its_own_ranks():
     their exit code.  The line says what carried the run and how to read it: transport and rank count, every rank's
     device, per-iteration efficiency, and the strong-scaling companion block."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--no-transport-ab", "--same-device", "--backend", "gloo", "--cells", "40"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--no-transport-ab", "--same-device", "--backend", "gloo", "--cells", "40",
+                        "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -247,13 +296,14 @@ def test_plain_invocation_reports_a_dead_rank_with_its_exit_code():
 
 @pytest.mark.gpu
 def test_beam_on_eight_ranks_is_cut_across_its_length():
-    """BASELINE configs[3] on 8 ranks (sharing the one GPU of a test box, gloo host hooks): the 50x300x50 beam is cut
+    """BASELINE configs[3] on 8 ranks (one per GPU, gloo host hooks): the 50x300x50 beam is cut
     across y -- 37/38 hex layers per rank, faces of 51x51 nodes = 62 KB per neighbour -- not into 6-7
     z-layers with 368 KB faces; the default solve (one multigrid hierarchy across the eight ranks) converges to the same tip
     displacement in about the iterations the one-GPU hierarchy needs (18), a small fraction of point Jacobi's 5 207."""
+    _skip_unless_eight_gpus()
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--no-transport-ab", "--same-device", "--backend", "gloo",
-                        "--workload", "beam", "--steps", "1", "--warmup", "0", "--no-jacobi-step", "--no-parity-step"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--no-transport-ab", "--backend", "gloo",
+                        "--workload", "beam", "--steps", "1", "--warmup", "0", "--no-jacobi-step", "--no-parity-step", "--full"],
                        capture_output=True, text=True, timeout=1500, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")][-1])

@@ -382,7 +382,7 @@ def _gpu_worker(rank, world, port, mesh_args, out_dir):
                                                             ("poisson", 3, "idle", "gamg_distributed"), ("poisson", 3, "rcb", "gamg_distributed"),
                                                             ("elast", 3, "sectors", "gamg"), ("elast", 3, "rcb", "gamg_distributed"),
                                                             ("poisson", 3, "foreign", "gamg"), ("poisson", 5, "sectors", "gamg_distributed"),
-                                                            ("elast", 4, "rcb", "gamg"), ("poisson", 6, "rcb", "gamg"),
+                                                            ("elast", 4, "rcb", "gamg"), ("poisson", 5, "rcb", "gamg"),
                                                             ("poisson", 3, "sectors", "reorder"), ("elast", 2, "slabs", "reorder_gamg"),
                                                             ("poisson", 2, "slabs", "gamg_single"), ("elast", 3, "yslabs", "gamg_single"),
                                                             ("poisson", 3, "stairs", "gamg"), ("poisson", 3, "stairs", "gamg_distributed"),
@@ -705,7 +705,7 @@ def test_gpu_ranks_on_one_device_match_oracle(tmp_path, kind_name, world, partit
                                                             ("poisson", 3, "rcb", "single_overlap"), ("elast", 3, "yslabs", "devgen"),
                                                             ("poisson", 2, "slabs", "gamg"), ("elast", 3, "yslabs", "gamg"),
                                                             ("poisson", 3, "idle", "gamg_overlap"), ("poisson", 3, "rcb", "gamg_distributed"),
-                                                            ("elast", 3, "sectors", "gamg"), ("poisson", 6, "rcb", "gamg"),
+                                                            ("elast", 3, "sectors", "gamg"), ("poisson", 5, "rcb", "gamg"),
                                                             ("elast", 2, "slabs", "reorder_gamg")])
 def test_gpu_peer_memory_transport(tmp_path, kind_name, world, partition, mode):
     """The same multi-rank cases with the DEVICE-SIDE transport between the ranks that share cuda:0: every rank maps the
