@@ -93,7 +93,7 @@ int pfem_solver_incidence_patterns(pfem_solver *s, int *count, int *longest);
 /* how the aggregates of every level of the last gamg hierarchy were formed (kind[l], l < *n_levels; the last level: 0):
  * 1 bricks of the lattice in one step, 2 node bricks in one step (rigid-body transfer), 3 bricks split between their owners
  * (several ranks whose dofs do not fill boxes), 4 pairing passes along the axes of the lattice, 5 matching on the strength
- * graph, 6 roots + neighbours (an independent set of the strength graph).                                                 */
+ * graph.                                                                                                                  */
 int pfem_solver_amg_aggregation(pfem_solver *s, int max_levels, int *n_levels, int *kind);
 /* several ranks: neighbour exchanges and all-reduces ONE V-cycle of the last solve enqueued (next to the CG's own exchange
  * and two all-reduces per iteration); 0 / 0 on one rank                                                                */

@@ -219,15 +219,11 @@ int lattice_assign(pfem_solver *s, const std::vector<double> &h_uniq, const int 
 // Bricks are refused where the couplings inside them are weak (below a quarter of the row's strongest): a verdict about the LEVEL.
 // Cells stretched along an axis make every row's coupling along it weak; a few nodes moved off their sites (a lattice by
 // numbering, lattice_positions_by_numbering) make a few such rows, and the bricks stay.  Refused from this share of the rows on
-// (PFEM_AMG_BRICK_WEAK_PERCENT; 0 = round 5's rule, any row).
-inline double amg_brick_weak_percent()
-{
-    static const double p = [] { const char *e = std::getenv("PFEM_AMG_BRICK_WEAK_PERCENT"); return e ? std::atof(e) : 5.0; }();
-    return p;
-}
+// (kAmgBrickWeakPercent; round 5 refused them from any row).
+constexpr double kAmgBrickWeakPercent = 5.0;
 inline bool amg_too_many_weak(double weak, double rows)
 {
-    return weak > 0.0 && (amg_brick_weak_percent() <= 0.0 || weak * 100.0 > amg_brick_weak_percent() * rows);
+    return weak > 0.0 && weak * 100.0 > kAmgBrickWeakPercent * rows;
 }
 
 int lattice_positions_global(pfem_solver *s, AmgLevel &L0, bool *is_lattice, bool nodes = false, bool split = false)
@@ -552,12 +548,11 @@ int amg_match(pfem_solver *s, AmgWork &W, const AmgGraph &G, const int32_t *hint
     PFEM_HIP(hipMemsetAsync(match.p, 0xff, sizeof(int32_t) * n, s->stream));
     // small graphs are dense (every aggregate touches most others): many nodes propose to the same neighbour and few
     // proposals are mutual per round, so they get more rounds (they cost nothing)
-    const int rounds_env = [] { const char *e = std::getenv("PFEM_AMG_ROUNDS"); return e ? std::atoi(e) : 0; }();
-    const int rounds = n < 8192 ? 8 * kAmgMatchRounds : (rounds_env > 0 ? rounds_env : kAmgMatchRounds);
+    const int rounds = n < 8192 ? 8 * kAmgMatchRounds : kAmgMatchRounds;
     for (int r = 0; r < rounds; ++r) {
         hipLaunchKernelGGL(k_amg_match_pick, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, n, static_cast<const int64_t *>(G.ptr.p),
                            static_cast<const int32_t *>(G.col.p), static_cast<const double *>(G.w.p), static_cast<const double *>(G.diag.p),
-                           hint, std::getenv("PFEM_AMG_NO_STRENGTH") ? 1 : 0, static_cast<const int32_t *>(match.p), cand.p);
+                           hint, static_cast<const int32_t *>(match.p), cand.p);
         hipLaunchKernelGGL(k_amg_match_commit, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, n, static_cast<const int32_t *>(cand.p), match.p);
     }
     PFEM_TRY(check_kernel("k_amg_match"));
@@ -568,71 +563,6 @@ int amg_match(pfem_solver *s, AmgWork &W, const AmgGraph &G, const int32_t *hint
     hipLaunchKernelGGL(k_amg_agg_ids, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, n, static_cast<const int32_t *>(match.p),
                        static_cast<const int32_t *>(rank.p), agg_step.p);
     PFEM_TRY(check_kernel("k_amg_agg_ids"));
-    int32_t total = 0;
-    PFEM_HIP(hipMemcpyAsync(&total, rank.p + n, sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
-    PFEM_HIP(hipStreamSynchronize(s->stream));
-    *na = total;
-    return PFEM_OK;
-}
-
-// roots + neighbours (k_mis_*): agg_step[node] = aggregate, *na = their number; same outputs as amg_match
-int amg_mis(pfem_solver *s, AmgWork &W, const AmgGraph &G, const int32_t *hint, DevBuf<int32_t> &agg_step, int64_t *na)
-{
-    const int64_t n = G.n;
-    DevBuf<char> &temp = W.temp;
-    DevBuf<int32_t> &match = W.match, &cand = W.cand, &is_root = W.is_root, &rank = W.mrank, &state = W.step;
-    DevBuf<uint64_t> &prio = W.keys, &t1 = W.skeys, &t2 = W.ukeys;
-    DevBuf<double> &smax = W.sums;
-    DevBuf<int> d_left;
-    const size_t n1 = static_cast<size_t>(std::max<int64_t>(n, 1));
-    PFEM_TRY(match.reserve(n1));
-    PFEM_TRY(cand.reserve(n1));
-    PFEM_TRY(state.reserve(n1));
-    PFEM_TRY(is_root.reserve(n1 + 1));
-    PFEM_TRY(rank.reserve(n1 + 1));
-    PFEM_TRY(prio.reserve(n1));
-    PFEM_TRY(t1.reserve(n1));
-    PFEM_TRY(t2.reserve(n1));
-    PFEM_TRY(smax.reserve(n1));
-    PFEM_TRY(d_left.alloc(1));
-    const dim3 grid(grid_for(n)), block(kBlock);
-    const int64_t *gp = G.ptr.p;
-    const int32_t *gc = G.col.p;
-    const double *gw = G.w.p, *gd = G.diag.p;
-    if (n > 0) {
-        hipLaunchKernelGGL(k_mis_init, grid, block, 0, s->stream, n, gp, gc, gw, gd, hint, smax.p, reinterpret_cast<unsigned long long *>(prio.p), state.p, match.p);
-        int left = 1;
-        for (int round = 0; round < 64 && left > 0; round += 4) {
-            PFEM_HIP(hipMemsetAsync(d_left.p, 0, sizeof(int), s->stream));
-            for (int k = 0; k < 4; ++k) {           // four rounds between two looks at the count (a round without undecided nodes does nothing)
-                hipLaunchKernelGGL(k_mis_spread<true>, grid, block, 0, s->stream, n, gp, gc, gw, gd, static_cast<const double *>(smax.p), static_cast<const int32_t *>(state.p),
-                                   reinterpret_cast<const unsigned long long *>(prio.p), reinterpret_cast<unsigned long long *>(t1.p));
-                hipLaunchKernelGGL(k_mis_spread<false>, grid, block, 0, s->stream, n, gp, gc, gw, gd, static_cast<const double *>(smax.p), static_cast<const int32_t *>(state.p),
-                                   reinterpret_cast<const unsigned long long *>(t1.p), reinterpret_cast<unsigned long long *>(t2.p));
-                hipLaunchKernelGGL(k_mis_roots, grid, block, 0, s->stream, n, reinterpret_cast<const unsigned long long *>(prio.p),
-                                   reinterpret_cast<const unsigned long long *>(t2.p), state.p, match.p);
-                hipLaunchKernelGGL(k_mis_join_pick, grid, block, 0, s->stream, n, gp, gc, gw, gd, static_cast<const double *>(smax.p), static_cast<const int32_t *>(state.p), cand.p);
-                hipLaunchKernelGGL(k_mis_join_commit, grid, block, 0, s->stream, n, static_cast<const int32_t *>(cand.p), state.p, match.p);
-                hipLaunchKernelGGL(k_mis_wait, grid, block, 0, s->stream, n, gp, gc, gw, gd, static_cast<const double *>(smax.p), static_cast<const int32_t *>(state.p), cand.p);
-                if (k == 3) hipLaunchKernelGGL(k_mis_wait_commit, grid, block, 0, s->stream, n, static_cast<const int32_t *>(cand.p), state.p, d_left.p);
-                else hipLaunchKernelGGL(k_mis_wait_commit, grid, block, 0, s->stream, n, static_cast<const int32_t *>(cand.p), state.p, static_cast<int *>(nullptr));
-            }
-            PFEM_TRY(check_kernel("k_mis_*"));
-            PFEM_HIP(hipMemcpyAsync(&left, d_left.p, sizeof(int), hipMemcpyDeviceToHost, s->stream));
-            PFEM_HIP(hipStreamSynchronize(s->stream));
-        }
-        for (int sweep = 0; sweep < 2; ++sweep) {
-            hipLaunchKernelGGL(k_mis_adopt_pick, grid, block, 0, s->stream, n, gp, gc, gw, gd, static_cast<const int32_t *>(state.p), static_cast<const int32_t *>(match.p), cand.p);
-            hipLaunchKernelGGL(k_mis_join_commit, grid, block, 0, s->stream, n, static_cast<const int32_t *>(cand.p), state.p, match.p);
-        }
-        PFEM_TRY(check_kernel("k_mis_adopt"));
-    }
-    PFEM_HIP(hipMemsetAsync(is_root.p + n, 0, sizeof(int32_t), s->stream));
-    hipLaunchKernelGGL(k_amg_match_finish, grid, block, 0, s->stream, n, match.p, is_root.p);
-    PFEM_TRY(amg_exclusive_sum(s, temp, is_root.p, rank.p, n + 1));
-    PFEM_TRY(agg_step.reserve(n1));
-    hipLaunchKernelGGL(k_amg_agg_ids, grid, block, 0, s->stream, n, static_cast<const int32_t *>(match.p), static_cast<const int32_t *>(rank.p), agg_step.p);
-    PFEM_TRY(check_kernel("k_amg_agg_ids (roots)"));
     int32_t total = 0;
     PFEM_HIP(hipMemcpyAsync(&total, rank.p + n, sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
     PFEM_HIP(hipStreamSynchronize(s->stream));
@@ -661,7 +591,7 @@ int amg_match_lattice(pfem_solver *s, AmgWork &W, const AmgGraph &G, const int32
     // The node a line of odd length leaves over: alone (a thin cell at the end of the line; every level stays aligned, and
     // that is what converges best: 200^3 12 iterations, with the node joined to its neighbour's pair 15) or in a brick of 3
     // (smaller coarse levels; on the 3-dof beam the cheaper cycle outweighs the iterations: 155 against 166 ms).
-    if ([&] { const char *e = std::getenv("PFEM_AMG_LATTICE_ABSORB"); return e ? std::atoi(e) != 0 : absorb; }()) {
+    if (absorb) {
         hipLaunchKernelGGL(k_amg_lat_absorb, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, n, gptr, gcol, gw, gd, pos, shift,
                            static_cast<const int32_t *>(match.p), cand.p);
         hipLaunchKernelGGL(k_amg_lat_join, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, n, static_cast<const int32_t *>(cand.p), match.p);
@@ -747,8 +677,7 @@ inline void amg_galerkin(pfem_solver *s, const AmgLevel &L, AmgLevel &C, const S
     if (L.code_of.p && !amg_galerkin_by_entry()) {
         if (C.n_loc < 1) return;                    // (a rank that holds nothing of this level)
         LatGalExtra X{nullptr, nullptr, nullptr, nullptr, nullptr};
-        static const bool fuse_on = [] { const char *e = std::getenv("PFEM_AMG_GALERKIN_EXTRAS"); return e ? std::atoi(e) != 0 : true; }();
-        if (extras && fuse_on && C.dinv.p && C.t.p && C.n_loc == C.n) {
+        if (extras && C.dinv.p && C.t.p && C.n_loc == C.n) {
             X.dinv_out = C.dinv.p;
             X.ratio_out = C.t.p;
             C.bound_fresh = true;
@@ -1529,7 +1458,7 @@ int amg_rbm_level(pfem_solver *s, Amg &M, AmgWork &W, AmgLevel &L, DevBuf<int32_
 // first step after a pattern build counts: at config 3 it took 91 ms, 72 of them this phase -- three passes of pairing with
 // a sorted aggregate graph each (24 ms on level 0) and the 64-bit sort of (coarse row, coarse col, fine slot) (10 ms).  When
 // every pair would be accepted the passes end in the bricks position >> shift anyway.  *done = false: the level is left to
-// the passes (weak couplings along an axis, couplings beyond the neighbouring bricks, PFEM_AMG_PASSES experiments).
+// the passes (weak couplings along an axis, couplings beyond the neighbouring bricks).
 template <class Phase>
 int amg_bricks_level(pfem_solver *s, Amg &M, AmgWork &W, AmgLevel &L, const SellDev &A, Phase &phase, int l, bool *done, bool coupled, bool overlap,
                      double *n_global)
@@ -1579,7 +1508,7 @@ int amg_bricks_level(pfem_solver *s, Amg &M, AmgWork &W, AmgLevel &L, const Sell
         PFEM_HIP(hipMemcpyAsync(why, d_fail.p, sizeof why, hipMemcpyDeviceToHost, s->stream));
         PFEM_HIP(hipMemcpyAsync(&na32, rank.p + nbricks, sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
         PFEM_HIP(hipStreamSynchronize(s->stream));
-        // (weak couplings inside the bricks: a verdict about the level -- refused from amg_brick_weak_percent() of the rows on,
+        // (weak couplings inside the bricks: a verdict about the level -- refused from kAmgBrickWeakPercent of the rows on,
         // amg_node_bricks; a coupling beyond the neighbouring bricks: one is enough, the 27 offset codes cannot hold it)
         fail = why[2] > 0 || amg_too_many_weak(why[1], n);
         if (why[0] && std::getenv("PFEM_AMG_VERBOSE"))
@@ -1902,8 +1831,8 @@ int amg_node_bricks(pfem_solver *s, AmgLevel &L, const AmgGraph &G, NodeBricks &
     // device: 18 / 22 / 22, then 27 / 41 / 54 with 5 / 6 / 8), while level 1 -- whose 6x6 blocks of fp64 made it the dearest level
     // of the cycle once the matrix itself streamed dictionary codes (54 M entries against 103 M two-byte codes) -- shrinks 3.3 /
     // 7.7 times: config 4 24.8 -> 20.9 -> 19.2 ms per step.  Scalar problems keep 2x2x2 (piecewise-constant coarse space: 10 -> 12
-    // iterations at 60^3, and level 1 is cheap there).  PFEM_AMG_NODE_BRICK0 = the largest brick edge allowed (2: round 4's bricks).
-    const int first_max = [] { const char *e = std::getenv("PFEM_AMG_NODE_BRICK0"); const int v = e ? std::atoi(e) : 4; return v >= 2 && v <= 8 ? v : 4; }();
+    // iterations at 60^3, and level 1 is cheap there).  first_max = the largest brick edge allowed (2: round 4's bricks).
+    constexpr int first_max = 4;
     std::vector<int32_t> table(3 * 1024, 0);
     const bool have = nn > 0;                           // (a rank that owns nothing of this level takes part in the verdict only)
     int64_t na = 1;
@@ -2084,9 +2013,8 @@ int amg_build_levels(pfem_solver *s, Amg &M, AmgWork &W, bool coupled, bool over
         const SellDev A = amg_sell(s, L);
         const int64_t R = coupled ? L.n_loc : L.n;           // rows (and columns) that take part in the Galerkin product
         const int64_t nn = L.n_nodes;
-        // (several ranks: L.lat_global is the same on every rank -- set from all-reduced verdicts only -- and so is the environment)
-        if (L.lattice && L.bs == 1 && (coupled ? L.lat_global : L.n_loc == L.n) && L.hint.p && !std::getenv("PFEM_AMG_PASSES") && !std::getenv("PFEM_AMG_PASSES0") &&
-            [] { const char *e = std::getenv("PFEM_AMG_BRICKS"); return e ? std::atoi(e) != 0 : true; }()) {
+        // (several ranks: L.lat_global is the same on every rank -- set from all-reduced verdicts only)
+        if (L.lattice && L.bs == 1 && (coupled ? L.lat_global : L.n_loc == L.n) && L.hint.p) {
             bool done = false;
             const int rc = amg_bricks_level(s, M, W, L, A, phase, l, &done, coupled, overlap, &n_global);
             if (rc == kAmgLastLevel) break;
@@ -2107,8 +2035,7 @@ int amg_build_levels(pfem_solver *s, Amg &M, AmgWork &W, bool coupled, bool over
         DevBuf<int32_t> sb_agg, sb_pos;
         int64_t sb_na = 0;
         int sb_hi[3] = {0, 0, 0}, sb_axis = 0, sb_shift[3] = {0, 0, 0};
-        if (coupled && L.lat_split && L.lattice && L.bs == 1 && (L.hint.p || L.n == 0) && !std::getenv("PFEM_AMG_PASSES") && !std::getenv("PFEM_AMG_PASSES0") &&
-            [] { const char *e = std::getenv("PFEM_AMG_BRICKS"); return e ? std::atoi(e) != 0 : true; }()) {
+        if (coupled && L.lat_split && L.lattice && L.bs == 1 && (L.hint.p || L.n == 0)) {
             PFEM_TRY(amg_split_bricks(s, W, L, A, &split_bricks, sb_agg, sb_pos, &sb_na, sb_hi, &sb_axis, sb_shift));
             if (split_bricks) phase(l, "split bricks: check + aggregates");
         }
@@ -2261,23 +2188,17 @@ int amg_build_levels(pfem_solver *s, Amg &M, AmgWork &W, bool coupled, bool over
         const int32_t *hint = L.hint.p;                 // null: indices
         int lat_hi[3] = {L.lat_hi[0], L.lat_hi[1], L.lat_hi[2]}, lat_axis = L.lat_axis;
         bool on_lattice = L.lattice;
-        // (PFEM_AMG_PASSES / PFEM_AMG_PASSES0: experiments with 2^passes nodes per aggregate, on all levels / on level 0 only)
-        const int n_passes = [&] {
-            const char *e0 = L.fine ? std::getenv("PFEM_AMG_PASSES0") : nullptr, *e = std::getenv("PFEM_AMG_PASSES");
-            const int v = e0 ? std::atoi(e0) : (e ? std::atoi(e) : 0);
-            // level 0 of a displacement problem on one rank: five passes, aggregates of up to 32 nodes -- the rigid-body coarse space
-            // carries them (see amg_node_bricks for the lattice's case), and level 1 with its 6x6 blocks is the dearest of the cycle:
-            // the beam with its nodes moved off the lattice 67 iterations / 116 ms with three passes, 52 / 74 with four, 61 / 72 with
-            // five, 59 / 71 with six (tools/r05/jitter_passes.sh)
-            return v >= 1 && v <= 6 ? v : ((L.fine && rbm && !coupled) ? 5 : kAmgPasses);
-        }();
+        // level 0 of a displacement problem on one rank: five passes, aggregates of up to 32 nodes -- the rigid-body coarse space
+        // carries them (see amg_node_bricks for the lattice's case), and level 1 with its 6x6 blocks is the dearest of the cycle:
+        // the beam with its nodes moved off the lattice 67 iterations / 116 ms with three passes, 52 / 74 with four, 61 / 72 with
+        // five, 59 / 71 with six (profiles/r05/beam_level0_aggregate_sizes.txt)
+        const int n_passes = (L.fine && rbm && !coupled) ? 5 : kAmgPasses;
         // levels with the rigid-body transfer on a full lattice (one rank): the bricks the passes would end in, in one step
         NodeBricks NB;
         bool node_bricks = false;
         // (several ranks, round 6: the same across the ranks when the positions are global and every rank's nodes fill a box --
-        // L.lat_nodes_global is set from all-reduced verdicts only, the same on every rank, and so is the environment)
-        if (rbm && (coupled ? L.lat_nodes_global : nn_loc == nn) && L.lattice && L.lat_full && (L.hint.p || nn == 0) && !std::getenv("PFEM_AMG_PASSES") &&
-            !std::getenv("PFEM_AMG_PASSES0") && [] { const char *e = std::getenv("PFEM_AMG_BRICKS"); return e ? std::atoi(e) != 0 : true; }()) {
+        // L.lat_nodes_global is set from all-reduced verdicts only, the same on every rank)
+        if (rbm && (coupled ? L.lat_nodes_global : nn_loc == nn) && L.lattice && L.lat_full && (L.hint.p || nn == 0)) {
             PFEM_TRY(amg_node_bricks(s, L, G, NB, &node_bricks, coupled));
             if (node_bricks) {
                 node_agg.swap(NB.node_agg);
@@ -2295,30 +2216,7 @@ int amg_build_levels(pfem_solver *s, Amg &M, AmgWork &W, bool coupled, bool over
             for (int d = 0; d < 3; ++d) lat_hi[d] = sb_hi[d];
             lat_axis = sb_axis;
         }
-        // Levels WITHOUT a lattice (a file mesh, nodes moved off their lattice) -- lab option, off by default: roots + neighbours
-        // (amg_mis) instead of the passes of pairwise matching: compact aggregates of a root and everybody around it, formed in a few
-        // sweeps over the graph without a sort (symbolic phase of the moved beam 24.8 -> 20.7 ms).  MEASURED AND NOT TAKEN (round 6,
-        // profiles/r06/roots_aggregation_on_moved_meshes.txt): the beam with moved nodes 61 -> 78 iterations (69 -> 95 ms) although the
-        // aggregates are no larger (21.8 nodes against 25.9) -- in a Kuhn triangulation a node's 14 neighbours stretch along the
-        // cells' common diagonal, and the star is more lopsided than what matching leaves; 200^3 with moved nodes 18 -> 22 iterations.
-        // PFEM_AMG_ROOTS=1: levels with the rigid-body transfer; =2: scalar levels too.
-        bool roots = false;
-        const int roots_env = [] { const char *e = std::getenv("PFEM_AMG_ROOTS"); return e ? std::atoi(e) : 0; }();
-        if (!node_bricks && !split_bricks && !(L.lattice && on_lattice) && nn_loc >= 0 && ((rbm && roots_env >= 1) || roots_env >= 2) &&
-            !std::getenv("PFEM_AMG_PASSES") && !std::getenv("PFEM_AMG_PASSES0")) {
-            DevBuf<int32_t> &nh = hint_a;
-            PFEM_TRY(amg_mis(s, W, *Gp, hint, node_agg, &na));
-            if (hint) {          // the aggregates' places along the curve: the lowest of their members'
-                PFEM_TRY(nh.alloc(static_cast<size_t>(std::max<int64_t>(na, 1))));
-                PFEM_HIP(hipMemsetAsync(nh.p, 0x7f, sizeof(int32_t) * static_cast<size_t>(std::max<int64_t>(na, 1)), s->stream));
-                hipLaunchKernelGGL(k_amg_hint_coarsen, dim3(grid_for(Gp->n)), dim3(kBlock), 0, s->stream, Gp->n, hint, static_cast<const int32_t *>(node_agg.p), nh.p);
-                PFEM_TRY(check_kernel("k_amg_hint_coarsen (roots)"));
-                hint = nh.p;
-            }
-            roots = true;
-            phase(l, "roots + neighbours");
-        }
-        for (int pass = 0; pass < ((node_bricks || split_bricks || roots) ? 0 : n_passes); ++pass) {
+        for (int pass = 0; pass < ((node_bricks || split_bricks) ? 0 : n_passes); ++pass) {
             DevBuf<int32_t> &step = W.step;
             int64_t na_new = 0;
             bool lattice_pass = L.lattice && on_lattice;
@@ -2388,7 +2286,7 @@ int amg_build_levels(pfem_solver *s, Amg &M, AmgWork &W, bool coupled, bool over
             if (last) break;
         }
 #undef G
-        L.agg_kind = node_bricks ? 2 : (split_bricks ? 3 : (roots ? 6 : (on_lattice ? 4 : 5)));
+        L.agg_kind = node_bricks ? 2 : (split_bricks ? 3 : (on_lattice ? 4 : 5));
         phase(l, "3 passes of matching");
         if (rbm) {
             const int rc = amg_rbm_level(s, M, W, L, node_agg, na, hint, on_lattice, lat_hi, lat_axis, phase, l, coupled, overlap, &n_global,
@@ -2597,11 +2495,10 @@ int amg_finish_levels(pfem_solver *s, Amg &M, bool coupled)
     if (coupled) PFEM_TRY(M.lam_all.alloc(static_cast<size_t>(std::max<int64_t>(256, 2 * static_cast<int64_t>(M.lev.size()) * s->nranks))));
     M.fused = !coupled && [] { const char *e = std::getenv("PFEM_AMG_FUSED"); return e ? std::atoi(e) != 0 : true; }();
     M.tail_from = -1;
-    const int64_t tail_rows = [] { const char *e = std::getenv("PFEM_AMG_TAIL_ROWS"); return e ? std::atoll(e) : static_cast<long long>(kAmgTailRows); }();
     for (size_t l = 1; l < M.lev.size() && !coupled; ++l)
         // (and few nonzeros: one workgroup is latency-bound, and a level of 6-dof nodes has 100+ entries per row -- the beam's
         // 918-row level inside the tail cost 186 us per cycle, three fused launches outside it cost less: 46.6 -> 44.0 ms per step)
-        if (M.lev[l]->n <= tail_rows && M.lev[l]->nnz <= kAmgTailNnz && M.lev.size() - l <= static_cast<size_t>(kAmgTailLevels)) { M.tail_from = static_cast<int>(l); break; }
+        if (M.lev[l]->n <= kAmgTailRows && M.lev[l]->nnz <= kAmgTailNnz && M.lev.size() - l <= static_cast<size_t>(kAmgTailLevels)) { M.tail_from = static_cast<int>(l); break; }
     M.w_to = M.tail_from > 0 ? M.tail_from : static_cast<int>(M.lev.size()) - 2;
     // the tail kernel works out of LDS (k_amg_tail): allow it what its levels' vectors + the first level's matrix take
     M.tail_lds_allowed = 0;
@@ -2699,8 +2596,7 @@ int amg_symbolic(pfem_solver *s, bool multi, bool overlap)
         // consecutive --: candidates for the rigid-body-mode coarse space; nodes = runs of ndof dofs, coordinates from the mesh
         // (one rank for now: a hierarchy across the ranks keeps the translations)
         // (several ranks: for the hierarchy across the ranks, ghost nodes included; the ranks decide together)
-        const bool rbm_wanted = [] { const char *e = std::getenv("PFEM_AMG_RBM"); return e ? std::atoi(e) != 0 : true; }() && (!multi || coupled);
-        if (rbm_wanted) {
+        if (!multi || coupled) {
             const int nd = s->mesh.ndof;
             bool cand = s->have_mesh && nd == s->mesh.ndim && nd >= 2 && s->n_owned % nd == 0 && s->n_loc % nd == 0 && (multi || s->n_owned >= 2 * nd);
             const int64_t nn0 = cand ? s->n_loc / nd : 0;
@@ -2743,8 +2639,7 @@ int amg_symbolic(pfem_solver *s, bool multi, bool overlap)
         // Scalar problem, one hierarchy across the ranks: GLOBAL positions of all local dofs, so that the levels can take their
         // bricks in one step there too (amg_bricks_level; collective -- every rank of such a solve comes through here)
         bool lattice_global = false, lattice_split = false;
-        if (coupled && L0->bs == 1 && L0->dim == 0 && !std::getenv("PFEM_AMG_NO_HINT") && !std::getenv("PFEM_AMG_NO_LATTICE") &&
-            [] { const char *e = std::getenv("PFEM_AMG_BRICKS"); return e ? std::atoi(e) != 0 : true; }()) {
+        if (coupled && L0->bs == 1 && L0->dim == 0) {
             since_t0("nodes of level 0");
             PFEM_TRY(lattice_positions_global(s, *L0, &lattice_global));
             since_t0("global lattice looked for");
@@ -2760,14 +2655,13 @@ int amg_symbolic(pfem_solver *s, bool multi, bool overlap)
         // so that level 0 -- and every level below it while it stays distributed -- takes its node bricks in one step as on one rank
         // (amg_node_bricks; without this the ranks paired in three passes and kept the 2x2x2 aggregates whose 6x6-block level 1 is
         // the dearest of the cycle).  (L0->dim is agreed above; collective.)
-        if (coupled && L0->dim > 0 && L0->bs == L0->dim && !std::getenv("PFEM_AMG_NO_HINT") && !std::getenv("PFEM_AMG_NO_LATTICE") &&
-            !std::getenv("PFEM_AMG_COUPLED_NODE_BRICKS_OFF") && [] { const char *e = std::getenv("PFEM_AMG_BRICKS"); return e ? std::atoi(e) != 0 : true; }()) {
+        if (coupled && L0->dim > 0 && L0->bs == L0->dim) {
             since_t0("nodes of level 0");
             PFEM_TRY(lattice_positions_global(s, *L0, &lattice_global, true));
             since_t0("global lattice of the nodes looked for");
             lattice = lattice_global;
         }
-        if (s->have_mesh && (s->n_owned > 1 || lattice_global || lattice_split) && !std::getenv("PFEM_AMG_NO_HINT") && !std::getenv("PFEM_AMG_NO_LATTICE")) {
+        if (s->have_mesh && (s->n_owned > 1 || lattice_global || lattice_split)) {
             DevBuf<int32_t> pos;
             int hi[3] = {0, 0, 0};
             since_t0("nodes of level 0");
@@ -2809,7 +2703,7 @@ int amg_symbolic(pfem_solver *s, bool multi, bool overlap)
                 PFEM_HIP(hipStreamSynchronize(s->stream));
             }
         }
-        if (!lattice && s->have_mesh && !s->reordered && s->n_owned > 1 && !std::getenv("PFEM_AMG_NO_HINT")) {
+        if (!lattice && s->have_mesh && !s->reordered && s->n_owned > 1) {
             DevBuf<int32_t> rank;
             if (morton_rank(s, rank) == PFEM_OK) {
                 PFEM_TRY(L0->hint.alloc(static_cast<size_t>(L0->n_nodes)));
@@ -2921,7 +2815,7 @@ int amg_numeric_coupled(pfem_solver *s, Amg &M, bool overlap)
 constexpr int64_t kAmgVdMinSlots = 1 << 20;
 int amg_value_codes(pfem_solver *s, Amg &M)
 {
-    const bool enabled = [] { const char *e = std::getenv("PFEM_SPMV_VALDICT"); return e ? std::atoi(e) != 0 : true; }();
+    const bool enabled = valdict_enabled();
     const int nl = static_cast<int>(M.lev.size());
     std::vector<int> cand;
     for (int l = 1; l + 1 < nl; ++l) {
@@ -3258,12 +3152,11 @@ double *amg_apply(pfem_solver *s, Amg &M, const double *r, const CgCtl *ctl, boo
     const int tail = (M.fused && M.tail_from > 0) ? M.tail_from : nl;         // levels [tail, nl) in one launch
     auto deg_of = [&](int l) { return (l == 0 && M.fine_degree > 0) ? M.fine_degree : M.cheb_degree; };
     auto fused_level = [&](int l) { return fuse && l >= 1 && l < tail && l < nl - 1; };
-    const bool blocked_spmv = [] { const char *e = std::getenv("PFEM_AMG_BLOCK_SPMV"); return e ? std::atoi(e) != 0 : true; }();
     auto ep = [&](int mode, AmgLevel &L, const double *xin, const double *r_in, int step, int add_dd0, double *r_out, double *dd_out, double *x) {
         const SellDev A = amg_sell(s, L);
         const dim3 grid(spmv_grid(A.n_slices)), block(kBlock);
         const double *dinv = L.dinv.p, *lam = L.lam.p;
-        if (L.gptr.p && (L.bs == 6 || L.bs == 3) && blocked_spmv) {          // a level below a rigid-body transfer: node-block form of the same product
+        if (L.gptr.p && (L.bs == 6 || L.bs == 3)) {          // a level below a rigid-body transfer: node-block form of the same product
             const int64_t *gp = L.gptr.p;
             const int32_t *gc = L.gcol.p;
 #define PFEM_BLK_EP(MODEV, CBV) hipLaunchKernelGGL((k_rbm_spmv_ep<MODEV, CBV>), grid, block, 0, s->stream, A, gp, gc, xin, r_in, dinv, lam, M.eig_ratio, step, add_dd0, r_out, dd_out, x, ctl)
@@ -3306,12 +3199,11 @@ double *amg_apply(pfem_solver *s, Amg &M, const double *r, const CgCtl *ctl, boo
             t.rbm_dim = L.rbm ? L.dim : 0; t.fb = L.bs; t.nn = L.n_nodes; t.node_agg = L.node_agg.p; t.roff = L.roff.p;
         }
         // the levels' vectors in LDS (6 a level; config 3: 343 + 64 rows = 19.5 KB) and, beside them, the first level's matrix when all
-        // of it fits 156 KB (config 3: 10 368 slots = 124 KB); PFEM_AMG_TAIL_LDS=0: off
+        // of it fits 156 KB (config 3: 10 368 slots = 124 KB)
         int64_t rows = 0;
         for (int q = 0; q < T.nlev; ++q) rows += T.lev[q].n;
-        static const bool lds_on = [] { const char *e = std::getenv("PFEM_AMG_TAIL_LDS"); return e ? std::atoi(e) != 0 : true; }();
         const size_t vec_b = static_cast<size_t>(6 * rows) * sizeof(double);
-        const bool use_lds = lds_on && vec_b <= 65536;
+        const bool use_lds = vec_b <= 65536;
         const AmgTailLevel &t0 = T.lev[0];
         const size_t mat_b = (T.nlev > 1 && t0.stored > 0) ? static_cast<size_t>(t0.stored) * 12 + static_cast<size_t>(t0.A.n_slices + 2) * 8 : 0;
         const bool mat = use_lds && mat_b > 0 && vec_b + mat_b <= 156 * 1024;
@@ -3424,7 +3316,7 @@ int amg_cycle_shape(pfem_solver *s, Amg &M)
 int run_pcg_amg(pfem_solver *s)
 {
     const int64_t n = s->n_loc;
-    const bool multi = s->nranks > 1 || (s->comm && s->have_plan && std::getenv("PFEM_FORCE_MULTI"));
+    const bool multi = s->nranks > 1 || (s->comm && s->have_plan && force_multi());
     mark_group_vals(s);
     PFEM_TRY(refresh_group_vals(s));
     bool overlap = false;
@@ -3489,41 +3381,19 @@ int run_pcg_amg(pfem_solver *s)
     const int deg0 = M.fine_degree > 0 ? M.fine_degree : M.cheb_degree;
     const bool fuse_first0 = M.fused && M.lev.size() > 1 && !M.coupled;
     const bool fuse_last0 = M.fused && M.lev.size() > 1 && deg0 == 1 && !M.coupled;
-    // Lab option, OFF by default (PFEM_CG_COOP=1): the last smoothing step, the two dot products, the new direction and the x update
-    // in ONE launch with a grid barrier in the middle (k_pc_post_dots_direction), taken when every block of its grid can be resident
-    // at once and a thread's rows fit its registers.  MEASURED AND NOT TAKEN (round 6, config 3, same box, two runs each):
-    // 14.27 / 14.17 ms per step against 13.50 / 13.49 with the three kernels -- the 126 MB of z traffic it saves (~20 us an
-    // iteration) cost 55 us: 768 persistent blocks stream five vectors at 12 waves a CU behind a barrier that waits for the slowest.
-    unsigned coop_grid = 0;
-    if (!multi && fuse_last0 && s->n_ghost == 0 && [] { const char *e = std::getenv("PFEM_CG_COOP"); return e ? std::atoi(e) != 0 : false; }()) {
-        static int cus = 0, occ = -1;
-        if (occ < 0) {
-            hipDeviceProp_t prop;
-            int dev = 0;
-            occ = 0;
-            if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void *>(k_pc_post_dots_direction), kBlock, 0) != hipSuccess) { occ = 0; (void)hipGetLastError(); }
-        }
-        // (a block to spare: the occupancy the runtime reports has been seen one block per CU too high on this stack)
-        if (cus > 0 && occ >= kCoopBlocksPerCu + 1) {
-            const unsigned g = static_cast<unsigned>(kCoopBlocksPerCu * cus);
-            if ((n + static_cast<int64_t>(g) * kBlock - 1) / (static_cast<int64_t>(g) * kBlock) <= kCoopMaxK && g <= static_cast<unsigned>(kMaxGrid)) coop_grid = g;
-        }
-    }
     // One rank: the cycle of the iterations (the one that takes the control block) is replayed from a hipGraph -- a
     // dependent tiny kernel costs ~3.4 us on a stream and ~1.75 us in a graph (tools/lab/graph_gap.hip), and six of the
     // eight levels of the 200^3 hierarchy are too small to fill the chip.  PFEM_CG_GRAPH=0 turns it off.
     bool use_vgraph = false;
     {
-        const int graph_env = [] { const char *e = std::getenv("PFEM_CG_GRAPH"); return e ? std::atoi(e) : 1; }();
+        const int graph_env = cg_graph_env();
         // (several ranks: stream launches.  The coupled cycle with its RCCL calls as one captured graph was tried this round -- it
         // would take the ~80 launches of an iteration off the host, which runs ahead of the device anyway -- and the replay never
         // returned in the self-peer probe (tools/probe_coupled.py); dropped)
         // (round 5: a transport whose calls are plain kernel launches with constant arguments -- peer memory, message counters on
         // the device -- lets the cycle ACROSS ranks be captured too: ~65 of an iteration's ~80 launches leave the host)
         const bool coupled_capturable = multi && M.coupled && !overlap && s->comm && s->comm->capturable() && s->comm->p2p_capturable() &&
-                                        (!M.rep || M.n_last_global <= s->comm->allreduce_capture_limit()) &&
-                                        [] { const char *e = std::getenv("PFEM_AMG_COUPLED_GRAPH"); return e ? std::atoi(e) != 0 : true; }();
+                                        (!M.rep || M.n_last_global <= s->comm->allreduce_capture_limit());
         if ((!multi || coupled_capturable) && graph_env && !M.graph_off && s->stream != nullptr) {
             std::vector<uint64_t> key = {reinterpret_cast<uint64_t>(s->d_r.p), reinterpret_cast<uint64_t>(ctl), reinterpret_cast<uint64_t>(s->stream),
                                          reinterpret_cast<uint64_t>(s->d_vals.p), reinterpret_cast<uint64_t>(s->d_cols.p), reinterpret_cast<uint64_t>(s->d_rvals.p),
@@ -3673,7 +3543,7 @@ int run_pcg_amg(pfem_solver *s)
     // ~40 launches (each leaves at once, ~0.1 ms together), a read costs a round trip: one rank sizes the next batch from
     // the contraction seen so far -- the multigrid cycle contracts at a steady rate -- instead of a fixed 4; several ranks
     // keep the fixed size (every rank must enqueue the same calls, and nothing may depend on a host's libm for that).
-    const int chunk_env = [] { const char *e = std::getenv("PFEM_CG_CHUNK"); const int c = e ? std::atoi(e) : 0; return c > 0 ? c : 0; }();
+    const int chunk_env = cg_chunk_env();
     const int chunk = chunk_env > 0 ? chunk_env : 4;
     size_t ev_used = 0, comm_used = 0;
     const size_t ev_per = multi ? 4 : 2;
@@ -3744,19 +3614,12 @@ int run_pcg_amg(pfem_solver *s)
             {
                 AmgLevel &L0 = *M.lev[0];
                 hipLaunchKernelGGL(k_pc_update, dim3(gv), block, 0, s->stream, ctl, it, n, pw_parts, pw_n, red_pw, static_cast<const double *>(s->d_p.p),
-                                   static_cast<const double *>(s->d_w.p), coop_grid ? static_cast<double *>(nullptr) : s->d_x.p, s->d_r.p, L0.n, static_cast<const double *>(L0.dinv.p),
+                                   static_cast<const double *>(s->d_w.p), s->d_x.p, s->d_r.p, L0.n, static_cast<const double *>(L0.dinv.p),
                                    static_cast<const double *>(L0.lam.p), M.eig_ratio, fuse_first0 ? L0.x : static_cast<double *>(nullptr),
                                    (fuse_first0 && deg0 > 1) ? L0.dd : static_cast<double *>(nullptr));
             }
             z = precondition(ctl);
             if (!z) return PFEM_ERR_COMM;
-            if (coop_grid) {
-                AmgLevel &L0 = *M.lev[0];
-                hipLaunchKernelGGL(k_pc_post_dots_direction, dim3(coop_grid), block, 0, s->stream, ctl, it, n, static_cast<const double *>(s->d_r.p),
-                                   static_cast<const double *>(L0.t.p), static_cast<const double *>(L0.dinv.p), static_cast<const double *>(L0.lam.p), M.eig_ratio,
-                                   static_cast<const double *>(z), s->d_p.p, s->d_x.p, part_rz, part_zz, s->d_hist.p, s->hist_cap, s->maxits);
-                continue;
-            }
             PFEM_TRY(dots(z, ctl, cev));
             hipLaunchKernelGGL(k_cg_direction_b, dim3(gv), block, 0, s->stream, ctl, it, n, static_cast<const double *>(part_rz),
                                static_cast<const double *>(part_zz), static_cast<int>(gv), red2, static_cast<const double *>(z), s->d_p.p,
@@ -3767,10 +3630,6 @@ int run_pcg_amg(pfem_solver *s)
         s->tm.host_enqueued_iterations += it - it0;
     }
     s->tm.host_comm_ms = host_comm_s * 1e3;
-    if (h.flag == -100) {
-        set_last_error("gamg pcg: the grid barrier of k_pc_post_dots_direction timed out (its blocks were not all resident); PFEM_CG_COOP=0 takes the three-kernel form");
-        return PFEM_ERR_STATE;
-    }
     s->last_its = h.its;
     s->last_reason = (h.flag == 2 && h.rn <= s->abstol) ? 3 : h.flag;
     s->last_rnorm = h.rn;

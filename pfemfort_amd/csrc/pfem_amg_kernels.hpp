@@ -14,13 +14,12 @@ namespace pfem {
 // line by line this makes ties pair along the numbering direction, so three passes build 2x2x2 bricks instead of random
 // octets; (3) parity of the lower index: of the two neighbours of a node on a line exactly one forms an "even" edge, so
 // the whole line pairs up in ONE round; (4) a hash of the pair.  Positive couplings (w >= 0) are not eligible.
-__device__ __forceinline__ int64_t amg_edge_key(int32_t i, int32_t j, int32_t hi_, int32_t hj_, double w, double di, double dj, int flat)
+__device__ __forceinline__ int64_t amg_edge_key(int32_t i, int32_t j, int32_t hi_, int32_t hj_, double w, double di, double dj)
 {
     if (!(w < 0.0) || !(di > 0.0) || !(dj > 0.0)) return -1;
     const double s = -w / sqrt(di * dj);
     int b = static_cast<int>(floor(8.0 * log2(s))) + 2048;
     b = b < 1 ? 1 : (b > 4095 ? 4095 : b);
-    if (flat) b = 1;                     // lab knob PFEM_AMG_NO_STRENGTH: every negative coupling equally strong
     // (2), (3) on the nodes' PLACE ALONG A SPACE-FILLING CURVE when the mesh came with coordinates (hi_, hj_: Morton ranks,
     // halved from pass to pass and from level to level), else on their indices
     const int64_t lo = hi_ < hj_ ? hi_ : hj_, hi = hi_ < hj_ ? hj_ : hi_;
@@ -34,7 +33,7 @@ __device__ __forceinline__ int64_t amg_edge_key(int32_t i, int32_t j, int32_t hi
 // every free node proposes to its best free neighbour
 __global__ void __launch_bounds__(kBlock) k_amg_match_pick(int64_t n, const int64_t *__restrict__ gptr, const int32_t *__restrict__ gcol,
                                                             const double *__restrict__ gw, const double *__restrict__ gdiag,
-                                                            const int32_t *__restrict__ hint /* null: the index */, int flat,
+                                                            const int32_t *__restrict__ hint /* null: the index */,
                                                             const int32_t *__restrict__ match, int32_t *__restrict__ cand)
 {
     const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
@@ -47,7 +46,7 @@ __global__ void __launch_bounds__(kBlock) k_amg_match_pick(int64_t n, const int6
         for (int64_t q = gptr[i]; q < gptr[i + 1]; ++q) {
             const int32_t j = gcol[q];
             if (j == i || match[j] >= 0) continue;
-            const int64_t k = amg_edge_key(static_cast<int32_t>(i), j, hi_, hint ? hint[j] : j, gw[q], di, gdiag[j], flat);
+            const int64_t k = amg_edge_key(static_cast<int32_t>(i), j, hi_, hint ? hint[j] : j, gw[q], di, gdiag[j]);
             if (k > bk) { bk = k; best = j; }
         }
     }
@@ -90,144 +89,6 @@ __global__ void __launch_bounds__(kBlock) k_amg_hint_coarsen(int64_t n, const in
 {
     const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
     if (i < n) atomicMin(&hint_c[agg[i]], (hint ? hint[i] : static_cast<int32_t>(i)) >> 1);
-}
-// ---- roots + neighbours: aggregates from an independent set of the strength graph (round 6) ---------------------------------
-// WHY.  Where a displacement problem's mesh has no lattice, five passes of pairwise matching gave the rigid-body transfer lopsided
-// aggregates (chains of pairs of pairs): the beam with its nodes moved off the lattice took 61 iterations where 4x4x4 bricks take
-// 22, and every pass cost a sorted aggregate graph.  The classical remedy (Vanek, Mandel, Brezina 1996: aggregation by roots)
-// gives compact ones in a few sweeps over the graph and no sort: a ROOT is a node whose priority is the highest within TWO
-// strong hops among the undecided (so roots end up at least three hops apart), its strong neighbours join it at once, nodes two
-// hops from a root wait; rounds repeat until nobody is undecided; then the waiting nodes join the aggregate of their strongest
-// decided neighbour (two sweeps), and whoever is still alone becomes a root.  j is a strong neighbour of i when
-// s_ij >= 1/4 max_k s_ik (the threshold of the pairing).  Priorities are a hash of the node's place along the curve / its index,
-// unique by construction: the outcome depends on nothing but the graph.  state: 0 undecided, 1 root, 2 member, 3 waiting.
-__device__ __forceinline__ double amg_strength(double w, double di, double dj);
-__device__ __forceinline__ unsigned long long mis_prio(int32_t place, int64_t i)
-{
-    unsigned long long h = static_cast<unsigned long long>(static_cast<uint32_t>(place)) * 0x9E3779B97F4A7C15ull;
-    h ^= h >> 29;
-    h *= 0xBF58476D1CE4E5B9ull;
-    h ^= h >> 32;
-    return ((h & 0x7fffffffull) << 32) | static_cast<unsigned long long>(i + 1);
-}
-__global__ void __launch_bounds__(kBlock) k_mis_init(int64_t n, const int64_t *__restrict__ gptr, const int32_t *__restrict__ gcol,
-                                                      const double *__restrict__ gw, const double *__restrict__ gdiag, const int32_t *__restrict__ hint,
-                                                      double *__restrict__ smax, unsigned long long *__restrict__ prio, int32_t *__restrict__ state,
-                                                      int32_t *__restrict__ match)
-{
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const double di = gdiag[i];
-    double m = 0.0;
-    for (int64_t q = gptr[i]; q < gptr[i + 1]; ++q) {
-        const int32_t j = gcol[q];
-        if (j != i) m = fmax(m, amg_strength(gw[q], di, gdiag[j]));
-    }
-    smax[i] = m;
-    prio[i] = mis_prio(hint ? hint[i] : static_cast<int32_t>(i), i);
-    state[i] = 0;
-    match[i] = -1;
-}
-// out[i] = max over i and its strong neighbours of (FIRST: the priority of the undecided / else: in[j])
-template <bool FIRST>
-__global__ void __launch_bounds__(kBlock) k_mis_spread(int64_t n, const int64_t *__restrict__ gptr, const int32_t *__restrict__ gcol,
-                                                        const double *__restrict__ gw, const double *__restrict__ gdiag, const double *__restrict__ smax,
-                                                        const int32_t *__restrict__ state, const unsigned long long *__restrict__ in,
-                                                        unsigned long long *__restrict__ out)
-{
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const double di = gdiag[i], thr = 0.25 * smax[i];
-    unsigned long long m = FIRST ? (state[i] == 0 ? in[i] : 0ull) : in[i];
-    for (int64_t q = gptr[i]; q < gptr[i + 1]; ++q) {
-        const int32_t j = gcol[q];
-        if (j == i) continue;
-        const double sij = amg_strength(gw[q], di, gdiag[j]);
-        if (!(sij > 0.0 && sij >= thr)) continue;
-        const unsigned long long v = FIRST ? (state[j] == 0 ? in[j] : 0ull) : in[j];
-        m = v > m ? v : m;
-    }
-    out[i] = m;
-}
-__global__ void __launch_bounds__(kBlock) k_mis_roots(int64_t n, const unsigned long long *__restrict__ prio, const unsigned long long *__restrict__ t2,
-                                                       int32_t *__restrict__ state, int32_t *__restrict__ match)
-{
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
-    if (i < n && state[i] == 0 && prio[i] == t2[i]) { state[i] = 1; match[i] = static_cast<int32_t>(i); }
-}
-// an undecided node next to a root joins it (the strongest such root, the lower index on a tie); cand = the root, else -1
-__global__ void __launch_bounds__(kBlock) k_mis_join_pick(int64_t n, const int64_t *__restrict__ gptr, const int32_t *__restrict__ gcol,
-                                                           const double *__restrict__ gw, const double *__restrict__ gdiag, const double *__restrict__ smax,
-                                                           const int32_t *__restrict__ state, int32_t *__restrict__ cand)
-{
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
-    if (i >= n) return;
-    int32_t best = -1;
-    if (state[i] == 0) {
-        const double di = gdiag[i], thr = 0.25 * smax[i];
-        double sb = 0.0;
-        for (int64_t q = gptr[i]; q < gptr[i + 1]; ++q) {
-            const int32_t j = gcol[q];
-            if (j == i || state[j] != 1) continue;
-            const double sij = amg_strength(gw[q], di, gdiag[j]);
-            if (sij > 0.0 && sij >= thr && (sij > sb || (sij == sb && j < best))) { sb = sij; best = j; }
-        }
-    }
-    cand[i] = best;
-}
-__global__ void __launch_bounds__(kBlock) k_mis_join_commit(int64_t n, const int32_t *__restrict__ cand, int32_t *__restrict__ state, int32_t *__restrict__ match)
-{
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
-    if (i < n && cand[i] >= 0) { state[i] = 2; match[i] = cand[i]; }
-}
-// an undecided node next to a MEMBER is two hops from a root: it waits (state 3); *left counts the nodes still undecided
-__global__ void __launch_bounds__(kBlock) k_mis_wait(int64_t n, const int64_t *__restrict__ gptr, const int32_t *__restrict__ gcol,
-                                                      const double *__restrict__ gw, const double *__restrict__ gdiag, const double *__restrict__ smax,
-                                                      const int32_t *__restrict__ state, int32_t *__restrict__ cand)
-{
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
-    if (i >= n) return;
-    int32_t w = 0;
-    if (state[i] == 0) {
-        const double di = gdiag[i], thr = 0.25 * smax[i];
-        for (int64_t q = gptr[i]; q < gptr[i + 1] && !w; ++q) {
-            const int32_t j = gcol[q];
-            if (j == i || state[j] != 2) continue;
-            const double sij = amg_strength(gw[q], di, gdiag[j]);
-            if (sij > 0.0 && sij >= thr) w = 1;
-        }
-    }
-    cand[i] = w;
-}
-__global__ void __launch_bounds__(kBlock) k_mis_wait_commit(int64_t n, const int32_t *__restrict__ cand, int32_t *__restrict__ state, int *__restrict__ left)
-{
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
-    if (i >= n) return;
-    if (cand[i]) state[i] = 3;
-    if (left && state[i] == 0) atomicAdd(left, 1);
-}
-// the waiting (and any still undecided) nodes: the aggregate of the strongest decided neighbour (any negative coupling counts here:
-// nobody stays alone for a threshold); cand = that aggregate's root, else -1
-__global__ void __launch_bounds__(kBlock) k_mis_adopt_pick(int64_t n, const int64_t *__restrict__ gptr, const int32_t *__restrict__ gcol,
-                                                            const double *__restrict__ gw, const double *__restrict__ gdiag,
-                                                            const int32_t *__restrict__ state, const int32_t *__restrict__ match, int32_t *__restrict__ cand)
-{
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
-    if (i >= n) return;
-    int32_t best = -1;
-    if (state[i] == 0 || state[i] == 3) {
-        const double di = gdiag[i];
-        double sb = 0.0;
-        int32_t bj = -1;
-        for (int64_t q = gptr[i]; q < gptr[i + 1]; ++q) {
-            const int32_t j = gcol[q];
-            if (j == i || (state[j] != 1 && state[j] != 2)) continue;
-            const double sij = amg_strength(gw[q], di, gdiag[j]);
-            if (sij > 0.0 && (sij > sb || (sij == sb && j < bj))) { sb = sij; bj = j; }
-        }
-        if (bj >= 0) best = match[bj];
-    }
-    cand[i] = best;
 }
 // ---- pairing on a tensor-product lattice -----------------------------------------------------------------------------
 // When the nodes of the mesh sit on a lattice (every coordinate takes few distinct values: the generated boxes, the
@@ -2059,10 +1920,10 @@ __global__ void __launch_bounds__(kBlock) k_pc_update(CgCtl *ctl, int it, int64_
     }
     const double alpha = ctl->beta[it & 1] / pw;
     const double c_first = z0 ? cheb_coef(lam[0], ratio, 0).c_first : 0.0;
-    const bool defer_x = x == nullptr;           // (the x update rides on k_pc_post_dots_direction, which streams p anyway: alpha travels in the control block)
-    if (defer_x && blockIdx.x == 0 && threadIdx.x == 0) ctl->alpha = alpha;
     for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < n; i += static_cast<int64_t>(gridDim.x) * kBlock) {
-        if (!defer_x) x[i] = __builtin_fma(alpha, p[i], x[i]);
+        x[i] = __builtin_fma(alpha, p[i], x[i]);
+        // (x's pair of loads completes before r's is issued: with all four in flight the kernel took 86 instead of 81 us at config 3)
+        __builtin_amdgcn_sched_barrier(0);
         const double ri = __builtin_fma(-alpha, w[i], r[i]);
         r[i] = ri;
         if (z0 && i < n_pc) {
@@ -2098,98 +1959,6 @@ __global__ void __launch_bounds__(kBlock) k_pc_post_dots(const CgCtl *ctl, int64
     }
     const double a = block_sum(rz, sm), c = block_sum(zz, sm);
     if (threadIdx.x == 0) { part_rz[blockIdx.x] = a; part_zz[blockIdx.x] = c; }
-}
-// k_pc_post_dots + k_cg_direction_b + the x update of k_pc_update in ONE launch (one rank; round 6).  The three kernels streamed
-// r, t, dinv, z | z, p | p, x: z was written by the first only to be read back by the second, and p was read twice.  Here every
-// thread keeps the z of its rows in registers across a grid barrier: phase 1 forms z and the block's (r,z), (z,z) partials;
-// all blocks meet (an arrival counter in the control block, bounded spin: a timeout ends the solve with an error instead of
-// hanging the device); phase 2 sums the partials -- every block the same sums in the same order --, judges convergence exactly as
-// k_cg_direction_b does, and streams p once: x += alpha p (the step k_pc_update left to this launch), p = z + beta p.
-// The grid is sized by the caller so that ALL blocks are resident at once (kCoopBlocksPerCu per CU, checked against the
-// occupancy the runtime reports, with a block to spare); K = rows a thread owns <= kCoopMaxK.
-constexpr int kCoopMaxK = 48;
-constexpr int kCoopBlocksPerCu = 3;
-constexpr unsigned long long kCoopSpinTicks = 300000000ull;          // 3 s at 100 MHz
-__global__ void __launch_bounds__(kBlock, kCoopBlocksPerCu) k_pc_post_dots_direction(CgCtl *ctl, int it, int64_t n, const double *__restrict__ r, const double *__restrict__ t,
-                                                                    const double *__restrict__ dinv, const double *__restrict__ lam, double ratio,
-                                                                    const double *__restrict__ z_in, double *__restrict__ p, double *__restrict__ x,
-                                                                    double *part_rz, double *part_zz, double *hist, int hist_cap, int maxits)
-{
-    __shared__ double sm[4];
-    __shared__ int ok_s;
-    if (ctl_finished_before(ctl, it)) return;
-    const bool breakdown = ctl->pad_ != 0;                    // (flagged by k_pc_update: (p,Ap) <= 0; x was not advanced)
-    const int64_t stride = static_cast<int64_t>(gridDim.x) * kBlock, i0 = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
-    const double c_first = cheb_coef(lam[0], ratio, 0).c_first;
-    double zr[kCoopMaxK];
-    double rz = 0.0, zz = 0.0;
-    if (!breakdown) {
-#pragma unroll
-        for (int k = 0; k < kCoopMaxK; ++k) {
-            const int64_t i = i0 + k * stride;
-            zr[k] = 0.0;
-            if (i < n) {
-                const double ri = r[i];
-                const double zi = z_in[i] + c_first * dinv[i] * (ri - t[i]);
-                zr[k] = zi;
-                rz = __builtin_fma(ri, zi, rz);
-                zz = __builtin_fma(zi, zi, zz);
-            }
-        }
-    }
-    const double a = block_sum(rz, sm), c = block_sum(zz, sm);
-    if (threadIdx.x == 0) {
-        part_rz[blockIdx.x] = breakdown ? 0.0 : a;
-        part_zz[blockIdx.x] = breakdown ? -1.0 : c;
-        // ---- grid barrier: arrival it + 1 of gridDim.x blocks each (the control block is zeroed at the start of a solve)
-        __threadfence();
-        const unsigned want = static_cast<unsigned>(it + 1) * gridDim.x;
-        __hip_atomic_fetch_add(&ctl->gbar, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned long long t0 = wall_clock64();
-        int ok = 1;
-        while (__hip_atomic_load(&ctl->gbar, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < want) {
-            __builtin_amdgcn_s_sleep(2);
-            if (wall_clock64() - t0 > kCoopSpinTicks) { ok = 0; break; }
-        }
-        ok_s = ok;
-    }
-    __syncthreads();
-    if (!ok_s) {                                              // not all blocks were resident: end the solve, do not hang
-        if (threadIdx.x == 0) ctl_publish(ctl, -100, it + 1);
-        return;
-    }
-    const int nparts = static_cast<int>(gridDim.x);
-    const double srz = sum_partials(part_rz, nparts, sm), szz = sum_partials(part_zz, nparts, sm);
-    const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
-    if (szz < 0.0) {
-        if (lead) ctl_publish(ctl, -10, it + 1);
-        return;
-    }
-    const double rn = sqrt(szz);
-    const double beta_old = ctl->beta[it & 1], alpha = ctl->alpha;
-    int flag = 0;
-    if (rn <= ctl->ttol) flag = 2;
-    else if (rn >= ctl->dtol * ctl->rn0) flag = -4;
-    else if (srz < 0.0) flag = -8;
-    else if (it + 1 >= maxits) flag = -3;
-    // (every block has read beta, alpha, ttol ... before the lead overwrites anything a LATER kernel reads only: beta of the other
-    // parity, rn, the history, the verdict -- nothing this launch still reads)
-    if (lead) {
-        ctl->beta[(it + 1) & 1] = srz;
-        ctl->rn = rn;
-        if (it + 1 < hist_cap) hist[it + 1] = rn;
-        ctl_publish(ctl, flag, it + 1);
-    }
-    const double bb = srz / beta_old;
-#pragma unroll
-    for (int k = 0; k < kCoopMaxK; ++k) {
-        const int64_t i = i0 + k * stride;
-        if (i < n) {
-            const double pi = p[i];
-            x[i] = __builtin_fma(alpha, pi, x[i]);           // the iterate of THIS iteration (also when it is the last)
-            if (flag == 0) p[i] = __builtin_fma(bb, pi, zr[k]);
-        }
-    }
 }
 
 // Single-reduction form of the loop (KSPCGUseSingleReduction; k_cg1_step with a STORED z = M^-1 r from the V-cycle): step `it`

@@ -61,8 +61,7 @@ struct AmgLevel {
                                           // needs when it leaves the brick path (xyz below) come from here instead of travelling down the levels
     DevBuf<double> xyz;                   // coupled hierarchy with a lattice: [3 x n_nodes] a corner of every node's aggregate (see k_amg_xyz_min)
     // how this level's aggregates were formed (pfem_solver_amg_aggregation): 0 none (last level), 1 bricks in one step, 2 node bricks
-    // in one step, 3 bricks split between their owners, 4 pairing passes on the lattice, 5 matching on the strength graph,
-    // 6 roots + neighbours (independent set)
+    // in one step, 3 bricks split between their owners, 4 pairing passes on the lattice, 5 matching on the strength graph
     int agg_kind = 0;
     // transfer to the next level (piecewise-constant prolongation)
     int64_t nc = 0;

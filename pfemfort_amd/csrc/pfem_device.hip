@@ -160,11 +160,6 @@ struct DevPool {
         static const size_t v = [] { const char *e = std::getenv("PFEM_POOL_FIT"); return e ? std::max<size_t>(1, static_cast<size_t>(std::atoll(e))) : 2; }();
         return v;
     }
-    static bool splitting()       // PFEM_POOL_SPLIT=0: round 4's pool (whole blocks within the fit factor only)
-    {
-        static const bool v = [] { const char *e = std::getenv("PFEM_POOL_SPLIT"); return e ? std::atoi(e) != 0 : true; }();
-        return v;
-    }
     static size_t min_bytes()
     {
         static const size_t v = [] { const char *e = std::getenv("PFEM_POOL_MIN_KB"); return (e ? static_cast<size_t>(std::atoll(e)) : 64) << 10; }();
@@ -196,7 +191,7 @@ struct DevPool {
         (void)hipGetDevice(&dev);
         size_t best = blocks.size();
         for (size_t i = 0; i < blocks.size(); ++i)
-            if (blocks[i].device == dev && blocks[i].bytes >= bytes && (splitting() || blocks[i].bytes <= fit() * bytes) &&
+            if (blocks[i].device == dev && blocks[i].bytes >= bytes &&
                 (best == blocks.size() || blocks[i].bytes < blocks[best].bytes)) best = i;
         if (best == blocks.size()) return nullptr;
         Block b = blocks[best];
@@ -205,13 +200,9 @@ struct DevPool {
         if (split && b.root < 0 && b.bytes >= kLargeBytes) {
             // a large block about to become a ROOT: one long-lived piece would pin all of it, and neither trim() nor give() could
             // hand the rest back.  Alone on the device that costs nothing; when the device runs short (other processes share it:
-            // ranks of a test or a development run) the block is not split -- it goes out whole if it fits within the factor,
-            // else the request goes to the driver (advisor, round 5)
+            // ranks of a test or a development run) the block is not split and the request goes to the driver (advisor, round 5)
             size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b < total_b / 4) {
-                if (b.bytes > fit() * bytes) return nullptr;
-                split = false;
-            }
+            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b < total_b / 4) return nullptr;
         }
         if (split) {
             // the front of the block goes out, the rest stays; a block split for the first time becomes a root
@@ -411,6 +402,13 @@ inline unsigned spmv_grid(int64_t n_slices)
     return static_cast<unsigned>(std::max<int64_t>(1, (n_slices + 3) / 4));
 }
 
+// PFEM_SPMV_VALDICT=0 keeps the SpMV values in fp64 (pfem_valdict.hpp); read per call: tests switch it
+inline bool valdict_enabled()
+{
+    const char *e = std::getenv("PFEM_SPMV_VALDICT");
+    return e ? std::atoi(e) != 0 : true;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -529,8 +527,7 @@ struct pfem_solver {
     bool vd_refused = false;       // pfem_valdict.hpp: more than kVdMax distinct values (decided once per pattern)
     int64_t min_groups_auto() const
     {
-        const char *e = std::getenv("PFEM_SPMV_VALDICT");
-        return (vd_refused || (e && std::atoi(e) == 0)) ? kMinGroupsAutoFp64 : kMinGroupsAuto;
+        return (vd_refused || !valdict_enabled()) ? kMinGroupsAutoFp64 : kMinGroupsAuto;
     }
     bool use_grouped() const
     {
@@ -951,7 +948,7 @@ int maybe_reorder(pfem_solver *s, const int32_t *edof_global, const double *xyz)
     s->reordered = true;
     // the nodes follow their dofs: with the nodes in the caller's (locality-free) order the gather assembly wrote its rows all
     // over the matrix -- 13 ms instead of 2 at config 3's size
-    if (m.nNode <= INT_MAX && !std::getenv("PFEM_DEBUG_KEEP_NODE_ORDER")) {
+    if (m.nNode <= INT_MAX) {
         const int64_t nn = m.nNode;
         DevBuf<uint64_t> nkeys, nskeys;
         DevBuf<int32_t> niota, norder, nperm;
@@ -1953,11 +1950,10 @@ int pattern_from_incidence(pfem_solver *s, bool *done)
 // synchronously (~30 GB/s) the first solve then paid 20-40 ms for the rest.  This is memory reservation, not work moved out
 // of a timer by stealth: the reference preallocates its matrix in the same place (solverpetsc.F:119-146, outside its
 // timers), and the first solve's symbolic phase is still timed whole.  Best effort: a failed allocation just leaves the pool
-// as it was.  PFEM_POOL_RESERVE=0 turns it off.
+// as it was.
 static void pool_reserve_for_setup(const pfem_solver *s)
 {
-    static const bool on = [] { const char *e = std::getenv("PFEM_POOL_RESERVE"); return e ? std::atoi(e) != 0 : true; }();
-    if (!on || s->pc != PFEM_PC_GAMG || !DevPool::splitting()) return;
+    if (s->pc != PFEM_PC_GAMG) return;
     const size_t want = 16 * static_cast<size_t>(std::max<int64_t>(s->stored, 0)) + 128 * static_cast<size_t>(std::max<int64_t>(s->n_loc, 0));
     const size_t have = dev_pool().held;
     if (want < have + (32u << 20)) return;
@@ -2193,7 +2189,7 @@ extern "C" int pfem_assemble(pfem_solver *s, const double *elemData, const doubl
                 PFEM_TRY(allow_lds(reinterpret_cast<const void *>(&k_gather_poisson_tet4)));
                 // (the relative-group copy of the values the CG's SpMV streams is written here too when that form is in use and the
                 // whole matrix is assembled by this kernel: k_rel_vals' 1.9 GB re-pack per solve -- 0.66 ms at config 3 -- goes away)
-                const bool both = s->use_rel() && s->d_relk.p && s->n_hubs == 0 && !std::getenv("PFEM_DEBUG_NO_REL_DIRECT");
+                const bool both = s->use_rel() && s->d_relk.p && s->n_hubs == 0;
                 // (level 0's inverse diagonal and Gershgorin ratios for the multigrid's numeric phase, while the rows are in LDS: one rank,
                 // the whole matrix assembled by this kernel, the hierarchy of this pattern in place -- every step but the first)
                 AmgLevel *L0 = (s->pc == PFEM_PC_GAMG && s->amg && s->amg->symbolic_ok && !s->amg->coupled && s->nranks == 1 && s->n_ghost == 0 &&
@@ -2201,10 +2197,10 @@ extern "C" int pfem_assemble(pfem_solver *s, const double *elemData, const doubl
                                 !std::getenv("PFEM_DEBUG_NO_ASM_BOUND")) ? s->amg->lev[0].get() : nullptr;
                 const bool bound = L0 && L0->dinv.p && L0->t.p && L0->dinv.n >= static_cast<size_t>(s->n_loc) && L0->t.n >= static_cast<size_t>(s->n_loc);
                 // (the SpMV's value CODES instead of the fp64 copy of that form when the last step left a dictionary, its hash table
-                // and a fully encoded code array behind: pfem_vdhash.hpp; PFEM_VD_DIRECT=0: the encode pass of round 5)
-                const bool vd_on = [] { const char *e = std::getenv("PFEM_SPMV_VALDICT"); return e ? std::atoi(e) != 0 : true; }();
+                // and a fully encoded code array behind: pfem_vdhash.hpp; else the encode pass of round 5)
+                const bool vd_on = valdict_enabled();
                 const bool direct = both && vd_on && s->vd_have_dict && s->vd_hash_ok && s->vd_ok && s->vd_rows == kRelRows && !s->rel_gap32 && s->d_vhash.p &&
-                                    s->d_vcodes.p && s->d_vstate.p && s->d_vcodes.n >= static_cast<size_t>(s->r_stored) && !std::getenv("PFEM_VD_DIRECT_OFF");
+                                    s->d_vcodes.p && s->d_vstate.p && s->d_vcodes.n >= static_cast<size_t>(s->r_stored);
                 if (direct) {
                     const VdState reset{s->vd_n, 0, 0, 0};
                     PFEM_HIP(hipMemcpyAsync(s->d_vstate.p, &reset, sizeof reset, hipMemcpyHostToDevice, s->stream));
@@ -2230,7 +2226,7 @@ extern "C" int pfem_assemble(pfem_solver *s, const double *elemData, const doubl
             PFEM_TRY(allow_lds(reinterpret_cast<const void *>(&k_gather_elast_rows)));
             // (plain block order: the XCD-contiguous one measured 3 % slower on the beam, 1.605 against 1.56 ms)
             {
-                const bool bothg = s->use_grouped() && s->d_row_group.p && s->n_hubs == 0 && !std::getenv("PFEM_DEBUG_NO_REL_DIRECT");
+                const bool bothg = s->use_grouped() && s->d_row_group.p && s->n_hubs == 0;
                 const bool patsf = pats && s->d_pat_flags.p;
                 hipLaunchKernelGGL(k_gather_elast_rows, rgrid, rblock, rlds, s->stream, m, A, s->d_rhs.p, prm, ip, ic, irec, ifl, nrow, s->d_err.p, 0u,
                                    bothg ? static_cast<const int32_t *>(s->d_row_group.p) : nullptr, bothg ? static_cast<const int32_t *>(s->d_group_row0.p) : nullptr,
@@ -2590,7 +2586,7 @@ int build_groups(pfem_solver *s)
     s->vd_hash_ok = s->vd_direct_pending = false;
     s->vd_rows = 0;
     s->d_row_group.release();
-    if (s->grouped && !std::getenv("PFEM_DEBUG_NO_REL_DIRECT")) {       // for an assembly that writes this copy itself; its zero padding is set here, once
+    if (s->grouped) {       // for an assembly that writes this copy itself; its zero padding is set here, once
         PFEM_TRY(s->d_row_group.alloc(static_cast<size_t>(n)));
         hipLaunchKernelGGL(k_row_group_index, dim3(grid_for(s->n_groups)), dim3(kBlock), 0, s->stream, static_cast<const int32_t *>(s->d_group_row0.p),
                            s->n_groups, s->d_row_group.p);
@@ -2703,7 +2699,7 @@ int build_rel_groups(pfem_solver *s)
     s->vd_hash_ok = s->vd_direct_pending = false;
     s->vd_rows = 0;
     s->d_relk.release();
-    if (s->max_row_len > 0 && !std::getenv("PFEM_DEBUG_NO_REL_DIRECT")) {
+    if (s->max_row_len > 0) {
         PFEM_TRY(s->d_relk.alloc(static_cast<size_t>(std::max<int64_t>(s->stored, 1))));
         PFEM_HIP(hipMemsetAsync(s->d_relk.p, 0xff, static_cast<size_t>(std::max<int64_t>(s->stored, 1)), s->stream));
         PFEM_HIP(hipMemsetAsync(s->d_rvals.p, 0, sizeof(double) * static_cast<size_t>(std::max<int64_t>(tot_e, 1)) * kRelRows, s->stream));
@@ -2727,7 +2723,7 @@ inline void mark_group_vals(pfem_solver *s)
 {
     // (... or nobody will read that copy: the SpMV streams codes that are current -- written by the assembly itself, its verdict
     // pending, or encoded from a copy that has since been overwritten by nothing)
-    const bool vd_on = [] { const char *e = std::getenv("PFEM_SPMV_VALDICT"); return e ? std::atoi(e) != 0 : true; }();
+    const bool vd_on = valdict_enabled();
     const bool codes_serve = vd_on && s->use_rel() && s->vd_rows == kRelRows && (s->vd_direct_pending || (s->vd_current && s->vd_ok));
     s->group_vals_stale = !((s->use_rel() && (s->rel_vals_current || codes_serve)) || (s->use_grouped() && s->grp_vals_current));
 }
@@ -2735,7 +2731,7 @@ inline void mark_group_vals(pfem_solver *s)
 // verdict decides which kernel the solve launches.
 int refresh_value_codes(pfem_solver *s)
 {
-    const bool enabled = [] { const char *e = std::getenv("PFEM_SPMV_VALDICT"); return e ? std::atoi(e) != 0 : true; }();     // (read per call: tests switch it)
+    const bool enabled = valdict_enabled();     // (read per call: tests switch it)
     const bool verbose = std::getenv("PFEM_VD_VERBOSE") != nullptr;
     const int rows = s->use_grouped() ? kGroupRows : ((s->use_rel() && !s->rel_gap32) ? kRelRows : 0);
     if (!enabled || rows == 0 || s->vd_refused) { s->vd_ok = false; return PFEM_OK; }
@@ -2817,7 +2813,7 @@ int refresh_group_vals(pfem_solver *s)
         // verdict.  A value the dictionary lacks -- new coefficients, a moved mesh -- and the full path takes over: the fp64 copy of
         // the group form re-packed from the row form, collection, sort, encode.
         s->vd_direct_pending = false;
-        const bool enabled = [] { const char *e = std::getenv("PFEM_SPMV_VALDICT"); return e ? std::atoi(e) != 0 : true; }();
+        const bool enabled = valdict_enabled();
         const VdState st = s->vd_direct_verdict;          // (read with the assembly's error word)
         if (enabled && !st.miss && !st.fail && s->use_rel() && s->vd_rows == kRelRows) {
             s->vd_ok = s->vd_current = true;
@@ -2855,7 +2851,7 @@ int refresh_group_vals_only(pfem_solver *s)
 // codes of the inverse diagonal for the Jacobi loop (DinvView), enqueued behind k_invert; nobody waits for the verdict
 int encode_dinv(pfem_solver *s, int64_t n)
 {
-    const bool enabled = [] { const char *e = std::getenv("PFEM_SPMV_VALDICT"); return e ? std::atoi(e) != 0 : true; }();
+    const bool enabled = valdict_enabled();
     s->dinv_codes = false;
     // (a matrix that repeats its values: so does its diagonal.  From 2^21 rows on: the encoding costs ~0.5 ms a solve -- the
     // one-workgroup sort of the dictionary most of it --, which 191 iterations at 100^3 do not earn back: 8.8 -> 10.0 ms there)
@@ -3770,6 +3766,13 @@ extern "C" int pfem_solver_comm_info(pfem_solver *s, int *n_peers, int64_t *doub
     return PFEM_OK;
 }
 
+// PFEM_MULTI_OVERLAP=0/1 overrides the exchange form the ranks vote on (agree_overlap); -1 when unset
+static int multi_overlap_env()
+{
+    const char *e = std::getenv("PFEM_MULTI_OVERLAP");
+    return e ? (std::atoi(e) != 0) : -1;
+}
+
 // What is actually carrying the multi-rank solve, as the transport itself reports it (bench.py prints this next to the
 // number): backend name ("rccl" / "host" / "none"), the rank count and device of the RCCL communicators (ncclCommCount,
 // ncclCommCuDevice; -1 for host hooks), the RCCL version, the device this solver runs on, and the form of the multi-rank
@@ -3789,8 +3792,8 @@ extern "C" int pfem_solver_comm_describe(pfem_solver *s, char *backend, int back
     if (backend_version) *backend_version = v;
     if (solver_device) *solver_device = s->device;
     if (overlapped_form) {
-        const char *e = std::getenv("PFEM_MULTI_OVERLAP");
-        *overlapped_form = e ? (std::atoi(e) != 0) : s->overlap_agreed;
+        const int o = multi_overlap_env();
+        *overlapped_form = o >= 0 ? o : s->overlap_agreed;
     }
     return PFEM_OK;
 }
@@ -4011,8 +4014,8 @@ inline bool want_single_reduction(const pfem_solver *s)
 int agree_overlap(pfem_solver *s, bool multi, bool *overlap)
 {
     *overlap = false;
-    const char *e = std::getenv("PFEM_MULTI_OVERLAP");
-    if (e) { *overlap = std::atoi(e) != 0; return PFEM_OK; }
+    const int forced = multi_overlap_env();
+    if (forced >= 0) { *overlap = forced != 0; return PFEM_OK; }
     if (!multi || s->nranks < 2 || !s->comm) return PFEM_OK;
     if (s->overlap_agreed < 0) {
         PFEM_TRY(ensure_comm_stream(s));
@@ -4029,6 +4032,23 @@ int agree_overlap(pfem_solver *s, bool multi, bool *overlap)
     return PFEM_OK;
 }
 
+// test knob PFEM_FORCE_MULTI: a single rank with a backend and an (empty) plan takes the multi-rank loop too
+inline bool force_multi() { return std::getenv("PFEM_FORCE_MULTI") != nullptr; }
+// PFEM_CG_GRAPH: 0 = no hipGraph replay of the iterations, 2 = replay whatever the size; read per solve
+inline int cg_graph_env()
+{
+    const char *e = std::getenv("PFEM_CG_GRAPH");
+    return e ? std::atoi(e) : 1;
+}
+// PFEM_CG_CHUNK: iterations enqueued between two reads of the control block; 0 when unset or not positive (each loop
+// has its own default)
+inline int cg_chunk_env()
+{
+    const char *e = std::getenv("PFEM_CG_CHUNK");
+    const int c = e ? std::atoi(e) : 0;
+    return c > 0 ? c : 0;
+}
+
 #include "pfem_amg.inc"
 
 int run_pcg(pfem_solver *s)
@@ -4037,8 +4057,7 @@ int run_pcg(pfem_solver *s)
     if (amg_in_effect(s)) return run_pcg_amg(s);
     if (want_single_reduction(s) && s->pc != PFEM_PC_NODE_BLOCK_JACOBI) return run_pcg_single(s);
     const int64_t n = s->n_loc;
-    // test knob PFEM_FORCE_MULTI: a single rank with a backend and an (empty) plan takes the multi-rank loop too
-    const bool multi = s->nranks > 1 || (s->comm && s->have_plan && std::getenv("PFEM_FORCE_MULTI"));
+    const bool multi = s->nranks > 1 || (s->comm && s->have_plan && force_multi());
     mark_group_vals(s);                    // the row form may have been re-assembled since the last solve
     PFEM_TRY(refresh_group_vals(s));
     // Two forms of the multi-rank iteration.  In order: whole SpMV, pack, exchange, all-reduce ... on the compute stream:
@@ -4186,7 +4205,7 @@ int run_pcg(pfem_solver *s)
     constexpr int64_t kGraphMaxRows = 1 << 18;
     bool use_graph = false;
     {
-        const int graph_env = [] { const char *e = std::getenv("PFEM_CG_GRAPH"); return e ? std::atoi(e) : 1; }();   // read per solve
+        const int graph_env = cg_graph_env();
         const bool sampled_ok = !s->profile_spmv || s->profile_every % kGraphIters == 0;
         if (graph_env && !s->cg_graph_off && !multi && !bpc && n > 0 && (n <= kGraphMaxRows || graph_env > 1) &&
             s->stream != nullptr && sampled_ok) {
@@ -4240,12 +4259,11 @@ int run_pcg(pfem_solver *s)
             use_graph = !s->cg_graph_off && s->cg_graph[0] && s->cg_graph[1];
         }
     }
-    const int chunk_env = [] { const char *e = std::getenv("PFEM_CG_CHUNK"); return e ? std::atoi(e) : 0; }();
     // test knob: dynamic LDS bytes added to the direction launches, so that only one or two of their blocks fit a CU
     // and most blocks START after the lead block has published its verdict (tests/test_gpu_parity.py: late blocks)
     const size_t dir_lds = [] { const char *e = std::getenv("PFEM_DEBUG_DIRECTION_LDS"); return e ? static_cast<size_t>(std::atol(e)) : 0; }();
     if (dir_lds) use_graph = false;
-    const int chunk = chunk_env > 0 ? chunk_env : 32;
+    const int chunk = cg_chunk_env() > 0 ? cg_chunk_env() : 32;
     size_t ev_used = 0, comm_used = 0;
     int it = 0;
     CgCtl h{};
@@ -4316,7 +4334,7 @@ int run_pcg(pfem_solver *s)
     constexpr int kMultiGraphIters = 4;
     bool use_mgraph = false;
     {
-        const int graph_env = [] { const char *e = std::getenv("PFEM_CG_GRAPH"); return e ? std::atoi(e) : 1; }();
+        const int graph_env = cg_graph_env();
         // Measured on MI355X / ROCm 7.2: a captured ncclAllReduce replays fine, a captured grouped ncclSend/ncclRecv
         // crashes the process (tools/probe_overlap.py, rank as its own neighbour).  So the graph is used by default only
         // when this rank has no neighbour to exchange with; PFEM_MULTI_GRAPH=1 forces it (RCCL builds that capture p2p).
@@ -4512,7 +4530,7 @@ int run_pcg(pfem_solver *s)
 int run_pcg_single(pfem_solver *s)
 {
     const int64_t n = s->n_loc;
-    const bool multi = s->nranks > 1 || (s->comm && s->have_plan && std::getenv("PFEM_FORCE_MULTI"));
+    const bool multi = s->nranks > 1 || (s->comm && s->have_plan && force_multi());
     mark_group_vals(s);
     PFEM_TRY(refresh_group_vals(s));
     bool overlap = false;
@@ -4570,7 +4588,7 @@ int run_pcg_single(pfem_solver *s)
     hipLaunchKernelGGL(k_cg_init, dim3(gv), block, 0, s->stream, n, s->n_owned, s->d_rhs.p, s->d_dinv.p, s->d_x.p, s->d_r.p, z, prz[0], pzz[0]);
     PFEM_TRY(check_kernel("k_cg_init"));
 
-    const int chunk = [] { const char *e = std::getenv("PFEM_CG_CHUNK"); const int c = e ? std::atoi(e) : 0; return c > 0 ? c : 32; }();
+    const int chunk = cg_chunk_env() > 0 ? cg_chunk_env() : 32;
     size_t ev_used = 0, comm_used = 0;
     double host_comm_s = 0.0;
     s->tm.graph_iterations = 0;
@@ -5205,7 +5223,3 @@ extern "C" int pfem_solver_amg_cycle(pfem_solver *s, int *cycle, int *last_level
     *last_level_visited_twice = M.cycle_gamma > 1 ? std::min(M.w_to, static_cast<int>(M.lev.size()) - 2) : 0;
     return PFEM_OK;
 }
-
-#ifdef PFEM_LAB
-#include "pfem_lab.inc"
-#endif
