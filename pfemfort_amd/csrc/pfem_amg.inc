@@ -913,7 +913,7 @@ int amg_couple_level(pfem_solver *s, AmgWork &W, AmgLevel &L, AmgLevel &C, bool 
         PFEM_TRY(b.alloc(Q.send_lidx.size()));
         s->d_send.swap(a);
         s->d_recv.swap(b);
-        s->mgraph_key.clear();             // (a captured Jacobi iteration points at the old buffers)
+        s->mgraph.invalidate();            // (a captured Jacobi iteration points at the old buffers)
     }
     std::vector<int32_t> sh_lidx, sh_ptr, sh_src;
     plan_unpack_lists(s->rank, static_cast<int>(Q.peers.size()), Q.peers.data(), Q.peer_off.data(), Q.send_lidx, sh_lidx, sh_ptr, sh_src);
@@ -2548,7 +2548,7 @@ int amg_symbolic(pfem_solver *s, bool multi, bool overlap)
     M.rbm = false;
     M.symbolic_ok = false;
     M.dense = false;
-    M.graph_key.clear();
+    M.graph.invalidate();
     {
         const int rc_size = s->stored > INT_MAX ? PFEM_ERR_ARG : PFEM_OK;
         if (rc_size != PFEM_OK) set_last_error("gamg: more than 2^31-1 stored matrix entries on one device");
@@ -3316,23 +3316,15 @@ int amg_cycle_shape(pfem_solver *s, Amg &M)
 int run_pcg_amg(pfem_solver *s)
 {
     const int64_t n = s->n_loc;
-    const bool multi = s->nranks > 1 || (s->comm && s->have_plan && force_multi());
+    const bool multi = cg_multi(s);
     mark_group_vals(s);
     PFEM_TRY(refresh_group_vals(s));
     bool overlap = false;
     PFEM_TRY(agree_overlap(s, multi, &overlap));
-    if (multi) {
-        if (!s->comm || !s->have_plan) {
-            set_last_error("a solver of a multi-rank run needs a communication backend (pfem_solver_set_comm_rccl / _host) "
-                           "and the neighbour plan (pfem_solver_set_neighbours) before the solve");
-            return PFEM_ERR_STATE;
-        }
-        PFEM_TRY(ensure_comm_stream(s));
-        PFEM_TRY(build_slice_lists(s));
-        if (!s->rhs_summed) {
-            PFEM_TRY(exchange_sum(s, s->d_rhs.p, overlap));
-            s->rhs_summed = true;
-        }
+    PFEM_TRY(cg_require_comm(s, multi));
+    if (multi && !s->rhs_summed) {
+        PFEM_TRY(exchange_sum(s, s->d_rhs.p, overlap));
+        s->rhs_summed = true;
     }
     bool did_symbolic = false;
     if (!s->amg || !s->amg->symbolic_ok) {
@@ -3368,12 +3360,7 @@ int run_pcg_amg(pfem_solver *s)
     double *part_pw = s->d_part_pw.p, *part_rz = s->d_part.p, *part_zz = s->d_part.p + kMaxGrid, *scal_pw = s->d_part.p + 2 * kMaxGrid;
     double *sbuf = s->d_sbuf.p;
     CgCtl *ctl = s->d_ctl.p;
-    if (s->hist_cap < s->maxits + 2) {
-        PFEM_TRY(s->d_hist.alloc(static_cast<size_t>(s->maxits) + 2));
-        s->hist_cap = s->maxits + 2;
-    }
-    PFEM_HIP(hipMemsetAsync(ctl, 0, sizeof(CgCtl), s->stream));
-    if (s->comm) s->comm->set_abort_word(&ctl->flag);          // (a device-side transport ends the solve through it when a wait fails)
+    PFEM_TRY(cg_reset_control(s, ctl));
     double host_comm_s = 0.0;
     // Two fusions of the cycle's ends with the CG's own vector kernels (iterations only; same arithmetic, same bits):
     // step 0 of the pre-smoothing on the assembled matrix rides on k_pc_update, and -- when the fine degree is 1 -- the one
@@ -3394,7 +3381,7 @@ int run_pcg_amg(pfem_solver *s)
         // the device -- lets the cycle ACROSS ranks be captured too: ~65 of an iteration's ~80 launches leave the host)
         const bool coupled_capturable = multi && M.coupled && !overlap && s->comm && s->comm->capturable() && s->comm->p2p_capturable() &&
                                         (!M.rep || M.n_last_global <= s->comm->allreduce_capture_limit());
-        if ((!multi || coupled_capturable) && graph_env && !M.graph_off && s->stream != nullptr) {
+        if ((!multi || coupled_capturable) && graph_env && s->stream != nullptr) {
             std::vector<uint64_t> key = {reinterpret_cast<uint64_t>(s->d_r.p), reinterpret_cast<uint64_t>(ctl), reinterpret_cast<uint64_t>(s->stream),
                                          reinterpret_cast<uint64_t>(s->d_vals.p), reinterpret_cast<uint64_t>(s->d_cols.p), reinterpret_cast<uint64_t>(s->d_rvals.p),
                                          reinterpret_cast<uint64_t>(s->d_gvals.p), reinterpret_cast<uint64_t>(s->d_dwords.p), spmv_key(s),
@@ -3410,34 +3397,17 @@ int run_pcg_amg(pfem_solver *s)
             };
             for (auto &L : M.lev) level_key(L);
             if (M.rep) for (auto &L : M.rep->lev) level_key(L);
-            if (key != M.graph_key || !M.graph) {
-                if (M.graph) { (void)hipGraphExecDestroy(M.graph); M.graph = nullptr; }
-                M.graph_key.clear();
-                PFEM_HIP(hipStreamSynchronize(s->stream));
-                hipGraph_t graph = nullptr;
-                bool ok = hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
-                if (ok) {
-                    if (M.coupled) ok = amg_apply_coupled(s, M, s->d_r.p, ctl, overlap) != nullptr;
-                    else (void)amg_apply(s, M, s->d_r.p, ctl, fuse_first0, fuse_last0);
-                    if (hipStreamEndCapture(s->stream, &graph) != hipSuccess || !graph) ok = false;
-                    if (ok && hipGraphInstantiate(&M.graph, graph, nullptr, nullptr, 0) != hipSuccess) ok = false;
-                    if (graph) (void)hipGraphDestroy(graph);
-                }
-                if (ok) {
-                    M.graph_key = key;
-                } else {            // not capturable here (e.g. a legacy default stream): stream launches from now on
-                    (void)hipGetLastError();
-                    if (M.graph) { (void)hipGraphExecDestroy(M.graph); M.graph = nullptr; }
-                    M.graph_off = true;
-                }
-            }
-            use_vgraph = !M.graph_off && M.graph != nullptr;
+            PFEM_TRY(M.graph.ensure(s->stream, std::move(key), {s->stream}, [&](int) {
+                if (M.coupled) return amg_apply_coupled(s, M, s->d_r.p, ctl, overlap) != nullptr;
+                (void)amg_apply(s, M, s->d_r.p, ctl, fuse_first0, fuse_last0);
+                return true;
+            }, &use_vgraph));
         }
     }
     // z = M^-1 r on every local dof: the V-cycle on the owned block, then (several ranks) the owners' values to the ghosts
     auto precondition = [&](const CgCtl *c) -> double * {
         if (use_vgraph && c == ctl) {
-            if (hipGraphLaunch(M.graph, s->stream) != hipSuccess) return nullptr;
+            if (hipGraphLaunch(M.graph.exec[0], s->stream) != hipSuccess) return nullptr;
             return M.lev[0]->x;
         }
         if (M.coupled) return amg_apply_coupled(s, M, s->d_r.p, c, overlap);      // z is the same on every holder already
@@ -3472,58 +3442,34 @@ int run_pcg_amg(pfem_solver *s)
     // (the replicated level's right-hand side) two per iteration instead of three.  One rank keeps the two-reduction loop (its
     // fused ends: the single-reduction form streams two more vectors).
     if (multi && M.coupled && want_single_reduction(s)) {
-        if (s->d_zg.store.n < static_cast<size_t>(n) + 2 * kVecGuard) {
-            PFEM_TRY(s->d_zg.store.alloc(static_cast<size_t>(n) + 2 * kVecGuard));
-            s->d_zg.p = s->d_zg.store.p + kVecGuard;
-        }
+        bool grown = false;
+        PFEM_TRY(ensure_guarded(s->d_zg, n, &grown));
         PFEM_HIP(hipMemsetAsync(s->d_zg.store.p, 0, (static_cast<size_t>(n) + 2 * kVecGuard) * sizeof(double), s->stream));
         if (s->d_sv.n < static_cast<size_t>(std::max<int64_t>(n, 1))) PFEM_TRY(s->d_sv.alloc(static_cast<size_t>(std::max<int64_t>(n, 1))));
         double *zg = s->d_zg.p, *sv = s->d_sv.p;
         hipLaunchKernelGGL(k_pc_init, dim3(gv), block, 0, s->stream, n, static_cast<const double *>(s->d_rhs.p), s->d_x.p, s->d_r.p);
-        const int chunk1 = 4;
-        int it = 0;
-        CgCtl h{};
-        s->tm.graph_iterations = 0;
-        s->tm.host_enqueue_ms = s->tm.host_comm_ms = 0.0;
-        s->tm.host_enqueued_iterations = 0;
-        for (;;) {
-            PFEM_HIP(hipMemcpyAsync(s->h_ctl, ctl, sizeof(CgCtl), hipMemcpyDeviceToHost, s->stream));
-            PFEM_HIP(hipStreamSynchronize(s->stream));
-            h = *s->h_ctl;
-            if (h.flag != 0) break;
-            const int it_end = std::min(it + chunk1, std::max(s->maxits, 0) + 1);      // step maxits only judges
-            if (it >= it_end) { h.flag = -3; break; }
-            const auto t_chunk = std::chrono::steady_clock::now();
-            const int it0 = it;
-            for (; it < it_end; ++it) {
-                double *zc = amg_apply_coupled(s, M, s->d_r.p, ctl, overlap);          // (every kernel leaves at once when the solve has finished)
-                if (!zc) return PFEM_ERR_COMM;
-                hipLaunchKernelGGL(k_pc_dots, dim3(gv), block, 0, s->stream, static_cast<const CgCtl *>(ctl), n, s->n_owned, static_cast<const double *>(s->d_r.p),
-                                   static_cast<const double *>(zc), part_rz, part_zz);
-                hipLaunchKernelGGL(k_pc_copy, dim3(gv), block, 0, s->stream, n, static_cast<const double *>(zc), zg);       // into the guarded SpMV input
-                PFEM_TRY(spmv_exchange(s, zg, sv, part_pw, gs, overlap, ctl, nullptr, nullptr, nullptr, nullptr, nullptr, &host_comm_s, [&](int nblocks) -> int {
-                    hipLaunchKernelGGL(k_reduce_partials3, dim3(1), dim3(1024), 0, s->stream, static_cast<const double *>(part_pw), nblocks,
-                                       static_cast<const double *>(part_rz), static_cast<const double *>(part_zz), static_cast<int>(gv), sbuf,
-                                       static_cast<const CgCtl *>(ctl));
-                    return 3;
-                }));
-                hipLaunchKernelGGL(k_pcg1_step, dim3(gv), block, 0, s->stream, ctl, it, n, static_cast<const double *>(sbuf), static_cast<const double *>(nullptr), 0,
-                                   static_cast<const double *>(nullptr), static_cast<const double *>(nullptr), 0, static_cast<const double *>(zg),
-                                   static_cast<const double *>(sv), s->d_p.p, s->d_w.p, s->d_x.p, s->d_r.p, s->rtol, s->abstol, s->dtol, s->d_hist.p,
-                                   s->hist_cap, s->maxits);
-            }
-            PFEM_TRY(check_kernel("gamg single-reduction pcg iteration"));
-            s->tm.host_enqueue_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_chunk).count();
-            s->tm.host_enqueued_iterations += it - it0;
-        }
-        s->tm.host_comm_ms = host_comm_s * 1e3;
-        s->last_its = h.its;
-        s->last_reason = (h.flag == 2 && h.rn <= s->abstol) ? 3 : h.flag;
-        s->last_rnorm = h.rn;
-        s->tm.spmv_ms_total = 0.0;
-        s->tm.spmv_launches = 0;
-        s->tm.iface_ms_total = s->tm.scalar_ms_total = s->tm.exposed_ms_total = 0.0;
-        s->tm.comm_samples = 0;
+        auto step1 = [&](int it, int, int *) -> int {
+            double *zc = amg_apply_coupled(s, M, s->d_r.p, ctl, overlap);          // (every kernel leaves at once when the solve has finished)
+            if (!zc) return PFEM_ERR_COMM;
+            hipLaunchKernelGGL(k_pc_dots, dim3(gv), block, 0, s->stream, static_cast<const CgCtl *>(ctl), n, s->n_owned, static_cast<const double *>(s->d_r.p),
+                               static_cast<const double *>(zc), part_rz, part_zz);
+            hipLaunchKernelGGL(k_pc_copy, dim3(gv), block, 0, s->stream, n, static_cast<const double *>(zc), zg);       // into the guarded SpMV input
+            PFEM_TRY(spmv_exchange(s, zg, sv, part_pw, gs, overlap, ctl, nullptr, nullptr, nullptr, nullptr, nullptr, &host_comm_s, [&](int nblocks) -> int {
+                hipLaunchKernelGGL(k_reduce_partials3, dim3(1), dim3(1024), 0, s->stream, static_cast<const double *>(part_pw), nblocks,
+                                   static_cast<const double *>(part_rz), static_cast<const double *>(part_zz), static_cast<int>(gv), sbuf,
+                                   static_cast<const CgCtl *>(ctl));
+                return 3;
+            }));
+            hipLaunchKernelGGL(k_pcg1_step, dim3(gv), block, 0, s->stream, ctl, it, n, static_cast<const double *>(sbuf), static_cast<const double *>(nullptr), 0,
+                               static_cast<const double *>(nullptr), static_cast<const double *>(nullptr), 0, static_cast<const double *>(zg),
+                               static_cast<const double *>(sv), s->d_p.p, s->d_w.p, s->d_x.p, s->d_r.p, s->rtol, s->abstol, s->dtol, s->d_hist.p,
+                               s->hist_cap, s->maxits);
+            return PFEM_OK;
+        };
+        // a fixed batch of 4 (step maxits only judges)
+        PFEM_TRY(cg_iterate(s, ctl, std::max(s->maxits, 0) + 1, host_comm_s, [](const CgCtl &) { return 4; }, step1,
+                            "gamg single-reduction pcg iteration"));
+        PFEM_TRY(CgSampler(s, multi).tally(overlap, s->last_its + 1, false));      // nothing sampled: zeroes the figures
         float fs = 0.f;
         PFEM_HIP(hipEventElapsedTime(&fs, ea, eb));
         M.numeric_ms = fs;
@@ -3545,122 +3491,54 @@ int run_pcg_amg(pfem_solver *s)
     // keep the fixed size (every rank must enqueue the same calls, and nothing may depend on a host's libm for that).
     const int chunk_env = cg_chunk_env();
     const int chunk = chunk_env > 0 ? chunk_env : 4;
-    size_t ev_used = 0, comm_used = 0;
-    const size_t ev_per = multi ? 4 : 2;
-    int it = 0;
-    CgCtl h{};
-    s->tm.graph_iterations = 0;
-    s->tm.host_enqueue_ms = s->tm.host_comm_ms = 0.0;
-    s->tm.host_enqueued_iterations = 0;
-    for (;;) {
-        PFEM_HIP(hipMemcpyAsync(s->h_ctl, ctl, sizeof(CgCtl), hipMemcpyDeviceToHost, s->stream));
-        PFEM_HIP(hipStreamSynchronize(s->stream));
-        h = *s->h_ctl;
-        if (h.flag != 0) break;
-        if (it >= s->maxits) { h.flag = -3; break; }
-        int batch = chunk;
+    auto batch = [&](const CgCtl &h) -> int {
         if (!multi && chunk_env == 0 && h.its >= chunk && h.rn > 0.0 && h.rn < h.rn0 && h.ttol > 0.0 && h.rn > h.ttol) {
             const double rate = std::pow(h.rn / h.rn0, 1.0 / h.its);         // mean contraction per iteration so far
             const double need = std::log(h.ttol / h.rn) / std::log(rate);
             // (three quarters of the estimate, at most 16: a CG that stalls and then drops -- the beam -- makes the estimate
             // overshoot near the end, and 60 iterations enqueued for nothing cost 7 ms there)
-            batch = need >= 1.0 ? std::min(16, std::max(1, static_cast<int>(std::ceil(0.75 * need)))) : 1;
+            return need >= 1.0 ? std::min(16, std::max(1, static_cast<int>(std::ceil(0.75 * need)))) : 1;
         }
-        const int it_end = std::min(it + batch, s->maxits);
-        const auto t_chunk = std::chrono::steady_clock::now();
-        const int it0 = it;
-        for (; it < it_end; ++it) {
-            hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr;
-            if (s->profile_spmv && it % s->profile_every == 0 && ev_used + ev_per <= 8192) {
-                while (s->spmv_events.size() < ev_used + ev_per) {
-                    hipEvent_t a;
-                    PFEM_HIP(hipEventCreate(&a));
-                    s->spmv_events.push_back(a);
-                }
-                e0 = s->spmv_events[ev_used];
-                e1 = s->spmv_events[ev_used + 1];
-                if (multi) { e2 = s->spmv_events[ev_used + 2]; e3 = s->spmv_events[ev_used + 3]; }
-                ev_used += ev_per;
-            }
-            const double *pw_parts = part_pw, *red_pw = nullptr;
-            int pw_n = static_cast<int>(gs);
-            hipEvent_t *cev = nullptr;
-            if (multi && e0 && comm_used + 8 <= 8192) {      // the sampled iterations also time the exchange and the all-reduces
-                while (s->comm_events.size() < comm_used + 8) {
-                    hipEvent_t e;
-                    PFEM_HIP(hipEventCreate(&e));
-                    s->comm_events.push_back(e);
-                }
-                cev = &s->comm_events[comm_used];
-                comm_used += 8;
-            }
-            if (multi) {
-                PFEM_TRY(spmv_exchange(s, s->d_p.p, s->d_w.p, part_pw, gs, overlap, ctl, e0, e1, e2, e3, cev, &host_comm_s, [&](int nblocks) -> int {
-                    hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, s->stream, static_cast<const double *>(part_pw),
-                                       static_cast<const double *>(nullptr), nblocks, sbuf, static_cast<const CgCtl *>(ctl));
-                    return 1;
-                }));
-                red_pw = sbuf;
-                pw_n = 0;
-            } else {
-                launch_spmv<true>(s, s->d_p.p, s->d_w.p, n, part_pw, ctl, e0, e1);
-                if (gs > kMaxGrid) {
-                    hipLaunchKernelGGL(k_fold_partials, dim3(kFoldBlocks), block, 0, s->stream, static_cast<const double *>(part_pw),
-                                       static_cast<int>(gs), scal_pw, static_cast<const CgCtl *>(ctl));
-                    pw_parts = scal_pw;
-                    pw_n = kFoldBlocks;
-                }
-            }
-            {
-                AmgLevel &L0 = *M.lev[0];
-                hipLaunchKernelGGL(k_pc_update, dim3(gv), block, 0, s->stream, ctl, it, n, pw_parts, pw_n, red_pw, static_cast<const double *>(s->d_p.p),
-                                   static_cast<const double *>(s->d_w.p), s->d_x.p, s->d_r.p, L0.n, static_cast<const double *>(L0.dinv.p),
-                                   static_cast<const double *>(L0.lam.p), M.eig_ratio, fuse_first0 ? L0.x : static_cast<double *>(nullptr),
-                                   (fuse_first0 && deg0 > 1) ? L0.dd : static_cast<double *>(nullptr));
-            }
-            z = precondition(ctl);
-            if (!z) return PFEM_ERR_COMM;
-            PFEM_TRY(dots(z, ctl, cev));
-            hipLaunchKernelGGL(k_cg_direction_b, dim3(gv), block, 0, s->stream, ctl, it, n, static_cast<const double *>(part_rz),
-                               static_cast<const double *>(part_zz), static_cast<int>(gv), red2, static_cast<const double *>(z), s->d_p.p,
-                               s->d_hist.p, s->hist_cap, s->maxits);
+        return chunk;
+    };
+    CgSampler sampler(s, multi);
+    auto step = [&](int it, int, int *) -> int {
+        hipEvent_t e[4] = {}, *cev = nullptr;
+        if (sampler.due(it)) {
+            PFEM_TRY(sampler.spmv(e));
+            PFEM_TRY(sampler.comm(&cev));        // the sampled iterations also time the exchange and the all-reduces
         }
-        PFEM_TRY(check_kernel("gamg pcg iteration"));
-        s->tm.host_enqueue_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_chunk).count();
-        s->tm.host_enqueued_iterations += it - it0;
-    }
-    s->tm.host_comm_ms = host_comm_s * 1e3;
-    s->last_its = h.its;
-    s->last_reason = (h.flag == 2 && h.rn <= s->abstol) ? 3 : h.flag;
-    s->last_rnorm = h.rn;
-    s->tm.spmv_ms_total = 0.0;
-    s->tm.spmv_launches = 0;
-    const size_t live = std::min(ev_used / ev_per, (static_cast<size_t>(h.its) + s->profile_every - 1) / s->profile_every);
-    for (size_t k = 0; k < live; ++k) {
-        for (size_t q = 0; q < ev_per; q += 2) {
-            const bool split = multi && overlap;
-            if (split && ((q == 0 && s->n_slices_b == 0) || (q == 2 && s->n_slices_i == 0))) continue;
-            if (multi && !split && q == 2) continue;
-            float f = 0.f;
-            PFEM_HIP(hipEventElapsedTime(&f, s->spmv_events[ev_per * k + q], s->spmv_events[ev_per * k + q + 1]));
-            s->tm.spmv_ms_total += f;
+        const double *pw_parts = part_pw, *red_pw = nullptr;
+        int pw_n = static_cast<int>(gs);
+        if (multi) {
+            PFEM_TRY(spmv_exchange(s, s->d_p.p, s->d_w.p, part_pw, gs, overlap, ctl, e[0], e[1], e[2], e[3], cev, &host_comm_s, [&](int nblocks) -> int {
+                hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, s->stream, static_cast<const double *>(part_pw),
+                                   static_cast<const double *>(nullptr), nblocks, sbuf, static_cast<const CgCtl *>(ctl));
+                return 1;
+            }));
+            red_pw = sbuf;
+            pw_n = 0;
+        } else {
+            launch_spmv<true>(s, s->d_p.p, s->d_w.p, n, part_pw, ctl, e[0], e[1]);
+            cg_fold(s, part_pw, gs, scal_pw, ctl, &pw_parts, &pw_n);
         }
-        ++s->tm.spmv_launches;
-    }
-    s->tm.iface_ms_total = s->tm.scalar_ms_total = s->tm.exposed_ms_total = 0.0;
-    s->tm.comm_samples = 0;
-    for (size_t k = 0; k < std::min(comm_used / 8, live); ++k) {     // same sampled iterations as the SpMV pairs (the SpMV's exchange)
-        hipEvent_t *c = &s->comm_events[8 * k];
-        float x = 0.f, a1 = 0.f, a2 = 0.f, w = 0.f;
-        PFEM_HIP(hipEventElapsedTime(&x, c[0], c[1]));
-        PFEM_HIP(hipEventElapsedTime(&a1, c[2], c[3]));
-        PFEM_HIP(hipEventElapsedTime(&a2, c[4], c[5]));
-        PFEM_HIP(hipEventElapsedTime(&w, c[6], c[7]));
-        s->tm.iface_ms_total += x;
-        s->tm.scalar_ms_total += a1 + a2;
-        s->tm.exposed_ms_total += w + a2;
-        ++s->tm.comm_samples;
-    }
+        {
+            AmgLevel &L0 = *M.lev[0];
+            hipLaunchKernelGGL(k_pc_update, dim3(gv), block, 0, s->stream, ctl, it, n, pw_parts, pw_n, red_pw, static_cast<const double *>(s->d_p.p),
+                               static_cast<const double *>(s->d_w.p), s->d_x.p, s->d_r.p, L0.n, static_cast<const double *>(L0.dinv.p),
+                               static_cast<const double *>(L0.lam.p), M.eig_ratio, fuse_first0 ? L0.x : static_cast<double *>(nullptr),
+                               (fuse_first0 && deg0 > 1) ? L0.dd : static_cast<double *>(nullptr));
+        }
+        z = precondition(ctl);
+        if (!z) return PFEM_ERR_COMM;
+        PFEM_TRY(dots(z, ctl, cev));
+        hipLaunchKernelGGL(k_cg_direction_b, dim3(gv), block, 0, s->stream, ctl, it, n, static_cast<const double *>(part_rz),
+                           static_cast<const double *>(part_zz), static_cast<int>(gv), red2, static_cast<const double *>(z), s->d_p.p,
+                           s->d_hist.p, s->hist_cap, s->maxits);
+        return PFEM_OK;
+    };
+    PFEM_TRY(cg_iterate(s, ctl, s->maxits, host_comm_s, batch, step, "gamg pcg iteration"));
+    PFEM_TRY(sampler.tally(overlap, s->last_its, true));
     float f = 0.f;
     PFEM_HIP(hipEventElapsedTime(&f, ea, eb));
     M.numeric_ms = f;

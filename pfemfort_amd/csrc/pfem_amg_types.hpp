@@ -126,13 +126,10 @@ struct Amg {
                                                      // (26 against 22 iterations): 1.5 is the robust middle for scalar problems; with
                                                      // 3 dofs per node 1.8 is the default (beam 205 -> 169 iterations, half-size beam 191 -> 155)
     // the V-cycle as a hipGraph (one rank): ~100 dependent launches, most of them on levels too small to fill the chip
-    hipGraphExec_t graph = nullptr;
-    std::vector<uint64_t> graph_key;
-    bool graph_off = false;
+    CgGraph graph;
     hipEvent_t ev_num0 = nullptr, ev_num1 = nullptr;   // around the numeric phase of a solve (created once)
     ~Amg()
     {
-        if (graph) (void)hipGraphExecDestroy(graph);
         if (ev_num0) (void)hipEventDestroy(ev_num0);
         if (ev_num1) (void)hipEventDestroy(ev_num1);
     }

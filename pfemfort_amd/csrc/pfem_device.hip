@@ -390,6 +390,60 @@ struct DevBuf {
 };
 inline void pool_trim(bool all) { dev_pool().trim(all); }
 
+// CG work captured once and replayed from a hipGraph while its key -- every pointer and size the captured launches
+// hold -- stays the same.  A capture the stream or the backend refuses turns the replay off until reset().
+struct CgGraph {
+    hipGraphExec_t exec[2] = {nullptr, nullptr};
+    int variants;                      // execs in use: captured, kept and dropped together
+    std::vector<uint64_t> key;
+    bool off = false;
+
+    explicit CgGraph(int variants = 1) : variants(variants) {}
+    CgGraph(const CgGraph &) = delete;
+    CgGraph &operator=(const CgGraph &) = delete;
+    ~CgGraph() { drop(); }
+    void drop()
+    {
+        for (auto &g : exec)
+            if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+        key.clear();
+    }
+    void invalidate() { key.clear(); }
+    void reset() { drop(); off = false; }
+    // Capture again on `stream` if the key changed (the streams in `quiesce` drained first); enqueue(variant) returns
+    // false when an enqueue failed.  *use: the execs may be launched.
+    template <class Enqueue>
+    int ensure(hipStream_t stream, std::vector<uint64_t> new_key, std::initializer_list<hipStream_t> quiesce, Enqueue enqueue, bool *use)
+    {
+        *use = false;
+        if (off) return PFEM_OK;
+        bool ok = new_key == key;
+        for (int v = 0; v < variants; ++v) ok = ok && exec[v];
+        if (!ok) {
+            drop();
+            for (hipStream_t q : quiesce) PFEM_HIP(hipStreamSynchronize(q));
+            ok = true;
+            for (int v = 0; v < variants && ok; ++v) {
+                hipGraph_t graph = nullptr;
+                if (hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal) != hipSuccess) { ok = false; break; }
+                ok = enqueue(v);
+                if (hipStreamEndCapture(stream, &graph) != hipSuccess || !graph) ok = false;
+                if (ok && hipGraphInstantiate(&exec[v], graph, nullptr, nullptr, 0) != hipSuccess) ok = false;
+                if (graph) (void)hipGraphDestroy(graph);
+            }
+            if (!ok) {          // not capturable here (e.g. a legacy default stream): stream launches from now on
+                (void)hipGetLastError();
+                drop();
+                off = true;
+                return PFEM_OK;
+            }
+            key = std::move(new_key);
+        }
+        *use = true;
+        return PFEM_OK;
+    }
+};
+
 #include "pfem_amg_types.hpp"
 
 constexpr size_t kMaxLdsBytes = 163840;       // LDS a single gfx950 workgroup may declare (MI355X_MICROARCH.md)
@@ -689,13 +743,9 @@ struct pfem_solver {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // hipGraph replay of the CG iteration (single rank, point Jacobi): units of kGraphIters iterations;
     // [0] = full iterations, [1] = the first SpMV left out (it is launched with its event pair on the stream)
-    hipGraphExec_t cg_graph[2] = {nullptr, nullptr};
-    std::vector<uint64_t> cg_graph_key;
-    bool cg_graph_off = false;
+    CgGraph cg_graph{2};
     // multi-rank: kMultiGraphIters iterations (both streams, the RCCL calls included) as one graph
-    hipGraphExec_t mgraph = nullptr;
-    std::vector<uint64_t> mgraph_key;
-    bool mgraph_off = false;
+    CgGraph mgraph;
     bool profile_spmv = false;
     int profile_every = 1;         // event pair around every profile_every-th SpMV launch of a solve
     std::vector<hipEvent_t> spmv_events;
@@ -798,7 +848,7 @@ extern "C" int pfem_solver_destroy(pfem_solver *s)
     for (hipEvent_t e : s->spmv_events) (void)hipEventDestroy(e);
     for (hipEvent_t e : s->comm_events) (void)hipEventDestroy(e);
     if (s->comm_stream) (void)hipStreamSynchronize(s->comm_stream);
-    if (s->mgraph) { (void)hipGraphExecDestroy(s->mgraph); s->mgraph = nullptr; }   // holds captured RCCL launches
+    s->mgraph.drop();          // holds captured RCCL launches
     delete s->comm;            // before the streams go: an RCCL communicator is destroyed here
     s->comm = nullptr;
     for (hipEvent_t e : s->xev) (void)hipEventDestroy(e);
@@ -807,8 +857,7 @@ extern "C" int pfem_solver_destroy(pfem_solver *s)
     if (s->ev1) (void)hipEventDestroy(s->ev1);
     if (s->h_ctl) (void)hipHostFree(s->h_ctl);
     if (s->h_err) (void)hipHostFree(s->h_err);
-    for (auto &g : s->cg_graph)
-        if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+    s->cg_graph.drop();
     if (s->own_stream && s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
     pool_trim(true);             // the solver's buffers really go back to the device
@@ -824,10 +873,8 @@ extern "C" int pfem_solver_set_stream(pfem_solver *s, void *hip_stream)
     // adopt the caller's stream as is; a null handle IS a stream (the legacy default stream,
     // which is what torch.cuda.current_stream() is unless the caller switched streams)
     s->stream = static_cast<hipStream_t>(hip_stream);
-    s->cg_graph_key.clear();
-    s->cg_graph_off = false;
-    s->mgraph_key.clear();
-    s->mgraph_off = false;
+    s->cg_graph.reset();
+    s->mgraph.reset();
     return PFEM_OK;
 }
 
@@ -1561,8 +1608,8 @@ int pattern_from_keys(pfem_solver *s, DevBuf<uint64_t> &keys, int64_t nkeys)
         return PFEM_ERR_ARG;
     }
     const int64_t n = s->n_loc;
-    s->cg_graph_key.clear();               // every array a captured CG iteration points at is about to be replaced
-    s->mgraph_key.clear();
+    s->cg_graph.invalidate();              // every array a captured CG iteration points at is about to be replaced
+    s->mgraph.invalidate();
     s->slices_fmt = -1;                    // ... and the boundary / interior slice lists belong to the old pattern
     if (s->amg) { s->amg->symbolic_ok = false; s->amg->coupled_refused = false; }   // ... and so does the multigrid hierarchy
     PFEM_TRY(use_sort_bits(s));
@@ -1869,8 +1916,8 @@ int pattern_from_incidence(pfem_solver *s, bool *done)
         PFEM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pattern_rows<false>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
         PFEM_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pattern_rows<true>), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
     }
-    s->cg_graph_key.clear();               // (as pattern_from_keys: everything that points at the old pattern goes)
-    s->mgraph_key.clear();
+    s->cg_graph.invalidate();              // (as pattern_from_keys: everything that points at the old pattern goes)
+    s->mgraph.invalidate();
     s->slices_fmt = -1;
     if (s->amg) { s->amg->symbolic_ok = false; s->amg->coupled_refused = false; }
     PFEM_TRY(use_sort_bits(s));
@@ -3480,9 +3527,7 @@ int ensure_comm_stream(pfem_solver *s)
 
 int install_backend(pfem_solver *s, int rank, int nranks, CommBackend *b)
 {
-    if (s->mgraph) { (void)hipGraphExecDestroy(s->mgraph); s->mgraph = nullptr; }
-    s->mgraph_key.clear();
-    s->mgraph_off = false;
+    s->mgraph.reset();
     if (s->comm) {      // nothing of the previous backend may still be in flight when its communicators go
         if (s->stream) (void)hipStreamSynchronize(s->stream);
         if (s->comm_stream) (void)hipStreamSynchronize(s->comm_stream);
@@ -4049,6 +4094,187 @@ inline int cg_chunk_env()
     return c > 0 ? c : 0;
 }
 
+// ---- what the CG loops (run_pcg, run_pcg_single, run_pcg_amg) share ----------------------------------------------------
+inline bool cg_multi(const pfem_solver *s) { return s->nranks > 1 || (s->comm && s->have_plan && force_multi()); }
+
+int cg_require_comm(pfem_solver *s, bool multi)
+{
+    if (!multi) return PFEM_OK;
+    if (!s->comm || !s->have_plan) {
+        set_last_error("a solver of a multi-rank run needs a communication backend (pfem_solver_set_comm_rccl / _host) "
+                       "and the neighbour plan (pfem_solver_set_neighbours) before the solve");
+        return PFEM_ERR_STATE;
+    }
+    PFEM_TRY(ensure_comm_stream(s));
+    return build_slice_lists(s);
+}
+
+int cg_reset_control(pfem_solver *s, CgCtl *ctl)
+{
+    if (s->hist_cap < s->maxits + 2) {
+        PFEM_TRY(s->d_hist.alloc(static_cast<size_t>(s->maxits) + 2));
+        s->hist_cap = s->maxits + 2;
+    }
+    PFEM_HIP(hipMemsetAsync(ctl, 0, sizeof(CgCtl), s->stream));
+    if (s->comm) s->comm->set_abort_word(&ctl->flag);          // (a device-side transport ends the solve through it when a wait fails)
+    return PFEM_OK;
+}
+
+// the SpMV's (p,Ap) partials as the update kernel takes them: too many blocks for every consumer block to re-sum are
+// folded to kFoldBlocks first
+void cg_fold(pfem_solver *s, const double *part_pw, unsigned gs, double *scal_pw, const CgCtl *ctl, const double **parts, int *nparts)
+{
+    *parts = part_pw;
+    *nparts = static_cast<int>(gs);
+    if (gs > kMaxGrid) {
+        hipLaunchKernelGGL(k_fold_partials, dim3(kFoldBlocks), dim3(kBlock), 0, s->stream, part_pw, static_cast<int>(gs), scal_pw, ctl);
+        *parts = scal_pw;
+        *nparts = kFoldBlocks;
+    }
+}
+
+// point Jacobi: dinv = 1 / diag(A); interface diagonals and rhs are summed over the ranks
+int cg_point_jacobi(pfem_solver *s, bool multi, bool overlap)
+{
+    const int64_t n = s->n_loc;
+    if (n > 0) {
+        hipLaunchKernelGGL(k_extract_diag, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, s->sell(), s->d_dinv.p);
+        PFEM_TRY(check_kernel("k_extract_diag"));
+    }
+    if (multi) {
+        PFEM_TRY(exchange_sum(s, s->d_dinv.p, overlap));
+        if (!s->rhs_summed) {
+            PFEM_TRY(exchange_sum(s, s->d_rhs.p, overlap));
+            s->rhs_summed = true;
+        }
+    }
+    if (n > 0) {
+        hipLaunchKernelGGL(k_invert, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, s->d_dinv.p, n);
+        PFEM_TRY(check_kernel("k_invert"));
+    }
+    return PFEM_OK;
+}
+
+// room for n rows and the guard bands on both sides; *grown: new storage (its zeros are the caller's to write)
+int ensure_guarded(pfem_solver::GuardedVec &g, int64_t n, bool *grown)
+{
+    *grown = g.store.n < static_cast<size_t>(n) + 2 * kVecGuard;
+    if (*grown) {
+        PFEM_TRY(g.store.alloc(static_cast<size_t>(n) + 2 * kVecGuard));
+        g.p = g.store.p + kVecGuard;
+    }
+    return PFEM_OK;
+}
+
+// Sampled timing of a solve (pfem_solver_profile_spmv): every profile_every-th iteration times its SpMV with an event
+// pair (several ranks: one pair for the boundary pass, one for the interior pass) and, on several ranks, the exchange
+// and the all-reduces with 8 events more (cev: [0,1] exchange, [2,3] first all-reduce, [4,5] second, [6,7] exposed wait).
+struct CgSampler {
+    pfem_solver *s;
+    bool multi;
+    size_t ev_per, ev_used = 0, comm_used = 0;
+    CgSampler(pfem_solver *s, bool multi) : s(s), multi(multi), ev_per(multi ? 4 : 2) {}
+
+    bool due(int it) const { return s->profile_spmv && it % s->profile_every == 0 && ev_used + ev_per <= 8192; }
+    // the SpMV events of a sampled iteration
+    int spmv(hipEvent_t e[4])
+    {
+        while (s->spmv_events.size() < ev_used + ev_per) {
+            hipEvent_t a;
+            PFEM_HIP(hipEventCreate(&a));
+            s->spmv_events.push_back(a);
+        }
+        for (size_t q = 0; q < ev_per; ++q) e[q] = s->spmv_events[ev_used + q];
+        ev_used += ev_per;
+        return PFEM_OK;
+    }
+    // the communication events of a sampled iteration (null on one rank or when they ran out)
+    int comm(hipEvent_t **cev)
+    {
+        *cev = nullptr;
+        if (!multi || comm_used + 8 > 8192) return PFEM_OK;
+        while (s->comm_events.size() < comm_used + 8) {
+            hipEvent_t e;
+            PFEM_HIP(hipEventCreate(&e));
+            s->comm_events.push_back(e);
+        }
+        *cev = &s->comm_events[comm_used];
+        comm_used += 8;
+        return PFEM_OK;
+    }
+    // into s->tm.  judged: the steps that did work (the tail of the last chunk exits at the flag test; the k-th sample
+    // belongs to step k * profile_every).  second_allreduce: cev[4] -> cev[5] spans an all-reduce between two dependent
+    // kernels, fully exposed
+    int tally(bool overlap, int judged, bool second_allreduce)
+    {
+        s->tm.spmv_ms_total = 0.0;
+        s->tm.spmv_launches = 0;
+        const size_t live = std::min(ev_used / ev_per, (static_cast<size_t>(judged) + s->profile_every - 1) / s->profile_every);
+        for (size_t k = 0; k < live; ++k) {
+            for (size_t q = 0; q < ev_per; q += 2) {
+                const bool split = multi && overlap;                   // boundary + interior pass, one event pair each
+                if (split && ((q == 0 && s->n_slices_b == 0) || (q == 2 && s->n_slices_i == 0))) continue;   // pass not launched
+                if (multi && !split && q == 2) continue;               // one pass over all slices
+                float f = 0.f;
+                PFEM_HIP(hipEventElapsedTime(&f, s->spmv_events[ev_per * k + q], s->spmv_events[ev_per * k + q + 1]));
+                s->tm.spmv_ms_total += f;
+            }
+            ++s->tm.spmv_launches;
+        }
+        s->tm.iface_ms_total = s->tm.scalar_ms_total = s->tm.exposed_ms_total = 0.0;
+        s->tm.comm_samples = 0;
+        for (size_t k = 0; k < std::min(comm_used / 8, live); ++k) {     // same sampled iterations as the SpMV pairs
+            hipEvent_t *c = &s->comm_events[8 * k];
+            float x = 0.f, a1 = 0.f, a2 = 0.f, w = 0.f;
+            PFEM_HIP(hipEventElapsedTime(&x, c[0], c[1]));
+            PFEM_HIP(hipEventElapsedTime(&a1, c[2], c[3]));
+            if (second_allreduce) PFEM_HIP(hipEventElapsedTime(&a2, c[4], c[5]));
+            PFEM_HIP(hipEventElapsedTime(&w, c[6], c[7]));
+            s->tm.iface_ms_total += x;
+            s->tm.scalar_ms_total += a1 + a2;
+            s->tm.exposed_ms_total += w + a2;
+            ++s->tm.comm_samples;
+        }
+        return PFEM_OK;
+    }
+};
+
+// The control loop of a solve: read the control block, stop on its flag or at step `last`, else enqueue batch(h) steps
+// more.  body(it, it_end, &k) enqueues from step `it` and sets k when it enqueued more than one step (a graph unit).
+// Ends with the solve's result in last_its / last_reason / last_rnorm and host_comm_s in the timings.
+template <class Batch, class Body>
+int cg_iterate(pfem_solver *s, const CgCtl *ctl, int last, const double &host_comm_s, Batch batch, Body body, const char *what)
+{
+    s->tm.graph_iterations = 0;
+    s->tm.host_enqueue_ms = s->tm.host_comm_ms = 0.0;
+    s->tm.host_enqueued_iterations = 0;
+    CgCtl h{};
+    for (int it = 0;;) {
+        PFEM_HIP(hipMemcpyAsync(s->h_ctl, ctl, sizeof(CgCtl), hipMemcpyDeviceToHost, s->stream));
+        PFEM_HIP(hipStreamSynchronize(s->stream));
+        h = *s->h_ctl;
+        if (h.flag != 0) break;
+        if (it >= last) { h.flag = -3; break; }
+        const int it_end = std::min(it + batch(h), last);
+        const auto t_chunk = std::chrono::steady_clock::now();
+        const int it_chunk0 = it;
+        while (it < it_end) {
+            int k = 1;
+            PFEM_TRY(body(it, it_end, &k));
+            if (k > 1) s->tm.graph_iterations += k;
+            it += k;
+        }
+        PFEM_TRY(check_kernel(what));
+        s->tm.host_enqueue_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_chunk).count();
+        s->tm.host_enqueued_iterations += it - it_chunk0;
+    }
+    s->tm.host_comm_ms = host_comm_s * 1e3;
+    s->last_its = h.its;
+    s->last_reason = (h.flag == 2 && h.rn <= s->abstol) ? 3 : h.flag;
+    s->last_rnorm = h.rn;
+    return PFEM_OK;
+}
+
 #include "pfem_amg.inc"
 
 int run_pcg(pfem_solver *s)
@@ -4057,7 +4283,7 @@ int run_pcg(pfem_solver *s)
     if (amg_in_effect(s)) return run_pcg_amg(s);
     if (want_single_reduction(s) && s->pc != PFEM_PC_NODE_BLOCK_JACOBI) return run_pcg_single(s);
     const int64_t n = s->n_loc;
-    const bool multi = s->nranks > 1 || (s->comm && s->have_plan && force_multi());
+    const bool multi = cg_multi(s);
     mark_group_vals(s);                    // the row form may have been re-assembled since the last solve
     PFEM_TRY(refresh_group_vals(s));
     // Two forms of the multi-rank iteration.  In order: whole SpMV, pack, exchange, all-reduce ... on the compute stream:
@@ -4081,15 +4307,7 @@ int run_pcg(pfem_solver *s)
     double *part_pw = s->d_part_pw.p, *part_rz = s->d_part.p, *part_zz = s->d_part.p + kMaxGrid;
     double *scal_pw = s->d_part.p + 2 * kMaxGrid;      // (p,Ap) reduced by k_reduce_partials
     CgCtl *ctl = s->d_ctl.p;
-    if (multi) {
-        if (!s->comm || !s->have_plan) {
-            set_last_error("a solver of a multi-rank run needs a communication backend (pfem_solver_set_comm_rccl / _host) "
-                           "and the neighbour plan (pfem_solver_set_neighbours) before the solve");
-            return PFEM_ERR_STATE;
-        }
-        PFEM_TRY(ensure_comm_stream(s));
-        PFEM_TRY(build_slice_lists(s));
-    }
+    PFEM_TRY(cg_require_comm(s, multi));
     double *sbuf = s->d_sbuf.p;                        // multi: [ (p,Ap) | - | (r,z) | (z,z) ] summed over the ranks
     // two partial arrays -> sbuf[at], sbuf[at+1] (one block, fixed order), then the all-reduce over the ranks
     auto reduce_scalars = [&](const double *p0, const double *p1, int np, int at, int cnt, const CgCtl *c) -> int {
@@ -4097,12 +4315,7 @@ int run_pcg(pfem_solver *s)
         PFEM_TRY(check_kernel("k_reduce_partials"));
         return scalar_allreduce(s, at, cnt);
     };
-    if (s->hist_cap < s->maxits + 2) {
-        PFEM_TRY(s->d_hist.alloc(static_cast<size_t>(s->maxits) + 2));
-        s->hist_cap = s->maxits + 2;
-    }
-    PFEM_HIP(hipMemsetAsync(ctl, 0, sizeof(CgCtl), s->stream));
-    if (s->comm) s->comm->set_abort_word(&ctl->flag);          // (a device-side transport ends the solve through it when a wait fails)
+    PFEM_TRY(cg_reset_control(s, ctl));
 
     const int32_t *grow0 = s->d_group_row0.p;
     s->block_pc_ok = true;
@@ -4164,22 +4377,7 @@ int run_pcg(pfem_solver *s)
                            s->d_rhs.p, s->d_binv[0].p, s->d_binv[1].p, s->d_binv[2].p, s->d_x.p, s->d_r.p, s->d_p.p, part_rz, part_zz);
         PFEM_TRY(check_kernel("k_cg_init_b"));
     } else {
-    // Jacobi: dinv = 1 / diag(A); interface diagonals and rhs are summed over the ranks
-    if (n > 0) {
-        hipLaunchKernelGGL(k_extract_diag, dim3(grid_for(n)), block, 0, s->stream, A, s->d_dinv.p);
-        PFEM_TRY(check_kernel("k_extract_diag"));
-    }
-    if (multi) {
-        PFEM_TRY(exchange_sum(s, s->d_dinv.p, overlap));
-        if (!s->rhs_summed) {
-            PFEM_TRY(exchange_sum(s, s->d_rhs.p, overlap));
-            s->rhs_summed = true;
-        }
-    }
-    if (n > 0) {
-        hipLaunchKernelGGL(k_invert, dim3(grid_for(n)), block, 0, s->stream, s->d_dinv.p, n);
-        PFEM_TRY(check_kernel("k_invert"));
-    }
+    PFEM_TRY(cg_point_jacobi(s, multi, overlap));
     PFEM_TRY(encode_dinv(s, n));
 
     hipLaunchKernelGGL(k_cg_init, dim3(gv), block, 0, s->stream, n, s->n_owned, s->d_rhs.p, s->d_dinv.p, s->d_x.p, s->d_r.p,
@@ -4203,60 +4401,37 @@ int run_pcg(pfem_solver *s)
     // The iteration index travels in the control block for replayed launches (it_arg = -1).
     constexpr int kGraphIters = 8;
     constexpr int64_t kGraphMaxRows = 1 << 18;
+    // what every captured iteration holds (a graph's key adds what its own launches hold)
+    const std::vector<uint64_t> iteration_key = {
+        reinterpret_cast<uint64_t>(s->d_p.p), reinterpret_cast<uint64_t>(s->d_w.p), reinterpret_cast<uint64_t>(s->d_r.p),
+        reinterpret_cast<uint64_t>(s->d_x.p), reinterpret_cast<uint64_t>(s->d_dinv.p), reinterpret_cast<uint64_t>(s->d_part.p),
+        reinterpret_cast<uint64_t>(s->d_part_pw.p), reinterpret_cast<uint64_t>(ctl), reinterpret_cast<uint64_t>(s->d_hist.p),
+        reinterpret_cast<uint64_t>(s->d_vals.p), reinterpret_cast<uint64_t>(s->d_cols.p), reinterpret_cast<uint64_t>(s->d_rvals.p),
+        reinterpret_cast<uint64_t>(s->d_gvals.p), reinterpret_cast<uint64_t>(s->d_dwords.p), reinterpret_cast<uint64_t>(s->stream),
+        static_cast<uint64_t>(s->hist_cap), static_cast<uint64_t>(s->maxits), static_cast<uint64_t>(n),
+        static_cast<uint64_t>(s->n_owned), static_cast<uint64_t>(gv), spmv_key(s)};
     bool use_graph = false;
     {
         const int graph_env = cg_graph_env();
         const bool sampled_ok = !s->profile_spmv || s->profile_every % kGraphIters == 0;
-        if (graph_env && !s->cg_graph_off && !multi && !bpc && n > 0 && (n <= kGraphMaxRows || graph_env > 1) &&
-            s->stream != nullptr && sampled_ok) {
-            const int fmt = spmv_form(s);
-            const std::vector<uint64_t> key = {
-                reinterpret_cast<uint64_t>(s->d_p.p), reinterpret_cast<uint64_t>(s->d_w.p), reinterpret_cast<uint64_t>(s->d_r.p),
-                reinterpret_cast<uint64_t>(s->d_x.p), reinterpret_cast<uint64_t>(s->d_dinv.p), reinterpret_cast<uint64_t>(s->d_part.p),
-                reinterpret_cast<uint64_t>(s->d_part_pw.p), reinterpret_cast<uint64_t>(ctl), reinterpret_cast<uint64_t>(s->d_hist.p),
-                reinterpret_cast<uint64_t>(s->d_vals.p), reinterpret_cast<uint64_t>(s->d_cols.p), reinterpret_cast<uint64_t>(s->d_rvals.p),
-                reinterpret_cast<uint64_t>(s->d_gvals.p), reinterpret_cast<uint64_t>(s->d_dwords.p), reinterpret_cast<uint64_t>(s->stream),
-                static_cast<uint64_t>(s->hist_cap), static_cast<uint64_t>(s->maxits), static_cast<uint64_t>(n),
-                static_cast<uint64_t>(s->n_owned), static_cast<uint64_t>(gs), static_cast<uint64_t>(gv), static_cast<uint64_t>(fmt), spmv_key(s)};
-            if (key != s->cg_graph_key || !s->cg_graph[0] || !s->cg_graph[1]) {
-                for (auto &g : s->cg_graph)
-                    if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
-                s->cg_graph_key.clear();
-                bool ok = true;
-                for (int variant = 0; variant < 2 && ok; ++variant) {
-                    hipGraph_t graph = nullptr;
-                    if (hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) { ok = false; break; }
-                    for (int k = 0; k < kGraphIters; ++k) {
-                        if (!(variant == 1 && k == 0)) launch_spmv<true>(s, s->d_p.p, s->d_w.p, n, part_pw, ctl);
-                        const double *pw_parts = part_pw;
-                        int pw_n = static_cast<int>(gs);
-                        if (gs > kMaxGrid) {
-                            hipLaunchKernelGGL(k_fold_partials, dim3(kFoldBlocks), block, 0, s->stream, static_cast<const double *>(part_pw),
-                                               static_cast<int>(gs), scal_pw, static_cast<const CgCtl *>(ctl));
-                            pw_parts = scal_pw;
-                            pw_n = kFoldBlocks;
-                        }
-                        hipLaunchKernelGGL(k_cg_update, dim3(gv), block, 0, s->stream, ctl, -1, n, s->n_owned, pw_parts, pw_n,
-                                           static_cast<const double *>(nullptr), s->d_p.p, s->d_w.p, s->dinv_view(), s->d_x.p, s->d_r.p,
-                                           part_rz, part_zz);
-                        hipLaunchKernelGGL(k_cg_direction, dim3(gv), block, 0, s->stream, ctl, -1, n, part_rz, part_zz,
-                                           static_cast<int>(gv), static_cast<const double *>(nullptr), s->d_r.p, s->dinv_view(), s->d_p.p,
-                                           s->d_hist.p, s->hist_cap, s->maxits, s->d_x.p);
-                    }
-                    if (hipStreamEndCapture(s->stream, &graph) != hipSuccess || !graph) { ok = false; break; }
-                    if (hipGraphInstantiate(&s->cg_graph[variant], graph, nullptr, nullptr, 0) != hipSuccess) ok = false;
-                    (void)hipGraphDestroy(graph);
+        if (graph_env && !multi && !bpc && n > 0 && (n <= kGraphMaxRows || graph_env > 1) && s->stream != nullptr && sampled_ok) {
+            std::vector<uint64_t> key = iteration_key;
+            key.insert(key.end(), {static_cast<uint64_t>(gs), static_cast<uint64_t>(spmv_form(s))});
+            PFEM_TRY(s->cg_graph.ensure(s->stream, std::move(key), {}, [&](int variant) {
+                for (int k = 0; k < kGraphIters; ++k) {
+                    if (!(variant == 1 && k == 0)) launch_spmv<true>(s, s->d_p.p, s->d_w.p, n, part_pw, ctl);
+                    const double *pw_parts;
+                    int pw_n;
+                    cg_fold(s, part_pw, gs, scal_pw, ctl, &pw_parts, &pw_n);
+                    hipLaunchKernelGGL(k_cg_update, dim3(gv), block, 0, s->stream, ctl, -1, n, s->n_owned, pw_parts, pw_n,
+                                       static_cast<const double *>(nullptr), s->d_p.p, s->d_w.p, s->dinv_view(), s->d_x.p, s->d_r.p,
+                                       part_rz, part_zz);
+                    hipLaunchKernelGGL(k_cg_direction, dim3(gv), block, 0, s->stream, ctl, -1, n, part_rz, part_zz,
+                                       static_cast<int>(gv), static_cast<const double *>(nullptr), s->d_r.p, s->dinv_view(), s->d_p.p,
+                                       s->d_hist.p, s->hist_cap, s->maxits, s->d_x.p);
                 }
-                if (ok) {
-                    s->cg_graph_key = key;
-                } else {        // not capturable here (e.g. a legacy default stream): stream launches from now on
-                    (void)hipGetLastError();
-                    for (auto &g : s->cg_graph)
-                        if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
-                    s->cg_graph_off = true;
-                }
-            }
-            use_graph = !s->cg_graph_off && s->cg_graph[0] && s->cg_graph[1];
+                return true;
+            }, &use_graph));
         }
     }
     // test knob: dynamic LDS bytes added to the direction launches, so that only one or two of their blocks fit a CU
@@ -4264,9 +4439,6 @@ int run_pcg(pfem_solver *s)
     const size_t dir_lds = [] { const char *e = std::getenv("PFEM_DEBUG_DIRECTION_LDS"); return e ? static_cast<size_t>(std::atol(e)) : 0; }();
     if (dir_lds) use_graph = false;
     const int chunk = cg_chunk_env() > 0 ? cg_chunk_env() : 32;
-    size_t ev_used = 0, comm_used = 0;
-    int it = 0;
-    CgCtl h{};
     if (s->profile_spmv && s->tm.event_overhead_ms == 0.0) {
         // Calibrate the measurement: a start/stop event pair reports marker-end -> kernel-end, i.e.
         // the kernel plus the marker-to-dispatch gap.  Time an EMPTY kernel the same way (minimum
@@ -4339,185 +4511,83 @@ int run_pcg(pfem_solver *s)
         // crashes the process (tools/probe_overlap.py, rank as its own neighbour).  So the graph is used by default only
         // when this rank has no neighbour to exchange with; PFEM_MULTI_GRAPH=1 forces it (RCCL builds that capture p2p).
         const bool p2p_ok = s->peers.empty() || std::getenv("PFEM_MULTI_GRAPH") != nullptr;
-        if (multi && !bpc && graph_env && p2p_ok && !dir_lds && !s->mgraph_off && s->comm->capturable() && s->stream != nullptr) {
-            const std::vector<uint64_t> key = {
-                reinterpret_cast<uint64_t>(s->d_p.p), reinterpret_cast<uint64_t>(s->d_w.p), reinterpret_cast<uint64_t>(s->d_r.p),
-                reinterpret_cast<uint64_t>(s->d_x.p), reinterpret_cast<uint64_t>(s->d_dinv.p), reinterpret_cast<uint64_t>(s->d_part.p),
-                reinterpret_cast<uint64_t>(s->d_part_pw.p), reinterpret_cast<uint64_t>(ctl), reinterpret_cast<uint64_t>(s->d_hist.p),
-                reinterpret_cast<uint64_t>(s->d_vals.p), reinterpret_cast<uint64_t>(s->d_cols.p), reinterpret_cast<uint64_t>(s->d_rvals.p),
-                reinterpret_cast<uint64_t>(s->d_gvals.p), reinterpret_cast<uint64_t>(s->d_dwords.p), reinterpret_cast<uint64_t>(s->stream),
+        if (multi && !bpc && graph_env && p2p_ok && !dir_lds && s->comm->capturable() && s->stream != nullptr) {
+            std::vector<uint64_t> key = iteration_key;
+            key.insert(key.end(), {
                 reinterpret_cast<uint64_t>(s->comm_stream), reinterpret_cast<uint64_t>(s->comm), reinterpret_cast<uint64_t>(s->d_send.p),
                 reinterpret_cast<uint64_t>(s->d_recv.p), reinterpret_cast<uint64_t>(sbuf), reinterpret_cast<uint64_t>(s->d_slices_b.p),
                 reinterpret_cast<uint64_t>(s->d_slices_i.p), reinterpret_cast<uint64_t>(s->d_send_lidx.p), reinterpret_cast<uint64_t>(s->d_sh_src.p),
-                static_cast<uint64_t>(s->hist_cap), static_cast<uint64_t>(s->maxits), static_cast<uint64_t>(n), static_cast<uint64_t>(s->n_owned),
                 static_cast<uint64_t>(s->n_send), static_cast<uint64_t>(s->n_sh), static_cast<uint64_t>(s->n_slices_b),
-                static_cast<uint64_t>(s->n_slices_i), static_cast<uint64_t>(gv), spmv_key(s)};
-            if (key != s->mgraph_key || !s->mgraph) {
-                if (s->mgraph) { (void)hipGraphExecDestroy(s->mgraph); s->mgraph = nullptr; }
-                s->mgraph_key.clear();
-                PFEM_HIP(hipStreamSynchronize(s->stream));
-                PFEM_HIP(hipStreamSynchronize(s->comm_stream));
-                bool ok = hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
-                if (ok) {
-                    for (int k = 0; k < kMultiGraphIters && ok; ++k) ok = multi_iteration(-1, nullptr, nullptr, nullptr, nullptr, nullptr) == PFEM_OK;
-                    hipGraph_t graph = nullptr;
-                    if (hipStreamEndCapture(s->stream, &graph) != hipSuccess || !graph) ok = false;
-                    if (ok && hipGraphInstantiate(&s->mgraph, graph, nullptr, nullptr, 0) != hipSuccess) ok = false;
-                    if (graph) (void)hipGraphDestroy(graph);
-                }
-                if (ok) {
-                    s->mgraph_key = key;
-                } else {        // capture refused (backend, stream kind): stream launches from now on
-                    (void)hipGetLastError();
-                    if (s->mgraph) { (void)hipGraphExecDestroy(s->mgraph); s->mgraph = nullptr; }
-                    s->mgraph_off = true;
-                }
-            }
-            use_mgraph = !s->mgraph_off && s->mgraph != nullptr;
+                static_cast<uint64_t>(s->n_slices_i)});
+            PFEM_TRY(s->mgraph.ensure(s->stream, std::move(key), {s->stream, s->comm_stream}, [&](int) {
+                bool ok = true;
+                for (int k = 0; k < kMultiGraphIters && ok; ++k) ok = multi_iteration(-1, nullptr, nullptr, nullptr, nullptr, nullptr) == PFEM_OK;
+                return ok;
+            }, &use_mgraph));
         }
     }
-    s->tm.graph_iterations = 0;
-    s->tm.host_enqueue_ms = s->tm.host_comm_ms = 0.0;
-    s->tm.host_enqueued_iterations = 0;
-    for (;;) {
-        PFEM_HIP(hipMemcpyAsync(s->h_ctl, ctl, sizeof(CgCtl), hipMemcpyDeviceToHost, s->stream));
-        PFEM_HIP(hipStreamSynchronize(s->stream));
-        h = *s->h_ctl;
-        if (h.flag != 0) break;
-        if (it >= s->maxits) { h.flag = -3; break; }   // maxits == 0
-        const int it_end = std::min(it + chunk, s->maxits);
-        const auto t_chunk = std::chrono::steady_clock::now();
-        const int it_chunk0 = it;
-        for (; it < it_end; ++it) {
-            // w = A p, partial (p, A_loc p) over ALL local rows (sub-assembled identity)
-            hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr;
-            const size_t ev_per = multi ? 4 : 2;      // multi: one pair for the boundary pass, one for the interior pass
-            const bool sample = s->profile_spmv && it % s->profile_every == 0 && ev_used + ev_per <= 8192;
-            if (use_mgraph && !sample && it + kMultiGraphIters <= it_end &&
-                (!s->profile_spmv || it % s->profile_every + kMultiGraphIters <= s->profile_every)) {
-                PFEM_HIP(hipGraphLaunch(s->mgraph, s->stream));        // no sampled iteration inside the unit
-                it += kMultiGraphIters - 1;
-                s->tm.graph_iterations += kMultiGraphIters;
-                continue;
-            }
-            if (sample) {
-                while (s->spmv_events.size() < ev_used + ev_per) {
-                    hipEvent_t a;
-                    PFEM_HIP(hipEventCreate(&a));
-                    s->spmv_events.push_back(a);
-                }
-                e0 = s->spmv_events[ev_used];
-                e1 = s->spmv_events[ev_used + 1];
-                if (multi) { e2 = s->spmv_events[ev_used + 2]; e3 = s->spmv_events[ev_used + 3]; }
-                ev_used += ev_per;
-            }
-            if (use_graph && it + kGraphIters <= it_end) {
-                // kGraphIters iterations from one graph launch; a sampled SpMV stays outside with its event pair
-                if (sample) launch_spmv<true>(s, s->d_p.p, s->d_w.p, n, part_pw, ctl, e0, e1);
-                PFEM_HIP(hipGraphLaunch(s->cg_graph[sample ? 1 : 0], s->stream));
-                it += kGraphIters - 1;
-                s->tm.graph_iterations += kGraphIters;
-                continue;
-            }
-            const double *red_pw = nullptr, *pw_parts = part_pw;
-            int pw_n = static_cast<int>(gs);
-            hipEvent_t *cev = nullptr;
-            if (multi && sample && comm_used + 8 <= 8192) {
-                while (s->comm_events.size() < comm_used + 8) {
-                    hipEvent_t e;
-                    PFEM_HIP(hipEventCreate(&e));
-                    s->comm_events.push_back(e);
-                }
-                cev = &s->comm_events[comm_used];
-                comm_used += 8;
-            }
-            if (multi && !bpc) {
-                PFEM_TRY(multi_iteration(it, e0, e1, e2, e3, cev));
-                continue;
-            }
+    CgSampler sampler(s, multi);
+    auto step = [&](int it, int it_end, int *used) -> int {
+        // w = A p, partial (p, A_loc p) over ALL local rows (sub-assembled identity)
+        hipEvent_t e[4] = {};
+        const bool sample = sampler.due(it);
+        if (use_mgraph && !sample && it + kMultiGraphIters <= it_end &&
+            (!s->profile_spmv || it % s->profile_every + kMultiGraphIters <= s->profile_every)) {
+            PFEM_HIP(hipGraphLaunch(s->mgraph.exec[0], s->stream));        // no sampled iteration inside the unit
+            *used = kMultiGraphIters;
+            return PFEM_OK;
+        }
+        if (sample) PFEM_TRY(sampler.spmv(e));
+        if (use_graph && it + kGraphIters <= it_end) {
+            // kGraphIters iterations from one graph launch; a sampled SpMV stays outside with its event pair
+            if (sample) launch_spmv<true>(s, s->d_p.p, s->d_w.p, n, part_pw, ctl, e[0], e[1]);
+            PFEM_HIP(hipGraphLaunch(s->cg_graph.exec[sample ? 1 : 0], s->stream));
+            *used = kGraphIters;
+            return PFEM_OK;
+        }
+        const double *red_pw = nullptr, *pw_parts = part_pw;
+        int pw_n = static_cast<int>(gs);
+        hipEvent_t *cev = nullptr;
+        if (sample) PFEM_TRY(sampler.comm(&cev));
+        if (multi && !bpc) return multi_iteration(it, e[0], e[1], e[2], e[3], cev);
+        if (multi) {
+            // node-block Jacobi on several ranks: the same SpMV / exchange sequence, block kernels below
+            PFEM_TRY(multi_spmv_exchange(e[0], e[1], e[2], e[3], cev));
+            red_pw = sbuf;
+        } else {
+            // with events: marker-end -> kernel-end of THIS launch (see event_overhead_ms)
+            launch_spmv<true>(s, s->d_p.p, s->d_w.p, n, part_pw, ctl, e[0], e[1]);
+            cg_fold(s, part_pw, gs, scal_pw, ctl, &pw_parts, &pw_n);
+        }
+        if (bpc) {
+            // residual ping-pong: iteration `it` reads r_a, writes r_b
+            const double *r_a = (it & 1) ? s->d_r2.p : s->d_r.p;
+            double *r_b = (it & 1) ? s->d_r.p : s->d_r2.p;
+            const uint32_t *rgp = s->d_row_grp.p;
+            hipLaunchKernelGGL(k_cg_update_b, dim3(gv), block, 0, s->stream, ctl, it, n, rgp, s->n_owned, pw_parts, pw_n, red_pw,
+                               s->d_p.p, s->d_w.p, s->d_binv[0].p, s->d_binv[1].p, s->d_binv[2].p, s->d_x.p, r_a, r_b, s->d_z.p,
+                               part_rz, part_zz);
             if (multi) {
-                // node-block Jacobi on several ranks: the same SpMV / exchange sequence, block kernels below
-                PFEM_TRY(multi_spmv_exchange(e0, e1, e2, e3, cev));
-                red_pw = sbuf;
-            } else {
-                // with events: marker-end -> kernel-end of THIS launch (see event_overhead_ms)
-                launch_spmv<true>(s, s->d_p.p, s->d_w.p, n, part_pw, ctl, e0, e1);
-                if (gs > kMaxGrid) {
-                    // too many SpMV blocks for every consumer block to re-sum: fold to kFoldBlocks first
-                    hipLaunchKernelGGL(k_fold_partials, dim3(kFoldBlocks), block, 0, s->stream, static_cast<const double *>(part_pw),
-                                       static_cast<int>(gs), scal_pw, static_cast<const CgCtl *>(ctl));
-                    pw_parts = scal_pw;
-                    pw_n = kFoldBlocks;
-                }
-            }
-            // (r,z), (z,z) of the owned rows -> one all-reduce of two doubles between the update and the direction kernel
-            auto scalars23 = [&]() -> int {
+                // (r,z), (z,z) of the owned rows -> one all-reduce of two doubles between the update and the direction kernel
                 hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, s->stream, static_cast<const double *>(part_rz),
                                    static_cast<const double *>(part_zz), static_cast<int>(gv), sbuf + 2, static_cast<const CgCtl *>(ctl));
                 if (cev) PFEM_HIP(hipEventRecord(cev[4], s->stream));
                 PFEM_TRY(s->comm->allreduce(sbuf + 2, 2, s->stream));
                 if (cev) PFEM_HIP(hipEventRecord(cev[5], s->stream));
-                return PFEM_OK;
-            };
-            if (bpc) {
-                // residual ping-pong: iteration `it` reads r_a, writes r_b
-                const double *r_a = (it & 1) ? s->d_r2.p : s->d_r.p;
-                double *r_b = (it & 1) ? s->d_r.p : s->d_r2.p;
-                const uint32_t *rgp = s->d_row_grp.p;
-                hipLaunchKernelGGL(k_cg_update_b, dim3(gv), block, 0, s->stream, ctl, it, n, rgp, s->n_owned, pw_parts, pw_n, red_pw,
-                                   s->d_p.p, s->d_w.p, s->d_binv[0].p, s->d_binv[1].p, s->d_binv[2].p, s->d_x.p, r_a, r_b, s->d_z.p,
-                                   part_rz, part_zz);
-                if (multi) PFEM_TRY(scalars23());
-                hipLaunchKernelGGL(k_cg_direction_b, dim3(gv), block, dir_lds, s->stream, ctl, it, n, part_rz, part_zz,
-                                   static_cast<int>(gv), red2, static_cast<const double *>(s->d_z.p), s->d_p.p, s->d_hist.p,
-                                   s->hist_cap, s->maxits);
-                continue;
             }
-            hipLaunchKernelGGL(k_cg_update, dim3(gv), block, 0, s->stream, ctl, it, n, s->n_owned, pw_parts, pw_n,
-                               red_pw, s->d_p.p, s->d_w.p, s->dinv_view(), s->d_x.p, s->d_r.p, part_rz, part_zz);
-            hipLaunchKernelGGL(k_cg_direction, dim3(gv), block, dir_lds, s->stream, ctl, it, n, part_rz, part_zz, static_cast<int>(gv),
-                               red2, s->d_r.p, s->dinv_view(), s->d_p.p, s->d_hist.p, s->hist_cap, s->maxits, s->d_x.p);
+            hipLaunchKernelGGL(k_cg_direction_b, dim3(gv), block, dir_lds, s->stream, ctl, it, n, part_rz, part_zz,
+                               static_cast<int>(gv), red2, static_cast<const double *>(s->d_z.p), s->d_p.p, s->d_hist.p,
+                               s->hist_cap, s->maxits);
+            return PFEM_OK;
         }
-        PFEM_TRY(check_kernel("pcg iteration"));
-        s->tm.host_enqueue_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_chunk).count();
-        s->tm.host_enqueued_iterations += it - it_chunk0;
-    }
-    s->tm.host_comm_ms = host_comm_s * 1e3;
-    s->last_its = h.its;
-    s->last_reason = (h.flag == 2 && h.rn <= s->abstol) ? 3 : h.flag;
-    s->last_rnorm = h.rn;
-    s->tm.spmv_ms_total = 0.0;
-    s->tm.spmv_launches = 0;
-    // only launches that did work count (the tail of the last chunk exits at the flag test)
-    // (the k-th pair belongs to iteration k * profile_every)
-    const size_t ev_per = multi ? 4 : 2;
-    const size_t live = std::min(ev_used / ev_per, (static_cast<size_t>(h.its) + s->profile_every - 1) / s->profile_every);
-    for (size_t k = 0; k < live; ++k) {
-        for (size_t q = 0; q < ev_per; q += 2) {
-            const bool split = multi && overlap;                   // boundary + interior pass, one event pair each
-            if (split && ((q == 0 && s->n_slices_b == 0) || (q == 2 && s->n_slices_i == 0))) continue;   // pass not launched
-            if (multi && !split && q == 2) continue;               // one pass over all slices
-            float f = 0.f;
-            PFEM_HIP(hipEventElapsedTime(&f, s->spmv_events[ev_per * k + q], s->spmv_events[ev_per * k + q + 1]));
-            s->tm.spmv_ms_total += f;
-        }
-        ++s->tm.spmv_launches;
-    }
-    s->tm.iface_ms_total = s->tm.scalar_ms_total = s->tm.exposed_ms_total = 0.0;
-    s->tm.comm_samples = 0;
-    for (size_t k = 0; k < std::min(comm_used / 8, live); ++k) {     // same sampled iterations as the SpMV pairs
-        hipEvent_t *c = &s->comm_events[8 * k];
-        float x = 0.f, a1 = 0.f, a2 = 0.f, w = 0.f;
-        PFEM_HIP(hipEventElapsedTime(&x, c[0], c[1]));
-        PFEM_HIP(hipEventElapsedTime(&a1, c[2], c[3]));
-        PFEM_HIP(hipEventElapsedTime(&a2, c[4], c[5]));
-        PFEM_HIP(hipEventElapsedTime(&w, c[6], c[7]));
-        s->tm.iface_ms_total += x;
-        s->tm.scalar_ms_total += a1 + a2;
-        s->tm.exposed_ms_total += w + a2;          // the second all-reduce sits between two dependent kernels: fully exposed
-        ++s->tm.comm_samples;
-    }
-    return PFEM_OK;
+        hipLaunchKernelGGL(k_cg_update, dim3(gv), block, 0, s->stream, ctl, it, n, s->n_owned, pw_parts, pw_n,
+                           red_pw, s->d_p.p, s->d_w.p, s->dinv_view(), s->d_x.p, s->d_r.p, part_rz, part_zz);
+        hipLaunchKernelGGL(k_cg_direction, dim3(gv), block, dir_lds, s->stream, ctl, it, n, part_rz, part_zz, static_cast<int>(gv),
+                           red2, s->d_r.p, s->dinv_view(), s->d_p.p, s->d_hist.p, s->hist_cap, s->maxits, s->d_x.p);
+        return PFEM_OK;
+    };
+    PFEM_TRY(cg_iterate(s, ctl, s->maxits, host_comm_s, [&](const CgCtl &) { return chunk; }, step, "pcg iteration"));
+    return sampler.tally(overlap, s->last_its, true);
 }
 
 // ---------------------------------------------------------------------------
@@ -4530,21 +4600,18 @@ int run_pcg(pfem_solver *s)
 int run_pcg_single(pfem_solver *s)
 {
     const int64_t n = s->n_loc;
-    const bool multi = s->nranks > 1 || (s->comm && s->have_plan && force_multi());
+    const bool multi = cg_multi(s);
     mark_group_vals(s);
     PFEM_TRY(refresh_group_vals(s));
     bool overlap = false;
     PFEM_TRY(agree_overlap(s, multi, &overlap));
     const unsigned gv = vec_grid(n), gs = spmv_blocks(s);
     const dim3 block(kBlock);
-    SellDev A = s->sell();
     if (s->d_part_pw.n < gs + 2) PFEM_TRY(s->d_part_pw.alloc(gs + 2));
     if (s->d_part1.n < 4 * static_cast<size_t>(kMaxGrid)) PFEM_TRY(s->d_part1.alloc(4 * static_cast<size_t>(kMaxGrid)));
-    if (s->d_zg.store.n < static_cast<size_t>(n) + 2 * kVecGuard) {
-        PFEM_TRY(s->d_zg.store.alloc(static_cast<size_t>(n) + 2 * kVecGuard));
-        PFEM_HIP(hipMemsetAsync(s->d_zg.store.p, 0, (static_cast<size_t>(n) + 2 * kVecGuard) * sizeof(double), s->stream));
-        s->d_zg.p = s->d_zg.store.p + kVecGuard;
-    }
+    bool grown = false;
+    PFEM_TRY(ensure_guarded(s->d_zg, n, &grown));
+    if (grown) PFEM_HIP(hipMemsetAsync(s->d_zg.store.p, 0, (static_cast<size_t>(n) + 2 * kVecGuard) * sizeof(double), s->stream));
     // the guard bands around THIS solve's n rows (the buffer may be longer than a new, smaller local system needs)
     PFEM_HIP(hipMemsetAsync(s->d_zg.store.p, 0, kVecGuard * sizeof(double), s->stream));
     PFEM_HIP(hipMemsetAsync(s->d_zg.p + n, 0, kVecGuard * sizeof(double), s->stream));
@@ -4553,145 +4620,48 @@ int run_pcg_single(pfem_solver *s)
     double *prz[2] = {s->d_part1.p, s->d_part1.p + 2 * kMaxGrid}, *pzz[2] = {s->d_part1.p + kMaxGrid, s->d_part1.p + 3 * kMaxGrid};
     double *z = s->d_zg.p, *sv = s->d_sv.p;
     CgCtl *ctl = s->d_ctl.p;
-    if (multi) {
-        if (!s->comm || !s->have_plan) {
-            set_last_error("a solver of a multi-rank run needs a communication backend (pfem_solver_set_comm_rccl / _host) "
-                           "and the neighbour plan (pfem_solver_set_neighbours) before the solve");
-            return PFEM_ERR_STATE;
-        }
-        PFEM_TRY(ensure_comm_stream(s));
-        PFEM_TRY(build_slice_lists(s));
-    }
-    if (s->hist_cap < s->maxits + 2) {
-        PFEM_TRY(s->d_hist.alloc(static_cast<size_t>(s->maxits) + 2));
-        s->hist_cap = s->maxits + 2;
-    }
-    PFEM_HIP(hipMemsetAsync(ctl, 0, sizeof(CgCtl), s->stream));
-    if (s->comm) s->comm->set_abort_word(&ctl->flag);          // (a device-side transport ends the solve through it when a wait fails)
-    // Jacobi: dinv = 1 / diag(A); interface diagonals and rhs are summed over the ranks
-    if (n > 0) {
-        hipLaunchKernelGGL(k_extract_diag, dim3(grid_for(n)), block, 0, s->stream, A, s->d_dinv.p);
-        PFEM_TRY(check_kernel("k_extract_diag"));
-    }
-    if (multi) {
-        PFEM_TRY(exchange_sum(s, s->d_dinv.p, overlap));
-        if (!s->rhs_summed) {
-            PFEM_TRY(exchange_sum(s, s->d_rhs.p, overlap));
-            s->rhs_summed = true;
-        }
-    }
-    if (n > 0) {
-        hipLaunchKernelGGL(k_invert, dim3(grid_for(n)), block, 0, s->stream, s->d_dinv.p, n);
-        PFEM_TRY(check_kernel("k_invert"));
-    }
+    PFEM_TRY(cg_require_comm(s, multi));
+    PFEM_TRY(cg_reset_control(s, ctl));
+    PFEM_TRY(cg_point_jacobi(s, multi, overlap));
     // x = 0, r = b, z = M^-1 b, first set of (r,z)/(z,z) partials
     hipLaunchKernelGGL(k_cg_init, dim3(gv), block, 0, s->stream, n, s->n_owned, s->d_rhs.p, s->d_dinv.p, s->d_x.p, s->d_r.p, z, prz[0], pzz[0]);
     PFEM_TRY(check_kernel("k_cg_init"));
 
     const int chunk = cg_chunk_env() > 0 ? cg_chunk_env() : 32;
-    size_t ev_used = 0, comm_used = 0;
     double host_comm_s = 0.0;
-    s->tm.graph_iterations = 0;
-    s->tm.host_enqueue_ms = s->tm.host_comm_ms = 0.0;
-    s->tm.host_enqueued_iterations = 0;
-    const size_t ev_per = multi ? 4 : 2;
-    int it = 0;                                 // steps enqueued; step `it` judges iterate `it` and produces iterate it+1
-    CgCtl h{};
-    for (;;) {
-        PFEM_HIP(hipMemcpyAsync(s->h_ctl, ctl, sizeof(CgCtl), hipMemcpyDeviceToHost, s->stream));
-        PFEM_HIP(hipStreamSynchronize(s->stream));
-        h = *s->h_ctl;
-        if (h.flag != 0) break;
-        const int it_end = std::min(it + chunk, std::max(s->maxits, 0) + 1);      // step maxits only judges
-        if (it >= it_end) { h.flag = -3; break; }                     // not reached: step maxits sets the flag
-        const auto t_chunk = std::chrono::steady_clock::now();
-        const int it_chunk0 = it;
-        for (; it < it_end; ++it) {
-            hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr, *cev = nullptr;
-            const bool sample = s->profile_spmv && it % s->profile_every == 0 && ev_used + ev_per <= 8192;
-            if (sample) {
-                while (s->spmv_events.size() < ev_used + ev_per) {
-                    hipEvent_t a;
-                    PFEM_HIP(hipEventCreate(&a));
-                    s->spmv_events.push_back(a);
-                }
-                e0 = s->spmv_events[ev_used];
-                e1 = s->spmv_events[ev_used + 1];
-                if (multi) { e2 = s->spmv_events[ev_used + 2]; e3 = s->spmv_events[ev_used + 3]; }
-                ev_used += ev_per;
-                if (multi && comm_used + 8 <= 8192) {
-                    while (s->comm_events.size() < comm_used + 8) {
-                        hipEvent_t e;
-                        PFEM_HIP(hipEventCreate(&e));
-                        s->comm_events.push_back(e);
-                    }
-                    cev = &s->comm_events[comm_used];
-                    comm_used += 8;
-                }
-            }
-            const double *in_rz = prz[it & 1], *in_zz = pzz[it & 1];
-            double *out_rz = prz[(it + 1) & 1], *out_zz = pzz[(it + 1) & 1];
-            const double *reduced = nullptr, *pw_parts = part_pw;
-            int pw_n = static_cast<int>(gs);
-            if (multi) {
-                PFEM_TRY(spmv_exchange(s, z, sv, part_pw, gs, overlap, ctl, e0, e1, e2, e3, cev, &host_comm_s, [&](int nblocks) -> int {
-                    hipLaunchKernelGGL(k_reduce_partials3, dim3(1), dim3(1024), 0, s->stream, static_cast<const double *>(part_pw), nblocks,
-                                       in_rz, in_zz, static_cast<int>(gv), sbuf, static_cast<const CgCtl *>(ctl));
-                    return 3;
-                }));
-                if (cev) { PFEM_HIP(hipEventRecord(cev[4], s->stream)); PFEM_HIP(hipEventRecord(cev[5], s->stream)); }   // no second all-reduce
-                reduced = sbuf;
-            } else {
-                launch_spmv<true>(s, z, sv, n, part_pw, ctl, e0, e1);
-                if (gs > kMaxGrid) {
-                    hipLaunchKernelGGL(k_fold_partials, dim3(kFoldBlocks), block, 0, s->stream, static_cast<const double *>(part_pw),
-                                       static_cast<int>(gs), scal_pw, static_cast<const CgCtl *>(ctl));
-                    pw_parts = scal_pw;
-                    pw_n = kFoldBlocks;
-                }
-            }
-            hipLaunchKernelGGL(k_cg1_step, dim3(gv), block, 0, s->stream, ctl, it, n, s->n_owned, pw_parts, pw_n, in_rz, in_zz,
-                               static_cast<int>(gv), reduced, static_cast<const double *>(s->d_dinv.p), z, static_cast<const double *>(sv),
-                               s->d_p.p, s->d_w.p, s->d_x.p, s->d_r.p, out_rz, out_zz, s->rtol, s->abstol, s->dtol, s->d_hist.p,
-                               s->hist_cap, s->maxits);
+    CgSampler sampler(s, multi);
+    // step `it` judges iterate `it` and produces iterate it+1; step maxits only judges
+    auto step = [&](int it, int, int *) -> int {
+        hipEvent_t e[4] = {}, *cev = nullptr;
+        if (sampler.due(it)) {
+            PFEM_TRY(sampler.spmv(e));
+            PFEM_TRY(sampler.comm(&cev));
         }
-        PFEM_TRY(check_kernel("single-reduction pcg iteration"));
-        s->tm.host_enqueue_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_chunk).count();
-        s->tm.host_enqueued_iterations += it - it_chunk0;
-    }
-    s->tm.host_comm_ms = host_comm_s * 1e3;
-    s->last_its = h.its;
-    s->last_reason = (h.flag == 2 && h.rn <= s->abstol) ? 3 : h.flag;
-    s->last_rnorm = h.rn;
-    // sampled SpMV launches that did work: steps 0 .. its (the last one only judged)
-    s->tm.spmv_ms_total = 0.0;
-    s->tm.spmv_launches = 0;
-    const size_t live = std::min(ev_used / ev_per, (static_cast<size_t>(h.its) + 1 + s->profile_every - 1) / s->profile_every);
-    for (size_t k = 0; k < live; ++k) {
-        for (size_t q = 0; q < ev_per; q += 2) {
-            const bool split = multi && overlap;
-            if (split && ((q == 0 && s->n_slices_b == 0) || (q == 2 && s->n_slices_i == 0))) continue;
-            if (multi && !split && q == 2) continue;
-            float f = 0.f;
-            PFEM_HIP(hipEventElapsedTime(&f, s->spmv_events[ev_per * k + q], s->spmv_events[ev_per * k + q + 1]));
-            s->tm.spmv_ms_total += f;
+        const double *in_rz = prz[it & 1], *in_zz = pzz[it & 1];
+        double *out_rz = prz[(it + 1) & 1], *out_zz = pzz[(it + 1) & 1];
+        const double *reduced = nullptr, *pw_parts = part_pw;
+        int pw_n = static_cast<int>(gs);
+        if (multi) {
+            PFEM_TRY(spmv_exchange(s, z, sv, part_pw, gs, overlap, ctl, e[0], e[1], e[2], e[3], cev, &host_comm_s, [&](int nblocks) -> int {
+                hipLaunchKernelGGL(k_reduce_partials3, dim3(1), dim3(1024), 0, s->stream, static_cast<const double *>(part_pw), nblocks,
+                                   in_rz, in_zz, static_cast<int>(gv), sbuf, static_cast<const CgCtl *>(ctl));
+                return 3;
+            }));
+            if (cev) { PFEM_HIP(hipEventRecord(cev[4], s->stream)); PFEM_HIP(hipEventRecord(cev[5], s->stream)); }   // no second all-reduce
+            reduced = sbuf;
+        } else {
+            launch_spmv<true>(s, z, sv, n, part_pw, ctl, e[0], e[1]);
+            cg_fold(s, part_pw, gs, scal_pw, ctl, &pw_parts, &pw_n);
         }
-        ++s->tm.spmv_launches;
-    }
-    s->tm.iface_ms_total = s->tm.scalar_ms_total = s->tm.exposed_ms_total = 0.0;
-    s->tm.comm_samples = 0;
-    for (size_t k = 0; k < std::min(comm_used / 8, live); ++k) {
-        hipEvent_t *c = &s->comm_events[8 * k];
-        float x = 0.f, a1 = 0.f, w = 0.f;
-        PFEM_HIP(hipEventElapsedTime(&x, c[0], c[1]));
-        PFEM_HIP(hipEventElapsedTime(&a1, c[2], c[3]));
-        PFEM_HIP(hipEventElapsedTime(&w, c[6], c[7]));
-        s->tm.iface_ms_total += x;
-        s->tm.scalar_ms_total += a1;
-        s->tm.exposed_ms_total += w;
-        ++s->tm.comm_samples;
-    }
-    return PFEM_OK;
+        hipLaunchKernelGGL(k_cg1_step, dim3(gv), block, 0, s->stream, ctl, it, n, s->n_owned, pw_parts, pw_n, in_rz, in_zz,
+                           static_cast<int>(gv), reduced, static_cast<const double *>(s->d_dinv.p), z, static_cast<const double *>(sv),
+                           s->d_p.p, s->d_w.p, s->d_x.p, s->d_r.p, out_rz, out_zz, s->rtol, s->abstol, s->dtol, s->d_hist.p,
+                           s->hist_cap, s->maxits);
+        return PFEM_OK;
+    };
+    PFEM_TRY(cg_iterate(s, ctl, std::max(s->maxits, 0) + 1, host_comm_s, [&](const CgCtl &) { return chunk; }, step,
+                        "single-reduction pcg iteration"));
+    return sampler.tally(overlap, s->last_its + 1, false);      // steps 0 .. its did work (the last one only judged)
 }
 
 }  // namespace
@@ -5180,7 +5150,7 @@ extern "C" int pfem_solver_set_amg_options(pfem_solver *s, int cheb_degree, int 
     if (!s->amg) return PFEM_ERR_NOMEM;
     s->amg->cheb_degree = cheb_degree;
     s->amg->fine_degree = fine_degree;
-    s->amg->graph_key.clear();
+    s->amg->graph.invalidate();
     s->amg->eig_ratio_given = eig_ratio > 0.0;
     if (eig_ratio > 0.0) s->amg->eig_ratio = eig_ratio;
     s->amg->coarse_scale_given = coarse_scale > 0.0;
@@ -5210,7 +5180,7 @@ extern "C" int pfem_solver_set_amg_cycle(pfem_solver *s, int cycle)
     if (!s->amg) return PFEM_ERR_NOMEM;
     s->amg->cycle_given = cycle != 0;
     if (cycle != 0) s->amg->cycle_gamma = cycle;
-    s->amg->graph_key.clear();
+    s->amg->graph.invalidate();
     return PFEM_OK;
 }
 // what the last gamg solve ran: 1 = V, 2 = W, and the last level whose problem got two visits

@@ -544,6 +544,53 @@ def test_blocks_that_start_late_still_apply_the_last_step(monkeypatch):
     assert np.array_equal(a.soln_free, b.soln_free)
 
 
+@pytest.mark.parametrize("case", ["jacobi", "pbjacobi", "single_reduction"])
+def test_jacobi_loops_same_bits_with_graphs_chunks_and_sampling(case, monkeypatch):
+    """The Jacobi CG loops enqueue their iterations from a replayed hipGraph or on the stream, in chunks of any size
+    between two reads of the control block, with sampled SpMV timings or without: none of it changes a bit of the
+    solve.  Small enough (below kGraphMaxRows) for the point-Jacobi loop to replay its graph."""
+    if case == "pbjacobi":
+        kind, ed = pf.ELAST_TET, H.ELAST_ELEMDATA
+        mesh = H.gen_box_tets(-0.5, 0.5, 6, 0.0, 6.0, 36, -0.5, 0.5, 6, bc_mode=1, ndof=3)
+    else:
+        kind, ed = pf.POISSON_TET, H.POISSON_ELEMDATA
+        mesh = H.gen_box_tets(-1, 1, 30, -1, 1, 30, -1, 1, 30)
+    s, _ = _device_problem(kind, mesh, ed)
+    if case == "pbjacobi":
+        s.setSpmvFormat("grouped")              # the node groups of node-block Jacobi at this size
+        s.buildPattern()
+        s.assemble(ed, H.TIMEDATA)
+        s.setPreconditioner("pbjacobi")
+        assert s.preconditioner() == "pbjacobi"
+    s.setSingleReduction(case == "single_reduction")
+    s.setTolerances(rtol=1e-10, maxits=20000)
+    ref = None
+    for graph in ("0", "1", "2"):
+        for chunk in ("1", None):
+            for every in (8, 0):
+                monkeypatch.setenv("PFEM_CG_GRAPH", graph)
+                if chunk is None:
+                    monkeypatch.delenv("PFEM_CG_CHUNK", raising=False)
+                else:
+                    monkeypatch.setenv("PFEM_CG_CHUNK", chunk)
+                s.profileSpmv(every)
+                its, reason, rn = s.factoriseAndSolve()
+                hist, u = s.getHistory(), s.getSolution()
+                if ref is None:
+                    ref = (its, reason, rn, hist, u)
+                    assert reason == 2 and its >= 8
+                setting = (graph, chunk, every)
+                assert (its, reason, rn) == ref[:3], setting
+                assert np.array_equal(hist, ref[3]) and np.array_equal(u, ref[4]), setting
+                t = s.timings()
+                judged = its + 1 if case == "single_reduction" else its     # the single-reduction loop's last SpMV only judges
+                assert t["spmv_launches"] == ((judged + 7) // 8 if every else 0), setting
+                # a unit of kGraphIters iterations fits only in a chunk of the default size
+                replays = case == "jacobi" and graph != "0" and chunk is None
+                assert (t["graph_iterations"] > 0) == replays, setting
+                assert t["host_enqueued_iterations"] >= its, setting
+
+
 @pytest.mark.parametrize("kind,box,bc_mode,nparts", [(pf.POISSON_TET, (6, 5, 7), 0, 1), (pf.POISSON_TET, (6, 5, 7), 0, 3),
                                                      (pf.ELAST_TET, (3, 6, 5), 1, 1), (pf.ELAST_TET, (3, 6, 5), 1, 2)])
 def test_device_generated_box_equals_host_generator_and_bookkeeping(kind, box, bc_mode, nparts):
