@@ -297,7 +297,8 @@ int pfem_solver_get_preconditioner(pfem_solver *s, int *pc_in_effect);
  * default 1: there an SpMV is dearest), lmax/lmin of the smoothing interval (until set: 16, and 8 for 3-dof nodes WITHOUT rigid-body modes), scaling of the coarse-grid
  * correction (the over-correction a piecewise-constant coarse space wants; until set: 1.5, and 1.8 for 3-dof nodes without rigid-body modes)   */
 int pfem_solver_set_amg_options(pfem_solver *s, int cheb_degree, int fine_degree, double eig_ratio, double coarse_scale);
-/* (eig_ratio <= 0 / coarse_scale <= 0: that knob stays automatic -- picked per kind of problem at the next symbolic phase) */
+/* (eig_ratio <= 0 / coarse_scale <= 0: that knob is automatic -- picked per kind of problem at the symbolic phase, and taken from
+ * the next solve on also where it was given a value before) */
 /* -pc_mg_cycle_type v|w (PETSc's PCMGSetCycleType behind PCGAMG): 1 = V(1,1), 2 = W(1,1) -- every coarse problem above the
  * single-launch tail of the cycle is visited twice, the second time on the residual of the first --, 0 = the default again
  * (V, as in PETSc).  W roughly halves the iterations on aggregates matched on the strength graph and costs more than it saves

@@ -2518,6 +2518,17 @@ int amg_finish_levels(pfem_solver *s, Amg &M, bool coupled)
 }
 
 
+// The smoothing interval and the coarse-grid scale in effect: the switch, else the value pfem_solver_set_amg_options gave, else
+// the automatic one of the last symbolic phase.  Taken at the symbolic and at every numeric phase: a knob the caller returns to
+// automatic on a hierarchy that is kept gets that hierarchy's automatic value, not the one it was given before.
+void amg_knobs(Amg &M)
+{
+    const char *er = std::getenv("PFEM_AMG_EIG_RATIO"), *cs = std::getenv("PFEM_AMG_COARSE_SCALE");
+    M.eig_ratio = er ? std::max(1.5, std::atof(er)) : (M.eig_ratio_given ? M.eig_ratio_opt : M.eig_ratio_auto);
+    M.coarse_scale = cs ? std::atof(cs) : (M.coarse_scale_given ? M.coarse_scale_opt : M.coarse_scale_auto);
+    if (M.rep) { M.rep->eig_ratio = M.eig_ratio; M.rep->coarse_scale = M.coarse_scale; }      // (the replicated tail: a copy at set-up)
+}
+
 // ---- symbolic phase: aggregates and Galerkin maps of every level (needs the matrix values: strength of connection) ----
 int amg_symbolic(pfem_solver *s, bool multi, bool overlap)
 {
@@ -2541,8 +2552,6 @@ int amg_symbolic(pfem_solver *s, bool multi, bool overlap)
     const bool coupled = M.coupled;
     if (const char *e = std::getenv("PFEM_AMG_CHEB_DEGREE")) M.cheb_degree = std::max(1, std::min(6, std::atoi(e)));
     if (const char *e = std::getenv("PFEM_AMG_FINE_DEGREE")) M.fine_degree = std::max(0, std::min(6, std::atoi(e)));
-    if (const char *e = std::getenv("PFEM_AMG_EIG_RATIO")) { M.eig_ratio = std::max(1.5, std::atof(e)); M.eig_ratio_given = true; }
-    if (const char *e = std::getenv("PFEM_AMG_COARSE_SCALE")) { M.coarse_scale = std::atof(e); M.coarse_scale_given = true; }
     M.lev.clear();
     M.rep.reset();
     M.rbm = false;
@@ -2717,9 +2726,10 @@ int amg_symbolic(pfem_solver *s, bool multi, bool overlap)
             }
         }
         // (with rigid-body modes the coarse space is no longer piecewise constant in what matters: the over-correction goes back to 1.5)
-        if (!M.coarse_scale_given) M.coarse_scale = (L0->bs == kGroupRows && L0->dim == 0) ? 1.8 : 1.5;
+        M.coarse_scale_auto = (L0->bs == kGroupRows && L0->dim == 0) ? 1.8 : 1.5;
         // (smoothing interval: measured per kind -- with rigid-body modes the beam takes 24 iterations at 8, 18 at 16 and at 30)
-        if (!M.eig_ratio_given) M.eig_ratio = (L0->bs > 1 && L0->dim == 0) ? 8.0 : 16.0;
+        M.eig_ratio_auto = (L0->bs > 1 && L0->dim == 0) ? 8.0 : 16.0;
+        amg_knobs(M);
         M.lev.push_back(std::move(L0));
     }
     since_t0("level 0 described (nodes, lattice)");
@@ -3335,8 +3345,12 @@ int run_pcg_amg(pfem_solver *s)
             rc = amg_symbolic(s, multi, overlap);
         }
         PFEM_TRY(rc);
+        // a new hierarchy: no level's bound or codes come from a product of the old one, nor level 0's bound from an assembly for it
+        s->asm_bound_fresh = false;
+        for (auto &L : s->amg->lev) L->bound_fresh = L->vd_direct = false;
     }
     Amg &M = *s->amg;
+    amg_knobs(M);
     PFEM_TRY(amg_cycle_shape(s, M));
     M.coupled_fused = [] { const char *e = std::getenv("PFEM_AMG_COUPLED_FUSED"); return e ? std::atoi(e) != 0 : true; }();
     if (M.coupled && M.coupled_fused && !s->d_row_sh.p && s->n_loc > 0) {        // level 0's dof -> shared index table (the coarse levels got theirs with their plans)

@@ -120,8 +120,12 @@ struct Amg {
                                                      // measured 200^3 52 -> 41 ms, beam 321 -> 279 ms against degree 2 everywhere
     bool eig_ratio_given = false;                    // likewise the smoothing interval: until set, lmax/16 .. lmax on scalar problems (with the lattice's
                                                      // hierarchy 3-7 % faster than /8 at 100^3, 160^3, 200^3), lmax/8 with 3 dofs per node (the beam: /16 costs 12 %)
-    bool coarse_scale_given = false;                 // set through pfem_solver_set_amg_options / PFEM_AMG_COARSE_SCALE; else 1.5, 1.8 for 3-dof nodes
-    double eig_ratio = 8.0, coarse_scale = 1.5;       // over-correction of the piecewise-constant coarse space (Braess 1995 takes 1.8).
+    bool coarse_scale_given = false;                 // set through pfem_solver_set_amg_options; else 1.5, 1.8 for 3-dof nodes
+    double eig_ratio_opt = 0.0, coarse_scale_opt = 0.0;        // ... the values it gave
+    double eig_ratio_auto = 16.0, coarse_scale_auto = 1.5;     // what the last symbolic phase picked for the problem
+    // eig_ratio / coarse_scale IN EFFECT (amg_knobs, at the symbolic and at every numeric phase): PFEM_AMG_EIG_RATIO / PFEM_AMG_COARSE_SCALE,
+    // else the given value, else the automatic one.  coarse_scale: over-correction of the piecewise-constant coarse space (Braess 1995 takes 1.8).
+    double eig_ratio = 8.0, coarse_scale = 1.5;
                                                      // measured 1.5 -> 1.8: 200^3 equal, the beam 228 -> 189 ms, the 9^3 tet10 mesh WORSE
                                                      // (26 against 22 iterations): 1.5 is the robust middle for scalar problems; with
                                                      // 3 dofs per node 1.8 is the default (beam 205 -> 169 iterations, half-size beam 191 -> 155)

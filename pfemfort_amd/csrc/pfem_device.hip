@@ -1321,6 +1321,7 @@ extern "C" int pfem_mesh_upload(pfem_solver *s, int kind, int64_t nElem, const i
     s->h_send_lidx.clear();
     s->d_row_sh.release();
     if (s->amg) s->amg->symbolic_ok = false;
+    s->asm_bound_fresh = false;            // (a level-0 bound the assembly left belongs to the hierarchy that goes)
     s->tm.upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return PFEM_OK;
 }
@@ -1612,6 +1613,7 @@ int pattern_from_keys(pfem_solver *s, DevBuf<uint64_t> &keys, int64_t nkeys)
     s->mgraph.invalidate();
     s->slices_fmt = -1;                    // ... and the boundary / interior slice lists belong to the old pattern
     if (s->amg) { s->amg->symbolic_ok = false; s->amg->coupled_refused = false; }   // ... and so does the multigrid hierarchy
+    s->asm_bound_fresh = false;            // ... with the level-0 bound an assembly left for it
     PFEM_TRY(use_sort_bits(s));
     const int end_bit = s->sort_end_bit;
     DevBuf<uint64_t> sorted;
@@ -1920,6 +1922,7 @@ int pattern_from_incidence(pfem_solver *s, bool *done)
     s->mgraph.invalidate();
     s->slices_fmt = -1;
     if (s->amg) { s->amg->symbolic_ok = false; s->amg->coupled_refused = false; }
+    s->asm_bound_fresh = false;
     PFEM_TRY(use_sort_bits(s));
     s->n_slices = (n + 63) / 64;
     PFEM_TRY(s->d_rowptr.alloc(static_cast<size_t>(n) + 1));
@@ -3699,6 +3702,7 @@ extern "C" int pfem_solver_set_neighbours(pfem_solver *s, int n_peers, const int
     s->slices_fmt = -1;
     s->overlap_agreed = -1;
     if (s->amg) { s->amg->symbolic_ok = false; s->amg->coupled_refused = false; }      // a coupled hierarchy has the plan built in
+    s->asm_bound_fresh = false;
     return PFEM_OK;
 }
 
@@ -5151,10 +5155,12 @@ extern "C" int pfem_solver_set_amg_options(pfem_solver *s, int cheb_degree, int 
     s->amg->cheb_degree = cheb_degree;
     s->amg->fine_degree = fine_degree;
     s->amg->graph.invalidate();
+    // (the values in effect are taken at the next numeric phase -- amg_knobs --, so a knob returned to automatic after a symbolic
+    // phase gets the automatic value that phase picked, not the last given one)
     s->amg->eig_ratio_given = eig_ratio > 0.0;
-    if (eig_ratio > 0.0) s->amg->eig_ratio = eig_ratio;
+    if (eig_ratio > 0.0) s->amg->eig_ratio_opt = eig_ratio;
     s->amg->coarse_scale_given = coarse_scale > 0.0;
-    if (coarse_scale > 0.0) s->amg->coarse_scale = coarse_scale;
+    if (coarse_scale > 0.0) s->amg->coarse_scale_opt = coarse_scale;
     return PFEM_OK;
 }
 
