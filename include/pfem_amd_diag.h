@@ -110,6 +110,10 @@ int pfem_solver_amg_cycle_profile(pfem_solver *s, int max_levels, int *n_levels,
 int pfem_solver_amg_pairing(pfem_solver *s, int *lattice_levels);
 /* the cycle the last gamg solve ran: 1 = V, 2 = W, and the last level whose problem got two visits (0 with V)          */
 int pfem_solver_amg_cycle(pfem_solver *s, int *cycle, int *last_level_visited_twice);
+/* 1 when the iterations of the last gamg solve ran the cycle's last product on the assembled matrix with the final smoothing
+ * step and the CG's (r,z), (z,z) as its epilogue (one rank, a 4-row relative-group SpMV form with 16-bit gaps, fine degree 1,
+ * PFEM_AMG_FUSED not 0); 0 when they took the stand-alone kernels                                                          */
+int pfem_solver_amg_level0_epilogue(pfem_solver *s, int *taken);
 
 /* Per-element Ke/Fe of the uploaded mesh as computed by the DEVICE kernel (parity
  * inspection): K_out[e*nsize*nsize + i + nsize*j], F_out[e*nsize + i].           */

@@ -3052,7 +3052,10 @@ int amg_smooth(pfem_solver *s, const Amg &M, AmgLevel &L, const double *b, bool 
 // its restriction is linear, so each rank restricts  [owned part of b] - [its own share of A x]  and the COARSE vector is
 // summed over the holders instead -- one exchange on the smaller level where two on the larger would be needed.
 // Level by level with plain kernels (no fused epilogues, no single-workgroup tail: both end at a rank's border).
-double *amg_apply(pfem_solver *s, Amg &M, const double *r, const CgCtl *ctl, bool first0_done = false, bool leave_last0 = false);
+// what amg_apply leaves of level 0's last post-smoothing step to its caller (fine degree 1): nothing; the step itself, t = A x
+// being in L0.t (k_pc_post_dots); or the product runs with the step and the CG's sums as its epilogue (Level0Ep: z in L0.t)
+enum { kLast0Smooth = 0, kLast0Product = 1, kLast0Epilogue = 2 };
+double *amg_apply(pfem_solver *s, Amg &M, const double *r, const CgCtl *ctl, bool first0_done = false, int last0 = kLast0Smooth);
 double *amg_apply_coupled(pfem_solver *s, Amg &M, const double *r, const CgCtl *ctl, bool overlap)
 {
     const int nl = static_cast<int>(M.lev.size());
@@ -3146,13 +3149,16 @@ double *amg_apply_coupled(pfem_solver *s, Amg &M, const double *r, const CgCtl *
     return M.lev[0]->x;
 }
 
-// z = M^-1 r: one V(1,1) cycle -- or W(1,1): M.cycle_gamma --; returns the vector that holds z (level 0's x).
+// z = M^-1 r: one V(1,1) cycle -- or W(1,1): M.cycle_gamma --; returns the vector that holds z (level 0's x; its t after kLast0Epilogue).
 // Three ways through a level, all the same arithmetic (PFEM_AMG_FUSED=0 takes the first everywhere; tested bit for bit):
-//   * level 0 and any level whose Chebyshev degree is not 2: SpMV launches + vector kernels (amg_smooth);
+//   * level 0 and any level whose Chebyshev degree is not 2: SpMV launches + vector kernels (amg_smooth).  Level 0's two ends
+//     ride on the CG's own kernels during the iterations: step 0 of the pre-smoothing on k_pc_update, and -- fine degree 1 --
+//     the post-smoothing step either on the dots kernel (k_pc_post_dots, t = A x stored) or, on one rank with a 4-row
+//     relative-group SpMV form, on the product itself: z and the CG's (r,z), (z,z) are its epilogue (Level0Ep), t is never stored;
 //   * levels 1 .. tail_from-1: the SpMV with the vector step as its epilogue (k_amg_spmv_ep), step 0 of the pre-smoothing
 //     done by the restriction kernel of the level above: 6 launches per level instead of 10;
 //   * levels tail_from .. last (at most 4096 rows): one workgroup walks them all in one launch (k_amg_tail).
-double *amg_apply(pfem_solver *s, Amg &M, const double *r, const CgCtl *ctl, bool first0_done, bool leave_last0)
+double *amg_apply(pfem_solver *s, Amg &M, const double *r, const CgCtl *ctl, bool first0_done, int last0)
 {
     const int nl = static_cast<int>(M.lev.size());
     // several ranks: the ghost part of z holds the owners' values after the exchange of the previous cycle; as an SpMV
@@ -3282,14 +3288,22 @@ double *amg_apply(pfem_solver *s, Amg &M, const double *r, const CgCtl *ctl, boo
         if (fused_level(l)) {
             ep(kEpFirstRes, L, L.x, b, 0, 0, L.r.p, L.dd, nullptr);
             ep(kEpNextLast, L, L.dd, L.r.p, 1, 1, nullptr, nullptr, L.x);
-        } else if (l == 0 && leave_last0) {
+        } else if (l == 0 && last0 == kLast0Epilogue) {
+            // degree 1, a 4-row form on one rank: the step and the CG's (r,z), (z,z) are the product's epilogue; z goes to L.t
+            // (other waves still gather L.x), one pair of partials per block, folded to kFoldBlocks here
+            const unsigned gs = spmv_blocks(s);
+            double *prz = s->d_part_ep.p, *pzz = prz + gs, *frz = pzz + gs, *fzz = frz + kFoldBlocks;
+            launch_spmv_level0_ep(s, L.x, Level0Ep{b, L.dinv.p, L.lam.p, M.eig_ratio, L.t.p, prz, pzz}, ctl);
+            hipLaunchKernelGGL(k_fold_partials2, dim3(kFoldBlocks, 2), dim3(kBlock), 0, s->stream, static_cast<const double *>(prz),
+                               static_cast<const double *>(pzz), static_cast<int>(gs), frz, fzz, ctl);
+        } else if (l == 0 && last0 == kLast0Product) {
             amg_spmv(s, M, L, L.x, L.t.p);          // degree 1: the step itself rides on the CG's dots kernel (k_pc_post_dots)
         } else {
             (void)amg_smooth(s, M, L, b, false, deg_of(l), ctl);
         }
     };
     visit(0);
-    return M.lev[0]->x;
+    return last0 == kLast0Epilogue ? M.lev[0]->t.p : M.lev[0]->x;
 }
 
 // ---- the CG solve with z = M^-1 r from the V-cycle (KSPSolve, solverpetsc.F:476; -pc_type gamg) -----------------------
@@ -3378,10 +3392,19 @@ int run_pcg_amg(pfem_solver *s)
     double host_comm_s = 0.0;
     // Two fusions of the cycle's ends with the CG's own vector kernels (iterations only; same arithmetic, same bits):
     // step 0 of the pre-smoothing on the assembled matrix rides on k_pc_update, and -- when the fine degree is 1 -- the one
-    // step of the post-smoothing rides on the dots kernel.  Both need at least two levels.
+    // step of the post-smoothing rides on the dots kernel (or, `ep0` below, on the product in front of it).  Both need at least two levels.
     const int deg0 = M.fine_degree > 0 ? M.fine_degree : M.cheb_degree;
     const bool fuse_first0 = M.fused && M.lev.size() > 1 && !M.coupled;
     const bool fuse_last0 = M.fused && M.lev.size() > 1 && deg0 == 1 && !M.coupled;
+    // One rank, level 0 in a relative-group form with 16-bit gaps: the iteration's (r,z), (z,z) are summed per block of the product
+    // (1024 consecutive rows, 4 to the thread) and folded to kFoldBlocks -- by the epilogue of the cycle's last product (Level0Ep)
+    // where the step rides on it, by k_pc_dots_rows4 behind every other cycle: the layout belongs to the form, not to the fusion.
+    const bool rows4 = !multi && spmv_has_level0_ep(s);
+    const bool ep0 = rows4 && fuse_last0;
+    const int last0 = ep0 ? kLast0Epilogue : (fuse_last0 ? kLast0Product : kLast0Smooth);
+    M.level0_ep = ep0;
+    if (rows4 && s->d_part_ep.n < 2 * static_cast<size_t>(gs) + 2 * kFoldBlocks) PFEM_TRY(s->d_part_ep.alloc(2 * static_cast<size_t>(gs) + 2 * kFoldBlocks));
+    double *ep_rz = s->d_part_ep.p, *ep_zz = ep_rz ? ep_rz + gs : nullptr, *fold_rz = ep_rz ? ep_zz + gs : nullptr, *fold_zz = ep_rz ? fold_rz + kFoldBlocks : nullptr;
     // One rank: the cycle of the iterations (the one that takes the control block) is replayed from a hipGraph -- a
     // dependent tiny kernel costs ~3.4 us on a stream and ~1.75 us in a graph (tools/lab/graph_gap.hip), and six of the
     // eight levels of the 200^3 hierarchy are too small to fill the chip.  PFEM_CG_GRAPH=0 turns it off.
@@ -3404,7 +3427,9 @@ int run_pcg_amg(pfem_solver *s)
                                          static_cast<uint64_t>(M.fused), static_cast<uint64_t>(M.tail_from + 1), static_cast<uint64_t>(M.coupled),
                                          static_cast<uint64_t>(M.cycle_gamma), static_cast<uint64_t>(M.w_to + 1),
                                          static_cast<uint64_t>(M.coupled_fused), reinterpret_cast<uint64_t>(s->d_send.p), reinterpret_cast<uint64_t>(s->d_recv.p),
-                                         reinterpret_cast<uint64_t>(s->comm), reinterpret_cast<uint64_t>(M.rep.get()), reinterpret_cast<uint64_t>(M.bx_glob.p)};
+                                         reinterpret_cast<uint64_t>(s->comm), reinterpret_cast<uint64_t>(M.rep.get()), reinterpret_cast<uint64_t>(M.bx_glob.p),
+                                         static_cast<uint64_t>(last0), ep0 ? reinterpret_cast<uint64_t>(s->d_part_ep.p) : 0, ep0 ? static_cast<uint64_t>(gs) : 0,
+                                         reinterpret_cast<uint64_t>(M.lev[0]->t.p), reinterpret_cast<uint64_t>(M.lev[0]->dinv.p)};
             auto level_key = [&](const std::unique_ptr<AmgLevel> &L) {
                 key.push_back(reinterpret_cast<uint64_t>(L->x)); key.push_back(reinterpret_cast<uint64_t>(L->vals.p)); key.push_back(static_cast<uint64_t>(L->n));
                 key.push_back(L->vd_ok ? static_cast<uint64_t>(L->vd_n + 1) : 0); key.push_back(reinterpret_cast<uint64_t>(L->vcodes.p));
@@ -3413,7 +3438,7 @@ int run_pcg_amg(pfem_solver *s)
             if (M.rep) for (auto &L : M.rep->lev) level_key(L);
             PFEM_TRY(M.graph.ensure(s->stream, std::move(key), {s->stream}, [&](int) {
                 if (M.coupled) return amg_apply_coupled(s, M, s->d_r.p, ctl, overlap) != nullptr;
-                (void)amg_apply(s, M, s->d_r.p, ctl, fuse_first0, fuse_last0);
+                (void)amg_apply(s, M, s->d_r.p, ctl, fuse_first0, last0);
                 return true;
             }, &use_vgraph));
         }
@@ -3422,16 +3447,24 @@ int run_pcg_amg(pfem_solver *s)
     auto precondition = [&](const CgCtl *c) -> double * {
         if (use_vgraph && c == ctl) {
             if (hipGraphLaunch(M.graph.exec[0], s->stream) != hipSuccess) return nullptr;
-            return M.lev[0]->x;
+            return ep0 ? M.lev[0]->t.p : M.lev[0]->x;
         }
         if (M.coupled) return amg_apply_coupled(s, M, s->d_r.p, c, overlap);      // z is the same on every holder already
-        double *z = amg_apply(s, M, s->d_r.p, c, c == ctl && fuse_first0, c == ctl && fuse_last0);
+        double *z = amg_apply(s, M, s->d_r.p, c, c == ctl && fuse_first0, c == ctl ? last0 : kLast0Smooth);
         if (c == ctl && fuse_last0) return z;            // the exchange follows the fused last step (dots lambda)
         if (multi && exchange_sum(s, z, overlap) != PFEM_OK) return nullptr;
         return z;
     };
     // (r,z), (z,z) over the owned rows; several ranks: summed into sbuf[2..3]
     auto dots = [&](double *z, const CgCtl *c, hipEvent_t *cev) -> int {
+        if (c == ctl && ep0) return PFEM_OK;             // (the cycle's last product left the folded sums)
+        if (c == ctl && rows4) {
+            hipLaunchKernelGGL(k_pc_dots_rows4, dim3(gs), block, 0, s->stream, c, s->n_owned, static_cast<const double *>(s->d_r.p),
+                               static_cast<const double *>(z), ep_rz, ep_zz);
+            hipLaunchKernelGGL(k_fold_partials2, dim3(kFoldBlocks, 2), block, 0, s->stream, static_cast<const double *>(ep_rz),
+                               static_cast<const double *>(ep_zz), static_cast<int>(gs), fold_rz, fold_zz, c);
+            return PFEM_OK;
+        }
         if (c == ctl && fuse_last0) {
             AmgLevel &L0 = *M.lev[0];
             hipLaunchKernelGGL(k_pc_post_dots, dim3(gv), block, 0, s->stream, c, n, s->n_owned, static_cast<const double *>(s->d_r.p),
@@ -3538,16 +3571,16 @@ int run_pcg_amg(pfem_solver *s)
         }
         {
             AmgLevel &L0 = *M.lev[0];
-            hipLaunchKernelGGL(k_pc_update, dim3(gv), block, 0, s->stream, ctl, it, n, pw_parts, pw_n, red_pw, static_cast<const double *>(s->d_p.p),
-                               static_cast<const double *>(s->d_w.p), s->d_x.p, s->d_r.p, L0.n, static_cast<const double *>(L0.dinv.p),
+            hipLaunchKernelGGL(k_pc_update, dim3(gv), block, 0, s->stream, ctl, it, n, pw_parts, pw_n, red_pw,
+                               static_cast<const double *>(s->d_w.p), s->d_r.p, L0.n, static_cast<const double *>(L0.dinv.p),
                                static_cast<const double *>(L0.lam.p), M.eig_ratio, fuse_first0 ? L0.x : static_cast<double *>(nullptr),
                                (fuse_first0 && deg0 > 1) ? L0.dd : static_cast<double *>(nullptr));
         }
         z = precondition(ctl);
         if (!z) return PFEM_ERR_COMM;
         PFEM_TRY(dots(z, ctl, cev));
-        hipLaunchKernelGGL(k_cg_direction_b, dim3(gv), block, 0, s->stream, ctl, it, n, static_cast<const double *>(part_rz),
-                           static_cast<const double *>(part_zz), static_cast<int>(gv), red2, static_cast<const double *>(z), s->d_p.p,
+        hipLaunchKernelGGL(k_pc_direction, dim3(gv), block, 0, s->stream, ctl, it, n, static_cast<const double *>(rows4 ? fold_rz : part_rz),
+                           static_cast<const double *>(rows4 ? fold_zz : part_zz), rows4 ? kFoldBlocks : static_cast<int>(gv), red2, static_cast<const double *>(z), s->d_p.p, s->d_x.p,
                            s->d_hist.p, s->hist_cap, s->maxits);
         return PFEM_OK;
     };

@@ -1903,13 +1903,14 @@ __global__ void __launch_bounds__(kBlock) k_pc_copy(int64_t n, const double *__r
 {
     for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < n; i += static_cast<int64_t>(gridDim.x) * kBlock) p[i] = z[i];
 }
-// alpha = beta/(p,w); x += alpha p; r -= alpha w.  A breakdown (p,w) <= 0 is handed to the dots kernel through ctl->pad_.
+// alpha = beta/(p,w); r -= alpha w.  The solution update x += alpha p is done by k_pc_direction, which holds p anyway (alpha
+// travels in ctl, as between k_cg_update and k_cg_direction).  A breakdown (p,w) <= 0 is handed to the dots kernel through ctl->pad_.
 // With z0 set the kernel also does step 0 of the V-cycle's pre-smoothing on the assembled matrix (zero guess:
 // z0 = dd0 = D^-1 r / theta over the first n_pc rows, what k_amg_cheb_first would compute from the r written here).
 __global__ void __launch_bounds__(kBlock) k_pc_update(CgCtl *ctl, int it, int64_t n, const double *part_pw, int nparts, const double *reduced_pw,
-                                                       const double *__restrict__ p, const double *__restrict__ w, double *__restrict__ x,
-                                                       double *__restrict__ r, int64_t n_pc, const double *__restrict__ dinv,
-                                                       const double *__restrict__ lam, double ratio, double *__restrict__ z0, double *__restrict__ dd0)
+                                                       const double *__restrict__ w, double *__restrict__ r, int64_t n_pc,
+                                                       const double *__restrict__ dinv, const double *__restrict__ lam, double ratio,
+                                                       double *__restrict__ z0, double *__restrict__ dd0)
 {
     __shared__ double sm[4];
     if (ctl->flag != 0) return;
@@ -1919,11 +1920,9 @@ __global__ void __launch_bounds__(kBlock) k_pc_update(CgCtl *ctl, int it, int64_
         return;
     }
     const double alpha = ctl->beta[it & 1] / pw;
+    if (blockIdx.x == 0 && threadIdx.x == 0) ctl->alpha = alpha;       // nobody in this launch reads it
     const double c_first = z0 ? cheb_coef(lam[0], ratio, 0).c_first : 0.0;
     for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < n; i += static_cast<int64_t>(gridDim.x) * kBlock) {
-        x[i] = __builtin_fma(alpha, p[i], x[i]);
-        // (x's pair of loads completes before r's is issued: with all four in flight the kernel took 86 instead of 81 us at config 3)
-        __builtin_amdgcn_sched_barrier(0);
         const double ri = __builtin_fma(-alpha, w[i], r[i]);
         r[i] = ri;
         if (z0 && i < n_pc) {
@@ -2039,6 +2038,78 @@ __global__ void __launch_bounds__(kBlock) k_pc_dots(const CgCtl *ctl, int64_t n,
     }
     const double a = block_sum(rz, sm), c = block_sum(zz, sm);
     if (threadIdx.x == 0) { part_rz[blockIdx.x] = a; part_zz[blockIdx.x] = c; }
+}
+
+// k_pc_dots with the partial sums laid out as the epilogue of level 0's last product lays them out (Level0Ep: one pair per block
+// of 1024 consecutive rows, thread t rows 4t .. 4t+3 in ascending order, the same block sum) -- behind a cycle that ran without
+// the epilogue (PFEM_AMG_FUSED=0, a fine degree other than 1), so that both give the CG the same bits.  Grid: the product's.
+__global__ void __launch_bounds__(kBlock) k_pc_dots_rows4(const CgCtl *ctl, int64_t n_owned, const double *__restrict__ r,
+                                                           const double *__restrict__ z, double *part_rz, double *part_zz)
+{
+    __shared__ double sm[4];
+    if (ctl && ctl->flag != 0) return;
+    if (ctl && ctl->pad_ != 0) {
+        if (threadIdx.x == 0) { part_rz[blockIdx.x] = 0.0; part_zz[blockIdx.x] = -1.0; }
+        return;
+    }
+    const int64_t r0 = (static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x) * kRelRows;
+    double rv[kRelRows], zv[kRelRows];
+    load_rows4(r, r0, n_owned, rv);
+    load_rows4(z, r0, n_owned, zv);
+    double rz = 0.0, zz = 0.0;
+#pragma unroll
+    for (int p = 0; p < kRelRows; ++p)
+        if (r0 + p < n_owned) {
+            rz = __builtin_fma(rv[p], zv[p], rz);
+            zz = __builtin_fma(zv[p], zv[p], zz);
+        }
+    const double a = block_sum(rz, sm), c = block_sum(zz, sm);
+    if (threadIdx.x == 0) { part_rz[blockIdx.x] = a; part_zz[blockIdx.x] = c; }
+}
+
+// finish (r,z), ||z||; x += alpha p (the step of THIS iteration, also when it turns out to be the last one: the test follows
+// the update; on a breakdown x is not advanced); convergence test; p = z + (beta_new/beta) p.  k_cg_direction with a stored z:
+// the same alpha and the same fma as when k_pc_update advanced x, one pass over p less per iteration.
+__global__ void __launch_bounds__(kBlock) k_pc_direction(CgCtl *ctl, int it, int64_t n, const double *part_rz, const double *part_zz, int nparts,
+                                                          const double *reduced, const double *__restrict__ z, double *__restrict__ p,
+                                                          double *__restrict__ x, double *hist, int hist_cap, int maxits)
+{
+    __shared__ double sm[4];
+    if (ctl_finished_before(ctl, it)) return;
+    double rz, zz;
+    if (reduced) { rz = reduced[0]; zz = reduced[1]; }
+    else { rz = sum_partials(part_rz, nparts, sm); zz = sum_partials(part_zz, nparts, sm); }
+    const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
+    if (zz < 0.0) {                          // breakdown flagged by k_pc_update: KSP_DIVERGED_INDEFINITE_MAT
+        if (lead) ctl_publish(ctl, -10, it + 1);
+        return;
+    }
+    const double rn = sqrt(zz);
+    const double beta_old = ctl->beta[it & 1];
+    int flag = 0;
+    if (rn <= ctl->ttol) flag = 2;
+    else if (rn >= ctl->dtol * ctl->rn0) flag = -4;
+    else if (rz < 0.0) flag = -8;
+    else if (it + 1 >= maxits) flag = -3;
+    if (lead) {
+        // other blocks of THIS launch read only beta[it&1]/ttol/dtol/rn0/alpha and test the verdict word against `it`
+        ctl->beta[(it + 1) & 1] = rz;
+        ctl->rn = rn;
+        if (it + 1 < hist_cap) hist[it + 1] = rn;
+        ctl_publish(ctl, flag, it + 1);
+    }
+    const double alpha = ctl->alpha;
+    if (flag != 0) {
+        for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < n; i += static_cast<int64_t>(gridDim.x) * kBlock)
+            __builtin_nontemporal_store(__builtin_fma(alpha, p[i], __builtin_nontemporal_load(x + i)), x + i);
+        return;
+    }
+    const double bb = rz / beta_old;
+    for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < n; i += static_cast<int64_t>(gridDim.x) * kBlock) {
+        const double pi = p[i];
+        __builtin_nontemporal_store(__builtin_fma(alpha, pi, __builtin_nontemporal_load(x + i)), x + i);
+        p[i] = __builtin_fma(bb, pi, z[i]);
+    }
 }
 
 }  // namespace pfem

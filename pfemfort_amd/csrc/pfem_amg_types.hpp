@@ -145,6 +145,7 @@ struct Amg {
     int cycle_gamma = 1, w_to = -1;
     bool cycle_given = false;
     bool fused = true;                               // fused SpMV epilogues on the coarse levels + the tail kernel (PFEM_AMG_FUSED=0: off)
+    bool level0_ep = false;                          // the last solve's iterations ran level 0's last product with its epilogue (Level0Ep)
     int coarsest_sweeps = 8;                         // Chebyshev degree on the last level when it is too large for the dense inverse
     // several ranks: one hierarchy ACROSS the ranks (aggregates stay inside a rank's owned dofs, the operators are the
     // global Galerkin products held sub-assembled, every SpMV of the cycle is followed by the level's neighbour exchange)

@@ -692,6 +692,7 @@ struct pfem_solver {
     // CG state
     DevBuf<double> d_part;     // 2 * kMaxGrid partial sums of the vector kernels + 2 reduced scalars
     DevBuf<double> d_part_pw;  // one (p,Ap) partial per SpMV block
+    DevBuf<double> d_part_ep;  // gamg on the 4-row forms: one (r,z) and one (z,z) partial per SpMV block + their 2 * kFoldBlocks folded sums
     DevBuf<CgCtl> d_ctl;
     DevBuf<double> d_hist;
     DevBuf<int> d_err;
@@ -2953,10 +2954,10 @@ void launch_spmv(pfem_solver *s, const double *x, double *y, int64_t n_dot, doub
         const double *d = s->d_vdict.p;
         const size_t lds = sizeof(double) * static_cast<size_t>(s->vd_n);
         if (s->rel_dict) {
-            if (e0) hipExtLaunchKernelGGL((k_spmvr_vd<WITH_DOT, true>), grid, block, lds, s->stream, e0, e1, 0, G, q, d, s->vd_n, s->n_loc, x, y, n_dot, partial, ctl, sel);
-            else hipLaunchKernelGGL((k_spmvr_vd<WITH_DOT, true>), grid, block, lds, s->stream, G, q, d, s->vd_n, s->n_loc, x, y, n_dot, partial, ctl, sel);
-        } else if (e0) hipExtLaunchKernelGGL((k_spmvr_vd<WITH_DOT, false>), grid, block, lds, s->stream, e0, e1, 0, G, q, d, s->vd_n, s->n_loc, x, y, n_dot, partial, ctl, sel);
-        else hipLaunchKernelGGL((k_spmvr_vd<WITH_DOT, false>), grid, block, lds, s->stream, G, q, d, s->vd_n, s->n_loc, x, y, n_dot, partial, ctl, sel);
+            if (e0) hipExtLaunchKernelGGL((k_spmvr_vd<WITH_DOT, true>), grid, block, lds, s->stream, e0, e1, 0, G, q, d, s->vd_n, s->n_loc, x, y, n_dot, partial, ctl, sel, Level0Ep{});
+            else hipLaunchKernelGGL((k_spmvr_vd<WITH_DOT, true>), grid, block, lds, s->stream, G, q, d, s->vd_n, s->n_loc, x, y, n_dot, partial, ctl, sel, Level0Ep{});
+        } else if (e0) hipExtLaunchKernelGGL((k_spmvr_vd<WITH_DOT, false>), grid, block, lds, s->stream, e0, e1, 0, G, q, d, s->vd_n, s->n_loc, x, y, n_dot, partial, ctl, sel, Level0Ep{});
+        else hipLaunchKernelGGL((k_spmvr_vd<WITH_DOT, false>), grid, block, lds, s->stream, G, q, d, s->vd_n, s->n_loc, x, y, n_dot, partial, ctl, sel, Level0Ep{});
     } else if (s->use_grouped()) {
         SellGDev G = s->sellg();
         if (s->row_dict) {
@@ -2970,10 +2971,10 @@ void launch_spmv(pfem_solver *s, const double *x, double *y, int64_t n_dot, doub
             if (e0) hipExtLaunchKernelGGL(k_spmvr32<WITH_DOT>, grid, block, 0, s->stream, e0, e1, 0, G, s->n_loc, x, y, n_dot, partial, ctl, sel);
             else hipLaunchKernelGGL(k_spmvr32<WITH_DOT>, grid, block, 0, s->stream, G, s->n_loc, x, y, n_dot, partial, ctl, sel);
         } else if (s->rel_dict) {
-            if (e0) hipExtLaunchKernelGGL((k_spmvr<WITH_DOT, true>), grid, block, 0, s->stream, e0, e1, 0, G, s->n_loc, x, y, n_dot, partial, ctl, sel);
-            else hipLaunchKernelGGL((k_spmvr<WITH_DOT, true>), grid, block, 0, s->stream, G, s->n_loc, x, y, n_dot, partial, ctl, sel);
-        } else if (e0) hipExtLaunchKernelGGL((k_spmvr<WITH_DOT, false>), grid, block, 0, s->stream, e0, e1, 0, G, s->n_loc, x, y, n_dot, partial, ctl, sel);
-        else hipLaunchKernelGGL((k_spmvr<WITH_DOT, false>), grid, block, 0, s->stream, G, s->n_loc, x, y, n_dot, partial, ctl, sel);
+            if (e0) hipExtLaunchKernelGGL((k_spmvr<WITH_DOT, true>), grid, block, 0, s->stream, e0, e1, 0, G, s->n_loc, x, y, n_dot, partial, ctl, sel, Level0Ep{});
+            else hipLaunchKernelGGL((k_spmvr<WITH_DOT, true>), grid, block, 0, s->stream, G, s->n_loc, x, y, n_dot, partial, ctl, sel, Level0Ep{});
+        } else if (e0) hipExtLaunchKernelGGL((k_spmvr<WITH_DOT, false>), grid, block, 0, s->stream, e0, e1, 0, G, s->n_loc, x, y, n_dot, partial, ctl, sel, Level0Ep{});
+        else hipLaunchKernelGGL((k_spmvr<WITH_DOT, false>), grid, block, 0, s->stream, G, s->n_loc, x, y, n_dot, partial, ctl, sel, Level0Ep{});
     } else if (s->cols16 && s->spmv_format != PFEM_SPMV_INT32) {
         Sell16Dev C{s->d_col0.p, s->d_dwords.p, s->d_slice_doff.p, s->d_row_gap_table.p};
         if (s->cols16_escape) {
@@ -2988,6 +2989,25 @@ void launch_spmv(pfem_solver *s, const double *x, double *y, int64_t n_dot, doub
         if (e0) hipExtLaunchKernelGGL(k_spmv<WITH_DOT>, grid, block, 0, s->stream, e0, e1, 0, A, x, y, n_dot, partial, ctl, sel);
         else hipLaunchKernelGGL(k_spmv<WITH_DOT>, grid, block, 0, s->stream, A, x, y, n_dot, partial, ctl, sel);
     }
+}
+
+// Level 0's product of gamg's up leg with the last smoothing step and the CG's (r,z), (z,z) as its epilogue (Level0Ep): the
+// relative-group forms with 16-bit gaps have one, with either value stream.  One rank (all slices, rows 1024 b .. of block b).
+inline bool spmv_has_level0_ep(const pfem_solver *s) { return s->use_rel() && !s->rel_gap32; }
+void launch_spmv_level0_ep(pfem_solver *s, const double *x, const Level0Ep &E, const CgCtl *ctl)
+{
+    const dim3 grid(spmv_blocks(s)), block(kBlock);
+    const SliceSel all{nullptr, 0};
+    SellRDev G = s->sellr();
+    double *none = nullptr;
+    if (s->vd_ok && s->vd_current && s->vd_rows == kRelRows) {
+        const unsigned long long *q = s->d_vcodes.p;
+        const double *d = s->d_vdict.p;
+        const size_t lds = sizeof(double) * static_cast<size_t>(s->vd_n);
+        if (s->rel_dict) hipLaunchKernelGGL((k_spmvr_vd<false, true, true>), grid, block, lds, s->stream, G, q, d, s->vd_n, s->n_loc, x, none, static_cast<int64_t>(0), none, ctl, all, E);
+        else hipLaunchKernelGGL((k_spmvr_vd<false, false, true>), grid, block, lds, s->stream, G, q, d, s->vd_n, s->n_loc, x, none, static_cast<int64_t>(0), none, ctl, all, E);
+    } else if (s->rel_dict) hipLaunchKernelGGL((k_spmvr<false, true, true>), grid, block, 0, s->stream, G, s->n_loc, x, none, static_cast<int64_t>(0), none, ctl, all, E);
+    else hipLaunchKernelGGL((k_spmvr<false, false, true>), grid, block, 0, s->stream, G, s->n_loc, x, none, static_cast<int64_t>(0), none, ctl, all, E);
 }
 
 }  // namespace
@@ -5189,6 +5209,15 @@ extern "C" int pfem_solver_set_amg_cycle(pfem_solver *s, int cycle)
     s->amg->graph.invalidate();
     return PFEM_OK;
 }
+// did the iterations of the last gamg solve run level 0's last product with its epilogue (Level0Ep)?
+extern "C" int pfem_solver_amg_level0_epilogue(pfem_solver *s, int *taken)
+{
+    if (!s || !taken) return PFEM_ERR_ARG;
+    if (!s->amg || !s->amg->symbolic_ok) return PFEM_ERR_STATE;
+    *taken = s->amg->level0_ep ? 1 : 0;
+    return PFEM_OK;
+}
+
 // what the last gamg solve ran: 1 = V, 2 = W, and the last level whose problem got two visits
 extern "C" int pfem_solver_amg_cycle(pfem_solver *s, int *cycle, int *last_level_visited_twice)
 {

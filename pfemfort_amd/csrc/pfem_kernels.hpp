@@ -2272,6 +2272,20 @@ __global__ void __launch_bounds__(kBlock) k_fold_partials(const double *__restri
     const double t = block_sum(a, sm);
     if (threadIdx.x == 0) out[blockIdx.x] = t;
 }
+// the same for two arrays of n partials in one launch (grid kFoldBlocks x 2: the (r,z) and (z,z) partials of Level0Ep)
+__global__ void __launch_bounds__(kBlock) k_fold_partials2(const double *__restrict__ part0, const double *__restrict__ part1, int n, double *out0,
+                                                            double *out1, const CgCtl *ctl)
+{
+    __shared__ double sm[4];
+    if (ctl && ctl->flag != 0) return;
+    const double *__restrict__ part = blockIdx.y ? part1 : part0;
+    const int chunk = (n + kFoldBlocks - 1) / kFoldBlocks;
+    const int lo = blockIdx.x * chunk, hi = min(n, lo + chunk);
+    double a = 0.0;
+    for (int i = lo + threadIdx.x; i < hi; i += kBlock) a += part[i];
+    const double t = block_sum(a, sm);
+    if (threadIdx.x == 0) (blockIdx.y ? out1 : out0)[blockIdx.x] = t;
+}
 
 // ---------------------------------------------------------------------------
 // Jacobi-PCG vector kernels (PETSc KSPCG semantics)
@@ -2733,26 +2747,84 @@ __device__ __forceinline__ void load_x4(const double *__restrict__ x, int c, dou
     xv[0] = a.x; xv[1] = a.y; xv[2] = b.x; xv[3] = b.y;
 }
 
-template <bool WITH_DOT, bool DICT = false>
+// v[p] = a[r0 + p] for the rows below n (the ragged last lane: 0 beyond); two 16-B loads where all four rows exist
+__device__ __forceinline__ void load_rows4(const double *__restrict__ a, int64_t r0, int64_t n, double (&v)[kRelRows])
+{
+    if (r0 + kRelRows <= n) {
+        const pfem_double2u lo = *reinterpret_cast<const pfem_double2u *>(a + r0);
+        const pfem_double2u hi = *reinterpret_cast<const pfem_double2u *>(a + r0 + 2);
+        v[0] = lo.x; v[1] = lo.y; v[2] = hi.x; v[3] = hi.y;
+    } else {
+#pragma unroll
+        for (int p = 0; p < kRelRows; ++p) v[p] = r0 + p < n ? a[r0 + p] : 0.0;
+    }
+}
+
+// Epilogue of the relative-group products with 16-bit gaps (k_spmvr / k_spmvr_vd<false, DICT, true>) for the last product of
+// gamg's V-cycle on the assembled matrix, t = A x on the way up with a fine Chebyshev degree of 1.  The lane that owns rows
+// r0 .. r0+3 has t_i in registers when its fma chain ends, so the last post-smoothing step and the CG's two sums are done there:
+//     z_i = x_i + c D^-1_ii (r_i - t_i),   (r,z) += r_i z_i,   (z,z) += z_i z_i      (k_pc_post_dots' expression: z keeps its bits)
+// instead of t going to memory and coming back with x, r and D^-1 in a vector kernel of its own.  z goes to a vector that is
+// NOT the product's input (other waves still gather x).  The sums leave as one pair of partials per block: block b holds rows
+// 1024 b .. 1024 b + 1023, thread t rows 4t .. 4t+3 in ascending order, waves summed as (w0 + w1) + (w2 + w3) -- the layout
+// k_pc_dots_rows4 reproduces behind an unfused cycle.  The control block's two early exits are k_pc_post_dots': nothing once the
+// solve has finished; after a breakdown flagged by k_pc_update every block leaves (0, -1).
+struct Level0Ep {
+    const double *r, *dinv, *lam;      // the CG's residual, level 0's inverse diagonal and eigenvalue bound
+    double ratio;
+    double *z;
+    double *part_rz, *part_zz;         // one entry per block of the product
+};
+__device__ __forceinline__ double cheb_first_coef(double lmax, double ratio)       // cheb_coef(lmax, ratio, 0).c_first
+{
+    const double lmin = lmax / ratio, theta = 0.5 * (lmax + lmin);
+    return 1.0 / theta;
+}
+__device__ __forceinline__ void level0_ep_rows(const Level0Ep &E, double c_first, int64_t r0, int64_t n_rows, const double (&xs)[kRelRows],
+                                               const double (&rv)[kRelRows], const double (&dv)[kRelRows], const double (&acc)[kRelRows],
+                                               double &rz, double &zz)
+{
+#pragma unroll
+    for (int p = 0; p < kRelRows; ++p)
+        if (r0 + p < n_rows) {
+            const double ri = rv[p];
+            const double zi = xs[p] + c_first * dv[p] * (ri - acc[p]);
+            E.z[r0 + p] = zi;
+            rz = __builtin_fma(ri, zi, rz);
+            zz = __builtin_fma(zi, zi, zz);
+        }
+}
+
+template <bool WITH_DOT, bool DICT = false, bool EP = false>
 __global__ void __launch_bounds__(kBlock) k_spmvr(SellRDev G, int64_t n_rows, const double *__restrict__ x,
                                                    double *__restrict__ y, int64_t n_dot, double *partial, const CgCtl *ctl,
-                                                   SliceSel sel)
+                                                   SliceSel sel, Level0Ep E)
 {
-    __shared__ double sm[4];
+    static_assert(!(WITH_DOT && EP), "the epilogue belongs to the cycle's product, the (p,Ap) partial to the CG's");
+    __shared__ double sm[4], sm2[4];
+    __shared__ int done_rz, done_zz;
     __shared__ uint32_t gap_tbl[DICT ? kGapTable : 1];
     if (WITH_DOT && ctl->flag != 0) return;
+    if (EP) {
+        if (ctl->flag != 0) return;
+        if (ctl->pad_ != 0) {
+            if (threadIdx.x == 0) { E.part_rz[blockIdx.x] = 0.0; E.part_zz[blockIdx.x] = -1.0; }
+            return;
+        }
+        if (threadIdx.x == 0) { done_rz = 0; done_zz = 0; }
+    }
     if (DICT) {
         static_assert(kGapTable == kBlock, "one table entry per thread");
         gap_tbl[DICT ? threadIdx.x : 0] = G.gap_table[threadIdx.x];
-        __syncthreads();
     }
+    if (DICT || EP) __syncthreads();
     // a 16-bit code of the gap stream -> the gap (dictionary form: codes with the top bit set index the table)
     const auto gap_of = [&](uint32_t code) -> int {
         return (DICT && (code & 0x8000u)) ? static_cast<int>(gap_tbl[DICT ? (code & (kGapTable - 1)) : 0]) : static_cast<int>(code);
     };
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t gs = pick_slice(sel, (static_cast<int64_t>(blockIdx.x) << 2) + wave, G.n_gslices);
-    double dot = 0.0;
+    double dot = 0.0, zz = 0.0;
     if (gs < G.n_gslices) {
         const int64_t off = G.gslice_off[gs];
         const int width = static_cast<int>((G.gslice_off[gs + 1] - off) >> 6);
@@ -2791,6 +2863,16 @@ __global__ void __launch_bounds__(kBlock) k_spmvr(SellRDev G, int64_t n_rows, co
 #pragma unroll
                 for (int p = 0; p < kRelRows; ++p) acc[p] = __builtin_fma(v[t][p], xv[t][p], acc[p]);
         }
+        // (the epilogue's operands: requested when the last full trip is over and its registers are free again, in flight
+        // together with the remainder's loads -- the register count of the plain product.  Requested with the wave's first
+        // loads instead they cost 10 / 24 registers and measured the same: the epilogue's 20 us are its bytes; LAB_NOTES)
+        const int64_t r0 = ((gs << 6) + lane) * kRelRows;
+        double xs[kRelRows] = {0.0, 0.0, 0.0, 0.0}, rv[kRelRows] = {0.0, 0.0, 0.0, 0.0}, dv[kRelRows] = {0.0, 0.0, 0.0, 0.0};
+        if (EP) {
+            load_x4(x, static_cast<int>(r0), xs);
+            load_rows4(E.r, r0, n_rows, rv);
+            load_rows4(E.dinv, r0, n_rows, dv);
+        }
         for (; j < nw; ++j) {
             const uint32_t w0 = __builtin_nontemporal_load(wp + 64 * j);
             const int c0 = c + gap_of(w0 & 0xffffu);
@@ -2808,17 +2890,23 @@ __global__ void __launch_bounds__(kBlock) k_spmvr(SellRDev G, int64_t n_rows, co
             }
             c = c1;
         }
-        const int64_t r0 = ((gs << 6) + lane) * kRelRows;
+        if (EP) level0_ep_rows(E, cheb_first_coef(E.lam[0], E.ratio), r0, n_rows, xs, rv, dv, acc, dot, zz);
+        else {
 #pragma unroll
         for (int p = 0; p < kRelRows; ++p)
             if (r0 + p < n_rows) {
                 y[r0 + p] = acc[p];
                 if (WITH_DOT && r0 + p < n_dot) dot = __builtin_fma(x[r0 + p], acc[p], dot);
             }
+        }
     }
     if (WITH_DOT) {
         const double t = block_sum(dot, sm);
         if (threadIdx.x == 0) partial[blockIdx.x] = t;
+    }
+    if (EP) {                               // (dot holds the lane's share of (r,z) here)
+        block_sum_last_wave(dot, sm, &done_rz, E.part_rz + blockIdx.x);
+        block_sum_last_wave(zz, sm2, &done_zz, E.part_zz + blockIdx.x);
     }
 }
 

@@ -179,20 +179,23 @@ __global__ void __launch_bounds__(kBlock) k_vd_encode16(const double *__restrict
 }
 
 // ---- the SpMVs of pfem_kernels.hpp over the codes: same slices, same lanes, same order of the fma chain, same partials ----
-template <bool WITH_DOT, bool DICT>
+// (EP: the product of gamg's up leg on level 0 with the last smoothing step and the CG's sums as its epilogue -- Level0Ep)
+template <bool WITH_DOT, bool DICT, bool EP = false>
 __global__ void __launch_bounds__(kBlock) k_spmvr_vd(SellRDev G, const unsigned long long *__restrict__ codes, const double *__restrict__ dict, int nd,
                                                       int64_t n_rows, const double *__restrict__ x, double *__restrict__ y, int64_t n_dot,
-                                                      double *partial, const CgCtl *ctl, SliceSel sel)
+                                                      double *partial, const CgCtl *ctl, SliceSel sel, Level0Ep E)
 {
+    static_assert(!(WITH_DOT && EP), "the epilogue belongs to the cycle's product, the (p,Ap) partial to the CG's");
     const unsigned vblock = blockIdx.x;
     extern __shared__ double vd[];
-    __shared__ double sm[4];
-    __shared__ int done_waves;
+    __shared__ double sm[4], sm2[4];
+    __shared__ int done_waves, done_zz;
     __shared__ uint32_t gap_tbl[DICT ? kGapTable : 1];
     // (the CG's verdict: requested here, looked at behind the barrier below -- the wave's first loads go out without waiting for it;
     // an iteration enqueued after the verdict still leaves before its main loop)
-    const int finished = WITH_DOT ? __builtin_nontemporal_load(&ctl->flag) : 0;
-    if (WITH_DOT && threadIdx.x == 0) done_waves = 0;         // (before the barrier below)
+    const int finished = (WITH_DOT || EP) ? __builtin_nontemporal_load(&ctl->flag) : 0;
+    const int broke = EP ? __builtin_nontemporal_load(&ctl->pad_) : 0;
+    if ((WITH_DOT || EP) && threadIdx.x == 0) { done_waves = 0; done_zz = 0; }         // (before the barrier below)
     // A wave's life is a chain of memory latencies (rocprofv3 --pmc: 58 % of the wave cycles waiting; with an XCD-contiguous block
     // order the fabric traffic falls from 0.59 GB to its ideal 0.36 GB and the time does not move -- LAB_NOTES): slice header ->
     // first entry -> trips of four entries -> remainder.  So the header, the first entry's operands and the first gap words are requested BEFORE the dictionary is copied to LDS,
@@ -224,11 +227,15 @@ __global__ void __launch_bounds__(kBlock) k_spmvr_vd(SellRDev G, const unsigned 
     for (int i = threadIdx.x; i < nd; i += kBlock) vd[i] = dict[i];
     if (DICT) gap_tbl[DICT ? threadIdx.x : 0] = G.gap_table[threadIdx.x];
     __syncthreads();
-    if (WITH_DOT && finished != 0) return;
+    if ((WITH_DOT || EP) && finished != 0) return;
+    if (EP && broke != 0) {
+        if (threadIdx.x == 0) { E.part_rz[vblock] = 0.0; E.part_zz[vblock] = -1.0; }
+        return;
+    }
     const auto gap_of = [&](uint32_t code) -> int {
         return (DICT && (code & 0x8000u)) ? static_cast<int>(gap_tbl[DICT ? (code & (kGapTable - 1)) : 0]) : static_cast<int>(code);
     };
-    double dot = 0.0;
+    double dot = 0.0, zz = 0.0;
     if (live) {
         double acc[kRelRows] = {0.0, 0.0, 0.0, 0.0};
         bool first_pending = width > 0;
@@ -255,6 +262,16 @@ __global__ void __launch_bounds__(kBlock) k_spmvr_vd(SellRDev G, const unsigned 
             for (int t = 0; t < 4; ++t)
 #pragma unroll
                 for (int p = 0; p < kRelRows; ++p) acc[p] = __builtin_fma(vd[(q[t] >> (16 * p)) & 0xffffu], xv[t][p], acc[p]);
+        }
+        // (the epilogue's operands: requested when the last full trip is over and its registers are free again, in flight
+        // together with the remainder's loads -- the register count of the plain product.  Requested with the wave's first
+        // loads instead they cost 10 / 24 registers and measured the same: the epilogue's 20 us are its bytes; LAB_NOTES)
+        const int64_t r0 = ((gs << 6) + lane) * kRelRows;
+        double rv[kRelRows] = {0.0, 0.0, 0.0, 0.0}, dv[kRelRows] = {0.0, 0.0, 0.0, 0.0};
+        if (EP) {
+            load_x4(x, static_cast<int>(r0), xself);
+            load_rows4(E.r, r0, n_rows, rv);
+            load_rows4(E.dinv, r0, n_rows, dv);
         }
         const int rem = width - 1 - 2 * j;          // 0 .. 3 entries are left (the same for the whole wave)
         if (rem > 0) {
@@ -286,15 +303,21 @@ __global__ void __launch_bounds__(kBlock) k_spmvr_vd(SellRDev G, const unsigned 
 #pragma unroll
             for (int p = 0; p < kRelRows; ++p) acc[p] = vd[(q0 >> (16 * p)) & 0xffffu] * x0[p];
         }
-        const int64_t r0 = ((gs << 6) + lane) * kRelRows;
+        if (EP) level0_ep_rows(E, cheb_first_coef(E.lam[0], E.ratio), r0, n_rows, xself, rv, dv, acc, dot, zz);
+        else {
 #pragma unroll
         for (int p = 0; p < kRelRows; ++p)
             if (r0 + p < n_rows) {
                 y[r0 + p] = acc[p];
                 if (WITH_DOT && r0 + p < n_dot) dot = __builtin_fma(xself[p], acc[p], dot);
             }
+        }
     }
     if (WITH_DOT) block_sum_last_wave(dot, sm, &done_waves, partial + vblock);      // (no barrier at the end of a wave's life)
+    if (EP) {                               // (dot holds the lane's share of (r,z) here)
+        block_sum_last_wave(dot, sm, &done_waves, E.part_rz + vblock);
+        block_sum_last_wave(zz, sm2, &done_zz, E.part_zz + vblock);
+    }
 }
 
 // W words = 2W consecutive entries of the node's rows (k_spmvg's trip over the codes)

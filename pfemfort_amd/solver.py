@@ -259,10 +259,12 @@ class PetscSolver:
         L.check(L.lib().pfem_solver_set_amg_cycle(self._h, code), "pfem_solver_set_amg_cycle")
 
     def amgCycle(self):
-        """What the last gamg solve ran: {"cycle": "v" | "w", "last_level_visited_twice": l} (0 with the V-cycle)."""
-        c, w = C.c_int(0), C.c_int(0)
+        """What the last gamg solve ran: {"cycle": "v" | "w", "last_level_visited_twice": l (0 with the V-cycle),
+        "level0_epilogue": the cycle's last fine product carried the final smoothing step and the CG's sums}."""
+        c, w, e = C.c_int(0), C.c_int(0), C.c_int(0)
         L.check(L.lib().pfem_solver_amg_cycle(self._h, C.byref(c), C.byref(w)), "pfem_solver_amg_cycle")
-        return {"cycle": "w" if c.value == 2 else "v", "last_level_visited_twice": w.value}
+        L.check(L.lib().pfem_solver_amg_level0_epilogue(self._h, C.byref(e)), "pfem_solver_amg_level0_epilogue")
+        return {"cycle": "w" if c.value == 2 else "v", "last_level_visited_twice": w.value, "level0_epilogue": bool(e.value)}
 
     def amgTransfer(self, level, xyz=False):
         """The transfer from ``level`` to the next: {"rbm": carries rotations?, "fine_bs", "coarse_bs", "dim", "n_nodes"} and, with
