@@ -114,6 +114,13 @@ int pfem_solver_amg_cycle(pfem_solver *s, int *cycle, int *last_level_visited_tw
  * step and the CG's (r,z), (z,z) as its epilogue (one rank, a 4-row relative-group SpMV form with 16-bit gaps, fine degree 1,
  * PFEM_AMG_FUSED not 0); 0 when they took the stand-alone kernels                                                          */
 int pfem_solver_amg_level0_epilogue(pfem_solver *s, int *taken);
+/* 1 when the numeric phase of the last gamg solve formed level 1 from the SpMV's 16-bit value codes (one rank, a scalar brick
+ * level 0 whose 4-row relative-group form streams codes that hold the current values; PFEM_AMG_GALERKIN_CODES not 0); 0 when it
+ * read the fp64 row form (the first step of a pattern forms the level in the symbolic phase: 0 as well).  Same bits either way. */
+int pfem_solver_amg_galerkin_from_codes(pfem_solver *s, int *taken);
+/* the stored values of coarse level `level` (>= 1) of the last hierarchy in slot order, padding included: *stored of them, the
+ * first min(max_values, *stored) copied to vals (max_values = 0: the count alone)                                             */
+int pfem_solver_amg_level_values(pfem_solver *s, int level, int64_t max_values, double *vals, int64_t *stored);
 
 /* Per-element Ke/Fe of the uploaded mesh as computed by the DEVICE kernel (parity
  * inspection): K_out[e*nsize*nsize + i + nsize*j], F_out[e*nsize + i].           */

@@ -671,7 +671,9 @@ inline bool amg_galerkin_by_entry()
 }
 // `extras` (numeric phase of a one-rank hierarchy): the product also leaves C's inverse diagonal and Gershgorin ratios (C.dinv,
 // C.t) and, where C streams value codes and has a dictionary with its hash table, C's codes (verdict word `vstate`, reset here)
-inline void amg_galerkin(pfem_solver *s, const AmgLevel &L, AmgLevel &C, const SellDev &A, bool extras = false, VdState *vstate = nullptr)
+// `from_codes` (level 0, amg_level0_codes said yes): the values are read as the SpMV's 16-bit codes instead of the row form's doubles
+inline void amg_galerkin(pfem_solver *s, const AmgLevel &L, AmgLevel &C, const SellDev &A, bool extras = false, VdState *vstate = nullptr,
+                         bool from_codes = false)
 {
     C.bound_fresh = C.vd_direct = false;
     if (L.code_of.p && !amg_galerkin_by_entry()) {
@@ -689,6 +691,15 @@ inline void amg_galerkin(pfem_solver *s, const AmgLevel &L, AmgLevel &C, const S
                 X.vstate = vstate;
                 C.vd_direct = true;
             }
+        }
+        if (from_codes) {
+            hipLaunchKernelGGL(k_lat_galerkin_codes, dim3(static_cast<unsigned>((C.n_loc + kLatGalThreads - 1) / kLatGalThreads)), dim3(kLatGalThreads),
+                               sizeof(double) * static_cast<size_t>(std::max(s->vd_n, 1)), s->stream, C.n_loc, static_cast<const int32_t *>(L.mem_ptr.p),
+                               static_cast<const int32_t *>(L.mem_idx.p), static_cast<const int64_t *>(s->d_rslice_off.p),
+                               static_cast<const unsigned long long *>(s->d_vcodes.p), static_cast<const uint32_t *>(L.glat.p),
+                               static_cast<const double *>(s->d_vdict.p), s->vd_n, static_cast<const uint32_t *>(L.code_mask.p),
+                               static_cast<const int64_t *>(C.slice_off.p), C.vals.p, X);
+            return;
         }
         hipLaunchKernelGGL(k_lat_galerkin, dim3(static_cast<unsigned>((C.n_loc + kLatGalThreads - 1) / kLatGalThreads)), dim3(kLatGalThreads), 0, s->stream, A, C.n_loc,
                            static_cast<const int32_t *>(L.mem_ptr.p), static_cast<const int32_t *>(L.mem_idx.p), static_cast<const uint8_t *>(L.code_of.p),
@@ -2917,8 +2928,46 @@ int amg_value_codes(pfem_solver *s, Amg &M)
     return PFEM_OK;
 }
 
+// May this numeric phase form level 1 from the SpMV's value codes (k_lat_galerkin_codes)?  One rank, a scalar brick level 0 without
+// hubs whose SpMV streams the 4-row relative-group form's 16-bit codes, and those codes hold THIS assembly's values against the
+// dictionary in place: vd_ok && vd_current, the very condition under which the CG's products read them (refresh_group_vals ran
+// before this phase: the assembly kernel's verdict has been read and was clean, or k_vd_encode has encoded the fp64 copy).  A step
+// whose assembly met a value the dictionary lacked keeps the fp64 kernel (vd_miss_step), like every other case.
+// PFEM_AMG_GALERKIN_CODES=0 (read at every phase): k_lat_galerkin as before.  The form's lattice codes are built at the first yes.
+int amg_level0_codes(pfem_solver *s, Amg &M, AmgLevel &L, bool *yes)
+{
+    *yes = false;
+    const char *e = std::getenv("PFEM_AMG_GALERKIN_CODES");
+    if (e && std::atoi(e) == 0) return PFEM_OK;
+    if (&M != s->amg.get() || M.coupled || M.rbm || cg_multi(s) || !L.fine || L.rbm || L.bs != 1 || !L.code_of.p || !L.code_mask.p || amg_galerkin_by_entry() ||
+        s->n_hubs != 0 || L.stored != s->stored || L.glat_refused)
+        return PFEM_OK;
+    if (!valdict_enabled() || !s->use_rel() || s->rel_gap32 || s->vd_rows != kRelRows || !(s->vd_ok && s->vd_current && s->vd_have_dict) || s->vd_miss_step ||
+        s->vd_n < 1 || s->vd_n > kVdMax || !s->d_vcodes.p || !s->d_vdict.p || !s->d_relk.p || !s->d_rslice_off.p || s->r_stored < 1 ||
+        s->d_vcodes.n < static_cast<size_t>(s->r_stored))
+        return PFEM_OK;
+    if (!L.glat.p || L.glat_for != s->r_stored) {
+        PFEM_TRY(L.glat.alloc(static_cast<size_t>(s->r_stored)));
+        L.glat_for = -1;
+        PFEM_HIP(hipMemsetAsync(L.glat.p, 0xff, sizeof(uint32_t) * static_cast<size_t>(s->r_stored), s->stream));
+        PFEM_HIP(hipMemsetAsync(s->d_err.p, 0, sizeof(int), s->stream));
+        hipLaunchKernelGGL(k_lat_group_codes, dim3(grid_for(L.n)), dim3(kBlock), 0, s->stream, amg_sell(s, L), static_cast<const uint8_t *>(L.code_of.p),
+                           static_cast<const uint8_t *>(s->d_relk.p), static_cast<const int64_t *>(s->d_rslice_off.p), reinterpret_cast<uint8_t *>(L.glat.p),
+                           s->d_err.p);
+        PFEM_TRY(check_kernel("k_lat_group_codes"));
+        int bad = 0;
+        PFEM_TRY(fetch_err(s, &bad));
+        PFEM_HIP(hipMemsetAsync(s->d_err.p, 0, sizeof(int), s->stream));
+        if (bad) { L.glat.release(); L.glat_refused = true; return PFEM_OK; }
+        L.glat_for = s->r_stored;
+    }
+    *yes = true;
+    return PFEM_OK;
+}
+
 int amg_numeric(pfem_solver *s, Amg &M, bool overlap)
 {
+    M.galerkin_from_codes = false;
     if (M.coupled) return amg_numeric_coupled(s, M, overlap);
     const bool fresh = M.galerkin_fresh;
     M.galerkin_fresh = false;
@@ -2928,7 +2977,14 @@ int amg_numeric(pfem_solver *s, Amg &M, bool overlap)
         if (l + 1 < M.lev.size() && !fresh) {
             AmgLevel &C = *M.lev[l + 1];
             if (L.rbm) amg_rbm_galerkin(s, L, C, A);
-            else amg_galerkin(s, L, C, A, !M.rbm && !M.coupled, M.vd_states.p ? M.vd_states.p + (l + 1) : nullptr);
+            else {
+                bool from_codes = false;
+                if (l == 0) PFEM_TRY(amg_level0_codes(s, M, L, &from_codes));
+                amg_galerkin(s, L, C, A, !M.rbm && !M.coupled, M.vd_states.p ? M.vd_states.p + (l + 1) : nullptr, from_codes);
+                if (from_codes) M.galerkin_from_codes = true;
+                if (l == 0 && std::getenv("PFEM_VD_VERBOSE"))
+                    std::fprintf(stderr, "  gamg numeric: level 1 summed from %s\n", from_codes ? "the SpMV's value codes" : "the fp64 row form");
+            }
         }
         const unsigned g = grid_for(A.n_slices * 64);
         if (!L.fine && L.bound_fresh && !fresh) {

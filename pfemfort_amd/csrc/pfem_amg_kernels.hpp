@@ -536,6 +536,37 @@ struct LatGalExtra {
     uint16_t *codes;                       // [coarse stored]
     VdState *vstate;
 };
+// the coarse row a thread has summed in acc[.][t]: the occupied codes in ascending order = the row's entries, and LatGalExtra's by-products
+__device__ __forceinline__ void lat_galerkin_row_out(const double (&acc)[kLatCodes][kLatGalThreads], int t, int64_t I, const uint32_t *__restrict__ code_mask,
+                                                     const int64_t *__restrict__ c_slice_off, double *__restrict__ coarse_vals, const LatGalExtra &X)
+{
+    const int64_t out0 = c_slice_off[I >> 6] + (I & 63);
+    double *out = coarse_vals + out0;
+    const uint32_t mask = code_mask[I];
+    int r = 0;
+    double sabs = 0.0;
+    bool missed = false;
+#pragma unroll
+    for (int c = 0; c < kLatCodes; ++c)
+        if (mask & (1u << c)) {
+            const double v = acc[c][t];
+            out[64LL * r] = v;
+            sabs += fabs(v);
+            if (X.vhash) {
+                int code = vd_hash_find(X.vhash, static_cast<unsigned long long>(__double_as_longlong(v)));
+                if (code < 0) { missed = true; code = 0; }
+                X.codes[out0 + 64LL * r] = static_cast<uint16_t>(code);
+            }
+            ++r;
+        }
+    if (X.dinv_out) {
+        const double d = (mask & (1u << 13)) ? acc[13][t] : 0.0;
+        const bool pos = d > 0.0;
+        X.dinv_out[I] = pos ? 1.0 / d : 1.0;
+        X.ratio_out[I] = pos ? sabs / d : 1.0;
+    }
+    if (missed) X.vstate->miss = 1;
+}
 // (Tried and dropped, round 6: the 27 accumulators in REGISTERS -- the code of "entry k of member j" is the same in nearly every lane
 // of a wave on a lattice, so it was read from one lane and the lanes that agree added under a wave-uniform switch, the others in
 // further turns.  Occupancy 10 -> 16 waves a CU and no LDS round trips, yet level 0 took 677 us against 545 and the small levels --
@@ -581,32 +612,94 @@ __global__ void __launch_bounds__(kLatGalThreads) k_lat_galerkin(SellDev A, int6
             }
         }
     }
-    const int64_t out0 = c_slice_off[I >> 6] + (I & 63);
-    double *out = coarse_vals + out0;
-    const uint32_t mask = code_mask[I];
-    int r = 0;
-    double sabs = 0.0;
-    bool missed = false;
-#pragma unroll
-    for (int c = 0; c < kLatCodes; ++c)
-        if (mask & (1u << c)) {
-            const double v = acc[c][t];
-            out[64LL * r] = v;
-            sabs += fabs(v);
-            if (X.vhash) {
-                int code = vd_hash_find(X.vhash, static_cast<unsigned long long>(__double_as_longlong(v)));
-                if (code < 0) { missed = true; code = 0; }
-                X.codes[out0 + 64LL * r] = static_cast<uint16_t>(code);
-            }
-            ++r;
-        }
-    if (X.dinv_out) {
-        const double d = (mask & (1u << 13)) ? acc[13][t] : 0.0;
-        const bool pos = d > 0.0;
-        X.dinv_out[I] = pos ? 1.0 / d : 1.0;
-        X.ratio_out[I] = pos ? sabs / d : 1.0;
+    lat_galerkin_row_out(acc, t, I, code_mask, c_slice_off, coarse_vals, X);
+}
+// ---- level 0's product from the SpMV's value codes ----------------------------------------------------------------------------
+// On a warm step the assembled values exist twice: as the row form's doubles (what k_lat_galerkin reads, 8 + 1 B a slot) and,
+// losslessly, as the 4-row relative-group form's 16-bit codes into the dictionary of distinct values (pfem_valdict.hpp; dict[code]
+// is the very double the assembly wrote).  k_lat_galerkin_codes sums the same coarse rows from the codes: 2 B of code + 1 B of
+// lattice offset code a slot, the dictionary in LDS.  The lattice codes of the group form (glat) lie parallel to the code words:
+// word i = off + 64 k + lane of the form holds four 16-bit value codes, glat[i] four bytes, one per row of the group; 0xff marks
+// an explicit zero of the union (a slot the row form does not have: skipped, not added).
+// Same additions in the same order as k_lat_galerkin: member rows ascending, a row's entries in ascending column order (the union
+// is stored in ascending relative column).  Every coarse value keeps its bits.
+// The two fine rows of a brick's x-pair mostly sit in one group: the thread keeps the group's words in registers for the second.
+constexpr int kLatGalChunk = 16;
+// glat from the row form's lattice codes (code_of) through the slot -> union entry map (relk): one thread per fine row
+__global__ void __launch_bounds__(kBlock) k_lat_group_codes(SellDev A, const uint8_t *__restrict__ code_of, const uint8_t *__restrict__ relk,
+                                                             const int64_t *__restrict__ rslice_off, uint8_t *__restrict__ glat, int *__restrict__ bad)
+{
+    const int64_t r = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    if (r >= A.n_rows) return;
+    const int64_t base = A.slice_off[r >> 6] + (r & 63);
+    const int len = A.rowlen[r];
+    const int64_t g = r >> 2;
+    const int64_t off = rslice_off[g >> 6];
+    const int width = static_cast<int>((rslice_off[(g >> 6) + 1] - off) >> 6);
+    uint8_t *gp = glat + 4 * (off + (g & 63)) + (r & 3);
+    for (int k = 0; k < len; ++k) {
+        const int64_t q = base + 64LL * k;
+        const int u = relk[q];
+        if (u >= width) { *bad = 1; continue; }         // (0xff: a slot without a union entry -- the map does not cover this form)
+        gp[4LL * 64 * u] = code_of[q];
     }
-    if (missed) X.vstate->miss = 1;
+}
+__global__ void __launch_bounds__(kLatGalThreads) k_lat_galerkin_codes(int64_t na, const int32_t *__restrict__ mem_ptr, const int32_t *__restrict__ mem_idx,
+                                                                        const int64_t *__restrict__ rslice_off, const unsigned long long *__restrict__ vcodes,
+                                                                        const uint32_t *__restrict__ glat, const double *__restrict__ dict, int nd,
+                                                                        const uint32_t *__restrict__ code_mask, const int64_t *__restrict__ c_slice_off,
+                                                                        double *__restrict__ coarse_vals, LatGalExtra X)
+{
+    __shared__ double acc[kLatCodes][kLatGalThreads];
+    extern __shared__ double lat_vd[];
+    const int64_t I = static_cast<int64_t>(blockIdx.x) * kLatGalThreads + threadIdx.x;
+    const int t = threadIdx.x;
+    const bool live = I < na;
+    const int32_t m0 = live ? mem_ptr[I] : 0, m1 = live ? mem_ptr[I + 1] : 0;      // (requested before the dictionary is copied)
+    for (int i = t; i < nd; i += kLatGalThreads) lat_vd[i] = dict[i];
+#pragma unroll
+    for (int c = 0; c < kLatCodes; ++c) acc[c][t] = 0.0;
+    __syncthreads();
+    if (!live) return;
+    unsigned long long w[kLatGalChunk];
+    uint32_t lc[kLatGalChunk];
+    int64_t held = -1;          // first word of the group whose first kLatGalChunk entries w / lc hold
+    for (int32_t mb = m0; mb < m1; mb += 8) {
+        int32_t mi[8];
+        int width[8];
+        int64_t wb[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) mi[j] = mb + j < m1 ? __builtin_nontemporal_load(mem_idx + mb + j) : -1;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int64_t gs = mi[j] >= 0 ? mi[j] >> 8 : 0;          // group = row / 4, slice = group / 64
+            const int64_t o0 = rslice_off[gs], o1 = rslice_off[gs + 1];
+            width[j] = mi[j] >= 0 ? static_cast<int>((o1 - o0) >> 6) : 0;
+            wb[j] = o0 + ((mi[j] >> 2) & 63);
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int sh16 = 16 * (mi[j] & 3), sh8 = 8 * (mi[j] & 3);
+            for (int k0 = 0; k0 < width[j]; k0 += kLatGalChunk) {
+                if (wb[j] != held || k0 > 0) {
+#pragma unroll
+                    for (int e = 0; e < kLatGalChunk; ++e) {
+                        const bool in = k0 + e < width[j];
+                        const int64_t q = wb[j] + 64LL * (k0 + e);
+                        w[e] = in ? __builtin_nontemporal_load(vcodes + q) : 0ull;
+                        lc[e] = in ? __builtin_nontemporal_load(glat + q) : ~0u;
+                    }
+                    held = k0 == 0 ? wb[j] : -1;
+                }
+#pragma unroll
+                for (int e = 0; e < kLatGalChunk; ++e) {
+                    const uint32_t c = (lc[e] >> sh8) & 0xffu;
+                    if (c < static_cast<uint32_t>(kLatCodes)) acc[c][t] += lat_vd[(w[e] >> sh16) & 0xffffu];
+                }
+            }
+        }
+    }
+    lat_galerkin_row_out(acc, t, I, code_mask, c_slice_off, coarse_vals, X);
 }
 // distinct values of one coordinate: every node drops its value into a small open-addressing table (a lattice has a few
 // hundred distinct values per axis, so almost every probe finds its value already there); *overflow when the table fills

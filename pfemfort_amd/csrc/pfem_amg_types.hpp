@@ -76,6 +76,12 @@ struct AmgLevel {
     // of this level's matrix and the occupied codes of every coarse row
     DevBuf<uint8_t> code_of;              // [stored]
     DevBuf<uint32_t> code_mask;           // [nc]
+    // level 0 in the 4-row relative-group SpMV form with 16-bit value codes: the offset codes of THAT form's slots, four bytes per
+    // union entry next to the four value codes (0xff: an explicit zero of the union) -- k_lat_galerkin_codes sums the next level
+    // from the codes.  Built once per hierarchy, when first wanted (amg_level0_codes); glat_for = the group form's entries it was built for.
+    DevBuf<uint32_t> glat;                // [r_stored]
+    int64_t glat_for = -1;
+    bool glat_refused = false;            // the slot -> union entry map does not cover the form: k_lat_galerkin stays
     // rigid-body-mode coarse space (pfem_amg_rbm.hpp): the level's dofs come `bs` to the node (block regular), the next level
     // has dim + (dim == 3 ? 3 : 1) per aggregate.  With rbm set, mem_ptr / mem_idx list the member NODES of every coarse node
     // and src_ptr / src_slot the fine node BLOCKS of every coarse node block; agg keeps the translation part of P.
@@ -146,6 +152,7 @@ struct Amg {
     bool cycle_given = false;
     bool fused = true;                               // fused SpMV epilogues on the coarse levels + the tail kernel (PFEM_AMG_FUSED=0: off)
     bool level0_ep = false;                          // the last solve's iterations ran level 0's last product with its epilogue (Level0Ep)
+    bool galerkin_from_codes = false;                // the last numeric phase formed level 1 from the SpMV's value codes (k_lat_galerkin_codes)
     int coarsest_sweeps = 8;                         // Chebyshev degree on the last level when it is too large for the dense inverse
     // several ranks: one hierarchy ACROSS the ranks (aggregates stay inside a rank's owned dofs, the operators are the
     // global Galerkin products held sub-assembled, every SpMV of the cycle is followed by the level's neighbour exchange)

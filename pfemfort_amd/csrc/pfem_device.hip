@@ -617,6 +617,8 @@ struct pfem_solver {
     // the group form keep their codes); vd_direct_pending: the last assembly wrote the codes itself, its verdict has not been read
     DevBuf<VdHashEntry> d_vhash;
     bool vd_hash_ok = false, vd_direct_pending = false;
+    bool vd_miss_step = false;       // the assembly of the values in place wrote codes and met a value the dictionary lacked: the full
+                                     // encode path served this step's SpMV, and gamg's set-up reads the fp64 copy (amg_level0_codes)
     VdState vd_direct_verdict{0, 0, 1, 0};
     DevBuf<double> d_vdict;
     DevBuf<VdState> d_vstate;
@@ -2634,7 +2636,7 @@ int build_groups(pfem_solver *s)
     s->grouped = miss == 0;          // a gap missing from the table: the row form stays (never wrong columns)
     s->grp_vals_current = false;
     s->vd_current = s->vd_ok = s->vd_have_dict = s->vd_refused = false;       // (a new pattern: new codes, a new verdict)
-    s->vd_hash_ok = s->vd_direct_pending = false;
+    s->vd_hash_ok = s->vd_direct_pending = s->vd_miss_step = false;
     s->vd_rows = 0;
     s->d_row_group.release();
     if (s->grouped) {       // for an assembly that writes this copy itself; its zero padding is set here, once
@@ -2747,7 +2749,7 @@ int build_rel_groups(pfem_solver *s)
     s->asm_bound_fresh = false;
     s->vd_direct_pending = false;
     s->vd_current = s->vd_ok = s->vd_have_dict = s->vd_refused = false;
-    s->vd_hash_ok = s->vd_direct_pending = false;
+    s->vd_hash_ok = s->vd_direct_pending = s->vd_miss_step = false;
     s->vd_rows = 0;
     s->d_relk.release();
     if (s->max_row_len > 0) {
@@ -2866,6 +2868,7 @@ int refresh_group_vals(pfem_solver *s)
         s->vd_direct_pending = false;
         const bool enabled = valdict_enabled();
         const VdState st = s->vd_direct_verdict;          // (read with the assembly's error word)
+        s->vd_miss_step = st.miss || st.fail;
         if (enabled && !st.miss && !st.fail && s->use_rel() && s->vd_rows == kRelRows) {
             s->vd_ok = s->vd_current = true;
             s->group_vals_stale = false;
@@ -2874,6 +2877,8 @@ int refresh_group_vals(pfem_solver *s)
         }
         s->vd_current = false;
         s->group_vals_stale = true;
+    } else if (!s->vd_current) {
+        s->vd_miss_step = false;          // (new values that came without a verdict: k_vd_encode vouches for the codes)
     }
     PFEM_TRY(refresh_group_vals_only(s));
     return refresh_value_codes(s);
@@ -5215,6 +5220,30 @@ extern "C" int pfem_solver_amg_level0_epilogue(pfem_solver *s, int *taken)
     if (!s || !taken) return PFEM_ERR_ARG;
     if (!s->amg || !s->amg->symbolic_ok) return PFEM_ERR_STATE;
     *taken = s->amg->level0_ep ? 1 : 0;
+    return PFEM_OK;
+}
+
+// did the last numeric phase form level 1 from the SpMV's value codes (k_lat_galerkin_codes)?
+extern "C" int pfem_solver_amg_galerkin_from_codes(pfem_solver *s, int *taken)
+{
+    if (!s || !taken) return PFEM_ERR_ARG;
+    *taken = (s->amg && s->amg->symbolic_ok && s->amg->galerkin_from_codes) ? 1 : 0;      // (no hierarchy: 0, like pfem_solver_amg_info's 0 levels)
+    return PFEM_OK;
+}
+// stored values of a coarse level (>= 1) of the last hierarchy, in slot order (the wave-sliced storage with its padding)
+extern "C" int pfem_solver_amg_level_values(pfem_solver *s, int level, int64_t max_values, double *vals, int64_t *stored)
+{
+    if (!s || !stored || level < 1 || max_values < 0 || (max_values > 0 && !vals)) return PFEM_ERR_ARG;
+    if (!s->amg || !s->amg->symbolic_ok) return PFEM_ERR_STATE;
+    const std::vector<AmgLevelRef> lev = amg_levels_of(*s->amg);
+    if (static_cast<size_t>(level) >= lev.size()) return PFEM_ERR_STATE;
+    const AmgLevel &L = *lev[static_cast<size_t>(level)].L;
+    *stored = L.stored;
+    const int64_t n = std::min<int64_t>(max_values, L.stored);
+    if (n < 1 || !L.vals.p) return PFEM_OK;
+    PFEM_TRY(use_device(s));
+    PFEM_HIP(hipStreamSynchronize(s->stream));
+    PFEM_HIP(hipMemcpy(vals, L.vals.p, sizeof(double) * static_cast<size_t>(n), hipMemcpyDeviceToHost));
     return PFEM_OK;
 }
 

@@ -303,8 +303,19 @@ class PetscSolver:
         L.check(L.lib().pfem_solver_amg_info(self._h, mx, C.byref(nl), rows, nnz, lam, C.byref(sym), C.byref(num), C.byref(deg),
                                              C.byref(fdeg), C.byref(ratio), C.byref(scale)), "pfem_solver_amg_info")
         n = nl.value
+        gc = C.c_int(0)
+        L.check(L.lib().pfem_solver_amg_galerkin_from_codes(self._h, C.byref(gc)), "pfem_solver_amg_galerkin_from_codes")
         return {"levels": n, "rows": list(rows[:n]), "nnz": list(nnz[:n]), "lambda_max": list(lam[:n]), "symbolic_ms": sym.value,
-                "numeric_ms": num.value, "cheb_degree": deg.value, "fine_degree": fdeg.value, "eig_ratio": ratio.value, "coarse_scale": scale.value}
+                "numeric_ms": num.value, "cheb_degree": deg.value, "fine_degree": fdeg.value, "eig_ratio": ratio.value, "coarse_scale": scale.value,
+                "galerkin_from_codes": bool(gc.value)}
+
+    def amgLevelValues(self, level):
+        """The stored values of coarse ``level`` (>= 1) of the last hierarchy, in slot order (padding included)."""
+        n = C.c_int64(0)
+        L.check(L.lib().pfem_solver_amg_level_values(self._h, level, 0, None, C.byref(n)), "pfem_solver_amg_level_values")
+        a = np.empty(n.value, np.float64)
+        L.check(L.lib().pfem_solver_amg_level_values(self._h, level, n.value, _p(a), C.byref(n)), "pfem_solver_amg_level_values")
+        return a
 
     def amgAggregates(self, level, n_rows):
         """Coarse dof of every dof of ``level`` (``n_rows`` = amgInfo()["rows"][level])."""
