@@ -114,6 +114,13 @@ int pfem_solver_amg_cycle(pfem_solver *s, int *cycle, int *last_level_visited_tw
  * step and the CG's (r,z), (z,z) as its epilogue (one rank, a 4-row relative-group SpMV form with 16-bit gaps, fine degree 1,
  * PFEM_AMG_FUSED not 0); 0 when they took the stand-alone kernels                                                          */
 int pfem_solver_amg_level0_epilogue(pfem_solver *s, int *taken);
+/* the first level of the cycle's single-launch tail (k_amg_tail walks it and every level below it in one workgroup), or -1
+ * when the cycle goes level by level all the way down (PFEM_AMG_FUSED=0, several ranks, no level small enough);
+ * *tail_build: which build of the tail the last cycle launched -- 0 none, 1 everything in memory, 2 vectors and index lists in
+ * LDS, 3 the first tail level's matrix in LDS as well; *bounds_by_products: coarse levels whose eigenvalue bound the last
+ * numeric phase took from the Galerkin product that formed them instead of k_amg_max_rows / k_amg_max (0 in a pattern's first
+ * solve, whose products run in the symbolic phase)                                                                       */
+int pfem_solver_amg_tail_from(pfem_solver *s, int *tail_from, int *tail_build, int *bounds_by_products);
 /* 1 when the numeric phase of the last gamg solve formed level 1 from the SpMV's 16-bit value codes (one rank, a scalar brick
  * level 0 whose 4-row relative-group form streams codes that hold the current values; PFEM_AMG_GALERKIN_CODES not 0); 0 when it
  * read the fp64 row form (the first step of a pattern forms the level in the symbolic phase: 0 as well).  Same bits either way. */

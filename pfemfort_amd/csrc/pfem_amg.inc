@@ -672,17 +672,20 @@ inline bool amg_galerkin_by_entry()
 // `extras` (numeric phase of a one-rank hierarchy): the product also leaves C's inverse diagonal and Gershgorin ratios (C.dinv,
 // C.t) and, where C streams value codes and has a dictionary with its hash table, C's codes (verdict word `vstate`, reset here)
 // `from_codes` (level 0, amg_level0_codes said yes): the values are read as the SpMV's 16-bit codes instead of the row form's doubles
-inline void amg_galerkin(pfem_solver *s, const AmgLevel &L, AmgLevel &C, const SellDev &A, bool extras = false, VdState *vstate = nullptr,
-                         bool from_codes = false)
+// `bound` (with extras; a word some kernel before this one has zeroed): the product also leaves the maximum of the ratios there --
+// C's Gershgorin bound, C.bound_done -- and zeroes `zero` for the product after it.  Returns whether it did.
+inline bool amg_galerkin(pfem_solver *s, const AmgLevel &L, AmgLevel &C, const SellDev &A, bool extras = false, VdState *vstate = nullptr,
+                         bool from_codes = false, double *bound = nullptr, double *zero = nullptr)
 {
-    C.bound_fresh = C.vd_direct = false;
+    C.bound_fresh = C.vd_direct = C.bound_done = false;
     if (L.code_of.p && !amg_galerkin_by_entry()) {
-        if (C.n_loc < 1) return;                    // (a rank that holds nothing of this level)
-        LatGalExtra X{nullptr, nullptr, nullptr, nullptr, nullptr};
+        if (C.n_loc < 1) return false;              // (a rank that holds nothing of this level)
+        LatGalExtra X{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
         if (extras && C.dinv.p && C.t.p && C.n_loc == C.n) {
             X.dinv_out = C.dinv.p;
             X.ratio_out = C.t.p;
             C.bound_fresh = true;
+            if (bound) { X.bound = bound; X.zero = zero; C.bound_done = true; }
             if (vstate && C.vd_have_dict && C.vd_hash_ok && C.vhash.p && C.vcodes.p && C.vcodes.n >= static_cast<size_t>(C.stored) && !C.vd_refused) {
                 const VdState reset{C.vd_n, 0, 0, 0};
                 (void)hipMemcpyAsync(vstate, &reset, sizeof reset, hipMemcpyHostToDevice, s->stream);
@@ -699,16 +702,17 @@ inline void amg_galerkin(pfem_solver *s, const AmgLevel &L, AmgLevel &C, const S
                                static_cast<const unsigned long long *>(s->d_vcodes.p), static_cast<const uint32_t *>(L.glat.p),
                                static_cast<const double *>(s->d_vdict.p), s->vd_n, static_cast<const uint32_t *>(L.code_mask.p),
                                static_cast<const int64_t *>(C.slice_off.p), C.vals.p, X);
-            return;
+            return C.bound_done;
         }
         hipLaunchKernelGGL(k_lat_galerkin, dim3(static_cast<unsigned>((C.n_loc + kLatGalThreads - 1) / kLatGalThreads)), dim3(kLatGalThreads), 0, s->stream, A, C.n_loc,
                            static_cast<const int32_t *>(L.mem_ptr.p), static_cast<const int32_t *>(L.mem_idx.p), static_cast<const uint8_t *>(L.code_of.p),
                            static_cast<const uint32_t *>(L.code_mask.p), static_cast<const int64_t *>(C.slice_off.p), C.vals.p, X);
-        return;
+        return C.bound_done;
     }
     hipLaunchKernelGGL(k_amg_galerkin, dim3(grid_for(L.nnz_c)), dim3(kBlock), 0, s->stream, L.nnz_c, static_cast<const int64_t *>(L.src_ptr.p),
                        static_cast<const int32_t *>(L.src_slot.p), static_cast<const int64_t *>(L.dst_slot.p),
                        static_cast<const double *>(A.vals), C.vals.p);
+    return false;
 }
 
 // Coupled hierarchy, one level (collective): the ghosts of level L learn their aggregates from the owners; the coarse
@@ -2483,6 +2487,34 @@ int amg_build_levels(pfem_solver *s, Amg &M, AmgWork &W, bool coupled, bool over
     return PFEM_OK;
 }
 
+// What the tail's LDS layout depends on (tail_view): the levels' rows, their transfers' kind, the first level's stored slots.
+void amg_tail_shape(const Amg &M, int tail, AmgTail &T)
+{
+    T.nlev = static_cast<int>(M.lev.size()) - tail;
+    for (int q = 0; q < T.nlev; ++q) {
+        const AmgLevel &L = *M.lev[static_cast<size_t>(tail + q)];
+        T.lev[q].n = L.n;
+        T.lev[q].rbm_dim = L.rbm ? L.dim : 0;
+        T.lev[q].stored = L.stored;
+        T.lev[q].A.n_slices = (L.n + 63) / 64;
+    }
+}
+// dynamic LDS of k_amg_tail: the vectors alone decide whether the tail works out of LDS (64 KB of them at most, as before the lists
+// came); the LDS builds then take vectors + index lists (vec_b, up to 16 KB more) and, when it fits beside them, the first level's matrix
+struct TailLds { size_t vecs_b, vec_b, mat_b; };
+TailLds tail_lds_bytes(const AmgTail &T)
+{
+    int64_t rows = 0, ints = 0;
+    for (int q = 0; q < T.nlev; ++q) { rows += T.lev[q].n; ints += tail_idx_ints(T, q); }
+    TailLds W;
+    W.vecs_b = static_cast<size_t>(6 * rows) * sizeof(double);
+    W.vec_b = static_cast<size_t>(6 * rows + ((ints + 1) >> 1)) * sizeof(double);
+    const AmgTailLevel &t0 = T.lev[0];
+    W.mat_b = (T.nlev > 1 && t0.stored > 0) ? static_cast<size_t>(t0.stored) * 12 + static_cast<size_t>(t0.A.n_slices + 2) * 8 : 0;
+    return W;
+}
+constexpr size_t kAmgTailLdsMax = 156 * 1024;
+
 // vectors of every level, the dense bottom, which levels the fused kernels take
 int amg_finish_levels(pfem_solver *s, Amg &M, bool coupled)
 {
@@ -2511,19 +2543,22 @@ int amg_finish_levels(pfem_solver *s, Amg &M, bool coupled)
         // 918-row level inside the tail cost 186 us per cycle, three fused launches outside it cost less: 46.6 -> 44.0 ms per step)
         if (M.lev[l]->n <= kAmgTailRows && M.lev[l]->nnz <= kAmgTailNnz && M.lev.size() - l <= static_cast<size_t>(kAmgTailLevels)) { M.tail_from = static_cast<int>(l); break; }
     M.w_to = M.tail_from > 0 ? M.tail_from : static_cast<int>(M.lev.size()) - 2;
-    // the tail kernel works out of LDS (k_amg_tail): allow it what its levels' vectors + the first level's matrix take
-    M.tail_lds_allowed = 0;
+    // the tail kernel works out of LDS (k_amg_tail): more than 64 KB of dynamic LDS has to be allowed per kernel, here, outside any
+    // stream capture -- the build with the matrix for vectors + lists + matrix, the build without it for vectors + lists
+    M.tail_lds_allowed = M.tail_vec_allowed = 0;
+    M.tail_build = 0;
     if (M.tail_from > 0) {
-        int64_t rows = 0;
-        for (size_t l = static_cast<size_t>(M.tail_from); l < M.lev.size(); ++l) rows += M.lev[l]->n;
-        const AmgLevel &T0 = *M.lev[static_cast<size_t>(M.tail_from)];
-        const size_t need = static_cast<size_t>(6 * rows) * sizeof(double) + static_cast<size_t>(T0.stored) * 12 + static_cast<size_t>((T0.n + 63) / 64 + 2) * 8;
-        if (need > 65536 && need <= 156 * 1024) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_amg_tail), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(need)) == hipSuccess)
-                M.tail_lds_allowed = need;
-            else
-                (void)hipGetLastError();
-        }
+        AmgTail T{};
+        amg_tail_shape(M, M.tail_from, T);
+        const TailLds W = tail_lds_bytes(T);
+        const size_t need = W.vec_b + W.mat_b;
+        auto allow = [](const void *k) {
+            if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kAmgTailLdsMax)) == hipSuccess) return kAmgTailLdsMax;
+            (void)hipGetLastError();
+            return static_cast<size_t>(0);
+        };
+        if (W.vecs_b <= 65536 && W.mat_b > 0 && need > 65536 && need <= kAmgTailLdsMax) M.tail_lds_allowed = allow(reinterpret_cast<const void *>(k_amg_tail<true, true>));
+        if (W.vecs_b <= 65536 && W.vec_b > 65536) M.tail_vec_allowed = allow(reinterpret_cast<const void *>(k_amg_tail<true, false>));
     }
     return PFEM_OK;
 }
@@ -2971,44 +3006,42 @@ int amg_numeric(pfem_solver *s, Amg &M, bool overlap)
     if (M.coupled) return amg_numeric_coupled(s, M, overlap);
     const bool fresh = M.galerkin_fresh;
     M.galerkin_fresh = false;
-    for (size_t l = 0; l < M.lev.size(); ++l) {
+    // A coarse level's bound without launches of its own (PFEM_AMG_FUSED not 0, plain transfers): the Galerkin product that writes the
+    // level's ratios leaves their maximum in the level's lam itself (LatGalExtra::bound).  The word has to be zero when that product
+    // starts, and it is zeroed inside this chain: level 1's by level 0's k_amg_max, which therefore runs BEFORE the first product
+    // (it reads what the assembly left, not what the product writes), level l + 2's by the product that forms level l + 1.
+    // `zeroed` = the level whose lam some kernel enqueued above has zeroed (0: none).
+    const bool own_bounds = M.fused && !M.rbm && !fresh && M.lev.size() > 1;
+    size_t zeroed = 0;
+    M.bounds_by_products = 0;
+    // level l's bound from its stored matrix, or from what the assembly (level 0) / the Galerkin product left in L.t
+    auto level_bound = [&](size_t l, double *zero) -> int {
         AmgLevel &L = *M.lev[l];
         const SellDev A = amg_sell(s, L);
-        if (l + 1 < M.lev.size() && !fresh) {
-            AmgLevel &C = *M.lev[l + 1];
-            if (L.rbm) amg_rbm_galerkin(s, L, C, A);
-            else {
-                bool from_codes = false;
-                if (l == 0) PFEM_TRY(amg_level0_codes(s, M, L, &from_codes));
-                amg_galerkin(s, L, C, A, !M.rbm && !M.coupled, M.vd_states.p ? M.vd_states.p + (l + 1) : nullptr, from_codes);
-                if (from_codes) M.galerkin_from_codes = true;
-                if (l == 0 && std::getenv("PFEM_VD_VERBOSE"))
-                    std::fprintf(stderr, "  gamg numeric: level 1 summed from %s\n", from_codes ? "the SpMV's value codes" : "the fp64 row form");
-            }
-        }
         const unsigned g = grid_for(A.n_slices * 64);
         if (!L.fine && L.bound_fresh && !fresh) {
             // the product that formed this level's values left its inverse diagonal in L.dinv and the rows' ratios in L.t (k_lat_galerkin)
             L.bound_fresh = false;
+            if (L.bound_done) { ++M.bounds_by_products; return PFEM_OK; }          // ... and their maximum in L.lam
             if (L.n > 65536) {
                 const unsigned gm = std::min<unsigned>(g, 512u);
                 hipLaunchKernelGGL(k_amg_max_rows, dim3(gm), dim3(kBlock), 0, s->stream, static_cast<const double *>(L.t.p), L.n, L.part_max.p);
-                hipLaunchKernelGGL(k_amg_max, dim3(1), dim3(1024), 0, s->stream, static_cast<const double *>(L.part_max.p), static_cast<int64_t>(gm), L.lam.p);
+                hipLaunchKernelGGL(k_amg_max, dim3(1), dim3(1024), 0, s->stream, static_cast<const double *>(L.part_max.p), static_cast<int64_t>(gm), L.lam.p, zero);
             } else {
-                hipLaunchKernelGGL(k_amg_max, dim3(1), dim3(1024), 0, s->stream, static_cast<const double *>(L.t.p), L.n, L.lam.p);
+                hipLaunchKernelGGL(k_amg_max, dim3(1), dim3(1024), 0, s->stream, static_cast<const double *>(L.t.p), L.n, L.lam.p, zero);
             }
-            continue;
+            return PFEM_OK;
         }
         if (L.fine && s->asm_bound_fresh && &M == s->amg.get()) {
             // the assembly kernel left the inverse diagonal in L.dinv and every row's sum |a_ij| / a_ii in L.t while the rows were in
             // LDS (k_gather_poisson_tet4): the maximum of the ratios is all that is left to do -- no pass over the assembled matrix
             const unsigned gm = std::min<unsigned>(g, 2048u);
             hipLaunchKernelGGL(k_amg_max_rows, dim3(gm), dim3(kBlock), 0, s->stream, static_cast<const double *>(L.t.p), L.n, L.part_max.p);
-            hipLaunchKernelGGL(k_amg_max, dim3(1), dim3(1024), 0, s->stream, static_cast<const double *>(L.part_max.p), static_cast<int64_t>(gm), L.lam.p);
+            hipLaunchKernelGGL(k_amg_max, dim3(1), dim3(1024), 0, s->stream, static_cast<const double *>(L.part_max.p), static_cast<int64_t>(gm), L.lam.p, zero);
             s->asm_bound_fresh = false;
         } else {
-        hipLaunchKernelGGL(k_amg_diag_bound, dim3(g), dim3(kBlock), 0, s->stream, A, static_cast<int32_t>(L.n), L.dinv.p, L.part_max.p);
-        hipLaunchKernelGGL(k_amg_max, dim3(1), dim3(1024), 0, s->stream, static_cast<const double *>(L.part_max.p), static_cast<int64_t>(g), L.lam.p);
+            hipLaunchKernelGGL(k_amg_diag_bound, dim3(g), dim3(kBlock), 0, s->stream, A, static_cast<int32_t>(L.n), L.dinv.p, L.part_max.p);
+            hipLaunchKernelGGL(k_amg_max, dim3(1), dim3(1024), 0, s->stream, static_cast<const double *>(L.part_max.p), static_cast<int64_t>(g), L.lam.p, zero);
         }
         if (M.rbm) {            // the bound on the symmetrically scaled operator; the smaller of the two is taken (k_rbm_bound_sym)
             if (!M.lam2.p) PFEM_TRY(M.lam2.alloc(1));
@@ -3017,6 +3050,32 @@ int amg_numeric(pfem_solver *s, Amg &M, bool overlap)
             hipLaunchKernelGGL(k_amg_max, dim3(1), dim3(1024), 0, s->stream, static_cast<const double *>(L.part_max.p), static_cast<int64_t>(g), M.lam2.p);
             hipLaunchKernelGGL(k_rbm_min2, dim3(1), dim3(64), 0, s->stream, static_cast<const double *>(M.lam2.p), L.lam.p);
         }
+        return PFEM_OK;
+    };
+    for (size_t l = 0; l < M.lev.size(); ++l) {
+        AmgLevel &L = *M.lev[l];
+        const SellDev A = amg_sell(s, L);
+        const bool bound_first = own_bounds && l == 0;
+        if (bound_first) {
+            PFEM_TRY(level_bound(0, M.lev[1]->lam.p));
+            zeroed = 1;
+        }
+        if (l + 1 < M.lev.size() && !fresh) {
+            AmgLevel &C = *M.lev[l + 1];
+            if (L.rbm) amg_rbm_galerkin(s, L, C, A);
+            else {
+                bool from_codes = false;
+                if (l == 0) PFEM_TRY(amg_level0_codes(s, M, L, &from_codes));
+                const bool mine = own_bounds && zeroed == l + 1;
+                double *next = mine && l + 2 < M.lev.size() ? M.lev[l + 2]->lam.p : nullptr;
+                if (amg_galerkin(s, L, C, A, !M.rbm && !M.coupled, M.vd_states.p ? M.vd_states.p + (l + 1) : nullptr, from_codes, mine ? C.lam.p : nullptr, next) && next)
+                    zeroed = l + 2;
+                if (from_codes) M.galerkin_from_codes = true;
+                if (l == 0 && std::getenv("PFEM_VD_VERBOSE"))
+                    std::fprintf(stderr, "  gamg numeric: level 1 summed from %s\n", from_codes ? "the SpMV's value codes" : "the fp64 row form");
+            }
+        }
+        if (!bound_first) PFEM_TRY(level_bound(l, nullptr));
     }
     PFEM_TRY(check_kernel("gamg numeric"));
     if (M.dense) {
@@ -3213,7 +3272,7 @@ double *amg_apply_coupled(pfem_solver *s, Amg &M, const double *r, const CgCtl *
 //     relative-group SpMV form, on the product itself: z and the CG's (r,z), (z,z) are its epilogue (Level0Ep), t is never stored;
 //   * levels 1 .. tail_from-1: the SpMV with the vector step as its epilogue (k_amg_spmv_ep), step 0 of the pre-smoothing
 //     done by the restriction kernel of the level above: 6 launches per level instead of 10;
-//   * levels tail_from .. last (at most 4096 rows): one workgroup walks them all in one launch (k_amg_tail).
+//   * levels tail_from .. last (at most kAmgTailRows rows each): one workgroup walks them all in one launch (k_amg_tail).
 double *amg_apply(pfem_solver *s, Amg &M, const double *r, const CgCtl *ctl, bool first0_done, int last0)
 {
     const int nl = static_cast<int>(M.lev.size());
@@ -3260,6 +3319,7 @@ double *amg_apply(pfem_solver *s, Amg &M, const double *r, const CgCtl *ctl, boo
         T.dense_inv = M.dense_inv.p;
         T.ratio = M.eig_ratio;
         T.scale = M.coarse_scale;
+        amg_tail_shape(M, tail, T);
         for (int q = 0; q < T.nlev; ++q) {
             AmgLevel &L = *M.lev[static_cast<size_t>(tail + q)];
             AmgTailLevel &t = T.lev[q];
@@ -3270,20 +3330,17 @@ double *amg_apply(pfem_solver *s, Amg &M, const double *r, const CgCtl *ctl, boo
             t.n = L.n; t.nc = L.nc; t.stored = L.stored;
             t.rbm_dim = L.rbm ? L.dim : 0; t.fb = L.bs; t.nn = L.n_nodes; t.node_agg = L.node_agg.p; t.roff = L.roff.p;
         }
-        // the levels' vectors in LDS (6 a level; config 3: 343 + 64 rows = 19.5 KB) and, beside them, the first level's matrix when all
-        // of it fits 156 KB (config 3: 10 368 slots = 124 KB)
-        int64_t rows = 0;
-        for (int q = 0; q < T.nlev; ++q) rows += T.lev[q].n;
-        const size_t vec_b = static_cast<size_t>(6 * rows) * sizeof(double);
-        const bool use_lds = vec_b <= 65536;
-        const AmgTailLevel &t0 = T.lev[0];
-        const size_t mat_b = (T.nlev > 1 && t0.stored > 0) ? static_cast<size_t>(t0.stored) * 12 + static_cast<size_t>(t0.A.n_slices + 2) * 8 : 0;
-        const bool mat = use_lds && mat_b > 0 && vec_b + mat_b <= 156 * 1024;
-        const size_t lds = use_lds ? vec_b + (mat ? mat_b : 0) : 0;
-        // (more than 64 KB of dynamic LDS has to be allowed per kernel: amg_finish_levels did, outside any stream capture)
-        const bool mat_ok = mat && (lds <= 65536 || lds <= M.tail_lds_allowed);
-        hipLaunchKernelGGL(k_amg_tail, dim3(1), dim3(1024), use_lds ? (mat_ok ? lds : vec_b) : 0, s->stream, T, ctl, use_lds ? 1 : 0,
-                           mat_ok ? t0.stored : static_cast<int64_t>(0));
+        // the levels' vectors in LDS (6 a level; config 3: 343 + 64 rows = 19.5 KB) with the plain transfers' index lists (3.4 KB) and,
+        // beside them, the first level's matrix when all of it fits 156 KB (config 3: 10 368 slots = 124 KB)
+        const TailLds W = tail_lds_bytes(T);
+        const size_t lds = W.vec_b + W.mat_b;
+        const bool use_lds = W.vecs_b <= 65536 && (W.vec_b <= 65536 || W.vec_b <= M.tail_vec_allowed || lds <= M.tail_lds_allowed);
+        const bool mat_ok = use_lds && W.mat_b > 0 && lds <= kAmgTailLdsMax && (lds <= 65536 || lds <= M.tail_lds_allowed);
+        const bool vec_ok = use_lds && (W.vec_b <= 65536 || W.vec_b <= M.tail_vec_allowed);
+        M.tail_build = mat_ok ? 3 : vec_ok ? 2 : 1;          // (reported by pfem_solver_amg_tail_from)
+        if (mat_ok) hipLaunchKernelGGL((k_amg_tail<true, true>), dim3(1), dim3(1024), lds, s->stream, T, ctl, T.lev[0].stored);
+        else if (vec_ok) hipLaunchKernelGGL((k_amg_tail<true, false>), dim3(1), dim3(1024), W.vec_b, s->stream, T, ctl, static_cast<int64_t>(0));
+        else hipLaunchKernelGGL((k_amg_tail<false, false>), dim3(1), dim3(1024), 0, s->stream, T, ctl, static_cast<int64_t>(0));
     };
     // one visit of level l: its problem  A_l x = b_l  (b_0 = r) answered in L.x -- pre-smoothing, the coarse problem (twice in a
     // W-cycle: the second time on what the first left), correction, post-smoothing
@@ -3417,7 +3474,7 @@ int run_pcg_amg(pfem_solver *s)
         PFEM_TRY(rc);
         // a new hierarchy: no level's bound or codes come from a product of the old one, nor level 0's bound from an assembly for it
         s->asm_bound_fresh = false;
-        for (auto &L : s->amg->lev) L->bound_fresh = L->vd_direct = false;
+        for (auto &L : s->amg->lev) L->bound_fresh = L->bound_done = L->vd_direct = false;
     }
     Amg &M = *s->amg;
     amg_knobs(M);

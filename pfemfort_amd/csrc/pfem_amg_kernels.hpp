@@ -535,9 +535,30 @@ struct LatGalExtra {
     const VdHashEntry *vhash;              // or null
     uint16_t *codes;                       // [coarse stored]
     VdState *vstate;
+    // the level's Gershgorin bound = the largest ratio, left here by the product itself instead of k_amg_max_rows / k_amg_max
+    // behind it: the blocks' maxima meet in *bound (zeroed by a kernel earlier in the chain); *zero is the word the NEXT product
+    // of the chain will use, zeroed by this one.  Both or null.
+    double *bound, *zero;
 };
+// The ratios are >= 0, so their bit patterns order like unsigned integers, and a maximum does not depend on the order it is taken
+// in: *bound gets the bits k_amg_max would leave.  Every thread of the block comes here (ratio 0 for one without a row).
+__device__ __forceinline__ void lat_bound_out(double ratio, const LatGalExtra &X)
+{
+    if (!X.bound) return;
+    __shared__ double wmax[kLatGalThreads / 64];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ratio = fmax(ratio, __shfl_xor(ratio, o, 64));
+    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = ratio;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double m = wmax[0];
+        for (int w = 1; w < kLatGalThreads / 64; ++w) m = fmax(m, wmax[w]);
+        atomicMax(reinterpret_cast<unsigned long long *>(X.bound), static_cast<unsigned long long>(__double_as_longlong(m)));
+    }
+}
 // the coarse row a thread has summed in acc[.][t]: the occupied codes in ascending order = the row's entries, and LatGalExtra's by-products
-__device__ __forceinline__ void lat_galerkin_row_out(const double (&acc)[kLatCodes][kLatGalThreads], int t, int64_t I, const uint32_t *__restrict__ code_mask,
+// returns the row's ratio (0 without dinv_out)
+__device__ __forceinline__ double lat_galerkin_row_out(const double (&acc)[kLatCodes][kLatGalThreads], int t, int64_t I, const uint32_t *__restrict__ code_mask,
                                                      const int64_t *__restrict__ c_slice_off, double *__restrict__ coarse_vals, const LatGalExtra &X)
 {
     const int64_t out0 = c_slice_off[I >> 6] + (I & 63);
@@ -559,13 +580,16 @@ __device__ __forceinline__ void lat_galerkin_row_out(const double (&acc)[kLatCod
             }
             ++r;
         }
+    double ratio = 0.0;
     if (X.dinv_out) {
         const double d = (mask & (1u << 13)) ? acc[13][t] : 0.0;
         const bool pos = d > 0.0;
         X.dinv_out[I] = pos ? 1.0 / d : 1.0;
-        X.ratio_out[I] = pos ? sabs / d : 1.0;
+        ratio = pos ? sabs / d : 1.0;
+        X.ratio_out[I] = ratio;
     }
     if (missed) X.vstate->miss = 1;
+    return ratio;
 }
 // (Tried and dropped, round 6: the 27 accumulators in REGISTERS -- the code of "entry k of member j" is the same in nearly every lane
 // of a wave on a lattice, so it was read from one lane and the lanes that agree added under a wave-uniform switch, the others in
@@ -578,41 +602,45 @@ __global__ void __launch_bounds__(kLatGalThreads) k_lat_galerkin(SellDev A, int6
 {
     __shared__ double acc[kLatCodes][kLatGalThreads];
     const int64_t I = static_cast<int64_t>(blockIdx.x) * kLatGalThreads + threadIdx.x;
-    if (I >= na) return;
     const int t = threadIdx.x;
+    if (X.zero && I == 0) X.zero[0] = 0.0;
+    double ratio = 0.0;
+    if (I < na) {
 #pragma unroll
-    for (int c = 0; c < kLatCodes; ++c) acc[c][t] = 0.0;
-    const int32_t m0 = mem_ptr[I], m1 = mem_ptr[I + 1];
-    for (int32_t mb = m0; mb < m1; mb += 8) {
-        int32_t mi[8];
-        int len[8];
-        int64_t base[8];
+        for (int c = 0; c < kLatCodes; ++c) acc[c][t] = 0.0;
+        const int32_t m0 = mem_ptr[I], m1 = mem_ptr[I + 1];
+        for (int32_t mb = m0; mb < m1; mb += 8) {
+            int32_t mi[8];
+            int len[8];
+            int64_t base[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) mi[j] = mb + j < m1 ? __builtin_nontemporal_load(mem_idx + mb + j) : -1;
+            for (int j = 0; j < 8; ++j) mi[j] = mb + j < m1 ? __builtin_nontemporal_load(mem_idx + mb + j) : -1;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            len[j] = mi[j] >= 0 ? A.rowlen[mi[j]] : 0;
-            base[j] = mi[j] >= 0 ? A.slice_off[mi[j] >> 6] + (mi[j] & 63) : 0;
-        }
+            for (int j = 0; j < 8; ++j) {
+                len[j] = mi[j] >= 0 ? A.rowlen[mi[j]] : 0;
+                base[j] = mi[j] >= 0 ? A.slice_off[mi[j] >> 6] + (mi[j] & 63) : 0;
+            }
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            for (int k0 = 0; k0 < len[j]; k0 += 16) {
-                double v[16];
-                uint8_t c[16];
+            for (int j = 0; j < 8; ++j) {
+                for (int k0 = 0; k0 < len[j]; k0 += 16) {
+                    double v[16];
+                    uint8_t c[16];
 #pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const bool in = k0 + e < len[j];
-                    const int64_t q = base[j] + 64LL * (k0 + e);
-                    v[e] = in ? __builtin_nontemporal_load(A.vals + q) : 0.0;
-                    c[e] = in ? __builtin_nontemporal_load(code_of + q) : static_cast<uint8_t>(0);
+                    for (int e = 0; e < 16; ++e) {
+                        const bool in = k0 + e < len[j];
+                        const int64_t q = base[j] + 64LL * (k0 + e);
+                        v[e] = in ? __builtin_nontemporal_load(A.vals + q) : 0.0;
+                        c[e] = in ? __builtin_nontemporal_load(code_of + q) : static_cast<uint8_t>(0);
+                    }
+#pragma unroll
+                    for (int e = 0; e < 16; ++e)
+                        if (k0 + e < len[j]) acc[c[e]][t] += v[e];
                 }
-#pragma unroll
-                for (int e = 0; e < 16; ++e)
-                    if (k0 + e < len[j]) acc[c[e]][t] += v[e];
             }
         }
+        ratio = lat_galerkin_row_out(acc, t, I, code_mask, c_slice_off, coarse_vals, X);
     }
-    lat_galerkin_row_out(acc, t, I, code_mask, c_slice_off, coarse_vals, X);
+    lat_bound_out(ratio, X);
 }
 // ---- level 0's product from the SpMV's value codes ----------------------------------------------------------------------------
 // On a warm step the assembled values exist twice: as the row form's doubles (what k_lat_galerkin reads, 8 + 1 B a slot) and,
@@ -660,46 +688,50 @@ __global__ void __launch_bounds__(kLatGalThreads) k_lat_galerkin_codes(int64_t n
 #pragma unroll
     for (int c = 0; c < kLatCodes; ++c) acc[c][t] = 0.0;
     __syncthreads();
-    if (!live) return;
-    unsigned long long w[kLatGalChunk];
-    uint32_t lc[kLatGalChunk];
-    int64_t held = -1;          // first word of the group whose first kLatGalChunk entries w / lc hold
-    for (int32_t mb = m0; mb < m1; mb += 8) {
-        int32_t mi[8];
-        int width[8];
-        int64_t wb[8];
+    if (X.zero && I == 0) X.zero[0] = 0.0;
+    double ratio = 0.0;
+    if (live) {
+        unsigned long long w[kLatGalChunk];
+        uint32_t lc[kLatGalChunk];
+        int64_t held = -1;          // first word of the group whose first kLatGalChunk entries w / lc hold
+        for (int32_t mb = m0; mb < m1; mb += 8) {
+            int32_t mi[8];
+            int width[8];
+            int64_t wb[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) mi[j] = mb + j < m1 ? __builtin_nontemporal_load(mem_idx + mb + j) : -1;
+            for (int j = 0; j < 8; ++j) mi[j] = mb + j < m1 ? __builtin_nontemporal_load(mem_idx + mb + j) : -1;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int64_t gs = mi[j] >= 0 ? mi[j] >> 8 : 0;          // group = row / 4, slice = group / 64
-            const int64_t o0 = rslice_off[gs], o1 = rslice_off[gs + 1];
-            width[j] = mi[j] >= 0 ? static_cast<int>((o1 - o0) >> 6) : 0;
-            wb[j] = o0 + ((mi[j] >> 2) & 63);
-        }
+            for (int j = 0; j < 8; ++j) {
+                const int64_t gs = mi[j] >= 0 ? mi[j] >> 8 : 0;          // group = row / 4, slice = group / 64
+                const int64_t o0 = rslice_off[gs], o1 = rslice_off[gs + 1];
+                width[j] = mi[j] >= 0 ? static_cast<int>((o1 - o0) >> 6) : 0;
+                wb[j] = o0 + ((mi[j] >> 2) & 63);
+            }
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int sh16 = 16 * (mi[j] & 3), sh8 = 8 * (mi[j] & 3);
-            for (int k0 = 0; k0 < width[j]; k0 += kLatGalChunk) {
-                if (wb[j] != held || k0 > 0) {
+            for (int j = 0; j < 8; ++j) {
+                const int sh16 = 16 * (mi[j] & 3), sh8 = 8 * (mi[j] & 3);
+                for (int k0 = 0; k0 < width[j]; k0 += kLatGalChunk) {
+                    if (wb[j] != held || k0 > 0) {
+#pragma unroll
+                        for (int e = 0; e < kLatGalChunk; ++e) {
+                            const bool in = k0 + e < width[j];
+                            const int64_t q = wb[j] + 64LL * (k0 + e);
+                            w[e] = in ? __builtin_nontemporal_load(vcodes + q) : 0ull;
+                            lc[e] = in ? __builtin_nontemporal_load(glat + q) : ~0u;
+                        }
+                        held = k0 == 0 ? wb[j] : -1;
+                    }
 #pragma unroll
                     for (int e = 0; e < kLatGalChunk; ++e) {
-                        const bool in = k0 + e < width[j];
-                        const int64_t q = wb[j] + 64LL * (k0 + e);
-                        w[e] = in ? __builtin_nontemporal_load(vcodes + q) : 0ull;
-                        lc[e] = in ? __builtin_nontemporal_load(glat + q) : ~0u;
+                        const uint32_t c = (lc[e] >> sh8) & 0xffu;
+                        if (c < static_cast<uint32_t>(kLatCodes)) acc[c][t] += lat_vd[(w[e] >> sh16) & 0xffffu];
                     }
-                    held = k0 == 0 ? wb[j] : -1;
-                }
-#pragma unroll
-                for (int e = 0; e < kLatGalChunk; ++e) {
-                    const uint32_t c = (lc[e] >> sh8) & 0xffu;
-                    if (c < static_cast<uint32_t>(kLatCodes)) acc[c][t] += lat_vd[(w[e] >> sh16) & 0xffffu];
                 }
             }
         }
+        ratio = lat_galerkin_row_out(acc, t, I, code_mask, c_slice_off, coarse_vals, X);
     }
-    lat_galerkin_row_out(acc, t, I, code_mask, c_slice_off, coarse_vals, X);
+    lat_bound_out(ratio, X);
 }
 // distinct values of one coordinate: every node drops its value into a small open-addressing table (a lattice has a few
 // hundred distinct values per axis, so almost every probe finds its value already there); *overflow when the table fills
@@ -1135,7 +1167,8 @@ __global__ void __launch_bounds__(kBlock) k_amg_max_rows(const double *__restric
     __syncthreads();
     if (threadIdx.x == 0) part_max[blockIdx.x] = fmax(fmax(sm[0], sm[1]), fmax(sm[2], sm[3]));
 }
-__global__ void __launch_bounds__(1024) k_amg_max(const double *__restrict__ part, int64_t n, double *out)
+// (zero: a word to clear for a later kernel of the chain -- the bound word the next Galerkin product's blocks meet in; or null)
+__global__ void __launch_bounds__(1024) k_amg_max(const double *__restrict__ part, int64_t n, double *out, double *zero = nullptr)
 {
     __shared__ double sm[16];
     double a = 0.0;
@@ -1148,6 +1181,7 @@ __global__ void __launch_bounds__(1024) k_amg_max(const double *__restrict__ par
         double t = 0.0;
         for (int w = 0; w < 16; ++w) t = fmax(t, sm[w]);
         out[0] = t;
+        if (zero) zero[0] = 0.0;
     }
 }
 
@@ -1780,47 +1814,72 @@ struct AmgTail {
 
 // Round 6: one workgroup has nothing to hide a latency behind, and every operation of the tail was a chain of dependent global
 // loads (row -> slice offset -> column -> x): the 343- and 64-row levels of config 3 cost 50 us per cycle, more than level 1 with
-// its million rows.  So the tail works out of LDS: every level's vectors (x, dd, t, r, b, dinv: 6 n doubles a level; use_lds) and,
-// when it fits beside them, the FIRST level's matrix -- values, columns, slice offsets (mat_slots = its stored slots, else 0) --,
-// which the cycle reads four times.  TailView = where a level's data live in this launch.  (The kernel's argument stays
-// untouched: a modified copy of it would live in scratch memory, and every field read would be a memory access.)
+// its million rows.  So the tail works out of LDS: every level's vectors (x, dd, t, r, b, dinv: 6 n doubles a level; kLds), the
+// index lists of its plain transfers (mem_ptr, mem_idx, agg) and, when it fits beside them, the FIRST level's matrix -- values,
+// columns, slice offsets (kMat; mat_slots = its stored slots) --, which the cycle reads four times.  TailView = where a level's
+// data live in this launch.  (The kernel's argument stays untouched: a modified copy of it would live in scratch memory, and
+// every field read would be a memory access.)
+// kLds and kMat are template parameters, not launch arguments: a pointer that is LDS in one launch and global in another is a
+// generic pointer, every access through it a flat_load / flat_store down the vector-memory path with a full drain behind it
+// (196 + 30 of them in the one kernel that took both).  With the choice made at compile time every view of the LDS variant is
+// an offset into tail_lds and is read with ds_read / written with ds_write.
 struct TailView {
     double *x, *dd, *t, *r, *b;
     const double *dinv;
     const int64_t *slice_off;
     const int32_t *cols;
     const double *vals;
+    const int32_t *agg, *mem_ptr, *mem_idx;          // the plain transfer's lists (a rigid-body transfer reads its own from the level)
+    // the first level's matrix staged in LDS (mat): views of their own, so that neither these nor the ones above are LDS in one
+    // level and global in the next
+    bool mat;
+    const int64_t *lds_slice_off;
+    const int32_t *lds_cols;
+    const double *lds_vals;
 };
-__device__ inline TailView tail_view(const AmgTail &T, int l, int use_lds, int64_t mat_slots, double *lds)
+// int32 entries of level q's transfer lists kept in LDS: mem_ptr (coarse rows + 1), mem_idx and agg (rows each)
+__host__ __device__ inline int64_t tail_idx_ints(const AmgTail &T, int q)
+{
+    return (q + 1 < T.nlev && !T.lev[q].rbm_dim) ? 2 * T.lev[q].n + T.lev[q + 1].n + 1 : 0;
+}
+// LDS layout: [6 n doubles of every level][index lists of every level, padded to 8 bytes][level 0's values | slice offsets | columns]
+template <bool kLds, bool kMat>
+__device__ inline TailView tail_view(const AmgTail &T, int l, int64_t mat_slots, double *lds)
 {
     const AmgTailLevel &L = T.lev[l];
-    TailView V{L.x, L.dd, L.t, L.r, L.b, L.dinv, L.A.slice_off, L.A.cols, L.A.vals};
-    if (use_lds) {
-        int64_t off = 0, tot = 0;
+    TailView V{L.x, L.dd, L.t, L.r, L.b, L.dinv, L.A.slice_off, L.A.cols, L.A.vals, L.agg, L.mem_ptr, L.mem_idx, false, nullptr, nullptr, nullptr};
+    if (kLds) {
+        int64_t off = 0, tot = 0, ioff = 0, itot = 0;
         for (int q = 0; q < T.nlev; ++q) {
-            if (q < l) off += 6 * T.lev[q].n;
+            if (q < l) { off += 6 * T.lev[q].n; ioff += tail_idx_ints(T, q); }
             tot += 6 * T.lev[q].n;
+            itot += tail_idx_ints(T, q);
         }
         double *base = lds + off;
         const int64_t n = L.n;
         V.x = base; V.dd = base + n; V.t = base + 2 * n; V.r = base + 3 * n; V.b = base + 4 * n; V.dinv = base + 5 * n;
-        if (l == 0 && mat_slots > 0) {
-            double *mv = lds + tot;
+        int32_t *ib = reinterpret_cast<int32_t *>(lds + tot) + ioff;          // (a level without lists never reads through these)
+        V.mem_ptr = ib;
+        V.mem_idx = ib + (l + 1 < T.nlev ? T.lev[l + 1].n + 1 : 0);
+        V.agg = V.mem_idx + n;
+        if (kMat) {
+            double *mv = lds + tot + ((itot + 1) >> 1);
             int64_t *so = reinterpret_cast<int64_t *>(mv + mat_slots);
-            V.vals = mv;
-            V.slice_off = so;
-            V.cols = reinterpret_cast<int32_t *>(so + L.A.n_slices + 1);
+            V.mat = l == 0;
+            V.lds_vals = mv;
+            V.lds_slice_off = so;
+            V.lds_cols = reinterpret_cast<int32_t *>(so + T.lev[0].A.n_slices + 1);
         }
     }
     return V;
 }
-__device__ inline void tail_spmv(const TailView &V, int64_t n_rows, const double *x, double *y)
+__device__ __forceinline__ void tail_spmv_rows(const int64_t *slice_off, const int32_t *cols, const double *vals, int64_t n_rows, const double *x, double *y)
 {
     for (int64_t i = threadIdx.x; i < n_rows; i += 1024) {
-        const int64_t off = V.slice_off[i >> 6];
-        const int width = static_cast<int>((V.slice_off[(i >> 6) + 1] - off) >> 6);
-        const int32_t *cp = V.cols + off + (i & 63);
-        const double *vp = V.vals + off + (i & 63);
+        const int64_t off = slice_off[i >> 6];
+        const int width = static_cast<int>((slice_off[(i >> 6) + 1] - off) >> 6);
+        const int32_t *cp = cols + off + (i & 63);
+        const double *vp = vals + off + (i & 63);
         double acc = 0.0;
         int k = 0;
         for (; k + 8 <= width; k += 8) {          // (columns, values and gathers of eight entries requested together, then the chain in its order)
@@ -1836,6 +1895,11 @@ __device__ inline void tail_spmv(const TailView &V, int64_t n_rows, const double
         for (; k < width; ++k) acc = __builtin_fma(vp[64 * k], x[cp[64 * k]], acc);
         y[i] = acc;
     }
+}
+__device__ inline void tail_spmv(const TailView &V, int64_t n_rows, const double *x, double *y)
+{
+    if (V.mat) tail_spmv_rows(V.lds_slice_off, V.lds_cols, V.lds_vals, n_rows, x, y);
+    else tail_spmv_rows(V.slice_off, V.cols, V.vals, n_rows, x, y);
     __syncthreads();
 }
 // Chebyshev smoothing exactly as amg_smooth enqueues it (k_amg_cheb_first / k_amg_cheb_next)
@@ -1886,22 +1950,30 @@ __device__ inline void tail_rbm_prolong(const AmgTailLevel &L, const TailView &V
 }
 // The first level's right-hand side comes from global memory (the restriction above wrote it), its answer goes back there (the
 // prolongation above reads it); nothing else of the tail is read by anybody.  Same operations in the same order: same bits.
-// use_lds = 0: everything stays where it is (a tail whose vectors do not fit).
-__global__ void __launch_bounds__(1024) k_amg_tail(const AmgTail T, const CgCtl *ctl, int use_lds, int64_t mat_slots)
+// kLds = false: everything stays where it is, behind plain global pointers (a tail whose vectors do not fit).
+// Everything the LDS variant reads from memory before its first barrier is requested in one go: the stop flag, the eigenvalue
+// bounds, the matrix, dinv, b and the index lists leave together, and one line in sixteen of the dense inverse is touched so
+// that the coarsest solve finds it in this XCD's L2 (the 32 KB are otherwise read once a cycle, between 1.7 GB of level-0
+// traffic).  The flag is looked at after the staging barrier: a launch behind the CG's stop pays the staging and leaves.
+template <bool kLds, bool kMat>
+__global__ void __launch_bounds__(1024) k_amg_tail(const AmgTail T, const CgCtl *ctl, int64_t mat_slots)
 {
     extern __shared__ double tail_lds[];
-    if (ctl && ctl->flag != 0) return;
+    const int stop = ctl ? ctl->flag : 0;
+    if (!kLds && stop != 0) return;
     const int nl = T.nlev;
     __shared__ double lam_of[kAmgTailLevels];    // (every level's eigenvalue bound: requested here, with everything else the tail reads first)
     if (threadIdx.x < static_cast<unsigned>(nl)) lam_of[threadIdx.x] = T.lev[threadIdx.x].lam[0];
-    if (!use_lds) __syncthreads();
-    if (use_lds) {
-        if (mat_slots > 0) {                     // eight slots a thread and trip in flight (the loads do not wait for the LDS stores of the trip before)
+    if (!kLds) __syncthreads();
+    if (kLds) {
+        double warm = 0.0;
+        if (T.dense_n > 0 && 16 * static_cast<int>(threadIdx.x) < T.dense_n * T.dense_n) warm = T.dense_inv[16 * threadIdx.x];
+        if (kMat) {                              // eight slots a thread and trip in flight (the loads do not wait for the LDS stores of the trip before)
             const AmgTailLevel &L = T.lev[0];
-            const TailView V = tail_view(T, 0, use_lds, mat_slots, tail_lds);
-            double *mv = const_cast<double *>(V.vals);
-            int32_t *mc = const_cast<int32_t *>(V.cols);
-            int64_t *so = const_cast<int64_t *>(V.slice_off);
+            const TailView V = tail_view<kLds, kMat>(T, 0, mat_slots, tail_lds);
+            double *mv = const_cast<double *>(V.lds_vals);
+            int32_t *mc = const_cast<int32_t *>(V.lds_cols);
+            int64_t *so = const_cast<int64_t *>(V.lds_slice_off);
             const double *__restrict__ gv = L.A.vals;
             const int32_t *__restrict__ gc = L.A.cols;
             for (int64_t q0 = threadIdx.x; q0 < mat_slots; q0 += 8 * 1024) {
@@ -1923,24 +1995,41 @@ __global__ void __launch_bounds__(1024) k_amg_tail(const AmgTail T, const CgCtl 
         }
         for (int l = 0; l < nl; ++l) {
             const AmgTailLevel &L = T.lev[l];
-            const TailView V = tail_view(T, l, use_lds, mat_slots, tail_lds);
+            const TailView V = tail_view<kLds, kMat>(T, l, mat_slots, tail_lds);
             double *dv = const_cast<double *>(V.dinv);
             for (int64_t i = threadIdx.x; i < L.n; i += 1024) {
                 dv[i] = L.dinv[i];
                 if (l == 0) V.b[i] = L.b[i];
             }
+            if (tail_idx_ints(T, l) > 0) {
+                int32_t *mp = const_cast<int32_t *>(V.mem_ptr), *mi = const_cast<int32_t *>(V.mem_idx), *ag = const_cast<int32_t *>(V.agg);
+                for (int64_t i = threadIdx.x; i < L.n; i += 1024) { mi[i] = L.mem_idx[i]; ag[i] = L.agg[i]; }
+                for (int64_t a = threadIdx.x; a <= T.lev[l + 1].n; a += 1024) mp[a] = L.mem_ptr[a];
+            }
         }
+        asm volatile("" ::"v"(warm));            // (the touch of the dense inverse is waited for here, with the staging loads)
         __syncthreads();
+        if (stop != 0) return;
     }
     for (int l = 0; l < nl; ++l) {
         const AmgTailLevel &L = T.lev[l];
-        const TailView V = tail_view(T, l, use_lds, mat_slots, tail_lds);
+        const TailView V = tail_view<kLds, kMat>(T, l, mat_slots, tail_lds);
         if (l == nl - 1) {
             if (T.dense_n > 0) {
+                // thread i's column of the inverse in groups of sixteen requests; the chain over j keeps its order
                 const int n = T.dense_n;
                 for (int i = threadIdx.x; i < n; i += 1024) {
+                    const double *__restrict__ col = T.dense_inv + i;
                     double a = 0.0;
-                    for (int j = 0; j < n; ++j) a = __builtin_fma(T.dense_inv[j * n + i], V.b[j], a);
+                    int j = 0;
+                    for (; j + 16 <= n; j += 16) {
+                        double m[16];
+#pragma unroll
+                        for (int u = 0; u < 16; ++u) m[u] = col[(j + u) * n];
+#pragma unroll
+                        for (int u = 0; u < 16; ++u) a = __builtin_fma(m[u], V.b[j + u], a);
+                    }
+                    for (; j < n; ++j) a = __builtin_fma(col[j * n], V.b[j], a);
                     V.x[i] = a;
                 }
                 __syncthreads();
@@ -1950,15 +2039,15 @@ __global__ void __launch_bounds__(1024) k_amg_tail(const AmgTail T, const CgCtl 
             break;
         }
         const AmgTailLevel &C = T.lev[l + 1];
-        const TailView VC = tail_view(T, l + 1, use_lds, mat_slots, tail_lds);
+        const TailView VC = tail_view<kLds, kMat>(T, l + 1, mat_slots, tail_lds);
         tail_smooth(L, V, V.b, true, T.deg, T.ratio, lam_of[l]);
         tail_spmv(V, L.n, V.x, V.t);
         if (L.rbm_dim) tail_rbm_restrict(L, V, C, VC);
         else
         for (int64_t a = threadIdx.x; a < C.n; a += 1024) {
             double acc = 0.0;
-            for (int q = L.mem_ptr[a]; q < L.mem_ptr[a + 1]; ++q) {
-                const int i = L.mem_idx[q];
+            for (int q = V.mem_ptr[a]; q < V.mem_ptr[a + 1]; ++q) {
+                const int i = V.mem_idx[q];
                 acc += V.b[i] - V.t[i];
             }
             VC.b[a] = acc;
@@ -1967,16 +2056,16 @@ __global__ void __launch_bounds__(1024) k_amg_tail(const AmgTail T, const CgCtl 
     }
     for (int l = nl - 2; l >= 0; --l) {
         const AmgTailLevel &L = T.lev[l];
-        const TailView V = tail_view(T, l, use_lds, mat_slots, tail_lds);
-        const TailView VC = tail_view(T, l + 1, use_lds, mat_slots, tail_lds);
+        const TailView V = tail_view<kLds, kMat>(T, l, mat_slots, tail_lds);
+        const TailView VC = tail_view<kLds, kMat>(T, l + 1, mat_slots, tail_lds);
         if (L.rbm_dim) tail_rbm_prolong(L, V, VC, T.scale);
         else
-        for (int64_t i = threadIdx.x; i < L.n; i += 1024) V.x[i] = __builtin_fma(T.scale, VC.x[L.agg[i]], V.x[i]);
+        for (int64_t i = threadIdx.x; i < L.n; i += 1024) V.x[i] = __builtin_fma(T.scale, VC.x[V.agg[i]], V.x[i]);
         __syncthreads();
         tail_smooth(L, V, V.b, false, T.deg, T.ratio, lam_of[l]);
     }
-    if (use_lds) {
-        const TailView V = tail_view(T, 0, use_lds, mat_slots, tail_lds);
+    if (kLds) {
+        const TailView V = tail_view<kLds, kMat>(T, 0, mat_slots, tail_lds);
         double *x_out = T.lev[0].x;
         for (int64_t i = threadIdx.x; i < T.lev[0].n; i += 1024) x_out[i] = V.x[i];
     }

@@ -108,6 +108,7 @@ struct AmgLevel {
     bool vd_hash_ok = false;              // vhash belongs to vdict, and every slot of vcodes carries a code of it
     bool vd_direct = false;               // this solve's codes came from the Galerkin product: verdict in Amg::vd_states, not read yet
     bool bound_fresh = false;             // dinv and t (ratios) of this level were written by the product that formed its values
+    bool bound_done = false;              // ... and lam (their maximum) as well
     double *x = nullptr, *dd = nullptr;
     DevBuf<double> x1;                    // W-cycle: the first visit's answer while the second is on its way
     double lam_host = 0.0;
@@ -144,7 +145,10 @@ struct Amg {
         if (ev_num1) (void)hipEventDestroy(ev_num1);
     }
     int tail_from = -1;                              // first level of the single-launch tail of the cycle (-1: none)
-    size_t tail_lds_allowed = 0;                     // dynamic LDS bytes k_amg_tail has been allowed beyond 64 KB (hipFuncSetAttribute, once)
+    size_t tail_lds_allowed = 0;                     // dynamic LDS bytes k_amg_tail<true, true> has been allowed beyond 64 KB (hipFuncSetAttribute)
+    size_t tail_vec_allowed = 0;                     // ... and k_amg_tail<true, false>
+    int tail_build = 0;                              // what the last cycle's tail launch was: 0 none, 1 all in memory, 2 vectors + lists in LDS, 3 + the matrix
+    int bounds_by_products = 0;                      // coarse levels whose bound the last numeric phase took from the Galerkin product (LatGalExtra::bound)
     // -pc_mg_cycle_type: 1 = V (default), 2 = W -- the coarse problem of every level from 1 down to w_to is visited twice (second
     // visit on the residual of the first).  The levels of the single-launch tail (<= 1024 rows each) stay a V inside:
     // w_to = tail_from, whether or not the fused kernels are in use (amg_cycle_shape has the measurements).

@@ -5257,3 +5257,15 @@ extern "C" int pfem_solver_amg_cycle(pfem_solver *s, int *cycle, int *last_level
     *last_level_visited_twice = M.cycle_gamma > 1 ? std::min(M.w_to, static_cast<int>(M.lev.size()) - 2) : 0;
     return PFEM_OK;
 }
+// the level from which the cycle runs in one launch (amg_apply's `tail`), -1: level by level to the bottom
+extern "C" int pfem_solver_amg_tail_from(pfem_solver *s, int *tail_from, int *tail_build, int *bounds_by_products)
+{
+    if (!s || !tail_from || !tail_build || !bounds_by_products) return PFEM_ERR_ARG;
+    if (!s->amg || !s->amg->symbolic_ok) return PFEM_ERR_STATE;
+    const Amg &M = *s->amg;
+    const bool tail = M.fused && M.tail_from > 0;
+    *tail_from = tail ? M.tail_from : -1;
+    *tail_build = tail ? M.tail_build : 0;
+    *bounds_by_products = M.bounds_by_products;
+    return PFEM_OK;
+}

@@ -260,11 +260,23 @@ class PetscSolver:
 
     def amgCycle(self):
         """What the last gamg solve ran: {"cycle": "v" | "w", "last_level_visited_twice": l (0 with the V-cycle),
-        "level0_epilogue": the cycle's last fine product carried the final smoothing step and the CG's sums}."""
-        c, w, e = C.c_int(0), C.c_int(0), C.c_int(0)
+        "level0_epilogue": the cycle's last fine product carried the final smoothing step and the CG's sums,
+        "tail_from": first level of the one-workgroup tail launch (-1: the cycle went level by level to the bottom),
+        "tail_build": None | "memory" | "lds" | "lds+matrix" (where that launch kept the levels' vectors and the first level's matrix)}."""
+        c, w, e, t, tb, bp = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(-1), C.c_int(0), C.c_int(0)
         L.check(L.lib().pfem_solver_amg_cycle(self._h, C.byref(c), C.byref(w)), "pfem_solver_amg_cycle")
         L.check(L.lib().pfem_solver_amg_level0_epilogue(self._h, C.byref(e)), "pfem_solver_amg_level0_epilogue")
-        return {"cycle": "w" if c.value == 2 else "v", "last_level_visited_twice": w.value, "level0_epilogue": bool(e.value)}
+        L.check(L.lib().pfem_solver_amg_tail_from(self._h, C.byref(t), C.byref(tb), C.byref(bp)), "pfem_solver_amg_tail_from")
+        return {"cycle": "w" if c.value == 2 else "v", "last_level_visited_twice": w.value, "level0_epilogue": bool(e.value),
+                "tail_from": t.value, "tail_build": [None, "memory", "lds", "lds+matrix"][tb.value]}
+
+    def amgBoundsByProducts(self):
+        """Coarse levels whose eigenvalue bound the last numeric set-up took from the Galerkin product that formed them, instead of
+        the stand-alone maximum kernels (0 in a pattern's first solve, whose products run in the symbolic phase: a property of the
+        solver's history, unlike amgCycle())."""
+        t, tb, bp = C.c_int(-1), C.c_int(0), C.c_int(0)
+        L.check(L.lib().pfem_solver_amg_tail_from(self._h, C.byref(t), C.byref(tb), C.byref(bp)), "pfem_solver_amg_tail_from")
+        return bp.value
 
     def amgTransfer(self, level, xyz=False):
         """The transfer from ``level`` to the next: {"rbm": carries rotations?, "fine_bs", "coarse_bs", "dim", "n_nodes"} and, with
