@@ -128,6 +128,16 @@ int pfem_solver_amg_galerkin_from_codes(pfem_solver *s, int *taken);
 /* the stored values of coarse level `level` (>= 1) of the last hierarchy in slot order, padding included: *stored of them, the
  * first min(max_values, *stored) copied to vals (max_values = 0: the count alone)                                             */
 int pfem_solver_amg_level_values(pfem_solver *s, int level, int64_t max_values, double *vals, int64_t *stored);
+/* the levels whose fused products of the last gamg solve read one-byte column codes instead of int32 columns (the levels that
+ * take the value dictionary, on one rank, once their codes have been built and compared with the columns on the device;
+ * PFEM_AMG_COL_CODES not 0), ascending: *n_levels of them, at most max_levels written; *builds: how many times this hierarchy has
+ * built a level's codes (a refused level is counted once and never built again)                                              */
+int pfem_solver_amg_column_codes(pfem_solver *s, int max_levels, int *n_levels, int *levels, int *builds);
+/* the columns of coarse level `level` (>= 1) of the last hierarchy in slot order, padding included: *stored of them, the first
+ * min(max_cols, *stored) copied to cols.  decoded = 0: the level's int32 columns; decoded = 1: decoded on the device from the
+ * level's column codes and offset table (PFEM_ERR_STATE when it has none).  The two agree on every slot of every row < n; the
+ * lanes past n of the last slice read 0 either way                                                                          */
+int pfem_solver_amg_level_columns(pfem_solver *s, int level, int decoded, int64_t max_cols, int32_t *cols, int64_t *stored);
 
 /* Per-element Ke/Fe of the uploaded mesh as computed by the DEVICE kernel (parity
  * inspection): K_out[e*nsize*nsize + i + nsize*j], F_out[e*nsize + i].           */

@@ -88,7 +88,7 @@ inline void amg_spmv(pfem_solver *s, const Amg &M, AmgLevel &L, const double *x,
         launch_spmv<false>(s, x, y, 0, nullptr, nullptr);
     } else {
         const SellDev A = amg_sell(s, L, amg_rows(M, L));
-        if (M.coupled && L.vd_ok && L.vcodes.p)         // the level's values as dictionary codes (amg_value_codes): same product, 6 B a slot
+        if (M.coupled && L.vd_ok && L.vcodes.p)         // the level's values as dictionary codes (amg_value_codes): same product, 4 + 2 B a slot
             hipLaunchKernelGGL(k_amg_spmv_pack_vd, dim3(spmv_grid(A.n_slices)), dim3(kBlock), sizeof(double) * static_cast<size_t>(L.vd_n), s->stream, A,
                                static_cast<const uint16_t *>(L.vcodes.p), static_cast<const double *>(L.vdict.p), L.vd_n, x, y,
                                ShareSum{nullptr, nullptr, nullptr, nullptr}, static_cast<double *>(nullptr), static_cast<const CgCtl *>(nullptr));
@@ -2600,6 +2600,8 @@ int amg_symbolic(pfem_solver *s, bool multi, bool overlap)
     if (const char *e = std::getenv("PFEM_AMG_FINE_DEGREE")) M.fine_degree = std::max(0, std::min(6, std::atoi(e)));
     M.lev.clear();
     M.rep.reset();
+    M.cc_builds = 0;
+    M.cc_used.clear();
     M.rbm = false;
     M.symbolic_ok = false;
     M.dense = false;
@@ -2869,6 +2871,63 @@ int amg_numeric_coupled(pfem_solver *s, Amg &M, bool overlap)
 // that have a dictionary are encoded against it, one read of the verdicts; then those without one, or with a value it lacks,
 // collect theirs -- a second read, in the first solve of a pattern only.  Config 3: level 1 (17.6 M slots, ~400 values).
 constexpr int64_t kAmgVdMinSlots = 1 << 20;
+
+// Column codes of the levels that take the value dictionary (one rank; AmgLevel::ccodes): do level l's fused products read them?
+inline bool amg_level_col_codes(const Amg &M, const AmgLevel &L)
+{
+    return M.col_codes && !M.coupled && L.vd_ok && L.vcodes.p && L.cc_ok && L.ccodes.p && L.cdelta.p && L.cd_n > 0;
+}
+// Built once per hierarchy, at the first numeric phase that wants them (PFEM_AMG_COL_CODES not 0): the distinct  col - row  of the
+// level collected (k_cc_collect; more than the cap -- 256, PFEM_AMG_COL_CODES_MAX=<n> lowers it -- refuses the level), sorted, every
+// slot encoded, and every slot decoded again and compared with `cols` (k_cc_verify).  All on the stream; the verdict travels with the
+// value codes' verdicts (read_states of amg_value_codes), so the phase waits for the device no more often than it did.
+int amg_column_codes_enqueue(pfem_solver *s, Amg &M, int l)
+{
+    AmgLevel &L = *M.lev[static_cast<size_t>(l)];
+    const size_t nl = M.lev.size();
+    if (M.cc_states.n < nl) PFEM_TRY(M.cc_states.alloc(nl));
+    if (!M.cc_hash.p) PFEM_TRY(M.cc_hash.alloc(kCcHash));
+    int cap = kCcMax;
+    if (const char *e = std::getenv("PFEM_AMG_COL_CODES_MAX")) cap = std::max(1, std::min(kCcMax, std::atoi(e)));
+    const size_t words = static_cast<size_t>(std::max<int64_t>(cc_words(L.stored, L.n_slices), 64));
+    PFEM_TRY(L.ccodes.alloc(words));
+    PFEM_TRY(L.cdelta.alloc(kCcMax));
+    const CcState init{0, 0, 0, cap};
+    CcState *st = M.cc_states.p + l;
+    PFEM_HIP(hipMemcpyAsync(st, &init, sizeof init, hipMemcpyHostToDevice, s->stream));
+    const SellDev A = amg_sell(s, L);
+    const unsigned grid = static_cast<unsigned>(std::min<int64_t>(std::max<int64_t>(1, (A.n_slices + 3) / 4), 4096));
+    hipLaunchKernelGGL(k_cc_fill, dim3(kCcHash / kBlock), dim3(kBlock), 0, s->stream, M.cc_hash.p, kCcHash, kCcEmpty);
+    hipLaunchKernelGGL(k_cc_collect, dim3(grid), dim3(kBlock), 0, s->stream, A, M.cc_hash.p, st);
+    hipLaunchKernelGGL(k_cc_finish, dim3(1), dim3(kCcHash), 0, s->stream, static_cast<const int32_t *>(M.cc_hash.p), L.cdelta.p, st);
+    hipLaunchKernelGGL(k_cc_encode, dim3(grid), dim3(kBlock), 0, s->stream, A, static_cast<const int32_t *>(L.cdelta.p), st, L.ccodes.p);
+    hipLaunchKernelGGL(k_cc_verify, dim3(grid), dim3(kBlock), 0, s->stream, A, static_cast<const int32_t *>(L.cdelta.p),
+                       static_cast<const uint32_t *>(L.ccodes.p), st);
+    PFEM_TRY(check_kernel("k_cc_collect / k_cc_finish / k_cc_encode / k_cc_verify"));
+    L.cc_pending = true;
+    ++M.cc_builds;
+    return PFEM_OK;
+}
+// ... after the read: no level runs a form that was not compared word for word
+void amg_column_codes_verdict(Amg &M, int l, const CcState &v)
+{
+    AmgLevel &L = *M.lev[static_cast<size_t>(l)];
+    L.cc_pending = false;
+    if (v.fail || v.mismatch || v.count < 1 || v.count > kCcMax || v.count > v.cap) {
+        L.cc_ok = false;
+        L.cc_refused = true;              // (for this hierarchy)
+        L.ccodes.release();
+        L.cdelta.release();
+        L.cd_n = 0;
+    } else {
+        L.cd_n = v.count;
+        L.cc_ok = true;
+    }
+    if (std::getenv("PFEM_VD_VERBOSE"))
+        std::fprintf(stderr, "  column codes, level %d: %d distinct offsets among %lld slots%s\n", l, v.count, static_cast<long long>(L.stored),
+                     L.cc_ok ? "" : (v.mismatch ? " -- the check failed, the level keeps its int32 columns" : " -- the level keeps its int32 columns"));
+}
+
 int amg_value_codes(pfem_solver *s, Amg &M)
 {
     const bool enabled = valdict_enabled();
@@ -2886,6 +2945,16 @@ int amg_value_codes(pfem_solver *s, Amg &M)
     if (cand.empty()) return PFEM_OK;
     if (M.vd_states.n < static_cast<size_t>(nl)) PFEM_TRY(M.vd_states.alloc(static_cast<size_t>(nl)));
     std::vector<VdState> st(static_cast<size_t>(nl));
+    // the same levels' column codes, when this hierarchy has none yet (their verdict rides on the first read below)
+    std::vector<int> cc_wait;
+    if (M.col_codes && !M.coupled && &M == s->amg.get() && !cg_multi(s))
+        for (int l : cand) {
+            AmgLevel &L = *M.lev[static_cast<size_t>(l)];
+            if (L.cc_ok || L.cc_refused) continue;
+            PFEM_TRY(amg_column_codes_enqueue(s, M, l));
+            cc_wait.push_back(l);
+        }
+    std::vector<CcState> cst(cc_wait.empty() ? 0 : static_cast<size_t>(nl));
     auto encode = [&](AmgLevel &L, int l) -> int {
         const unsigned grid = static_cast<unsigned>(std::min<int64_t>((L.stored + kBlock - 1) / kBlock, 4096));
         hipLaunchKernelGGL(k_vd_encode16, dim3(grid), dim3(kBlock), sizeof(uint64_t) * kVdMax, s->stream, static_cast<const double *>(L.vals.p), L.stored,
@@ -2894,7 +2963,11 @@ int amg_value_codes(pfem_solver *s, Amg &M)
     };
     auto read_states = [&]() -> int {
         PFEM_HIP(hipMemcpyAsync(st.data(), M.vd_states.p, sizeof(VdState) * static_cast<size_t>(nl), hipMemcpyDeviceToHost, s->stream));
+        if (!cc_wait.empty())
+            PFEM_HIP(hipMemcpyAsync(cst.data(), M.cc_states.p, sizeof(CcState) * static_cast<size_t>(nl), hipMemcpyDeviceToHost, s->stream));
         PFEM_HIP(hipStreamSynchronize(s->stream));
+        for (int l : cc_wait) amg_column_codes_verdict(M, l, cst[static_cast<size_t>(l)]);
+        cc_wait.clear();
         return PFEM_OK;
     };
     std::vector<int> build;
@@ -3299,10 +3372,19 @@ double *amg_apply(pfem_solver *s, Amg &M, const double *r, const CgCtl *ctl, boo
         if (L.vd_ok && L.vcodes.p) {          // the level's values as dictionary codes (amg_value_codes)
             const uint16_t *q = L.vcodes.p;
             const double *d = L.vdict.p;
+            if (amg_level_col_codes(M, L)) {          // ... and its columns as one-byte codes (amg_column_codes_enqueue): 1 + 2 B a slot
+                const uint32_t *cw = L.ccodes.p;
+                const int32_t *cdl = L.cdelta.p;
+                const size_t lds_cc = sizeof(double) * static_cast<size_t>(L.vd_n) + sizeof(int32_t) * static_cast<size_t>(L.cd_n);
+#define PFEM_CC_EP(MODEV) hipLaunchKernelGGL((k_amg_spmv_ep_vd<MODEV, true>), grid, block, lds_cc, s->stream, A, q, d, L.vd_n, xin, r_in, dinv, lam, M.eig_ratio, step, add_dd0, r_out, dd_out, x, ctl, cw, cdl, L.cd_n)
+                if (mode == kEpNextLast) PFEM_CC_EP(kEpNextLast); else if (mode == kEpResid) PFEM_CC_EP(kEpResid); else PFEM_CC_EP(kEpFirstRes);
+#undef PFEM_CC_EP
+                return;
+            }
             const size_t lds = sizeof(double) * static_cast<size_t>(L.vd_n);
-            if (mode == kEpNextLast) hipLaunchKernelGGL(k_amg_spmv_ep_vd<kEpNextLast>, grid, block, lds, s->stream, A, q, d, L.vd_n, xin, r_in, dinv, lam, M.eig_ratio, step, add_dd0, r_out, dd_out, x, ctl);
-            else if (mode == kEpResid) hipLaunchKernelGGL(k_amg_spmv_ep_vd<kEpResid>, grid, block, lds, s->stream, A, q, d, L.vd_n, xin, r_in, dinv, lam, M.eig_ratio, step, add_dd0, r_out, dd_out, x, ctl);
-            else hipLaunchKernelGGL(k_amg_spmv_ep_vd<kEpFirstRes>, grid, block, lds, s->stream, A, q, d, L.vd_n, xin, r_in, dinv, lam, M.eig_ratio, step, add_dd0, r_out, dd_out, x, ctl);
+            if (mode == kEpNextLast) hipLaunchKernelGGL((k_amg_spmv_ep_vd<kEpNextLast, false>), grid, block, lds, s->stream, A, q, d, L.vd_n, xin, r_in, dinv, lam, M.eig_ratio, step, add_dd0, r_out, dd_out, x, ctl, nullptr, nullptr, 0);
+            else if (mode == kEpResid) hipLaunchKernelGGL((k_amg_spmv_ep_vd<kEpResid, false>), grid, block, lds, s->stream, A, q, d, L.vd_n, xin, r_in, dinv, lam, M.eig_ratio, step, add_dd0, r_out, dd_out, x, ctl, nullptr, nullptr, 0);
+            else hipLaunchKernelGGL((k_amg_spmv_ep_vd<kEpFirstRes, false>), grid, block, lds, s->stream, A, q, d, L.vd_n, xin, r_in, dinv, lam, M.eig_ratio, step, add_dd0, r_out, dd_out, x, ctl, nullptr, nullptr, 0);
             return;
         }
         if (mode == kEpNextLast) hipLaunchKernelGGL(k_amg_spmv_ep<kEpNextLast>, grid, block, 0, s->stream, A, xin, r_in, dinv, lam, M.eig_ratio, step, add_dd0, r_out, dd_out, x, ctl);
@@ -3480,6 +3562,7 @@ int run_pcg_amg(pfem_solver *s)
     amg_knobs(M);
     PFEM_TRY(amg_cycle_shape(s, M));
     M.coupled_fused = [] { const char *e = std::getenv("PFEM_AMG_COUPLED_FUSED"); return e ? std::atoi(e) != 0 : true; }();
+    M.col_codes = [] { const char *e = std::getenv("PFEM_AMG_COL_CODES"); return e ? std::atoi(e) != 0 : true; }();      // (read at every solve)
     if (M.coupled && M.coupled_fused && !s->d_row_sh.p && s->n_loc > 0) {        // level 0's dof -> shared index table (the coarse levels got theirs with their plans)
         PFEM_TRY(s->d_row_sh.alloc(static_cast<size_t>(s->n_loc)));
         PFEM_HIP(hipMemsetAsync(s->d_row_sh.p, 0xff, sizeof(int32_t) * static_cast<size_t>(s->n_loc), s->stream));
@@ -3495,6 +3578,9 @@ int run_pcg_amg(pfem_solver *s)
     if (M.rep) M.rep->galerkin_fresh = did_symbolic;
     PFEM_TRY(amg_numeric(s, M, overlap));
     PFEM_HIP(hipEventRecord(eb, s->stream));
+    M.cc_used.clear();              // (pfem_solver_amg_column_codes: what this solve's cycles run)
+    for (size_t l = 1; l + 1 < M.lev.size(); ++l)
+        if (amg_level_col_codes(M, *M.lev[l])) M.cc_used.push_back(static_cast<int>(l));
     const unsigned gv = vec_grid(n), gs = spmv_blocks(s);
     const dim3 block(kBlock);
     if (s->d_part_pw.n < gs + 2) PFEM_TRY(s->d_part_pw.alloc(gs + 2));
@@ -3546,6 +3632,10 @@ int run_pcg_amg(pfem_solver *s)
             auto level_key = [&](const std::unique_ptr<AmgLevel> &L) {
                 key.push_back(reinterpret_cast<uint64_t>(L->x)); key.push_back(reinterpret_cast<uint64_t>(L->vals.p)); key.push_back(static_cast<uint64_t>(L->n));
                 key.push_back(L->vd_ok ? static_cast<uint64_t>(L->vd_n + 1) : 0); key.push_back(reinterpret_cast<uint64_t>(L->vcodes.p));
+                // (the column codes: whether the level's products read them, and from where)
+                const bool cc = amg_level_col_codes(M, *L);
+                key.push_back(cc ? static_cast<uint64_t>(L->cd_n + 1) : 0); key.push_back(cc ? reinterpret_cast<uint64_t>(L->ccodes.p) : 0);
+                key.push_back(cc ? reinterpret_cast<uint64_t>(L->cdelta.p) : 0);
             };
             for (auto &L : M.lev) level_key(L);
             if (M.rep) for (auto &L : M.rep->lev) level_key(L);

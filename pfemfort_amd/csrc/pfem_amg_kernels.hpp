@@ -1658,26 +1658,208 @@ __global__ void __launch_bounds__(kBlock) k_amg_spmv_ep(SellDev A, const double 
     }
 }
 
-// the same kernel over 16-bit value codes (pfem_valdict.hpp): v = dict[code], the dictionary in LDS; same products in the same order
-template <int MODE>
+// Column codes of a coarse level (amg_column_codes): one byte per slot, the index of  col - row  among the level's distinct offsets
+// (at most kCcMax), four slots of a lane to the 32-bit word, [slice][quad of slots][lane].  Slice s starts at quad
+// (slice_off[s] / 64 + 3 s) / 4: floor((a + w + 3) / 4) - floor(a / 4) >= ceil(w / 4) for any a, so a slice of width w has its
+// ceil(w / 4) quads before the next slice starts, whatever the widths; cc_words() = where a slice after the last would start.
+constexpr int kCcMax = 256;
+constexpr int kCcHash = 1024;                    // words of the collection's hash tables (in LDS per block, one in memory)
+constexpr int32_t kCcEmpty = INT32_MIN;          // (no offset: columns and rows are both in [0, 2^31))
+struct CcState { int count, fail, mismatch, cap; };
+__host__ __device__ __forceinline__ int64_t cc_word_off(int64_t slice_off_s, int64_t s) { return (((slice_off_s >> 6) + 3 * s) >> 2) << 6; }
+__host__ __device__ __forceinline__ int64_t cc_words(int64_t stored, int64_t n_slices) { return cc_word_off(stored, n_slices); }
+
+__global__ void __launch_bounds__(kBlock) k_cc_fill(int32_t *tab, int n, int32_t v)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i < n) tab[i] = v;
+}
+// d into the open-addressing table tab; *count = distinct offsets in it.  false: the table is full
+__device__ __forceinline__ bool cc_insert(int32_t *tab, int32_t d, int *count)
+{
+    uint32_t h = (static_cast<uint32_t>(d) * 2654435761u) >> 22;
+    for (int p = 0; p < kCcHash; ++p) {
+        int32_t old = __atomic_load_n(&tab[h], __ATOMIC_RELAXED);
+        if (old == kCcEmpty) {
+            old = atomicCAS(&tab[h], kCcEmpty, d);
+            if (old == kCcEmpty) { atomicAdd(count, 1); return true; }
+        }
+        if (old == d) return true;
+        h = (h + 1) & (kCcHash - 1);
+    }
+    return false;
+}
+// the distinct  col - row  over the stored slots (padding included) of the rows < n: per block in LDS, then into gtab.  More than
+// st->cap of them: st->fail, and every block that sees it leaves.  A wave per slice, grid-stride.
+__global__ void __launch_bounds__(kBlock) k_cc_collect(SellDev A, int32_t *gtab, CcState *st)
+{
+    __shared__ int32_t tab[kCcHash];
+    __shared__ int cnt, bad;
+    for (int i = threadIdx.x; i < kCcHash; i += kBlock) tab[i] = kCcEmpty;
+    if (threadIdx.x == 0) { cnt = 0; bad = __atomic_load_n(&st->fail, __ATOMIC_RELAXED); }
+    __syncthreads();
+    const int cap = st->cap;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int64_t s = (static_cast<int64_t>(blockIdx.x) << 2) + wave; s < A.n_slices; s += static_cast<int64_t>(gridDim.x) << 2) {
+        const int64_t off = A.slice_off[s];
+        const int width = static_cast<int>((A.slice_off[s + 1] - off) >> 6);
+        const int64_t i = (s << 6) + lane;
+        if (i >= A.n_rows) continue;
+        const int32_t *__restrict__ cp = A.cols + off + lane;
+        for (int k = 0; k < width; ++k) {
+            if (__atomic_load_n(&bad, __ATOMIC_RELAXED)) break;
+            const int32_t d = cp[64 * k] - static_cast<int32_t>(i);
+            if (!cc_insert(tab, d, &cnt) || __atomic_load_n(&cnt, __ATOMIC_RELAXED) > cap) __atomic_store_n(&bad, 1, __ATOMIC_RELAXED);
+        }
+    }
+    __syncthreads();
+    if (bad) {
+        if (threadIdx.x == 0) atomicExch(&st->fail, 1);
+        return;
+    }
+    for (int i = threadIdx.x; i < kCcHash; i += kBlock)
+        if (tab[i] != kCcEmpty && (!cc_insert(gtab, tab[i], &st->count) || __atomic_load_n(&st->count, __ATOMIC_RELAXED) > cap)) atomicExch(&st->fail, 1);
+}
+// the table in ascending order (one block; every offset finds its rank by counting): cdelta[0 .. st->count)
+__global__ void __launch_bounds__(kCcHash) k_cc_finish(const int32_t *__restrict__ gtab, int32_t *__restrict__ cdelta, CcState *st)
+{
+    __shared__ int32_t tab[kCcHash];
+    tab[threadIdx.x] = gtab[threadIdx.x];
+    __syncthreads();
+    if (st->fail || st->count < 1 || st->count > st->cap || st->count > kCcMax) {
+        if (threadIdx.x == 0) st->fail = 1;
+        return;
+    }
+    const int32_t d = tab[threadIdx.x];
+    if (d == kCcEmpty) return;
+    int rank = 0;
+    for (int j = 0; j < kCcHash; ++j) rank += (tab[j] != kCcEmpty && tab[j] < d) ? 1 : 0;
+    cdelta[rank] = d;
+}
+// a byte per slot of the rows < n: the place of its offset in cdelta (found by bisection in LDS; an offset that is not there:
+// st->fail); a lane writes the words of its row, four slots each, unused bytes of the last word and the lanes past n: 0
+__global__ void __launch_bounds__(kBlock) k_cc_encode(SellDev A, const int32_t *__restrict__ cdelta, CcState *st, uint32_t *__restrict__ cw)
+{
+    __shared__ int32_t cd[kCcMax];
+    if (st->fail) return;
+    const int nd = st->count;
+    for (int i = threadIdx.x; i < nd; i += kBlock) cd[i] = cdelta[i];
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int64_t s = (static_cast<int64_t>(blockIdx.x) << 2) + wave; s < A.n_slices; s += static_cast<int64_t>(gridDim.x) << 2) {
+        const int64_t off = A.slice_off[s];
+        const int width = static_cast<int>((A.slice_off[s + 1] - off) >> 6);
+        const int64_t i = (s << 6) + lane;
+        const int32_t *__restrict__ cp = A.cols + off + lane;
+        uint32_t *__restrict__ wp = cw + cc_word_off(off, s) + lane;
+        for (int k = 0; k < width; k += 4) {
+            uint32_t w = 0;
+            for (int j = 0; j < 4 && k + j < width && i < A.n_rows; ++j) {
+                const int32_t d = cp[64 * (k + j)] - static_cast<int32_t>(i);
+                int lo = 0, hi = nd - 1;
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (cd[mid] < d) lo = mid + 1;
+                    else hi = mid;
+                }
+                if (cd[lo] != d) atomicExch(&st->fail, 1);
+                w |= static_cast<uint32_t>(lo) << (8 * j);
+            }
+            wp[64 * (k >> 2)] = w;
+        }
+    }
+}
+// the check before the form is used: every stored slot of every row < n decoded the way the product decodes it and compared with
+// the level's int32 column, which must lie in [0, n).  Any difference: st->mismatch (the level keeps its int32 kernel)
+__global__ void __launch_bounds__(kBlock) k_cc_verify(SellDev A, const int32_t *__restrict__ cdelta, const uint32_t *__restrict__ cw, CcState *st)
+{
+    __shared__ int32_t cd[kCcMax];
+    if (st->fail) return;
+    const int nd = st->count;
+    for (int i = threadIdx.x; i < kCcMax; i += kBlock) cd[i] = i < nd ? cdelta[i] : 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int wrong = 0;
+    for (int64_t s = (static_cast<int64_t>(blockIdx.x) << 2) + wave; s < A.n_slices; s += static_cast<int64_t>(gridDim.x) << 2) {
+        const int64_t off = A.slice_off[s];
+        const int width = static_cast<int>((A.slice_off[s + 1] - off) >> 6);
+        const int64_t i = (s << 6) + lane;
+        if (i >= A.n_rows) continue;
+        const int32_t *__restrict__ cp = A.cols + off + lane;
+        const uint32_t *__restrict__ wp = cw + cc_word_off(off, s) + lane;
+        for (int k = 0; k < width; ++k) {
+            const uint32_t code = (wp[64 * (k >> 2)] >> (8 * (k & 3))) & 0xffu;
+            const int32_t c = static_cast<int32_t>(i) + cd[code];
+            if (static_cast<int>(code) >= nd || c != cp[64 * k] || c < 0 || c >= A.n_rows) wrong = 1;
+        }
+    }
+    if (wrong) atomicExch(&st->mismatch, 1);
+}
+// diagnostics (pfem_solver_amg_level_columns): the level's columns in slot order decoded from the codes; lanes past n: 0, as k_fill_sell leaves them
+__global__ void __launch_bounds__(kBlock) k_cc_decode(SellDev A, const int32_t *__restrict__ cdelta, int nd, const uint32_t *__restrict__ cw, int32_t *__restrict__ out)
+{
+    __shared__ int32_t cd[kCcMax];
+    for (int i = threadIdx.x; i < kCcMax; i += kBlock) cd[i] = i < nd ? cdelta[i] : 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int64_t s = (static_cast<int64_t>(blockIdx.x) << 2) + wave; s < A.n_slices; s += static_cast<int64_t>(gridDim.x) << 2) {
+        const int64_t off = A.slice_off[s];
+        const int width = static_cast<int>((A.slice_off[s + 1] - off) >> 6);
+        const int64_t i = (s << 6) + lane;
+        const uint32_t *__restrict__ wp = cw + cc_word_off(off, s) + lane;
+        for (int k = 0; k < width; ++k)
+            out[off + 64 * k + lane] = i < A.n_rows ? static_cast<int32_t>(i) + cd[(wp[64 * (k >> 2)] >> (8 * (k & 3))) & 0xffu] : 0;
+    }
+}
+
+// the same kernel over 16-bit value codes (pfem_valdict.hpp): v = dict[code], the dictionary in LDS; same products in the same order.
+// CC: the columns come as one-byte codes too (above): col = i + cd[code], the offsets in LDS behind the dictionary, one word of four
+// codes per lane and quad of slots.  The lanes past n of the last slice leave before the loop (they have no codes, and nothing
+// to store); every other lane runs the slots of its row, padding included, in the same order into the same fma chain: same bits.
+template <int MODE, bool CC = false>
 __global__ void __launch_bounds__(kBlock) k_amg_spmv_ep_vd(SellDev A, const uint16_t *__restrict__ codes, const double *__restrict__ dict, int nd,
                                                             const double *__restrict__ xin, const double *r_in, const double *__restrict__ dinv,
                                                             const double *__restrict__ lam, double ratio, int step, int add_dd0, double *r_out,
-                                                            double *dd_out, double *x, const CgCtl *ctl)
+                                                            double *dd_out, double *x, const CgCtl *ctl,
+                                                            const uint32_t *__restrict__ cw = nullptr, const int32_t *__restrict__ cdelta = nullptr, int ncd = 0)
 {
     extern __shared__ double vd[];
     if (ctl && ctl->flag != 0) return;
     for (int i = threadIdx.x; i < nd; i += kBlock) vd[i] = dict[i];
+    int32_t *cd = reinterpret_cast<int32_t *>(vd + nd);
+    if (CC)
+        for (int i = threadIdx.x; i < ncd; i += kBlock) cd[i] = cdelta[i];
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t s = (static_cast<int64_t>(blockIdx.x) << 2) + wave;
     if (s >= A.n_slices) return;
     const int64_t off = A.slice_off[s];
     const int width = static_cast<int>((A.slice_off[s + 1] - off) >> 6);
-    const int32_t *__restrict__ cp = A.cols + off + lane;
     const uint16_t *__restrict__ qp = codes + off + lane;
     double acc = 0.0;
     int k = 0;
+    if (CC) {
+        const int64_t i = (s << 6) + lane;
+        if (i >= A.n_rows) return;
+        const double *__restrict__ xi = xin + i;
+        const uint32_t *__restrict__ wp = cw + cc_word_off(off, s) + lane;
+        for (; k + 4 <= width; k += 4) {
+            uint16_t q[4];
+            double xv[4];
+            const uint32_t w = wp[16 * k];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) q[j] = qp[64 * (k + j)];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) xv[j] = xi[cd[(w >> (8 * j)) & 0xffu]];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc = __builtin_fma(vd[q[j]], xv[j], acc);
+        }
+        if (k < width) {
+            const uint32_t w = wp[16 * k];
+            for (int j = 0; k < width; ++k, ++j) acc = __builtin_fma(vd[qp[64 * k]], xi[cd[(w >> (8 * j)) & 0xffu]], acc);
+        }
+    } else {
+    const int32_t *__restrict__ cp = A.cols + off + lane;
     for (; k + 4 <= width; k += 4) {
         int c[4];
         uint16_t q[4];
@@ -1690,6 +1872,7 @@ __global__ void __launch_bounds__(kBlock) k_amg_spmv_ep_vd(SellDev A, const uint
         for (int j = 0; j < 4; ++j) acc = __builtin_fma(vd[q[j]], xv[j], acc);
     }
     for (; k < width; ++k) acc = __builtin_fma(vd[qp[64 * k]], xin[cp[64 * k]], acc);
+    }
     const int64_t i = (s << 6) + lane;
     if (i >= A.n_rows) return;
     if (MODE == kEpResid) {

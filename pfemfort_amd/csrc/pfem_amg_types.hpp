@@ -96,7 +96,8 @@ struct AmgLevel {
     // smoother and work vectors (x and dd are SpMV inputs: on level 0 they carry the guard bands of the fast SpMV forms)
     DevBuf<double> dinv, t, r, b, x_store, dd_store, lam, part_max;
     // values as 16-bit codes into a dictionary of the distinct ones (pfem_valdict.hpp; scalar coarse levels of a one-rank hierarchy
-    // whose Galerkin sums repeat -- bricks of a lattice): the fused SpMVs of the cycle stream 4 + 2 B a slot instead of 4 + 8
+    // whose Galerkin sums repeat -- bricks of a lattice): the fused SpMVs of the cycle stream 4 + 2 B a slot instead of 4 + 8 (1 + 2 B
+    // with the column codes below)
     DevBuf<uint16_t> vcodes;
     DevBuf<double> vdict;
     DevBuf<unsigned long long> vtable;
@@ -109,6 +110,17 @@ struct AmgLevel {
     bool vd_direct = false;               // this solve's codes came from the Galerkin product: verdict in Amg::vd_states, not read yet
     bool bound_fresh = false;             // dinv and t (ratios) of this level were written by the product that formed its values
     bool bound_done = false;              // ... and lam (their maximum) as well
+    // columns as one-byte codes (amg_column_codes; the levels that take the value dictionary): col - row takes a handful of values on a
+    // lattice's bricks (17 on the levels of a box of tetrahedra; a padding slot holds the row itself: 0).  cdelta = the cd_n distinct offsets, ascending;
+    // ccodes = a byte per slot, its offset's index, four slots of a lane to the word, laid out [slice][quad of slots][lane] with slice
+    // s starting at word 64 * ((slice_off[s] / 64 + 3 s) / 4) (cc_word_off: consecutive slices never overlap whatever their widths).
+    // Built once per hierarchy and compared with `cols` word for word on the device (k_cc_verify) before cc_ok is set; the int32
+    // columns stay for everything else that reads them.
+    DevBuf<int32_t> cdelta;
+    DevBuf<uint32_t> ccodes;
+    int cd_n = 0;
+    bool cc_ok = false, cc_refused = false;
+    bool cc_pending = false;              // built and checked on the stream, the verdict (Amg::cc_states) not read yet
     double *x = nullptr, *dd = nullptr;
     DevBuf<double> x1;                    // W-cycle: the first visit's answer while the second is on its way
     double lam_host = 0.0;
@@ -177,5 +189,10 @@ struct Amg {
     bool rbm = false;                                // some level carries rigid-body modes: eigenvalue bounds on the symmetrically scaled operators
     DevBuf<double> lam2;                             // ... scratch of that second bound
     DevBuf<VdState> vd_states;                       // one verdict per level (amg_value_codes)
+    DevBuf<CcState> cc_states;                       // ... and one of the column codes (amg_column_codes)
+    DevBuf<int32_t> cc_hash;                         // scratch of their collection: the distinct offsets met so far (kCcHash words)
+    bool col_codes = true;                           // PFEM_AMG_COL_CODES (read at every solve): verified levels run k_amg_spmv_ep_vd<., true>
+    int cc_builds = 0;                               // levels whose column codes this hierarchy has built (a refused level is not built again)
+    std::vector<int> cc_used;                        // levels whose products of the last solve read column codes
     int cycle_exchanges = 0, cycle_allreduces = 0;   // coupled: neighbour exchanges / all-reduces one V-cycle enqueues (counted by the last cycle)
 };

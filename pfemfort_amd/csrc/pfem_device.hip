@@ -5247,6 +5247,51 @@ extern "C" int pfem_solver_amg_level_values(pfem_solver *s, int level, int64_t m
     return PFEM_OK;
 }
 
+// the levels whose fused products of the last gamg solve read one-byte column codes (AmgLevel::ccodes), ascending; *builds = how
+// often this hierarchy has built (or tried to build) a level's codes
+extern "C" int pfem_solver_amg_column_codes(pfem_solver *s, int max_levels, int *n_levels, int *levels, int *builds)
+{
+    if (!s || !n_levels || !builds || max_levels < 0 || (max_levels > 0 && !levels)) return PFEM_ERR_ARG;
+    if (!s->amg || !s->amg->symbolic_ok) return PFEM_ERR_STATE;
+    const Amg &M = *s->amg;
+    *n_levels = 0;
+    for (int l : M.cc_used)
+        if (*n_levels < max_levels) levels[(*n_levels)++] = l;
+    *builds = M.cc_builds;
+    return PFEM_OK;
+}
+// the columns of coarse level `level` (>= 1) of the last hierarchy in slot order, padding included: the int32 array the level keeps
+// (decoded = 0), or what the products' decode makes of the level's column codes and offset table, on the device (decoded = 1;
+// PFEM_ERR_STATE when the level has no verified codes)
+extern "C" int pfem_solver_amg_level_columns(pfem_solver *s, int level, int decoded, int64_t max_cols, int32_t *cols, int64_t *stored)
+{
+    if (!s || !stored || level < 1 || max_cols < 0 || (max_cols > 0 && !cols)) return PFEM_ERR_ARG;
+    if (!s->amg || !s->amg->symbolic_ok) return PFEM_ERR_STATE;
+    const std::vector<AmgLevelRef> lev = amg_levels_of(*s->amg);
+    if (static_cast<size_t>(level) >= lev.size()) return PFEM_ERR_STATE;
+    const AmgLevel &L = *lev[static_cast<size_t>(level)].L;
+    if (decoded && !(L.cc_ok && L.ccodes.p && L.cdelta.p)) return PFEM_ERR_STATE;
+    *stored = L.stored;
+    const int64_t n = std::min<int64_t>(max_cols, L.stored);
+    if (n < 1 || !L.cols.p) return PFEM_OK;
+    PFEM_TRY(use_device(s));
+    PFEM_HIP(hipStreamSynchronize(s->stream));
+    if (!decoded) {
+        PFEM_HIP(hipMemcpy(cols, L.cols.p, sizeof(int32_t) * static_cast<size_t>(n), hipMemcpyDeviceToHost));
+        return PFEM_OK;
+    }
+    DevBuf<int32_t> out;
+    PFEM_TRY(out.alloc(static_cast<size_t>(L.stored)));
+    const SellDev A = amg_sell(s, L);
+    const unsigned grid = static_cast<unsigned>(std::min<int64_t>(std::max<int64_t>(1, (A.n_slices + 3) / 4), 4096));
+    hipLaunchKernelGGL(k_cc_decode, dim3(grid), dim3(kBlock), 0, s->stream, A, static_cast<const int32_t *>(L.cdelta.p), L.cd_n,
+                       static_cast<const uint32_t *>(L.ccodes.p), out.p);
+    PFEM_TRY(check_kernel("k_cc_decode"));
+    PFEM_HIP(hipStreamSynchronize(s->stream));
+    PFEM_HIP(hipMemcpy(cols, out.p, sizeof(int32_t) * static_cast<size_t>(n), hipMemcpyDeviceToHost));
+    return PFEM_OK;
+}
+
 // what the last gamg solve ran: 1 = V, 2 = W, and the last level whose problem got two visits
 extern "C" int pfem_solver_amg_cycle(pfem_solver *s, int *cycle, int *last_level_visited_twice)
 {

@@ -262,13 +262,19 @@ class PetscSolver:
         """What the last gamg solve ran: {"cycle": "v" | "w", "last_level_visited_twice": l (0 with the V-cycle),
         "level0_epilogue": the cycle's last fine product carried the final smoothing step and the CG's sums,
         "tail_from": first level of the one-workgroup tail launch (-1: the cycle went level by level to the bottom),
-        "tail_build": None | "memory" | "lds" | "lds+matrix" (where that launch kept the levels' vectors and the first level's matrix)}."""
+        "tail_build": None | "memory" | "lds" | "lds+matrix" (where that launch kept the levels' vectors and the first level's matrix),
+        "column_codes": the levels whose fused products read one-byte column codes, "column_code_builds": how many times this
+        hierarchy has built a level's column codes}."""
         c, w, e, t, tb, bp = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(-1), C.c_int(0), C.c_int(0)
         L.check(L.lib().pfem_solver_amg_cycle(self._h, C.byref(c), C.byref(w)), "pfem_solver_amg_cycle")
         L.check(L.lib().pfem_solver_amg_level0_epilogue(self._h, C.byref(e)), "pfem_solver_amg_level0_epilogue")
         L.check(L.lib().pfem_solver_amg_tail_from(self._h, C.byref(t), C.byref(tb), C.byref(bp)), "pfem_solver_amg_tail_from")
+        ncc, nb = C.c_int(0), C.c_int(0)
+        cc = (C.c_int * 32)()
+        L.check(L.lib().pfem_solver_amg_column_codes(self._h, 32, C.byref(ncc), cc, C.byref(nb)), "pfem_solver_amg_column_codes")
         return {"cycle": "w" if c.value == 2 else "v", "last_level_visited_twice": w.value, "level0_epilogue": bool(e.value),
-                "tail_from": t.value, "tail_build": [None, "memory", "lds", "lds+matrix"][tb.value]}
+                "tail_from": t.value, "tail_build": [None, "memory", "lds", "lds+matrix"][tb.value],
+                "column_codes": list(cc[:ncc.value]), "column_code_builds": nb.value}
 
     def amgBoundsByProducts(self):
         """Coarse levels whose eigenvalue bound the last numeric set-up took from the Galerkin product that formed them, instead of
@@ -327,6 +333,15 @@ class PetscSolver:
         L.check(L.lib().pfem_solver_amg_level_values(self._h, level, 0, None, C.byref(n)), "pfem_solver_amg_level_values")
         a = np.empty(n.value, np.float64)
         L.check(L.lib().pfem_solver_amg_level_values(self._h, level, n.value, _p(a), C.byref(n)), "pfem_solver_amg_level_values")
+        return a
+
+    def amgLevelColumns(self, level, decoded=False):
+        """The columns of coarse ``level`` (>= 1) of the last hierarchy, in slot order (padding included): the level's int32 array,
+        or -- ``decoded`` -- what the device decodes from the level's one-byte column codes and offset table."""
+        n = C.c_int64(0)
+        L.check(L.lib().pfem_solver_amg_level_columns(self._h, level, int(bool(decoded)), 0, None, C.byref(n)), "pfem_solver_amg_level_columns")
+        a = np.empty(n.value, np.int32)
+        L.check(L.lib().pfem_solver_amg_level_columns(self._h, level, int(bool(decoded)), n.value, _p(a), C.byref(n)), "pfem_solver_amg_level_columns")
         return a
 
     def amgAggregates(self, level, n_rows):
