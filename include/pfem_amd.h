@@ -103,6 +103,21 @@ int pfem_elast_tria_ke(const double xNode[3], const double yNode[3],
                        const double *elemData /*E,nu,thick,bx,by*/, const double *timeData,
                        const double valC[6], double K[36], double F[6]);
 
+/* Post-processing of one element from its nodal values valC[nsize] -- the grad u -> strain -> stress -> B^T sigma chain of
+ * ResidualElasticityLinearTetra (elementutilitieselasticity3D.F:575-723) and the residual halves of the StiffnessResidual...
+ * routines, consistent with the Klocal of the routines above (DESIGN.md "Post-processing"):
+ *   grad[ng]   Poisson: grad u (ng = 2 tria, 3 tet).  Elasticity: strain, Voigt order of the B matrix with ENGINEERING shear:
+ *              [xx,yy,zz,gxy,gyz,gzx] (ng = 6) for the tet, [xx,yy,gxy] (ng = 3) for the triangle
+ *   flux[ng]   Poisson: q = -(kx,ky,kz) o grad u (PFEM_POISSON_TRIA_INLINE: k = 1).  Elasticity: sigma = D strain with the D of
+ *              the stiffness routine; the plane-stress D(3,3) = b1(1-nu) of the reference is kept, so the 2-D
+ *              shear stress carries the reference's factor
+ *   scalar     Poisson: |q|_2.  Elasticity: von Mises (plane stress: sqrt(sxx^2 - sxx syy + syy^2 + 3 txy^2))
+ *   fint[nsize] dvol B^T sigma (Poisson: dvol grad N . (k o grad u)) = Klocal valC to rounding, Klocal at af = 1
+ * kind = PFEM_POISSON_TRIA ... PFEM_ELAST_TRIA, elemData as for the kind's stiffness routine (not read for the inline
+ * triangle); zNode may be NULL in 2-D; any output may be NULL.  PFEM_ERR_NEG_JAC for an inverted element.                 */
+int pfem_elem_post(int kind, const double *xNode, const double *yNode, const double *zNode /* NULL in 2-D */,
+                   const double *elemData, const double *valC, double *grad, double *flux, double *scalar, double *fint);
+
 /* ========================================================================= */
 /* 2. driver bookkeeping, host, integer-exact (tetrapoissonparallelimpl1.F)   */
 /* ========================================================================= */
@@ -318,6 +333,28 @@ int pfem_solver_set_cg_single_reduction(pfem_solver *s, int on);
  * NodeDofArrayNew(n,d)-1; the reference's own row formula ignores constrained dofs);
  * ids this rank does not own and negative ids are skipped.                                      */
 int pfem_rhs_add_values(pfem_solver *s, int64_t n, const int64_t *global_dof, const double *values);
+
+/* ---- post-processing of a solution on the device ------------------------- */
+/* u_nodal: host array [node*ndof + d] in the CALLER's node numbering (the one pfem_mesh_upload received, or the generator's own
+ * for pfem_mesh_generate_box*), or NULL = the field of the last solve (x at the free dofs, solnApplied at the constrained ones;
+ * PFEM_ERR_STATE before a solve).  The internal renumbering never shows.  One rank and the batched path only: PFEM_ERR_STATE
+ * on a handle without a mesh (MatSetValues path) and with a communication backend of more than one rank.
+ *
+ * pfem_post_elements: pfem_elem_post for every element, one thread per element; outputs SoA grad[c*nElem + e],
+ * flux[c*nElem + e], scalar[e], any of them NULL.  Needs the mesh only.                                                    */
+int pfem_post_elements(pfem_solver *s, const double *elemData, const double *u_nodal,
+                       double *grad, double *flux, double *scalar);
+/* R[node*ndof + d] = sum over the elements of (K_e u_e - F_e) at EVERY node dof, K_e / F_e exactly those pfem_assemble computes
+ * for elemData / timeData: at a free dof of a converged solution the nodal force applied through pfem_rhs_add_values (zero
+ * where none was), at a constrained dof the reaction; the sum of R_d over all nodes is -sum F_e whatever u is.  With the gather
+ * form of the assembly in effect one thread per node sums its incident elements in ascending element order (no atomics, the
+ * same bits in every run; hub nodes by a restricted atomic pass); otherwise one thread per element with f64 atomics.
+ * Needs the pattern.                                                                                                       */
+int pfem_post_nodal_forces(pfem_solver *s, const double *elemData, const double *timeData,
+                           const double *u_nodal, double *R);
+/* KSPBuildResidual / -ksp_monitor_true_residual: |b - K x|_2 and |b|_2 over the owned rows for the x of the last solve, K x by
+ * the SpMV form in effect (pfem_solver_solve's rnorm is |M^-1 r| of the CG recurrence).  PFEM_ERR_STATE before a solve.     */
+int pfem_solver_true_residual(pfem_solver *s, double *rnorm2, double *bnorm2);
 
 /* ---- inspection / export (device -> host) -------------------------------- */
 /* global dof id of every local row (owned first, then ghosts ascending) */

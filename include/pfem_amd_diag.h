@@ -27,6 +27,8 @@ int pfem_solver_set_assembly_mode(pfem_solver *s, int mode);
  * gather records (> 255 entries: "hubs" -- their rows alone are assembled by a scatter pass with atomics, every other
  * row keeps one writer); threads and LDS bytes per block of the row-accumulating gather kernels                      */
 int pfem_solver_assembly_info(pfem_solver *s, int *gather_form, int *hub_nodes, int *block_threads, int64_t *lds_bytes);
+/* kernel time (HIP events around the kernels; host copies excluded) of the last pfem_post_elements / pfem_post_nodal_forces call */
+int pfem_post_timings(pfem_solver *s, double *elements_ms, double *nodal_forces_ms);
 /* Matrix encoding streamed by the SpMV.  AUTO uses 16-bit gaps between the ascending columns of a
  * row (4 + 2 B per entry instead of 4 B) whenever every gap of the pattern fits, and on top of that
  * serves consecutive rows with identical column sets (the dof rows of a node) from one lane with a

@@ -24,6 +24,7 @@ INSERT_VALUES, ADD_VALUES = 1, 2
 NPELEM = {POISSON_TRIA: 3, POISSON_TET: 4, ELAST_TET: 4, POISSON_TRIA_INLINE: 3, ELAST_TRIA: 3}
 NDOF = {POISSON_TRIA: 1, POISSON_TET: 1, ELAST_TET: 3, POISSON_TRIA_INLINE: 1, ELAST_TRIA: 2}
 NDIM = {POISSON_TRIA: 2, POISSON_TET: 3, ELAST_TET: 3, POISSON_TRIA_INLINE: 2, ELAST_TRIA: 2}
+NG = {POISSON_TRIA: 2, POISSON_TET: 3, ELAST_TET: 6, POISSON_TRIA_INLINE: 2, ELAST_TRIA: 3}   # components of grad / flux (pfem_elem_post)
 
 
 class PfemError(RuntimeError):
@@ -65,6 +66,7 @@ SIGNATURES = {
     "pfem_poisson_tet_ke": [_P] * 8,
     "pfem_elast_tet_ke": [_P] * 8,
     "pfem_elast_tria_ke": [_P] * 7,
+    "pfem_elem_post": [_I] + [_P] * 9,
     "pfem_gen_box_tets": [_D, _D, _I, _D, _D, _I, _D, _D, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "pfem_dof_numbering": [_L, _I, _L, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "pfem_renumber_mesh": [_L, _I, _L, _I, _P, _P, _P, _P, _P, _P],
@@ -133,6 +135,10 @@ SIGNATURES = {
     "pfem_solver_amg_level_columns": [_P, _I, _I, _L, _P, _P],
     "pfem_eval_elems": [_P, _P, _P, _P, _P],
     "pfem_rhs_add_values": [_P, _L, _P, _P],
+    "pfem_post_elements": [_P] * 6,
+    "pfem_post_nodal_forces": [_P] * 5,
+    "pfem_solver_true_residual": [_P, _P, _P],
+    "pfem_post_timings": [_P, _P, _P],
     "pfem_matrix_info": [_P, _P, _P, _P, _P],
     "pfem_get_local_to_global": [_P, _P],
     "pfem_get_csr": [_P, _P, _P, _P],

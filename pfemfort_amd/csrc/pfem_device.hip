@@ -702,6 +702,8 @@ struct pfem_solver {
     int *h_err = nullptr;      // pinned
     int last_its = 0, last_reason = 0;
     double last_rnorm = 0.0;
+    bool solved = false;       // d_x holds the x of a solve of the current pattern (post-processing with u = NULL, true residual)
+    double post_elements_ms = 0.0, post_forces_ms = 0.0;   // kernel time of the last pfem_post_* call (pfem_post_timings)
     int hist_cap = 0;
 
     // compat (host staging of MatSetValues / VecSetValues)
@@ -1578,6 +1580,7 @@ namespace {
 int alloc_vectors(pfem_solver *s)
 {
     const size_t n = static_cast<size_t>(s->n_loc);
+    s->solved = false;
     PFEM_TRY(s->d_rhs.alloc(n));
     PFEM_TRY(s->d_x.alloc(n));
     PFEM_TRY(s->d_r.alloc(n));
@@ -3154,6 +3157,215 @@ extern "C" int pfem_bench_spmv(pfem_solver *s, int reps, double *ms_per_launch)
     double ms = 0;
     PFEM_TRY(elapsed(s, &ms));
     *ms_per_launch = ms / reps;
+    return PFEM_OK;
+}
+
+// ---------------------------------------------------------------------------
+// post-processing: element fields, nodal forces / reactions, true residual
+// ---------------------------------------------------------------------------
+namespace {
+
+// what the post-processing passes do not cover yet: sums over the ranks at interface nodes
+int post_one_rank(const pfem_solver *s, const char *who)
+{
+    if (s->nranks > 1) {
+        set_last_error(std::string(who) + ": not available with a communication backend of more than one rank");
+        return PFEM_ERR_STATE;
+    }
+    return PFEM_OK;
+}
+
+// The nodal field [node * ndof + d] on the device, in the DEVICE's node order: the caller's array (caller's node numbering), or
+// -- u_nodal == NULL -- the field of the last solve: x at the free dofs, solnApplied at the constrained ones.
+int post_nodal_field(pfem_solver *s, const double *u_nodal, DevBuf<double> &u, const char *who)
+{
+    const MeshDev &m = s->mesh;
+    const int64_t nn = m.nNode, nv = nn * m.ndof;
+    PFEM_TRY(u.alloc(static_cast<size_t>(std::max<int64_t>(nv, 1))));
+    if (u_nodal) {
+        std::vector<double> tmp;
+        if (!s->h_nperm.empty()) {
+            tmp.resize(static_cast<size_t>(nv));
+            for (int64_t n = 0; n < nn; ++n)
+                for (int d = 0; d < m.ndof; ++d)
+                    tmp[static_cast<size_t>(static_cast<int64_t>(s->h_nperm[static_cast<size_t>(n)]) * m.ndof + d)] = u_nodal[n * m.ndof + d];
+        }
+        PFEM_HIP(hipMemcpyAsync(u.p, tmp.empty() ? u_nodal : tmp.data(), sizeof(double) * nv, hipMemcpyHostToDevice, s->stream));
+        PFEM_HIP(hipStreamSynchronize(s->stream));       // (tmp goes out of scope)
+        return PFEM_OK;
+    }
+    if (!s->have_pattern || !s->solved) {
+        set_last_error(std::string(who) + ": no nodal field given and no solve of this pattern to take one from");
+        return PFEM_ERR_STATE;
+    }
+    PFEM_HIP(hipMemcpyAsync(u.p, s->d_soln.p, sizeof(double) * nv, hipMemcpyDeviceToDevice, s->stream));
+    if (s->have_incidence && s->n_hubs == 0 && s->d_node_row.p)
+        hipLaunchKernelGGL(k_post_nodal_by_node, dim3(grid_for(nv)), dim3(kBlock), 0, s->stream, nv, static_cast<const int32_t *>(s->d_node_row.p),
+                           static_cast<const double *>(s->d_x.p), u.p);
+    else if (m.nElem > 0)
+        hipLaunchKernelGGL(k_post_nodal_by_elem, dim3(grid_for(m.nElem * m.nsize)), dim3(kBlock), 0, s->stream, m, static_cast<const double *>(s->d_x.p), u.p);
+    return check_kernel("k_post_nodal");
+}
+
+}  // namespace
+
+extern "C" int pfem_post_elements(pfem_solver *s, const double *elemData, const double *u_nodal, double *grad, double *flux, double *scalar)
+{
+    if (!s) return PFEM_ERR_ARG;
+    PFEM_TRY(post_one_rank(s, "pfem_post_elements"));
+    if (!s->have_mesh) {
+        set_last_error("pfem_post_elements: no mesh on the device (the MatSetValues path has none)");
+        return PFEM_ERR_STATE;
+    }
+    const MeshDev &m = s->mesh;
+    if (m.kind != PFEM_POISSON_TRIA_INLINE && !elemData) return PFEM_ERR_ARG;
+    PFEM_TRY(use_device(s));
+    DevBuf<double> u, dg, df, ds;
+    PFEM_TRY(post_nodal_field(s, u_nodal, u, "pfem_post_elements"));
+    const ElemPrm prm = make_prm(elemData, nullptr, m.kind);
+    const int ng = post_components(m.kind);
+    const size_t ne = static_cast<size_t>(m.nElem);
+    if (grad) PFEM_TRY(dg.alloc(std::max<size_t>(ne * ng, 1)));
+    if (flux) PFEM_TRY(df.alloc(std::max<size_t>(ne * ng, 1)));
+    if (scalar) PFEM_TRY(ds.alloc(std::max<size_t>(ne, 1)));
+    PFEM_HIP(hipMemsetAsync(s->d_err.p, 0, sizeof(int), s->stream));
+    PFEM_HIP(hipEventRecord(s->ev0, s->stream));
+    if (m.nElem > 0) {
+        const dim3 grid(grid_for(m.nElem)), block(kBlock);
+        const double *up = u.p;
+#define PFEM_POST(KIND) hipLaunchKernelGGL(k_post_elements<KIND>, grid, block, 0, s->stream, m, prm, up, dg.p, df.p, ds.p, s->d_err.p)
+        switch (m.kind) {
+        case PFEM_POISSON_TRIA: PFEM_POST(PFEM_POISSON_TRIA); break;
+        case PFEM_POISSON_TET: PFEM_POST(PFEM_POISSON_TET); break;
+        case PFEM_ELAST_TET: PFEM_POST(PFEM_ELAST_TET); break;
+        case PFEM_POISSON_TRIA_INLINE: PFEM_POST(PFEM_POISSON_TRIA_INLINE); break;
+        case PFEM_ELAST_TRIA: PFEM_POST(PFEM_ELAST_TRIA); break;
+        }
+#undef PFEM_POST
+        PFEM_TRY(check_kernel("k_post_elements"));
+    }
+    PFEM_HIP(hipEventRecord(s->ev1, s->stream));
+    if (grad) PFEM_HIP(hipMemcpyAsync(grad, dg.p, sizeof(double) * ne * ng, hipMemcpyDeviceToHost, s->stream));
+    if (flux) PFEM_HIP(hipMemcpyAsync(flux, df.p, sizeof(double) * ne * ng, hipMemcpyDeviceToHost, s->stream));
+    if (scalar) PFEM_HIP(hipMemcpyAsync(scalar, ds.p, sizeof(double) * ne, hipMemcpyDeviceToHost, s->stream));
+    int err = 0;
+    PFEM_TRY(fetch_err(s, &err));
+    PFEM_TRY(elapsed(s, &s->post_elements_ms));
+    return err;
+}
+
+extern "C" int pfem_post_nodal_forces(pfem_solver *s, const double *elemData, const double *timeData, const double *u_nodal, double *R)
+{
+    if (!s || !R) return PFEM_ERR_ARG;
+    PFEM_TRY(post_one_rank(s, "pfem_post_nodal_forces"));
+    if (!s->have_mesh) {
+        set_last_error("pfem_post_nodal_forces: no mesh on the device (the MatSetValues path has none)");
+        return PFEM_ERR_STATE;
+    }
+    if (!s->have_pattern) {
+        set_last_error("pfem_post_nodal_forces: build the pattern first");
+        return PFEM_ERR_STATE;
+    }
+    const MeshDev &m = s->mesh;
+    if (m.kind != PFEM_POISSON_TRIA_INLINE && !elemData) return PFEM_ERR_ARG;
+    PFEM_TRY(use_device(s));
+    DevBuf<double> u, dR;
+    PFEM_TRY(post_nodal_field(s, u_nodal, u, "pfem_post_nodal_forces"));
+    const ElemPrm prm = make_prm(elemData, timeData, m.kind);
+    const int64_t nn = m.nNode, nv = nn * m.ndof;
+    PFEM_TRY(dR.alloc(static_cast<size_t>(std::max<int64_t>(nv, 1))));
+    const bool gather = m.nElem > 0 && s->assembly_mode == PFEM_ASSEMBLY_GATHER && s->have_incidence && s->d_inc_rec.p;
+    const uint8_t *hubs = (gather && s->n_hubs > 0) ? s->d_node_hub.p : nullptr;
+    const double *up = u.p;
+    PFEM_HIP(hipMemsetAsync(s->d_err.p, 0, sizeof(int), s->stream));
+    PFEM_HIP(hipEventRecord(s->ev0, s->stream));
+    if (!gather) PFEM_HIP(hipMemsetAsync(dR.p, 0, sizeof(double) * static_cast<size_t>(std::max<int64_t>(nv, 1)), s->stream));
+    if (gather) {
+        // one thread per node, no atomics: every entry of R is stored by its node's thread
+        const dim3 grid(grid_for(nn)), block(kBlock);
+        const int64_t *ip = s->d_inc_ptr.p;
+        const int32_t *ic = s->d_inc_cnt.p;
+        const int4 *irec = s->d_inc_rec.p;
+#define PFEM_POST(KIND) hipLaunchKernelGGL(k_post_forces_gather<KIND>, grid, block, 0, s->stream, m, prm, ip, ic, irec, hubs, up, dR.p, s->d_err.p)
+        switch (m.kind) {
+        case PFEM_POISSON_TRIA: PFEM_POST(PFEM_POISSON_TRIA); break;
+        case PFEM_POISSON_TET: PFEM_POST(PFEM_POISSON_TET); break;
+        case PFEM_ELAST_TET: PFEM_POST(PFEM_ELAST_TET); break;
+        case PFEM_POISSON_TRIA_INLINE: PFEM_POST(PFEM_POISSON_TRIA_INLINE); break;
+        case PFEM_ELAST_TRIA: PFEM_POST(PFEM_ELAST_TRIA); break;
+        }
+#undef PFEM_POST
+        PFEM_TRY(check_kernel("k_post_forces_gather"));
+    }
+    if (m.nElem > 0 && (!gather || hubs)) {
+        // one thread per element, f64 atomics: the whole mesh (scatter form, no incidence records), or the hub nodes only
+        const dim3 grid(grid_for(m.nElem)), block(kBlock);
+#define PFEM_POST(KIND) hipLaunchKernelGGL(k_post_forces_scatter<KIND>, grid, block, 0, s->stream, m, prm, hubs, up, dR.p, s->d_err.p)
+        switch (m.kind) {
+        case PFEM_POISSON_TRIA: PFEM_POST(PFEM_POISSON_TRIA); break;
+        case PFEM_POISSON_TET: PFEM_POST(PFEM_POISSON_TET); break;
+        case PFEM_ELAST_TET: PFEM_POST(PFEM_ELAST_TET); break;
+        case PFEM_POISSON_TRIA_INLINE: PFEM_POST(PFEM_POISSON_TRIA_INLINE); break;
+        case PFEM_ELAST_TRIA: PFEM_POST(PFEM_ELAST_TRIA); break;
+        }
+#undef PFEM_POST
+        PFEM_TRY(check_kernel("k_post_forces_scatter"));
+    }
+    PFEM_HIP(hipEventRecord(s->ev1, s->stream));
+    std::vector<double> tmp;
+    double *out = R;
+    if (!s->h_niperm.empty()) { tmp.resize(static_cast<size_t>(nv)); out = tmp.data(); }
+    PFEM_HIP(hipMemcpyAsync(out, dR.p, sizeof(double) * nv, hipMemcpyDeviceToHost, s->stream));
+    int err = 0;
+    PFEM_TRY(fetch_err(s, &err));
+    PFEM_TRY(elapsed(s, &s->post_forces_ms));
+    if (err) return err;
+    if (!s->h_niperm.empty())             // the caller's node numbering
+        for (int64_t i = 0; i < nn; ++i)
+            for (int d = 0; d < m.ndof; ++d)
+                R[static_cast<int64_t>(s->h_niperm[static_cast<size_t>(i)]) * m.ndof + d] = tmp[static_cast<size_t>(i * m.ndof + d)];
+    return PFEM_OK;
+}
+
+// |b - K x|_2 and |b|_2 over the owned rows for the x of the last solve, K x by the SpMV form in effect (KSPBuildResidual /
+// -ksp_monitor_true_residual: the CG's own rnorm is |M^-1 r| of its recurrence)
+extern "C" int pfem_solver_true_residual(pfem_solver *s, double *rnorm2, double *bnorm2)
+{
+    if (!s) return PFEM_ERR_ARG;
+    PFEM_TRY(post_one_rank(s, "pfem_solver_true_residual"));
+    if (!s->have_pattern || !s->solved) {
+        set_last_error("pfem_solver_true_residual: no solve of this pattern yet");
+        return PFEM_ERR_STATE;
+    }
+    PFEM_TRY(use_device(s));
+    const int64_t n = s->n_loc;
+    DevBuf<double> part;
+    PFEM_TRY(part.alloc(2 * kMaxGrid + 2));
+    PFEM_HIP(hipMemcpyAsync(s->d_p.p, s->d_x.p, sizeof(double) * static_cast<size_t>(n), hipMemcpyDeviceToDevice, s->stream));
+    mark_group_vals(s);
+    PFEM_TRY(refresh_group_vals(s));
+    launch_spmv<false>(s, s->d_p.p, s->d_w.p, 0, nullptr, nullptr);
+    PFEM_TRY(check_kernel("k_spmv"));
+    const unsigned gv = vec_grid(s->n_owned);
+    hipLaunchKernelGGL(k_post_residual_partials, dim3(gv), dim3(kBlock), 0, s->stream, s->n_owned, static_cast<const double *>(s->d_rhs.p),
+                       static_cast<const double *>(s->d_w.p), part.p, part.p + kMaxGrid);
+    hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, s->stream, static_cast<const double *>(part.p),
+                       static_cast<const double *>(part.p + kMaxGrid), static_cast<int>(gv), part.p + 2 * kMaxGrid, static_cast<const CgCtl *>(nullptr));
+    PFEM_TRY(check_kernel("k_post_residual_partials"));
+    double h[2] = {0.0, 0.0};
+    PFEM_HIP(hipMemcpyAsync(h, part.p + 2 * kMaxGrid, 2 * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    PFEM_HIP(hipStreamSynchronize(s->stream));
+    if (rnorm2) *rnorm2 = std::sqrt(h[0]);
+    if (bnorm2) *bnorm2 = std::sqrt(h[1]);
+    return PFEM_OK;
+}
+
+// kernel time of the last pfem_post_elements / pfem_post_nodal_forces call (HIP events around the kernels, host copies excluded)
+extern "C" int pfem_post_timings(pfem_solver *s, double *elements_ms, double *nodal_forces_ms)
+{
+    if (!s) return PFEM_ERR_ARG;
+    if (elements_ms) *elements_ms = s->post_elements_ms;
+    if (nodal_forces_ms) *nodal_forces_ms = s->post_forces_ms;
     return PFEM_OK;
 }
 
@@ -4935,6 +5147,7 @@ extern "C" int pfem_solver_solve(pfem_solver *s, int *its, int *reason, double *
         s->host_values_dirty = false;
     }
     PFEM_TRY(run_pcg(s));
+    s->solved = true;
     PFEM_HIP(hipEventRecord(s->ev1, s->stream));
     PFEM_TRY(elapsed(s, &s->tm.solve_ms));
     if (s->comm) PFEM_TRY(s->comm->health());

@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #define PFEM_HD __host__ __device__ __forceinline__
 #else
+#include <cmath>
 #define PFEM_HD inline
 #endif
 
@@ -479,6 +480,193 @@ PFEM_HD bool elast_tet(const double x[4], const double y[4], const double z[4], 
         F[3 * a + 0] = 0.0 + b4 * bforce[0];
         F[3 * a + 1] = 0.0 + b4 * bforce[1];
         F[3 * a + 2] = 0.0 + b4 * bforce[2];
+    }
+    return true;
+}
+
+// ---------------------------------------------------------------------------
+// Post-processing of a solution, element by element (pfem_elem_post / pfem_post_elements / pfem_post_nodal_forces): from the
+// nodal values valC of one element
+//   grad   Poisson: grad u.  Elasticity: the strain B valC in the B matrix's own Voigt order with ENGINEERING shear --
+//          [xx,yy,zz,gxy,gyz,gzx] for the tet [elementutilitieselasticity3D.F:359-371], [xx,yy,gxy] for the triangle.
+//   flux   Poisson: q = -(kx,ky,kz) o grad u.  Elasticity: sigma = D strain with the very D the stiffness routine beside it
+//          uses (elast_material / elast2d_material).  The plane-stress D(3,3) is the reference's b1(1-nu) = 2G:
+//          the 2-D shear stress therefore carries the reference's factor, twice the textbook G gxy.
+//   scalar Poisson: |q|_2.  Elasticity: von Mises -- the 6-component form in 3-D, sqrt(sxx^2 - sxx syy + syy^2 + 3 txy^2)
+//          for plane stress.
+//   fint   dvol B^T sigma (Poisson: dvol grad N . (k o grad u)): the element's internal nodal forces.  fint = Klocal valC to
+//          rounding, with Klocal of the stiffness routine at af = 1 (tests/test_post_host.py).
+// Geometry, material and dvol are those of the stiffness routines.  Two things of the reference are NOT followed, because
+// they disagree with the K they sit beside (DESIGN.md "deviations"): its explicit residual routine multiplies HALF shear
+// strains by G [elementutilitieselasticity3D.F:676-683], and the residual half of the Poisson routines (poisson_tet above,
+// `f - b1*du0 ...`) leaves the conductivity out.  dvol is handed back for the load vector of the nodal forces.
+// ---------------------------------------------------------------------------
+PFEM_HD bool poisson_tet_post(const double x[4], const double y[4], const double z[4], double kx, double ky, double kz,
+                              const double valC[4], double grad[3], double flux[3], double &scalar, double fint[4], double &dvol)
+{
+    TetGeom g;
+    tet_geometry(x, y, z, g);
+    if (g.jac < 0.0) return false;
+    dvol = kGaussWtTet * g.jac;
+    double du0 = 0.0, du1 = 0.0, du2 = 0.0;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        du0 = du0 + valC[a] * g.gx[a];
+        du1 = du1 + valC[a] * g.gy[a];
+        du2 = du2 + valC[a] * g.gz[a];
+    }
+    const double q0 = kx * du0, q1 = ky * du1, q2 = kz * du2;      // k o grad u
+    grad[0] = du0;  grad[1] = du1;  grad[2] = du2;
+    flux[0] = -q0;  flux[1] = -q1;  flux[2] = -q2;
+    scalar = sqrt((q0 * q0 + q1 * q1) + q2 * q2);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const double b1 = g.gx[i] * dvol, b2 = g.gy[i] * dvol, b3 = g.gz[i] * dvol;
+        fint[i] = (b1 * q0 + b2 * q1) + b3 * q2;
+    }
+    return true;
+}
+
+// `oriented` = false: the inline element of the serial driver (poisson_tria_inline), which has no orientation test -- k = 1 and
+// the gradients of tria_geometry (differences of coordinates; the inline routine's own area formula, products of absolute
+// coordinates, loses digits that a gradient of the solution should not lose: its fint agrees with poisson_tria_inline's
+// K valC to the rounding of THAT formula)
+PFEM_HD bool poisson_tria_post(const double x[3], const double y[3], double kx, double ky, const double valC[3], double grad[2],
+                               double flux[2], double &scalar, double fint[3], double &dvol, bool oriented = true)
+{
+    TriaGeom g;
+    tria_geometry(x, y, g);
+    if (oriented && g.jac < 0.0) return false;
+    dvol = 0.5 * g.jac;
+    double du0 = 0.0, du1 = 0.0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        du0 = du0 + valC[a] * g.gx[a];
+        du1 = du1 + valC[a] * g.gy[a];
+    }
+    const double q0 = kx * du0, q1 = ky * du1;
+    grad[0] = du0;  grad[1] = du1;
+    flux[0] = -q0;  flux[1] = -q1;
+    scalar = sqrt(q0 * q0 + q1 * q1);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) fint[i] = (g.gx[i] * dvol) * q0 + (g.gy[i] * dvol) * q1;
+    return true;
+}
+
+PFEM_HD bool elast_tet_post(const double x[4], const double y[4], const double z[4], double E, double nu, const double valC[12],
+                            double grad[6], double flux[6], double &scalar, double fint[12], double &dvol)
+{
+    TetGeom g;
+    tet_geometry(x, y, z, g);
+    if (g.jac < 0.0) return false;
+    dvol = kGaussWtTet * g.jac;
+    const ElastMat m = elast_material(E, nu);
+    // strain = B valC, B rows [xx,yy,zz,xy,yz,zx]: column 3a+0 = (gx,0,0,gy,0,gz), 3a+1 = (0,gy,0,gx,gz,0), 3a+2 = (0,0,gz,0,gy,gx)
+    double exx = 0.0, eyy = 0.0, ezz = 0.0, gxy = 0.0, gyz = 0.0, gzx = 0.0;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const double u = valC[3 * a], v = valC[3 * a + 1], w = valC[3 * a + 2];
+        exx = exx + g.gx[a] * u;
+        eyy = eyy + g.gy[a] * v;
+        ezz = ezz + g.gz[a] * w;
+        gxy = (gxy + g.gy[a] * u) + g.gx[a] * v;
+        gyz = (gyz + g.gz[a] * v) + g.gy[a] * w;
+        gzx = (gzx + g.gz[a] * u) + g.gx[a] * w;
+    }
+    const double sxx = (m.d11 * exx + m.d12 * eyy) + m.d12 * ezz;
+    const double syy = (m.d12 * exx + m.d11 * eyy) + m.d12 * ezz;
+    const double szz = (m.d12 * exx + m.d12 * eyy) + m.d11 * ezz;
+    const double txy = m.gsh * gxy, tyz = m.gsh * gyz, tzx = m.gsh * gzx;
+    grad[0] = exx;  grad[1] = eyy;  grad[2] = ezz;  grad[3] = gxy;  grad[4] = gyz;  grad[5] = gzx;
+    flux[0] = sxx;  flux[1] = syy;  flux[2] = szz;  flux[3] = txy;  flux[4] = tyz;  flux[5] = tzx;
+    const double d0 = sxx - syy, d1 = syy - szz, d2 = szz - sxx;
+    scalar = sqrt(0.5 * ((d0 * d0 + d1 * d1) + d2 * d2) + 3.0 * ((txy * txy + tyz * tyz) + tzx * tzx));
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {                            // B^T sigma: the rows of elast_block_v
+        const double ax = g.gx[a], ay = g.gy[a], az = g.gz[a];
+        fint[3 * a + 0] = dvol * ((ax * sxx + ay * txy) + az * tzx);
+        fint[3 * a + 1] = dvol * ((ay * syy + ax * txy) + az * tyz);
+        fint[3 * a + 2] = dvol * ((az * szz + ay * tyz) + ax * tzx);
+    }
+    return true;
+}
+
+PFEM_HD bool elast_tria_post(const double x[3], const double y[3], double E, double nu, double thick, const double valC[6],
+                             double grad[3], double flux[3], double &scalar, double fint[6], double &dvol)
+{
+    TriaGeom g;
+    tria_geometry(x, y, g);
+    if (g.jac < 0.0) return false;
+    dvol = 0.5 * (g.jac * thick);
+    const Elast2dMat m = elast2d_material(E, nu);
+    double exx = 0.0, eyy = 0.0, gxy = 0.0;                  // B columns (gx,0,gy) / (0,gy,gx)
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        exx = exx + g.gx[a] * valC[2 * a];
+        eyy = eyy + g.gy[a] * valC[2 * a + 1];
+        gxy = (gxy + g.gy[a] * valC[2 * a]) + g.gx[a] * valC[2 * a + 1];
+    }
+    const double sxx = m.d11 * exx + m.d12 * eyy, syy = m.d12 * exx + m.d11 * eyy, txy = m.d33 * gxy;
+    grad[0] = exx;  grad[1] = eyy;  grad[2] = gxy;
+    flux[0] = sxx;  flux[1] = syy;  flux[2] = txy;
+    scalar = sqrt(((sxx * sxx - sxx * syy) + syy * syy) + 3.0 * (txy * txy));
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        fint[2 * a] = dvol * (g.gx[a] * sxx + g.gy[a] * txy);
+        fint[2 * a + 1] = dvol * (g.gy[a] * syy + g.gx[a] * txy);
+    }
+    return true;
+}
+
+// components of grad / flux per kind (kinds as in include/pfem_amd.h: 1 Poisson tria, 2 Poisson tet, 3 elasticity tet,
+// 4 inline Poisson tria, 5 elasticity tria)
+PFEM_HD int post_components(int kind) { return kind == 3 ? 6 : ((kind == 2 || kind == 5) ? 3 : 2); }
+
+// One element of any kind; z is not read in 2-D.  ed = elemData of the kind's stiffness routine.
+PFEM_HD bool elem_post(int kind, const double *x, const double *y, const double *z, const double *ed, const double *valC,
+                       double *grad, double *flux, double &scalar, double *fint, double &dvol)
+{
+    switch (kind) {
+    case 1: return poisson_tria_post(x, y, ed[0], ed[1], valC, grad, flux, scalar, fint, dvol);
+    case 2: return poisson_tet_post(x, y, z, ed[0], ed[1], ed[2], valC, grad, flux, scalar, fint, dvol);
+    case 3: return elast_tet_post(x, y, z, ed[0], ed[1], valC, grad, flux, scalar, fint, dvol);
+    case 4: return poisson_tria_post(x, y, 1.0, 1.0, valC, grad, flux, scalar, fint, dvol, false);
+    default: return elast_tria_post(x, y, ed[0], ed[1], ed[2], valC, grad, flux, scalar, fint, dvol);
+    }
+}
+
+// r = Klocal valC - Flocal for the Klocal, Flocal the assembly takes from the stiffness routine with valC = 0 (af scales the
+// Poisson matrices only; source term -6 of the Poisson tet, body force of the elasticity kinds): the element's share of the
+// nodal forces R of pfem_post_nodal_forces.
+PFEM_HD bool elem_nodal_forces(int kind, const double *x, const double *y, const double *z, const double *ed, double af,
+                               const double *valC, double *r)
+{
+    double grad[6], flux[6], scalar, dvol;
+    if (!elem_post(kind, x, y, z, ed, valC, grad, flux, scalar, r, dvol)) return false;
+    if (kind == 2) {
+        const double N[4] = {0.25, 0.25, 1.0 - 0.25 - 0.25 - 0.25, 0.25};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) r[i] = af * r[i] - (N[i] * dvol) * -6.0;
+    } else if (kind == 1) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) r[i] = af * r[i];
+    } else if (kind == 3) {
+        const double N[4] = {0.25, 0.25, 1.0 - 0.25 - 0.25 - 0.25, 0.25};
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            const double b4 = dvol * N[a];
+#pragma unroll
+            for (int d = 0; d < 3; ++d) r[3 * a + d] = r[3 * a + d] - b4 * ed[3 + d];
+        }
+    } else if (kind == 5) {
+        double N[3];
+        tria_shape_gp(N);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const double b4 = dvol * N[a];
+            r[2 * a] = r[2 * a] - b4 * ed[3];
+            r[2 * a + 1] = r[2 * a + 1] - b4 * ed[4];
+        }
     }
     return true;
 }

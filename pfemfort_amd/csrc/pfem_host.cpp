@@ -81,6 +81,24 @@ extern "C" int pfem_elast_tria_ke(const double xNode[3], const double yNode[3], 
     return elast_tria(xNode, yNode, elemData[0], elemData[1], elemData[2], bf, K, F) ? PFEM_OK : PFEM_ERR_NEG_JAC;
 }
 
+// Post-processing of one element (pfem_elem.hpp: elem_post): strain / gradient, stress / flux, von Mises / |q| and the
+// internal nodal forces from the element's nodal values; any output may be NULL.
+extern "C" int pfem_elem_post(int kind, const double *xNode, const double *yNode, const double *zNode, const double *elemData,
+                              const double *valC, double *grad, double *flux, double *scalar, double *fint)
+{
+    if (!kind_valid(kind) || !xNode || !yNode || !valC) return PFEM_ERR_ARG;
+    if (kind_ndim(kind) == 3 && !zNode) return PFEM_ERR_ARG;
+    if (kind != PFEM_POISSON_TRIA_INLINE && !elemData) return PFEM_ERR_ARG;
+    double g[6], f[6], sc = 0.0, fi[12], dvol = 0.0;
+    if (!elem_post(kind, xNode, yNode, zNode, elemData, valC, g, f, sc, fi, dvol)) return PFEM_ERR_NEG_JAC;
+    const int ng = post_components(kind), nsize = kind_npelem(kind) * kind_ndof(kind);
+    if (grad) std::copy(g, g + ng, grad);
+    if (flux) std::copy(f, f + ng, flux);
+    if (scalar) *scalar = sc;
+    if (fint) std::copy(fi, fi + nsize, fint);
+    return PFEM_OK;
+}
+
 // ---------------------------------------------------------------------------
 // 2. structured box mesh (genTetra.cpp)
 // ---------------------------------------------------------------------------

@@ -1550,6 +1550,166 @@ __global__ void __launch_bounds__(kBlock) k_eval_elems(MeshDev m, ElemPrm prm, d
 }
 
 // ---------------------------------------------------------------------------
+// post-processing of a solution (pfem_post_elements / pfem_post_nodal_forces / pfem_solver_true_residual)
+// ---------------------------------------------------------------------------
+// All of it is memory-bound gathering: an element reads npe node ids, npe * (ndim + ndof) doubles through L2 (the nodal
+// vector is at most 3 nNode doubles) and does a few hundred flops.  No LDS; the element arithmetic is pfem_elem.hpp's.
+
+// The nodal field of the last solve, [node * ndof + d] in the device's node order: a free dof takes x at its matrix row, a
+// constrained one keeps the solnApplied the vector was initialised with.  By node where the gather form's node -> row table
+// holds every node (no hubs) ...
+__global__ void __launch_bounds__(kBlock) k_post_nodal_by_node(int64_t n, const int32_t *__restrict__ node_row, const double *__restrict__ x,
+                                                                double *__restrict__ u)
+{
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const int r = node_row[i];
+    if (r >= 0) u[i] = x[r];
+}
+// ... and through the elements' dof arrays otherwise (every element of a node stores the same value)
+__global__ void __launch_bounds__(kBlock) k_post_nodal_by_elem(MeshDev m, const double *__restrict__ x, double *__restrict__ u)
+{
+    const int64_t t = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    if (t >= m.nElem * m.nsize) return;
+    const int64_t e = t % m.nElem;
+    const int i = static_cast<int>(t / m.nElem);
+    const int r = m.edof[t];
+    if (r >= 0) u[static_cast<int64_t>(m.conn[(i / m.ndof) * m.nElem + e]) * m.ndof + i % m.ndof] = x[r];
+}
+
+// coordinates and nodal values of one element from its node numbers (KIND is a template argument of the kernels below: the
+// per-element arrays stay in registers and the switch of elem_post folds away)
+template <int KIND> struct PostKind {
+    static constexpr int NPE = (KIND == PFEM_POISSON_TET || KIND == PFEM_ELAST_TET) ? 4 : 3;
+    static constexpr int NDOF = KIND == PFEM_ELAST_TET ? 3 : (KIND == PFEM_ELAST_TRIA ? 2 : 1);
+    static constexpr int NDIM = NPE == 4 ? 3 : 2;
+    static constexpr int NG = KIND == PFEM_ELAST_TET ? 6 : ((KIND == PFEM_POISSON_TET || KIND == PFEM_ELAST_TRIA) ? 3 : 2);
+};
+template <int KIND>
+__device__ __forceinline__ void post_load_elem(const MeshDev &m, const int nd[4], const double *__restrict__ u, double x[4], double y[4],
+                                               double z[4], double valC[12])
+{
+    using P = PostKind<KIND>;
+#pragma unroll
+    for (int a = 0; a < P::NPE; ++a) {
+        x[a] = m.xyz[nd[a]];
+        y[a] = m.xyz[m.nNode + nd[a]];
+        z[a] = P::NDIM == 3 ? m.xyz[2 * m.nNode + nd[a]] : 0.0;
+#pragma unroll
+        for (int d = 0; d < P::NDOF; ++d) valC[P::NDOF * a + d] = u[static_cast<int64_t>(nd[a]) * P::NDOF + d];
+    }
+}
+
+// One thread per element: gradient / strain, flux / stress, |q| / von Mises, stored SoA (component-major, coalesced in e).
+template <int KIND>
+__global__ void __launch_bounds__(kBlock) k_post_elements(MeshDev m, ElemPrm prm, const double *__restrict__ u, double *__restrict__ grad,
+                                                           double *__restrict__ flux, double *__restrict__ scalar, int *err)
+{
+    using P = PostKind<KIND>;
+    const int64_t e = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    if (e >= m.nElem) return;
+    int nd[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int a = 0; a < P::NPE; ++a) nd[a] = m.conn[a * m.nElem + e];
+    double x[4], y[4], z[4], valC[12], g[6], f[6], fint[12], sc, dvol;
+    post_load_elem<KIND>(m, nd, u, x, y, z, valC);
+    if (!elem_post(KIND, x, y, z, prm.ed, valC, g, f, sc, fint, dvol)) { atomicMax(err, PFEM_ERR_NEG_JAC); return; }
+#pragma unroll
+    for (int c = 0; c < P::NG; ++c) {
+        if (grad) grad[c * m.nElem + e] = g[c];
+        if (flux) flux[c * m.nElem + e] = f[c];
+    }
+    if (scalar) scalar[e] = sc;
+}
+
+// Nodal forces R[node * ndof + d] = sum_e (K_e u_e - F_e), gather form: one thread per node walks the node's packed incidence
+// records (ascending element id, the order of the assembly's gather kernels), evaluates the element from the records' other
+// nodes and adds its own rows -- one writer per entry, no atomics, the same bits in every run.  The node's OWN records are
+// read, not the pattern table of the assembly (k_incpat_*): that table covers nodes with a matrix row only, and the reactions
+// live at the nodes without one.  Hub nodes have no records (k_build_inc_rec): their entries are zeroed here and summed by
+// k_post_forces_scatter restricted to them.
+template <int KIND>
+__global__ void __launch_bounds__(kBlock) k_post_forces_gather(MeshDev m, ElemPrm prm, const int64_t *__restrict__ inc_ptr,
+                                                                const int32_t *__restrict__ inc_cnt, const int4 *__restrict__ inc_rec,
+                                                                const uint8_t *__restrict__ node_hub, const double *__restrict__ u,
+                                                                double *__restrict__ R, int *err)
+{
+    using P = PostKind<KIND>;
+    const int64_t n = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    if (n >= m.nNode) return;
+    double acc[P::NDOF];
+#pragma unroll
+    for (int d = 0; d < P::NDOF; ++d) acc[d] = 0.0;
+    const int cnt = (node_hub && node_hub[n]) ? 0 : inc_cnt[n];
+    const int64_t beg = inc_ptr[n >> 6] + (n & 63), end = beg + 64LL * cnt;
+    for (int64_t t = beg; t < end; t += 64) {
+        const int4 rc = inc_rec[t];
+        const int a = static_cast<int>((static_cast<uint32_t>(rc.x) >> 31) | ((static_cast<uint32_t>(rc.y) >> 31) << 1));
+        const int o[3] = {rc.x & 0x7fffffff, rc.y & 0x7fffffff, rc.z};
+        int nd[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int i = 0; i < P::NPE; ++i) {
+            const int q = i < a ? i : (i > 0 ? i - 1 : 0);
+            nd[i] = (i == a) ? static_cast<int>(n) : o[q];
+        }
+        double x[4], y[4], z[4], valC[12], r[12];
+        post_load_elem<KIND>(m, nd, u, x, y, z, valC);
+        if (!elem_nodal_forces(KIND, x, y, z, prm.ed, prm.af, valC, r)) { atomicMax(err, PFEM_ERR_NEG_JAC); continue; }
+#pragma unroll
+        for (int i = 0; i < P::NPE; ++i)
+            if (i == a) {
+#pragma unroll
+                for (int d = 0; d < P::NDOF; ++d) acc[d] += r[P::NDOF * i + d];
+            }
+    }
+#pragma unroll
+    for (int d = 0; d < P::NDOF; ++d) R[n * P::NDOF + d] = acc[d];
+}
+
+// The same sums, scatter form: one thread per element, f64 atomics into R (zeroed by the caller).  only_nodes != nullptr: the
+// hub pass of the gather form -- only the entries of flagged nodes are added.
+template <int KIND>
+__global__ void __launch_bounds__(kBlock) k_post_forces_scatter(MeshDev m, ElemPrm prm, const uint8_t *__restrict__ only_nodes,
+                                                                 const double *__restrict__ u, double *R, int *err)
+{
+    using P = PostKind<KIND>;
+    const int64_t e = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    if (e >= m.nElem) return;
+    int nd[4] = {0, 0, 0, 0};
+    bool any = only_nodes == nullptr;
+#pragma unroll
+    for (int a = 0; a < P::NPE; ++a) {
+        nd[a] = m.conn[a * m.nElem + e];
+        if (only_nodes && only_nodes[nd[a]]) any = true;
+    }
+    if (!any) return;
+    double x[4], y[4], z[4], valC[12], r[12];
+    post_load_elem<KIND>(m, nd, u, x, y, z, valC);
+    if (!elem_nodal_forces(KIND, x, y, z, prm.ed, prm.af, valC, r)) { atomicMax(err, PFEM_ERR_NEG_JAC); return; }
+#pragma unroll
+    for (int a = 0; a < P::NPE; ++a) {
+        if (only_nodes && !only_nodes[nd[a]]) continue;
+#pragma unroll
+        for (int d = 0; d < P::NDOF; ++d) add_f64(&R[static_cast<int64_t>(nd[a]) * P::NDOF + d], r[P::NDOF * a + d]);
+    }
+}
+
+// per-block partials of |b - w|^2 and |b|^2 over the owned rows (w = K x from the SpMV in effect); fixed order, reproducible
+__global__ void __launch_bounds__(kBlock) k_post_residual_partials(int64_t n_owned, const double *__restrict__ b, const double *__restrict__ w,
+                                                                    double *part_r, double *part_b)
+{
+    __shared__ double sm[4];
+    double rr = 0.0, bb = 0.0;
+    for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < n_owned; i += static_cast<int64_t>(gridDim.x) * kBlock) {
+        const double bi = b[i], ri = bi - w[i];
+        rr = __builtin_fma(ri, ri, rr);
+        bb = __builtin_fma(bi, bi, bb);
+    }
+    const double a = block_sum(rr, sm), c = block_sum(bb, sm);
+    if (threadIdx.x == 0) { part_r[blockIdx.x] = a; part_b[blockIdx.x] = c; }
+}
+
+// ---------------------------------------------------------------------------
 // matrix utilities
 // ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(kBlock) k_sell_to_csr(SellDev A, const int64_t *rowptr, int32_t *cols, double *vals)

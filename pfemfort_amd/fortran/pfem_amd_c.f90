@@ -138,6 +138,34 @@ module pfem_amd_c
       type(c_ptr), value :: s
       real(c_double) :: elemData(*), timeData(*)
     end function
+    ! post-processing of a solution (include/pfem_amd.h, sections 1 and 4); arguments that may be NULL are passed as
+    ! type(c_ptr) by value (c_loc of the array, or c_null_ptr)
+    integer(c_int) function pfem_elem_post(kind, x, y, z, ed, vc, grad, flux, scalar, fint) bind(C, name="pfem_elem_post")
+      import
+      integer(c_int), value :: kind
+      real(c_double) :: x(*), y(*), vc(*)
+      type(c_ptr), value :: z, ed                 ! z: c_null_ptr in 2-D
+      type(c_ptr), value :: grad, flux, scalar, fint
+    end function
+    integer(c_int) function pfem_post_elements(s, elemData, u_nodal, grad, flux, scalar) bind(C, name="pfem_post_elements")
+      import
+      type(c_ptr), value :: s
+      real(c_double) :: elemData(*)
+      type(c_ptr), value :: u_nodal               ! (node-1)*ndof+dof in the caller's node numbering; c_null_ptr: the last solve's field
+      type(c_ptr), value :: grad, flux, scalar    ! column-major grad(nElem,ng), flux(nElem,ng), scalar(nElem)
+    end function
+    integer(c_int) function pfem_post_nodal_forces(s, elemData, timeData, u_nodal, R) bind(C, name="pfem_post_nodal_forces")
+      import
+      type(c_ptr), value :: s
+      real(c_double) :: elemData(*), timeData(*)
+      type(c_ptr), value :: u_nodal
+      real(c_double) :: R(*)                      ! (node-1)*ndof+dof
+    end function
+    integer(c_int) function pfem_solver_true_residual(s, rnorm2, bnorm2) bind(C, name="pfem_solver_true_residual")
+      import
+      type(c_ptr), value :: s
+      real(c_double) :: rnorm2, bnorm2
+    end function
     function pfem_last_error_string() bind(C, name="pfem_last_error_string") result(p)
       import
       type(c_ptr) :: p

@@ -255,6 +255,20 @@ def StiffnessResidualElasticityLinearTria(xNode, yNode, elemData, timeData, valC
     return K, F
 
 
+def ElementPost(kind, xNode, yNode, zNode, elemData, valC):
+    """Post-processing of one element (pfem_elem_post; the grad u -> strain -> stress -> B^T sigma chain of
+    ResidualElasticityLinearTetra, elementutilitieselasticity3D.F:575-723, consistent with Klocal): returns
+    ``(grad[ng], flux[ng], scalar, fint[nsize])`` -- gradient / engineering Voigt strain, flux / stress, ``|q|`` / von Mises,
+    internal nodal forces ``= Klocal @ valC`` to rounding.  ``zNode`` is None in 2-D."""
+    ng = L.NG[kind]
+    grad = np.empty(ng); flux = np.empty(ng); sc = C.c_double(0); fint = np.empty(L.NPELEM[kind] * L.NDOF[kind])
+    z = None if zNode is None else _f64(zNode)
+    ed = None if elemData is None else _f64(elemData)
+    L.check(L.lib().pfem_elem_post(kind, _p(_f64(xNode)), _p(_f64(yNode)), _p(z), _p(ed), _p(_f64(valC)), _p(grad), _p(flux),
+                                   C.byref(sc), _p(fint)), "pfem_elem_post")
+    return grad, flux, sc.value, fint
+
+
 def find_ghosts(edof, row_start, n_owned):
     """Ascending unique global dof ids of ``edof`` outside the owned block (host-only)."""
     e = _i32(edof).ravel()

@@ -407,6 +407,48 @@ class PetscSolver:
         L.check(L.lib().pfem_eval_elems(self._h, _p(ed), _p(_f64(timeData)), _p(K), _p(F)), "pfem_eval_elems")
         return K.transpose(0, 2, 1).copy(), F     # column-major blocks -> K[e][i,j] = Klocal(i,j)
 
+    # ---- post-processing of a solution (one rank, batched path) -----------------------
+    def elementFields(self, elemData, u=None):
+        """``(grad, flux, scalar)`` of every element for the nodal field ``u`` ((nNode, ndof) or flat, the caller's node numbering;
+        ``None``: the last solve's): gradient / engineering Voigt strain and flux / stress as ``(ng, nElem)``, ``|q|`` / von Mises
+        as ``(nElem,)`` (``host.ElementPost`` is the per-element mirror)."""
+        kind = getattr(self, "kind", None)
+        ed = None if elemData is None else _f64(elemData)
+        uu = None if u is None else _f64(u).ravel()
+        if kind is None:                       # no mesh on this handle: the library says so
+            L.check(L.lib().pfem_post_elements(self._h, _p(ed), _p(uu), None, None, None), "pfem_post_elements")
+        assert uu is None or uu.size == self.nNode * L.NDOF[kind]
+        ng = L.NG[kind]
+        grad = np.empty((ng, self.nElem)); flux = np.empty((ng, self.nElem)); scalar = np.empty(self.nElem)
+        L.check(L.lib().pfem_post_elements(self._h, _p(ed), _p(uu), _p(grad), _p(flux), _p(scalar)), "pfem_post_elements")
+        return grad, flux, scalar
+
+    def nodalForces(self, elemData, timeData, u=None):
+        """``R (nNode, ndof)`` = sum over the elements of ``K_e u_e - F_e`` at every node dof: the applied nodal force at a free dof
+        of a converged solution, the reaction at a constrained one (``u`` as in ``elementFields``)."""
+        kind = getattr(self, "kind", None)
+        ed = None if elemData is None else _f64(elemData)
+        td = None if timeData is None else _f64(timeData)
+        uu = None if u is None else _f64(u).ravel()
+        if kind is None:
+            L.check(L.lib().pfem_post_nodal_forces(self._h, _p(ed), _p(td), _p(uu), _p(np.empty(1))), "pfem_post_nodal_forces")
+        assert uu is None or uu.size == self.nNode * L.NDOF[kind]
+        R = np.empty((self.nNode, L.NDOF[kind]))
+        L.check(L.lib().pfem_post_nodal_forces(self._h, _p(ed), _p(td), _p(uu), _p(R)), "pfem_post_nodal_forces")
+        return R
+
+    def trueResidual(self):
+        """``(|b - K x|_2, |b|_2)`` over the owned rows for the x of the last solve (-ksp_monitor_true_residual)."""
+        r = C.c_double(0); b = C.c_double(0)
+        L.check(L.lib().pfem_solver_true_residual(self._h, C.byref(r), C.byref(b)), "pfem_solver_true_residual")
+        return r.value, b.value
+
+    def postTimings(self):
+        """Kernel milliseconds of the last ``elementFields`` / ``nodalForces`` call (HIP events, host copies excluded)."""
+        a = C.c_double(0); b = C.c_double(0)
+        L.check(L.lib().pfem_post_timings(self._h, C.byref(a), C.byref(b)), "pfem_post_timings")
+        return {"elements_ms": a.value, "nodal_forces_ms": b.value}
+
     def matrixInfo(self):
         a, b, c, d = (C.c_int64(0) for _ in range(4))
         L.check(L.lib().pfem_matrix_info(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)), "pfem_matrix_info")
