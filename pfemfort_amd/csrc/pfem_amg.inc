@@ -3002,25 +3002,18 @@ int amg_value_codes(pfem_solver *s, Amg &M)
     for (int l : build) {
         AmgLevel &L = *M.lev[static_cast<size_t>(l)];
         const unsigned grid = static_cast<unsigned>(std::min<int64_t>((L.stored + kBlock - 1) / kBlock, 4096));
-        PFEM_HIP(hipMemsetAsync(L.vtable.p, 0xff, sizeof(unsigned long long) * kVdTable, s->stream));
-        PFEM_HIP(hipMemsetAsync(M.vd_states.p + l, 0, sizeof(VdState), s->stream));
-        hipLaunchKernelGGL(k_vd_collect, dim3(grid), dim3(kBlock), 0, s->stream, static_cast<const double *>(L.vals.p), L.stored, L.vtable.p, M.vd_states.p + l);
-        hipLaunchKernelGGL(k_vd_finish, dim3(1), dim3(1024), 0, s->stream, static_cast<const unsigned long long *>(L.vtable.p), L.vdict.p, M.vd_states.p + l);
-        PFEM_TRY(check_kernel("k_vd_collect / k_vd_finish (coarse level)"));
-        // the dictionary's hash table: from the next solve on the Galerkin product looks the codes up itself (k_lat_galerkin)
+        // with the dictionary's hash table: from the next solve on the Galerkin product looks the codes up itself (k_lat_galerkin)
         L.vd_hash_ok = false;
         if (!L.vhash.p) PFEM_TRY(L.vhash.alloc(kVdHashSlots));
-        PFEM_HIP(hipMemsetAsync(L.vhash.p, 0xff, sizeof(VdHashEntry) * kVdHashSlots, s->stream));
-        hipLaunchKernelGGL(k_vd_hash_build, dim3((kVdMax + kBlock - 1) / kBlock), dim3(kBlock), 0, s->stream, static_cast<const double *>(L.vdict.p),
-                           static_cast<const VdState *>(M.vd_states.p + l), L.vhash.p);
-        PFEM_TRY(check_kernel("k_vd_hash_build (coarse level)"));
+        PFEM_TRY(enqueue_value_dictionary(s->stream, L.vals.p, L.stored, grid, L.vtable.p, L.vdict.p, M.vd_states.p + l));
+        PFEM_TRY(enqueue_vd_hash(s->stream, L.vdict.p, M.vd_states.p + l, L.vhash.p));
         PFEM_TRY(encode(L, l));
     }
     PFEM_TRY(read_states());
     for (int l : build) {
         AmgLevel &L = *M.lev[static_cast<size_t>(l)];
         const VdState &v = st[static_cast<size_t>(l)];
-        if (v.fail || v.count < 1 || v.count > kVdMax || v.miss) {
+        if (!vd_usable(v)) {
             L.vd_ok = L.vd_have_dict = L.vd_hash_ok = false;
             L.vd_refused = true;              // (for this hierarchy)
         } else {
@@ -3050,7 +3043,8 @@ int amg_level0_codes(pfem_solver *s, Amg &M, AmgLevel &L, bool *yes)
     if (&M != s->amg.get() || M.coupled || M.rbm || cg_multi(s) || !L.fine || L.rbm || L.bs != 1 || !L.code_of.p || !L.code_mask.p || amg_galerkin_by_entry() ||
         s->n_hubs != 0 || L.stored != s->stored || L.glat_refused)
         return PFEM_OK;
-    if (!valdict_enabled() || !s->use_rel() || s->rel_gap32 || s->vd_rows != kRelRows || !(s->vd_ok && s->vd_current && s->vd_have_dict) || s->vd_miss_step ||
+    const SpmvForm f = spmv_form(s);
+    if (!valdict_enabled() || f.layout != SpmvLayout::Rel4 || !f.codes || !s->vd_have_dict || s->vd_miss_step ||
         s->vd_n < 1 || s->vd_n > kVdMax || !s->d_vcodes.p || !s->d_vdict.p || !s->d_relk.p || !s->d_rslice_off.p || s->r_stored < 1 ||
         s->d_vcodes.n < static_cast<size_t>(s->r_stored))
         return PFEM_OK;
@@ -3360,36 +3354,30 @@ double *amg_apply(pfem_solver *s, Amg &M, const double *r, const CgCtl *ctl, boo
         const SellDev A = amg_sell(s, L);
         const dim3 grid(spmv_grid(A.n_slices)), block(kBlock);
         const double *dinv = L.dinv.p, *lam = L.lam.p;
-        if (L.gptr.p && (L.bs == 6 || L.bs == 3)) {          // a level below a rigid-body transfer: node-block form of the same product
-            const int64_t *gp = L.gptr.p;
-            const int32_t *gc = L.gcol.p;
-#define PFEM_BLK_EP(MODEV, CBV) hipLaunchKernelGGL((k_rbm_spmv_ep<MODEV, CBV>), grid, block, 0, s->stream, A, gp, gc, xin, r_in, dinv, lam, M.eig_ratio, step, add_dd0, r_out, dd_out, x, ctl)
-            if (L.bs == 6) { if (mode == kEpNextLast) PFEM_BLK_EP(kEpNextLast, 6); else if (mode == kEpResid) PFEM_BLK_EP(kEpResid, 6); else PFEM_BLK_EP(kEpFirstRes, 6); }
-            else { if (mode == kEpNextLast) PFEM_BLK_EP(kEpNextLast, 3); else if (mode == kEpResid) PFEM_BLK_EP(kEpResid, 3); else PFEM_BLK_EP(kEpFirstRes, 3); }
-#undef PFEM_BLK_EP
-            return;
-        }
-        if (L.vd_ok && L.vcodes.p) {          // the level's values as dictionary codes (amg_value_codes)
-            const uint16_t *q = L.vcodes.p;
-            const double *d = L.vdict.p;
-            if (amg_level_col_codes(M, L)) {          // ... and its columns as one-byte codes (amg_column_codes_enqueue): 1 + 2 B a slot
-                const uint32_t *cw = L.ccodes.p;
-                const int32_t *cdl = L.cdelta.p;
-                const size_t lds_cc = sizeof(double) * static_cast<size_t>(L.vd_n) + sizeof(int32_t) * static_cast<size_t>(L.cd_n);
-#define PFEM_CC_EP(MODEV) hipLaunchKernelGGL((k_amg_spmv_ep_vd<MODEV, true>), grid, block, lds_cc, s->stream, A, q, d, L.vd_n, xin, r_in, dinv, lam, M.eig_ratio, step, add_dd0, r_out, dd_out, x, ctl, cw, cdl, L.cd_n)
-                if (mode == kEpNextLast) PFEM_CC_EP(kEpNextLast); else if (mode == kEpResid) PFEM_CC_EP(kEpResid); else PFEM_CC_EP(kEpFirstRes);
-#undef PFEM_CC_EP
-                return;
+        const hipStream_t st = s->stream;
+        with_ep_mode(mode, [&](auto mode_c) {
+            constexpr int MODE = decltype(mode_c)::value;
+            if (L.gptr.p && (L.bs == 6 || L.bs == 3)) {          // a level below a rigid-body transfer: node-block form of the same product
+                const int64_t *gp = L.gptr.p;
+                const int32_t *gc = L.gcol.p;
+                if (L.bs == 6) hipLaunchKernelGGL((k_rbm_spmv_ep<MODE, 6>), grid, block, 0, st, A, gp, gc, xin, r_in, dinv, lam, M.eig_ratio, step, add_dd0, r_out, dd_out, x, ctl);
+                else hipLaunchKernelGGL((k_rbm_spmv_ep<MODE, 3>), grid, block, 0, st, A, gp, gc, xin, r_in, dinv, lam, M.eig_ratio, step, add_dd0, r_out, dd_out, x, ctl);
+            } else if (L.vd_ok && L.vcodes.p) {          // the level's values as dictionary codes (amg_value_codes)
+                const uint16_t *q = L.vcodes.p;
+                const double *d = L.vdict.p;
+                const size_t lds = sizeof(double) * static_cast<size_t>(L.vd_n);
+                if (amg_level_col_codes(M, L)) {          // ... and its columns as one-byte codes (amg_column_codes_enqueue): 1 + 2 B a slot
+                    const uint32_t *cw = L.ccodes.p;
+                    const int32_t *cdl = L.cdelta.p;
+                    const size_t lds_cc = lds + sizeof(int32_t) * static_cast<size_t>(L.cd_n);
+                    hipLaunchKernelGGL((k_amg_spmv_ep_vd<MODE, true>), grid, block, lds_cc, st, A, q, d, L.vd_n, xin, r_in, dinv, lam, M.eig_ratio, step, add_dd0, r_out, dd_out, x, ctl, cw, cdl, L.cd_n);
+                } else {
+                    hipLaunchKernelGGL((k_amg_spmv_ep_vd<MODE, false>), grid, block, lds, st, A, q, d, L.vd_n, xin, r_in, dinv, lam, M.eig_ratio, step, add_dd0, r_out, dd_out, x, ctl, nullptr, nullptr, 0);
+                }
+            } else {
+                hipLaunchKernelGGL(k_amg_spmv_ep<MODE>, grid, block, 0, st, A, xin, r_in, dinv, lam, M.eig_ratio, step, add_dd0, r_out, dd_out, x, ctl);
             }
-            const size_t lds = sizeof(double) * static_cast<size_t>(L.vd_n);
-            if (mode == kEpNextLast) hipLaunchKernelGGL((k_amg_spmv_ep_vd<kEpNextLast, false>), grid, block, lds, s->stream, A, q, d, L.vd_n, xin, r_in, dinv, lam, M.eig_ratio, step, add_dd0, r_out, dd_out, x, ctl, nullptr, nullptr, 0);
-            else if (mode == kEpResid) hipLaunchKernelGGL((k_amg_spmv_ep_vd<kEpResid, false>), grid, block, lds, s->stream, A, q, d, L.vd_n, xin, r_in, dinv, lam, M.eig_ratio, step, add_dd0, r_out, dd_out, x, ctl, nullptr, nullptr, 0);
-            else hipLaunchKernelGGL((k_amg_spmv_ep_vd<kEpFirstRes, false>), grid, block, lds, s->stream, A, q, d, L.vd_n, xin, r_in, dinv, lam, M.eig_ratio, step, add_dd0, r_out, dd_out, x, ctl, nullptr, nullptr, 0);
-            return;
-        }
-        if (mode == kEpNextLast) hipLaunchKernelGGL(k_amg_spmv_ep<kEpNextLast>, grid, block, 0, s->stream, A, xin, r_in, dinv, lam, M.eig_ratio, step, add_dd0, r_out, dd_out, x, ctl);
-        else if (mode == kEpResid) hipLaunchKernelGGL(k_amg_spmv_ep<kEpResid>, grid, block, 0, s->stream, A, xin, r_in, dinv, lam, M.eig_ratio, step, add_dd0, r_out, dd_out, x, ctl);
-        else hipLaunchKernelGGL(k_amg_spmv_ep<kEpFirstRes>, grid, block, 0, s->stream, A, xin, r_in, dinv, lam, M.eig_ratio, step, add_dd0, r_out, dd_out, x, ctl);
+        });
     };
     // the levels [tail, nl) in one launch
     auto run_tail = [&]() {
@@ -3488,7 +3476,7 @@ double *amg_apply(pfem_solver *s, Amg &M, const double *r, const CgCtl *ctl, boo
             // (other waves still gather L.x), one pair of partials per block, folded to kFoldBlocks here
             const unsigned gs = spmv_blocks(s);
             double *prz = s->d_part_ep.p, *pzz = prz + gs, *frz = pzz + gs, *fzz = frz + kFoldBlocks;
-            launch_spmv_level0_ep(s, L.x, Level0Ep{b, L.dinv.p, L.lam.p, M.eig_ratio, L.t.p, prz, pzz}, ctl);
+            launch_spmv<false, true>(s, L.x, nullptr, 0, nullptr, ctl, nullptr, nullptr, SliceSel{nullptr, 0}, Level0Ep{b, L.dinv.p, L.lam.p, M.eig_ratio, L.t.p, prz, pzz});
             hipLaunchKernelGGL(k_fold_partials2, dim3(kFoldBlocks, 2), dim3(kBlock), 0, s->stream, static_cast<const double *>(prz),
                                static_cast<const double *>(pzz), static_cast<int>(gs), frz, fzz, ctl);
         } else if (l == 0 && last0 == kLast0Product) {
@@ -3598,7 +3586,7 @@ int run_pcg_amg(pfem_solver *s)
     // One rank, level 0 in a relative-group form with 16-bit gaps: the iteration's (r,z), (z,z) are summed per block of the product
     // (1024 consecutive rows, 4 to the thread) and folded to kFoldBlocks -- by the epilogue of the cycle's last product (Level0Ep)
     // where the step rides on it, by k_pc_dots_rows4 behind every other cycle: the layout belongs to the form, not to the fusion.
-    const bool rows4 = !multi && spmv_has_level0_ep(s);
+    const bool rows4 = !multi && spmv_form(s).has_level0_epilogue();
     const bool ep0 = rows4 && fuse_last0;
     const int last0 = ep0 ? kLast0Epilogue : (fuse_last0 ? kLast0Product : kLast0Smooth);
     M.level0_ep = ep0;

@@ -20,6 +20,7 @@
 #include <mutex>
 #include <thread>
 #include <string>
+#include <type_traits>
 #include <deque>
 #include <functional>
 #include <map>
@@ -583,10 +584,6 @@ struct pfem_solver {
     {
         return (vd_refused || !valdict_enabled()) ? kMinGroupsAutoFp64 : kMinGroupsAuto;
     }
-    bool use_grouped() const
-    {
-        return grouped && (spmv_format == PFEM_SPMV_GROUPED || (spmv_format == PFEM_SPMV_AUTO && n_groups >= min_groups_auto()));
-    }
     // SpMV-only relative row groups (k_spmvr): 4 consecutive rows, one relative column stream
     bool relgrouped = false;
     bool rel_gap32 = false;        // ... with one 32-bit gap per entry (offsets further apart than 65535: k_spmvr32)
@@ -636,11 +633,6 @@ struct pfem_solver {
     {
         return dinv_codes ? DinvView{d_dinv.p, d_dcodes.p, d_ddict.p, reinterpret_cast<const int *>(d_dstate.p)}
                           : DinvView{d_dinv.p, nullptr, nullptr, nullptr};
-    }
-    bool use_rel() const
-    {
-        return relgrouped && !use_grouped() &&
-               (spmv_format == PFEM_SPMV_GROUPED || (spmv_format == PFEM_SPMV_AUTO && n_rgroups >= min_groups_auto()));
     }
     SellRDev sellr() const
     {
@@ -770,6 +762,71 @@ struct pfem_solver {
 };
 
 namespace {
+
+// The SpMV form in effect: which of the thirteen kernels the next product launches, and what the getters and the graph keys
+// say about it.  spmv_form() is the one place that combines the format asked for, the forms the pattern has, AUTO's thresholds
+// and the state of the value codes; it is computed per call, never kept (valdict_enabled() and min_groups_auto() read the
+// environment, and tests switch it).
+enum class SpmvLayout { Row32, Row16, Row16Escape, Group3, Rel4, Rel4Gap32 };
+struct SpmvForm {
+    SpmvLayout layout;
+    bool gap_table;   // 16-bit codes whose top bit indexes the table of large gaps (Row16, Group3, Rel4 only)
+    bool codes_fit;   // the code array in place was written for this form (vd_rows), whatever its state
+    bool codes;       // ... and holds the current values against an accepted dictionary: the SpMV streams it (Group3, Rel4 only)
+    bool rel() const { return layout == SpmvLayout::Rel4 || layout == SpmvLayout::Rel4Gap32; }
+    int rows_per_lane() const { return layout == SpmvLayout::Group3 ? kGroupRows : (rel() ? kRelRows : 1); }
+    int code_rows() const { return (layout == SpmvLayout::Group3 || layout == SpmvLayout::Rel4) ? rows_per_lane() : 0; }   // 0: a form without codes
+    int column_bits() const { return (layout == SpmvLayout::Row32 || layout == SpmvLayout::Rel4Gap32) ? 32 : 16; }
+    int64_t slices(const pfem_solver *s) const { return layout == SpmvLayout::Group3 ? s->n_gslices : (rel() ? s->n_rslices : s->n_slices); }
+    bool has_level0_epilogue() const { return layout == SpmvLayout::Rel4; }       // (Level0Ep: either value stream)
+    uint64_t kernel_id() const { return static_cast<uint64_t>(layout) | (gap_table ? 8u : 0u) | (codes ? 16u : 0u); }   // one per kernel, < 32
+};
+SpmvForm spmv_form(const pfem_solver *s)
+{
+    // a group form the pattern has is taken when asked for, and by AUTO from min_groups_auto() groups on
+    const auto taken = [s](int64_t groups) { return s->spmv_format == PFEM_SPMV_GROUPED || (s->spmv_format == PFEM_SPMV_AUTO && groups >= s->min_groups_auto()); };
+    const bool group3 = s->grouped && taken(s->n_groups), rel4 = s->relgrouped && !group3 && taken(s->n_rgroups);
+    const bool row16 = s->cols16 && s->spmv_format != PFEM_SPMV_INT32;
+    const SpmvLayout layout = group3  ? SpmvLayout::Group3
+                              : rel4  ? (s->rel_gap32 ? SpmvLayout::Rel4Gap32 : SpmvLayout::Rel4)
+                              : row16 ? (s->cols16_escape ? SpmvLayout::Row16Escape : SpmvLayout::Row16)
+                                      : SpmvLayout::Row32;
+    SpmvForm f{layout, false, false, false};
+    f.gap_table = layout == SpmvLayout::Rel4 ? s->rel_dict : ((layout == SpmvLayout::Group3 || layout == SpmvLayout::Row16) && s->row_dict);
+    f.codes_fit = f.code_rows() != 0 && s->vd_rows == f.code_rows();
+    f.codes = f.codes_fit && s->vd_ok && s->vd_current;
+    return f;
+}
+
+// compile-time copies of a run-time flag / of the relative groups' gap mode / of an epilogue mode for the kernels' template arguments
+template <class F>
+void with_flag(bool on, F &&f)
+{
+    if (on) f(std::true_type{});
+    else f(std::false_type{});
+}
+template <class F>
+void with_gap_mode(bool gap32, bool dict, F &&f)
+{
+    if (gap32) f(std::integral_constant<int, kGap32>{});
+    else if (dict) f(std::integral_constant<int, kGapDict16>{});
+    else f(std::integral_constant<int, kGapLit16>{});
+}
+template <class F>
+void with_ep_mode(int mode, F &&f)          // (the coarse levels' epilogue mode: pfem_amg.inc)
+{
+    if (mode == kEpNextLast) f(std::integral_constant<int, kEpNextLast>{});
+    else if (mode == kEpResid) f(std::integral_constant<int, kEpResid>{});
+    else f(std::integral_constant<int, kEpFirstRes>{});
+}
+
+// one kernel launch, between the sampling events when the caller has them
+template <class... P, class... A>
+void launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, hipEvent_t e0, hipEvent_t e1, A... args)
+{
+    if (e0) hipExtLaunchKernelGGL(kernel, grid, block, lds, st, e0, e1, 0, static_cast<P>(args)...);
+    else hipLaunchKernelGGL(kernel, grid, block, lds, st, static_cast<P>(args)...);
+}
 
 int use_device(pfem_solver *s)
 {
@@ -2245,7 +2302,8 @@ extern "C" int pfem_assemble(pfem_solver *s, const double *elemData, const doubl
                 PFEM_TRY(allow_lds(reinterpret_cast<const void *>(&k_gather_poisson_tet4)));
                 // (the relative-group copy of the values the CG's SpMV streams is written here too when that form is in use and the
                 // whole matrix is assembled by this kernel: k_rel_vals' 1.9 GB re-pack per solve -- 0.66 ms at config 3 -- goes away)
-                const bool both = s->use_rel() && s->d_relk.p && s->n_hubs == 0;
+                const SpmvForm f = spmv_form(s);
+                const bool both = f.rel() && s->d_relk.p && s->n_hubs == 0;
                 // (level 0's inverse diagonal and Gershgorin ratios for the multigrid's numeric phase, while the rows are in LDS: one rank,
                 // the whole matrix assembled by this kernel, the hierarchy of this pattern in place -- every step but the first)
                 AmgLevel *L0 = (s->pc == PFEM_PC_GAMG && s->amg && s->amg->symbolic_ok && !s->amg->coupled && s->nranks == 1 && s->n_ghost == 0 &&
@@ -2255,7 +2313,7 @@ extern "C" int pfem_assemble(pfem_solver *s, const double *elemData, const doubl
                 // (the SpMV's value CODES instead of the fp64 copy of that form when the last step left a dictionary, its hash table
                 // and a fully encoded code array behind: pfem_vdhash.hpp; else the encode pass of round 5)
                 const bool vd_on = valdict_enabled();
-                const bool direct = both && vd_on && s->vd_have_dict && s->vd_hash_ok && s->vd_ok && s->vd_rows == kRelRows && !s->rel_gap32 && s->d_vhash.p &&
+                const bool direct = both && vd_on && s->vd_have_dict && s->vd_hash_ok && s->vd_ok && f.codes_fit && s->d_vhash.p &&
                                     s->d_vcodes.p && s->d_vstate.p && s->d_vcodes.n >= static_cast<size_t>(s->r_stored);
                 if (direct) {
                     const VdState reset{s->vd_n, 0, 0, 0};
@@ -2282,7 +2340,7 @@ extern "C" int pfem_assemble(pfem_solver *s, const double *elemData, const doubl
             PFEM_TRY(allow_lds(reinterpret_cast<const void *>(&k_gather_elast_rows)));
             // (plain block order: the XCD-contiguous one measured 3 % slower on the beam, 1.605 against 1.56 ms)
             {
-                const bool bothg = s->use_grouped() && s->d_row_group.p && s->n_hubs == 0;
+                const bool bothg = spmv_form(s).layout == SpmvLayout::Group3 && s->d_row_group.p && s->n_hubs == 0;
                 const bool patsf = pats && s->d_pat_flags.p;
                 hipLaunchKernelGGL(k_gather_elast_rows, rgrid, rblock, rlds, s->stream, m, A, s->d_rhs.p, prm, ip, ic, irec, ifl, nrow, s->d_err.p, 0u,
                                    bothg ? static_cast<const int32_t *>(s->d_row_group.p) : nullptr, bothg ? static_cast<const int32_t *>(s->d_group_row0.p) : nullptr,
@@ -2727,16 +2785,12 @@ int build_rel_groups(pfem_solver *s)
     s->r_gap_words = tot_w;
     PFEM_TRY(s->d_rdwords.alloc(static_cast<size_t>(std::max<int64_t>(tot_w, 1))));
     PFEM_TRY(s->d_rvals.alloc(static_cast<size_t>(std::max<int64_t>(tot_e, 1)) * kRelRows));
-#define PFEM_REL_FILL(MODE)                                                                                                       \
-    hipLaunchKernelGGL(k_rel_cols_fill<MODE>, dim3(grid_for(s->n_rslices * 64)), dim3(kBlock), 0, s->stream, s->sell(), s->n_rgroups, \
-                       s->n_rslices, static_cast<const int64_t *>(s->d_rslice_off.p),                                             \
-                       static_cast<const int64_t *>(s->d_rslice_doff.p), s->d_rcol0.p, s->d_rdwords.p,                            \
-                       static_cast<const uint32_t *>(s->d_gap_table.p), s->d_err.p)
     PFEM_HIP(hipMemsetAsync(s->d_err.p, 0, sizeof(int), s->stream));
-    if (gap32) PFEM_REL_FILL(kGap32);
-    else if (dict) PFEM_REL_FILL(kGapDict16);
-    else PFEM_REL_FILL(kGapLit16);
-#undef PFEM_REL_FILL
+    with_gap_mode(gap32, dict, [&](auto mode) {
+        hipLaunchKernelGGL(k_rel_cols_fill<decltype(mode)::value>, dim3(grid_for(s->n_rslices * 64)), dim3(kBlock), 0, s->stream, s->sell(), s->n_rgroups,
+                           s->n_rslices, static_cast<const int64_t *>(s->d_rslice_off.p), static_cast<const int64_t *>(s->d_rslice_doff.p), s->d_rcol0.p,
+                           s->d_rdwords.p, static_cast<const uint32_t *>(s->d_gap_table.p), s->d_err.p);
+    });
     PFEM_TRY(check_kernel("k_rel_cols_fill"));
     int miss = 0;
     PFEM_TRY(fetch_err(s, &miss));
@@ -2761,9 +2815,9 @@ int build_rel_groups(pfem_solver *s)
         PFEM_HIP(hipMemsetAsync(s->d_rvals.p, 0, sizeof(double) * static_cast<size_t>(std::max<int64_t>(tot_e, 1)) * kRelRows, s->stream));
         PFEM_HIP(hipMemsetAsync(s->d_err.p, 0, sizeof(int), s->stream));
         const dim3 vg(static_cast<unsigned>(s->n_rslices));
-        if (gap32) hipLaunchKernelGGL(k_rel_slot_map<kGap32>, vg, dim3(kBlock), 0, s->stream, s->sell(), s->sellr(), s->d_relk.p, s->d_err.p);
-        else if (dict) hipLaunchKernelGGL(k_rel_slot_map<kGapDict16>, vg, dim3(kBlock), 0, s->stream, s->sell(), s->sellr(), s->d_relk.p, s->d_err.p);
-        else hipLaunchKernelGGL(k_rel_slot_map<kGapLit16>, vg, dim3(kBlock), 0, s->stream, s->sell(), s->sellr(), s->d_relk.p, s->d_err.p);
+        with_gap_mode(gap32, dict, [&](auto mode) {
+            hipLaunchKernelGGL(k_rel_slot_map<decltype(mode)::value>, vg, dim3(kBlock), 0, s->stream, s->sell(), s->sellr(), s->d_relk.p, s->d_err.p);
+        });
         PFEM_TRY(check_kernel("k_rel_slot_map"));
         int wide = 0;
         PFEM_TRY(fetch_err(s, &wide));
@@ -2779,17 +2833,37 @@ inline void mark_group_vals(pfem_solver *s)
 {
     // (... or nobody will read that copy: the SpMV streams codes that are current -- written by the assembly itself, its verdict
     // pending, or encoded from a copy that has since been overwritten by nothing)
-    const bool vd_on = valdict_enabled();
-    const bool codes_serve = vd_on && s->use_rel() && s->vd_rows == kRelRows && (s->vd_direct_pending || (s->vd_current && s->vd_ok));
-    s->group_vals_stale = !((s->use_rel() && (s->rel_vals_current || codes_serve)) || (s->use_grouped() && s->grp_vals_current));
+    const SpmvForm f = spmv_form(s);
+    const bool codes_serve = valdict_enabled() && f.rel() && f.codes_fit && (s->vd_direct_pending || (s->vd_current && s->vd_ok));
+    s->group_vals_stale = !((f.rel() && (s->rel_vals_current || codes_serve)) || (f.layout == SpmvLayout::Group3 && s->grp_vals_current));
 }
+
+// The dictionary of `n` values (pfem_valdict.hpp), enqueued: table and state cleared, the distinct values collected and sorted
+// into `dict`.  The verdict stays in `state` for the caller to read, or not.
+int enqueue_value_dictionary(hipStream_t st, const double *vals, int64_t n, unsigned grid, unsigned long long *table, double *dict, VdState *state)
+{
+    PFEM_HIP(hipMemsetAsync(table, 0xff, sizeof(unsigned long long) * kVdTable, st));
+    PFEM_HIP(hipMemsetAsync(state, 0, sizeof(VdState), st));
+    hipLaunchKernelGGL(k_vd_collect, dim3(grid), dim3(kBlock), 0, st, vals, n, table, state);
+    hipLaunchKernelGGL(k_vd_finish, dim3(1), dim3(1024), 0, st, static_cast<const unsigned long long *>(table), dict, state);
+    return check_kernel("k_vd_collect / k_vd_finish");
+}
+// ... and the look-up table by which a kernel finds a value's code itself (pfem_vdhash.hpp)
+int enqueue_vd_hash(hipStream_t st, const double *dict, const VdState *state, VdHashEntry *hash)
+{
+    PFEM_HIP(hipMemsetAsync(hash, 0xff, sizeof(VdHashEntry) * kVdHashSlots, st));
+    hipLaunchKernelGGL(k_vd_hash_build, dim3((kVdMax + kBlock - 1) / kBlock), dim3(kBlock), 0, st, dict, state, hash);
+    return check_kernel("k_vd_hash_build");
+}
+// ... and the verdict that makes it one the kernels may use (`miss`: of the encode pass that followed)
+inline bool vd_usable(const VdState &v) { return !v.fail && v.count >= 1 && v.count <= kVdMax && !v.miss; }
 // The SpMV's codes of the current values (pfem_valdict.hpp).  One wait for the device per call that finds new values: the
 // verdict decides which kernel the solve launches.
 int refresh_value_codes(pfem_solver *s)
 {
     const bool enabled = valdict_enabled();     // (read per call: tests switch it)
     const bool verbose = std::getenv("PFEM_VD_VERBOSE") != nullptr;
-    const int rows = s->use_grouped() ? kGroupRows : ((s->use_rel() && !s->rel_gap32) ? kRelRows : 0);
+    const int rows = spmv_form(s).code_rows();
     if (!enabled || rows == 0 || s->vd_refused) { s->vd_ok = false; return PFEM_OK; }
     if (s->vd_current && s->vd_rows == rows) return PFEM_OK;
     const auto t0 = std::chrono::steady_clock::now();
@@ -2820,14 +2894,10 @@ int refresh_value_codes(pfem_solver *s)
         done = st.miss == 0;
     }
     if (!done) {
-        PFEM_HIP(hipMemsetAsync(s->d_vtable.p, 0xff, sizeof(unsigned long long) * kVdTable, s->stream));
-        PFEM_HIP(hipMemsetAsync(s->d_vstate.p, 0, sizeof(VdState), s->stream));
-        hipLaunchKernelGGL(k_vd_collect, dim3(grid), dim3(kBlock), 0, s->stream, vals, static_cast<int64_t>(rows) * n_entries, s->d_vtable.p, s->d_vstate.p);
-        hipLaunchKernelGGL(k_vd_finish, dim3(1), dim3(1024), 0, s->stream, static_cast<const unsigned long long *>(s->d_vtable.p), s->d_vdict.p, s->d_vstate.p);
-        PFEM_TRY(check_kernel("k_vd_collect / k_vd_finish"));
+        PFEM_TRY(enqueue_value_dictionary(s->stream, vals, static_cast<int64_t>(rows) * n_entries, grid, s->d_vtable.p, s->d_vdict.p, s->d_vstate.p));
         PFEM_HIP(hipMemcpyAsync(&st, s->d_vstate.p, sizeof st, hipMemcpyDeviceToHost, s->stream));
         PFEM_HIP(hipStreamSynchronize(s->stream));
-        if (st.fail || st.count < 1 || st.count > kVdMax) {
+        if (!vd_usable(st)) {          // (miss is 0 here: nothing has been encoded yet)
             s->vd_ok = s->vd_have_dict = s->vd_hash_ok = false;
             s->vd_refused = true;          // (until the pattern changes: a mesh of this kind does not repeat its element matrices)
             if (verbose) std::fprintf(stderr, "  value dictionary: more than %d distinct matrix values, the SpMV keeps its fp64 copy\n", kVdMax);
@@ -2838,10 +2908,7 @@ int refresh_value_codes(pfem_solver *s)
         s->vd_hash_ok = false;
         if (rows == kRelRows) {         // the look-up table the assembly kernel uses from the next step on (pfem_vdhash.hpp)
             if (!s->d_vhash.p) PFEM_TRY(s->d_vhash.alloc(kVdHashSlots));
-            PFEM_HIP(hipMemsetAsync(s->d_vhash.p, 0xff, sizeof(VdHashEntry) * kVdHashSlots, s->stream));
-            hipLaunchKernelGGL(k_vd_hash_build, dim3((kVdMax + kBlock - 1) / kBlock), dim3(kBlock), 0, s->stream, static_cast<const double *>(s->d_vdict.p),
-                               static_cast<const VdState *>(s->d_vstate.p), s->d_vhash.p);
-            PFEM_TRY(check_kernel("k_vd_hash_build"));
+            PFEM_TRY(enqueue_vd_hash(s->stream, s->d_vdict.p, s->d_vstate.p, s->d_vhash.p));
         }
         PFEM_TRY(encode());
         if (st.miss) {                  // (cannot happen for finite values; whatever it is, the fp64 copy is always right)
@@ -2861,9 +2928,9 @@ int refresh_value_codes(pfem_solver *s)
 }
 
 // grouped copy of the current matrix values (the row form is what assembly writes)
-int refresh_group_vals_only(pfem_solver *s);
 int refresh_group_vals(pfem_solver *s)
 {
+    const SpmvForm f = spmv_form(s);
     if (s->vd_direct_pending) {
         // the assembly wrote the SpMV's codes itself (k_gather_poisson_tet4 through the dictionary's hash table): one read of its
         // verdict.  A value the dictionary lacks -- new coefficients, a moved mesh -- and the full path takes over: the fp64 copy of
@@ -2872,7 +2939,7 @@ int refresh_group_vals(pfem_solver *s)
         const bool enabled = valdict_enabled();
         const VdState st = s->vd_direct_verdict;          // (read with the assembly's error word)
         s->vd_miss_step = st.miss || st.fail;
-        if (enabled && !st.miss && !st.fail && s->use_rel() && s->vd_rows == kRelRows) {
+        if (enabled && !st.miss && !st.fail && f.rel() && f.codes_fit) {
             s->vd_ok = s->vd_current = true;
             s->group_vals_stale = false;
             if (std::getenv("PFEM_VD_VERBOSE")) std::fprintf(stderr, "  value dictionary: codes written by the assembly kernel (%d values)\n", s->vd_n);
@@ -2883,28 +2950,20 @@ int refresh_group_vals(pfem_solver *s)
     } else if (!s->vd_current) {
         s->vd_miss_step = false;          // (new values that came without a verdict: k_vd_encode vouches for the codes)
     }
-    PFEM_TRY(refresh_group_vals_only(s));
-    return refresh_value_codes(s);
-}
-int refresh_group_vals_only(pfem_solver *s)
-{
-    if (s->use_rel() && s->group_vals_stale) {
+    if (s->group_vals_stale && f.rows_per_lane() > 1) {          // the form's own fp64 copy, re-packed from the row form
         s->vd_current = false;
-        const dim3 vg(static_cast<unsigned>(s->n_rslices));
-        if (s->rel_gap32) hipLaunchKernelGGL(k_rel_vals<kGap32>, vg, dim3(kBlock), 0, s->stream, s->sell(), s->sellr(), s->d_rvals.p);
-        else if (s->rel_dict) hipLaunchKernelGGL(k_rel_vals<kGapDict16>, vg, dim3(kBlock), 0, s->stream, s->sell(), s->sellr(), s->d_rvals.p);
-        else hipLaunchKernelGGL(k_rel_vals<kGapLit16>, vg, dim3(kBlock), 0, s->stream, s->sell(), s->sellr(), s->d_rvals.p);
-        PFEM_TRY(check_kernel("k_rel_vals"));
+        if (f.rel()) {
+            with_gap_mode(f.layout == SpmvLayout::Rel4Gap32, f.gap_table, [&](auto mode) {
+                hipLaunchKernelGGL(k_rel_vals<decltype(mode)::value>, dim3(static_cast<unsigned>(s->n_rslices)), dim3(kBlock), 0, s->stream, s->sell(),
+                                   s->sellr(), s->d_rvals.p);
+            });
+        } else {
+            hipLaunchKernelGGL(k_group_vals, dim3(grid_for(s->n_gslices * 64)), dim3(kBlock), 0, s->stream, s->sell(), s->sellg(), s->d_gvals.p);
+        }
+        PFEM_TRY(check_kernel("k_rel_vals / k_group_vals"));
         s->group_vals_stale = false;
-        return PFEM_OK;
     }
-    if (!s->use_grouped() || !s->group_vals_stale) return PFEM_OK;
-    s->vd_current = false;
-    hipLaunchKernelGGL(k_group_vals, dim3(grid_for(s->n_gslices * 64)), dim3(kBlock), 0, s->stream, s->sell(), s->sellg(),
-                       s->d_gvals.p);
-    PFEM_TRY(check_kernel("k_group_vals"));
-    s->group_vals_stale = false;
-    return PFEM_OK;
+    return refresh_value_codes(s);
 }
 
 // codes of the inverse diagonal for the Jacobi loop (DinvView), enqueued behind k_invert; nobody waits for the verdict
@@ -2915,16 +2974,13 @@ int encode_dinv(pfem_solver *s, int64_t n)
     // (a matrix that repeats its values: so does its diagonal.  From 2^21 rows on: the encoding costs ~0.5 ms a solve -- the
     // one-workgroup sort of the dictionary most of it --, which 191 iterations at 100^3 do not earn back: 8.8 -> 10.0 ms there)
     const int64_t min_rows = [] { const char *e = std::getenv("PFEM_DINV_CODES_MIN_ROWS"); return e ? std::atoll(e) : static_cast<long long>(1 << 21); }();
-    if (!enabled || !(s->vd_ok && s->vd_current) || n < min_rows) return PFEM_OK;
+    if (!enabled || !spmv_form(s).codes || n < min_rows) return PFEM_OK;
     if (s->d_dcodes.n < static_cast<size_t>(n)) PFEM_TRY(s->d_dcodes.alloc(static_cast<size_t>(n)));
     if (!s->d_ddict.p) PFEM_TRY(s->d_ddict.alloc(kVdMax));
     if (!s->d_dtable.p) PFEM_TRY(s->d_dtable.alloc(kVdTable));
     if (!s->d_dstate.p) PFEM_TRY(s->d_dstate.alloc(1));
     const unsigned grid = static_cast<unsigned>(std::min<int64_t>((n + kBlock - 1) / kBlock, 4096));
-    PFEM_HIP(hipMemsetAsync(s->d_dtable.p, 0xff, sizeof(unsigned long long) * kVdTable, s->stream));
-    PFEM_HIP(hipMemsetAsync(s->d_dstate.p, 0, sizeof(VdState), s->stream));
-    hipLaunchKernelGGL(k_vd_collect, dim3(grid), dim3(kBlock), 0, s->stream, static_cast<const double *>(s->d_dinv.p), n, s->d_dtable.p, s->d_dstate.p);
-    hipLaunchKernelGGL(k_vd_finish, dim3(1), dim3(1024), 0, s->stream, static_cast<const unsigned long long *>(s->d_dtable.p), s->d_ddict.p, s->d_dstate.p);
+    PFEM_TRY(enqueue_value_dictionary(s->stream, s->d_dinv.p, n, grid, s->d_dtable.p, s->d_ddict.p, s->d_dstate.p));
     hipLaunchKernelGGL(k_vd_encode16, dim3(grid), dim3(kBlock), sizeof(uint64_t) * kVdMax, s->stream, static_cast<const double *>(s->d_dinv.p), n,
                        static_cast<const double *>(s->d_ddict.p), s->d_dstate.p, s->d_dcodes.p);
     PFEM_TRY(check_kernel("inverse diagonal: value codes"));
@@ -2932,90 +2988,43 @@ int encode_dinv(pfem_solver *s, int64_t n)
     return PFEM_OK;
 }
 
-inline unsigned spmv_blocks(const pfem_solver *s)
-{
-    return s->use_grouped() ? spmv_grid(s->n_gslices) : (s->use_rel() ? spmv_grid(s->n_rslices) : spmv_grid(s->n_slices));
-}
+inline unsigned spmv_blocks(const pfem_solver *s) { return spmv_grid(spmv_form(s).slices(s)); }
 
-// the CG / standalone SpMV launch: row-grouped form when the pattern has it, else 16-bit gaps when available
-// and not disabled, else int32.  `sel`: all slices (default) or a list of them (multi-GPU boundary / interior pass;
-// `partial` then points at this pass's share of the (p,Ap) partials).
-template <bool WITH_DOT>
+// the CG / standalone SpMV launch in the form in effect (spmv_form).  `sel`: all slices (default) or a list of them (multi-GPU
+// boundary / interior pass; `partial` then points at this pass's share of the (p,Ap) partials).
+// EP: level 0's product of gamg's up leg with the last smoothing step and the CG's (r,z), (z,z) as its epilogue `E` -- the
+// relative-group form with 16-bit gaps has one, with either value stream; the caller has asked has_level0_epilogue().  One
+// rank (all slices, rows 1024 b .. of block b).
+template <bool WITH_DOT, bool EP = false>
 void launch_spmv(pfem_solver *s, const double *x, double *y, int64_t n_dot, double *partial, const CgCtl *ctl,
-                 hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr, SliceSel sel = SliceSel{nullptr, 0})
+                 hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr, SliceSel sel = SliceSel{nullptr, 0}, const Level0Ep &E = Level0Ep{})
 {
-    const dim3 grid(sel.list ? spmv_grid(sel.count) : spmv_blocks(s)), block(kBlock);
-    SellDev A = s->sell();
-    if (s->vd_ok && s->vd_current && s->use_grouped() && s->vd_rows == kGroupRows) {
-        SellGDev G = s->sellg();
-        const unsigned long long *q = s->d_vcodes.p;
-        const double *d = s->d_vdict.p;
-        const size_t lds = sizeof(double) * static_cast<size_t>(s->vd_n);
-        if (s->row_dict) {
-            if (e0) hipExtLaunchKernelGGL((k_spmvg_vd<WITH_DOT, true>), grid, block, lds, s->stream, e0, e1, 0, G, q, d, s->vd_n, s->n_loc, x, y, n_dot, partial, ctl, sel);
-            else hipLaunchKernelGGL((k_spmvg_vd<WITH_DOT, true>), grid, block, lds, s->stream, G, q, d, s->vd_n, s->n_loc, x, y, n_dot, partial, ctl, sel);
-        } else if (e0) hipExtLaunchKernelGGL((k_spmvg_vd<WITH_DOT, false>), grid, block, lds, s->stream, e0, e1, 0, G, q, d, s->vd_n, s->n_loc, x, y, n_dot, partial, ctl, sel);
-        else hipLaunchKernelGGL((k_spmvg_vd<WITH_DOT, false>), grid, block, lds, s->stream, G, q, d, s->vd_n, s->n_loc, x, y, n_dot, partial, ctl, sel);
-    } else if (s->vd_ok && s->vd_current && s->use_rel() && !s->rel_gap32 && s->vd_rows == kRelRows) {
-        SellRDev G = s->sellr();
-        const unsigned long long *q = s->d_vcodes.p;
-        const double *d = s->d_vdict.p;
-        const size_t lds = sizeof(double) * static_cast<size_t>(s->vd_n);
-        if (s->rel_dict) {
-            if (e0) hipExtLaunchKernelGGL((k_spmvr_vd<WITH_DOT, true>), grid, block, lds, s->stream, e0, e1, 0, G, q, d, s->vd_n, s->n_loc, x, y, n_dot, partial, ctl, sel, Level0Ep{});
-            else hipLaunchKernelGGL((k_spmvr_vd<WITH_DOT, true>), grid, block, lds, s->stream, G, q, d, s->vd_n, s->n_loc, x, y, n_dot, partial, ctl, sel, Level0Ep{});
-        } else if (e0) hipExtLaunchKernelGGL((k_spmvr_vd<WITH_DOT, false>), grid, block, lds, s->stream, e0, e1, 0, G, q, d, s->vd_n, s->n_loc, x, y, n_dot, partial, ctl, sel, Level0Ep{});
-        else hipLaunchKernelGGL((k_spmvr_vd<WITH_DOT, false>), grid, block, lds, s->stream, G, q, d, s->vd_n, s->n_loc, x, y, n_dot, partial, ctl, sel, Level0Ep{});
-    } else if (s->use_grouped()) {
-        SellGDev G = s->sellg();
-        if (s->row_dict) {
-            if (e0) hipExtLaunchKernelGGL((k_spmvg<WITH_DOT, true>), grid, block, 0, s->stream, e0, e1, 0, G, s->n_loc, x, y, n_dot, partial, ctl, sel);
-            else hipLaunchKernelGGL((k_spmvg<WITH_DOT, true>), grid, block, 0, s->stream, G, s->n_loc, x, y, n_dot, partial, ctl, sel);
-        } else if (e0) hipExtLaunchKernelGGL((k_spmvg<WITH_DOT, false>), grid, block, 0, s->stream, e0, e1, 0, G, s->n_loc, x, y, n_dot, partial, ctl, sel);
-        else hipLaunchKernelGGL((k_spmvg<WITH_DOT, false>), grid, block, 0, s->stream, G, s->n_loc, x, y, n_dot, partial, ctl, sel);
-    } else if (s->use_rel()) {
-        SellRDev G = s->sellr();
-        if (s->rel_gap32) {
-            if (e0) hipExtLaunchKernelGGL(k_spmvr32<WITH_DOT>, grid, block, 0, s->stream, e0, e1, 0, G, s->n_loc, x, y, n_dot, partial, ctl, sel);
-            else hipLaunchKernelGGL(k_spmvr32<WITH_DOT>, grid, block, 0, s->stream, G, s->n_loc, x, y, n_dot, partial, ctl, sel);
-        } else if (s->rel_dict) {
-            if (e0) hipExtLaunchKernelGGL((k_spmvr<WITH_DOT, true>), grid, block, 0, s->stream, e0, e1, 0, G, s->n_loc, x, y, n_dot, partial, ctl, sel, Level0Ep{});
-            else hipLaunchKernelGGL((k_spmvr<WITH_DOT, true>), grid, block, 0, s->stream, G, s->n_loc, x, y, n_dot, partial, ctl, sel, Level0Ep{});
-        } else if (e0) hipExtLaunchKernelGGL((k_spmvr<WITH_DOT, false>), grid, block, 0, s->stream, e0, e1, 0, G, s->n_loc, x, y, n_dot, partial, ctl, sel, Level0Ep{});
-        else hipLaunchKernelGGL((k_spmvr<WITH_DOT, false>), grid, block, 0, s->stream, G, s->n_loc, x, y, n_dot, partial, ctl, sel, Level0Ep{});
-    } else if (s->cols16 && s->spmv_format != PFEM_SPMV_INT32) {
-        Sell16Dev C{s->d_col0.p, s->d_dwords.p, s->d_slice_doff.p, s->d_row_gap_table.p};
-        if (s->cols16_escape) {
-            if (e0) hipExtLaunchKernelGGL((k_spmv16e<WITH_DOT>), grid, block, 0, s->stream, e0, e1, 0, A, C, x, y, n_dot, partial, ctl, sel);
-            else hipLaunchKernelGGL((k_spmv16e<WITH_DOT>), grid, block, 0, s->stream, A, C, x, y, n_dot, partial, ctl, sel);
-        } else if (s->row_dict) {
-            if (e0) hipExtLaunchKernelGGL((k_spmv16<WITH_DOT, true>), grid, block, 0, s->stream, e0, e1, 0, A, C, x, y, n_dot, partial, ctl, sel);
-            else hipLaunchKernelGGL((k_spmv16<WITH_DOT, true>), grid, block, 0, s->stream, A, C, x, y, n_dot, partial, ctl, sel);
-        } else if (e0) hipExtLaunchKernelGGL((k_spmv16<WITH_DOT, false>), grid, block, 0, s->stream, e0, e1, 0, A, C, x, y, n_dot, partial, ctl, sel);
-        else hipLaunchKernelGGL((k_spmv16<WITH_DOT, false>), grid, block, 0, s->stream, A, C, x, y, n_dot, partial, ctl, sel);
-    } else {
-        if (e0) hipExtLaunchKernelGGL(k_spmv<WITH_DOT>, grid, block, 0, s->stream, e0, e1, 0, A, x, y, n_dot, partial, ctl, sel);
-        else hipLaunchKernelGGL(k_spmv<WITH_DOT>, grid, block, 0, s->stream, A, x, y, n_dot, partial, ctl, sel);
-    }
-}
-
-// Level 0's product of gamg's up leg with the last smoothing step and the CG's (r,z), (z,z) as its epilogue (Level0Ep): the
-// relative-group forms with 16-bit gaps have one, with either value stream.  One rank (all slices, rows 1024 b .. of block b).
-inline bool spmv_has_level0_ep(const pfem_solver *s) { return s->use_rel() && !s->rel_gap32; }
-void launch_spmv_level0_ep(pfem_solver *s, const double *x, const Level0Ep &E, const CgCtl *ctl)
-{
-    const dim3 grid(spmv_blocks(s)), block(kBlock);
-    const SliceSel all{nullptr, 0};
-    SellRDev G = s->sellr();
-    double *none = nullptr;
-    if (s->vd_ok && s->vd_current && s->vd_rows == kRelRows) {
-        const unsigned long long *q = s->d_vcodes.p;
-        const double *d = s->d_vdict.p;
-        const size_t lds = sizeof(double) * static_cast<size_t>(s->vd_n);
-        if (s->rel_dict) hipLaunchKernelGGL((k_spmvr_vd<false, true, true>), grid, block, lds, s->stream, G, q, d, s->vd_n, s->n_loc, x, none, static_cast<int64_t>(0), none, ctl, all, E);
-        else hipLaunchKernelGGL((k_spmvr_vd<false, false, true>), grid, block, lds, s->stream, G, q, d, s->vd_n, s->n_loc, x, none, static_cast<int64_t>(0), none, ctl, all, E);
-    } else if (s->rel_dict) hipLaunchKernelGGL((k_spmvr<false, true, true>), grid, block, 0, s->stream, G, s->n_loc, x, none, static_cast<int64_t>(0), none, ctl, all, E);
-    else hipLaunchKernelGGL((k_spmvr<false, false, true>), grid, block, 0, s->stream, G, s->n_loc, x, none, static_cast<int64_t>(0), none, ctl, all, E);
+    const SpmvForm f = spmv_form(s);
+    const dim3 grid(spmv_grid(sel.list ? sel.count : f.slices(s))), block(kBlock);
+    const hipStream_t st = s->stream;
+    const unsigned long long *q = s->d_vcodes.p;          // f.codes: the value stream ...
+    const double *d = s->d_vdict.p;
+    const size_t lds = f.codes ? sizeof(double) * static_cast<size_t>(s->vd_n) : 0;          // ... and its dictionary in LDS
+    const Sell16Dev C{s->d_col0.p, s->d_dwords.p, s->d_slice_doff.p, s->d_row_gap_table.p};          // (the row forms' 16-bit gaps)
+    with_flag(f.gap_table, [&](auto gap_table) {
+        constexpr bool DICT = decltype(gap_table)::value;
+        switch (f.layout) {
+        case SpmvLayout::Group3:
+            if (f.codes) return launch(k_spmvg_vd<WITH_DOT, DICT>, grid, block, lds, st, e0, e1, s->sellg(), q, d, s->vd_n, s->n_loc, x, y, n_dot, partial, ctl, sel);
+            return launch(k_spmvg<WITH_DOT, DICT>, grid, block, 0, st, e0, e1, s->sellg(), s->n_loc, x, y, n_dot, partial, ctl, sel);
+        case SpmvLayout::Rel4:
+            if (f.codes) return launch(k_spmvr_vd<WITH_DOT, DICT, EP>, grid, block, lds, st, e0, e1, s->sellr(), q, d, s->vd_n, s->n_loc, x, y, n_dot, partial, ctl, sel, E);
+            return launch(k_spmvr<WITH_DOT, DICT, EP>, grid, block, 0, st, e0, e1, s->sellr(), s->n_loc, x, y, n_dot, partial, ctl, sel, E);
+        case SpmvLayout::Rel4Gap32:
+            return launch(k_spmvr32<WITH_DOT>, grid, block, 0, st, e0, e1, s->sellr(), s->n_loc, x, y, n_dot, partial, ctl, sel);
+        case SpmvLayout::Row16:
+            return launch(k_spmv16<WITH_DOT, DICT>, grid, block, 0, st, e0, e1, s->sell(), C, x, y, n_dot, partial, ctl, sel);
+        case SpmvLayout::Row16Escape:
+            return launch(k_spmv16e<WITH_DOT>, grid, block, 0, st, e0, e1, s->sell(), C, x, y, n_dot, partial, ctl, sel);
+        case SpmvLayout::Row32:
+            return launch(k_spmv<WITH_DOT>, grid, block, 0, st, e0, e1, s->sell(), x, y, n_dot, partial, ctl, sel);
+        }
+    });
 }
 
 }  // namespace
@@ -3023,8 +3032,7 @@ void launch_spmv_level0_ep(pfem_solver *s, const double *x, const Level0Ep &E, c
 extern "C" int pfem_solver_get_spmv_format(pfem_solver *s, int *bits_per_column)
 {
     if (!s || !bits_per_column) return PFEM_ERR_ARG;
-    if (s->use_rel()) *bits_per_column = s->rel_gap32 ? 32 : 16;
-    else *bits_per_column = (s->cols16 && s->spmv_format != PFEM_SPMV_INT32) ? 16 : 32;
+    *bits_per_column = spmv_form(s).column_bits();
     return PFEM_OK;
 }
 
@@ -3032,7 +3040,7 @@ extern "C" int pfem_solver_get_spmv_gap_escapes(pfem_solver *s, int *in_use)
 {
     if (!s || !in_use) return PFEM_ERR_ARG;
     if (!s->have_pattern) return PFEM_ERR_STATE;
-    *in_use = (!s->use_rel() && !s->use_grouped() && s->cols16 && s->cols16_escape && s->spmv_format != PFEM_SPMV_INT32) ? 1 : 0;
+    *in_use = spmv_form(s).layout == SpmvLayout::Row16Escape ? 1 : 0;
     return PFEM_OK;
 }
 
@@ -3041,9 +3049,9 @@ extern "C" int pfem_solver_get_spmv_gap_table(pfem_solver *s, int *entries)
     if (!s || !entries) return PFEM_ERR_ARG;
     if (!s->have_pattern) return PFEM_ERR_STATE;
     *entries = 0;
-    const bool row_form16 = !s->use_rel() && (s->use_grouped() || (s->cols16 && s->spmv_format != PFEM_SPMV_INT32));
-    const uint32_t *tbl = (s->use_rel() && s->rel_dict) ? s->d_gap_table.p : ((row_form16 && s->row_dict) ? s->d_row_gap_table.p : nullptr);
-    if (tbl) {
+    const SpmvForm f = spmv_form(s);
+    if (f.gap_table) {
+        const uint32_t *tbl = f.rel() ? s->d_gap_table.p : s->d_row_gap_table.p;
         PFEM_TRY(use_device(s));
         std::vector<uint32_t> t(kGapTable);
         PFEM_HIP(hipMemcpy(t.data(), tbl, sizeof(uint32_t) * kGapTable, hipMemcpyDeviceToHost));
@@ -3076,7 +3084,7 @@ extern "C" int pfem_solver_get_preconditioner(pfem_solver *s, int *pc_in_effect)
 extern "C" int pfem_solver_get_spmv_row_group(pfem_solver *s, int *rows_per_lane)
 {
     if (!s || !rows_per_lane) return PFEM_ERR_ARG;
-    *rows_per_lane = s->use_grouped() ? kGroupRows : (s->use_rel() ? kRelRows : 1);
+    *rows_per_lane = spmv_form(s).rows_per_lane();
     return PFEM_OK;
 }
 
@@ -3088,16 +3096,13 @@ extern "C" int pfem_solver_spmv_bytes(pfem_solver *s, int64_t *format_bytes)
     if (!s || !format_bytes) return PFEM_ERR_ARG;
     if (!s->have_pattern) return PFEM_ERR_STATE;
     int64_t b = 16 * s->n_loc;                                             // x read, y written
-    const bool vd = s->vd_ok && s->vd_current;                             // 8 B of codes per lane entry (all its rows) instead of 8 B per slot
-    if (vd && s->use_grouped() && s->vd_rows == kGroupRows)
-        b += s->g_stored * 8 + s->g_gap_words * 4 + s->n_gslices * (64 * 4 + 16) + (s->n_groups + 1) * 4;
-    else if (vd && s->use_rel() && !s->rel_gap32 && s->vd_rows == kRelRows)
-        b += s->r_stored * 8 + s->r_gap_words * 4 + s->n_rslices * (64 * 4 + 16);
-    else if (s->use_grouped())
-        b += s->g_stored * kGroupRows * 8 + s->g_gap_words * 4 + s->n_gslices * (64 * 4 + 16) + (s->n_groups + 1) * 4;
-    else if (s->use_rel())
-        b += s->r_stored * kRelRows * 8 + s->r_gap_words * 4 + s->n_rslices * (64 * 4 + 16);
-    else if (s->cols16 && s->spmv_format != PFEM_SPMV_INT32)
+    const SpmvForm f = spmv_form(s);
+    const int64_t planes = f.codes ? 1 : f.rows_per_lane();                // 8 B of codes per lane entry (all its rows) instead of 8 B per slot
+    if (f.layout == SpmvLayout::Group3)
+        b += s->g_stored * planes * 8 + s->g_gap_words * 4 + s->n_gslices * (64 * 4 + 16) + (s->n_groups + 1) * 4;
+    else if (f.rel())
+        b += s->r_stored * planes * 8 + s->r_gap_words * 4 + s->n_rslices * (64 * 4 + 16);
+    else if (f.layout != SpmvLayout::Row32)
         b += s->stored * 8 + s->gap_words * 4 + s->n_slices * (64 * 4 + 16);
     else
         b += s->stored * 12 + s->n_slices * 8 + s->n_loc * 4;
@@ -3110,7 +3115,7 @@ extern "C" int pfem_solver_get_spmv_value_dictionary(pfem_solver *s, int *entrie
 {
     if (!s || !entries) return PFEM_ERR_ARG;
     if (!s->have_pattern) return PFEM_ERR_STATE;
-    *entries = (s->vd_ok && s->vd_current) ? s->vd_n : 0;
+    *entries = (s->vd_ok && s->vd_current) ? s->vd_n : 0;          // (as it always was: without a look at the form, see spmv_form)
     return PFEM_OK;
 }
 
@@ -4164,25 +4169,21 @@ int scalar_allreduce(pfem_solver *s, int at, int n)
     return s->comm->allreduce(s->d_sbuf.p + at, n, s->stream);
 }
 
-// which SpMV form the next launch uses (key of the slice lists and of the captured graph)
-inline int spmv_form(const pfem_solver *s)
-{
-    return s->use_grouped() ? 3 : (s->use_rel() ? (s->rel_gap32 ? 5 : (s->rel_dict ? 6 : 4)) : ((s->cols16 && s->spmv_format != PFEM_SPMV_INT32) ? 2 : 1));
-}
-
-// ... and what a captured launch of it depends on besides (value dictionary in use, its size)
+// what a captured SpMV launch depends on: the kernel of the form in effect, the value dictionary's size, the code arrays
 inline uint64_t spmv_key(const pfem_solver *s)
 {
-    return static_cast<uint64_t>(spmv_form(s)) | ((s->vd_ok && s->vd_current) ? (static_cast<uint64_t>(s->vd_n + 1) << 8) : 0) | (s->dinv_codes ? 1ull << 7 : 0) |
+    const SpmvForm f = spmv_form(s);
+    return f.kernel_id() | (f.codes ? (static_cast<uint64_t>(s->vd_n + 1) << 8) : 0) | (s->dinv_codes ? 1ull << 7 : 0) |
            (static_cast<uint64_t>(reinterpret_cast<uintptr_t>(s->d_vcodes.p)) << 24);
 }
 
 // boundary / interior slice lists of the SpMV form in use
 int build_slice_lists(pfem_solver *s)
 {
-    const int fmt = spmv_form(s);
+    const SpmvForm f = spmv_form(s);
+    const int fmt = static_cast<int>(f.layout);          // (the lists depend on how the form cuts the rows into slices, no more)
     if (s->slices_fmt == fmt) return PFEM_OK;
-    const int64_t ns = fmt == 3 ? s->n_gslices : (fmt >= 4 ? s->n_rslices : s->n_slices);
+    const int64_t ns = f.slices(s);
     std::vector<char> flag(static_cast<size_t>(std::max<int64_t>(ns, 1)), 0);
     if (s->n_sh > 0 && ns > 0) {
         DevBuf<char> d_flag;
@@ -4191,8 +4192,8 @@ int build_slice_lists(pfem_solver *s)
         PFEM_HIP(hipMemsetAsync(d_flag.p, 0, static_cast<size_t>(ns), s->stream));
         const int32_t *rg = nullptr;
         int shift = 6;                                  // 64 rows per slice
-        if (fmt >= 4) shift = 8;                        // 64 groups of kRelRows = 4 consecutive rows
-        if (fmt == 3) {                                 // 64 groups of up to 3 rows: look the group up
+        if (f.rel()) shift = 8;                         // 64 groups of kRelRows = 4 consecutive rows
+        if (f.layout == SpmvLayout::Group3) {           // 64 groups of up to 3 rows: look the group up
             PFEM_TRY(d_row_group.alloc(static_cast<size_t>(s->n_loc)));
             hipLaunchKernelGGL(k_row_group_index, dim3(grid_for(s->n_groups)), dim3(kBlock), 0, s->stream,
                                static_cast<const int32_t *>(s->d_group_row0.p), s->n_groups, d_row_group.p);
@@ -4657,7 +4658,7 @@ int run_pcg(pfem_solver *s)
         const bool sampled_ok = !s->profile_spmv || s->profile_every % kGraphIters == 0;
         if (graph_env && !multi && !bpc && n > 0 && (n <= kGraphMaxRows || graph_env > 1) && s->stream != nullptr && sampled_ok) {
             std::vector<uint64_t> key = iteration_key;
-            key.insert(key.end(), {static_cast<uint64_t>(gs), static_cast<uint64_t>(spmv_form(s))});
+            key.insert(key.end(), {static_cast<uint64_t>(gs), spmv_form(s).kernel_id()});
             PFEM_TRY(s->cg_graph.ensure(s->stream, std::move(key), {}, [&](int variant) {
                 for (int k = 0; k < kGraphIters; ++k) {
                     if (!(variant == 1 && k == 0)) launch_spmv<true>(s, s->d_p.p, s->d_w.p, n, part_pw, ctl);
