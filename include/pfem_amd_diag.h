@@ -140,6 +140,19 @@ int pfem_solver_amg_column_codes(pfem_solver *s, int max_levels, int *n_levels, 
  * level's column codes and offset table (PFEM_ERR_STATE when it has none).  The two agree on every slot of every row < n; the
  * lanes past n of the last slice read 0 either way                                                                          */
 int pfem_solver_amg_level_columns(pfem_solver *s, int level, int decoded, int64_t max_cols, int32_t *cols, int64_t *stored);
+/* coarse level `level` (>= 1) of the last hierarchy as plain CSR with the padding slots dropped and the columns of a row ascending,
+ * as pfem_get_csr hands out the matrix itself: rowptr [*n + 1], cols and vals [*nnz].  A slot belongs to its row iff its index
+ * within the row is below the row's stored length, whatever it holds.  rowptr = cols = vals = NULL: the sizes alone (call twice).
+ * One rank after a gamg solve; PFEM_ERR_STATE without a hierarchy or with one across the ranks.  Built on the host from the
+ * level's arrays copied back: what the tests compare with an independently formed P^T A P.                                    */
+int pfem_solver_amg_level_csr(pfem_solver *s, int level, int64_t *rowptr, int32_t *cols, double *vals, int64_t *n, int64_t *nnz);
+/* z = M^-1 r: ONE application of the multigrid cycle of the last gamg solve, with the numeric set-up (coarse operators, inverse
+ * diagonals, bounds, dense bottom) that solve left -- the call its CG makes for z_0.  r and z: host arrays of n_local doubles in
+ * the caller's dof order (the internal renumbering does not show).  Synchronises the stream.  Leaves the cycle's graph and every
+ * state the next solve reads as they are: solve, apply, solve gives the bits of solve, solve.  One rank after a gamg solve;
+ * PFEM_ERR_STATE without a hierarchy or with one across the ranks.  What the tests compare, vector by vector, with the oracle's
+ * cycle evaluated in extended precision.                                                                                       */
+int pfem_solver_amg_apply(pfem_solver *s, const double *r, double *z);
 
 /* Per-element Ke/Fe of the uploaded mesh as computed by the DEVICE kernel (parity
  * inspection): K_out[e*nsize*nsize + i + nsize*j], F_out[e*nsize + i].           */

@@ -133,6 +133,8 @@ SIGNATURES = {
     "pfem_solver_amg_level_values": [_P, _I, _L, _P, _P],
     "pfem_solver_amg_column_codes": [_P, _I, _P, _P, _P],
     "pfem_solver_amg_level_columns": [_P, _I, _I, _L, _P, _P],
+    "pfem_solver_amg_level_csr": [_P, _I, _P, _P, _P, _P, _P],
+    "pfem_solver_amg_apply": [_P, _P, _P],
     "pfem_eval_elems": [_P, _P, _P, _P, _P],
     "pfem_rhs_add_values": [_P, _L, _P, _P],
     "pfem_post_elements": [_P] * 6,

@@ -5506,6 +5506,86 @@ extern "C" int pfem_solver_amg_level_columns(pfem_solver *s, int level, int deco
     return PFEM_OK;
 }
 
+// coarse level `level` (>= 1) of the last one-rank hierarchy as plain CSR, rows and ascending columns, without the padding of the
+// wave-sliced storage: entry k of row i sits in slot slice_off[i / 64] + 64 k + i % 64 and belongs to the row iff k < rowlen[i]
+// (a padding slot holds the row's own number and a zero, which a real diagonal entry could hold too).  Built on the host from the
+// level's arrays copied back.  rowptr / cols / vals null: the sizes alone.
+extern "C" int pfem_solver_amg_level_csr(pfem_solver *s, int level, int64_t *rowptr, int32_t *cols, double *vals, int64_t *n, int64_t *nnz)
+{
+    if (!s || !n || !nnz || level < 1 || ((rowptr || cols || vals) && !(rowptr && cols && vals))) return PFEM_ERR_ARG;
+    if (!s->amg || !s->amg->symbolic_ok || s->amg->coupled || s->amg->rep || s->nranks > 1) return PFEM_ERR_STATE;
+    const Amg &M = *s->amg;
+    if (static_cast<size_t>(level) >= M.lev.size()) return PFEM_ERR_STATE;
+    const AmgLevel &L = *M.lev[static_cast<size_t>(level)];
+    if (!L.slice_off.p || !L.rowlen.p || !L.cols.p || !L.vals.p || L.n < 1) return PFEM_ERR_STATE;
+    PFEM_TRY(use_device(s));
+    PFEM_HIP(hipStreamSynchronize(s->stream));
+    const int64_t rows = L.n, n_slices = (rows + 63) / 64;
+    std::vector<int32_t> len(static_cast<size_t>(rows));
+    PFEM_HIP(hipMemcpy(len.data(), L.rowlen.p, sizeof(int32_t) * len.size(), hipMemcpyDeviceToHost));
+    int64_t total = 0;
+    for (int32_t v : len) {
+        if (v < 0) return PFEM_ERR_STATE;
+        total += v;
+    }
+    *n = rows;
+    *nnz = total;
+    if (!rowptr) return PFEM_OK;
+    std::vector<int64_t> off(static_cast<size_t>(n_slices) + 1);
+    PFEM_HIP(hipMemcpy(off.data(), L.slice_off.p, sizeof(int64_t) * off.size(), hipMemcpyDeviceToHost));
+    std::vector<int32_t> c(static_cast<size_t>(L.stored));
+    std::vector<double> v(static_cast<size_t>(L.stored));
+    PFEM_HIP(hipMemcpy(c.data(), L.cols.p, sizeof(int32_t) * c.size(), hipMemcpyDeviceToHost));
+    PFEM_HIP(hipMemcpy(v.data(), L.vals.p, sizeof(double) * v.size(), hipMemcpyDeviceToHost));
+    std::vector<std::pair<int32_t, double>> row;
+    rowptr[0] = 0;
+    for (int64_t i = 0; i < rows; ++i) {
+        const int64_t base = off[static_cast<size_t>(i >> 6)] + (i & 63);
+        row.clear();
+        for (int k = 0; k < len[static_cast<size_t>(i)]; ++k) {
+            const int64_t slot = base + 64LL * k;
+            if (slot < 0 || slot >= L.stored) return PFEM_ERR_STATE;
+            row.emplace_back(c[static_cast<size_t>(slot)], v[static_cast<size_t>(slot)]);
+        }
+        std::stable_sort(row.begin(), row.end(), [](const std::pair<int32_t, double> &a, const std::pair<int32_t, double> &b) { return a.first < b.first; });
+        int64_t o = rowptr[i];
+        for (const auto &e : row) { cols[o] = e.first; vals[o] = e.second; ++o; }
+        rowptr[i + 1] = o;
+    }
+    return PFEM_OK;
+}
+
+// z = M^-1 r: one application of the cycle of the last gamg solve on one rank, with the numeric set-up that solve left -- the call
+// its CG makes for z_0 (plain launches, no control block, every level-0 step by the stand-alone kernels).  r and z in the caller's
+// dof order.  The right-hand side goes through a vector of its own and the cycle writes the levels' work vectors only, which every
+// solve fills before it reads them: the cycle's graph and everything the next solve reads stay as they are.
+extern "C" int pfem_solver_amg_apply(pfem_solver *s, const double *r, double *z)
+{
+    if (!s || !r || !z) return PFEM_ERR_ARG;
+    if (!s->amg || !s->amg->symbolic_ok || s->amg->coupled || s->amg->rep || s->nranks > 1 || !s->have_pattern) return PFEM_ERR_STATE;
+    Amg &M = *s->amg;
+    if (M.lev.empty() || !M.lev[0]->x || !M.lev[0]->lam.p || !M.lev[0]->dinv.p) return PFEM_ERR_STATE;
+    PFEM_TRY(use_device(s));
+    const int64_t n = s->n_loc;
+    std::vector<double> ri;
+    if (s->reordered) {                     // the caller's numbering -> the internal one
+        ri.assign(r, r + n);
+        for (int64_t i = 0; i < s->n_owned; ++i) ri[static_cast<size_t>(s->h_perm[static_cast<size_t>(i)])] = r[i];
+    }
+    DevBuf<double> d_in;
+    PFEM_TRY(d_in.alloc(static_cast<size_t>(std::max<int64_t>(n, 1))));
+    PFEM_HIP(hipMemcpyAsync(d_in.p, s->reordered ? ri.data() : r, sizeof(double) * static_cast<size_t>(n), hipMemcpyHostToDevice, s->stream));
+    mark_group_vals(s);
+    PFEM_TRY(refresh_group_vals(s));
+    const int tail_build = M.tail_build;
+    const double *d_z = amg_apply(s, M, d_in.p, nullptr);
+    M.tail_build = tail_build;              // (what the last SOLVE's cycle launched, pfem_solver_amg_tail_from)
+    if (!d_z) return PFEM_ERR_HIP;
+    PFEM_TRY(check_kernel("amg_apply"));
+    PFEM_TRY(download_external(s, d_z, z, n));         // (synchronises the stream)
+    return PFEM_OK;
+}
+
 // what the last gamg solve ran: 1 = V, 2 = W, and the last level whose problem got two visits
 extern "C" int pfem_solver_amg_cycle(pfem_solver *s, int *cycle, int *last_level_visited_twice)
 {

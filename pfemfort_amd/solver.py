@@ -344,6 +344,26 @@ class PetscSolver:
         L.check(L.lib().pfem_solver_amg_level_columns(self._h, level, int(bool(decoded)), n.value, _p(a), C.byref(n)), "pfem_solver_amg_level_columns")
         return a
 
+    def amgLevelCSR(self, level):
+        """Coarse ``level`` (>= 1) of the last hierarchy as ``(rowptr, cols, vals)``: plain CSR without the storage's padding, the
+        columns of a row ascending (one rank)."""
+        n, nnz = C.c_int64(0), C.c_int64(0)
+        L.check(L.lib().pfem_solver_amg_level_csr(self._h, level, None, None, None, C.byref(n), C.byref(nnz)), "pfem_solver_amg_level_csr")
+        rowptr = np.empty(n.value + 1, np.int64)
+        cols = np.empty(nnz.value, np.int32)
+        vals = np.empty(nnz.value, np.float64)
+        L.check(L.lib().pfem_solver_amg_level_csr(self._h, level, _p(rowptr), _p(cols), _p(vals), C.byref(n), C.byref(nnz)), "pfem_solver_amg_level_csr")
+        return rowptr, cols, vals
+
+    def amgApply(self, r):
+        """``z = M^-1 r``: one application of the last gamg solve's cycle with the set-up that solve left (one rank; ``r`` and ``z`` in
+        the caller's dof order).  Changes nothing the next solve reads."""
+        r = _f64(r)
+        assert r.ndim == 1 and r.size == self.matrixInfo()["n_local"]
+        z = np.empty_like(r)
+        L.check(L.lib().pfem_solver_amg_apply(self._h, _p(r), _p(z)), "pfem_solver_amg_apply")
+        return z
+
     def amgAggregates(self, level, n_rows):
         """Coarse dof of every dof of ``level`` (``n_rows`` = amgInfo()["rows"][level])."""
         a = np.empty(n_rows, np.int32)

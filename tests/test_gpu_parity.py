@@ -964,7 +964,10 @@ def _transfers(s, info=None):
 
 def _gamg_vs_oracle(s, rtol=1e-10):
     """Solve with gamg on the device, then restate the SAME solve on the CPU (oracle.pcg_amg) with the aggregates the
-    device formed: iteration count, residual history and solution."""
+    device formed: iteration count, residual history and solution.  A whole solve only: CG reaches the same solution with any
+    symmetric positive definite preconditioner and the history entries are norms, so a slightly wrong level, bound or cycle step
+    passes here.  The pieces -- every coarse operator, every bound, one application z = M^-1 r vector by vector -- are tested in
+    test_gpu_amg_pieces.py (pfem_solver_amg_level_csr, pfem_solver_amg_apply against tests/amg_reference.py)."""
     s.setTolerances(rtol=rtol, maxits=10000)
     s.setPreconditioner("gamg")
     its, reason, rn = s.factoriseAndSolve()
