@@ -42,6 +42,18 @@ inline bool amg_in_effect(const pfem_solver *s)
 {
     return s->pc == PFEM_PC_GAMG;
 }
+// PFEM_AMG_VERBOSE: the symbolic phase says on stderr where its time goes and why a level leaves the brick path (read at every call)
+inline bool amg_verbose()
+{
+    return std::getenv("PFEM_AMG_VERBOSE") != nullptr;
+}
+// PFEM_AMG_BRICK_SORT: brick and node-brick levels take the sorted route to their maps (A/B; the bricks also take it for rows too
+// long for 16-bit counters).  Read once per process.
+inline bool amg_brick_sort()
+{
+    static const bool v = std::getenv("PFEM_AMG_BRICK_SORT") != nullptr;
+    return v;
+}
 
 // level 0 = the rank's OWNED block of its matrix: the owned rows come first in the local numbering, so the block is the
 // first n_owned rows with the columns below n_owned (the kernels that walk rows take the column limit)
@@ -97,6 +109,21 @@ inline void amg_spmv(pfem_solver *s, const Amg &M, AmgLevel &L, const double *x,
                            static_cast<int64_t>(0), static_cast<double *>(nullptr), static_cast<const CgCtl *>(nullptr), SliceSel{nullptr, 0});
     }
 }
+
+// PFEM_AMG_VERBOSE: where the symbolic phase spends its time -- the time since the last mark, after a synchronisation
+struct AmgPhaseClock {
+    hipStream_t stream;
+    bool verbose;
+    std::chrono::steady_clock::time_point tick;
+    void operator()(int lvl, const char *what)
+    {
+        if (!verbose) return;
+        (void)hipStreamSynchronize(stream);
+        const auto now = std::chrono::steady_clock::now();
+        std::fprintf(stderr, "  gamg symbolic level %d %-28s %9.2f ms\n", lvl, what, std::chrono::duration<double, std::milli>(now - tick).count());
+        tick = now;
+    }
+};
 
 // small host vectors summed over the ranks (symbolic phase of a coupled hierarchy: level sizes, verdicts); collective
 int amg_allreduce_host(pfem_solver *s, double *v, int n)
@@ -303,7 +330,7 @@ int lattice_positions_global(pfem_solver *s, AmgLevel &L0, bool *is_lattice, boo
         double bad = unplaced ? 1.0 : 0.0;
         PFEM_TRY(amg_allreduce_host(s, &bad, 1));
         if (bad > 0.0) {
-            if (std::getenv("PFEM_AMG_VERBOSE")) std::fprintf(stderr, "  gamg symbolic: some rank owns dofs that none of its own mesh nodes carries: no split bricks\n");
+            if (amg_verbose()) std::fprintf(stderr, "  gamg symbolic: some rank owns dofs that none of its own mesh nodes carries: no split bricks\n");
             return PFEM_OK;
         }
     }
@@ -322,7 +349,7 @@ int lattice_positions_global(pfem_solver *s, AmgLevel &L0, bool *is_lattice, boo
             gmax[d] = std::max(gmax[d], static_cast<int>(b[3 + d]));
         }
         if (vol != b[6] && !split) {                   // a rank's owned dofs do not fill a box of the lattice
-            if (std::getenv("PFEM_AMG_VERBOSE"))
+            if (amg_verbose())
                 std::fprintf(stderr, "  gamg symbolic: rank %d owns %g %s in a box of %g positions: no bricks across the ranks\n", q, b[6], nodes ? "nodes" : "dofs", vol);
             return PFEM_OK;
         }
@@ -425,6 +452,15 @@ struct AmgGraph {
     DevBuf<int64_t> ptr;
     DevBuf<int32_t> col;
     DevBuf<double> w, diag;
+    int reserve(int64_t rows, int64_t entries)
+    {
+        n = rows;
+        nnz = entries;
+        PFEM_TRY(ptr.reserve(static_cast<size_t>(n) + 1));
+        PFEM_TRY(col.reserve(static_cast<size_t>(std::max<int64_t>(nnz, 1))));
+        PFEM_TRY(w.reserve(static_cast<size_t>(std::max<int64_t>(nnz, 1))));
+        return diag.reserve(static_cast<size_t>(std::max<int64_t>(n, 1)));
+    }
 };
 struct AmgWork {
     DevBuf<char> temp;
@@ -446,11 +482,17 @@ int amg_exclusive_sum(pfem_solver *s, DevBuf<char> &temp, const T *in, T *out, i
     return PFEM_OK;
 }
 
-inline int amg_key_bits(int64_t n)
+// (key, value) pairs sorted by bits [0, end_bit) of the key; the stream is synchronised before temp is regrown: a pooled block
+// may still be read
+template <class K, class V>
+int amg_sort_pairs(pfem_solver *s, DevBuf<char> &temp, const K *keys_in, K *keys_out, const V *vals_in, V *vals_out, int64_t count, int end_bit)
 {
-    int bits = 1;
-    while ((1LL << bits) < std::max<int64_t>(n, 2)) ++bits;
-    return std::min(64, 32 + bits);
+    size_t tb = 0;
+    const int ni = static_cast<int>(count);
+    PFEM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys_in, keys_out, vals_in, vals_out, ni, 0, end_bit, s->stream));
+    if (tb > temp.n) { PFEM_HIP(hipStreamSynchronize(s->stream)); PFEM_TRY(temp.alloc(tb)); }
+    PFEM_HIP(hipcub::DeviceRadixSort::SortPairs(temp.p, tb, keys_in, keys_out, vals_in, vals_out, ni, 0, end_bit, s->stream));
+    return PFEM_OK;
 }
 
 // Runs of equal keys of a SORTED array: unique keys (ascending) and the start of every run (m + 1 entries).  Flags + one
@@ -483,22 +525,28 @@ int amg_unique_runs(pfem_solver *s, AmgWork &W, const uint64_t *skeys, int64_t c
     return PFEM_OK;
 }
 
+// The padding entries collapse into one run of the all-ones sentinel key at the end of the unique keys: dropped (its slots are
+// never read).  (On the solver's stream: the scatter that wrote ukeys is still in flight, and no hipFree synchronises for us.)
+int amg_drop_sentinel_run(pfem_solver *s, const uint64_t *ukeys, int64_t *m)
+{
+    if (*m < 1) return PFEM_OK;
+    uint64_t last = 0;
+    PFEM_HIP(hipMemcpyAsync(&last, ukeys + (*m - 1), sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
+    PFEM_HIP(hipStreamSynchronize(s->stream));
+    if (last == ~0ull) --*m;
+    return PFEM_OK;
+}
+
 // (key, double) pairs -> sorted, reduced by key: unique keys and sums; the all-ones sentinel key, if any, is dropped
-int amg_sort_reduce(pfem_solver *s, AmgWork &W, DevBuf<uint64_t> &keys, DevBuf<double> &vals, int64_t count, int end_bit,
+int amg_sort_reduce(pfem_solver *s, AmgWork &W, DevBuf<uint64_t> &keys, DevBuf<double> &vals, int64_t count,
                     DevBuf<uint64_t> &ukeys, DevBuf<double> &sums, int64_t *n_unique)
 {
     if (count > INT_MAX) { set_last_error("gamg: more than 2^31-1 graph entries on one device"); return PFEM_ERR_ARG; }
-    DevBuf<char> &temp = W.temp;
     DevBuf<uint64_t> &skeys = W.skeys;
     DevBuf<double> &svals = W.svals;
     PFEM_TRY(skeys.reserve(static_cast<size_t>(count)));
     PFEM_TRY(svals.reserve(static_cast<size_t>(count)));
-    const int ni = static_cast<int>(count);
-    size_t tb = 0;
-    PFEM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys.p, skeys.p, vals.p, svals.p, ni, 0, 64, s->stream));
-    if (tb > temp.n) { PFEM_HIP(hipStreamSynchronize(s->stream)); PFEM_TRY(temp.alloc(tb)); }
-    PFEM_HIP(hipcub::DeviceRadixSort::SortPairs(temp.p, tb, keys.p, skeys.p, vals.p, svals.p, ni, 0, 64, s->stream));
-    (void)end_bit;
+    PFEM_TRY(amg_sort_pairs(s, W.temp, keys.p, skeys.p, vals.p, svals.p, count, 64));
     DevBuf<int64_t> &start = W.start;
     int64_t m = 0;
     PFEM_TRY(amg_unique_runs(s, W, skeys.p, count, ukeys, start, &m, false));
@@ -507,23 +555,27 @@ int amg_sort_reduce(pfem_solver *s, AmgWork &W, DevBuf<uint64_t> &keys, DevBuf<d
         hipLaunchKernelGGL(k_amg_run_sums, dim3(grid_for(m)), dim3(kBlock), 0, s->stream, m, static_cast<const int64_t *>(start.p),
                            static_cast<const double *>(svals.p), static_cast<const uint64_t *>(ukeys.p), sums.p);
         PFEM_TRY(check_kernel("k_amg_run_sums"));
-        uint64_t last = 0;
-        PFEM_HIP(hipMemcpyAsync(&last, ukeys.p + (m - 1), sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
-        PFEM_HIP(hipStreamSynchronize(s->stream));
-        if (last == ~0ull) --m;
+        PFEM_TRY(amg_drop_sentinel_run(s, ukeys.p, &m));
     }
     *n_unique = m;
     return PFEM_OK;
 }
 
+// The sorted route to a coarse pattern.  The caller has emitted `count` (key, slot) pairs into W.keys / W.slots; here they are
+// sorted (the slots in key order: src_slot, `count` of them) and the runs of equal keys found: ukeys, as long as the coarse
+// pattern has entries, and the start of every run in src_ptr.  *nnz_c = the runs.  A caller whose pairs cover padding slots
+// drops the sentinel's run (amg_drop_sentinel_run: a word back to the host, which the other callers do not pay for); the
+// pattern's storage is the caller's too (amg_store_pattern, or the block split of a rigid-body level).
+int amg_pattern_from_keys(pfem_solver *s, AmgWork &W, int64_t count, int32_t *src_slot, DevBuf<int64_t> &src_ptr, DevBuf<uint64_t> &ukeys, int64_t *nnz_c)
+{
+    PFEM_TRY(W.skeys.reserve(static_cast<size_t>(count)));
+    PFEM_TRY(amg_sort_pairs(s, W.temp, W.keys.p, W.skeys.p, W.slots.p, src_slot, count, 64));
+    return amg_unique_runs(s, W, W.skeys.p, count, ukeys, src_ptr, nnz_c);
+}
+
 int amg_graph_from_unique(pfem_solver *s, DevBuf<uint64_t> &ukeys, DevBuf<double> &sums, int64_t m, int64_t n, int squared, AmgGraph &G)
 {
-    G.n = n;
-    G.nnz = m;
-    PFEM_TRY(G.ptr.reserve(static_cast<size_t>(n) + 1));
-    PFEM_TRY(G.col.reserve(static_cast<size_t>(std::max<int64_t>(m, 1))));
-    PFEM_TRY(G.w.reserve(static_cast<size_t>(std::max<int64_t>(m, 1))));
-    PFEM_TRY(G.diag.reserve(static_cast<size_t>(std::max<int64_t>(n, 1))));
+    PFEM_TRY(G.reserve(n, m));
     PFEM_HIP(hipMemsetAsync(G.diag.p, 0, sizeof(double) * std::max<int64_t>(n, 1), s->stream));
     hipLaunchKernelGGL(k_row_bounds, dim3(grid_for(std::max<int64_t>(m, n + 1))), dim3(kBlock), 0, s->stream, ukeys.p, m, n, G.ptr.p);
     PFEM_TRY(check_kernel("k_row_bounds (gamg graph)"));
@@ -535,30 +587,23 @@ int amg_graph_from_unique(pfem_solver *s, DevBuf<uint64_t> &ukeys, DevBuf<double
     return PFEM_OK;
 }
 
-// one pass of pairwise matching on G: agg_step[node] = aggregate (pairs and singles), *na = their number
-int amg_match(pfem_solver *s, AmgWork &W, const AmgGraph &G, const int32_t *hint, DevBuf<int32_t> &agg_step, int64_t *na)
+// a pairing pass over n nodes, either kind.  Begins: W.match = nobody matched yet, W.cand for the proposals.  Ends: the roots of
+// the pairs and singles in W.match are numbered -- agg_step[node] = aggregate, *na = their number.
+int amg_match_begin(pfem_solver *s, AmgWork &W, int64_t n)
 {
-    const int64_t n = G.n;
-    DevBuf<char> &temp = W.temp;
-    DevBuf<int32_t> &match = W.match, &cand = W.cand, &is_root = W.is_root, &rank = W.mrank;
-    PFEM_TRY(match.reserve(static_cast<size_t>(n)));
-    PFEM_TRY(cand.reserve(static_cast<size_t>(n)));
-    PFEM_TRY(is_root.reserve(static_cast<size_t>(n) + 1));
-    PFEM_TRY(rank.reserve(static_cast<size_t>(n) + 1));
-    PFEM_HIP(hipMemsetAsync(match.p, 0xff, sizeof(int32_t) * n, s->stream));
-    // small graphs are dense (every aggregate touches most others): many nodes propose to the same neighbour and few
-    // proposals are mutual per round, so they get more rounds (they cost nothing)
-    const int rounds = n < 8192 ? 8 * kAmgMatchRounds : kAmgMatchRounds;
-    for (int r = 0; r < rounds; ++r) {
-        hipLaunchKernelGGL(k_amg_match_pick, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, n, static_cast<const int64_t *>(G.ptr.p),
-                           static_cast<const int32_t *>(G.col.p), static_cast<const double *>(G.w.p), static_cast<const double *>(G.diag.p),
-                           hint, static_cast<const int32_t *>(match.p), cand.p);
-        hipLaunchKernelGGL(k_amg_match_commit, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, n, static_cast<const int32_t *>(cand.p), match.p);
-    }
-    PFEM_TRY(check_kernel("k_amg_match"));
+    PFEM_TRY(W.match.reserve(static_cast<size_t>(n)));
+    PFEM_TRY(W.cand.reserve(static_cast<size_t>(n)));
+    PFEM_TRY(W.is_root.reserve(static_cast<size_t>(n) + 1));
+    PFEM_TRY(W.mrank.reserve(static_cast<size_t>(n) + 1));
+    PFEM_HIP(hipMemsetAsync(W.match.p, 0xff, sizeof(int32_t) * n, s->stream));
+    return PFEM_OK;
+}
+int amg_match_end(pfem_solver *s, AmgWork &W, int64_t n, DevBuf<int32_t> &agg_step, int64_t *na)
+{
+    DevBuf<int32_t> &match = W.match, &is_root = W.is_root, &rank = W.mrank;
     PFEM_HIP(hipMemsetAsync(is_root.p + n, 0, sizeof(int32_t), s->stream));
     hipLaunchKernelGGL(k_amg_match_finish, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, n, match.p, is_root.p);
-    PFEM_TRY(amg_exclusive_sum(s, temp, is_root.p, rank.p, n + 1));
+    PFEM_TRY(amg_exclusive_sum(s, W.temp, is_root.p, rank.p, n + 1));
     PFEM_TRY(agg_step.reserve(static_cast<size_t>(n)));
     hipLaunchKernelGGL(k_amg_agg_ids, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, n, static_cast<const int32_t *>(match.p),
                        static_cast<const int32_t *>(rank.p), agg_step.p);
@@ -570,19 +615,33 @@ int amg_match(pfem_solver *s, AmgWork &W, const AmgGraph &G, const int32_t *hint
     return PFEM_OK;
 }
 
+// one pass of pairwise matching on G: agg_step[node] = aggregate (pairs and singles), *na = their number
+int amg_match(pfem_solver *s, AmgWork &W, const AmgGraph &G, const int32_t *hint, DevBuf<int32_t> &agg_step, int64_t *na)
+{
+    const int64_t n = G.n;
+    DevBuf<int32_t> &match = W.match, &cand = W.cand;
+    PFEM_TRY(amg_match_begin(s, W, n));
+    // small graphs are dense (every aggregate touches most others): many nodes propose to the same neighbour and few
+    // proposals are mutual per round, so they get more rounds (they cost nothing)
+    const int rounds = n < 8192 ? 8 * kAmgMatchRounds : kAmgMatchRounds;
+    for (int r = 0; r < rounds; ++r) {
+        hipLaunchKernelGGL(k_amg_match_pick, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, n, static_cast<const int64_t *>(G.ptr.p),
+                           static_cast<const int32_t *>(G.col.p), static_cast<const double *>(G.w.p), static_cast<const double *>(G.diag.p),
+                           hint, static_cast<const int32_t *>(match.p), cand.p);
+        hipLaunchKernelGGL(k_amg_match_commit, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, n, static_cast<const int32_t *>(cand.p), match.p);
+    }
+    PFEM_TRY(check_kernel("k_amg_match"));
+    return amg_match_end(s, W, n, agg_step, na);
+}
+
 // one pass of pairing along one axis of the lattice (hint = positions); same outputs as amg_match, plus the roots in
 // W.match for the positions of the aggregates
 int amg_match_lattice(pfem_solver *s, AmgWork &W, const AmgGraph &G, const int32_t *pos, int axis, bool absorb, DevBuf<int32_t> &agg_step, int64_t *na)
 {
     const int64_t n = G.n;
     const int shift = 10 * axis;
-    DevBuf<char> &temp = W.temp;
-    DevBuf<int32_t> &match = W.match, &cand = W.cand, &is_root = W.is_root, &rank = W.mrank;
-    PFEM_TRY(match.reserve(static_cast<size_t>(n)));
-    PFEM_TRY(cand.reserve(static_cast<size_t>(n)));
-    PFEM_TRY(is_root.reserve(static_cast<size_t>(n) + 1));
-    PFEM_TRY(rank.reserve(static_cast<size_t>(n) + 1));
-    PFEM_HIP(hipMemsetAsync(match.p, 0xff, sizeof(int32_t) * n, s->stream));
+    DevBuf<int32_t> &match = W.match, &cand = W.cand;
+    PFEM_TRY(amg_match_begin(s, W, n));
     const int64_t *gptr = G.ptr.p;
     const int32_t *gcol = G.col.p;
     const double *gw = G.w.p, *gd = G.diag.p;
@@ -597,18 +656,7 @@ int amg_match_lattice(pfem_solver *s, AmgWork &W, const AmgGraph &G, const int32
         hipLaunchKernelGGL(k_amg_lat_join, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, n, static_cast<const int32_t *>(cand.p), match.p);
     }
     PFEM_TRY(check_kernel("k_amg_lat_*"));
-    PFEM_HIP(hipMemsetAsync(is_root.p + n, 0, sizeof(int32_t), s->stream));
-    hipLaunchKernelGGL(k_amg_match_finish, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, n, match.p, is_root.p);
-    PFEM_TRY(amg_exclusive_sum(s, temp, is_root.p, rank.p, n + 1));
-    PFEM_TRY(agg_step.reserve(static_cast<size_t>(n)));
-    hipLaunchKernelGGL(k_amg_agg_ids, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, n, static_cast<const int32_t *>(match.p),
-                       static_cast<const int32_t *>(rank.p), agg_step.p);
-    PFEM_TRY(check_kernel("k_amg_agg_ids"));
-    int32_t total = 0;
-    PFEM_HIP(hipMemcpyAsync(&total, rank.p + n, sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
-    PFEM_HIP(hipStreamSynchronize(s->stream));
-    *na = total;
-    return PFEM_OK;
+    return amg_match_end(s, W, n, agg_step, na);
 }
 
 // wave-sliced storage of a coarse matrix from its sorted unique (row << 32 | col) keys
@@ -638,6 +686,57 @@ int amg_sell_from_keys(pfem_solver *s, AmgWork &W, const uint64_t *ukeys, int64_
                        C.n_slices, static_cast<const int64_t *>(C.slice_off.p), C.cols.p);
     PFEM_TRY(check_kernel("k_fill_sell (gamg)"));
     PFEM_HIP(hipMemsetAsync(C.vals.p, 0, sizeof(double) * std::max<int64_t>(stored, 1), s->stream));
+    return PFEM_OK;
+}
+
+// the coarse pattern's wave-sliced storage (C) and, per coarse entry, its slot there: where the numeric product puts its sum
+int amg_store_pattern(pfem_solver *s, AmgWork &W, const uint64_t *ukeys, int64_t nnz_c, AmgLevel &C, DevBuf<int64_t> &dst_slot)
+{
+    PFEM_TRY(amg_sell_from_keys(s, W, ukeys, nnz_c, C));
+    PFEM_TRY(dst_slot.alloc(static_cast<size_t>(std::max<int64_t>(nnz_c, 1))));
+    hipLaunchKernelGGL(k_amg_dst_slots, dim3(grid_for(nnz_c)), dim3(kBlock), 0, s->stream, nnz_c, ukeys, static_cast<const int64_t *>(C.rowptr.p),
+                       static_cast<const int64_t *>(C.slice_off.p), dst_slot.p);
+    return check_kernel("k_amg_dst_slots");
+}
+
+// Members of every coarse dof (restriction as a gather), ascending: L.mem_ptr (n_coarse + 1) and L.mem_idx.  key[i] = the coarse
+// dof of member i, sorted by its bits below end_bit.  skip_empty: without members nothing is numbered or sorted.
+int amg_member_lists(pfem_solver *s, AmgWork &W, AmgLevel &L, const int32_t *key, int64_t n_members, int64_t n_coarse, int end_bit,
+                     bool skip_empty = false)
+{
+    DevBuf<int32_t> &cnt = W.cnt, &idx = W.idx, &skey = W.skey32;
+    PFEM_TRY(cnt.reserve(static_cast<size_t>(n_coarse) + 1));
+    PFEM_TRY(idx.reserve(static_cast<size_t>(std::max<int64_t>(n_members, 1))));
+    PFEM_TRY(skey.reserve(static_cast<size_t>(std::max<int64_t>(n_members, 1))));
+    PFEM_TRY(L.mem_ptr.alloc(static_cast<size_t>(n_coarse) + 1));
+    PFEM_TRY(L.mem_idx.alloc(static_cast<size_t>(std::max<int64_t>(n_members, 1))));
+    PFEM_HIP(hipMemsetAsync(cnt.p, 0, sizeof(int32_t) * (n_coarse + 1), s->stream));
+    hipLaunchKernelGGL(k_amg_count, dim3(grid_for(n_members)), dim3(kBlock), 0, s->stream, n_members, key, cnt.p);
+    PFEM_TRY(amg_exclusive_sum(s, W.temp, cnt.p, L.mem_ptr.p, n_coarse + 1));
+    if (skip_empty && n_members < 1) return PFEM_OK;
+    hipLaunchKernelGGL(k_amg_iota, dim3(grid_for(n_members)), dim3(kBlock), 0, s->stream, n_members, idx.p);
+    return amg_sort_pairs(s, W.temp, key, skey.p, static_cast<const int32_t *>(idx.p), L.mem_idx.p, n_members, end_bit);
+}
+
+// Counts and two scans instead of a sort (k_lat_codes_*, k_rbm_codes_*).  `count` launches the caller's count kernel, which
+// leaves per coarse row (n of them) its coarse entries in W.head and its fine entries in W.rank and raises *d_fail; the
+// exclusive sums of the two go to W.cnt and W.idx (what the caller's fill kernel reads) and the totals and the verdict come back.
+int amg_count_scans(pfem_solver *s, AmgWork &W, int64_t n, const std::function<void()> &count, const char *what, const int *d_fail,
+                    int32_t *n_entries, int32_t *n_pairs, int *fail)
+{
+    DevBuf<int32_t> &entries = W.head, &pairs = W.rank, &entry_off = W.cnt, &pair_off = W.idx;
+    PFEM_TRY(entries.reserve(static_cast<size_t>(n) + 1));
+    PFEM_TRY(pairs.reserve(static_cast<size_t>(n) + 1));
+    PFEM_TRY(entry_off.reserve(static_cast<size_t>(n) + 1));
+    PFEM_TRY(pair_off.reserve(static_cast<size_t>(n) + 1));
+    count();
+    PFEM_TRY(check_kernel(what));
+    PFEM_TRY(amg_exclusive_sum(s, W.temp, entries.p, entry_off.p, n + 1));
+    PFEM_TRY(amg_exclusive_sum(s, W.temp, pairs.p, pair_off.p, n + 1));
+    PFEM_HIP(hipMemcpyAsync(n_entries, entry_off.p + n, sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+    PFEM_HIP(hipMemcpyAsync(n_pairs, pair_off.p + n, sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+    PFEM_HIP(hipMemcpyAsync(fail, d_fail, sizeof(int), hipMemcpyDeviceToHost, s->stream));
+    PFEM_HIP(hipStreamSynchronize(s->stream));
     return PFEM_OK;
 }
 
@@ -1018,25 +1117,17 @@ int amg_replicate(pfem_solver *s, Amg &M, AmgWork &W, AmgLevel &C, int64_t n_glo
     PFEM_TRY(check_kernel("k_amg_emit_global_entries"));
     PFEM_TRY(s->comm->allreduce(M.rep_buf.p, 2 * total, s->stream));
     // merged pattern + the maps of the merge (kept in C's Galerkin fields: C has no distributed level below it)
-    DevBuf<uint64_t> &keys = W.keys, &skeys = W.skeys;
+    DevBuf<uint64_t> &keys = W.keys;
     DevBuf<uint64_t> ukeys;
     DevBuf<int32_t> &pos = W.slots;
     PFEM_TRY(keys.reserve(static_cast<size_t>(total)));
-    PFEM_TRY(skeys.reserve(static_cast<size_t>(total)));
     PFEM_TRY(pos.reserve(static_cast<size_t>(total)));
     PFEM_TRY(C.src_slot.alloc(static_cast<size_t>(total)));
     hipLaunchKernelGGL(k_amg_keys_from_pairs, dim3(grid_for(total)), dim3(kBlock), 0, s->stream, total, static_cast<const double *>(M.rep_buf.p),
                        static_cast<const double *>(M.rep_buf.p + total), keys.p, pos.p);
     PFEM_TRY(check_kernel("k_amg_keys_from_pairs"));
-    {
-        size_t tb = 0;
-        const int ni = static_cast<int>(total);
-        PFEM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys.p, skeys.p, pos.p, C.src_slot.p, ni, 0, 64, s->stream));
-        if (tb > W.temp.n) { PFEM_HIP(hipStreamSynchronize(s->stream)); PFEM_TRY(W.temp.alloc(tb)); }
-        PFEM_HIP(hipcub::DeviceRadixSort::SortPairs(W.temp.p, tb, keys.p, skeys.p, pos.p, C.src_slot.p, ni, 0, 64, s->stream));
-    }
     int64_t nnz_rep = 0;
-    PFEM_TRY(amg_unique_runs(s, W, skeys.p, total, ukeys, C.src_ptr, &nnz_rep));
+    PFEM_TRY(amg_pattern_from_keys(s, W, total, C.src_slot.p, C.src_ptr, ukeys, &nnz_rep));
     C.nnz_c = nnz_rep;
     M.rep.reset(new (std::nothrow) Amg());
     if (!M.rep) return PFEM_ERR_NOMEM;
@@ -1052,11 +1143,7 @@ int amg_replicate(pfem_solver *s, Amg &M, AmgWork &W, AmgLevel &C, int64_t n_glo
     R0.n = R0.n_loc = n_global;
     R0.bs = C.bs;
     R0.n_nodes = C.bs > 1 ? nodes_total : n_global;
-    PFEM_TRY(amg_sell_from_keys(s, W, ukeys.p, nnz_rep, R0));
-    PFEM_TRY(C.dst_slot.alloc(static_cast<size_t>(std::max<int64_t>(nnz_rep, 1))));
-    hipLaunchKernelGGL(k_amg_dst_slots, dim3(grid_for(nnz_rep)), dim3(kBlock), 0, s->stream, nnz_rep, static_cast<const uint64_t *>(ukeys.p),
-                       static_cast<const int64_t *>(R0.rowptr.p), static_cast<const int64_t *>(R0.slice_off.p), C.dst_slot.p);
-    PFEM_TRY(check_kernel("k_amg_dst_slots (replicated level)"));
+    PFEM_TRY(amg_store_pattern(s, W, ukeys.p, nnz_rep, R0, C.dst_slot));
     if (C.bs > 1) {        // dofs of one node stay together on the replicated levels too: node and component of every dof, by global number
         double *node_g = M.rep_buf.p, *comp_g = M.rep_buf.p + n_global;
         PFEM_HIP(hipMemsetAsync(M.rep_buf.p, 0, sizeof(double) * static_cast<size_t>(2 * n_global), s->stream));
@@ -1227,9 +1314,8 @@ inline void amg_rbm_galerkin(pfem_solver *s, const AmgLevel &L, AmgLevel &C, con
 // Several ranks (coupled): the aggregates are the owned nodes'; the ghost nodes learn theirs, the centroids and the rotation
 // verdicts from the owners (amg_couple_level + two more sum-exchanges); everything else runs over all local nodes.
 int amg_couple_level(pfem_solver *s, AmgWork &W, AmgLevel &L, AmgLevel &C, bool overlap, int cb, const std::vector<double> *nc_of);
-template <class Phase>
 int amg_rbm_level(pfem_solver *s, Amg &M, AmgWork &W, AmgLevel &L, DevBuf<int32_t> &node_agg, int64_t na, const int32_t *hint,
-                  bool on_lattice, const int lat_hi[3], int lat_axis, Phase &phase, int l, bool coupled, bool overlap, double *n_global,
+                  bool on_lattice, const int lat_hi[3], int lat_axis, AmgPhaseClock &phase, int l, bool coupled, bool overlap, double *n_global,
                   const int *brick_box = nullptr /* node bricks (one rank): bricks along x, y, z of the box the aggregates are numbered in */)
 {
     DevBuf<char> &temp = W.temp;
@@ -1294,25 +1380,7 @@ int amg_rbm_level(pfem_solver *s, Amg &M, AmgWork &W, AmgLevel &L, DevBuf<int32_
         if (na > 0) PFEM_HIP(hipMemcpyAsync(C.hint.p, hint, sizeof(int32_t) * static_cast<size_t>(na), hipMemcpyDeviceToDevice, s->stream));
     }
     // ---- member nodes of every coarse node (ghosts included), ascending
-    {
-        DevBuf<int32_t> &cnt = W.cnt, &idx = W.idx, &skey = W.skey32;
-        PFEM_TRY(cnt.reserve(static_cast<size_t>(na_loc) + 1));
-        PFEM_TRY(idx.reserve(static_cast<size_t>(std::max<int64_t>(nn, 1))));
-        PFEM_TRY(skey.reserve(static_cast<size_t>(std::max<int64_t>(nn, 1))));
-        PFEM_TRY(L.mem_ptr.alloc(static_cast<size_t>(na_loc) + 1));
-        PFEM_TRY(L.mem_idx.alloc(static_cast<size_t>(std::max<int64_t>(nn, 1))));
-        PFEM_HIP(hipMemsetAsync(cnt.p, 0, sizeof(int32_t) * (na_loc + 1), s->stream));
-        hipLaunchKernelGGL(k_amg_count, dim3(grid_for(nn)), dim3(kBlock), 0, s->stream, nn, static_cast<const int32_t *>(L.node_agg.p), cnt.p);
-        PFEM_TRY(amg_exclusive_sum(s, temp, cnt.p, L.mem_ptr.p, na_loc + 1));
-        if (nn > 0) {
-            hipLaunchKernelGGL(k_amg_iota, dim3(grid_for(nn)), dim3(kBlock), 0, s->stream, nn, idx.p);
-            size_t tb = 0;
-            const int ni = static_cast<int>(nn);
-            PFEM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, L.node_agg.p, skey.p, idx.p, L.mem_idx.p, ni, 0, 32, s->stream));
-            if (tb > temp.n) { PFEM_HIP(hipStreamSynchronize(s->stream)); PFEM_TRY(temp.alloc(tb)); }
-            PFEM_HIP(hipcub::DeviceRadixSort::SortPairs(temp.p, tb, L.node_agg.p, skey.p, idx.p, L.mem_idx.p, ni, 0, 32, s->stream));
-        }
-    }
+    PFEM_TRY(amg_member_lists(s, W, L, L.node_agg.p, nn, na_loc, 32, true));
     // ---- centroids (the coarse nodes' coordinates) and the nodes' offsets from them
     {
         PFEM_TRY(rot_ok.reserve(static_cast<size_t>(na_loc) + 1));
@@ -1355,37 +1423,28 @@ int amg_rbm_level(pfem_solver *s, Amg &M, AmgWork &W, AmgLevel &L, DevBuf<int32_
     phase(l, "rbm: members + centroids");
     // ---- coarse block pattern: (coarse row node, coarse col node, fine block) sorted; the maps of the numeric product
     {
-        DevBuf<uint64_t> &keys = W.keys, &skeys = W.skeys;
+        DevBuf<uint64_t> &keys = W.keys;
         DevBuf<uint64_t> ukeys;
         DevBuf<int32_t> &idx = W.slots;
         const int64_t nblk = L.nblk;
         int64_t nblk_c = 0;
         PFEM_TRY(L.src_slot.alloc(static_cast<size_t>(std::max<int64_t>(nblk, 1))));
         bool by_codes = false;
-        if (nblk > 0 && brick_box && !coupled && na > 0 && !std::getenv("PFEM_AMG_BRICK_SORT")) {
+        if (nblk > 0 && brick_box && !coupled && na > 0 && !amg_brick_sort()) {
             // node bricks: the 27 bricks around a coarse node are its only possible columns -- counts and two scans, no sort
             DevBuf<uint16_t> code_cnt;
             DevBuf<int> d_fail;
             DevBuf<int32_t> &n_entries = W.head, &n_pairs = W.rank, &entry_off = W.cnt, &pair_off = W.idx;
             PFEM_TRY(code_cnt.alloc(static_cast<size_t>(kRbmCodes) * na));
             PFEM_TRY(d_fail.alloc(1));
-            PFEM_TRY(n_entries.reserve(static_cast<size_t>(na) + 1));
-            PFEM_TRY(n_pairs.reserve(static_cast<size_t>(na) + 1));
-            PFEM_TRY(entry_off.reserve(static_cast<size_t>(na) + 1));
-            PFEM_TRY(pair_off.reserve(static_cast<size_t>(na) + 1));
             PFEM_HIP(hipMemsetAsync(d_fail.p, 0, sizeof(int), s->stream));
-            hipLaunchKernelGGL(k_rbm_codes_count, dim3(grid_for(na + 1)), dim3(kBlock), 0, s->stream, na, static_cast<const int32_t *>(L.mem_ptr.p),
-                               static_cast<const int32_t *>(L.mem_idx.p), static_cast<const int64_t *>(L.gptr.p), static_cast<const int32_t *>(L.gcol.p),
-                               static_cast<const int32_t *>(L.node_agg.p), brick_box[0], brick_box[1], code_cnt.p, n_entries.p, n_pairs.p, d_fail.p);
-            PFEM_TRY(check_kernel("k_rbm_codes_count"));
-            PFEM_TRY(amg_exclusive_sum(s, temp, n_entries.p, entry_off.p, na + 1));
-            PFEM_TRY(amg_exclusive_sum(s, temp, n_pairs.p, pair_off.p, na + 1));
             int32_t tot[2] = {0, 0};
             int fail = 0;
-            PFEM_HIP(hipMemcpyAsync(&tot[0], entry_off.p + na, sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
-            PFEM_HIP(hipMemcpyAsync(&tot[1], pair_off.p + na, sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
-            PFEM_HIP(hipMemcpyAsync(&fail, d_fail.p, sizeof(int), hipMemcpyDeviceToHost, s->stream));
-            PFEM_HIP(hipStreamSynchronize(s->stream));
+            PFEM_TRY(amg_count_scans(s, W, na, [&] {
+                hipLaunchKernelGGL(k_rbm_codes_count, dim3(grid_for(na + 1)), dim3(kBlock), 0, s->stream, na, static_cast<const int32_t *>(L.mem_ptr.p),
+                                   static_cast<const int32_t *>(L.mem_idx.p), static_cast<const int64_t *>(L.gptr.p), static_cast<const int32_t *>(L.gcol.p),
+                                   static_cast<const int32_t *>(L.node_agg.p), brick_box[0], brick_box[1], code_cnt.p, n_entries.p, n_pairs.p, d_fail.p);
+            }, "k_rbm_codes_count", d_fail.p, &tot[0], &tot[1], &fail));
             if (!fail && tot[1] == nblk) {
                 nblk_c = tot[0];
                 PFEM_TRY(ukeys.alloc(static_cast<size_t>(std::max<int64_t>(nblk_c, 1))));
@@ -1402,17 +1461,11 @@ int amg_rbm_level(pfem_solver *s, Amg &M, AmgWork &W, AmgLevel &L, DevBuf<int32_
         if (by_codes) {
         } else if (nblk > 0) {
             PFEM_TRY(keys.reserve(static_cast<size_t>(nblk)));
-            PFEM_TRY(skeys.reserve(static_cast<size_t>(nblk)));
             PFEM_TRY(idx.reserve(static_cast<size_t>(nblk)));
             hipLaunchKernelGGL(k_rbm_emit_block_keys, dim3(grid_for(nblk)), dim3(kBlock), 0, s->stream, nblk, static_cast<const int32_t *>(L.brow.p),
                                static_cast<const int32_t *>(L.gcol.p), static_cast<const int32_t *>(L.node_agg.p), keys.p, idx.p);
             PFEM_TRY(check_kernel("k_rbm_emit_block_keys"));
-            size_t tb = 0;
-            const int ni = static_cast<int>(nblk);
-            PFEM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys.p, skeys.p, idx.p, L.src_slot.p, ni, 0, 64, s->stream));
-            if (tb > temp.n) { PFEM_HIP(hipStreamSynchronize(s->stream)); PFEM_TRY(temp.alloc(tb)); }
-            PFEM_HIP(hipcub::DeviceRadixSort::SortPairs(temp.p, tb, keys.p, skeys.p, idx.p, L.src_slot.p, ni, 0, 64, s->stream));
-            PFEM_TRY(amg_unique_runs(s, W, skeys.p, nblk, ukeys, L.src_ptr, &nblk_c));
+            PFEM_TRY(amg_pattern_from_keys(s, W, nblk, L.src_slot.p, L.src_ptr, ukeys, &nblk_c));
         } else {
             PFEM_TRY(L.src_ptr.alloc(1));
             PFEM_HIP(hipMemsetAsync(L.src_ptr.p, 0, sizeof(int64_t), s->stream));
@@ -1474,8 +1527,7 @@ int amg_rbm_level(pfem_solver *s, Amg &M, AmgWork &W, AmgLevel &L, DevBuf<int32_
 // a sorted aggregate graph each (24 ms on level 0) and the 64-bit sort of (coarse row, coarse col, fine slot) (10 ms).  When
 // every pair would be accepted the passes end in the bricks position >> shift anyway.  *done = false: the level is left to
 // the passes (weak couplings along an axis, couplings beyond the neighbouring bricks).
-template <class Phase>
-int amg_bricks_level(pfem_solver *s, Amg &M, AmgWork &W, AmgLevel &L, const SellDev &A, Phase &phase, int l, bool *done, bool coupled, bool overlap,
+int amg_bricks_level(pfem_solver *s, Amg &M, AmgWork &W, AmgLevel &L, const SellDev &A, AmgPhaseClock &phase, int l, bool *done, bool coupled, bool overlap,
                      double *n_global)
 {
     *done = false;
@@ -1526,7 +1578,7 @@ int amg_bricks_level(pfem_solver *s, Amg &M, AmgWork &W, AmgLevel &L, const Sell
         // (weak couplings inside the bricks: a verdict about the level -- refused from kAmgBrickWeakPercent of the rows on,
         // amg_node_bricks; a coupling beyond the neighbouring bricks: one is enough, the 27 offset codes cannot hold it)
         fail = why[2] > 0 || amg_too_many_weak(why[1], n);
-        if (why[0] && std::getenv("PFEM_AMG_VERBOSE"))
+        if (why[0] && amg_verbose())
             std::fprintf(stderr, "  gamg symbolic level %d bricks%s: %d of %lld rows with a weak sibling coupling, %d with a coupling beyond the neighbouring bricks (shifts %d %d %d, positions up to %d %d %d)\n",
                          l, fail ? " refused" : " kept", why[1], static_cast<long long>(n), why[2], B.shift[0], B.shift[1], B.shift[2], L.lat_hi[0], L.lat_hi[1], L.lat_hi[2]);
         return PFEM_OK;
@@ -1555,7 +1607,7 @@ int amg_bricks_level(pfem_solver *s, Amg &M, AmgWork &W, AmgLevel &L, const Sell
     if (coupled ? (nc_global < 1.0 || nc_global * 10.0 > *n_global * 8.0) : (na < 1 || na * 10 > n * 8 || 27 * na + 1 > 0xfffffff0LL)) return kAmgLastLevel;
     phase(l, "bricks: check + ranks");
     L.nc = na;
-    L.agg_kind = 1;
+    L.agg_kind = kAggBricks;
     std::unique_ptr<AmgLevel> Cp(new (std::nothrow) AmgLevel());
     if (!Cp) return PFEM_ERR_NOMEM;
     AmgLevel &C = *Cp;
@@ -1595,50 +1647,26 @@ int amg_bricks_level(pfem_solver *s, Amg &M, AmgWork &W, AmgLevel &L, const Sell
     C.lat_axis = axis;
     // ---- members of every coarse dof (restriction as a gather)
     {
-        DevBuf<int32_t> &cnt = W.cnt, &idx = W.idx, &skey = W.skey32;
-        PFEM_TRY(cnt.reserve(static_cast<size_t>(nal) + 1));
-        PFEM_TRY(idx.reserve(static_cast<size_t>(std::max<int64_t>(R, 1))));
-        PFEM_TRY(skey.reserve(static_cast<size_t>(std::max<int64_t>(R, 1))));
-        PFEM_TRY(L.mem_ptr.alloc(static_cast<size_t>(nal) + 1));
-        PFEM_TRY(L.mem_idx.alloc(static_cast<size_t>(std::max<int64_t>(R, 1))));
-        PFEM_HIP(hipMemsetAsync(cnt.p, 0, sizeof(int32_t) * (nal + 1), s->stream));
-        hipLaunchKernelGGL(k_amg_count, dim3(grid_for(R)), dim3(kBlock), 0, s->stream, R, static_cast<const int32_t *>(L.agg.p), cnt.p);
-        PFEM_TRY(amg_exclusive_sum(s, temp, cnt.p, L.mem_ptr.p, nal + 1));
-        hipLaunchKernelGGL(k_amg_iota, dim3(grid_for(R)), dim3(kBlock), 0, s->stream, R, idx.p);
-        size_t tb = 0;
-        const int ni = static_cast<int>(R);
         int bits = 1;
         while ((1LL << bits) < nal) ++bits;
-        PFEM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, L.agg.p, skey.p, idx.p, L.mem_idx.p, ni, 0, bits, s->stream));
-        if (tb > temp.n) { PFEM_HIP(hipStreamSynchronize(s->stream)); PFEM_TRY(temp.alloc(tb)); }
-        PFEM_HIP(hipcub::DeviceRadixSort::SortPairs(temp.p, tb, L.agg.p, skey.p, idx.p, L.mem_idx.p, ni, 0, bits, s->stream));
+        PFEM_TRY(amg_member_lists(s, W, L, L.agg.p, R, nal, bits));
     }
     phase(l, "bricks: aggregates + member lists");
     // ---- Galerkin maps.  From the member lists, no sort (k_lat_codes_*): two walks of every coarse row's member rows and two
     // scans over the coarse rows instead of a 32-bit sort of every stored entry (config 3, level 0: 6.4 -> see LAB_NOTES).
-    static const bool brick_sort = std::getenv("PFEM_AMG_BRICK_SORT") != nullptr;      // the sorted form (A/B; also taken for rows too long for 16-bit counters)
     bool maps_done = false;
-    if (!brick_sort && L.stored <= INT_MAX) {
+    if (!amg_brick_sort() && L.stored <= INT_MAX) {
         DevBuf<uint16_t> code_cnt;
         DevBuf<int32_t> &n_entries = W.head, &n_pairs = W.rank, &entry_off = W.cnt, &pair_off = W.idx;
         DevBuf<uint64_t> ukeys;
         PFEM_TRY(code_cnt.alloc(static_cast<size_t>(kLatCodes) * nal));
-        PFEM_TRY(n_entries.reserve(static_cast<size_t>(nal) + 1));
-        PFEM_TRY(n_pairs.reserve(static_cast<size_t>(nal) + 1));
-        PFEM_TRY(entry_off.reserve(static_cast<size_t>(nal) + 1));
-        PFEM_TRY(pair_off.reserve(static_cast<size_t>(nal) + 1));
-        hipLaunchKernelGGL(k_lat_codes_count, dim3(grid_for(nal + 1)), dim3(kBlock), 0, s->stream, Ar, static_cast<const int32_t *>(L.hint.p), B, nal,
-                           static_cast<const int32_t *>(L.mem_ptr.p), static_cast<const int32_t *>(L.mem_idx.p), static_cast<const int32_t *>(bc),
-                           code_cnt.p, n_entries.p, n_pairs.p, d_fail.p);
-        PFEM_TRY(check_kernel("k_lat_codes_count"));
-        PFEM_TRY(amg_exclusive_sum(s, temp, n_entries.p, entry_off.p, nal + 1));
-        PFEM_TRY(amg_exclusive_sum(s, temp, n_pairs.p, pair_off.p, nal + 1));
         int32_t tot[2] = {0, 0};
         int too_long = 0;
-        PFEM_HIP(hipMemcpyAsync(&tot[0], entry_off.p + nal, sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
-        PFEM_HIP(hipMemcpyAsync(&tot[1], pair_off.p + nal, sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
-        PFEM_HIP(hipMemcpyAsync(&too_long, d_fail.p, sizeof(int), hipMemcpyDeviceToHost, s->stream));
-        PFEM_HIP(hipStreamSynchronize(s->stream));
+        PFEM_TRY(amg_count_scans(s, W, nal, [&] {
+            hipLaunchKernelGGL(k_lat_codes_count, dim3(grid_for(nal + 1)), dim3(kBlock), 0, s->stream, Ar, static_cast<const int32_t *>(L.hint.p), B, nal,
+                               static_cast<const int32_t *>(L.mem_ptr.p), static_cast<const int32_t *>(L.mem_idx.p), static_cast<const int32_t *>(bc),
+                               code_cnt.p, n_entries.p, n_pairs.p, d_fail.p);
+        }, "k_lat_codes_count", d_fail.p, &tot[0], &tot[1], &too_long));
         maps_done = !too_long;
         const int64_t nnz_c = tot[0];
         if (maps_done) {
@@ -1660,18 +1688,14 @@ int amg_bricks_level(pfem_solver *s, Amg &M, AmgWork &W, AmgLevel &L, const Sell
 #undef PFEM_LAT_FILL
         PFEM_TRY(check_kernel("k_lat_codes_fill"));
         L.nnz_c = nnz_c;
-        PFEM_TRY(amg_sell_from_keys(s, W, ukeys.p, nnz_c, C));
-        if (maps) {
-            PFEM_TRY(L.dst_slot.alloc(static_cast<size_t>(std::max<int64_t>(nnz_c, 1))));
-            hipLaunchKernelGGL(k_amg_dst_slots, dim3(grid_for(nnz_c)), dim3(kBlock), 0, s->stream, nnz_c, static_cast<const uint64_t *>(ukeys.p),
-                               static_cast<const int64_t *>(C.rowptr.p), static_cast<const int64_t *>(C.slice_off.p), L.dst_slot.p);
-            PFEM_TRY(check_kernel("k_amg_dst_slots (bricks)"));
-        }
+        if (maps) PFEM_TRY(amg_store_pattern(s, W, ukeys.p, nnz_c, C, L.dst_slot));
+        else PFEM_TRY(amg_sell_from_keys(s, W, ukeys.p, nnz_c, C));
         }
         PFEM_HIP(hipStreamSynchronize(s->stream));       // (ukeys, code_cnt go out of scope)
     }
     if (!maps_done) {
-        // (27 * coarse row + offset code, fine slot) sorted on 32-bit keys, runs = coarse entries
+        // (27 * coarse row + offset code, fine slot) sorted on 32-bit keys, runs = coarse entries.  The one sorted route that does not
+        // go through amg_pattern_from_keys: its run kernels (k_lat_run_*) read 32-bit keys and decode them into the 64-bit ones.
         DevBuf<uint32_t> &keys = W.keys32, &skeys = W.skeys32;
         DevBuf<int32_t> &slots = W.slots, &head = W.head, &hrank = W.rank;
         DevBuf<uint64_t> ukeys;
@@ -1690,13 +1714,9 @@ int amg_bricks_level(pfem_solver *s, Amg &M, AmgWork &W, AmgLevel &L, const Sell
         PFEM_TRY(check_kernel("k_lat_emit_keys"));
         int bits = 1;
         while ((1ULL << bits) <= sentinel) ++bits;
-        size_t tb = 0;
-        const int ni = static_cast<int>(cnt);
         // (slots of slices beyond this level's rows keep the 0xffffffff fill: above the sentinel, they sort behind it with all 32 bits;
         // the level's own storage has none, so the sentinel's bits suffice)
-        PFEM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys.p, skeys.p, slots.p, L.src_slot.p, ni, 0, bits, s->stream));
-        if (tb > temp.n) { PFEM_HIP(hipStreamSynchronize(s->stream)); PFEM_TRY(temp.alloc(tb)); }
-        PFEM_HIP(hipcub::DeviceRadixSort::SortPairs(temp.p, tb, keys.p, skeys.p, slots.p, L.src_slot.p, ni, 0, bits, s->stream));
+        PFEM_TRY(amg_sort_pairs(s, temp, keys.p, skeys.p, slots.p, L.src_slot.p, cnt, bits));
         hipLaunchKernelGGL(k_lat_run_heads, dim3(grid_for(cnt + 1)), dim3(kBlock), 0, s->stream, cnt, static_cast<const uint32_t *>(skeys.p), head.p);
         PFEM_TRY(amg_exclusive_sum(s, temp, head.p, hrank.p, cnt + 1));
         int32_t m32 = 0;
@@ -1709,18 +1729,9 @@ int amg_bricks_level(pfem_solver *s, Amg &M, AmgWork &W, AmgLevel &L, const Sell
                            static_cast<const int32_t *>(head.p), static_cast<const int32_t *>(hrank.p), sentinel, static_cast<const int32_t *>(bc), B,
                            static_cast<const int32_t *>(rank.p), ukeys.p, L.src_ptr.p);
         PFEM_TRY(check_kernel("k_lat_run_scatter"));
-        if (nnz_c > 0) {      // the padding entries collapse into one sentinel run at the end: dropped (its slots are never read)
-            uint64_t last = 0;
-            PFEM_HIP(hipMemcpyAsync(&last, ukeys.p + (nnz_c - 1), sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
-            PFEM_HIP(hipStreamSynchronize(s->stream));
-            if (last == ~0ull) --nnz_c;
-        }
+        PFEM_TRY(amg_drop_sentinel_run(s, ukeys.p, &nnz_c));
         L.nnz_c = nnz_c;
-        PFEM_TRY(amg_sell_from_keys(s, W, ukeys.p, nnz_c, C));
-        PFEM_TRY(L.dst_slot.alloc(static_cast<size_t>(std::max<int64_t>(nnz_c, 1))));
-        hipLaunchKernelGGL(k_amg_dst_slots, dim3(grid_for(nnz_c)), dim3(kBlock), 0, s->stream, nnz_c, static_cast<const uint64_t *>(ukeys.p),
-                           static_cast<const int64_t *>(C.rowptr.p), static_cast<const int64_t *>(C.slice_off.p), L.dst_slot.p);
-        PFEM_TRY(check_kernel("k_amg_dst_slots (bricks)"));
+        PFEM_TRY(amg_store_pattern(s, W, ukeys.p, nnz_c, C, L.dst_slot));
         PFEM_HIP(hipStreamSynchronize(s->stream));       // (ukeys goes out of scope)
     }
     phase(l, "bricks: Galerkin maps + coarse pattern");
@@ -1906,18 +1917,18 @@ int amg_node_bricks(pfem_solver *s, AmgLevel &L, const AmgGraph &G, NodeBricks &
         PFEM_TRY(amg_allreduce_host(s, v, 4));
         if (rc != PFEM_OK) return rc;
         if (v[0] > 0.0) { set_last_error("gamg symbolic phase: another rank failed (allocation or size limit); all ranks stop together"); return PFEM_ERR_COMM; }
-        if (std::getenv("PFEM_AMG_VERBOSE") && v[1] > 0.0) std::fprintf(stderr, "  gamg symbolic: node bricks across ranks: %g of %g nodes with a weak coupling inside their brick\n", v[1], v[3]);
+        if (amg_verbose() && v[1] > 0.0) std::fprintf(stderr, "  gamg symbolic: node bricks across ranks: %g of %g nodes with a weak coupling inside their brick\n", v[1], v[3]);
         if (amg_too_many_weak(v[1], v[3]) || v[2] < 1.0 || v[2] * 10.0 > v[3] * 8.0) {
-            if (std::getenv("PFEM_AMG_VERBOSE"))
+            if (amg_verbose())
                 std::fprintf(stderr, "  gamg symbolic: node bricks across ranks refused (%g nodes with a weak coupling inside a brick, %g bricks for %g nodes)\n", v[1], v[2], v[3]);
             return PFEM_OK;
         }
         if (!have) { PFEM_TRY(N.node_agg.alloc(1)); PFEM_TRY(N.hint.alloc(1)); }
     } else {
         PFEM_TRY(rc);
-        if (std::getenv("PFEM_AMG_VERBOSE") && fail) std::fprintf(stderr, "  gamg symbolic: node bricks: %d of %lld nodes with a weak coupling inside their brick\n", fail, static_cast<long long>(nn));
+        if (amg_verbose() && fail) std::fprintf(stderr, "  gamg symbolic: node bricks: %d of %lld nodes with a weak coupling inside their brick\n", fail, static_cast<long long>(nn));
         if (amg_too_many_weak(fail, static_cast<double>(nn))) {
-            if (std::getenv("PFEM_AMG_VERBOSE")) std::fprintf(stderr, "  gamg symbolic: node bricks refused (weak couplings inside the bricks): the passes take the level\n");
+            if (amg_verbose()) std::fprintf(stderr, "  gamg symbolic: node bricks refused (weak couplings inside the bricks): the passes take the level\n");
             return PFEM_OK;
         }
     }
@@ -1976,7 +1987,7 @@ int amg_split_bricks(pfem_solver *s, AmgWork &W, AmgLevel &L, const SellDev &A, 
         PFEM_HIP(hipMemcpyAsync(&na32, rank.p + nbricks, sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
         PFEM_HIP(hipStreamSynchronize(s->stream));
         fail = amg_too_many_weak(why[1], n);
-        if (fail && std::getenv("PFEM_AMG_VERBOSE"))
+        if (fail && amg_verbose())
             std::fprintf(stderr, "  gamg symbolic: split bricks refused on this rank: %d of %lld owned rows with a weak sibling coupling\n", why[1], static_cast<long long>(n));
         return PFEM_OK;
     };
@@ -2006,28 +2017,424 @@ int amg_split_bricks(pfem_solver *s, AmgWork &W, AmgLevel &L, const SellDev &A, 
 // ---- the levels below M.lev.back(): aggregates, transfer maps, coarse patterns (and one numeric product each) ----------
 int amg_finish_levels(pfem_solver *s, Amg &M, bool coupled);
 int amg_replicate(pfem_solver *s, Amg &M, AmgWork &W, AmgLevel &C, int64_t n_global, bool overlap);
+// What the steps of one level hand each other (amg_build_levels): the aggregates of the level's nodes, and where they sit
+struct AmgLevelBuild {
+    DevBuf<int32_t> node_agg;                // node -> aggregate so far
+    int64_t na = 0;                          // aggregates so far
+    const int32_t *hint = nullptr;           // their places along the curve / positions on the lattice (null: indices), held by one of
+    DevBuf<int32_t> hint_a, hint_b;          //   these (pass by pass), by NB or by sb_pos
+    int lat_hi[3] = {0, 0, 0}, lat_axis = 0;
+    bool on_lattice = false;
+    bool rbm = false, have_graph = false;    // the level takes the rigid-body transfer / came with its node graph
+    AmgGraph *G = nullptr;                   // the strength graph the next pass pairs on (two objects in the work set, used alternately)
+    int gcur = 0;
+    bool node_bricks = false;
+    NodeBricks NB;
+    bool split_bricks = false;
+    DevBuf<int32_t> sb_agg, sb_pos;
+    int64_t sb_na = 0;
+    int sb_hi[3] = {0, 0, 0}, sb_axis = 0, sb_shift[3] = {0, 0, 0};
+};
+
+// small enough for every rank to hold it whole: the rest of the hierarchy is replicated (*done)
+int amg_replicate_rest(pfem_solver *s, Amg &M, AmgWork &W, bool coupled, double n_global, bool overlap, AmgPhaseClock &phase, int l, bool *done)
+{
+    const char *e = std::getenv("PFEM_AMG_REPLICATE_ROWS");
+    const int64_t replicate_rows = e ? std::atoll(e) : kAmgReplicateRows;
+    *done = coupled && n_global > kAmgDense && n_global <= static_cast<double>(replicate_rows);
+    if (!*done) return PFEM_OK;
+    PFEM_TRY(amg_replicate(s, M, W, *M.lev.back(), static_cast<int64_t>(n_global), overlap));
+    phase(l, "replicated levels");
+    return PFEM_OK;
+}
+
+// several ranks whose dofs do not fill boxes: a rank's aggregate = its part of a brick (amg_split_bricks); collective
+int amg_level_split_bricks(pfem_solver *s, AmgWork &W, AmgLevel &L, const SellDev &A, bool coupled, AmgLevelBuild &B, AmgPhaseClock &phase, int l)
+{
+    const int64_t nn = L.n_nodes;
+    if (coupled && L.lat_split && L.lattice && L.bs == 1 && (L.hint.p || L.n == 0)) {
+        PFEM_TRY(amg_split_bricks(s, W, L, A, &B.split_bricks, B.sb_agg, B.sb_pos, &B.sb_na, B.sb_hi, &B.sb_axis, B.sb_shift));
+        if (B.split_bricks) phase(l, "split bricks: check + aggregates");
+    }
+    // (a level that leaves the brick path on several ranks: the corners the replicated level will want, from the positions)
+    if (coupled && (L.lat_global || (L.lat_split && !B.split_bricks)) && L.bs == 1 && !L.xyz.p && nn > 0 && L.hint.p && L.lat_coord.size() == 3 * 1024) {
+        DevBuf<double> coord;
+        PFEM_TRY(coord.alloc(3 * 1024));
+        PFEM_TRY(L.xyz.alloc(static_cast<size_t>(3 * nn)));
+        PFEM_HIP(hipMemcpyAsync(coord.p, L.lat_coord.data(), sizeof(double) * 3 * 1024, hipMemcpyHostToDevice, s->stream));
+        hipLaunchKernelGGL(k_lat_xyz_from_pos, dim3(grid_for(nn)), dim3(kBlock), 0, s->stream, nn, static_cast<const int32_t *>(L.hint.p),
+                           static_cast<const double *>(coord.p), L.xyz.p);
+        PFEM_TRY(check_kernel("k_lat_xyz_from_pos"));
+        PFEM_HIP(hipStreamSynchronize(s->stream));
+    }
+    return PFEM_OK;
+}
+
+// the level's strength graph on its nodes, in B.G: the node graph of a rigid-body level (all local, or the owned nodes' rows of
+// it), the matrix itself (scalar problem), or the dofs' entries summed node by node; none where split bricks gave the aggregates.
+// Decides B.rbm on the way.
+int amg_level_graph(pfem_solver *s, Amg &M, AmgWork &W, AmgLevel &L, const SellDev &A, bool coupled, AmgLevelBuild &B)
+{
+    const int64_t R = coupled ? L.n_loc : L.n, nn = L.n_nodes;
+    B.gcur = 0;
+    B.G = &W.graphs[0];
+    const int32_t col_limit = static_cast<int32_t>(L.n);       // coarse levels: every column; level 0: the owned ones
+    // rigid-body modes: the level qualifies when its dofs come bs to the node in a block-regular matrix (checked here for
+    // the assembled matrix; a coarse level of this kind is block regular by construction)
+    // (several ranks, one hierarchy across them: the node graph spans all local nodes -- owned first, ghosts after them --, the
+    // pairing sees the owned nodes' rows without their ghost columns; one hierarchy per rank: not a candidate)
+    const int64_t nn_loc = L.bs > 0 ? R / L.bs : 0;
+    bool rbm_here = L.dim > 0 && L.cen.p && (coupled || L.n_loc == L.n) && L.n == nn * L.bs && R == nn_loc * L.bs;
+    double rbm_bad = 0.0;
+    // (a level that amg_rbm_level built comes with its node graph -- the coarse block pattern it was stored from: nothing to check)
+    B.have_graph = rbm_here && !L.fine && L.gptr.p && L.gcol.p && L.brow.p && L.nblk > 0 && L.gptr.n == static_cast<size_t>(nn_loc) + 1;
+    if (rbm_here && !B.have_graph) {
+        const SellDev Ar = amg_sell(s, L, R);
+        DevBuf<int64_t> deg;
+        DevBuf<int> d_bad;
+        PFEM_TRY(deg.alloc(static_cast<size_t>(nn_loc) + 1));
+        PFEM_TRY(d_bad.alloc(1));
+        PFEM_HIP(hipMemsetAsync(d_bad.p, 0, sizeof(int), s->stream));
+        hipLaunchKernelGGL(k_rbm_check_rows, dim3(grid_for(R + 1)), dim3(kBlock), 0, s->stream, Ar, L.bs, nn_loc, deg.p, d_bad.p);
+        PFEM_TRY(check_kernel("k_rbm_check_rows"));
+        PFEM_TRY(L.gptr.alloc(static_cast<size_t>(nn_loc) + 1));
+        PFEM_TRY(amg_exclusive_sum(s, W.temp, deg.p, L.gptr.p, nn_loc + 1));
+        int bad = 0;
+        int64_t nblk = 0;
+        PFEM_HIP(hipMemcpyAsync(&bad, d_bad.p, sizeof(int), hipMemcpyDeviceToHost, s->stream));
+        PFEM_HIP(hipMemcpyAsync(&nblk, L.gptr.p + nn_loc, sizeof(int64_t), hipMemcpyDeviceToHost, s->stream));
+        PFEM_HIP(hipStreamSynchronize(s->stream));
+        if (bad || nblk > INT_MAX || (nblk < 1 && nn_loc > 0)) rbm_bad = 1.0;
+        L.nblk = nblk;
+    }
+    if (coupled && L.dim > 0) {              // all ranks take the same transfer
+        double v[2] = {rbm_here ? 0.0 : 1.0, rbm_bad};
+        PFEM_TRY(amg_allreduce_host(s, v, 2));
+        rbm_here = v[0] == 0.0 && v[1] == 0.0;
+    } else if (rbm_bad > 0.0) {
+        rbm_here = false;
+    }
+    if (!rbm_here) L.gptr.release();
+    L.rbm = B.rbm = rbm_here;
+    if (B.split_bricks) {
+        // (no strength graph: the aggregates are there)
+    } else if (B.rbm) {
+        const SellDev Ar = amg_sell(s, L, R);
+        M.rbm = true;
+        if (!B.have_graph) {
+            PFEM_TRY(L.gcol.alloc(static_cast<size_t>(std::max<int64_t>(L.nblk, 1))));
+            PFEM_TRY(L.brow.alloc(static_cast<size_t>(std::max<int64_t>(L.nblk, 1))));
+        }
+        // (DIM lanes per node, 64 / DIM nodes per wave)
+        auto graph_fill = [&](int64_t nodes, double *gw, double *gd) {
+            const int npw = 64 / L.dim;
+            const unsigned blocks = static_cast<unsigned>(((nodes + npw - 1) / npw * 64 + kBlock - 1) / kBlock);
+            if (L.dim == 3) hipLaunchKernelGGL(k_rbm_graph_fill_rows<3>, dim3(std::max(blocks, 1u)), dim3(kBlock), 0, s->stream, Ar, L.bs, nodes,
+                                               static_cast<const int64_t *>(L.gptr.p), L.gcol.p, L.brow.p, gw, gd);
+            else hipLaunchKernelGGL(k_rbm_graph_fill_rows<2>, dim3(std::max(blocks, 1u)), dim3(kBlock), 0, s->stream, Ar, L.bs, nodes,
+                                    static_cast<const int64_t *>(L.gptr.p), L.gcol.p, L.brow.p, gw, gd);
+        };
+        if (nn_loc == nn) {
+            PFEM_TRY(B.G->reserve(nn, L.nblk));
+            graph_fill(nn, B.G->w.p, B.G->diag.p);
+            PFEM_TRY(check_kernel("k_rbm_graph_fill"));
+            PFEM_HIP(hipMemcpyAsync(B.G->ptr.p, L.gptr.p, sizeof(int64_t) * (nn + 1), hipMemcpyDeviceToDevice, s->stream));
+            if (L.nblk > 0) PFEM_HIP(hipMemcpyAsync(B.G->col.p, L.gcol.p, sizeof(int32_t) * L.nblk, hipMemcpyDeviceToDevice, s->stream));
+        } else {
+            // all local nodes' graph first (weights in the work set), then the owned nodes' rows without ghost columns
+            DevBuf<double> &w_all = W.svals, &d_all = W.sums;
+            DevBuf<int64_t> odeg;
+            PFEM_TRY(w_all.reserve(static_cast<size_t>(std::max<int64_t>(L.nblk, 1))));
+            PFEM_TRY(d_all.reserve(static_cast<size_t>(std::max<int64_t>(nn_loc, 1))));
+            PFEM_TRY(odeg.alloc(static_cast<size_t>(nn) + 1));
+            graph_fill(nn_loc, w_all.p, d_all.p);
+            hipLaunchKernelGGL(k_rbm_owned_degree, dim3(grid_for(nn + 1)), dim3(kBlock), 0, s->stream, nn, static_cast<const int64_t *>(L.gptr.p),
+                               static_cast<const int32_t *>(L.gcol.p), odeg.p);
+            PFEM_TRY(check_kernel("k_rbm_owned_degree"));
+            B.G->n = nn;
+            PFEM_TRY(B.G->ptr.reserve(static_cast<size_t>(nn) + 1));
+            PFEM_TRY(amg_exclusive_sum(s, W.temp, odeg.p, B.G->ptr.p, nn + 1));
+            int64_t onnz = 0;
+            PFEM_HIP(hipMemcpyAsync(&onnz, B.G->ptr.p + nn, sizeof(int64_t), hipMemcpyDeviceToHost, s->stream));
+            PFEM_HIP(hipStreamSynchronize(s->stream));
+            B.G->nnz = onnz;
+            PFEM_TRY(B.G->col.reserve(static_cast<size_t>(std::max<int64_t>(onnz, 1))));
+            PFEM_TRY(B.G->w.reserve(static_cast<size_t>(std::max<int64_t>(onnz, 1))));
+            PFEM_TRY(B.G->diag.reserve(static_cast<size_t>(std::max<int64_t>(nn, 1))));
+            hipLaunchKernelGGL(k_rbm_owned_graph, dim3(grid_for(nn)), dim3(kBlock), 0, s->stream, nn, static_cast<const int64_t *>(L.gptr.p),
+                               static_cast<const int32_t *>(L.gcol.p), static_cast<const double *>(w_all.p), static_cast<const int64_t *>(B.G->ptr.p),
+                               B.G->col.p, B.G->w.p);
+            PFEM_TRY(check_kernel("k_rbm_owned_graph"));
+            if (nn > 0) PFEM_HIP(hipMemcpyAsync(B.G->diag.p, d_all.p, sizeof(double) * nn, hipMemcpyDeviceToDevice, s->stream));
+            PFEM_HIP(hipStreamSynchronize(s->stream));        // (odeg goes out of scope)
+        }
+    } else if (L.bs == 1 && L.n_loc == L.n) {
+        // scalar problem: the matrix itself (rows are sorted and unique already)
+        PFEM_TRY(B.G->reserve(L.n, L.nnz));
+        const int64_t *rowptr = L.fine ? s->d_rowptr.p : L.rowptr.p;
+        PFEM_HIP(hipMemcpyAsync(B.G->ptr.p, rowptr, sizeof(int64_t) * (L.n + 1), hipMemcpyDeviceToDevice, s->stream));
+        hipLaunchKernelGGL(k_sell_to_csr, dim3(grid_for(L.n)), dim3(kBlock), 0, s->stream, A, static_cast<const int64_t *>(B.G->ptr.p), B.G->col.p, B.G->w.p);
+        hipLaunchKernelGGL(k_extract_diag, dim3(grid_for(L.n)), dim3(kBlock), 0, s->stream, A, B.G->diag.p);
+        PFEM_TRY(check_kernel("gamg scalar graph"));
+    } else {
+        DevBuf<uint64_t> &keys = W.keys, &ukeys = W.ukeys;
+        DevBuf<double> &vals = W.vals, &sums = W.sums;
+        PFEM_TRY(keys.reserve(static_cast<size_t>(L.stored)));
+        PFEM_TRY(vals.reserve(static_cast<size_t>(L.stored)));
+        const int64_t cnt = L.stored;      // slots of rows beyond this block keep the sentinel key
+        PFEM_HIP(hipMemsetAsync(keys.p, 0xff, sizeof(uint64_t) * static_cast<size_t>(L.stored), s->stream));
+        PFEM_HIP(hipMemsetAsync(vals.p, 0, sizeof(double) * static_cast<size_t>(L.stored), s->stream));
+        hipLaunchKernelGGL(k_amg_emit_node_keys, dim3(grid_for(A.n_slices * 64)), dim3(kBlock), 0, s->stream, A,
+                           L.bs > 1 ? static_cast<const int32_t *>(L.node_of.p) : static_cast<const int32_t *>(nullptr), col_limit,
+                           L.bs > 1 ? 1 : 0, keys.p, vals.p);
+        PFEM_TRY(check_kernel("k_amg_emit_node_keys"));
+        int64_t m = 0;
+        PFEM_TRY(amg_sort_reduce(s, W, keys, vals, cnt, ukeys, sums, &m));
+        PFEM_TRY(amg_graph_from_unique(s, ukeys, sums, m, nn, L.bs > 1 ? 1 : 0, *B.G));
+    }
+    return PFEM_OK;
+}
+
+// the aggregates of the level's nodes (B.node_agg, B.na, their places in B.hint): node bricks in one step, the split bricks found
+// before, or passes of pairwise matching -- along the lattice's axes while that pairs, then on the strength graph
+int amg_level_aggregates(pfem_solver *s, AmgWork &W, AmgLevel &L, bool coupled, AmgLevelBuild &B, AmgPhaseClock &phase, int l)
+{
+    const int64_t nn = L.n_nodes, nn_loc = L.bs > 0 ? (coupled ? L.n_loc : L.n) / L.bs : 0;
+    PFEM_TRY(B.node_agg.alloc(static_cast<size_t>(std::max<int64_t>(nn, 1))));
+    hipLaunchKernelGGL(k_amg_iota, dim3(grid_for(nn)), dim3(kBlock), 0, s->stream, nn, B.node_agg.p);
+    B.na = nn;
+    B.hint = L.hint.p;                              // null: indices
+    for (int d = 0; d < 3; ++d) B.lat_hi[d] = L.lat_hi[d];
+    B.lat_axis = L.lat_axis;
+    B.on_lattice = L.lattice;
+    // level 0 of a displacement problem on one rank: five passes, aggregates of up to 32 nodes -- the rigid-body coarse space
+    // carries them (see amg_node_bricks for the lattice's case), and level 1 with its 6x6 blocks is the dearest of the cycle:
+    // the beam with its nodes moved off the lattice 67 iterations / 116 ms with three passes, 52 / 74 with four, 61 / 72 with
+    // five, 59 / 71 with six (profiles/r05/beam_level0_aggregate_sizes.txt)
+    const int n_passes = (L.fine && B.rbm && !coupled) ? 5 : kAmgPasses;
+    // levels with the rigid-body transfer on a full lattice (one rank): the bricks the passes would end in, in one step
+    // (several ranks, round 6: the same across the ranks when the positions are global and every rank's nodes fill a box --
+    // L.lat_nodes_global is set from all-reduced verdicts only, the same on every rank)
+    if (B.rbm && (coupled ? L.lat_nodes_global : nn_loc == nn) && L.lattice && L.lat_full && (L.hint.p || nn == 0)) {
+        PFEM_TRY(amg_node_bricks(s, L, *B.G, B.NB, &B.node_bricks, coupled));
+        if (B.node_bricks) {
+            B.node_agg.swap(B.NB.node_agg);
+            B.na = B.NB.na;
+            B.hint = B.NB.hint.p;
+            for (int d = 0; d < 3; ++d) B.lat_hi[d] = B.NB.hi[d];
+            B.lat_axis = B.NB.axis;
+            phase(l, "node bricks: check + aggregates");
+        }
+    }
+    if (B.split_bricks) {
+        B.node_agg.swap(B.sb_agg);
+        B.na = B.sb_na;
+        B.hint = B.sb_pos.p;
+        for (int d = 0; d < 3; ++d) B.lat_hi[d] = B.sb_hi[d];
+        B.lat_axis = B.sb_axis;
+    }
+    for (int pass = 0; pass < ((B.node_bricks || B.split_bricks) ? 0 : n_passes); ++pass) {
+        DevBuf<int32_t> &step = W.step;
+        int64_t na_new = 0;
+        bool lattice_pass = L.lattice && B.on_lattice;
+        int axis = B.lat_axis;
+        if (lattice_pass) {
+            // the next axis that still has an extent (a beam runs out of x and z long before y) and along which the nodes
+            // do pair: an axis across which the couplings are weak (anisotropic operator) pairs next to nothing and is
+            // passed over -- semi-coarsening along the strong axes, still on the lattice
+            bool paired = false;
+            for (int k = 0; k < 3 && !paired; ++k, axis = (axis + 1) % 3) {
+                if (B.lat_hi[axis] < 1) continue;
+                PFEM_TRY(amg_match_lattice(s, W, *B.G, B.hint, axis, L.bs > 1, step, &na_new));
+                if (na_new * 10 <= B.G->n * 8) { paired = true; break; }
+            }
+            phase(l, "  lattice pairing");
+            if (!paired) {
+                // no axis left, or couplings too uneven for the strength threshold everywhere (thin cells of a replicated
+                // level): from here on the matching on the strength graph, ties by index
+                lattice_pass = B.on_lattice = false;
+                B.hint = nullptr;
+            }
+        }
+        if (lattice_pass) {
+            DevBuf<int32_t> &nh = (pass & 1) ? B.hint_b : B.hint_a;
+            PFEM_TRY(nh.alloc(static_cast<size_t>(std::max<int64_t>(na_new, 1))));
+            hipLaunchKernelGGL(k_amg_lat_coarsen, dim3(grid_for(B.G->n)), dim3(kBlock), 0, s->stream, B.G->n, B.hint, static_cast<const int32_t *>(W.match.p),
+                               static_cast<const int32_t *>(step.p), 10 * axis, nh.p);
+            PFEM_TRY(check_kernel("k_amg_lat_coarsen"));
+            B.hint = nh.p;
+            B.lat_hi[axis] >>= 1;
+            B.lat_axis = (axis + 1) % 3;
+        } else {
+        PFEM_TRY(amg_match(s, W, *B.G, B.hint, step, &na_new));
+        phase(l, "  matching rounds");
+        }
+        if (B.hint && !lattice_pass) {
+            DevBuf<int32_t> &nh = (pass & 1) ? B.hint_b : B.hint_a;
+            PFEM_TRY(nh.alloc(static_cast<size_t>(na_new)));
+            PFEM_HIP(hipMemsetAsync(nh.p, 0x7f, sizeof(int32_t) * static_cast<size_t>(na_new), s->stream));
+            hipLaunchKernelGGL(k_amg_hint_coarsen, dim3(grid_for(B.G->n)), dim3(kBlock), 0, s->stream, B.G->n, B.hint, static_cast<const int32_t *>(step.p), nh.p);
+            PFEM_TRY(check_kernel("k_amg_hint_coarsen"));
+            B.hint = nh.p;
+        }
+        hipLaunchKernelGGL(k_amg_compose, dim3(grid_for(nn)), dim3(kBlock), 0, s->stream, nn, B.node_agg.p, static_cast<const int32_t *>(step.p));
+        PFEM_TRY(check_kernel("k_amg_compose"));
+        const bool last = pass + 1 == n_passes || na_new <= 1;
+        if (!last) {
+            // graph of the aggregates
+            DevBuf<uint64_t> &keys = W.keys, &ukeys = W.ukeys;
+            DevBuf<double> &vals = W.vals, &sums = W.sums;
+            const int64_t cnt = B.G->nnz + B.G->n;
+            PFEM_TRY(keys.reserve(static_cast<size_t>(cnt)));
+            PFEM_TRY(vals.reserve(static_cast<size_t>(cnt)));
+            hipLaunchKernelGGL(k_amg_emit_coarse_graph, dim3(grid_for(B.G->n)), dim3(kBlock), 0, s->stream, B.G->n, B.G->nnz,
+                               static_cast<const int64_t *>(B.G->ptr.p), static_cast<const int32_t *>(B.G->col.p), static_cast<const double *>(B.G->w.p),
+                               static_cast<const double *>(B.G->diag.p), static_cast<const int32_t *>(step.p), L.bs > 1 ? 1 : 0, keys.p, vals.p);
+            PFEM_TRY(check_kernel("k_amg_emit_coarse_graph"));
+            int64_t m = 0;
+            phase(l, "  emit aggregate graph");
+            PFEM_TRY(amg_sort_reduce(s, W, keys, vals, cnt, ukeys, sums, &m));
+            phase(l, "  sort + reduce by key");
+            B.gcur ^= 1;                                  // the aggregates' graph goes into the other graph object
+            PFEM_TRY(amg_graph_from_unique(s, ukeys, sums, m, na_new, 0, W.graphs[B.gcur]));
+            B.G = &W.graphs[B.gcur];
+        }
+        B.na = na_new;
+        if (last) break;
+    }
+    L.agg_kind = B.node_bricks ? kAggNodeBricks : (B.split_bricks ? kAggSplitBricks : (B.on_lattice ? kAggLatticePasses : kAggMatching));
+    phase(l, "3 passes of matching");
+    return PFEM_OK;
+}
+
+// the coarse dofs -- the (aggregate, component) pairs that occur -- and the level they make (Cp): its rows, across ranks its
+// neighbour plan, its nodes and their places.  kAmgLastLevel: the coarsening has stalled.
+int amg_level_coarse_dofs(pfem_solver *s, AmgWork &W, AmgLevel &L, bool coupled, bool overlap, AmgLevelBuild &B, double n_global,
+                          std::unique_ptr<AmgLevel> &Cp, double *nc_global_out)
+{
+    const int64_t R = coupled ? L.n_loc : L.n, nn = L.n_nodes;
+    const int64_t nslots = B.na * L.bs;
+    if (coupled) PFEM_TRY(amg_agree(s, nslots > INT_MAX - 8 ? PFEM_ERR_ARG : PFEM_OK));
+    else if (nslots > INT_MAX - 8) return PFEM_ERR_ARG;
+    DevBuf<int32_t> &flag = W.flag, &rank = W.crank;
+    PFEM_TRY(flag.reserve(static_cast<size_t>(nslots) + 1));
+    PFEM_TRY(rank.reserve(static_cast<size_t>(nslots) + 1));
+    PFEM_HIP(hipMemsetAsync(flag.p, 0, sizeof(int32_t) * (nslots + 1), s->stream));
+    const int32_t *node_of = L.bs > 1 ? L.node_of.p : nullptr, *comp_of = L.bs > 1 ? L.comp_of.p : nullptr;
+    hipLaunchKernelGGL(k_amg_mark_cdofs, dim3(grid_for(L.n)), dim3(kBlock), 0, s->stream, L.n, node_of, comp_of,
+                       static_cast<const int32_t *>(B.node_agg.p), L.bs, flag.p);
+    PFEM_TRY(amg_exclusive_sum(s, W.temp, flag.p, rank.p, nslots + 1));
+    int32_t nc32 = 0;
+    PFEM_HIP(hipMemcpyAsync(&nc32, rank.p + nslots, sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+    PFEM_HIP(hipStreamSynchronize(s->stream));
+    const int64_t nc = nc32;
+    std::vector<double> nc_of;                   // coupled: coarse dofs of every rank
+    double nc_global = static_cast<double>(nc);
+    if (coupled) {
+        nc_of.assign(static_cast<size_t>(s->nranks), 0.0);
+        nc_of[static_cast<size_t>(s->rank)] = static_cast<double>(nc);
+        PFEM_TRY(amg_allreduce_host(s, nc_of.data(), s->nranks));
+        nc_global = 0.0;
+        for (double v : nc_of) nc_global += v;
+        if (nc_global < 1.0 || nc_global * 10.0 > n_global * 8.0) return kAmgLastLevel;      // (decided by all ranks alike)
+    } else if (nc < 1 || nc * 10 > L.n * 8) {
+        return kAmgLastLevel;                    // the coarsening has stalled: this level is the last one
+    }
+    L.nc = nc;
+    PFEM_TRY(L.agg.alloc(static_cast<size_t>(std::max<int64_t>(R, 1))));
+    hipLaunchKernelGGL(k_amg_assign_cdofs, dim3(grid_for(L.n)), dim3(kBlock), 0, s->stream, L.n, node_of, comp_of,
+                       static_cast<const int32_t *>(B.node_agg.p), L.bs, static_cast<const int32_t *>(rank.p), L.agg.p);
+    PFEM_TRY(check_kernel("k_amg_assign_cdofs"));
+    Cp.reset(new (std::nothrow) AmgLevel());
+    if (!Cp) return PFEM_ERR_NOMEM;
+    AmgLevel &C = *Cp;
+    C.n = nc;
+    C.n_loc = nc;
+    if (coupled) {
+        for (int q = 0; q < s->rank; ++q) C.gid_off += static_cast<int64_t>(nc_of[static_cast<size_t>(q)]);
+        const int rc = amg_couple_level(s, W, L, C, overlap, 0, nullptr);
+        if (rc != PFEM_OK) return rc;
+    }
+    C.bs = L.bs;
+    C.n_nodes = L.bs > 1 ? B.na : nc;
+    if (B.hint && C.n_nodes == B.na) {                  // the next level pairs on along the same curve / on the coarser lattice
+        C.lattice = L.lattice && B.on_lattice;
+        for (int d = 0; d < 3; ++d) C.lat_hi[d] = B.lat_hi[d];
+        C.lat_axis = B.lat_axis;
+        if (L.xyz.p && B.na > 0) {
+            DevBuf<unsigned long long> keys;
+            PFEM_TRY(keys.alloc(static_cast<size_t>(3 * B.na)));
+            PFEM_TRY(C.xyz.alloc(static_cast<size_t>(3 * B.na)));
+            PFEM_HIP(hipMemsetAsync(keys.p, 0xff, sizeof(unsigned long long) * static_cast<size_t>(3 * B.na), s->stream));
+            hipLaunchKernelGGL(k_amg_xyz_min, dim3(grid_for(nn)), dim3(kBlock), 0, s->stream, nn, static_cast<const int32_t *>(B.node_agg.p),
+                               static_cast<const double *>(L.xyz.p), B.na, keys.p);
+            hipLaunchKernelGGL(k_amg_xyz_decode, dim3(grid_for(3 * B.na)), dim3(kBlock), 0, s->stream, 3 * B.na,
+                               static_cast<const unsigned long long *>(keys.p), C.xyz.p);
+            PFEM_TRY(check_kernel("k_amg_xyz_min"));
+            PFEM_HIP(hipStreamSynchronize(s->stream));
+        }
+        PFEM_TRY(C.hint.alloc(static_cast<size_t>(std::max<int64_t>(B.na, 1))));
+        if (B.na > 0) PFEM_HIP(hipMemcpyAsync(C.hint.p, B.hint, sizeof(int32_t) * static_cast<size_t>(B.na), hipMemcpyDeviceToDevice, s->stream));
+        if (B.split_bricks) {             // the next level splits its bricks the same way: the box of this rank's owned coarse positions, the positions' coordinates
+            C.lat_split = true;
+            for (int d = 0; d < 3; ++d) { C.lat_tlo[d] = L.lat_tlo[d] >> B.sb_shift[d]; C.lat_thi[d] = L.lat_thi[d] >> B.sb_shift[d]; }
+            C.lat_coord.assign(3 * 1024, 0.0);
+            if (L.lat_coord.size() == 3 * 1024)
+                for (int d = 0; d < 3; ++d)
+                    for (int pc = 0; pc <= B.lat_hi[d] && pc < 1024; ++pc) C.lat_coord[static_cast<size_t>(1024 * d + pc)] = L.lat_coord[static_cast<size_t>(1024 * d + std::min(pc << B.sb_shift[d], 1023))];
+        }
+    }
+    if (L.bs > 1) {
+        PFEM_TRY(C.node_of.alloc(static_cast<size_t>(nc)));
+        PFEM_TRY(C.comp_of.alloc(static_cast<size_t>(nc)));
+        hipLaunchKernelGGL(k_amg_coarse_nodes, dim3(grid_for(nslots)), dim3(kBlock), 0, s->stream, nslots, L.bs,
+                           static_cast<const int32_t *>(flag.p), static_cast<const int32_t *>(rank.p), C.node_of.p, C.comp_of.p);
+        PFEM_TRY(check_kernel("k_amg_coarse_nodes"));
+    }
+    *nc_global_out = nc_global;
+    return PFEM_OK;
+}
+
+// coarse pattern and the maps of the numeric Galerkin product: (coarse row, coarse col, fine slot) triples, sorted.
+// (A formulation by coarse rows -- one thread per coarse row, its column set and its sums in LDS, the fine matrix read in
+// its own order, no sort -- was built and measured in round 3: numeric phase 3.96 instead of 2.28 ms at config 3, the
+// thread's chain of dependent loads over its 8 member rows is latency-bound.  Dropped.)
+int amg_level_maps(pfem_solver *s, AmgWork &W, AmgLevel &L, AmgLevel &C, int64_t R)
+{
+    DevBuf<uint64_t> &keys = W.keys;
+    DevBuf<uint64_t> ukeys;                       // (as long as the coarse matrix has entries: exact)
+    DevBuf<int32_t> &slots = W.slots;
+    PFEM_TRY(keys.reserve(static_cast<size_t>(L.stored)));
+    PFEM_TRY(slots.reserve(static_cast<size_t>(L.stored)));
+    PFEM_HIP(hipMemsetAsync(keys.p, 0xff, sizeof(uint64_t) * static_cast<size_t>(L.stored), s->stream));   // slots of ghost rows
+    PFEM_HIP(hipMemsetAsync(slots.p, 0, sizeof(int32_t) * static_cast<size_t>(L.stored), s->stream));
+    const SellDev Ar = amg_sell(s, L, R);
+    hipLaunchKernelGGL(k_amg_emit_rap_keys, dim3(grid_for(Ar.n_slices * 64)), dim3(kBlock), 0, s->stream, Ar,
+                       static_cast<const int32_t *>(L.agg.p), static_cast<int32_t>(R), keys.p, slots.p);
+    PFEM_TRY(check_kernel("k_amg_emit_rap_keys"));
+    PFEM_TRY(L.src_slot.alloc(static_cast<size_t>(L.stored)));
+    int64_t nnz_c = 0;
+    PFEM_TRY(amg_pattern_from_keys(s, W, L.stored, L.src_slot.p, L.src_ptr, ukeys, &nnz_c));
+    PFEM_TRY(amg_drop_sentinel_run(s, ukeys.p, &nnz_c));          // (the slots of ghost rows and of the padding)
+    L.nnz_c = nnz_c;
+    PFEM_TRY(amg_store_pattern(s, W, ukeys.p, nnz_c, C, L.dst_slot));
+    PFEM_HIP(hipStreamSynchronize(s->stream));
+    return PFEM_OK;
+}
+
 int amg_build_levels(pfem_solver *s, Amg &M, AmgWork &W, bool coupled, bool overlap)
 {
-    DevBuf<char> &temp = W.temp;
-    const bool verbose = std::getenv("PFEM_AMG_VERBOSE") != nullptr;
-    auto tick = std::chrono::steady_clock::now();
-    auto phase = [&](int lvl, const char *what) {          // PFEM_AMG_VERBOSE: where the symbolic phase spends its time
-        if (!verbose) return;
-        (void)hipStreamSynchronize(s->stream);
-        const auto now = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "  gamg symbolic level %d %-28s %9.2f ms\n", lvl, what, std::chrono::duration<double, std::milli>(now - tick).count());
-        tick = now;
-    };
+    AmgPhaseClock phase{s->stream, amg_verbose(), std::chrono::steady_clock::now()};
     phase(-1, "level 0 nodes + curve places");
     double n_global = static_cast<double>(M.lev[0]->n);       // rows of the current level over all ranks (coupled)
     if (coupled) PFEM_TRY(amg_allreduce_host(s, &n_global, 1));
-    const int64_t replicate_rows = [] { const char *e = std::getenv("PFEM_AMG_REPLICATE_ROWS"); return e ? std::atoll(e) : static_cast<long long>(kAmgReplicateRows); }();
     for (int l = 0; l + 1 < kAmgMaxLevels; ++l) {
         AmgLevel &L = *M.lev[static_cast<size_t>(l)];
         if (coupled ? n_global <= kAmgDense : L.n <= kAmgDense) break;
         const SellDev A = amg_sell(s, L);
         const int64_t R = coupled ? L.n_loc : L.n;           // rows (and columns) that take part in the Galerkin product
-        const int64_t nn = L.n_nodes;
+        bool replicated = false;
+        // ---- a scalar level on a lattice: bricks in one step
         // (several ranks: L.lat_global is the same on every rank -- set from all-reduced verdicts only)
         if (L.lattice && L.bs == 1 && (coupled ? L.lat_global : L.n_loc == L.n) && L.hint.p) {
             bool done = false;
@@ -2036,452 +2443,56 @@ int amg_build_levels(pfem_solver *s, Amg &M, AmgWork &W, bool coupled, bool over
             if (rc != PFEM_OK) return rc;
             if (done) {
                 if (!coupled) n_global = static_cast<double>(M.lev.back()->n);
-                // small enough for every rank to hold it whole: the rest of the hierarchy is replicated
-                if (coupled && n_global > kAmgDense && n_global <= static_cast<double>(replicate_rows)) {
-                    PFEM_TRY(amg_replicate(s, M, W, *M.lev.back(), static_cast<int64_t>(n_global), overlap));
-                    phase(l, "replicated levels");
-                    break;
-                }
+                PFEM_TRY(amg_replicate_rest(s, M, W, coupled, n_global, overlap, phase, l, &replicated));
+                if (replicated) break;
                 continue;
             }
         }
-        // ---- several ranks whose dofs do not fill boxes: a rank's aggregate = its part of a brick (amg_split_bricks); collective
-        bool split_bricks = false;
-        DevBuf<int32_t> sb_agg, sb_pos;
-        int64_t sb_na = 0;
-        int sb_hi[3] = {0, 0, 0}, sb_axis = 0, sb_shift[3] = {0, 0, 0};
-        if (coupled && L.lat_split && L.lattice && L.bs == 1 && (L.hint.p || L.n == 0)) {
-            PFEM_TRY(amg_split_bricks(s, W, L, A, &split_bricks, sb_agg, sb_pos, &sb_na, sb_hi, &sb_axis, sb_shift));
-            if (split_bricks) phase(l, "split bricks: check + aggregates");
-        }
-        // (a level that leaves the brick path on several ranks: the corners the replicated level will want, from the positions)
-        if (coupled && (L.lat_global || (L.lat_split && !split_bricks)) && L.bs == 1 && !L.xyz.p && nn > 0 && L.hint.p && L.lat_coord.size() == 3 * 1024) {
-            DevBuf<double> coord;
-            PFEM_TRY(coord.alloc(3 * 1024));
-            PFEM_TRY(L.xyz.alloc(static_cast<size_t>(3 * nn)));
-            PFEM_HIP(hipMemcpyAsync(coord.p, L.lat_coord.data(), sizeof(double) * 3 * 1024, hipMemcpyHostToDevice, s->stream));
-            hipLaunchKernelGGL(k_lat_xyz_from_pos, dim3(grid_for(nn)), dim3(kBlock), 0, s->stream, nn, static_cast<const int32_t *>(L.hint.p),
-                               static_cast<const double *>(coord.p), L.xyz.p);
-            PFEM_TRY(check_kernel("k_lat_xyz_from_pos"));
-            PFEM_HIP(hipStreamSynchronize(s->stream));
-        }
-        // ---- pass-1 strength graph on the nodes (two graph objects in the work set, used alternately pass by pass)
-        int gcur = 0;
-        AmgGraph *Gp = &W.graphs[0];
-#define G (*Gp)
-        const int32_t col_limit = static_cast<int32_t>(L.n);       // coarse levels: every column; level 0: the owned ones
-        // rigid-body modes: the level qualifies when its dofs come bs to the node in a block-regular matrix (checked here for
-        // the assembled matrix; a coarse level of this kind is block regular by construction)
-        // (several ranks, one hierarchy across them: the node graph spans all local nodes -- owned first, ghosts after them --, the
-        // pairing sees the owned nodes' rows without their ghost columns; one hierarchy per rank: not a candidate)
-        const int64_t nn_loc = L.bs > 0 ? R / L.bs : 0;
-        bool rbm = L.dim > 0 && L.cen.p && (coupled || L.n_loc == L.n) && L.n == nn * L.bs && R == nn_loc * L.bs;
-        double rbm_bad = 0.0;
-        // (a level that amg_rbm_level built comes with its node graph -- the coarse block pattern it was stored from: nothing to check)
-        const bool have_graph = rbm && !L.fine && L.gptr.p && L.gcol.p && L.brow.p && L.nblk > 0 && L.gptr.n == static_cast<size_t>(nn_loc) + 1;
-        if (rbm && !have_graph) {
-            const SellDev Ar = amg_sell(s, L, R);
-            DevBuf<int64_t> deg;
-            DevBuf<int> d_bad;
-            PFEM_TRY(deg.alloc(static_cast<size_t>(nn_loc) + 1));
-            PFEM_TRY(d_bad.alloc(1));
-            PFEM_HIP(hipMemsetAsync(d_bad.p, 0, sizeof(int), s->stream));
-            hipLaunchKernelGGL(k_rbm_check_rows, dim3(grid_for(R + 1)), dim3(kBlock), 0, s->stream, Ar, L.bs, nn_loc, deg.p, d_bad.p);
-            PFEM_TRY(check_kernel("k_rbm_check_rows"));
-            PFEM_TRY(L.gptr.alloc(static_cast<size_t>(nn_loc) + 1));
-            PFEM_TRY(amg_exclusive_sum(s, temp, deg.p, L.gptr.p, nn_loc + 1));
-            int bad = 0;
-            int64_t nblk = 0;
-            PFEM_HIP(hipMemcpyAsync(&bad, d_bad.p, sizeof(int), hipMemcpyDeviceToHost, s->stream));
-            PFEM_HIP(hipMemcpyAsync(&nblk, L.gptr.p + nn_loc, sizeof(int64_t), hipMemcpyDeviceToHost, s->stream));
-            PFEM_HIP(hipStreamSynchronize(s->stream));
-            if (bad || nblk > INT_MAX || (nblk < 1 && nn_loc > 0)) rbm_bad = 1.0;
-            L.nblk = nblk;
-        }
-        if (coupled && L.dim > 0) {              // all ranks take the same transfer
-            double v[2] = {rbm ? 0.0 : 1.0, rbm_bad};
-            PFEM_TRY(amg_allreduce_host(s, v, 2));
-            rbm = v[0] == 0.0 && v[1] == 0.0;
-        } else if (rbm_bad > 0.0) {
-            rbm = false;
-        }
-        if (!rbm) L.gptr.release();
-        L.rbm = rbm;
-        if (split_bricks) {
-            // (no strength graph: the aggregates are there)
-        } else if (rbm) {
-            const SellDev Ar = amg_sell(s, L, R);
-            M.rbm = true;
-            if (!have_graph) {
-                PFEM_TRY(L.gcol.alloc(static_cast<size_t>(std::max<int64_t>(L.nblk, 1))));
-                PFEM_TRY(L.brow.alloc(static_cast<size_t>(std::max<int64_t>(L.nblk, 1))));
-            }
-            // (DIM lanes per node, 64 / DIM nodes per wave)
-            auto graph_fill = [&](int64_t nodes, double *gw, double *gd) {
-                const int npw = 64 / L.dim;
-                const unsigned blocks = static_cast<unsigned>(((nodes + npw - 1) / npw * 64 + kBlock - 1) / kBlock);
-                if (L.dim == 3) hipLaunchKernelGGL(k_rbm_graph_fill_rows<3>, dim3(std::max(blocks, 1u)), dim3(kBlock), 0, s->stream, Ar, L.bs, nodes,
-                                                   static_cast<const int64_t *>(L.gptr.p), L.gcol.p, L.brow.p, gw, gd);
-                else hipLaunchKernelGGL(k_rbm_graph_fill_rows<2>, dim3(std::max(blocks, 1u)), dim3(kBlock), 0, s->stream, Ar, L.bs, nodes,
-                                        static_cast<const int64_t *>(L.gptr.p), L.gcol.p, L.brow.p, gw, gd);
-            };
-            if (nn_loc == nn) {
-                G.n = nn;
-                G.nnz = L.nblk;
-                PFEM_TRY(G.ptr.reserve(static_cast<size_t>(nn) + 1));
-                PFEM_TRY(G.col.reserve(static_cast<size_t>(std::max<int64_t>(L.nblk, 1))));
-                PFEM_TRY(G.w.reserve(static_cast<size_t>(std::max<int64_t>(L.nblk, 1))));
-                PFEM_TRY(G.diag.reserve(static_cast<size_t>(std::max<int64_t>(nn, 1))));
-                graph_fill(nn, G.w.p, G.diag.p);
-                PFEM_TRY(check_kernel("k_rbm_graph_fill"));
-                PFEM_HIP(hipMemcpyAsync(G.ptr.p, L.gptr.p, sizeof(int64_t) * (nn + 1), hipMemcpyDeviceToDevice, s->stream));
-                if (L.nblk > 0) PFEM_HIP(hipMemcpyAsync(G.col.p, L.gcol.p, sizeof(int32_t) * L.nblk, hipMemcpyDeviceToDevice, s->stream));
-            } else {
-                // all local nodes' graph first (weights in the work set), then the owned nodes' rows without ghost columns
-                DevBuf<double> &w_all = W.svals, &d_all = W.sums;
-                DevBuf<int64_t> odeg;
-                PFEM_TRY(w_all.reserve(static_cast<size_t>(std::max<int64_t>(L.nblk, 1))));
-                PFEM_TRY(d_all.reserve(static_cast<size_t>(std::max<int64_t>(nn_loc, 1))));
-                PFEM_TRY(odeg.alloc(static_cast<size_t>(nn) + 1));
-                graph_fill(nn_loc, w_all.p, d_all.p);
-                hipLaunchKernelGGL(k_rbm_owned_degree, dim3(grid_for(nn + 1)), dim3(kBlock), 0, s->stream, nn, static_cast<const int64_t *>(L.gptr.p),
-                                   static_cast<const int32_t *>(L.gcol.p), odeg.p);
-                PFEM_TRY(check_kernel("k_rbm_owned_degree"));
-                G.n = nn;
-                PFEM_TRY(G.ptr.reserve(static_cast<size_t>(nn) + 1));
-                PFEM_TRY(amg_exclusive_sum(s, temp, odeg.p, G.ptr.p, nn + 1));
-                int64_t onnz = 0;
-                PFEM_HIP(hipMemcpyAsync(&onnz, G.ptr.p + nn, sizeof(int64_t), hipMemcpyDeviceToHost, s->stream));
-                PFEM_HIP(hipStreamSynchronize(s->stream));
-                G.nnz = onnz;
-                PFEM_TRY(G.col.reserve(static_cast<size_t>(std::max<int64_t>(onnz, 1))));
-                PFEM_TRY(G.w.reserve(static_cast<size_t>(std::max<int64_t>(onnz, 1))));
-                PFEM_TRY(G.diag.reserve(static_cast<size_t>(std::max<int64_t>(nn, 1))));
-                hipLaunchKernelGGL(k_rbm_owned_graph, dim3(grid_for(nn)), dim3(kBlock), 0, s->stream, nn, static_cast<const int64_t *>(L.gptr.p),
-                                   static_cast<const int32_t *>(L.gcol.p), static_cast<const double *>(w_all.p), static_cast<const int64_t *>(G.ptr.p),
-                                   G.col.p, G.w.p);
-                PFEM_TRY(check_kernel("k_rbm_owned_graph"));
-                if (nn > 0) PFEM_HIP(hipMemcpyAsync(G.diag.p, d_all.p, sizeof(double) * nn, hipMemcpyDeviceToDevice, s->stream));
-                PFEM_HIP(hipStreamSynchronize(s->stream));        // (odeg goes out of scope)
-            }
-        } else if (L.bs == 1 && L.n_loc == L.n) {
-            // scalar problem: the matrix itself (rows are sorted and unique already)
-            G.n = L.n;
-            G.nnz = L.nnz;
-            PFEM_TRY(G.ptr.reserve(static_cast<size_t>(L.n) + 1));
-            PFEM_TRY(G.col.reserve(static_cast<size_t>(std::max<int64_t>(L.nnz, 1))));
-            PFEM_TRY(G.w.reserve(static_cast<size_t>(std::max<int64_t>(L.nnz, 1))));
-            PFEM_TRY(G.diag.reserve(static_cast<size_t>(L.n)));
-            const int64_t *rowptr = L.fine ? s->d_rowptr.p : L.rowptr.p;
-            PFEM_HIP(hipMemcpyAsync(G.ptr.p, rowptr, sizeof(int64_t) * (L.n + 1), hipMemcpyDeviceToDevice, s->stream));
-            hipLaunchKernelGGL(k_sell_to_csr, dim3(grid_for(L.n)), dim3(kBlock), 0, s->stream, A, static_cast<const int64_t *>(G.ptr.p), G.col.p, G.w.p);
-            hipLaunchKernelGGL(k_extract_diag, dim3(grid_for(L.n)), dim3(kBlock), 0, s->stream, A, G.diag.p);
-            PFEM_TRY(check_kernel("gamg scalar graph"));
-        } else {
-            DevBuf<uint64_t> &keys = W.keys, &ukeys = W.ukeys;
-            DevBuf<double> &vals = W.vals, &sums = W.sums;
-            PFEM_TRY(keys.reserve(static_cast<size_t>(L.stored)));
-            PFEM_TRY(vals.reserve(static_cast<size_t>(L.stored)));
-            const int64_t cnt = L.stored;      // slots of rows beyond this block keep the sentinel key
-            PFEM_HIP(hipMemsetAsync(keys.p, 0xff, sizeof(uint64_t) * static_cast<size_t>(L.stored), s->stream));
-            PFEM_HIP(hipMemsetAsync(vals.p, 0, sizeof(double) * static_cast<size_t>(L.stored), s->stream));
-            hipLaunchKernelGGL(k_amg_emit_node_keys, dim3(grid_for(A.n_slices * 64)), dim3(kBlock), 0, s->stream, A,
-                               L.bs > 1 ? static_cast<const int32_t *>(L.node_of.p) : static_cast<const int32_t *>(nullptr), col_limit,
-                               L.bs > 1 ? 1 : 0, keys.p, vals.p);
-            PFEM_TRY(check_kernel("k_amg_emit_node_keys"));
-            int64_t m = 0;
-            PFEM_TRY(amg_sort_reduce(s, W, keys, vals, cnt, amg_key_bits(nn), ukeys, sums, &m));
-            PFEM_TRY(amg_graph_from_unique(s, ukeys, sums, m, nn, L.bs > 1 ? 1 : 0, G));
-        }
+        // ---- the aggregates of the level's nodes
+        AmgLevelBuild B;
+        PFEM_TRY(amg_level_split_bricks(s, W, L, A, coupled, B, phase, l));
+        PFEM_TRY(amg_level_graph(s, M, W, L, A, coupled, B));
         phase(l, "strength graph");
-        // ---- three passes of pairwise matching; node_agg = node -> aggregate so far
-        DevBuf<int32_t> node_agg;
-        PFEM_TRY(node_agg.alloc(static_cast<size_t>(std::max<int64_t>(nn, 1))));
-        hipLaunchKernelGGL(k_amg_iota, dim3(grid_for(nn)), dim3(kBlock), 0, s->stream, nn, node_agg.p);
-        int64_t na = nn;
-        DevBuf<int32_t> hint_a, hint_b;                 // places of the current graph's nodes along the curve (pass by pass)
-        const int32_t *hint = L.hint.p;                 // null: indices
-        int lat_hi[3] = {L.lat_hi[0], L.lat_hi[1], L.lat_hi[2]}, lat_axis = L.lat_axis;
-        bool on_lattice = L.lattice;
-        // level 0 of a displacement problem on one rank: five passes, aggregates of up to 32 nodes -- the rigid-body coarse space
-        // carries them (see amg_node_bricks for the lattice's case), and level 1 with its 6x6 blocks is the dearest of the cycle:
-        // the beam with its nodes moved off the lattice 67 iterations / 116 ms with three passes, 52 / 74 with four, 61 / 72 with
-        // five, 59 / 71 with six (profiles/r05/beam_level0_aggregate_sizes.txt)
-        const int n_passes = (L.fine && rbm && !coupled) ? 5 : kAmgPasses;
-        // levels with the rigid-body transfer on a full lattice (one rank): the bricks the passes would end in, in one step
-        NodeBricks NB;
-        bool node_bricks = false;
-        // (several ranks, round 6: the same across the ranks when the positions are global and every rank's nodes fill a box --
-        // L.lat_nodes_global is set from all-reduced verdicts only, the same on every rank)
-        if (rbm && (coupled ? L.lat_nodes_global : nn_loc == nn) && L.lattice && L.lat_full && (L.hint.p || nn == 0)) {
-            PFEM_TRY(amg_node_bricks(s, L, G, NB, &node_bricks, coupled));
-            if (node_bricks) {
-                node_agg.swap(NB.node_agg);
-                na = NB.na;
-                hint = NB.hint.p;
-                for (int d = 0; d < 3; ++d) lat_hi[d] = NB.hi[d];
-                lat_axis = NB.axis;
-                phase(l, "node bricks: check + aggregates");
-            }
-        }
-        if (split_bricks) {
-            node_agg.swap(sb_agg);
-            na = sb_na;
-            hint = sb_pos.p;
-            for (int d = 0; d < 3; ++d) lat_hi[d] = sb_hi[d];
-            lat_axis = sb_axis;
-        }
-        for (int pass = 0; pass < ((node_bricks || split_bricks) ? 0 : n_passes); ++pass) {
-            DevBuf<int32_t> &step = W.step;
-            int64_t na_new = 0;
-            bool lattice_pass = L.lattice && on_lattice;
-            int axis = lat_axis;
-            if (lattice_pass) {
-                // the next axis that still has an extent (a beam runs out of x and z long before y) and along which the nodes
-                // do pair: an axis across which the couplings are weak (anisotropic operator) pairs next to nothing and is
-                // passed over -- semi-coarsening along the strong axes, still on the lattice
-                bool paired = false;
-                for (int k = 0; k < 3 && !paired; ++k, axis = (axis + 1) % 3) {
-                    if (lat_hi[axis] < 1) continue;
-                    PFEM_TRY(amg_match_lattice(s, W, G, hint, axis, L.bs > 1, step, &na_new));
-                    if (na_new * 10 <= G.n * 8) { paired = true; break; }
-                }
-                phase(l, "  lattice pairing");
-                if (!paired) {
-                    // no axis left, or couplings too uneven for the strength threshold everywhere (thin cells of a replicated
-                    // level): from here on the matching on the strength graph, ties by index
-                    lattice_pass = on_lattice = false;
-                    hint = nullptr;
-                }
-            }
-            if (lattice_pass) {
-                DevBuf<int32_t> &nh = (pass & 1) ? hint_b : hint_a;
-                PFEM_TRY(nh.alloc(static_cast<size_t>(std::max<int64_t>(na_new, 1))));
-                hipLaunchKernelGGL(k_amg_lat_coarsen, dim3(grid_for(G.n)), dim3(kBlock), 0, s->stream, G.n, hint, static_cast<const int32_t *>(W.match.p),
-                                   static_cast<const int32_t *>(step.p), 10 * axis, nh.p);
-                PFEM_TRY(check_kernel("k_amg_lat_coarsen"));
-                hint = nh.p;
-                lat_hi[axis] >>= 1;
-                lat_axis = (axis + 1) % 3;
-            } else {
-            PFEM_TRY(amg_match(s, W, G, hint, step, &na_new));
-            phase(l, "  matching rounds");
-            }
-            if (hint && !lattice_pass) {
-                DevBuf<int32_t> &nh = (pass & 1) ? hint_b : hint_a;
-                PFEM_TRY(nh.alloc(static_cast<size_t>(na_new)));
-                PFEM_HIP(hipMemsetAsync(nh.p, 0x7f, sizeof(int32_t) * static_cast<size_t>(na_new), s->stream));
-                hipLaunchKernelGGL(k_amg_hint_coarsen, dim3(grid_for(G.n)), dim3(kBlock), 0, s->stream, G.n, hint, static_cast<const int32_t *>(step.p), nh.p);
-                PFEM_TRY(check_kernel("k_amg_hint_coarsen"));
-                hint = nh.p;
-            }
-            hipLaunchKernelGGL(k_amg_compose, dim3(grid_for(nn)), dim3(kBlock), 0, s->stream, nn, node_agg.p, static_cast<const int32_t *>(step.p));
-            PFEM_TRY(check_kernel("k_amg_compose"));
-            const bool last = pass + 1 == n_passes || na_new <= 1;
-            if (!last) {
-                // graph of the aggregates
-                DevBuf<uint64_t> &keys = W.keys, &ukeys = W.ukeys;
-                DevBuf<double> &vals = W.vals, &sums = W.sums;
-                const int64_t cnt = G.nnz + G.n;
-                PFEM_TRY(keys.reserve(static_cast<size_t>(cnt)));
-                PFEM_TRY(vals.reserve(static_cast<size_t>(cnt)));
-                hipLaunchKernelGGL(k_amg_emit_coarse_graph, dim3(grid_for(G.n)), dim3(kBlock), 0, s->stream, G.n, G.nnz,
-                                   static_cast<const int64_t *>(G.ptr.p), static_cast<const int32_t *>(G.col.p), static_cast<const double *>(G.w.p),
-                                   static_cast<const double *>(G.diag.p), static_cast<const int32_t *>(step.p), L.bs > 1 ? 1 : 0, keys.p, vals.p);
-                PFEM_TRY(check_kernel("k_amg_emit_coarse_graph"));
-                int64_t m = 0;
-                phase(l, "  emit aggregate graph");
-                PFEM_TRY(amg_sort_reduce(s, W, keys, vals, cnt, amg_key_bits(na_new), ukeys, sums, &m));
-                phase(l, "  sort + reduce by key");
-                gcur ^= 1;                                  // the aggregates' graph goes into the other graph object
-                PFEM_TRY(amg_graph_from_unique(s, ukeys, sums, m, na_new, 0, W.graphs[gcur]));
-                Gp = &W.graphs[gcur];
-            }
-            na = na_new;
-            if (last) break;
-        }
-#undef G
-        L.agg_kind = node_bricks ? 2 : (split_bricks ? 3 : (on_lattice ? 4 : 5));
-        phase(l, "3 passes of matching");
-        if (rbm) {
-            const int rc = amg_rbm_level(s, M, W, L, node_agg, na, hint, on_lattice, lat_hi, lat_axis, phase, l, coupled, overlap, &n_global,
-                                         node_bricks ? NB.nbk : nullptr);
+        PFEM_TRY(amg_level_aggregates(s, W, L, coupled, B, phase, l));
+        // ---- the level below, with the rigid-body transfer ...
+        if (B.rbm) {
+            const int rc = amg_rbm_level(s, M, W, L, B.node_agg, B.na, B.hint, B.on_lattice, B.lat_hi, B.lat_axis, phase, l, coupled, overlap, &n_global,
+                                         B.node_bricks ? B.NB.nbk : nullptr);
             if (rc == kAmgLastLevel) break;
             if (rc != PFEM_OK) return rc;
-            if (node_bricks) {              // the coarse nodes fill their box of positions again
+            if (B.node_bricks) {              // the coarse nodes fill their box of positions again
                 AmgLevel &Cn = *M.lev.back();
                 Cn.lat_full = true;
-                for (int d = 0; d < 3; ++d) { Cn.lat_tlo[d] = NB.tlo[d]; Cn.lat_thi[d] = NB.thi[d]; }
+                for (int d = 0; d < 3; ++d) { Cn.lat_tlo[d] = B.NB.tlo[d]; Cn.lat_thi[d] = B.NB.thi[d]; }
                 if (coupled) {              // ... every rank's, in the same global brick coordinates: the next level cuts its bricks at the same borders
                     Cn.lat_nodes_global = true;
-                    for (int d = 0; d < 3; ++d) Cn.lat_str[d] = NB.str[d];
+                    for (int d = 0; d < 3; ++d) Cn.lat_str[d] = B.NB.str[d];
                 }
             }
-            if (coupled && n_global > kAmgDense && n_global <= static_cast<double>(replicate_rows)) {
-                PFEM_TRY(amg_replicate(s, M, W, *M.lev.back(), static_cast<int64_t>(n_global), overlap));
-                phase(l, "replicated levels");
-                break;
-            }
+            PFEM_TRY(amg_replicate_rest(s, M, W, coupled, n_global, overlap, phase, l, &replicated));
+            if (replicated) break;
             continue;
         }
-        // ---- coarse dofs: (aggregate, component) pairs that occur
-        const int64_t nslots = na * L.bs;
-        if (coupled) PFEM_TRY(amg_agree(s, nslots > INT_MAX - 8 ? PFEM_ERR_ARG : PFEM_OK));
-        else if (nslots > INT_MAX - 8) return PFEM_ERR_ARG;
-        DevBuf<int32_t> &flag = W.flag, &rank = W.crank;
-        PFEM_TRY(flag.reserve(static_cast<size_t>(nslots) + 1));
-        PFEM_TRY(rank.reserve(static_cast<size_t>(nslots) + 1));
-        PFEM_HIP(hipMemsetAsync(flag.p, 0, sizeof(int32_t) * (nslots + 1), s->stream));
-        const int32_t *node_of = L.bs > 1 ? L.node_of.p : nullptr, *comp_of = L.bs > 1 ? L.comp_of.p : nullptr;
-        hipLaunchKernelGGL(k_amg_mark_cdofs, dim3(grid_for(L.n)), dim3(kBlock), 0, s->stream, L.n, node_of, comp_of,
-                           static_cast<const int32_t *>(node_agg.p), L.bs, flag.p);
-        PFEM_TRY(amg_exclusive_sum(s, temp, flag.p, rank.p, nslots + 1));
-        int32_t nc32 = 0;
-        PFEM_HIP(hipMemcpyAsync(&nc32, rank.p + nslots, sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+        // ---- ... or with one coarse dof per aggregate and component: coarse dofs, member lists, maps and pattern
+        std::unique_ptr<AmgLevel> Cp;
+        double nc_global = 0.0;
+        const int rc = amg_level_coarse_dofs(s, W, L, coupled, overlap, B, n_global, Cp, &nc_global);
+        if (rc == kAmgLastLevel) break;
+        if (rc != PFEM_OK) return rc;
+        PFEM_TRY(amg_member_lists(s, W, L, L.agg.p, R, Cp->n_loc, 32));
         PFEM_HIP(hipStreamSynchronize(s->stream));
-        const int64_t nc = nc32;
-        std::vector<double> nc_of;                   // coupled: coarse dofs of every rank
-        double nc_global = static_cast<double>(nc);
-        if (coupled) {
-            nc_of.assign(static_cast<size_t>(s->nranks), 0.0);
-            nc_of[static_cast<size_t>(s->rank)] = static_cast<double>(nc);
-            PFEM_TRY(amg_allreduce_host(s, nc_of.data(), s->nranks));
-            nc_global = 0.0;
-            for (double v : nc_of) nc_global += v;
-            if (nc_global < 1.0 || nc_global * 10.0 > n_global * 8.0) break;      // (decided by all ranks alike)
-        } else if (nc < 1 || nc * 10 > L.n * 8) {
-            break;                                   // the coarsening has stalled: this level is the last one
-        }
-        L.nc = nc;
-        PFEM_TRY(L.agg.alloc(static_cast<size_t>(std::max<int64_t>(R, 1))));
-        hipLaunchKernelGGL(k_amg_assign_cdofs, dim3(grid_for(L.n)), dim3(kBlock), 0, s->stream, L.n, node_of, comp_of,
-                           static_cast<const int32_t *>(node_agg.p), L.bs, static_cast<const int32_t *>(rank.p), L.agg.p);
-        PFEM_TRY(check_kernel("k_amg_assign_cdofs"));
-        std::unique_ptr<AmgLevel> Cp(new (std::nothrow) AmgLevel());
-        if (!Cp) return PFEM_ERR_NOMEM;
-        AmgLevel &C = *Cp;
-        C.n = nc;
-        C.n_loc = nc;
-        if (coupled) {
-            for (int q = 0; q < s->rank; ++q) C.gid_off += static_cast<int64_t>(nc_of[static_cast<size_t>(q)]);
-            const int rc = amg_couple_level(s, W, L, C, overlap, 0, nullptr);
-            if (rc != PFEM_OK) return rc;
-        }
-        const int64_t nc_loc = C.n_loc;
-        C.bs = L.bs;
-        C.n_nodes = L.bs > 1 ? na : nc;
-        if (hint && C.n_nodes == na) {                  // the next level pairs on along the same curve / on the coarser lattice
-            C.lattice = L.lattice && on_lattice;
-            for (int d = 0; d < 3; ++d) C.lat_hi[d] = lat_hi[d];
-            C.lat_axis = lat_axis;
-            if (L.xyz.p && na > 0) {
-                DevBuf<unsigned long long> keys;
-                PFEM_TRY(keys.alloc(static_cast<size_t>(3 * na)));
-                PFEM_TRY(C.xyz.alloc(static_cast<size_t>(3 * na)));
-                PFEM_HIP(hipMemsetAsync(keys.p, 0xff, sizeof(unsigned long long) * static_cast<size_t>(3 * na), s->stream));
-                hipLaunchKernelGGL(k_amg_xyz_min, dim3(grid_for(nn)), dim3(kBlock), 0, s->stream, nn, static_cast<const int32_t *>(node_agg.p),
-                                   static_cast<const double *>(L.xyz.p), na, keys.p);
-                hipLaunchKernelGGL(k_amg_xyz_decode, dim3(grid_for(3 * na)), dim3(kBlock), 0, s->stream, 3 * na,
-                                   static_cast<const unsigned long long *>(keys.p), C.xyz.p);
-                PFEM_TRY(check_kernel("k_amg_xyz_min"));
-                PFEM_HIP(hipStreamSynchronize(s->stream));
-            }
-            PFEM_TRY(C.hint.alloc(static_cast<size_t>(std::max<int64_t>(na, 1))));
-            if (na > 0) PFEM_HIP(hipMemcpyAsync(C.hint.p, hint, sizeof(int32_t) * static_cast<size_t>(na), hipMemcpyDeviceToDevice, s->stream));
-            if (split_bricks) {             // the next level splits its bricks the same way: the box of this rank's owned coarse positions, the positions' coordinates
-                C.lat_split = true;
-                for (int d = 0; d < 3; ++d) { C.lat_tlo[d] = L.lat_tlo[d] >> sb_shift[d]; C.lat_thi[d] = L.lat_thi[d] >> sb_shift[d]; }
-                C.lat_coord.assign(3 * 1024, 0.0);
-                if (L.lat_coord.size() == 3 * 1024)
-                    for (int d = 0; d < 3; ++d)
-                        for (int pc = 0; pc <= lat_hi[d] && pc < 1024; ++pc) C.lat_coord[static_cast<size_t>(1024 * d + pc)] = L.lat_coord[static_cast<size_t>(1024 * d + std::min(pc << sb_shift[d], 1023))];
-            }
-        }
-        if (L.bs > 1) {
-            PFEM_TRY(C.node_of.alloc(static_cast<size_t>(nc)));
-            PFEM_TRY(C.comp_of.alloc(static_cast<size_t>(nc)));
-            hipLaunchKernelGGL(k_amg_coarse_nodes, dim3(grid_for(nslots)), dim3(kBlock), 0, s->stream, nslots, L.bs,
-                               static_cast<const int32_t *>(flag.p), static_cast<const int32_t *>(rank.p), C.node_of.p, C.comp_of.p);
-            PFEM_TRY(check_kernel("k_amg_coarse_nodes"));
-        }
-        // ---- members of every coarse dof (restriction as a gather)
-        {
-            DevBuf<int32_t> &cnt = W.cnt, &idx = W.idx, &skey = W.skey32;
-            PFEM_TRY(cnt.reserve(static_cast<size_t>(nc_loc) + 1));
-            PFEM_TRY(idx.reserve(static_cast<size_t>(std::max<int64_t>(R, 1))));
-            PFEM_TRY(skey.reserve(static_cast<size_t>(std::max<int64_t>(R, 1))));
-            PFEM_TRY(L.mem_ptr.alloc(static_cast<size_t>(nc_loc) + 1));
-            PFEM_TRY(L.mem_idx.alloc(static_cast<size_t>(std::max<int64_t>(R, 1))));
-            PFEM_HIP(hipMemsetAsync(cnt.p, 0, sizeof(int32_t) * (nc_loc + 1), s->stream));
-            hipLaunchKernelGGL(k_amg_count, dim3(grid_for(R)), dim3(kBlock), 0, s->stream, R, static_cast<const int32_t *>(L.agg.p), cnt.p);
-            PFEM_TRY(amg_exclusive_sum(s, temp, cnt.p, L.mem_ptr.p, nc_loc + 1));
-            hipLaunchKernelGGL(k_amg_iota, dim3(grid_for(R)), dim3(kBlock), 0, s->stream, R, idx.p);
-            size_t tb = 0;
-            const int ni = static_cast<int>(R);
-            PFEM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, L.agg.p, skey.p, idx.p, L.mem_idx.p, ni, 0, 32, s->stream));
-            if (tb > temp.n) { PFEM_HIP(hipStreamSynchronize(s->stream)); PFEM_TRY(temp.alloc(tb)); }
-            PFEM_HIP(hipcub::DeviceRadixSort::SortPairs(temp.p, tb, L.agg.p, skey.p, idx.p, L.mem_idx.p, ni, 0, 32, s->stream));
-            PFEM_HIP(hipStreamSynchronize(s->stream));
-        }
         phase(l, "coarse dofs + member lists");
-        // ---- coarse pattern and the maps of the numeric Galerkin product: (coarse row, coarse col, fine slot) triples, sorted.
-        // (A formulation by coarse rows -- one thread per coarse row, its column set and its sums in LDS, the fine matrix read in
-        // its own order, no sort -- was built and measured in round 3: numeric phase 3.96 instead of 2.28 ms at config 3, the
-        // thread's chain of dependent loads over its 8 member rows is latency-bound.  Dropped.)
-        {
-            DevBuf<uint64_t> &keys = W.keys, &skeys = W.skeys;
-            DevBuf<uint64_t> ukeys;                       // (as long as the coarse matrix has entries: exact)
-            DevBuf<int32_t> &slots = W.slots;
-            PFEM_TRY(keys.reserve(static_cast<size_t>(L.stored)));
-            PFEM_TRY(slots.reserve(static_cast<size_t>(L.stored)));
-            PFEM_HIP(hipMemsetAsync(keys.p, 0xff, sizeof(uint64_t) * static_cast<size_t>(L.stored), s->stream));   // slots of ghost rows
-            PFEM_HIP(hipMemsetAsync(slots.p, 0, sizeof(int32_t) * static_cast<size_t>(L.stored), s->stream));
-            const SellDev Ar = amg_sell(s, L, R);
-            hipLaunchKernelGGL(k_amg_emit_rap_keys, dim3(grid_for(Ar.n_slices * 64)), dim3(kBlock), 0, s->stream, Ar,
-                               static_cast<const int32_t *>(L.agg.p), static_cast<int32_t>(R), keys.p, slots.p);
-            PFEM_TRY(check_kernel("k_amg_emit_rap_keys"));
-            PFEM_TRY(skeys.reserve(static_cast<size_t>(L.stored)));
-            PFEM_TRY(L.src_slot.alloc(static_cast<size_t>(L.stored)));
-            const int ni = static_cast<int>(L.stored);
-            size_t tb = 0;
-            PFEM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys.p, skeys.p, slots.p, L.src_slot.p, ni, 0, 64, s->stream));
-            if (tb > temp.n) { PFEM_HIP(hipStreamSynchronize(s->stream)); PFEM_TRY(temp.alloc(tb)); }
-            PFEM_HIP(hipcub::DeviceRadixSort::SortPairs(temp.p, tb, keys.p, skeys.p, slots.p, L.src_slot.p, ni, 0, 64, s->stream));
-            PFEM_HIP(hipStreamSynchronize(s->stream));
-            int64_t nnz_c = 0;
-            PFEM_TRY(amg_unique_runs(s, W, skeys.p, L.stored, ukeys, L.src_ptr, &nnz_c));
-            if (nnz_c > 0) {      // the padding entries collapse into one sentinel run at the end: dropped (its slots are never read)
-                uint64_t last = 0;
-                // (on the solver's stream: the scatter that wrote ukeys is still in flight, and no hipFree synchronises for us any more)
-                PFEM_HIP(hipMemcpyAsync(&last, ukeys.p + (nnz_c - 1), sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
-                PFEM_HIP(hipStreamSynchronize(s->stream));
-                if (last == ~0ull) --nnz_c;
-            }
-            L.nnz_c = nnz_c;
-            PFEM_TRY(amg_sell_from_keys(s, W, ukeys.p, nnz_c, C));
-            PFEM_TRY(L.dst_slot.alloc(static_cast<size_t>(std::max<int64_t>(nnz_c, 1))));
-            hipLaunchKernelGGL(k_amg_dst_slots, dim3(grid_for(nnz_c)), dim3(kBlock), 0, s->stream, nnz_c, static_cast<const uint64_t *>(ukeys.p),
-                               static_cast<const int64_t *>(C.rowptr.p), static_cast<const int64_t *>(C.slice_off.p), L.dst_slot.p);
-            PFEM_TRY(check_kernel("k_amg_dst_slots"));
-            PFEM_HIP(hipStreamSynchronize(s->stream));
-        }
+        PFEM_TRY(amg_level_maps(s, W, L, *Cp, R));
         phase(l, "Galerkin maps + coarse pattern");
-        if (coupled) PFEM_TRY(amg_agree(s, C.stored > INT_MAX ? PFEM_ERR_ARG : PFEM_OK));
-        else if (C.stored > INT_MAX) return PFEM_ERR_ARG;
+        if (coupled) PFEM_TRY(amg_agree(s, Cp->stored > INT_MAX ? PFEM_ERR_ARG : PFEM_OK));
+        else if (Cp->stored > INT_MAX) return PFEM_ERR_ARG;
         M.lev.push_back(std::move(Cp));
         // the next level's strength graph needs this level's VALUES: one numeric product right away
-        {
-            AmgLevel &Cn = *M.lev.back();
-            amg_galerkin(s, L, Cn, A);
-            PFEM_TRY(check_kernel("k_amg_galerkin (symbolic)"));
-        }
+        amg_galerkin(s, L, *M.lev.back(), A);
+        PFEM_TRY(check_kernel("k_amg_galerkin (symbolic)"));
         n_global = nc_global;
-        // small enough for every rank to hold it whole: the rest of the hierarchy is replicated
-        if (coupled && n_global > kAmgDense && n_global <= static_cast<double>(replicate_rows)) {
-            PFEM_TRY(amg_replicate(s, M, W, *M.lev.back(), static_cast<int64_t>(n_global), overlap));
-            phase(l, "replicated levels");
-            break;
-        }
+        PFEM_TRY(amg_replicate_rest(s, M, W, coupled, n_global, overlap, phase, l, &replicated));
+        if (replicated) break;
     }
     M.n_last_global = coupled ? static_cast<int64_t>(n_global) : M.lev.back()->n;
     return PFEM_OK;
@@ -2582,7 +2593,7 @@ int amg_symbolic(pfem_solver *s, bool multi, bool overlap)
     if (!s->amg) return PFEM_ERR_NOMEM;
     Amg &M = *s->amg;
     const auto t0 = std::chrono::steady_clock::now();
-    const bool verbose = std::getenv("PFEM_AMG_VERBOSE") != nullptr;
+    const bool verbose = amg_verbose();
     const size_t malloc_calls0 = dev_pool().st_malloc_calls;         // (PFEM_POOL_VERBOSE: what the phase spent inside hipMalloc)
     const size_t malloc_bytes0 = dev_pool().st_malloc;
     const double malloc_ms0 = dev_pool().st_malloc_ms;

@@ -13,6 +13,16 @@ struct AmgPlan {
     DevBuf<int32_t> d_row_sh;             // [n_loc] index of every local dof among the plan's shared dofs, -1: not shared (fused pack / unpack)
 };
 
+// how a level's aggregates were formed; the numbers are what pfem_solver_amg_aggregation hands out
+enum AmgAggKind : int {
+    kAggNone = 0,               // the last level
+    kAggBricks = 1,             // bricks in one step
+    kAggNodeBricks = 2,         // node bricks in one step
+    kAggSplitBricks = 3,        // bricks split between their owners
+    kAggLatticePasses = 4,      // pairing passes on the lattice
+    kAggMatching = 5,           // matching on the strength graph
+};
+
 struct AmgLevel {
     int64_t n = 0, n_slices = 0, stored = 0, nnz = 0;
     // several ranks, coupled hierarchy: the level's matrix has n_loc >= n rows -- the n dofs this rank owns (the domain of
@@ -60,8 +70,7 @@ struct AmgLevel {
     std::vector<double> lat_coord;        // [3 x 1024] coordinate of every position (a brick sits at its lowest corner): the corners a level
                                           // needs when it leaves the brick path (xyz below) come from here instead of travelling down the levels
     DevBuf<double> xyz;                   // coupled hierarchy with a lattice: [3 x n_nodes] a corner of every node's aggregate (see k_amg_xyz_min)
-    // how this level's aggregates were formed (pfem_solver_amg_aggregation): 0 none (last level), 1 bricks in one step, 2 node bricks
-    // in one step, 3 bricks split between their owners, 4 pairing passes on the lattice, 5 matching on the strength graph
+    // how this level's aggregates were formed (pfem_solver_amg_aggregation reports the numbers; AmgAggKind below)
     int agg_kind = 0;
     // transfer to the next level (piecewise-constant prolongation)
     int64_t nc = 0;
