@@ -117,6 +117,18 @@ int pfem_elast_tria_ke(const double xNode[3], const double yNode[3],
  * triangle); zNode may be NULL in 2-D; any output may be NULL.  PFEM_ERR_NEG_JAC for an inverted element.                 */
 int pfem_elem_post(int kind, const double *xNode, const double *yNode, const double *zNode /* NULL in 2-D */,
                    const double *elemData, const double *valC, double *grad, double *flux, double *scalar, double *fint);
+/* The scalar of pfem_elem_post evaluated on ANY flux / stress vector flux[ng] of the kind, in its stored Voigt order (the
+ * recovered nodal values of pfem_post_nodal_recovery): |q|_2, von Mises, the plane-stress form above.                        */
+int pfem_post_scalar(int kind, const double *flux, double *scalar);
+/* One element's share of the Zienkiewicz-Zhu indicator.  nodal_flux[a*ng + c]: recovered values at the element's nodes; with
+ * f = flux and V = dvol of pfem_elem_post (volume; area; area x thickness for PFEM_ELAST_TRIA), d_ac = nodal_flux[a*ng+c] - f_c
+ * and d the space dimension
+ *   eta2       = V / ((d+1)(d+2)) sum_c [ sum_a d_ac^2 + (sum_a d_ac)^2 ]   -- the exact integral of |sigma* - sigma_h|^2 over the
+ *                simplex, sigma* interpolated linearly from the nodes (P1 mass matrix V (1 + delta_ab) / ((d+1)(d+2)))
+ *   flux_norm2 = V sum_c f_c^2
+ * plain Euclidean sums over the ng stored components.  Either output may be NULL.  PFEM_ERR_NEG_JAC for an inverted element.  */
+int pfem_elem_recovery_error(int kind, const double *xNode, const double *yNode, const double *zNode, const double *elemData,
+                             const double *valC, const double *nodal_flux, double *eta2, double *flux_norm2);
 
 /* ========================================================================= */
 /* 2. driver bookkeeping, host, integer-exact (tetrapoissonparallelimpl1.F)   */
@@ -182,6 +194,16 @@ int pfem_text_table_parse(const char *buf, int64_t len, int64_t rows, int cols, 
 int pfem_write_vtk(const char *path, int ndim, int64_t nElem, int64_t nNode, int npElem, int ndof,
                    const double *coords, const int32_t *conn, const int32_t *elem_procid,
                    const double *soln);
+/* pfem_write_vtk's file with further arrays: n_cell cell arrays after `procid` inside CELL_DATA, n_point point arrays after
+ * `solution` inside POINT_DATA.  Array k has *_ncomp[k] components per item, laid out data[i*ncomp + c]:
+ *   1: "SCALARS name float 1" + "LOOKUP_TABLE default";  3: "VECTORS name float";  9: "TENSORS name float", three rows of three
+ *   per item and a blank line;  any other count: PFEM_ERR_ARG.  Names may not be empty or contain whitespace (PFEM_ERR_ARG).
+ * The new arrays are written as %16.8E, one item per line (F12.6 would print a strain of 1e-7 as zero); coords, procid and
+ * solution keep the reference's formats.  With n_cell = n_point = 0 the file is pfem_write_vtk's, byte for byte.           */
+int pfem_write_vtk_fields(const char *path, int ndim, int64_t nElem, int64_t nNode, int npElem, int ndof,
+                          const double *coords, const int32_t *conn, const int32_t *elem_procid, const double *soln,
+                          int n_cell, const char *const *cell_name, const int *cell_ncomp, const double *const *cell_data,
+                          int n_point, const char *const *point_name, const int *point_ncomp, const double *const *point_data);
 /* temp.dat of the drivers: one record per free dof, " ii ind value" (tetrapoissonparallelimpl1.F:935-942) or, with
  * ii = ind = NULL, the value alone (tetraelasticityparallelimpl1.F:1031-1046); values as %.16E.  Formatted on all host
  * threads like pfem_write_vtk.                                                                                      */
@@ -352,6 +374,24 @@ int pfem_post_elements(pfem_solver *s, const double *elemData, const double *u_n
  * Needs the pattern.                                                                                                       */
 int pfem_post_nodal_forces(pfem_solver *s, const double *elemData, const double *timeData,
                            const double *u_nodal, double *R);
+#define PFEM_POST_FLUX 0
+#define PFEM_POST_GRAD 1
+/* Recovery of a nodal field from the piecewise-constant element field by volume-weighted averaging:
+ *   nodal[node*ng + c] = sum_e w_e f_c(e) / sum_e w_e over the elements at the node, w_e = dvol of pfem_elem_post (volume; area;
+ *   area x thickness for PFEM_ELAST_TRIA), f = flux (field == PFEM_POST_FLUX) or grad (PFEM_POST_GRAD) of pfem_elem_post;
+ *   nodal_scalar[node] = pfem_post_scalar of the recovered flux (PFEM_POST_FLUX only, else it must be NULL: PFEM_ERR_ARG);
+ *   weight[node] = sum_e w_e.
+ * A node without elements gets zeros.  Any output may be NULL.  With the gather form of the assembly in effect one thread per
+ * node walks its incident elements in ascending element order (no atomics, the same bits in every run; hub nodes by a
+ * restricted atomic pass and a division); otherwise one thread per element with f64 atomics, then the division.  Needs the
+ * pattern (the incidence lists).                                                                                           */
+int pfem_post_nodal_recovery(pfem_solver *s, const double *elemData, const double *u_nodal, int field,
+                             double *nodal, double *nodal_scalar, double *weight);
+/* Zienkiewicz-Zhu error indicator: eta2[e] = pfem_elem_recovery_error of every element against the recovered nodal flux (the
+ * recovery above runs on the device and its result stays there), and the sums of eta2 and flux_norm2 over all elements
+ * (per-block partials in fixed order: reproducible where the recovery is).  Any output may be NULL.                        */
+int pfem_post_error_indicator(pfem_solver *s, const double *elemData, const double *u_nodal,
+                              double *eta2, double *eta2_total, double *flux_norm2_total);
 /* KSPBuildResidual / -ksp_monitor_true_residual: |b - K x|_2 and |b|_2 over the owned rows for the x of the last solve, K x by
  * the SpMV form in effect (pfem_solver_solve's rnorm is |M^-1 r| of the CG recurrence).  PFEM_ERR_STATE before a solve.     */
 int pfem_solver_true_residual(pfem_solver *s, double *rnorm2, double *bnorm2);

@@ -29,6 +29,8 @@ int pfem_solver_set_assembly_mode(pfem_solver *s, int mode);
 int pfem_solver_assembly_info(pfem_solver *s, int *gather_form, int *hub_nodes, int *block_threads, int64_t *lds_bytes);
 /* kernel time (HIP events around the kernels; host copies excluded) of the last pfem_post_elements / pfem_post_nodal_forces call */
 int pfem_post_timings(pfem_solver *s, double *elements_ms, double *nodal_forces_ms);
+/* the same for the last pfem_post_nodal_recovery / pfem_post_error_indicator call (the indicator's time includes its recovery) */
+int pfem_post_recovery_timings(pfem_solver *s, double *recovery_ms, double *indicator_ms);
 /* Matrix encoding streamed by the SpMV.  AUTO uses 16-bit gaps between the ascending columns of a
  * row (4 + 2 B per entry instead of 4 B) whenever every gap of the pattern fits, and on top of that
  * serves consecutive rows with identical column sets (the dof rows of a node) from one lane with a

@@ -67,6 +67,8 @@ SIGNATURES = {
     "pfem_elast_tet_ke": [_P] * 8,
     "pfem_elast_tria_ke": [_P] * 7,
     "pfem_elem_post": [_I] + [_P] * 9,
+    "pfem_post_scalar": [_I, _P, _P],
+    "pfem_elem_recovery_error": [_I] + [_P] * 8,
     "pfem_gen_box_tets": [_D, _D, _I, _D, _D, _I, _D, _D, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "pfem_dof_numbering": [_L, _I, _L, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "pfem_renumber_mesh": [_L, _I, _L, _I, _P, _P, _P, _P, _P, _P],
@@ -78,6 +80,7 @@ SIGNATURES = {
     "pfem_text_table_shape": [C.c_char_p, _L, _P, _P],
     "pfem_text_table_parse": [C.c_char_p, _L, _L, _I, _P],
     "pfem_write_vtk": [C.c_char_p, _I, _L, _L, _I, _I, _P, _P, _P, _P],
+    "pfem_write_vtk_fields": [C.c_char_p, _I, _L, _L, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P],
     "pfem_write_temp_dat": [C.c_char_p, _L, _P, _P, _P],
     "pfem_solver_create": [_P, _L, _L, _L, _P, _P, _I],
     "pfem_solver_destroy": [_P],
@@ -139,8 +142,11 @@ SIGNATURES = {
     "pfem_rhs_add_values": [_P, _L, _P, _P],
     "pfem_post_elements": [_P] * 6,
     "pfem_post_nodal_forces": [_P] * 5,
+    "pfem_post_nodal_recovery": [_P, _P, _P, _I, _P, _P, _P],
+    "pfem_post_error_indicator": [_P] * 6,
     "pfem_solver_true_residual": [_P, _P, _P],
     "pfem_post_timings": [_P, _P, _P],
+    "pfem_post_recovery_timings": [_P, _P, _P],
     "pfem_matrix_info": [_P, _P, _P, _P, _P],
     "pfem_get_local_to_global": [_P, _P],
     "pfem_get_csr": [_P, _P, _P, _P],

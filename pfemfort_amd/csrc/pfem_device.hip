@@ -696,6 +696,7 @@ struct pfem_solver {
     double last_rnorm = 0.0;
     bool solved = false;       // d_x holds the x of a solve of the current pattern (post-processing with u = NULL, true residual)
     double post_elements_ms = 0.0, post_forces_ms = 0.0;   // kernel time of the last pfem_post_* call (pfem_post_timings)
+    double post_recovery_ms = 0.0, post_indicator_ms = 0.0;   // ... of the last recovery / indicator call (pfem_post_recovery_timings)
     int hist_cap = 0;
 
     // compat (host staging of MatSetValues / VecSetValues)
@@ -3212,6 +3213,98 @@ int post_nodal_field(pfem_solver *s, const double *u_nodal, DevBuf<double> &u, c
     return check_kernel("k_post_nodal");
 }
 
+// mesh, pattern and rank count that a pass over the incidence lists needs, in the words of pfem_post_nodal_forces
+int post_needs_pattern(const pfem_solver *s, const char *who)
+{
+    PFEM_TRY(post_one_rank(s, who));
+    if (!s->have_mesh) {
+        set_last_error(std::string(who) + ": no mesh on the device (the MatSetValues path has none)");
+        return PFEM_ERR_STATE;
+    }
+    if (!s->have_pattern) {
+        set_last_error(std::string(who) + ": build the pattern first");
+        return PFEM_ERR_STATE;
+    }
+    return PFEM_OK;
+}
+
+// Launches of the nodal recovery (enqueued only): nodal[node * ng + c], weight[node] and -- nscalar != nullptr -- the scalar of the
+// recovered vector, all in the DEVICE's node order.  Gather form: one thread per node, then the hub nodes by the restricted
+// element pass and the division; scatter form: zero, element pass over all nodes, division.
+int post_recovery_launch(pfem_solver *s, const ElemPrm &prm, const double *up, int use_grad, double *nodal, double *nscalar, double *weight)
+{
+    const MeshDev &m = s->mesh;
+    const int64_t nn = m.nNode;
+    const int ng = post_components(m.kind);
+    const bool gather = m.nElem > 0 && s->assembly_mode == PFEM_ASSEMBLY_GATHER && s->have_incidence && s->d_inc_rec.p;
+    const uint8_t *hubs = (gather && s->n_hubs > 0) ? s->d_node_hub.p : nullptr;
+    if (gather) {
+        const dim3 grid(grid_for(nn)), block(kBlock);
+        const int64_t *ip = s->d_inc_ptr.p;
+        const int32_t *ic = s->d_inc_cnt.p;
+        const int4 *irec = s->d_inc_rec.p;
+#define PFEM_POST(KIND) hipLaunchKernelGGL(k_post_recovery_gather<KIND>, grid, block, 0, s->stream, m, prm, ip, ic, irec, hubs, up, use_grad, nodal, nscalar, weight, s->d_err.p)
+        switch (m.kind) {
+        case PFEM_POISSON_TRIA: PFEM_POST(PFEM_POISSON_TRIA); break;
+        case PFEM_POISSON_TET: PFEM_POST(PFEM_POISSON_TET); break;
+        case PFEM_ELAST_TET: PFEM_POST(PFEM_ELAST_TET); break;
+        case PFEM_POISSON_TRIA_INLINE: PFEM_POST(PFEM_POISSON_TRIA_INLINE); break;
+        case PFEM_ELAST_TRIA: PFEM_POST(PFEM_ELAST_TRIA); break;
+        }
+#undef PFEM_POST
+        PFEM_TRY(check_kernel("k_post_recovery_gather"));
+        if (!hubs) return PFEM_OK;
+    } else {
+        PFEM_HIP(hipMemsetAsync(nodal, 0, sizeof(double) * static_cast<size_t>(std::max<int64_t>(nn * ng, 1)), s->stream));
+        PFEM_HIP(hipMemsetAsync(weight, 0, sizeof(double) * static_cast<size_t>(std::max<int64_t>(nn, 1)), s->stream));
+    }
+    if (m.nElem > 0) {
+        const dim3 grid(grid_for(m.nElem)), block(kBlock);
+#define PFEM_POST(KIND) hipLaunchKernelGGL(k_post_recovery_scatter<KIND>, grid, block, 0, s->stream, m, prm, hubs, up, use_grad, nodal, weight, s->d_err.p)
+        switch (m.kind) {
+        case PFEM_POISSON_TRIA: PFEM_POST(PFEM_POISSON_TRIA); break;
+        case PFEM_POISSON_TET: PFEM_POST(PFEM_POISSON_TET); break;
+        case PFEM_ELAST_TET: PFEM_POST(PFEM_ELAST_TET); break;
+        case PFEM_POISSON_TRIA_INLINE: PFEM_POST(PFEM_POISSON_TRIA_INLINE); break;
+        case PFEM_ELAST_TRIA: PFEM_POST(PFEM_ELAST_TRIA); break;
+        }
+#undef PFEM_POST
+        PFEM_TRY(check_kernel("k_post_recovery_scatter"));
+    }
+    {
+        const dim3 grid(grid_for(nn)), block(kBlock);
+        const double *w = weight;
+#define PFEM_POST(KIND) hipLaunchKernelGGL(k_post_recovery_divide<KIND>, grid, block, 0, s->stream, nn, hubs, w, nodal, nscalar)
+        switch (m.kind) {
+        case PFEM_POISSON_TRIA: PFEM_POST(PFEM_POISSON_TRIA); break;
+        case PFEM_POISSON_TET: PFEM_POST(PFEM_POISSON_TET); break;
+        case PFEM_ELAST_TET: PFEM_POST(PFEM_ELAST_TET); break;
+        case PFEM_POISSON_TRIA_INLINE: PFEM_POST(PFEM_POISSON_TRIA_INLINE); break;
+        case PFEM_ELAST_TRIA: PFEM_POST(PFEM_ELAST_TRIA); break;
+        }
+#undef PFEM_POST
+    }
+    return check_kernel("k_post_recovery_divide");
+}
+
+// a per-node device array [node * nc + c] in the device's node order to the host in the CALLER's node numbering
+int post_nodes_to_caller(pfem_solver *s, const double *dev, int nc, double *out)
+{
+    const int64_t nn = s->mesh.nNode;
+    if (s->h_niperm.empty()) {
+        PFEM_HIP(hipMemcpyAsync(out, dev, sizeof(double) * static_cast<size_t>(nn * nc), hipMemcpyDeviceToHost, s->stream));
+        PFEM_HIP(hipStreamSynchronize(s->stream));
+        return PFEM_OK;
+    }
+    std::vector<double> tmp(static_cast<size_t>(nn * nc));
+    PFEM_HIP(hipMemcpyAsync(tmp.data(), dev, sizeof(double) * static_cast<size_t>(nn * nc), hipMemcpyDeviceToHost, s->stream));
+    PFEM_HIP(hipStreamSynchronize(s->stream));
+    for (int64_t i = 0; i < nn; ++i)
+        for (int c = 0; c < nc; ++c)
+            out[static_cast<int64_t>(s->h_niperm[static_cast<size_t>(i)]) * nc + c] = tmp[static_cast<size_t>(i * nc + c)];
+    return PFEM_OK;
+}
+
 }  // namespace
 
 extern "C" int pfem_post_elements(pfem_solver *s, const double *elemData, const double *u_nodal, double *grad, double *flux, double *scalar)
@@ -3332,6 +3425,93 @@ extern "C" int pfem_post_nodal_forces(pfem_solver *s, const double *elemData, co
     return PFEM_OK;
 }
 
+// Recovered nodal flux / stress (or gradient / strain): the volume-weighted average of the element values at every node
+extern "C" int pfem_post_nodal_recovery(pfem_solver *s, const double *elemData, const double *u_nodal, int field, double *nodal,
+                                        double *nodal_scalar, double *weight)
+{
+    if (!s || (field != PFEM_POST_FLUX && field != PFEM_POST_GRAD)) return PFEM_ERR_ARG;
+    if (field == PFEM_POST_GRAD && nodal_scalar) {
+        set_last_error("pfem_post_nodal_recovery: the scalar is defined for the flux / stress only");
+        return PFEM_ERR_ARG;
+    }
+    PFEM_TRY(post_needs_pattern(s, "pfem_post_nodal_recovery"));
+    const MeshDev &m = s->mesh;
+    if (m.kind != PFEM_POISSON_TRIA_INLINE && !elemData) return PFEM_ERR_ARG;
+    PFEM_TRY(use_device(s));
+    DevBuf<double> u, dn, dsc, dw;
+    PFEM_TRY(post_nodal_field(s, u_nodal, u, "pfem_post_nodal_recovery"));
+    const ElemPrm prm = make_prm(elemData, nullptr, m.kind);
+    const int ng = post_components(m.kind);
+    const size_t nn = static_cast<size_t>(m.nNode);
+    PFEM_TRY(dn.alloc(std::max<size_t>(nn * ng, 1)));
+    PFEM_TRY(dw.alloc(std::max<size_t>(nn, 1)));
+    if (nodal_scalar) PFEM_TRY(dsc.alloc(std::max<size_t>(nn, 1)));
+    PFEM_HIP(hipMemsetAsync(s->d_err.p, 0, sizeof(int), s->stream));
+    PFEM_HIP(hipEventRecord(s->ev0, s->stream));
+    PFEM_TRY(post_recovery_launch(s, prm, u.p, field == PFEM_POST_GRAD, dn.p, dsc.p, dw.p));
+    PFEM_HIP(hipEventRecord(s->ev1, s->stream));
+    int err = 0;
+    PFEM_TRY(fetch_err(s, &err));
+    PFEM_TRY(elapsed(s, &s->post_recovery_ms));
+    if (err) return err;
+    if (nodal) PFEM_TRY(post_nodes_to_caller(s, dn.p, ng, nodal));
+    if (nodal_scalar) PFEM_TRY(post_nodes_to_caller(s, dsc.p, 1, nodal_scalar));
+    if (weight) PFEM_TRY(post_nodes_to_caller(s, dw.p, 1, weight));
+    return PFEM_OK;
+}
+
+// Zienkiewicz-Zhu indicator: the recovery above (its result stays on the device), then one pass over the elements
+extern "C" int pfem_post_error_indicator(pfem_solver *s, const double *elemData, const double *u_nodal, double *eta2, double *eta2_total,
+                                         double *flux_norm2_total)
+{
+    if (!s) return PFEM_ERR_ARG;
+    PFEM_TRY(post_needs_pattern(s, "pfem_post_error_indicator"));
+    const MeshDev &m = s->mesh;
+    if (m.kind != PFEM_POISSON_TRIA_INLINE && !elemData) return PFEM_ERR_ARG;
+    PFEM_TRY(use_device(s));
+    DevBuf<double> u, dn, dw, de, part;
+    PFEM_TRY(post_nodal_field(s, u_nodal, u, "pfem_post_error_indicator"));
+    const ElemPrm prm = make_prm(elemData, nullptr, m.kind);
+    const int ng = post_components(m.kind);
+    const size_t nn = static_cast<size_t>(m.nNode), ne = static_cast<size_t>(m.nElem);
+    PFEM_TRY(dn.alloc(std::max<size_t>(nn * ng, 1)));
+    PFEM_TRY(dw.alloc(std::max<size_t>(nn, 1)));
+    if (eta2) PFEM_TRY(de.alloc(std::max<size_t>(ne, 1)));
+    PFEM_TRY(part.alloc(2 * kMaxGrid + 2));
+    PFEM_HIP(hipMemsetAsync(s->d_err.p, 0, sizeof(int), s->stream));
+    PFEM_HIP(hipEventRecord(s->ev0, s->stream));
+    PFEM_TRY(post_recovery_launch(s, prm, u.p, 0, dn.p, nullptr, dw.p));
+    {
+        const unsigned gv = vec_grid(m.nElem);
+        const dim3 grid(gv), block(kBlock);
+        const double *up = u.p, *np = dn.p;
+#define PFEM_POST(KIND) hipLaunchKernelGGL(k_post_indicator<KIND>, grid, block, 0, s->stream, m, prm, up, np, de.p, part.p, part.p + kMaxGrid, s->d_err.p)
+        switch (m.kind) {
+        case PFEM_POISSON_TRIA: PFEM_POST(PFEM_POISSON_TRIA); break;
+        case PFEM_POISSON_TET: PFEM_POST(PFEM_POISSON_TET); break;
+        case PFEM_ELAST_TET: PFEM_POST(PFEM_ELAST_TET); break;
+        case PFEM_POISSON_TRIA_INLINE: PFEM_POST(PFEM_POISSON_TRIA_INLINE); break;
+        case PFEM_ELAST_TRIA: PFEM_POST(PFEM_ELAST_TRIA); break;
+        }
+#undef PFEM_POST
+        PFEM_TRY(check_kernel("k_post_indicator"));
+        hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, s->stream, static_cast<const double *>(part.p),
+                           static_cast<const double *>(part.p + kMaxGrid), static_cast<int>(gv), part.p + 2 * kMaxGrid, static_cast<const CgCtl *>(nullptr));
+        PFEM_TRY(check_kernel("k_reduce_partials"));
+    }
+    PFEM_HIP(hipEventRecord(s->ev1, s->stream));
+    double h[2] = {0.0, 0.0};
+    if (eta2) PFEM_HIP(hipMemcpyAsync(eta2, de.p, sizeof(double) * ne, hipMemcpyDeviceToHost, s->stream));
+    PFEM_HIP(hipMemcpyAsync(h, part.p + 2 * kMaxGrid, 2 * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    int err = 0;
+    PFEM_TRY(fetch_err(s, &err));
+    PFEM_TRY(elapsed(s, &s->post_indicator_ms));
+    if (err) return err;
+    if (eta2_total) *eta2_total = h[0];
+    if (flux_norm2_total) *flux_norm2_total = h[1];
+    return PFEM_OK;
+}
+
 // |b - K x|_2 and |b|_2 over the owned rows for the x of the last solve, K x by the SpMV form in effect (KSPBuildResidual /
 // -ksp_monitor_true_residual: the CG's own rnorm is |M^-1 r| of its recurrence)
 extern "C" int pfem_solver_true_residual(pfem_solver *s, double *rnorm2, double *bnorm2)
@@ -3371,6 +3551,15 @@ extern "C" int pfem_post_timings(pfem_solver *s, double *elements_ms, double *no
     if (!s) return PFEM_ERR_ARG;
     if (elements_ms) *elements_ms = s->post_elements_ms;
     if (nodal_forces_ms) *nodal_forces_ms = s->post_forces_ms;
+    return PFEM_OK;
+}
+
+// kernel time of the last pfem_post_nodal_recovery / pfem_post_error_indicator call (the indicator's includes its own recovery)
+extern "C" int pfem_post_recovery_timings(pfem_solver *s, double *recovery_ms, double *indicator_ms)
+{
+    if (!s) return PFEM_ERR_ARG;
+    if (recovery_ms) *recovery_ms = s->post_recovery_ms;
+    if (indicator_ms) *indicator_ms = s->post_indicator_ms;
     return PFEM_OK;
 }
 

@@ -671,4 +671,50 @@ PFEM_HD bool elem_nodal_forces(int kind, const double *x, const double *y, const
     return true;
 }
 
+// ---------------------------------------------------------------------------
+// Nodal recovery and the Zienkiewicz-Zhu indicator (pfem_post_nodal_recovery / pfem_post_error_indicator)
+// ---------------------------------------------------------------------------
+// The scalar of elem_post, evaluated on ANY flux / stress vector in the kind's stored Voigt order (the recovered nodal values):
+// |q|_2, von Mises, the plane-stress form.  The expressions are elem_post's, term for term (|q| of -q is |q|'s own bits).
+PFEM_HD double post_scalar(int kind, const double *f)
+{
+    switch (kind) {
+    case 2: return sqrt((f[0] * f[0] + f[1] * f[1]) + f[2] * f[2]);
+    case 3: {
+        const double d0 = f[0] - f[1], d1 = f[1] - f[2], d2 = f[2] - f[0];
+        return sqrt(0.5 * ((d0 * d0 + d1 * d1) + d2 * d2) + 3.0 * ((f[3] * f[3] + f[4] * f[4]) + f[5] * f[5]));
+    }
+    case 5: return sqrt(((f[0] * f[0] - f[0] * f[1]) + f[1] * f[1]) + 3.0 * (f[2] * f[2]));
+    default: return sqrt(f[0] * f[0] + f[1] * f[1]);
+    }
+}
+
+// One element's share of the ZZ indicator.  sigma* is interpolated linearly from nodal[a * ng + c], sigma_h = flux of elem_post is
+// constant, so with d_ac = nodal[a * ng + c] - f_c and the P1 mass matrix V (1 + delta_ab) / ((d+1)(d+2)) of a simplex in d
+// dimensions the integral of |sigma* - sigma_h|^2 is exactly
+//     eta2 = V / ((d+1)(d+2)) sum_c [ sum_a d_ac^2 + (sum_a d_ac)^2 ],        fnorm2 = V sum_c f_c^2,
+// a plain Euclidean sum over the ng stored Voigt components (no D^-1 weighting; shear components count once, as stored).  V is
+// elem_post's dvol (area x thickness for the plane-stress triangle).  nodal == flux at every node gives eta2 = 0.0 exactly.
+PFEM_HD bool elem_recovery_error(int kind, const double *x, const double *y, const double *z, const double *ed, const double *valC,
+                                 const double *nodal, double &eta2, double &fnorm2)
+{
+    double grad[6], flux[6], fint[12], scalar, dvol;
+    if (!elem_post(kind, x, y, z, ed, valC, grad, flux, scalar, fint, dvol)) return false;
+    const int ng = post_components(kind), npe = (kind == 2 || kind == 3) ? 4 : 3;
+    double e2 = 0.0, f2 = 0.0;
+    for (int c = 0; c < ng; ++c) {
+        double sq = 0.0, sm = 0.0;
+        for (int a = 0; a < npe; ++a) {
+            const double d = nodal[a * ng + c] - flux[c];
+            sq = sq + d * d;
+            sm = sm + d;
+        }
+        e2 = e2 + (sq + sm * sm);
+        f2 = f2 + flux[c] * flux[c];
+    }
+    eta2 = dvol / static_cast<double>(npe * (npe + 1)) * e2;
+    fnorm2 = dvol * f2;
+    return true;
+}
+
 }  // namespace pfem

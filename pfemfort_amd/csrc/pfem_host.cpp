@@ -8,6 +8,7 @@
 #include <omp.h>
 #endif
 #include <algorithm>
+#include <cctype>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -96,6 +97,28 @@ extern "C" int pfem_elem_post(int kind, const double *xNode, const double *yNode
     if (flux) std::copy(f, f + ng, flux);
     if (scalar) *scalar = sc;
     if (fint) std::copy(fi, fi + nsize, fint);
+    return PFEM_OK;
+}
+
+// The scalar of pfem_elem_post on any flux / stress vector of the kind (pfem_elem.hpp: post_scalar)
+extern "C" int pfem_post_scalar(int kind, const double *flux, double *scalar)
+{
+    if (!kind_valid(kind) || !flux || !scalar) return PFEM_ERR_ARG;
+    *scalar = post_scalar(kind, flux);
+    return PFEM_OK;
+}
+
+// One element's share of the ZZ indicator from recovered nodal fluxes nodal_flux[a * ng + c] (pfem_elem.hpp: elem_recovery_error)
+extern "C" int pfem_elem_recovery_error(int kind, const double *xNode, const double *yNode, const double *zNode, const double *elemData,
+                                        const double *valC, const double *nodal_flux, double *eta2, double *flux_norm2)
+{
+    if (!kind_valid(kind) || !xNode || !yNode || !valC || !nodal_flux) return PFEM_ERR_ARG;
+    if (kind_ndim(kind) == 3 && !zNode) return PFEM_ERR_ARG;
+    if (kind != PFEM_POISSON_TRIA_INLINE && !elemData) return PFEM_ERR_ARG;
+    double e2 = 0.0, f2 = 0.0;
+    if (!elem_recovery_error(kind, xNode, yNode, zNode, elemData, valC, nodal_flux, e2, f2)) return PFEM_ERR_NEG_JAC;
+    if (eta2) *eta2 = e2;
+    if (flux_norm2) *flux_norm2 = f2;
     return PFEM_OK;
 }
 
@@ -641,15 +664,54 @@ void emit_records(std::FILE *f, int64_t n, int max_rec, F fmt)
             if (used[t]) std::fwrite(bufs[t].data(), 1, used[t], f);
     }
 }
-}  // namespace
 
-extern "C" int pfem_write_vtk(const char *path, int ndim, int64_t nElem, int64_t nNode, int npElem, int ndof,
-                              const double *coords /*SoA [d*nNode+n]*/, const int32_t *conn /*SoA, 0-based*/,
-                              const int32_t *elem_procid, const double *soln /*[n*ndof+d]*/)
+// Further arrays of a CELL_DATA / POINT_DATA section: data[i * ncomp + c], "%16.8E" per value (the F12.6 of the reference's
+// arrays would print a strain of 1e-7 as zero), one item per line; a tensor takes three lines and a blank one.
+struct VtkArrays {
+    int n = 0;
+    const char *const *name = nullptr;
+    const int *ncomp = nullptr;
+    const double *const *data = nullptr;
+};
+
+bool vtk_arrays_valid(const VtkArrays &a)
+{
+    if (a.n < 0 || (a.n > 0 && (!a.name || !a.ncomp || !a.data))) return false;
+    for (int k = 0; k < a.n; ++k) {
+        if (a.ncomp[k] != 1 && a.ncomp[k] != 3 && a.ncomp[k] != 9) return false;
+        if (!a.data[k] || !a.name[k] || !a.name[k][0]) return false;
+        for (const char *c = a.name[k]; *c; ++c)
+            if (std::isspace(static_cast<unsigned char>(*c))) return false;
+    }
+    return true;
+}
+
+void emit_vtk_arrays(std::FILE *f, int64_t n, const VtkArrays &a)
+{
+    for (int k = 0; k < a.n; ++k) {
+        const int nc = a.ncomp[k];
+        const double *v = a.data[k];
+        if (nc == 1) std::fprintf(f, "SCALARS %s float 1\nLOOKUP_TABLE default\n", a.name[k]);
+        else std::fprintf(f, "%s %s float\n", nc == 3 ? "VECTORS" : "TENSORS", a.name[k]);
+        emit_records(f, n, 9 * 24 + 8, [&](char *p, int64_t i) {
+            char *q = p;
+            for (int c = 0; c < nc; ++c) {
+                q += std::snprintf(q, 24, "%16.8E", v[i * nc + c]);
+                if (c % 3 == 2 || nc == 1) *q++ = '\n';
+            }
+            if (nc == 9) *q++ = '\n';
+            return static_cast<int>(q - p);
+        });
+    }
+}
+
+int write_vtk_file(const char *path, int ndim, int64_t nElem, int64_t nNode, int npElem, int ndof, const double *coords,
+                   const int32_t *conn, const int32_t *elem_procid, const double *soln, const VtkArrays &cell, const VtkArrays &point)
 {
     if (!path || (ndim != 2 && ndim != 3) || nElem < 0 || nNode < 0 || npElem < 3 || ndof < 1 || !coords || !conn ||
         !elem_procid || !soln)
         return PFEM_ERR_ARG;
+    if (!vtk_arrays_valid(cell) || !vtk_arrays_valid(point)) return PFEM_ERR_ARG;
     int cell_type;                                               // writervtk.F:85-140
     if (ndim == 2) cell_type = npElem == 3 ? 5 : (npElem == 6 ? 22 : 9);
     else cell_type = npElem == 4 ? 10 : (npElem == 6 ? 13 : 12);
@@ -686,6 +748,7 @@ extern "C" int pfem_write_vtk(const char *path, int ndim, int64_t nElem, int64_t
     std::fprintf(f, "CELL_DATA%10lld\n", static_cast<long long>(nElem));
     std::fputs("SCALARS procid int 1\nLOOKUP_TABLE default\n", f);
     emit_records(f, nElem, 16, [&](char *p, int64_t e) { int k = fmt_int(p, 3, elem_procid[e]); p[k] = '\n'; return k + 1; });
+    emit_vtk_arrays(f, nElem, cell);
     std::fprintf(f, "POINT_DATA%10lld\n", static_cast<long long>(nNode));
     if (ndof == 1) {
         std::fputs("SCALARS solution float 1\nLOOKUP_TABLE default\n", f);
@@ -696,9 +759,32 @@ extern "C" int pfem_write_vtk(const char *path, int ndim, int64_t nElem, int64_t
             return triple(p, soln[n * ndof], soln[n * ndof + 1], ndof == 2 ? 0.0 : soln[n * ndof + 2]);
         });
     }
+    emit_vtk_arrays(f, nNode, point);
     const bool ok = std::fflush(f) == 0 && !std::ferror(f);
     std::fclose(f);
     return ok ? PFEM_OK : PFEM_ERR_ARG;
+}
+}  // namespace
+
+extern "C" int pfem_write_vtk(const char *path, int ndim, int64_t nElem, int64_t nNode, int npElem, int ndof,
+                              const double *coords /*SoA [d*nNode+n]*/, const int32_t *conn /*SoA, 0-based*/,
+                              const int32_t *elem_procid, const double *soln /*[n*ndof+d]*/)
+{
+    return write_vtk_file(path, ndim, nElem, nNode, npElem, ndof, coords, conn, elem_procid, soln, VtkArrays(), VtkArrays());
+}
+
+// pfem_write_vtk's file with further arrays: cell arrays after `procid` inside CELL_DATA, point arrays after `solution` inside
+// POINT_DATA (ncomp 1 SCALARS, 3 VECTORS, 9 TENSORS).  Without arrays the same bytes as pfem_write_vtk.
+extern "C" int pfem_write_vtk_fields(const char *path, int ndim, int64_t nElem, int64_t nNode, int npElem, int ndof,
+                                     const double *coords, const int32_t *conn, const int32_t *elem_procid, const double *soln,
+                                     int n_cell, const char *const *cell_name, const int *cell_ncomp, const double *const *cell_data,
+                                     int n_point, const char *const *point_name, const int *point_ncomp,
+                                     const double *const *point_data)
+{
+    VtkArrays cell, point;
+    cell.n = n_cell;  cell.name = cell_name;  cell.ncomp = cell_ncomp;  cell.data = cell_data;
+    point.n = n_point;  point.name = point_name;  point.ncomp = point_ncomp;  point.data = point_data;
+    return write_vtk_file(path, ndim, nElem, nNode, npElem, ndof, coords, conn, elem_procid, soln, cell, point);
 }
 
 // temp.dat of the drivers (tetrapoissonparallelimpl1.F:935-942: "ii, ind, value" per free dof; the elasticity driver

@@ -1694,6 +1694,134 @@ __global__ void __launch_bounds__(kBlock) k_post_forces_scatter(MeshDev m, ElemP
     }
 }
 
+// Nodal recovery nodal[n * NG + c] = sum_e w_e f_c(e) / sum_e w_e (w = dvol of elem_post, f = its flux, or its grad with use_grad),
+// gather form: k_post_forces_gather's walk over the node's own incidence records, ascending element id; w f_c and w accumulate
+// in registers (NG + 1 doubles), the thread divides and stores -- one writer per entry, no atomics, the same bits in every run.
+// A node without elements stores zeros.  Hub nodes have no records: zeros here, which k_post_recovery_scatter(only_nodes) and
+// k_post_recovery_divide(only_nodes) turn into their values.  Traffic per record: 16 B of record, (NPE - 1) (NDIM + NDOF)
+// doubles of the other nodes through L2; the node's own coordinates and values are loaded again with each record (L1 hits).
+template <int KIND>
+__global__ void __launch_bounds__(kBlock) k_post_recovery_gather(MeshDev m, ElemPrm prm, const int64_t *__restrict__ inc_ptr,
+                                                                  const int32_t *__restrict__ inc_cnt, const int4 *__restrict__ inc_rec,
+                                                                  const uint8_t *__restrict__ node_hub, const double *__restrict__ u,
+                                                                  int use_grad, double *__restrict__ nodal, double *__restrict__ nscalar,
+                                                                  double *__restrict__ weight, int *err)
+{
+    using P = PostKind<KIND>;
+    const int64_t n = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    if (n >= m.nNode) return;
+    double acc[P::NG], wsum = 0.0;
+#pragma unroll
+    for (int c = 0; c < P::NG; ++c) acc[c] = 0.0;
+    const int cnt = (node_hub && node_hub[n]) ? 0 : inc_cnt[n];
+    const int64_t beg = inc_ptr[n >> 6] + (n & 63), end = beg + 64LL * cnt;
+    for (int64_t t = beg; t < end; t += 64) {
+        const int4 rc = inc_rec[t];
+        const int a = static_cast<int>((static_cast<uint32_t>(rc.x) >> 31) | ((static_cast<uint32_t>(rc.y) >> 31) << 1));
+        const int o[3] = {rc.x & 0x7fffffff, rc.y & 0x7fffffff, rc.z};
+        int nd[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int i = 0; i < P::NPE; ++i) {
+            const int q = i < a ? i : (i > 0 ? i - 1 : 0);
+            nd[i] = (i == a) ? static_cast<int>(n) : o[q];
+        }
+        double x[4], y[4], z[4], valC[12], g[6], f[6], fint[12], sc, dvol;
+        post_load_elem<KIND>(m, nd, u, x, y, z, valC);
+        if (!elem_post(KIND, x, y, z, prm.ed, valC, g, f, sc, fint, dvol)) { atomicMax(err, PFEM_ERR_NEG_JAC); continue; }
+#pragma unroll
+        for (int c = 0; c < P::NG; ++c) acc[c] += dvol * (use_grad ? g[c] : f[c]);
+        wsum += dvol;
+    }
+    double r[P::NG];
+#pragma unroll
+    for (int c = 0; c < P::NG; ++c) {
+        r[c] = wsum != 0.0 ? acc[c] / wsum : 0.0;
+        nodal[n * P::NG + c] = r[c];
+    }
+    if (nscalar) nscalar[n] = post_scalar(KIND, r);
+    weight[n] = wsum;
+}
+
+// The numerators sum_e w_e f_c(e) into nodal and the weights sum_e w_e into weight (both zeroed by the caller; weight is never
+// NULL here), scatter form: one thread per element, f64 atomics.  only_nodes != nullptr: the hub pass of the gather form -- only
+// the entries of flagged nodes (zeroed by k_post_recovery_gather) are added.  k_post_recovery_divide finishes.
+template <int KIND>
+__global__ void __launch_bounds__(kBlock) k_post_recovery_scatter(MeshDev m, ElemPrm prm, const uint8_t *__restrict__ only_nodes,
+                                                                   const double *__restrict__ u, int use_grad, double *nodal,
+                                                                   double *weight, int *err)
+{
+    using P = PostKind<KIND>;
+    const int64_t e = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    if (e >= m.nElem) return;
+    int nd[4] = {0, 0, 0, 0};
+    bool any = only_nodes == nullptr;
+#pragma unroll
+    for (int a = 0; a < P::NPE; ++a) {
+        nd[a] = m.conn[a * m.nElem + e];
+        if (only_nodes && only_nodes[nd[a]]) any = true;
+    }
+    if (!any) return;
+    double x[4], y[4], z[4], valC[12], g[6], f[6], fint[12], sc, dvol;
+    post_load_elem<KIND>(m, nd, u, x, y, z, valC);
+    if (!elem_post(KIND, x, y, z, prm.ed, valC, g, f, sc, fint, dvol)) { atomicMax(err, PFEM_ERR_NEG_JAC); return; }
+#pragma unroll
+    for (int a = 0; a < P::NPE; ++a) {
+        if (only_nodes && !only_nodes[nd[a]]) continue;
+#pragma unroll
+        for (int c = 0; c < P::NG; ++c) add_f64(&nodal[static_cast<int64_t>(nd[a]) * P::NG + c], dvol * (use_grad ? g[c] : f[c]));
+        add_f64(&weight[nd[a]], dvol);
+    }
+}
+
+// nodal[n * NG + c] /= weight[n] (zeros where the node has no element) and the scalar of the quotient, for the nodes
+// k_post_recovery_scatter summed: all of them, or the flagged ones
+template <int KIND>
+__global__ void __launch_bounds__(kBlock) k_post_recovery_divide(int64_t nNode, const uint8_t *__restrict__ only_nodes,
+                                                                  const double *__restrict__ weight, double *__restrict__ nodal,
+                                                                  double *__restrict__ nscalar)
+{
+    using P = PostKind<KIND>;
+    const int64_t n = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    if (n >= nNode || (only_nodes && !only_nodes[n])) return;
+    const double w = weight[n];
+    double r[P::NG];
+#pragma unroll
+    for (int c = 0; c < P::NG; ++c) {
+        r[c] = w != 0.0 ? nodal[n * P::NG + c] / w : 0.0;
+        nodal[n * P::NG + c] = r[c];
+    }
+    if (nscalar) nscalar[n] = post_scalar(KIND, r);
+}
+
+// ZZ indicator: one thread per element gathers the NPE * NG recovered values of its nodes and evaluates elem_recovery_error;
+// eta2[e] (coalesced) and the block's partial sums of eta2 and flux_norm2 in block_sum's fixed order (k_reduce_partials adds
+// the partials).  The grid is grid_for(nElem) blocks wide at most kMaxGrid: a block strides over the elements.
+template <int KIND>
+__global__ void __launch_bounds__(kBlock) k_post_indicator(MeshDev m, ElemPrm prm, const double *__restrict__ u, const double *__restrict__ nodal,
+                                                            double *__restrict__ eta2, double *part_eta, double *part_fn, int *err)
+{
+    using P = PostKind<KIND>;
+    __shared__ double sm[4];
+    double se = 0.0, sf = 0.0;
+    for (int64_t e = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; e < m.nElem; e += static_cast<int64_t>(gridDim.x) * kBlock) {
+        int nd[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int a = 0; a < P::NPE; ++a) nd[a] = m.conn[a * m.nElem + e];
+        double x[4], y[4], z[4], valC[12], nf[4 * P::NG], e2, f2;
+        post_load_elem<KIND>(m, nd, u, x, y, z, valC);
+#pragma unroll
+        for (int a = 0; a < P::NPE; ++a)
+#pragma unroll
+            for (int c = 0; c < P::NG; ++c) nf[a * P::NG + c] = nodal[static_cast<int64_t>(nd[a]) * P::NG + c];
+        if (!elem_recovery_error(KIND, x, y, z, prm.ed, valC, nf, e2, f2)) { atomicMax(err, PFEM_ERR_NEG_JAC); continue; }
+        if (eta2) eta2[e] = e2;
+        se += e2;
+        sf += f2;
+    }
+    const double a = block_sum(se, sm), c = block_sum(sf, sm);
+    if (threadIdx.x == 0) { part_eta[blockIdx.x] = a; part_fn[blockIdx.x] = c; }
+}
+
 // per-block partials of |b - w|^2 and |b|^2 over the owned rows (w = K x from the SpMV in effect); fixed order, reproducible
 __global__ void __launch_bounds__(kBlock) k_post_residual_partials(int64_t n_owned, const double *__restrict__ b, const double *__restrict__ w,
                                                                     double *part_r, double *part_b)

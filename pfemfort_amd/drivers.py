@@ -35,6 +35,7 @@ class Result:
     reason: int
     rnorm: float
     timers: dict = field(default_factory=dict)
+    elemData: np.ndarray | None = None   # what the element loop ran with (post-processing of the solution)
 
     def temp_dat(self):
         """Rows of the reference's ``temp.dat`` dump (tetrapoissonparallelimpl1.F:935-942):
@@ -47,9 +48,12 @@ class Result:
             ind = self.dm.node_map_get_old[assy // ndof] * ndof + assy % ndof + 1
         return np.arange(1, len(assy) + 1), ind, self.soln_free
 
-    def write_outputs(self, directory=".", elem_procid=None):
+    def write_outputs(self, directory=".", elem_procid=None, fields=False):
         """The output step of the drivers: ``temp.dat`` (:935-942 / elasticity :1031-1046) and the
-        legacy VTK file through the writervtk.F-compatible writer (:944-966)."""
+        legacy VTK file through the writervtk.F-compatible writer (:944-966).  ``fields=True`` also writes
+        ``<name>-fields.vtk``: the same file with the element flux / stress, its scalar and the Zienkiewicz-Zhu indicator
+        ``eta = sqrt(eta2)`` as cell arrays and the recovered nodal flux / stress and its scalar as point arrays, by OLD node id
+        like ``solnVTK`` (one rank and ``mode="batched"``: the library's PFEM_ERR_STATE otherwise)."""
         import os
         ndof = self.dm.NodeDofArrayNew.shape[1]
         ii, ind, val = self.temp_dat()
@@ -58,6 +62,23 @@ class Result:
         pid = np.zeros(self.mesh.nElem, np.int32) if elem_procid is None else elem_procid
         H.writeoutputvtk(self.mesh.xyz.shape[0], self.mesh.xyz, self.mesh.conn, pid, self.solnVTK, os.path.join(directory, name),
                          ndof=ndof)
+        if fields:
+            s, old = self.solver, self.dm.node_map_get_old
+            _, flux, scalar = s.elementFields(self.elemData)
+            eta2, _, _ = s.errorIndicator(self.elemData)
+            nodal, nscalar, _ = s.nodalRecovery(self.elemData)
+
+            def by_old(a):                   # the solver's nodes are the NEW ids: back to the file's, as _finish does
+                out = np.empty_like(a)
+                out[old] = a
+                return out
+
+            f, sc = ("flux", "flux_magnitude") if ndof == 1 else ("stress", "von_mises")
+            H.writeoutputvtk_fields(self.mesh.xyz.shape[0], self.mesh.xyz, self.mesh.conn, pid, self.solnVTK,
+                                    os.path.join(directory, name[:-4] + "-fields.vtk"), ndof=ndof,
+                                    cell_fields={f: flux.T, sc: scalar, "eta": np.sqrt(eta2)},
+                                    point_fields={f + "_recovered": by_old(nodal), sc + "_recovered": by_old(nscalar)},
+                                    voigt=() if ndof == 1 else (f, f + "_recovered"))
         return os.path.join(directory, name)
 
 
@@ -70,14 +91,14 @@ def _setup(kind, mesh: H.Mesh, nParts=1, node_proc_id=None):
     return dm, conn_new, xyz_new, edof
 
 
-def _finish(kind, mesh, dm, solver, its, reason, rnorm, timers, u_free):
+def _finish(kind, mesh, dm, solver, its, reason, rnorm, timers, u_free, elemData=None):
     ndof = L.NDOF[kind]
     full = dm.solnApplied.reshape(-1, ndof).copy()                       # :914-918 applied BC values
     assy = H.assy_for_soln(dm.NodeDofArrayNew)                           # :722-734
     full.reshape(-1)[assy] = u_free                                      # :936-941
     solnVTK = np.empty_like(full)
     solnVTK[dm.node_map_get_old] = full
-    return Result(kind, mesh, dm, solver, u_free, solnVTK, its, reason, rnorm, timers)
+    return Result(kind, mesh, dm, solver, u_free, solnVTK, its, reason, rnorm, timers, elemData)
 
 
 def _run(kind, mesh, elemData, timeData, mode, rtol, maxits, verbose, pc=None):
@@ -145,7 +166,7 @@ def _run(kind, mesh, elemData, timeData, mode, rtol, maxits, verbose, pc=None):
         print("Divergence." if reason < 0 else f" Convergence in {its} iterations.")
     u = solver.getSolution()                                             # VecScatterCreateToAll + VecGetArray :922-932
     timers.update(solver.timings())
-    return _finish(kind, mesh, dm, solver, its, reason, rnorm, timers, u)
+    return _finish(kind, mesh, dm, solver, its, reason, rnorm, timers, u, elemData)
 
 
 def run_parallel(kind, mesh: H.Mesh, elem_proc_id, node_proc_id, dist, torch, elemData=None, timeData=None, rtol=1e-5,
@@ -196,7 +217,7 @@ def run_parallel(kind, mesh: H.Mesh, elem_proc_id, node_proc_id, dist, torch, el
     for r0, x in parts:
         u[r0:r0 + len(x)] = x
     timers.update(solver.timings())
-    return _finish(kind, mesh, dm, solver, its, reason, rnorm, timers, u)
+    return _finish(kind, mesh, dm, solver, its, reason, rnorm, timers, u, elemData)
 
 
 def tetrapoissonparallelimpl1(mesh: H.Mesh | str, mode="batched", rtol=1e-5, maxits=10000, verbose=False, pc=None) -> Result:

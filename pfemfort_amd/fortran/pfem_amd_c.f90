@@ -120,6 +120,19 @@ module pfem_amd_c
       real(c_double) :: coords(*), soln(*)
       integer(c_int) :: conn(*), procid(*)
     end function
+    ! pfem_write_vtk's file with further cell / point arrays: *_name are arrays of c_loc's of NUL-terminated names, *_data arrays
+    ! of c_loc's of data(ncomp,n) column-major; ncomp 1 / 3 / 9
+    integer(c_int) function pfem_write_vtk_fields(path, ndim, nElem, nNode, npElem, ndof, coords, conn, procid, soln, &
+        n_cell, cell_name, cell_ncomp, cell_data, n_point, point_name, point_ncomp, point_data) bind(C, name="pfem_write_vtk_fields")
+      import
+      character(kind=c_char) :: path(*)
+      integer(c_int), value :: ndim, npElem, ndof, n_cell, n_point
+      integer(c_int64_t), value :: nElem, nNode
+      real(c_double) :: coords(*), soln(*)
+      integer(c_int) :: conn(*), procid(*)
+      type(c_ptr) :: cell_name(*), cell_data(*), point_name(*), point_data(*)
+      integer(c_int) :: cell_ncomp(*), point_ncomp(*)
+    end function
     ! the element loop as one device call (the fast path of include/pfem_amd.h, section 4)
     integer(c_int) function pfem_mesh_upload(s, kind, nElem, conn, nNode, xyz, edof, solnApplied) bind(C, name="pfem_mesh_upload")
       import
@@ -160,6 +173,25 @@ module pfem_amd_c
       real(c_double) :: elemData(*), timeData(*)
       type(c_ptr), value :: u_nodal
       real(c_double) :: R(*)                      ! (node-1)*ndof+dof
+    end function
+    ! field: 0 flux / stress, 1 gradient / strain (PFEM_POST_FLUX / PFEM_POST_GRAD); nodal_scalar must be c_null_ptr for field 1
+    integer(c_int) function pfem_post_nodal_recovery(s, elemData, u_nodal, field, nodal, nodal_scalar, weight) &
+        bind(C, name="pfem_post_nodal_recovery")
+      import
+      type(c_ptr), value :: s
+      real(c_double) :: elemData(*)
+      type(c_ptr), value :: u_nodal
+      integer(c_int), value :: field
+      type(c_ptr), value :: nodal, nodal_scalar, weight   ! nodal(ng,nNode) column-major = (node-1)*ng+c; (nNode); (nNode)
+    end function
+    integer(c_int) function pfem_post_error_indicator(s, elemData, u_nodal, eta2, eta2_total, flux_norm2_total) &
+        bind(C, name="pfem_post_error_indicator")
+      import
+      type(c_ptr), value :: s
+      real(c_double) :: elemData(*)
+      type(c_ptr), value :: u_nodal
+      type(c_ptr), value :: eta2                  ! eta2(nElem) or c_null_ptr
+      real(c_double) :: eta2_total, flux_norm2_total
     end function
     integer(c_int) function pfem_solver_true_residual(s, rnorm2, bnorm2) bind(C, name="pfem_solver_true_residual")
       import

@@ -269,6 +269,32 @@ def ElementPost(kind, xNode, yNode, zNode, elemData, valC):
     return grad, flux, sc.value, fint
 
 
+def PostScalar(kind, flux):
+    """The scalar of ``ElementPost`` on any flux / stress vector(s) of the kind, ``(ng,)`` or ``(n, ng)`` in the stored Voigt
+    order (pfem_post_scalar): ``|q|``, von Mises, the plane-stress form."""
+    f = _f64(flux)
+    rows = f.reshape(-1, L.NG[kind])
+    out = np.empty(rows.shape[0])
+    sc = C.c_double(0)
+    for i, r in enumerate(rows):
+        L.check(L.lib().pfem_post_scalar(kind, _p(np.ascontiguousarray(r)), C.byref(sc)), "pfem_post_scalar")
+        out[i] = sc.value
+    return float(out[0]) if f.ndim == 1 else out
+
+
+def ElementRecoveryError(kind, xNode, yNode, zNode, elemData, valC, nodal_flux):
+    """One element's share of the Zienkiewicz-Zhu indicator (pfem_elem_recovery_error): ``nodal_flux (npe, ng)`` are the
+    recovered values at the element's nodes; returns ``(eta2, flux_norm2)``."""
+    z = None if zNode is None else _f64(zNode)
+    ed = None if elemData is None else _f64(elemData)
+    nf = _f64(nodal_flux).ravel()
+    assert nf.size == L.NPELEM[kind] * L.NG[kind]
+    e2 = C.c_double(0); f2 = C.c_double(0)
+    L.check(L.lib().pfem_elem_recovery_error(kind, _p(_f64(xNode)), _p(_f64(yNode)), _p(z), _p(ed), _p(_f64(valC)), _p(nf),
+                                             C.byref(e2), C.byref(f2)), "pfem_elem_recovery_error")
+    return e2.value, f2.value
+
+
 def find_ghosts(edof, row_start, n_owned):
     """Ascending unique global dof ids of ``edof`` outside the owned block (host-only)."""
     e = _i32(edof).ravel()
@@ -319,3 +345,64 @@ def writeoutputvtk(ndim, coords, elemNodeConn, elem_procid, soln, fileName, ndof
         ndof = soln.size // nNode
     L.check(L.lib().pfem_write_vtk(str(fileName).encode(), ndim, nElem, nNode, conn.shape[0], ndof, _p(coords), _p(conn),
                                    _p(pid), _p(soln.ravel())), "writeoutputvtk")
+
+
+def _vtk_array(name, a, n):
+    """One extra array of the writer as (n, ncomp)."""
+    a = _f64(a)
+    if a.ndim == 1:
+        a = a.reshape(-1, 1)
+    if a.shape[0] != n:
+        raise ValueError(f"{name}: {a.shape[0]} items, expected {n}")
+    return a
+
+
+def voigt_to_tensor(v):
+    """``(n, 6)`` [xx,yy,zz,xy,yz,zx] or ``(n, 3)`` [xx,yy,xy] (components as stored) -> ``(n, 9)`` symmetric 3x3, row-major."""
+    v = _f64(v)
+    t = np.zeros((v.shape[0], 9))
+    if v.shape[1] == 6:
+        xx, yy, zz, xy, yz, zx = v.T
+        t[:, 0], t[:, 4], t[:, 8] = xx, yy, zz
+        t[:, 1] = t[:, 3] = xy
+        t[:, 5] = t[:, 7] = yz
+        t[:, 2] = t[:, 6] = zx
+    elif v.shape[1] == 3:
+        t[:, 0], t[:, 4] = v[:, 0], v[:, 1]
+        t[:, 1] = t[:, 3] = v[:, 2]
+    else:
+        raise ValueError("Voigt vectors have 3 or 6 components")
+    return t
+
+
+def writeoutputvtk_fields(ndim, coords, elemNodeConn, elem_procid, soln, fileName, ndof=None, cell_fields=None, point_fields=None,
+                          voigt=()):
+    """``writeoutputvtk``'s file with further arrays (pfem_write_vtk_fields): ``cell_fields`` / ``point_fields`` map a name to
+    ``(n,)`` scalars, ``(n, 3)`` vectors (``(n, 2)``: padded with a zero), ``(n, 6)`` Voigt [xx,yy,zz,xy,yz,zx] -- written as a
+    symmetric 3x3 tensor -- or ``(n, 9)``.  A name in ``voigt`` marks an ``(n, 3)`` array as plane Voigt [xx,yy,xy] instead of
+    a vector.  Without fields the bytes are ``writeoutputvtk``'s."""
+    coords = _f64(coords); conn = _i32(elemNodeConn); pid = _i32(elem_procid)
+    soln = _f64(soln)
+    nNode, nElem = coords.shape[1], conn.shape[1]
+    if ndof is None:
+        ndof = soln.size // nNode
+
+    def pack(fields, n):
+        names, ncomp, arrays = [], [], []
+        for name, a in (fields or {}).items():
+            a = _vtk_array(name, a, n)
+            if a.shape[1] == 6 or (a.shape[1] == 3 and name in voigt):
+                a = voigt_to_tensor(a)
+            elif a.shape[1] == 2:
+                a = np.concatenate([a, np.zeros((n, 1))], axis=1)
+            names.append(str(name).encode()); ncomp.append(a.shape[1]); arrays.append(np.ascontiguousarray(a))
+        k = len(names)
+        return (k, (C.c_char_p * max(k, 1))(*names), (C.c_int * max(k, 1))(*ncomp),
+                (C.c_void_p * max(k, 1))(*[a.ctypes.data for a in arrays]), arrays)
+
+    nc, cn, cc, cd, keep_c = pack(cell_fields, nElem)
+    npt, pn, pc, pd, keep_p = pack(point_fields, nNode)
+    L.check(L.lib().pfem_write_vtk_fields(str(fileName).encode(), ndim, nElem, nNode, conn.shape[0], ndof, _p(coords), _p(conn),
+                                          _p(pid), _p(soln.ravel()), nc, C.cast(cn, C.c_void_p), C.cast(cc, C.c_void_p),
+                                          C.cast(cd, C.c_void_p), npt, C.cast(pn, C.c_void_p), C.cast(pc, C.c_void_p),
+                                          C.cast(pd, C.c_void_p)), "writeoutputvtk_fields")

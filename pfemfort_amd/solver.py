@@ -457,6 +457,44 @@ class PetscSolver:
         L.check(L.lib().pfem_post_nodal_forces(self._h, _p(ed), _p(td), _p(uu), _p(R)), "pfem_post_nodal_forces")
         return R
 
+    def nodalRecovery(self, elemData, u=None, field="flux"):
+        """``(nodal (nNode, ng), nodal_scalar (nNode,) or None, weight (nNode,))``: the volume-weighted average of the element
+        flux / stress (``field="flux"``) or gradient / strain (``"grad"``) at every node, the scalar of the recovered flux
+        (``None`` for ``"grad"``) and the sum of the weights (``u`` as in ``elementFields``; ``host.PostScalar`` mirrors the
+        scalar)."""
+        kind = getattr(self, "kind", None)
+        ed = None if elemData is None else _f64(elemData)
+        uu = None if u is None else _f64(u).ravel()
+        fld = {"flux": 0, "grad": 1}[field]
+        if kind is None:
+            L.check(L.lib().pfem_post_nodal_recovery(self._h, _p(ed), _p(uu), fld, None, None, None), "pfem_post_nodal_recovery")
+        assert uu is None or uu.size == self.nNode * L.NDOF[kind]
+        nodal = np.empty((self.nNode, L.NG[kind])); weight = np.empty(self.nNode)
+        scalar = np.empty(self.nNode) if fld == 0 else None
+        L.check(L.lib().pfem_post_nodal_recovery(self._h, _p(ed), _p(uu), fld, _p(nodal), _p(scalar), _p(weight)),
+                "pfem_post_nodal_recovery")
+        return nodal, scalar, weight
+
+    def errorIndicator(self, elemData, u=None):
+        """Zienkiewicz-Zhu indicator ``(eta2 (nElem,), eta2_total, flux_norm2_total)``: per element the integral of
+        ``|recovered nodal flux - element flux|^2`` (``host.ElementRecoveryError``), and the sums over the mesh."""
+        kind = getattr(self, "kind", None)
+        ed = None if elemData is None else _f64(elemData)
+        uu = None if u is None else _f64(u).ravel()
+        tot = C.c_double(0); fn = C.c_double(0)
+        if kind is None:
+            L.check(L.lib().pfem_post_error_indicator(self._h, _p(ed), _p(uu), None, C.byref(tot), C.byref(fn)), "pfem_post_error_indicator")
+        assert uu is None or uu.size == self.nNode * L.NDOF[kind]
+        eta2 = np.empty(self.nElem)
+        L.check(L.lib().pfem_post_error_indicator(self._h, _p(ed), _p(uu), _p(eta2), C.byref(tot), C.byref(fn)), "pfem_post_error_indicator")
+        return eta2, tot.value, fn.value
+
+    def recoveryTimings(self):
+        """Kernel milliseconds of the last ``nodalRecovery`` / ``errorIndicator`` call (the indicator's includes its recovery)."""
+        a = C.c_double(0); b = C.c_double(0)
+        L.check(L.lib().pfem_post_recovery_timings(self._h, C.byref(a), C.byref(b)), "pfem_post_recovery_timings")
+        return {"recovery_ms": a.value, "indicator_ms": b.value}
+
     def trueResidual(self):
         """``(|b - K x|_2, |b|_2)`` over the owned rows for the x of the last solve (-ksp_monitor_true_residual)."""
         r = C.c_double(0); b = C.c_double(0)

@@ -1,5 +1,6 @@
-"""Kernel time of the post-processing passes (pfem_post_elements, pfem_post_nodal_forces) on BASELINE configs 3 and 4 beside the
-assembly kernel of the same run, with the compulsory bytes of each pass.  `python tools/lab/post_measure.py [out.json]`."""
+"""Kernel time of the post-processing passes (pfem_post_elements, pfem_post_nodal_forces, pfem_post_nodal_recovery,
+pfem_post_error_indicator) on BASELINE configs 3 and 4 beside the assembly kernel of the same run, with the compulsory bytes of
+each pass.  `python tools/lab/post_measure.py [out.json]`."""
 import json
 import os
 import sys
@@ -32,10 +33,18 @@ for name, kind, box, bc, ndof, ed in (("config3_poisson_200", pf.POISSON_TET, (-
         el.append(s.postTimings()["elements_ms"])
         s.nodalForces(ed, H.TIMEDATA, u)
         nf.append(s.postTimings()["nodal_forces_ms"])
+    rec, ind, recs = [], [], []
+    for _ in range(4):                     # the recovery and the indicator (its time includes its own recovery), same run
+        s.nodalRecovery(ed, u)
+        rec.append(s.recoveryTimings()["recovery_ms"])
+        s.errorIndicator(ed, u)
+        ind.append(s.recoveryTimings()["indicator_ms"])
     s.setAssemblyMode("scatter")
     for _ in range(3):
         s.nodalForces(ed, H.TIMEDATA, u)
         nfs.append(s.postTimings()["nodal_forces_ms"])
+        s.nodalRecovery(ed, u)
+        recs.append(s.recoveryTimings()["recovery_ms"])
     s.setAssemblyMode("gather")
     ng = {pf.POISSON_TET: 3, pf.ELAST_TET: 6}[kind]
     nElem, nNode = s.nElem, s.nNode
@@ -44,9 +53,16 @@ for name, kind, box, bc, ndof, ed in (("config3_poisson_200", pf.POISSON_TET, (-
     # compulsory bytes: every array read or written once
     b_el = nElem * 16 + nNode * (3 + ndof) * 8 + nElem * (2 * ng + 1) * 8
     b_nf = inc * 16 + (nNode // 64 + 1) * 8 + nNode * 4 + nNode * (3 + ndof) * 8 + nNode * ndof * 8
+    b_rec = inc * 16 + (nNode // 64 + 1) * 8 + nNode * 4 + nNode * (3 + ndof) * 8 + nNode * (ng + 2) * 8
+    b_ind = nElem * 16 + nNode * (3 + ndof) * 8 + nNode * ng * 8 + nElem * 8          # the element pass alone
     r = {"nElem": nElem, "nNode": nNode, "assembly": info, "patterns": s.incidencePatterns(),
          "assemble_ms": asm, "post_elements_ms": el, "post_nodal_forces_gather_ms": nf, "post_nodal_forces_scatter_ms": nfs,
          "elementFields_wall_s": wall,
+         "post_recovery_gather_ms": rec, "post_recovery_scatter_ms": recs, "post_indicator_with_recovery_ms": ind,
+         "post_recovery_gather_compulsory_bytes": b_rec, "post_indicator_pass_compulsory_bytes": b_ind,
+         "post_recovery_gather_TBps": b_rec / (min(rec[1:]) * 1e-3) / 1e12,
+         "post_recovery_gather_over_forces_gather": min(rec[1:]) / min(nf[1:]),
+         "post_indicator_pass_ms": min(ind[1:]) - min(rec[1:]),
          "post_elements_compulsory_bytes": b_el, "post_nodal_forces_gather_compulsory_bytes": b_nf,
          "post_elements_TBps": b_el / (min(el[1:]) * 1e-3) / 1e12, "post_nodal_forces_gather_TBps": b_nf / (min(nf[1:]) * 1e-3) / 1e12}
     out[name] = r
