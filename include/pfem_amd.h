@@ -300,6 +300,18 @@ int pfem_mesh_generate_box_axis(pfem_solver *s, int kind, double x0, double x1, 
                                 double z0, double z1, int nEz, int bc_mode, int axis, int nparts, int part);
 /* the mesh as the device holds it; edof in LOCAL numbering (owned rows first, ghosts after); any pointer may be NULL */
 int pfem_mesh_download(pfem_solver *s, int32_t *conn, double *xyz, int32_t *edof_local, double *solnApplied);
+/* Several materials.  elem_mat[e] in 0 .. n_mat-1 (1 <= n_mat <= 256: one byte per element on the device) names the material
+ * of element e, in the order of the conn given to pfem_mesh_upload, or of pfem_gen_box_tets for pfem_mesh_generate_box*.  While
+ * a map is set, the elemData argument of pfem_assemble, pfem_eval_elems and the pfem_post_* calls is a TABLE
+ * elemData[m * stride + k] and element e takes row elem_mat[e]; stride >= the kind's count of elemData entries (Poisson tet 3,
+ * Poisson triangle 2, elastic tet 6, elastic triangle 5).  timeData stays global.  The table is an argument of every call and
+ * may change from call to call; the map may not: it is legal after a mesh upload / generate and before pfem_pattern_build
+ * (PFEM_ERR_STATE afterwards, and on a handle without a mesh).  elem_mat == NULL or n_mat == 0 clears the map, and so does a
+ * new mesh.  PFEM_ERR_ARG: nElem is not the mesh's, an id out of range, n_mat > 256, stride too small, or
+ * PFEM_POISSON_TRIA_INLINE (which has no material).  One rank only: pfem_assemble with a map and a communication backend of
+ * more than one rank is PFEM_ERR_STATE.  pfem_mesh_get_materials: n_mat = 0 without a map; elem_mat may be NULL. */
+int pfem_mesh_set_materials(pfem_solver *s, int64_t nElem, const int32_t *elem_mat, int n_mat, int stride);
+int pfem_mesh_get_materials(pfem_solver *s, int *n_mat, int *stride, int32_t *elem_mat);
 int pfem_pattern_build(pfem_solver *s);
 /* setZero + element loop :817-884 on the device: Ke/Fe, Dirichlet lifting,
  * atomic scatter into the device matrix and rhs.                                */

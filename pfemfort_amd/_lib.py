@@ -25,6 +25,7 @@ NPELEM = {POISSON_TRIA: 3, POISSON_TET: 4, ELAST_TET: 4, POISSON_TRIA_INLINE: 3,
 NDOF = {POISSON_TRIA: 1, POISSON_TET: 1, ELAST_TET: 3, POISSON_TRIA_INLINE: 1, ELAST_TRIA: 2}
 NDIM = {POISSON_TRIA: 2, POISSON_TET: 3, ELAST_TET: 3, POISSON_TRIA_INLINE: 2, ELAST_TRIA: 2}
 NG = {POISSON_TRIA: 2, POISSON_TET: 3, ELAST_TET: 6, POISSON_TRIA_INLINE: 2, ELAST_TRIA: 3}   # components of grad / flux (pfem_elem_post)
+NELEMDATA = {POISSON_TRIA: 2, POISSON_TET: 3, ELAST_TET: 6, POISSON_TRIA_INLINE: 0, ELAST_TRIA: 5}   # elemData entries the kind reads
 
 
 class PfemError(RuntimeError):
@@ -103,6 +104,8 @@ SIGNATURES = {
     "pfem_box_slab_sizes_axis": [_I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
     "pfem_mesh_generate_box_axis": [_P, _I, _D, _D, _I, _D, _D, _I, _D, _D, _I, _I, _I, _I, _I],
     "pfem_mesh_download": [_P, _P, _P, _P, _P],
+    "pfem_mesh_set_materials": [_P, _L, _P, _I, _I],
+    "pfem_mesh_get_materials": [_P, _P, _P, _P],
     "pfem_pattern_build": [_P],
     "pfem_assemble": [_P, _P, _P],
     "pfem_solver_set_assembly_mode": [_P, _I],

@@ -538,6 +538,12 @@ struct pfem_solver {
     DevBuf<int32_t> d_inc_ea;      // ... entries 4*e + a, ascending element id, entry j of node n at ptr[n/64]+64j+n%64
     DevBuf<int4> d_inc_rec;        // packed {other nodes, slots} record per incidence (replaces ea + slots + elemrec)
     DevBuf<uint16_t> d_inc_flags;  // ... with the constrained-dof bits of the element (kinds with ndof > 1)
+    // several materials (pfem_mesh_set_materials): n_mat > 0 while a map is set; elemData is then a table of n_mat rows
+    int n_mat = 0, mat_stride = 0;
+    std::vector<uint8_t> h_elem_mat;   // the map as given (pfem_mesh_get_materials)
+    DevBuf<uint8_t> d_elem_mat;        // [nElem] row of every element ...
+    DevBuf<uint8_t> d_inc_mat;         // ... and of every visit of the incidence records, in their layout (k_build_inc_mat)
+    DevBuf<double> d_mat_tab;          // the table of the call in progress, [n_mat * mat_stride]
     // the lists as translated copies of a few patterns (k_incpat_*): node -> pattern, pattern -> records relative to the node
     DevBuf<uint16_t> d_node_pat, d_pat_flags;
     DevBuf<int4> d_pat_rec;
@@ -1321,6 +1327,28 @@ int download_external(pfem_solver *s, const double *d_vec, double *out, int64_t 
     return PFEM_OK;
 }
 
+// no material map: one elemData for the whole mesh again
+void clear_materials(pfem_solver *s)
+{
+    s->n_mat = s->mat_stride = 0;
+    s->h_elem_mat.clear();
+    s->d_elem_mat.release();
+    s->d_inc_mat.release();
+    s->d_mat_tab.release();
+}
+
+// entries of elemData that the element kind reads (0: the kind has no material)
+int kind_elem_data(int kind)
+{
+    switch (kind) {
+    case PFEM_POISSON_TET: return 3;
+    case PFEM_POISSON_TRIA: return 2;
+    case PFEM_ELAST_TET: return 6;
+    case PFEM_ELAST_TRIA: return 5;
+    default: return 0;
+    }
+}
+
 }  // namespace
 
 extern "C" int pfem_mesh_upload(pfem_solver *s, int kind, int64_t nElem, const int32_t *conn,
@@ -1376,6 +1404,7 @@ extern "C" int pfem_mesh_upload(pfem_solver *s, int kind, int64_t nElem, const i
     m.xyz = s->d_xyz.p;
     m.soln = s->d_soln.p;
     PFEM_TRY(maybe_reorder(s, edof, xyz));
+    clear_materials(s);
     s->have_mesh = true;
     s->have_pattern = false;
     // a neighbour plan set before this upload names dofs in the previous mesh's (internal) numbering: it has to be set again
@@ -1566,6 +1595,7 @@ extern "C" int pfem_mesh_generate_box_axis(pfem_solver *s, int kind, double x0, 
     s->reordered = false;
     s->h_perm.clear();
     s->h_iperm.clear();
+    clear_materials(s);
     s->have_mesh = true;
     s->have_pattern = false;
     s->have_plan = false;
@@ -1577,6 +1607,55 @@ extern "C" int pfem_mesh_generate_box(pfem_solver *s, int kind, double x0, doubl
                                       double z0, double z1, int nEz, int bc_mode, int nparts, int part)
 {
     return pfem_mesh_generate_box_axis(s, kind, x0, x1, nEx, y0, y1, nEy, z0, z1, nEz, bc_mode, 2, nparts, part);
+}
+
+// The material of every element: elem_mat[e] in 0 .. n_mat-1 names the row of the elemData TABLE that the numeric and the
+// post-processing calls take while the map is set (elemData[m * stride + k]).  Elements are never reordered on the device (the
+// internal renumbering moves nodes and dofs only), so the map is stored as given.  Legal between the mesh and the pattern:
+// the per-visit bytes of the gather kernels are made from the element lists, which pfem_pattern_build releases.
+extern "C" int pfem_mesh_set_materials(pfem_solver *s, int64_t nElem, const int32_t *elem_mat, int n_mat, int stride)
+{
+    if (!s) return PFEM_ERR_ARG;
+    if (!s->have_mesh) return PFEM_ERR_STATE;
+    if (s->have_pattern) {
+        set_last_error("pfem_mesh_set_materials: the pattern is built; set the map between the mesh and pfem_pattern_build");
+        return PFEM_ERR_STATE;
+    }
+    if (!elem_mat || n_mat == 0) {
+        clear_materials(s);
+        return PFEM_OK;
+    }
+    const MeshDev &m = s->mesh;
+    const int need = kind_elem_data(m.kind);
+    if (need == 0) {
+        set_last_error("pfem_mesh_set_materials: this element kind has no material");
+        return PFEM_ERR_ARG;
+    }
+    if (nElem != m.nElem || n_mat < 1 || n_mat > 256 || stride < need) return PFEM_ERR_ARG;
+    for (int64_t e = 0; e < nElem; ++e)
+        if (elem_mat[e] < 0 || elem_mat[e] >= n_mat) return PFEM_ERR_ARG;
+    PFEM_TRY(use_device(s));
+    std::vector<uint8_t> bytes(static_cast<size_t>(nElem));
+    for (int64_t e = 0; e < nElem; ++e) bytes[static_cast<size_t>(e)] = static_cast<uint8_t>(elem_mat[e]);
+    PFEM_TRY(s->d_elem_mat.alloc(static_cast<size_t>(std::max<int64_t>(nElem, 1))));
+    if (nElem > 0) PFEM_HIP(hipMemcpyAsync(s->d_elem_mat.p, bytes.data(), static_cast<size_t>(nElem), hipMemcpyHostToDevice, s->stream));
+    PFEM_HIP(hipStreamSynchronize(s->stream));
+    s->h_elem_mat.swap(bytes);
+    s->d_inc_mat.release();
+    s->n_mat = n_mat;
+    s->mat_stride = stride;
+    return PFEM_OK;
+}
+
+extern "C" int pfem_mesh_get_materials(pfem_solver *s, int *n_mat, int *stride, int32_t *elem_mat)
+{
+    if (!s) return PFEM_ERR_ARG;
+    if (!s->have_mesh) return PFEM_ERR_STATE;
+    if (n_mat) *n_mat = s->n_mat;
+    if (stride) *stride = s->mat_stride;
+    if (elem_mat && s->n_mat > 0)
+        for (size_t e = 0; e < s->h_elem_mat.size(); ++e) elem_mat[e] = s->h_elem_mat[e];
+    return PFEM_OK;
 }
 
 // the mesh as the device holds it (tests: generated box against the host generator + bookkeeping); edof comes back in
@@ -1925,6 +2004,16 @@ int build_incidence_records(pfem_solver *s)
         }
     PFEM_HIP(hipStreamSynchronize(s->stream));
     PFEM_TRY(build_incidence_patterns(s));
+    s->d_inc_mat.release();
+    if (s->n_mat > 0) {
+        // the material byte of every visit, next to the records and in their layout (the padding of a chunk is never read)
+        PFEM_TRY(s->d_inc_mat.alloc(static_cast<size_t>(std::max<int64_t>(inc_total, 1))));
+        PFEM_HIP(hipMemsetAsync(s->d_inc_mat.p, 0, static_cast<size_t>(std::max<int64_t>(inc_total, 1)), s->stream));
+        hipLaunchKernelGGL(k_build_inc_mat, dim3(grid_for(m.nNode)), dim3(kBlock), 0, s->stream, m.nNode,
+                           static_cast<const int64_t *>(s->d_inc_ptr.p), static_cast<const int32_t *>(s->d_inc_cnt.p),
+                           static_cast<const int32_t *>(s->d_inc_ea.p), static_cast<const uint8_t *>(s->d_elem_mat.p), s->d_inc_mat.p);
+        PFEM_TRY(check_kernel("k_build_inc_mat"));
+    }
     s->d_inc_ea.release();          // the lists the records came from are dropped
     s->d_inc_slots.release();
     s->d_node4.release();
@@ -2247,16 +2336,26 @@ int zero_values(pfem_solver *s, bool rows_overwritten = false)
     return PFEM_OK;
 }
 
-}  // namespace
-
-extern "C" int pfem_assemble(pfem_solver *s, const double *elemData, const double *timeData)
+// The element parameter of a call while a material map is set: the caller's table goes to the device on the call's stream
+// (it may differ from call to call), the bytes were placed when the map was set (elem_mat) and the pattern built (inc_mat).
+int make_prm_tab(pfem_solver *s, const double *elemData, const double *timeData, ElemPrmTab *out)
 {
-    if (!s) return PFEM_ERR_ARG;
-    if (!s->have_mesh || !s->have_pattern) return PFEM_ERR_STATE;
+    const size_t n = static_cast<size_t>(s->n_mat) * static_cast<size_t>(s->mat_stride);
+    if (!s->d_mat_tab.p || s->d_mat_tab.n < n) PFEM_TRY(s->d_mat_tab.alloc(n));
+    PFEM_HIP(hipMemcpyAsync(s->d_mat_tab.p, elemData, n * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    out->tab = s->d_mat_tab.p;
+    out->elem_mat = s->d_elem_mat.p;
+    out->inc_mat = s->d_inc_mat.p;
+    out->stride = s->mat_stride;
+    out->af = timeData ? timeData[1] : 1.0;
+    return PFEM_OK;
+}
+
+// pfem_assemble past its checks, for one elemData (PRM = ElemPrm) or a table of them (ElemPrmTab)
+template <class PRM>
+int assemble_with(pfem_solver *s, const PRM prm)
+{
     const MeshDev &m = s->mesh;
-    if (m.kind != PFEM_POISSON_TRIA_INLINE && !elemData) return PFEM_ERR_ARG;
-    PFEM_TRY(use_device(s));
-    const ElemPrm prm = make_prm(elemData, timeData, m.kind);
     PFEM_HIP(hipMemsetAsync(s->d_err.p, 0, sizeof(int), s->stream));
     PFEM_HIP(hipEventRecord(s->ev0, s->stream));
     const bool gather = m.nElem > 0 && s->assembly_mode == PFEM_ASSEMBLY_GATHER && s->have_incidence;
@@ -2294,13 +2393,13 @@ extern "C" int pfem_assemble(pfem_solver *s, const double *elemData, const doubl
         };
 #define PFEM_GATHER(KIND)                                                                                             \
     if (use_lds) {                                                                                                    \
-        PFEM_TRY(allow_lds(reinterpret_cast<const void *>(&k_gather_scalar<KIND, true>)));                            \
-        hipLaunchKernelGGL((k_gather_scalar<KIND, true>), rgrid, rblock, rlds, s->stream, m, A, s->d_rhs.p, prm, ip, ic, irec, nrow, s->d_err.p); \
-    } else hipLaunchKernelGGL((k_gather_scalar<KIND, false>), grid, block, 0, s->stream, m, A, s->d_rhs.p, prm, ip, ic, irec, nrow, s->d_err.p)
+        PFEM_TRY(allow_lds(reinterpret_cast<const void *>(&k_gather_scalar<KIND, true, PRM>)));                            \
+        hipLaunchKernelGGL((k_gather_scalar<KIND, true, PRM>), rgrid, rblock, rlds, s->stream, m, A, s->d_rhs.p, prm, ip, ic, irec, nrow, s->d_err.p); \
+    } else hipLaunchKernelGGL((k_gather_scalar<KIND, false, PRM>), grid, block, 0, s->stream, m, A, s->d_rhs.p, prm, ip, ic, irec, nrow, s->d_err.p)
         switch (m.kind) {
         case PFEM_POISSON_TET:
             if (use_lds && s->d_node4.p && !std::getenv("PFEM_DEBUG_GATHER_SOA")) {
-                PFEM_TRY(allow_lds(reinterpret_cast<const void *>(&k_gather_poisson_tet4)));
+                PFEM_TRY(allow_lds(reinterpret_cast<const void *>(&k_gather_poisson_tet4<PRM>)));
                 // (the relative-group copy of the values the CG's SpMV streams is written here too when that form is in use and the
                 // whole matrix is assembled by this kernel: k_rel_vals' 1.9 GB re-pack per solve -- 0.66 ms at config 3 -- goes away)
                 const SpmvForm f = spmv_form(s);
@@ -2320,7 +2419,7 @@ extern "C" int pfem_assemble(pfem_solver *s, const double *elemData, const doubl
                     const VdState reset{s->vd_n, 0, 0, 0};
                     PFEM_HIP(hipMemcpyAsync(s->d_vstate.p, &reset, sizeof reset, hipMemcpyHostToDevice, s->stream));
                 }
-                hipLaunchKernelGGL(k_gather_poisson_tet4, xgrid, rblock, rlds, s->stream, m.nNode, A, s->d_rhs.p, prm, ip, ic, irec, nrow,
+                hipLaunchKernelGGL(k_gather_poisson_tet4<PRM>, xgrid, rblock, rlds, s->stream, m.nNode, A, s->d_rhs.p, prm, ip, ic, irec, nrow,
                                    static_cast<const double4 *>(s->d_node4.p), s->d_err.p, xcd_per,
                                    both ? static_cast<const uint8_t *>(s->d_relk.p) : nullptr, both ? static_cast<const int64_t *>(s->d_rslice_off.p) : nullptr,
                                    (both && !direct) ? s->d_rvals.p : nullptr, bound ? L0->dinv.p : nullptr, bound ? L0->t.p : nullptr,
@@ -2338,12 +2437,12 @@ extern "C" int pfem_assemble(pfem_solver *s, const double *elemData, const doubl
         case PFEM_POISSON_TRIA: PFEM_GATHER(PFEM_POISSON_TRIA); break;
         case PFEM_POISSON_TRIA_INLINE: PFEM_GATHER(PFEM_POISSON_TRIA_INLINE); break;
         case PFEM_ELAST_TET:
-            PFEM_TRY(allow_lds(reinterpret_cast<const void *>(&k_gather_elast_rows)));
+            PFEM_TRY(allow_lds(reinterpret_cast<const void *>(&k_gather_elast_rows<PRM>)));
             // (plain block order: the XCD-contiguous one measured 3 % slower on the beam, 1.605 against 1.56 ms)
             {
                 const bool bothg = spmv_form(s).layout == SpmvLayout::Group3 && s->d_row_group.p && s->n_hubs == 0;
                 const bool patsf = pats && s->d_pat_flags.p;
-                hipLaunchKernelGGL(k_gather_elast_rows, rgrid, rblock, rlds, s->stream, m, A, s->d_rhs.p, prm, ip, ic, irec, ifl, nrow, s->d_err.p, 0u,
+                hipLaunchKernelGGL(k_gather_elast_rows<PRM>, rgrid, rblock, rlds, s->stream, m, A, s->d_rhs.p, prm, ip, ic, irec, ifl, nrow, s->d_err.p, 0u,
                                    bothg ? static_cast<const int32_t *>(s->d_row_group.p) : nullptr, bothg ? static_cast<const int32_t *>(s->d_group_row0.p) : nullptr,
                                    bothg ? static_cast<const int64_t *>(s->d_gslice_off.p) : nullptr, bothg ? s->d_gvals.p : nullptr,
                                    patsf ? static_cast<const uint16_t *>(s->d_node_pat.p) : nullptr, patsf ? static_cast<const int4 *>(s->d_pat_rec.p) : nullptr,
@@ -2352,8 +2451,8 @@ extern "C" int pfem_assemble(pfem_solver *s, const double *elemData, const doubl
             }
             break;
         case PFEM_ELAST_TRIA:
-            PFEM_TRY(allow_lds(reinterpret_cast<const void *>(&k_gather_elast2d_rows)));
-            hipLaunchKernelGGL(k_gather_elast2d_rows, rgrid, rblock, rlds, s->stream, m, A, s->d_rhs.p, prm, ip, ic, irec, ifl, nrow, s->d_err.p);
+            PFEM_TRY(allow_lds(reinterpret_cast<const void *>(&k_gather_elast2d_rows<PRM>)));
+            hipLaunchKernelGGL(k_gather_elast2d_rows<PRM>, rgrid, rblock, rlds, s->stream, m, A, s->d_rhs.p, prm, ip, ic, irec, ifl, nrow, s->d_err.p);
             break;
         }
 #undef PFEM_GATHER
@@ -2367,19 +2466,19 @@ extern "C" int pfem_assemble(pfem_solver *s, const double *elemData, const doubl
         const uint8_t *only = gather ? s->d_node_hub.p : nullptr;
         switch (m.kind) {
         case PFEM_POISSON_TET:
-            hipLaunchKernelGGL(k_assemble_scalar<PFEM_POISSON_TET>, grid, block, 0, s->stream, m, A, s->d_rhs.p, prm, s->d_err.p, only);
+            hipLaunchKernelGGL((k_assemble_scalar<PFEM_POISSON_TET, PRM>), grid, block, 0, s->stream, m, A, s->d_rhs.p, prm, s->d_err.p, only);
             break;
         case PFEM_POISSON_TRIA:
-            hipLaunchKernelGGL(k_assemble_scalar<PFEM_POISSON_TRIA>, grid, block, 0, s->stream, m, A, s->d_rhs.p, prm, s->d_err.p, only);
+            hipLaunchKernelGGL((k_assemble_scalar<PFEM_POISSON_TRIA, PRM>), grid, block, 0, s->stream, m, A, s->d_rhs.p, prm, s->d_err.p, only);
             break;
         case PFEM_POISSON_TRIA_INLINE:
-            hipLaunchKernelGGL(k_assemble_scalar<PFEM_POISSON_TRIA_INLINE>, grid, block, 0, s->stream, m, A, s->d_rhs.p, prm, s->d_err.p, only);
+            hipLaunchKernelGGL((k_assemble_scalar<PFEM_POISSON_TRIA_INLINE, PRM>), grid, block, 0, s->stream, m, A, s->d_rhs.p, prm, s->d_err.p, only);
             break;
         case PFEM_ELAST_TET:
-            hipLaunchKernelGGL(k_assemble_elast, grid, block, 0, s->stream, m, A, s->d_rhs.p, prm, s->d_err.p, only);
+            hipLaunchKernelGGL(k_assemble_elast<PRM>, grid, block, 0, s->stream, m, A, s->d_rhs.p, prm, s->d_err.p, only);
             break;
         case PFEM_ELAST_TRIA:
-            hipLaunchKernelGGL(k_assemble_elast2d, grid, block, 0, s->stream, m, A, s->d_rhs.p, prm, s->d_err.p, only);
+            hipLaunchKernelGGL(k_assemble_elast2d<PRM>, grid, block, 0, s->stream, m, A, s->d_rhs.p, prm, s->d_err.p, only);
             break;
         }
         PFEM_TRY(check_kernel("k_assemble"));
@@ -2400,6 +2499,27 @@ extern "C" int pfem_assemble(pfem_solver *s, const double *elemData, const doubl
     s->vd_current = false;
     s->status = PFEM_ASSEMBLY_OK;
     return PFEM_OK;
+}
+
+}  // namespace
+
+extern "C" int pfem_assemble(pfem_solver *s, const double *elemData, const double *timeData)
+{
+    if (!s) return PFEM_ERR_ARG;
+    if (!s->have_mesh || !s->have_pattern) return PFEM_ERR_STATE;
+    const MeshDev &m = s->mesh;
+    if (m.kind != PFEM_POISSON_TRIA_INLINE && !elemData) return PFEM_ERR_ARG;
+    if (s->n_mat > 0 && s->nranks > 1) {
+        set_last_error("pfem_assemble: a material map on more than one rank is not supported");
+        return PFEM_ERR_STATE;
+    }
+    PFEM_TRY(use_device(s));
+    if (s->n_mat > 0) {
+        ElemPrmTab tab{};
+        PFEM_TRY(make_prm_tab(s, elemData, timeData, &tab));
+        return assemble_with(s, tab);
+    }
+    return assemble_with(s, make_prm(elemData, timeData, m.kind));
 }
 
 // Specified nodal forces: VecSetValue(rhsVec, row, fact, ADD_VALUES) after the element loop
@@ -2440,14 +2560,18 @@ extern "C" int pfem_eval_elems(pfem_solver *s, const double *elemData, const dou
     if (!s->have_mesh) return PFEM_ERR_STATE;
     PFEM_TRY(use_device(s));
     const MeshDev &m = s->mesh;
-    const ElemPrm prm = make_prm(elemData, timeData, m.kind);
+    if (s->n_mat > 0 && !elemData) return PFEM_ERR_ARG;
+    const ElemPrm prm = make_prm(s->n_mat > 0 ? nullptr : elemData, timeData, m.kind);
+    ElemPrmTab tab{};
+    if (s->n_mat > 0) PFEM_TRY(make_prm_tab(s, elemData, timeData, &tab));
     const size_t nk = static_cast<size_t>(m.nElem) * m.nsize * m.nsize, nf = static_cast<size_t>(m.nElem) * m.nsize;
     DevBuf<double> dK, dF;
     PFEM_TRY(dK.alloc(nk));
     PFEM_TRY(dF.alloc(nf));
     PFEM_HIP(hipMemsetAsync(s->d_err.p, 0, sizeof(int), s->stream));
     if (m.nElem > 0) {
-        hipLaunchKernelGGL(k_eval_elems, dim3(grid_for(m.nElem)), dim3(kBlock), 0, s->stream, m, prm, dK.p, dF.p, s->d_err.p);
+        if (s->n_mat > 0) hipLaunchKernelGGL(k_eval_elems<ElemPrmTab>, dim3(grid_for(m.nElem)), dim3(kBlock), 0, s->stream, m, tab, dK.p, dF.p, s->d_err.p);
+        else hipLaunchKernelGGL(k_eval_elems<ElemPrm>, dim3(grid_for(m.nElem)), dim3(kBlock), 0, s->stream, m, prm, dK.p, dF.p, s->d_err.p);
         PFEM_TRY(check_kernel("k_eval_elems"));
     }
     PFEM_HIP(hipMemcpyAsync(K_out, dK.p, nk * sizeof(double), hipMemcpyDeviceToHost, s->stream));
@@ -3231,7 +3355,8 @@ int post_needs_pattern(const pfem_solver *s, const char *who)
 // Launches of the nodal recovery (enqueued only): nodal[node * ng + c], weight[node] and -- nscalar != nullptr -- the scalar of the
 // recovered vector, all in the DEVICE's node order.  Gather form: one thread per node, then the hub nodes by the restricted
 // element pass and the division; scatter form: zero, element pass over all nodes, division.
-int post_recovery_launch(pfem_solver *s, const ElemPrm &prm, const double *up, int use_grad, double *nodal, double *nscalar, double *weight)
+template <class PRM>
+int post_recovery_launch(pfem_solver *s, const PRM &prm, const double *up, int use_grad, double *nodal, double *nscalar, double *weight)
 {
     const MeshDev &m = s->mesh;
     const int64_t nn = m.nNode;
@@ -3243,7 +3368,7 @@ int post_recovery_launch(pfem_solver *s, const ElemPrm &prm, const double *up, i
         const int64_t *ip = s->d_inc_ptr.p;
         const int32_t *ic = s->d_inc_cnt.p;
         const int4 *irec = s->d_inc_rec.p;
-#define PFEM_POST(KIND) hipLaunchKernelGGL(k_post_recovery_gather<KIND>, grid, block, 0, s->stream, m, prm, ip, ic, irec, hubs, up, use_grad, nodal, nscalar, weight, s->d_err.p)
+#define PFEM_POST(KIND) hipLaunchKernelGGL((k_post_recovery_gather<KIND, PRM>), grid, block, 0, s->stream, m, prm, ip, ic, irec, hubs, up, use_grad, nodal, nscalar, weight, s->d_err.p)
         switch (m.kind) {
         case PFEM_POISSON_TRIA: PFEM_POST(PFEM_POISSON_TRIA); break;
         case PFEM_POISSON_TET: PFEM_POST(PFEM_POISSON_TET); break;
@@ -3260,7 +3385,7 @@ int post_recovery_launch(pfem_solver *s, const ElemPrm &prm, const double *up, i
     }
     if (m.nElem > 0) {
         const dim3 grid(grid_for(m.nElem)), block(kBlock);
-#define PFEM_POST(KIND) hipLaunchKernelGGL(k_post_recovery_scatter<KIND>, grid, block, 0, s->stream, m, prm, hubs, up, use_grad, nodal, weight, s->d_err.p)
+#define PFEM_POST(KIND) hipLaunchKernelGGL((k_post_recovery_scatter<KIND, PRM>), grid, block, 0, s->stream, m, prm, hubs, up, use_grad, nodal, weight, s->d_err.p)
         switch (m.kind) {
         case PFEM_POISSON_TRIA: PFEM_POST(PFEM_POISSON_TRIA); break;
         case PFEM_POISSON_TET: PFEM_POST(PFEM_POISSON_TET); break;
@@ -3320,7 +3445,10 @@ extern "C" int pfem_post_elements(pfem_solver *s, const double *elemData, const 
     PFEM_TRY(use_device(s));
     DevBuf<double> u, dg, df, ds;
     PFEM_TRY(post_nodal_field(s, u_nodal, u, "pfem_post_elements"));
-    const ElemPrm prm = make_prm(elemData, nullptr, m.kind);
+    const bool mats = s->n_mat > 0;
+    const ElemPrm prm = make_prm(mats ? nullptr : elemData, nullptr, m.kind);
+    ElemPrmTab tab{};
+    if (mats) PFEM_TRY(make_prm_tab(s, elemData, nullptr, &tab));
     const int ng = post_components(m.kind);
     const size_t ne = static_cast<size_t>(m.nElem);
     if (grad) PFEM_TRY(dg.alloc(std::max<size_t>(ne * ng, 1)));
@@ -3331,7 +3459,9 @@ extern "C" int pfem_post_elements(pfem_solver *s, const double *elemData, const 
     if (m.nElem > 0) {
         const dim3 grid(grid_for(m.nElem)), block(kBlock);
         const double *up = u.p;
-#define PFEM_POST(KIND) hipLaunchKernelGGL(k_post_elements<KIND>, grid, block, 0, s->stream, m, prm, up, dg.p, df.p, ds.p, s->d_err.p)
+#define PFEM_POST(KIND)                                                                                                          \
+    if (mats) hipLaunchKernelGGL((k_post_elements<KIND, ElemPrmTab>), grid, block, 0, s->stream, m, tab, up, dg.p, df.p, ds.p, s->d_err.p); \
+    else hipLaunchKernelGGL((k_post_elements<KIND, ElemPrm>), grid, block, 0, s->stream, m, prm, up, dg.p, df.p, ds.p, s->d_err.p)
         switch (m.kind) {
         case PFEM_POISSON_TRIA: PFEM_POST(PFEM_POISSON_TRIA); break;
         case PFEM_POISSON_TET: PFEM_POST(PFEM_POISSON_TET); break;
@@ -3369,7 +3499,10 @@ extern "C" int pfem_post_nodal_forces(pfem_solver *s, const double *elemData, co
     PFEM_TRY(use_device(s));
     DevBuf<double> u, dR;
     PFEM_TRY(post_nodal_field(s, u_nodal, u, "pfem_post_nodal_forces"));
-    const ElemPrm prm = make_prm(elemData, timeData, m.kind);
+    const bool mats = s->n_mat > 0;
+    const ElemPrm prm = make_prm(mats ? nullptr : elemData, timeData, m.kind);
+    ElemPrmTab tab{};
+    if (mats) PFEM_TRY(make_prm_tab(s, elemData, timeData, &tab));
     const int64_t nn = m.nNode, nv = nn * m.ndof;
     PFEM_TRY(dR.alloc(static_cast<size_t>(std::max<int64_t>(nv, 1))));
     const bool gather = m.nElem > 0 && s->assembly_mode == PFEM_ASSEMBLY_GATHER && s->have_incidence && s->d_inc_rec.p;
@@ -3384,7 +3517,9 @@ extern "C" int pfem_post_nodal_forces(pfem_solver *s, const double *elemData, co
         const int64_t *ip = s->d_inc_ptr.p;
         const int32_t *ic = s->d_inc_cnt.p;
         const int4 *irec = s->d_inc_rec.p;
-#define PFEM_POST(KIND) hipLaunchKernelGGL(k_post_forces_gather<KIND>, grid, block, 0, s->stream, m, prm, ip, ic, irec, hubs, up, dR.p, s->d_err.p)
+#define PFEM_POST(KIND)                                                                                                          \
+    if (mats) hipLaunchKernelGGL((k_post_forces_gather<KIND, ElemPrmTab>), grid, block, 0, s->stream, m, tab, ip, ic, irec, hubs, up, dR.p, s->d_err.p); \
+    else hipLaunchKernelGGL((k_post_forces_gather<KIND, ElemPrm>), grid, block, 0, s->stream, m, prm, ip, ic, irec, hubs, up, dR.p, s->d_err.p)
         switch (m.kind) {
         case PFEM_POISSON_TRIA: PFEM_POST(PFEM_POISSON_TRIA); break;
         case PFEM_POISSON_TET: PFEM_POST(PFEM_POISSON_TET); break;
@@ -3398,7 +3533,9 @@ extern "C" int pfem_post_nodal_forces(pfem_solver *s, const double *elemData, co
     if (m.nElem > 0 && (!gather || hubs)) {
         // one thread per element, f64 atomics: the whole mesh (scatter form, no incidence records), or the hub nodes only
         const dim3 grid(grid_for(m.nElem)), block(kBlock);
-#define PFEM_POST(KIND) hipLaunchKernelGGL(k_post_forces_scatter<KIND>, grid, block, 0, s->stream, m, prm, hubs, up, dR.p, s->d_err.p)
+#define PFEM_POST(KIND)                                                                                                          \
+    if (mats) hipLaunchKernelGGL((k_post_forces_scatter<KIND, ElemPrmTab>), grid, block, 0, s->stream, m, tab, hubs, up, dR.p, s->d_err.p); \
+    else hipLaunchKernelGGL((k_post_forces_scatter<KIND, ElemPrm>), grid, block, 0, s->stream, m, prm, hubs, up, dR.p, s->d_err.p)
         switch (m.kind) {
         case PFEM_POISSON_TRIA: PFEM_POST(PFEM_POISSON_TRIA); break;
         case PFEM_POISSON_TET: PFEM_POST(PFEM_POISSON_TET); break;
@@ -3440,7 +3577,10 @@ extern "C" int pfem_post_nodal_recovery(pfem_solver *s, const double *elemData, 
     PFEM_TRY(use_device(s));
     DevBuf<double> u, dn, dsc, dw;
     PFEM_TRY(post_nodal_field(s, u_nodal, u, "pfem_post_nodal_recovery"));
-    const ElemPrm prm = make_prm(elemData, nullptr, m.kind);
+    const bool mats = s->n_mat > 0;
+    const ElemPrm prm = make_prm(mats ? nullptr : elemData, nullptr, m.kind);
+    ElemPrmTab tab{};
+    if (mats) PFEM_TRY(make_prm_tab(s, elemData, nullptr, &tab));
     const int ng = post_components(m.kind);
     const size_t nn = static_cast<size_t>(m.nNode);
     PFEM_TRY(dn.alloc(std::max<size_t>(nn * ng, 1)));
@@ -3448,7 +3588,8 @@ extern "C" int pfem_post_nodal_recovery(pfem_solver *s, const double *elemData, 
     if (nodal_scalar) PFEM_TRY(dsc.alloc(std::max<size_t>(nn, 1)));
     PFEM_HIP(hipMemsetAsync(s->d_err.p, 0, sizeof(int), s->stream));
     PFEM_HIP(hipEventRecord(s->ev0, s->stream));
-    PFEM_TRY(post_recovery_launch(s, prm, u.p, field == PFEM_POST_GRAD, dn.p, dsc.p, dw.p));
+    if (mats) PFEM_TRY(post_recovery_launch(s, tab, u.p, field == PFEM_POST_GRAD, dn.p, dsc.p, dw.p));
+    else PFEM_TRY(post_recovery_launch(s, prm, u.p, field == PFEM_POST_GRAD, dn.p, dsc.p, dw.p));
     PFEM_HIP(hipEventRecord(s->ev1, s->stream));
     int err = 0;
     PFEM_TRY(fetch_err(s, &err));
@@ -3471,7 +3612,10 @@ extern "C" int pfem_post_error_indicator(pfem_solver *s, const double *elemData,
     PFEM_TRY(use_device(s));
     DevBuf<double> u, dn, dw, de, part;
     PFEM_TRY(post_nodal_field(s, u_nodal, u, "pfem_post_error_indicator"));
-    const ElemPrm prm = make_prm(elemData, nullptr, m.kind);
+    const bool mats = s->n_mat > 0;
+    const ElemPrm prm = make_prm(mats ? nullptr : elemData, nullptr, m.kind);
+    ElemPrmTab tab{};
+    if (mats) PFEM_TRY(make_prm_tab(s, elemData, nullptr, &tab));
     const int ng = post_components(m.kind);
     const size_t nn = static_cast<size_t>(m.nNode), ne = static_cast<size_t>(m.nElem);
     PFEM_TRY(dn.alloc(std::max<size_t>(nn * ng, 1)));
@@ -3480,12 +3624,15 @@ extern "C" int pfem_post_error_indicator(pfem_solver *s, const double *elemData,
     PFEM_TRY(part.alloc(2 * kMaxGrid + 2));
     PFEM_HIP(hipMemsetAsync(s->d_err.p, 0, sizeof(int), s->stream));
     PFEM_HIP(hipEventRecord(s->ev0, s->stream));
-    PFEM_TRY(post_recovery_launch(s, prm, u.p, 0, dn.p, nullptr, dw.p));
+    if (mats) PFEM_TRY(post_recovery_launch(s, tab, u.p, 0, dn.p, nullptr, dw.p));
+    else PFEM_TRY(post_recovery_launch(s, prm, u.p, 0, dn.p, nullptr, dw.p));
     {
         const unsigned gv = vec_grid(m.nElem);
         const dim3 grid(gv), block(kBlock);
         const double *up = u.p, *np = dn.p;
-#define PFEM_POST(KIND) hipLaunchKernelGGL(k_post_indicator<KIND>, grid, block, 0, s->stream, m, prm, up, np, de.p, part.p, part.p + kMaxGrid, s->d_err.p)
+#define PFEM_POST(KIND)                                                                                                          \
+    if (mats) hipLaunchKernelGGL((k_post_indicator<KIND, ElemPrmTab>), grid, block, 0, s->stream, m, tab, up, np, de.p, part.p, part.p + kMaxGrid, s->d_err.p); \
+    else hipLaunchKernelGGL((k_post_indicator<KIND, ElemPrm>), grid, block, 0, s->stream, m, prm, up, np, de.p, part.p, part.p + kMaxGrid, s->d_err.p)
         switch (m.kind) {
         case PFEM_POISSON_TRIA: PFEM_POST(PFEM_POISSON_TRIA); break;
         case PFEM_POISSON_TET: PFEM_POST(PFEM_POISSON_TET); break;

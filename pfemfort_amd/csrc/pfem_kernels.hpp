@@ -46,6 +46,28 @@ struct ElemPrm {
     double af;      // timeData(2)
 };
 
+// The same for a mesh of several materials (pfem_mesh_set_materials): a table of elemData rows in global memory (at most
+// 256 x 6 doubles: it lives in the caches) and one byte per element that names the element's row.  The kernels that take an
+// element parameter are templates on its type: PRM = ElemPrm is the code of a mesh without a map, argument list included.
+//   elem_mat[e]   thread-per-element kernels (hub / scatter forms, k_eval_elems, element passes of post-processing)
+//   inc_mat[t]    thread-per-node kernels: one byte per (node, element) visit next to the 16-B record inc_rec[t], in the same
+//                 wave-sliced layout (k_build_inc_mat).  A node that reads translated pattern records (pat_rec) still reads
+//                 its OWN byte stream: the pattern gives the other nodes and the slots, never the material.
+struct ElemPrmTab {
+    const double *tab;         // [n_mat * stride]
+    const uint8_t *elem_mat;   // [nElem]
+    const uint8_t *inc_mat;    // [inc_total], nullptr without incidence records
+    int stride;
+    double af;                 // timeData(2)
+};
+template <class PRM> struct PrmTraits { static constexpr bool kTab = false; };
+template <> struct PrmTraits<ElemPrmTab> { static constexpr bool kTab = true; };
+// elemData of element e / of the visit at position t of the incidence records
+__device__ __forceinline__ const double *prm_elem(const ElemPrm &p, int64_t) { return p.ed; }
+__device__ __forceinline__ const double *prm_elem(const ElemPrmTab &p, int64_t e) { return p.tab + p.stride * static_cast<int>(p.elem_mat[e]); }
+__device__ __forceinline__ const double *prm_visit(const ElemPrm &p, int64_t) { return p.ed; }
+__device__ __forceinline__ const double *prm_visit(const ElemPrmTab &p, int64_t t) { return p.tab + p.stride * static_cast<int>(p.inc_mat[t]); }
+
 // ---------------------------------------------------------------------------
 // wave / block reductions (wave = 64 lanes)
 // ---------------------------------------------------------------------------
@@ -393,8 +415,8 @@ __device__ __forceinline__ void add_f64(double *p, double v)
 //   MatSetValues reads the column-major Klocal row-major, i.e. entry (row_i,col_j)
 //   receives Klocal(j,i) (tetrapoissonparallelimpl1.F:851); lifting :859-870;
 //   VecSetValues :880.
-template <int KIND>
-__global__ void __launch_bounds__(kBlock) k_assemble_scalar(MeshDev m, SellDev A, double *rhs, ElemPrm prm, int *err,
+template <int KIND, class PRM = ElemPrm>
+__global__ void __launch_bounds__(kBlock) k_assemble_scalar(MeshDev m, SellDev A, double *rhs, PRM prm, int *err,
                                                              const uint8_t *__restrict__ only_nodes)
 {
     // only_nodes != nullptr: the hub pass of the gather form -- only the rows of flagged nodes are scattered
@@ -419,11 +441,12 @@ __global__ void __launch_bounds__(kBlock) k_assemble_scalar(MeshDev m, SellDev A
     }
     double K[NPE * NPE], F[NPE];
     const double valC[4] = {0.0, 0.0, 0.0, 0.0};   // drivers pass valC = 0 (:824)
+    const double *ed = prm_elem(prm, e);
     bool ok;
     if constexpr (KIND == PFEM_POISSON_TET)
-        ok = poisson_tet(x, y, z, prm.ed[0], prm.ed[1], prm.ed[2], prm.af, valC, K, F);
+        ok = poisson_tet(x, y, z, ed[0], ed[1], ed[2], prm.af, valC, K, F);
     else if constexpr (KIND == PFEM_POISSON_TRIA)
-        ok = poisson_tria(x, y, prm.ed[0], prm.ed[1], prm.af, valC, K, F);
+        ok = poisson_tria(x, y, ed[0], ed[1], prm.af, valC, K, F);
     else
         ok = poisson_tria_inline(x, y, K, F);
     if (!ok) { atomicMax(err, PFEM_ERR_NEG_JAC); return; }
@@ -455,7 +478,8 @@ __global__ void __launch_bounds__(kBlock) k_assemble_scalar(MeshDev m, SellDev A
 // (pfem_elem.hpp: elast_block) straight into lifting + scatter.  A node's free dofs
 // are consecutive global ids, hence consecutive entries of a sorted row, so one
 // binary search per (row, node) serves up to three columns.
-__global__ void __launch_bounds__(kBlock) k_assemble_elast(MeshDev m, SellDev A, double *rhs, ElemPrm prm, int *err,
+template <class PRM = ElemPrm>
+__global__ void __launch_bounds__(kBlock) k_assemble_elast(MeshDev m, SellDev A, double *rhs, PRM prm, int *err,
                                                             const uint8_t *__restrict__ only_nodes)
 {
     const int64_t e = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
@@ -477,14 +501,15 @@ __global__ void __launch_bounds__(kBlock) k_assemble_elast(MeshDev m, SellDev A,
     tet_geometry(x, y, z, g);
     if (g.jac < 0.0) { atomicMax(err, PFEM_ERR_NEG_JAC); return; }
     const double dvol = kGaussWtTet * g.jac;
-    const ElastMat mat = elast_material(prm.ed[0], prm.ed[1]);
+    const double *ed = prm_elem(prm, e);
+    const ElastMat mat = elast_material(ed[0], ed[1]);
     double F[12];
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
         const double b4 = dvol * 0.25;
-        F[3 * a + 0] = 0.0 + b4 * prm.ed[3];
-        F[3 * a + 1] = 0.0 + b4 * prm.ed[4];
-        F[3 * a + 2] = 0.0 + b4 * prm.ed[5];
+        F[3 * a + 0] = 0.0 + b4 * ed[3];
+        F[3 * a + 1] = 0.0 + b4 * ed[4];
+        F[3 * a + 2] = 0.0 + b4 * ed[5];
     }
     // Dirichlet values of the constrained dofs (solnApplied(elemDofGlobal), :938-950)
     double fact[12];
@@ -799,6 +824,20 @@ __global__ void __launch_bounds__(kBlock) k_build_inc_rec(MeshDev m, const int64
     }
 }
 
+// The material byte of every visit (pfem_mesh_set_materials): inc_mat[t] = elem_mat[element of visit t], in the layout of
+// inc_rec -- entry j of node n at inc_ptr[n >> 6] + 64 j + (n & 63) -- so a wave reads 64 consecutive bytes next to its 1 KiB
+// of records.  Written for every node with a list, hubs included (their rows are assembled per element, from elem_mat).
+__global__ void __launch_bounds__(kBlock) k_build_inc_mat(int64_t nNode, const int64_t *__restrict__ inc_ptr,
+                                                           const int32_t *__restrict__ inc_cnt, const int32_t *__restrict__ inc_ea,
+                                                           const uint8_t *__restrict__ elem_mat, uint8_t *__restrict__ inc_mat)
+{
+    const int64_t n = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    if (n >= nNode) return;
+    const int cnt = inc_cnt[n];
+    const int64_t beg = inc_ptr[n >> 6] + (n & 63), end = beg + 64LL * cnt;
+    for (int64_t t = beg; t < end; t += 64) inc_mat[t] = elem_mat[inc_ea[t] >> 2];
+}
+
 // ---- incidence lists as TRANSLATED copies of a few patterns ----
 // The packed records are 16 B per visit: 3.1 GB at config 3, two thirds of what the gather kernel fetches from HBM (rocprofv3
 // --pmc: 3.3 GB fetched, 1.5 GB written in 1.48 ms -- and the same kernel with the element geometry for nothing is no faster,
@@ -1002,8 +1041,8 @@ __device__ __forceinline__ int64_t xcd_contiguous_block(unsigned b, unsigned per
 // LDSACC: the node's row is accumulated in LDS (entry k of thread t at acc[k*T + t], T = block
 // size: conflict free) and written out once, coalesced, instead of ~6 global read-modify-writes
 // per entry; the caller provides maxlen*T*8 bytes of dynamic LDS.  Same additions in the same order.
-template <int KIND, bool LDSACC>
-__global__ void __launch_bounds__(kBlock) k_gather_scalar(MeshDev m, SellDev A, double *rhs, ElemPrm prm,
+template <int KIND, bool LDSACC, class PRM = ElemPrm>
+__global__ void __launch_bounds__(kBlock) k_gather_scalar(MeshDev m, SellDev A, double *rhs, PRM prm,
                                                            const int64_t *__restrict__ inc_ptr,
                                                            const int32_t *__restrict__ inc_cnt,
                                                            const int4 *__restrict__ inc_rec,
@@ -1049,6 +1088,7 @@ __global__ void __launch_bounds__(kBlock) k_gather_scalar(MeshDev m, SellDev A, 
         }
         // this node's entries of the element: Klocal(a,:) for the lifting, Klocal(:,a) for the row
         double Krow[NPE], Kcol[NPE], f = 0.0;
+        const double *ed = prm_visit(prm, t);
         bool ok;
         if constexpr (KIND == PFEM_POISSON_TET) {
             bool any_fixed = false;
@@ -1056,11 +1096,11 @@ __global__ void __launch_bounds__(kBlock) k_gather_scalar(MeshDev m, SellDev A, 
             for (int i = 0; i < NPE; ++i) any_fixed |= fixed[i];
 #pragma unroll
             for (int i = 0; i < NPE; ++i) Krow[i] = 0.0;
-            ok = poisson_tet_node_lean(x, y, z, prm.ed[0], prm.ed[1], prm.ed[2], prm.af, a, any_fixed, Kcol, Krow, f);
+            ok = poisson_tet_node_lean(x, y, z, ed[0], ed[1], ed[2], prm.af, a, any_fixed, Kcol, Krow, f);
         } else {
             double K[NPE * NPE], F[NPE];
             if constexpr (KIND == PFEM_POISSON_TRIA)
-                ok = poisson_tria(x, y, prm.ed[0], prm.ed[1], prm.af, valC, K, F);
+                ok = poisson_tria(x, y, ed[0], ed[1], prm.af, valC, K, F);
             else
                 ok = poisson_tria_inline(x, y, K, F);
 #pragma unroll
@@ -1101,7 +1141,7 @@ __global__ void __launch_bounds__(kBlock) k_pack_node4(MeshDev m, double4 *__res
 // node A of the element (self) and c0, c1, c2 the element's other three nodes in their local order
 template <int A>
 __device__ __forceinline__ bool gather_visit(const double4 &self, const double4 &c0, const double4 &c1, const double4 &c2, uint32_t slots,
-                                             const ElemPrm &prm, double *acc, int T, double &facc)
+                                             const double *ed, double af, double *acc, int T, double &facc)
 {
     const double4 &n0 = A == 0 ? self : c0;
     const double4 &n1 = A == 1 ? self : (A < 1 ? c0 : c1);
@@ -1116,7 +1156,7 @@ __device__ __forceinline__ bool gather_visit(const double4 &self, const double4 
         any_fixed |= fixed[i];
     }
     double Krow[4] = {0.0, 0.0, 0.0, 0.0}, Kcol[4], f = 0.0;
-    if (!poisson_tet_node_lean(x, y, z, prm.ed[0], prm.ed[1], prm.ed[2], prm.af, A, any_fixed, Kcol, Krow, f)) return false;
+    if (!poisson_tet_node_lean(x, y, z, ed[0], ed[1], ed[2], af, A, any_fixed, Kcol, Krow, f)) return false;
 #pragma unroll
     for (int i = 0; i < 4; ++i)            // Flocal(a) -= Klocal(a,i)*u_D(i)   (:859-870)
         if (fixed[i]) f = f - Krow[i] * ud[i];
@@ -1137,7 +1177,8 @@ __device__ __forceinline__ bool gather_visit(const double4 &self, const double4 
 // the coordinates and the Dirichlet value of a node come from ONE 32-B record (k_pack_node4) instead of four arrays
 // -- the gathers, not the streamed incidence records, were what kept this kernel waiting: 9 scattered 8-B reads per visit
 // -- and the next incidence record is already in flight while an element is evaluated.
-__global__ void __launch_bounds__(kBlock) k_gather_poisson_tet4(int64_t nNode, SellDev A, double *rhs, ElemPrm prm,
+template <class PRM = ElemPrm>
+__global__ void __launch_bounds__(kBlock) k_gather_poisson_tet4(int64_t nNode, SellDev A, double *rhs, PRM prm,
                                                                  const int64_t *__restrict__ inc_ptr,
                                                                  const int32_t *__restrict__ inc_cnt,
                                                                  const int4 *__restrict__ inc_rec,
@@ -1189,6 +1230,20 @@ __global__ void __launch_bounds__(kBlock) k_gather_poisson_tet4(int64_t nNode, S
     } else {
         co[0] = co[1] = co[2] = double4{0.0, 0.0, 0.0, 0.0};
     }
+    // (several materials: the visit's byte comes from the node's own stream whichever records it reads.  Byte -> row of the
+    // table -> arithmetic is a chain of two dependent loads: like the records, the byte is fetched two visits ahead and the
+    // three conductivities of the row one visit ahead)
+    const uint8_t *mp = nullptr;
+    int mat_next2 = 0;
+    double ed_next[3] = {0.0, 0.0, 0.0};
+    if constexpr (PrmTraits<PRM>::kTab) {
+        mp = prm.inc_mat + (inc_ptr[n >> 6] + (n & 63));
+        if (cnt > 0) {
+            const double *r0 = prm.tab + prm.stride * static_cast<int>(mp[0]);
+            ed_next[0] = r0[0]; ed_next[1] = r0[1]; ed_next[2] = r0[2];
+        }
+        if (cnt > 1) mat_next2 = mp[64];
+    }
     bool neg_jac = false;
     // (the slot of the row's own column -- the diagonal -- is the node's own slot in any of its visits: the first one's)
     const int kd = cnt > 0 ? static_cast<int>((static_cast<uint32_t>(rc_next.w) >>
@@ -1205,12 +1260,24 @@ __global__ void __launch_bounds__(kBlock) k_gather_poisson_tet4(int64_t nNode, S
         }
         const uint32_t slots = static_cast<uint32_t>(rc.w);
         const int a = static_cast<int>((static_cast<uint32_t>(rc.x) >> 31) | ((static_cast<uint32_t>(rc.y) >> 31) << 1));
+        const double ed_cur[3] = {ed_next[0], ed_next[1], ed_next[2]};
+        const double *ed;
+        if constexpr (PrmTraits<PRM>::kTab) {
+            ed = ed_cur;
+            if (v + 1 < cnt) {
+                const double *r1 = prm.tab + prm.stride * mat_next2;
+                ed_next[0] = r1[0]; ed_next[1] = r1[1]; ed_next[2] = r1[2];
+                if (v + 2 < cnt) mat_next2 = mp[static_cast<int64_t>(v + 2) * 64];
+            }
+        } else {
+            ed = prm.ed;
+        }
         bool ok = true;
         switch (a) {
-        case 0: ok = gather_visit<0>(self, c0, c1, c2, slots, prm, acc, T, facc); break;
-        case 1: ok = gather_visit<1>(self, c0, c1, c2, slots, prm, acc, T, facc); break;
-        case 2: ok = gather_visit<2>(self, c0, c1, c2, slots, prm, acc, T, facc); break;
-        default: ok = gather_visit<3>(self, c0, c1, c2, slots, prm, acc, T, facc); break;
+        case 0: ok = gather_visit<0>(self, c0, c1, c2, slots, ed, prm.af, acc, T, facc); break;
+        case 1: ok = gather_visit<1>(self, c0, c1, c2, slots, ed, prm.af, acc, T, facc); break;
+        case 2: ok = gather_visit<2>(self, c0, c1, c2, slots, ed, prm.af, acc, T, facc); break;
+        default: ok = gather_visit<3>(self, c0, c1, c2, slots, ed, prm.af, acc, T, facc); break;
         }
         neg_jac = neg_jac || !ok;
     }
@@ -1265,7 +1332,8 @@ __global__ void __launch_bounds__(kBlock) k_gather_poisson_tet4(int64_t nNode, S
 // stored once, coalesced -- no read-modify-write of the matrix in global memory (what bounded
 // the thread-per-node form: 5.0 ms on the 50x300x50 beam).  The three threads of a node walk the same packed incidence list and
 // recompute the element geometry; same additions in the same (ascending element) order.
-__global__ void __launch_bounds__(kBlock) k_gather_elast_rows(MeshDev m, SellDev A, double *rhs, ElemPrm prm,
+template <class PRM = ElemPrm>
+__global__ void __launch_bounds__(kBlock) k_gather_elast_rows(MeshDev m, SellDev A, double *rhs, PRM prm,
                                                                const int64_t *__restrict__ inc_ptr,
                                                                const int32_t *__restrict__ inc_cnt,
                                                                const int4 *__restrict__ inc_rec,
@@ -1297,10 +1365,24 @@ __global__ void __launch_bounds__(kBlock) k_gather_elast_rows(MeshDev m, SellDev
     const int len = A.rowlen[row];
     double *acc = lds_acc + threadIdx.x;
     for (int k = 0; k < len; ++k) acc[k * T] = 0.0;
-    const ElastMat mat = elast_material(prm.ed[0], prm.ed[1]);
-    const double bf = p == 0 ? prm.ed[3] : (p == 1 ? prm.ed[4] : prm.ed[5]);
+    // (several materials: the material constants once per visit, from the row the node's own byte stream names)
+    const double *ed0;
+    const uint8_t *mp = nullptr;
+    if constexpr (PrmTraits<PRM>::kTab) {
+        mp = prm.inc_mat + (inc_ptr[n >> 6] + (n & 63));
+        ed0 = prm.tab;
+    } else {
+        ed0 = prm.ed;
+    }
+    ElastMat mat = elast_material(ed0[0], ed0[1]);
+    double bf = p == 0 ? ed0[3] : (p == 1 ? ed0[4] : ed0[5]);
     double facc = 0.0;
     for (int v = 0; v < cnt; ++v) {
+        if constexpr (PrmTraits<PRM>::kTab) {
+            const double *ed = prm.tab + prm.stride * static_cast<int>(mp[static_cast<int64_t>(v) * 64]);
+            mat = elast_material(ed[0], ed[1]);
+            bf = p == 0 ? ed[3] : (p == 1 ? ed[4] : ed[5]);
+        }
         const int4 rc = rp[static_cast<int64_t>(v) * rstep];
         const uint32_t flags = fp[static_cast<int64_t>(v) * rstep];
         const uint32_t slots = static_cast<uint32_t>(rc.w);
@@ -1373,7 +1455,8 @@ __global__ void __launch_bounds__(kBlock) k_gather_elast_rows(MeshDev m, SellDev
 // plane-stress elasticity on P1 triangles (2 dofs per node, next row 8f.1): same two
 // formulations as the tetrahedron kernels, 2x2 node blocks from elast2d_block_v
 // ---------------------------------------------------------------------------
-__global__ void __launch_bounds__(kBlock) k_assemble_elast2d(MeshDev m, SellDev A, double *rhs, ElemPrm prm, int *err,
+template <class PRM = ElemPrm>
+__global__ void __launch_bounds__(kBlock) k_assemble_elast2d(MeshDev m, SellDev A, double *rhs, PRM prm, int *err,
                                                               const uint8_t *__restrict__ only_nodes)
 {
     const int64_t e = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
@@ -1390,15 +1473,16 @@ __global__ void __launch_bounds__(kBlock) k_assemble_elast2d(MeshDev m, SellDev 
     TriaGeom g;
     tria_geometry(x, y, g);
     if (g.jac < 0.0) { atomicMax(err, PFEM_ERR_NEG_JAC); return; }
-    const double dvol = 0.5 * (g.jac * prm.ed[2]);
-    const Elast2dMat mat = elast2d_material(prm.ed[0], prm.ed[1]);
+    const double *ed = prm_elem(prm, e);
+    const double dvol = 0.5 * (g.jac * ed[2]);
+    const Elast2dMat mat = elast2d_material(ed[0], ed[1]);
     double N[3], F[6], fact[6];
     tria_shape_gp(N);
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         const double b4 = dvol * N[a];
-        F[2 * a] = 0.0 + b4 * prm.ed[3];
-        F[2 * a + 1] = 0.0 + b4 * prm.ed[4];
+        F[2 * a] = 0.0 + b4 * ed[3];
+        F[2 * a + 1] = 0.0 + b4 * ed[4];
     }
 #pragma unroll
     for (int i = 0; i < 6; ++i) fact[i] = dof[i] < 0 ? m.soln[2LL * nd[i / 2] + i % 2] : 0.0;
@@ -1440,7 +1524,8 @@ __global__ void __launch_bounds__(kBlock) k_assemble_elast2d(MeshDev m, SellDev 
 }
 
 // Plane-stress sibling of k_gather_elast_rows: one thread per (node, dof) row, 2x2 node blocks.
-__global__ void __launch_bounds__(kBlock) k_gather_elast2d_rows(MeshDev m, SellDev A, double *rhs, ElemPrm prm,
+template <class PRM = ElemPrm>
+__global__ void __launch_bounds__(kBlock) k_gather_elast2d_rows(MeshDev m, SellDev A, double *rhs, PRM prm,
                                                                  const int64_t *__restrict__ inc_ptr,
                                                                  const int32_t *__restrict__ inc_cnt,
                                                                  const int4 *__restrict__ inc_rec,
@@ -1461,12 +1546,23 @@ __global__ void __launch_bounds__(kBlock) k_gather_elast2d_rows(MeshDev m, SellD
     const int len = A.rowlen[row];
     double *acc = lds_acc + threadIdx.x;
     for (int k = 0; k < len; ++k) acc[k * T] = 0.0;
-    const Elast2dMat mat = elast2d_material(prm.ed[0], prm.ed[1]);
+    Elast2dMat mat;
     double N[3];
     tria_shape_gp(N);
-    const double bf = p == 0 ? prm.ed[3] : prm.ed[4];
+    double bf = 0.0, thick = 0.0;
+    if constexpr (!PrmTraits<PRM>::kTab) {
+        mat = elast2d_material(prm.ed[0], prm.ed[1]);
+        bf = p == 0 ? prm.ed[3] : prm.ed[4];
+        thick = prm.ed[2];
+    }
     double facc = 0.0;
     for (int64_t t = beg; t < end; t += 64) {
+        if constexpr (PrmTraits<PRM>::kTab) {
+            const double *ed = prm_visit(prm, t);
+            mat = elast2d_material(ed[0], ed[1]);
+            bf = p == 0 ? ed[3] : ed[4];
+            thick = ed[2];
+        }
         const int4 rc = inc_rec[t];
         const uint32_t flags = inc_flags[t];
         const uint32_t slots = static_cast<uint32_t>(rc.w);
@@ -1482,7 +1578,7 @@ __global__ void __launch_bounds__(kBlock) k_gather_elast2d_rows(MeshDev m, SellD
         TriaGeom g;
         tria_geometry(x, y, g);
         if (g.jac < 0.0) { atomicMax(err, PFEM_ERR_NEG_JAC); return; }
-        const double dvol = 0.5 * (g.jac * prm.ed[2]);
+        const double dvol = 0.5 * (g.jac * thick);
         double ax = g.gx[0], ay = g.gy[0], na = N[0];
 #pragma unroll
         for (int i = 1; i < 3; ++i)
@@ -1517,7 +1613,8 @@ __global__ void __launch_bounds__(kBlock) k_gather_elast2d_rows(MeshDev m, SellD
 }
 
 // Parity inspection: Ke/Fe of every element exactly as the assembly kernels compute them.
-__global__ void __launch_bounds__(kBlock) k_eval_elems(MeshDev m, ElemPrm prm, double *Kout, double *Fout, int *err)
+template <class PRM = ElemPrm>
+__global__ void __launch_bounds__(kBlock) k_eval_elems(MeshDev m, PRM prm, double *Kout, double *Fout, int *err)
 {
     const int64_t e = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
     if (e >= m.nElem) return;
@@ -1530,19 +1627,20 @@ __global__ void __launch_bounds__(kBlock) k_eval_elems(MeshDev m, ElemPrm prm, d
     }
     const double valC[4] = {0.0, 0.0, 0.0, 0.0};
     double *K = Kout + e * m.nsize * m.nsize, *F = Fout + e * m.nsize;
+    const double *ed = prm_elem(prm, e);
     bool ok = false;
     switch (m.kind) {
-    case PFEM_POISSON_TET: ok = poisson_tet(x, y, z, prm.ed[0], prm.ed[1], prm.ed[2], prm.af, valC, K, F); break;
-    case PFEM_POISSON_TRIA: ok = poisson_tria(x, y, prm.ed[0], prm.ed[1], prm.af, valC, K, F); break;
+    case PFEM_POISSON_TET: ok = poisson_tet(x, y, z, ed[0], ed[1], ed[2], prm.af, valC, K, F); break;
+    case PFEM_POISSON_TRIA: ok = poisson_tria(x, y, ed[0], ed[1], prm.af, valC, K, F); break;
     case PFEM_POISSON_TRIA_INLINE: ok = poisson_tria_inline(x, y, K, F); break;
     case PFEM_ELAST_TET: {
-        const double bf[3] = {prm.ed[3], prm.ed[4], prm.ed[5]};
-        ok = elast_tet(x, y, z, prm.ed[0], prm.ed[1], bf, K, F);
+        const double bf[3] = {ed[3], ed[4], ed[5]};
+        ok = elast_tet(x, y, z, ed[0], ed[1], bf, K, F);
         break;
     }
     case PFEM_ELAST_TRIA: {
-        const double bf[2] = {prm.ed[3], prm.ed[4]};
-        ok = elast_tria(x, y, prm.ed[0], prm.ed[1], prm.ed[2], bf, K, F);
+        const double bf[2] = {ed[3], ed[4]};
+        ok = elast_tria(x, y, ed[0], ed[1], ed[2], bf, K, F);
         break;
     }
     }
@@ -1601,8 +1699,8 @@ __device__ __forceinline__ void post_load_elem(const MeshDev &m, const int nd[4]
 }
 
 // One thread per element: gradient / strain, flux / stress, |q| / von Mises, stored SoA (component-major, coalesced in e).
-template <int KIND>
-__global__ void __launch_bounds__(kBlock) k_post_elements(MeshDev m, ElemPrm prm, const double *__restrict__ u, double *__restrict__ grad,
+template <int KIND, class PRM = ElemPrm>
+__global__ void __launch_bounds__(kBlock) k_post_elements(MeshDev m, PRM prm, const double *__restrict__ u, double *__restrict__ grad,
                                                            double *__restrict__ flux, double *__restrict__ scalar, int *err)
 {
     using P = PostKind<KIND>;
@@ -1613,7 +1711,7 @@ __global__ void __launch_bounds__(kBlock) k_post_elements(MeshDev m, ElemPrm prm
     for (int a = 0; a < P::NPE; ++a) nd[a] = m.conn[a * m.nElem + e];
     double x[4], y[4], z[4], valC[12], g[6], f[6], fint[12], sc, dvol;
     post_load_elem<KIND>(m, nd, u, x, y, z, valC);
-    if (!elem_post(KIND, x, y, z, prm.ed, valC, g, f, sc, fint, dvol)) { atomicMax(err, PFEM_ERR_NEG_JAC); return; }
+    if (!elem_post(KIND, x, y, z, prm_elem(prm, e), valC, g, f, sc, fint, dvol)) { atomicMax(err, PFEM_ERR_NEG_JAC); return; }
 #pragma unroll
     for (int c = 0; c < P::NG; ++c) {
         if (grad) grad[c * m.nElem + e] = g[c];
@@ -1628,8 +1726,8 @@ __global__ void __launch_bounds__(kBlock) k_post_elements(MeshDev m, ElemPrm prm
 // read, not the pattern table of the assembly (k_incpat_*): that table covers nodes with a matrix row only, and the reactions
 // live at the nodes without one.  Hub nodes have no records (k_build_inc_rec): their entries are zeroed here and summed by
 // k_post_forces_scatter restricted to them.
-template <int KIND>
-__global__ void __launch_bounds__(kBlock) k_post_forces_gather(MeshDev m, ElemPrm prm, const int64_t *__restrict__ inc_ptr,
+template <int KIND, class PRM = ElemPrm>
+__global__ void __launch_bounds__(kBlock) k_post_forces_gather(MeshDev m, PRM prm, const int64_t *__restrict__ inc_ptr,
                                                                 const int32_t *__restrict__ inc_cnt, const int4 *__restrict__ inc_rec,
                                                                 const uint8_t *__restrict__ node_hub, const double *__restrict__ u,
                                                                 double *__restrict__ R, int *err)
@@ -1654,7 +1752,7 @@ __global__ void __launch_bounds__(kBlock) k_post_forces_gather(MeshDev m, ElemPr
         }
         double x[4], y[4], z[4], valC[12], r[12];
         post_load_elem<KIND>(m, nd, u, x, y, z, valC);
-        if (!elem_nodal_forces(KIND, x, y, z, prm.ed, prm.af, valC, r)) { atomicMax(err, PFEM_ERR_NEG_JAC); continue; }
+        if (!elem_nodal_forces(KIND, x, y, z, prm_visit(prm, t), prm.af, valC, r)) { atomicMax(err, PFEM_ERR_NEG_JAC); continue; }
 #pragma unroll
         for (int i = 0; i < P::NPE; ++i)
             if (i == a) {
@@ -1668,8 +1766,8 @@ __global__ void __launch_bounds__(kBlock) k_post_forces_gather(MeshDev m, ElemPr
 
 // The same sums, scatter form: one thread per element, f64 atomics into R (zeroed by the caller).  only_nodes != nullptr: the
 // hub pass of the gather form -- only the entries of flagged nodes are added.
-template <int KIND>
-__global__ void __launch_bounds__(kBlock) k_post_forces_scatter(MeshDev m, ElemPrm prm, const uint8_t *__restrict__ only_nodes,
+template <int KIND, class PRM = ElemPrm>
+__global__ void __launch_bounds__(kBlock) k_post_forces_scatter(MeshDev m, PRM prm, const uint8_t *__restrict__ only_nodes,
                                                                  const double *__restrict__ u, double *R, int *err)
 {
     using P = PostKind<KIND>;
@@ -1685,7 +1783,7 @@ __global__ void __launch_bounds__(kBlock) k_post_forces_scatter(MeshDev m, ElemP
     if (!any) return;
     double x[4], y[4], z[4], valC[12], r[12];
     post_load_elem<KIND>(m, nd, u, x, y, z, valC);
-    if (!elem_nodal_forces(KIND, x, y, z, prm.ed, prm.af, valC, r)) { atomicMax(err, PFEM_ERR_NEG_JAC); return; }
+    if (!elem_nodal_forces(KIND, x, y, z, prm_elem(prm, e), prm.af, valC, r)) { atomicMax(err, PFEM_ERR_NEG_JAC); return; }
 #pragma unroll
     for (int a = 0; a < P::NPE; ++a) {
         if (only_nodes && !only_nodes[nd[a]]) continue;
@@ -1700,8 +1798,8 @@ __global__ void __launch_bounds__(kBlock) k_post_forces_scatter(MeshDev m, ElemP
 // A node without elements stores zeros.  Hub nodes have no records: zeros here, which k_post_recovery_scatter(only_nodes) and
 // k_post_recovery_divide(only_nodes) turn into their values.  Traffic per record: 16 B of record, (NPE - 1) (NDIM + NDOF)
 // doubles of the other nodes through L2; the node's own coordinates and values are loaded again with each record (L1 hits).
-template <int KIND>
-__global__ void __launch_bounds__(kBlock) k_post_recovery_gather(MeshDev m, ElemPrm prm, const int64_t *__restrict__ inc_ptr,
+template <int KIND, class PRM = ElemPrm>
+__global__ void __launch_bounds__(kBlock) k_post_recovery_gather(MeshDev m, PRM prm, const int64_t *__restrict__ inc_ptr,
                                                                   const int32_t *__restrict__ inc_cnt, const int4 *__restrict__ inc_rec,
                                                                   const uint8_t *__restrict__ node_hub, const double *__restrict__ u,
                                                                   int use_grad, double *__restrict__ nodal, double *__restrict__ nscalar,
@@ -1727,7 +1825,7 @@ __global__ void __launch_bounds__(kBlock) k_post_recovery_gather(MeshDev m, Elem
         }
         double x[4], y[4], z[4], valC[12], g[6], f[6], fint[12], sc, dvol;
         post_load_elem<KIND>(m, nd, u, x, y, z, valC);
-        if (!elem_post(KIND, x, y, z, prm.ed, valC, g, f, sc, fint, dvol)) { atomicMax(err, PFEM_ERR_NEG_JAC); continue; }
+        if (!elem_post(KIND, x, y, z, prm_visit(prm, t), valC, g, f, sc, fint, dvol)) { atomicMax(err, PFEM_ERR_NEG_JAC); continue; }
 #pragma unroll
         for (int c = 0; c < P::NG; ++c) acc[c] += dvol * (use_grad ? g[c] : f[c]);
         wsum += dvol;
@@ -1745,8 +1843,8 @@ __global__ void __launch_bounds__(kBlock) k_post_recovery_gather(MeshDev m, Elem
 // The numerators sum_e w_e f_c(e) into nodal and the weights sum_e w_e into weight (both zeroed by the caller; weight is never
 // NULL here), scatter form: one thread per element, f64 atomics.  only_nodes != nullptr: the hub pass of the gather form -- only
 // the entries of flagged nodes (zeroed by k_post_recovery_gather) are added.  k_post_recovery_divide finishes.
-template <int KIND>
-__global__ void __launch_bounds__(kBlock) k_post_recovery_scatter(MeshDev m, ElemPrm prm, const uint8_t *__restrict__ only_nodes,
+template <int KIND, class PRM = ElemPrm>
+__global__ void __launch_bounds__(kBlock) k_post_recovery_scatter(MeshDev m, PRM prm, const uint8_t *__restrict__ only_nodes,
                                                                    const double *__restrict__ u, int use_grad, double *nodal,
                                                                    double *weight, int *err)
 {
@@ -1763,7 +1861,7 @@ __global__ void __launch_bounds__(kBlock) k_post_recovery_scatter(MeshDev m, Ele
     if (!any) return;
     double x[4], y[4], z[4], valC[12], g[6], f[6], fint[12], sc, dvol;
     post_load_elem<KIND>(m, nd, u, x, y, z, valC);
-    if (!elem_post(KIND, x, y, z, prm.ed, valC, g, f, sc, fint, dvol)) { atomicMax(err, PFEM_ERR_NEG_JAC); return; }
+    if (!elem_post(KIND, x, y, z, prm_elem(prm, e), valC, g, f, sc, fint, dvol)) { atomicMax(err, PFEM_ERR_NEG_JAC); return; }
 #pragma unroll
     for (int a = 0; a < P::NPE; ++a) {
         if (only_nodes && !only_nodes[nd[a]]) continue;
@@ -1796,8 +1894,8 @@ __global__ void __launch_bounds__(kBlock) k_post_recovery_divide(int64_t nNode, 
 // ZZ indicator: one thread per element gathers the NPE * NG recovered values of its nodes and evaluates elem_recovery_error;
 // eta2[e] (coalesced) and the block's partial sums of eta2 and flux_norm2 in block_sum's fixed order (k_reduce_partials adds
 // the partials).  The grid is grid_for(nElem) blocks wide at most kMaxGrid: a block strides over the elements.
-template <int KIND>
-__global__ void __launch_bounds__(kBlock) k_post_indicator(MeshDev m, ElemPrm prm, const double *__restrict__ u, const double *__restrict__ nodal,
+template <int KIND, class PRM = ElemPrm>
+__global__ void __launch_bounds__(kBlock) k_post_indicator(MeshDev m, PRM prm, const double *__restrict__ u, const double *__restrict__ nodal,
                                                             double *__restrict__ eta2, double *part_eta, double *part_fn, int *err)
 {
     using P = PostKind<KIND>;
@@ -1813,7 +1911,7 @@ __global__ void __launch_bounds__(kBlock) k_post_indicator(MeshDev m, ElemPrm pr
         for (int a = 0; a < P::NPE; ++a)
 #pragma unroll
             for (int c = 0; c < P::NG; ++c) nf[a * P::NG + c] = nodal[static_cast<int64_t>(nd[a]) * P::NG + c];
-        if (!elem_recovery_error(KIND, x, y, z, prm.ed, valC, nf, e2, f2)) { atomicMax(err, PFEM_ERR_NEG_JAC); continue; }
+        if (!elem_recovery_error(KIND, x, y, z, prm_elem(prm, e), valC, nf, e2, f2)) { atomicMax(err, PFEM_ERR_NEG_JAC); continue; }
         if (eta2) eta2[e] = e2;
         se += e2;
         sf += f2;

@@ -35,7 +35,8 @@ class Result:
     reason: int
     rnorm: float
     timers: dict = field(default_factory=dict)
-    elemData: np.ndarray | None = None   # what the element loop ran with (post-processing of the solution)
+    elemData: np.ndarray | None = None   # what the element loop ran with (post-processing of the solution): one vector, or
+    elem_mat: np.ndarray | None = None   # -- with a material id per element (the mesh's element order) -- the (n_mat, stride) table
 
     def temp_dat(self):
         """Rows of the reference's ``temp.dat`` dump (tetrapoissonparallelimpl1.F:935-942):
@@ -53,7 +54,8 @@ class Result:
         legacy VTK file through the writervtk.F-compatible writer (:944-966).  ``fields=True`` also writes
         ``<name>-fields.vtk``: the same file with the element flux / stress, its scalar and the Zienkiewicz-Zhu indicator
         ``eta = sqrt(eta2)`` as cell arrays and the recovered nodal flux / stress and its scalar as point arrays, by OLD node id
-        like ``solnVTK`` (one rank and ``mode="batched"``: the library's PFEM_ERR_STATE otherwise)."""
+        like ``solnVTK`` (one rank and ``mode="batched"``: the library's PFEM_ERR_STATE otherwise).  A run with several materials
+        (``elem_mat``) evaluates them with its table, and the file carries the cell scalar ``material``."""
         import os
         ndof = self.dm.NodeDofArrayNew.shape[1]
         ii, ind, val = self.temp_dat()
@@ -74,9 +76,12 @@ class Result:
                 return out
 
             f, sc = ("flux", "flux_magnitude") if ndof == 1 else ("stress", "von_mises")
+            cells = {f: flux.T, sc: scalar, "eta": np.sqrt(eta2)}
+            if self.elem_mat is not None:
+                cells["material"] = np.asarray(self.elem_mat, np.float64)
             H.writeoutputvtk_fields(self.mesh.xyz.shape[0], self.mesh.xyz, self.mesh.conn, pid, self.solnVTK,
                                     os.path.join(directory, name[:-4] + "-fields.vtk"), ndof=ndof,
-                                    cell_fields={f: flux.T, sc: scalar, "eta": np.sqrt(eta2)},
+                                    cell_fields=cells,
                                     point_fields={f + "_recovered": by_old(nodal), sc + "_recovered": by_old(nscalar)},
                                     voigt=() if ndof == 1 else (f, f + "_recovered"))
         return os.path.join(directory, name)
@@ -91,17 +96,34 @@ def _setup(kind, mesh: H.Mesh, nParts=1, node_proc_id=None):
     return dm, conn_new, xyz_new, edof
 
 
-def _finish(kind, mesh, dm, solver, its, reason, rnorm, timers, u_free, elemData=None):
+def _finish(kind, mesh, dm, solver, its, reason, rnorm, timers, u_free, elemData=None, elem_mat=None):
     ndof = L.NDOF[kind]
     full = dm.solnApplied.reshape(-1, ndof).copy()                       # :914-918 applied BC values
     assy = H.assy_for_soln(dm.NodeDofArrayNew)                           # :722-734
     full.reshape(-1)[assy] = u_free                                      # :936-941
     solnVTK = np.empty_like(full)
     solnVTK[dm.node_map_get_old] = full
-    return Result(kind, mesh, dm, solver, u_free, solnVTK, its, reason, rnorm, timers, elemData)
+    return Result(kind, mesh, dm, solver, u_free, solnVTK, its, reason, rnorm, timers, elemData, elem_mat)
 
 
-def _run(kind, mesh, elemData, timeData, mode, rtol, maxits, verbose, pc=None):
+def _materials(mesh, elemData, elem_mat):
+    """``(table, ids)`` of a run with several materials: ``elem_mat[e]`` names the row of the 2-D ``elemData`` that element
+    ``e`` of ``mesh.conn`` uses; ``(elemData, None)`` without ``elem_mat``."""
+    if elem_mat is None:
+        return elemData, None
+    if elemData is None:
+        raise ValueError("elem_mat needs the elemData table, one row per material")
+    table = np.ascontiguousarray(elemData, dtype=np.float64)
+    ids = np.ascontiguousarray(elem_mat, dtype=np.int32).ravel()
+    if table.ndim != 2:
+        raise ValueError("with elem_mat, elemData is a 2-D (n_mat, stride) table")
+    if ids.size != mesh.nElem or (ids.size and (ids.min() < 0 or ids.max() >= table.shape[0])):
+        raise ValueError("elem_mat: one id in 0 .. n_mat-1 per element of the mesh")
+    return table, ids
+
+
+def _run(kind, mesh, elemData, timeData, mode, rtol, maxits, verbose, pc=None, elem_mat=None):
+    elemData, elem_mat = _materials(mesh, elemData, elem_mat)
     dm, conn_new, xyz_new, edof = _setup(kind, mesh)
     N = dm.size_global
     nsize = edof.shape[0]
@@ -115,6 +137,8 @@ def _run(kind, mesh, elemData, timeData, mode, rtol, maxits, verbose, pc=None):
         solver.setPreconditioner(pc)
     if mode == "batched":
         solver.uploadMesh(kind, conn_new, xyz_new, edof, dm.solnApplied)
+        if elem_mat is not None:                                         # (the renumbering moves nodes, not elements)
+            solver.setMaterials(elem_mat, n_mat=elemData.shape[0], stride=elemData.shape[1])
         solver.buildPattern()                                            # :786-802
         t0 = time.perf_counter()                                         # tstart :826
         solver.assemble(elemData, timeData)                              # setZero :817 + loop :828-884
@@ -130,14 +154,15 @@ def _run(kind, mesh, elemData, timeData, mode, rtol, maxits, verbose, pc=None):
         for e in range(mesh.nElem):                                      # :828-884
             nd = conn_new[:, e]
             xN, yN = xyz_new[0, nd], xyz_new[1, nd]
+            ed = elemData if elem_mat is None else elemData[elem_mat[e]]  # the element's own row of the table
             if kind == L.POISSON_TET:
-                K, F = H.StiffnessResidualPoissonLinearTetra(xN, yN, xyz_new[2, nd], elemData, timeData, valC)
+                K, F = H.StiffnessResidualPoissonLinearTetra(xN, yN, xyz_new[2, nd], ed, timeData, valC)
             elif kind == L.ELAST_TET:
-                K, F = H.StiffnessResidualElasticityLinearTetra(xN, yN, xyz_new[2, nd], elemData, timeData, valC)
+                K, F = H.StiffnessResidualElasticityLinearTetra(xN, yN, xyz_new[2, nd], ed, timeData, valC)
             elif kind == L.POISSON_TRIA:
-                K, F = H.StiffnessResidualPoissonLinearTria(xN, yN, elemData, timeData, valC)
+                K, F = H.StiffnessResidualPoissonLinearTria(xN, yN, ed, timeData, valC)
             elif kind == L.ELAST_TRIA:
-                K, F = H.StiffnessResidualElasticityLinearTria(xN, yN, elemData, timeData, valC)
+                K, F = H.StiffnessResidualElasticityLinearTria(xN, yN, ed, timeData, valC)
             else:
                 raise ValueError("compat mode needs a module element routine")
             f = edof[:, e]
@@ -166,7 +191,7 @@ def _run(kind, mesh, elemData, timeData, mode, rtol, maxits, verbose, pc=None):
         print("Divergence." if reason < 0 else f" Convergence in {its} iterations.")
     u = solver.getSolution()                                             # VecScatterCreateToAll + VecGetArray :922-932
     timers.update(solver.timings())
-    return _finish(kind, mesh, dm, solver, its, reason, rnorm, timers, u, elemData)
+    return _finish(kind, mesh, dm, solver, its, reason, rnorm, timers, u, elemData, elem_mat)
 
 
 def run_parallel(kind, mesh: H.Mesh, elem_proc_id, node_proc_id, dist, torch, elemData=None, timeData=None, rtol=1e-5,
@@ -220,39 +245,51 @@ def run_parallel(kind, mesh: H.Mesh, elem_proc_id, node_proc_id, dist, torch, el
     return _finish(kind, mesh, dm, solver, its, reason, rnorm, timers, u, elemData)
 
 
-def tetrapoissonparallelimpl1(mesh: H.Mesh | str, mode="batched", rtol=1e-5, maxits=10000, verbose=False, pc=None) -> Result:
-    """PROGRAM TetraMeshPoissonEquation (tetrapoissonparallelimpl1.F) on one rank / one GPU."""
+def tetrapoissonparallelimpl1(mesh: H.Mesh | str, mode="batched", rtol=1e-5, maxits=10000, verbose=False, pc=None, elem_mat=None,
+                              elemData=None) -> Result:
+    """PROGRAM TetraMeshPoissonEquation (tetrapoissonparallelimpl1.F) on one rank / one GPU.  ``elemData``: another vector than
+    the PROGRAM's, or -- with ``elem_mat``, one material id per element -- the ``(n_mat, stride)`` table of a body of several
+    materials (all five drivers; not part of the reference, whose drivers hard-code one material)."""
     if isinstance(mesh, str):
         mesh = H.read_mesh(mesh)
-    return _run(L.POISSON_TET, mesh, H.POISSON_ELEMDATA, H.TIMEDATA, mode, rtol, maxits, verbose, pc)   # :822-824
+    ed = H.POISSON_ELEMDATA if elemData is None else elemData
+    return _run(L.POISSON_TET, mesh, ed, H.TIMEDATA, mode, rtol, maxits, verbose, pc, elem_mat)   # :822-824
 
 
-def tetraelasticityparallelimpl1(mesh: H.Mesh | str, mode="batched", rtol=1e-5, maxits=10000, verbose=False, pc=None) -> Result:
+def tetraelasticityparallelimpl1(mesh: H.Mesh | str, mode="batched", rtol=1e-5, maxits=10000, verbose=False, pc=None, elem_mat=None,
+                                 elemData=None) -> Result:
     """PROGRAM of tetraelasticityparallelimpl1.F (body force only; DESIGN.md 'deviations')."""
     if isinstance(mesh, str):
         mesh = H.read_mesh(mesh)
-    return _run(L.ELAST_TET, mesh, H.ELAST_ELEMDATA, H.TIMEDATA, mode, rtol, maxits, verbose, pc)       # :894-902
+    ed = H.ELAST_ELEMDATA if elemData is None else elemData
+    return _run(L.ELAST_TET, mesh, ed, H.TIMEDATA, mode, rtol, maxits, verbose, pc, elem_mat)       # :894-902
 
 
-def triapoissonserialimpl1(mesh: H.Mesh | str, rtol=1e-5, maxits=10000, verbose=False, pc=None) -> Result:
-    """PROGRAM of triapoissonserialimpl1.F: inline Ke = area*B*B^T (:573-594), Laplace."""
+def triapoissonserialimpl1(mesh: H.Mesh | str, rtol=1e-5, maxits=10000, verbose=False, pc=None, elem_mat=None, elemData=None) -> Result:
+    """PROGRAM of triapoissonserialimpl1.F: inline Ke = area*B*B^T (:573-594), Laplace.  The inline element has no material:
+    ``elem_mat`` (with its table) is the library's PFEM_ERR_ARG, ``elemData`` without it is ignored."""
     if isinstance(mesh, str):
         mesh = H.read_mesh(mesh)
-    return _run(L.POISSON_TRIA_INLINE, mesh, None, H.TIMEDATA, "batched", rtol, maxits, verbose, pc)
+    return _run(L.POISSON_TRIA_INLINE, mesh, elemData if elem_mat is not None else None, H.TIMEDATA, "batched", rtol, maxits, verbose, pc,
+                elem_mat)
 
 
-def triapoissonparallelimpl1(mesh: H.Mesh | str, mode="batched", rtol=1e-5, maxits=10000, verbose=False, pc=None) -> Result:
+def triapoissonparallelimpl1(mesh: H.Mesh | str, mode="batched", rtol=1e-5, maxits=10000, verbose=False, pc=None, elem_mat=None,
+                             elemData=None) -> Result:
     """PROGRAM of triapoissonparallelimpl1.F on one rank: the module routine
     StiffnessResidualPoissonLinearTria (:862), kx = ky = 1, no source (next row 8f.1)."""
     if isinstance(mesh, str):
         mesh = H.read_mesh(mesh)
-    return _run(L.POISSON_TRIA, mesh, np.array([1.0, 1.0]), H.TIMEDATA, mode, rtol, maxits, verbose, pc)
+    ed = np.array([1.0, 1.0]) if elemData is None else elemData
+    return _run(L.POISSON_TRIA, mesh, ed, H.TIMEDATA, mode, rtol, maxits, verbose, pc, elem_mat)
 
 
-def triaelasticityparallelimpl1(mesh: H.Mesh | str, mode="batched", rtol=1e-5, maxits=10000, verbose=False, pc=None) -> Result:
+def triaelasticityparallelimpl1(mesh: H.Mesh | str, mode="batched", rtol=1e-5, maxits=10000, verbose=False, pc=None, elem_mat=None,
+                                elemData=None) -> Result:
     """PROGRAM of triaelasticityparallelimpl1.F on one rank with its intended semantics (the committed
     driver USEs a module that does not exist and reads thick/bforce uninitialised: SURVEY A.3#7, 8f.1):
     plane stress, E = 240.565, nu = 0.3 (REAL(4) literals), unit thickness, nodal forces from ForceBC."""
     if isinstance(mesh, str):
         mesh = H.read_mesh(mesh)
-    return _run(L.ELAST_TRIA, mesh, H.ELAST2D_ELEMDATA, H.TIMEDATA, mode, rtol, maxits, verbose, pc)
+    ed = H.ELAST2D_ELEMDATA if elemData is None else elemData
+    return _run(L.ELAST_TRIA, mesh, ed, H.TIMEDATA, mode, rtol, maxits, verbose, pc, elem_mat)

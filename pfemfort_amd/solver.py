@@ -178,6 +178,50 @@ class PetscSolver:
         L.check(L.lib().pfem_mesh_download(self._h, _p(conn), _p(xyz), _p(edof), _p(sa)), "pfem_mesh_download")
         return conn, xyz, edof, sa
 
+    # ---- several materials -------------------------------------------------------------
+    def setMaterials(self, elem_mat, n_mat=None, stride=None):
+        """Material id of every element (``elem_mat[e]`` in ``0 .. n_mat-1``, at most 256 materials; the element order of
+        ``uploadMesh``'s ``conn`` / of ``host.gen_box_tets`` for a generated box).  From here on ``assemble``, ``evalElems``,
+        ``elementFields``, ``nodalForces``, ``nodalRecovery`` and ``errorIndicator`` take a 2-D ``(n_mat, stride)`` table as
+        ``elemData`` and element ``e`` uses row ``elem_mat[e]``.  The stride is fixed HERE, not at first use: ``stride`` (default:
+        the kind's count of elemData entries -- Poisson tet 3, Poisson triangle 2, elastic tet 6, elastic triangle 5), and every
+        later table must have that many columns.  ``n_mat`` defaults to ``max(elem_mat) + 1``.  Legal between the mesh and
+        ``buildPattern``; ``elem_mat=None`` clears the map, and so does a new mesh.  One rank only."""
+        if elem_mat is None:
+            L.check(L.lib().pfem_mesh_set_materials(self._h, 0, None, 0, 0), "pfem_mesh_set_materials")
+            return
+        em = _i32(elem_mat).ravel()
+        if n_mat is None:
+            n_mat = int(em.max()) + 1 if em.size else 1
+        if stride is None:
+            stride = L.NELEMDATA.get(getattr(self, "kind", None), 0)
+        L.check(L.lib().pfem_mesh_set_materials(self._h, em.size, _p(em), int(n_mat), int(stride)), "pfem_mesh_set_materials")
+
+    def materials(self):
+        """``(elem_mat, n_mat, stride)`` of the map in effect, or ``None`` without one."""
+        n = C.c_int(0); st = C.c_int(0)
+        L.check(L.lib().pfem_mesh_get_materials(self._h, C.byref(n), C.byref(st), None), "pfem_mesh_get_materials")
+        if n.value == 0:
+            return None
+        em = np.empty(self.nElem, np.int32)
+        L.check(L.lib().pfem_mesh_get_materials(self._h, C.byref(n), C.byref(st), _p(em)), "pfem_mesh_get_materials")
+        return em, n.value, st.value
+
+    def _elem_data(self, elemData):
+        """``elemData`` as the library reads it: one vector, or -- while a material map is set -- the ``(n_mat, stride)`` table."""
+        if elemData is None:
+            return None
+        ed = _f64(elemData)
+        n = C.c_int(0); st = C.c_int(0)
+        if self._h and getattr(self, "kind", None) is not None:
+            L.check(L.lib().pfem_mesh_get_materials(self._h, C.byref(n), C.byref(st), None), "pfem_mesh_get_materials")
+        if n.value:
+            if ed.shape != (n.value, st.value):
+                raise ValueError(f"elemData of shape {ed.shape}: the material map wants a ({n.value}, {st.value}) table")
+        elif ed.ndim != 1:
+            raise ValueError("a 2-D elemData table needs a material map (setMaterials)")
+        return ed
+
     def buildPattern(self):
         L.check(L.lib().pfem_pattern_build(self._h), "pfem_pattern_build")
 
@@ -412,7 +456,7 @@ class PetscSolver:
         return b.value
 
     def assemble(self, elemData, timeData):
-        ed = None if elemData is None else _f64(elemData)
+        ed = self._elem_data(elemData)
         L.check(L.lib().pfem_assemble(self._h, _p(ed), _p(_f64(timeData))), "pfem_assemble")
 
     def addNodalForces(self, global_dof, values):
@@ -423,7 +467,7 @@ class PetscSolver:
     def evalElems(self, elemData, timeData):
         ns = L.NPELEM[self.kind] * L.NDOF[self.kind]
         K = np.empty((self.nElem, ns, ns)); F = np.empty((self.nElem, ns))
-        ed = None if elemData is None else _f64(elemData)
+        ed = self._elem_data(elemData)
         L.check(L.lib().pfem_eval_elems(self._h, _p(ed), _p(_f64(timeData)), _p(K), _p(F)), "pfem_eval_elems")
         return K.transpose(0, 2, 1).copy(), F     # column-major blocks -> K[e][i,j] = Klocal(i,j)
 
@@ -433,7 +477,7 @@ class PetscSolver:
         ``None``: the last solve's): gradient / engineering Voigt strain and flux / stress as ``(ng, nElem)``, ``|q|`` / von Mises
         as ``(nElem,)`` (``host.ElementPost`` is the per-element mirror)."""
         kind = getattr(self, "kind", None)
-        ed = None if elemData is None else _f64(elemData)
+        ed = self._elem_data(elemData)
         uu = None if u is None else _f64(u).ravel()
         if kind is None:                       # no mesh on this handle: the library says so
             L.check(L.lib().pfem_post_elements(self._h, _p(ed), _p(uu), None, None, None), "pfem_post_elements")
@@ -447,7 +491,7 @@ class PetscSolver:
         """``R (nNode, ndof)`` = sum over the elements of ``K_e u_e - F_e`` at every node dof: the applied nodal force at a free dof
         of a converged solution, the reaction at a constrained one (``u`` as in ``elementFields``)."""
         kind = getattr(self, "kind", None)
-        ed = None if elemData is None else _f64(elemData)
+        ed = self._elem_data(elemData)
         td = None if timeData is None else _f64(timeData)
         uu = None if u is None else _f64(u).ravel()
         if kind is None:
@@ -463,7 +507,7 @@ class PetscSolver:
         (``None`` for ``"grad"``) and the sum of the weights (``u`` as in ``elementFields``; ``host.PostScalar`` mirrors the
         scalar)."""
         kind = getattr(self, "kind", None)
-        ed = None if elemData is None else _f64(elemData)
+        ed = self._elem_data(elemData)
         uu = None if u is None else _f64(u).ravel()
         fld = {"flux": 0, "grad": 1}[field]
         if kind is None:
@@ -479,7 +523,7 @@ class PetscSolver:
         """Zienkiewicz-Zhu indicator ``(eta2 (nElem,), eta2_total, flux_norm2_total)``: per element the integral of
         ``|recovered nodal flux - element flux|^2`` (``host.ElementRecoveryError``), and the sums over the mesh."""
         kind = getattr(self, "kind", None)
-        ed = None if elemData is None else _f64(elemData)
+        ed = self._elem_data(elemData)
         uu = None if u is None else _f64(u).ravel()
         tot = C.c_double(0); fn = C.c_double(0)
         if kind is None:
