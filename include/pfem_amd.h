@@ -130,6 +130,30 @@ int pfem_post_scalar(int kind, const double *flux, double *scalar);
 int pfem_elem_recovery_error(int kind, const double *xNode, const double *yNode, const double *zNode, const double *elemData,
                              const double *valC, const double *nodal_flux, double *eta2, double *flux_norm2);
 
+/* ---- loads on a side of an element -------------------------------------- */
+/* Side f of an element is the face (tets, f = 0..3) or edge (triangles, f = 0..2) OPPOSITE local node f; its nodes are the
+ * element's other local nodes in ascending local order.  The reference has nothing of the kind: its surface loads arrive
+ * integrated by hand as nodal forces (cookmembranetria32-ForceBC.dat is a traction of 6.25 on the edge x = 48).
+ *   PFEM_LOAD_FLUX      the Poisson kinds, 1 component: g = (k grad u).n, the normal flux INTO the body (= -q.n with the q of
+ *                       pfem_elem_post); adds the integral of N_a g to the row of node a
+ *   PFEM_LOAD_TRACTION  the elasticity kinds, ndof components: force per unit area (per unit length and thickness in 2-D)
+ *   PFEM_LOAD_PRESSURE  the elasticity kinds, 1 component: the traction -p n, n the outward unit normal                       */
+#define PFEM_LOAD_FLUX 1
+#define PFEM_LOAD_TRACTION 2
+#define PFEM_LOAD_PRESSURE 3
+/* One side of one element: measure (area of the face / length of the edge), unit normal[ndim] pointing away from local node
+ * `side` -- decided from that node's position, never from the order of the nodes -- and the consistent nodal load F[nsize] of
+ * values[a*ncomp + c], a over the side's nodes in ascending local order, taken as linear on the side:
+ *   3-D  F_a = A/12 (2 g_a + g_b + g_c)        2-D  F_a = L thick/6 (2 g_a + g_b)
+ * zeros at the dofs of the opposite node.  thick = elemData[2] for PFEM_ELAST_TRIA, 1 otherwise (elemData may then be NULL).
+ * Any output may be NULL; with F == NULL load and values are not read.  PFEM_ERR_ARG: side out of range, a load that does not
+ * fit the kind.  PFEM_ERR_NEG_JAC: a side of zero measure (or an element so flat that no side of it has an outside).
+ * Shares its source (csrc/pfem_elem.hpp) with the kernels of pfem_surface_geometry / pfem_rhs_add_surface_load: same bits.  */
+int pfem_face_load(int kind, const double *xNode, const double *yNode, const double *zNode /* NULL in 2-D */,
+                   int side, int load, const double *values /* [(npe-1)*ncomp], per side node */,
+                   const double *elemData /* thickness, PFEM_ELAST_TRIA only; else may be NULL */,
+                   double *F /* [nsize], zero off the side */, double *measure, double *normal /* [ndim] */);
+
 /* ========================================================================= */
 /* 2. driver bookkeeping, host, integer-exact (tetrapoissonparallelimpl1.F)   */
 /* ========================================================================= */
@@ -367,6 +391,37 @@ int pfem_solver_set_cg_single_reduction(pfem_solver *s, int on);
  * NodeDofArrayNew(n,d)-1; the reference's own row formula ignores constrained dofs);
  * ids this rank does not own and negative ids are skipped.                                      */
 int pfem_rhs_add_values(pfem_solver *s, int64_t n, const int64_t *global_dof, const double *values);
+
+/* ---- surface loads -------------------------------------------------------- */
+/* Elements are never reordered on the device, so (element, side) -- element in the order of the conn given to pfem_mesh_upload,
+ * or of pfem_gen_box_tets for pfem_mesh_generate_box*; side as for pfem_face_load -- names a face for the mesh's whole life.
+ * One rank only (PFEM_ERR_STATE with a communication backend of more than one rank: a cut between ranks would look like a
+ * boundary) and the batched path only (PFEM_ERR_STATE on a handle without a mesh).
+ *
+ * pfem_mesh_boundary_faces: the sides that belong to exactly one element, sorted by (element, side).  Two-call: with NULL arrays
+ * only *nFace is set.  Needs the mesh only; the same output before and after pfem_pattern_build.  Found on the device: a
+ * radix sort of one 64-bit key per side and one thread per side that scans its run of equal keys;
+ * temporary device memory (32 npe + 4) nElem bytes plus the sort's own.  The result is kept on the handle until the next mesh.
+ * PFEM_ERR_ARG: 2^29 elements or more (element * 4 + side is carried in 32 bits).                                         */
+int pfem_mesh_boundary_faces(pfem_solver *s, int64_t *nFace, int32_t *face_elem, int32_t *face_side);
+/* measure[i], normal[c*nFace + i] and face_nodes[a*nFace + i] (the side's nodes in ascending local order, in the caller's node
+ * numbering) of any sides, boundary or not; one thread per side, pfem_face_load's arithmetic.  Any output may be NULL.
+ * PFEM_ERR_ARG: an element or side out of range.  PFEM_ERR_NEG_JAC: a side of zero measure among them.                        */
+int pfem_surface_geometry(pfem_solver *s, int64_t nFace, const int32_t *face_elem, const int32_t *face_side,
+                          double *measure, double *normal /* [c*nFace + i] */, int32_t *face_nodes /* [a*nFace + i] */);
+#define PFEM_LOAD_UNIFORM 0        /* values[ncomp]                                   */
+#define PFEM_LOAD_PER_FACE 1       /* values[i*ncomp + c]                              */
+#define PFEM_LOAD_PER_FACE_NODE 2  /* values[(i*(npe-1) + a)*ncomp + c]: linear on the side (hydrostatic pressure) */
+/* rhs += the consistent nodal loads (pfem_face_load) of the nFace sides, one thread per side, f64 atomics into the rows of the
+ * sides' free dofs; constrained dofs are skipped, as the reference skips negative indices.  Semantics of pfem_rhs_add_values:
+ * needs the pattern, is called after pfem_assemble (which zeroes the rhs) and before the solve, and again after every later
+ * pfem_assemble.  Interior sides are accepted (the normal is the named element's outward one) and a side given twice adds
+ * twice.  elemData is read for PFEM_ELAST_TRIA only (the thickness): the vector, or the table while a material map is set,
+ * exactly as pfem_assemble takes it.  PFEM_ERR_ARG: an element or side out of range, a load that does not fit the mesh's kind,
+ * a bad layout.  PFEM_ERR_STATE: no pattern, more than one rank.  PFEM_ERR_NEG_JAC: a side of zero measure among them (the
+ * other sides are added).  Robin terms (they would add to K) and follower loads are not covered.                           */
+int pfem_rhs_add_surface_load(pfem_solver *s, int64_t nFace, const int32_t *face_elem, const int32_t *face_side,
+                              int load, int layout, const double *values, const double *elemData);
 
 /* ---- post-processing of a solution on the device ------------------------- */
 /* u_nodal: host array [node*ndof + d] in the CALLER's node numbering (the one pfem_mesh_upload received, or the generator's own

@@ -20,6 +20,9 @@ POISSON_TRIA, POISSON_TET, ELAST_TET, POISSON_TRIA_INLINE, ELAST_TRIA = 1, 2, 3,
 # solver status (solverpetsc.F:64-68)
 SOLVER_EMPTY, PATTERN_OK, INIT_OK, ASSEMBLY_OK, FACTORISE_OK = 1, 2, 3, 4, 5
 INSERT_VALUES, ADD_VALUES = 1, 2
+# loads on a side of an element and the layouts of their values (pfem_face_load / pfem_rhs_add_surface_load)
+LOAD_FLUX, LOAD_TRACTION, LOAD_PRESSURE = 1, 2, 3
+LOAD_UNIFORM, LOAD_PER_FACE, LOAD_PER_FACE_NODE = 0, 1, 2
 
 NPELEM = {POISSON_TRIA: 3, POISSON_TET: 4, ELAST_TET: 4, POISSON_TRIA_INLINE: 3, ELAST_TRIA: 3}
 NDOF = {POISSON_TRIA: 1, POISSON_TET: 1, ELAST_TET: 3, POISSON_TRIA_INLINE: 1, ELAST_TRIA: 2}
@@ -70,6 +73,7 @@ SIGNATURES = {
     "pfem_elem_post": [_I] + [_P] * 9,
     "pfem_post_scalar": [_I, _P, _P],
     "pfem_elem_recovery_error": [_I] + [_P] * 8,
+    "pfem_face_load": [_I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P],
     "pfem_gen_box_tets": [_D, _D, _I, _D, _D, _I, _D, _D, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "pfem_dof_numbering": [_L, _I, _L, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "pfem_renumber_mesh": [_L, _I, _L, _I, _P, _P, _P, _P, _P, _P],
@@ -143,6 +147,9 @@ SIGNATURES = {
     "pfem_solver_amg_apply": [_P, _P, _P],
     "pfem_eval_elems": [_P, _P, _P, _P, _P],
     "pfem_rhs_add_values": [_P, _L, _P, _P],
+    "pfem_mesh_boundary_faces": [_P, _P, _P, _P],
+    "pfem_surface_geometry": [_P, _L, _P, _P, _P, _P, _P],
+    "pfem_rhs_add_surface_load": [_P, _L, _P, _P, _I, _I, _P, _P],
     "pfem_post_elements": [_P] * 6,
     "pfem_post_nodal_forces": [_P] * 5,
     "pfem_post_nodal_recovery": [_P, _P, _P, _I, _P, _P, _P],

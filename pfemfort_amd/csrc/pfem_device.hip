@@ -544,6 +544,9 @@ struct pfem_solver {
     DevBuf<uint8_t> d_elem_mat;        // [nElem] row of every element ...
     DevBuf<uint8_t> d_inc_mat;         // ... and of every visit of the incidence records, in their layout (k_build_inc_mat)
     DevBuf<double> d_mat_tab;          // the table of the call in progress, [n_mat * mat_stride]
+    // boundary sides of the mesh (pfem_mesh_boundary_faces), sorted by (element, side); kept until the next mesh
+    bool have_bfaces = false;
+    std::vector<int32_t> h_bface_elem, h_bface_side;
     // the lists as translated copies of a few patterns (k_incpat_*): node -> pattern, pattern -> records relative to the node
     DevBuf<uint16_t> d_node_pat, d_pat_flags;
     DevBuf<int4> d_pat_rec;
@@ -1337,6 +1340,14 @@ void clear_materials(pfem_solver *s)
     s->d_mat_tab.release();
 }
 
+// a new mesh has other boundary sides
+void clear_boundary_faces(pfem_solver *s)
+{
+    s->have_bfaces = false;
+    s->h_bface_elem.clear();
+    s->h_bface_side.clear();
+}
+
 // entries of elemData that the element kind reads (0: the kind has no material)
 int kind_elem_data(int kind)
 {
@@ -1405,6 +1416,7 @@ extern "C" int pfem_mesh_upload(pfem_solver *s, int kind, int64_t nElem, const i
     m.soln = s->d_soln.p;
     PFEM_TRY(maybe_reorder(s, edof, xyz));
     clear_materials(s);
+    clear_boundary_faces(s);
     s->have_mesh = true;
     s->have_pattern = false;
     // a neighbour plan set before this upload names dofs in the previous mesh's (internal) numbering: it has to be set again
@@ -1596,6 +1608,7 @@ extern "C" int pfem_mesh_generate_box_axis(pfem_solver *s, int kind, double x0, 
     s->h_perm.clear();
     s->h_iperm.clear();
     clear_materials(s);
+    clear_boundary_faces(s);
     s->have_mesh = true;
     s->have_pattern = false;
     s->have_plan = false;
@@ -2551,6 +2564,205 @@ extern "C" int pfem_rhs_add_values(pfem_solver *s, int64_t n, const int64_t *gdo
     PFEM_TRY(check_kernel("k_add_values"));
     PFEM_HIP(hipStreamSynchronize(s->stream));
     return PFEM_OK;
+}
+
+// ---------------------------------------------------------------------------
+// surface loads: boundary sides, their geometry, their consistent nodal loads
+// ---------------------------------------------------------------------------
+namespace {
+
+// mesh and rank count that the surface calls need
+int surface_needs_mesh(const pfem_solver *s, const char *who)
+{
+    if (s->nranks > 1) {
+        set_last_error(std::string(who) + ": not available with a communication backend of more than one rank");
+        return PFEM_ERR_STATE;
+    }
+    if (!s->have_mesh) {
+        set_last_error(std::string(who) + ": no mesh on the device (the MatSetValues path has none)");
+        return PFEM_ERR_STATE;
+    }
+    return PFEM_OK;
+}
+
+// the (element, side) lists of a call, checked on the host and copied to the device
+int surface_upload_sides(pfem_solver *s, int64_t nFace, const int32_t *fe, const int32_t *fs, DevBuf<int32_t> &de, DevBuf<int32_t> &ds)
+{
+    const MeshDev &m = s->mesh;
+    for (int64_t i = 0; i < nFace; ++i)
+        if (fe[i] < 0 || fe[i] >= m.nElem || fs[i] < 0 || fs[i] >= m.npe) return PFEM_ERR_ARG;
+    PFEM_TRY(de.alloc(static_cast<size_t>(nFace)));
+    PFEM_TRY(ds.alloc(static_cast<size_t>(nFace)));
+    PFEM_HIP(hipMemcpyAsync(de.p, fe, sizeof(int32_t) * nFace, hipMemcpyHostToDevice, s->stream));
+    PFEM_HIP(hipMemcpyAsync(ds.p, fs, sizeof(int32_t) * nFace, hipMemcpyHostToDevice, s->stream));
+    return PFEM_OK;
+}
+
+// The sides that belong to exactly one element, into the handle's cache.  Everything O(nElem) runs on the device: keys, a radix
+// sort over the 2 nbits key bits that matter, the match of every pair against its run, and a flagged selection of the ids
+// 4 e + f in ascending order -- which IS the order (element, side).  The host sees the boundary's ids only.
+// Temporary device memory: two (key, value) buffers of npe nElem pairs each (32 npe nElem bytes), 4 nElem flag bytes, the ids
+// of the boundary, and the sort's own few MB.
+int find_boundary_faces(pfem_solver *s)
+{
+    const MeshDev &m = s->mesh;
+    clear_boundary_faces(s);
+    if (m.nElem >= (1LL << 29)) {                  // 4 e + f in 32 bits, and hipcub counts the 4 nElem ids in an int
+        set_last_error("pfem_mesh_boundary_faces: 2^29 elements or more");
+        return PFEM_ERR_ARG;
+    }
+    if (m.nElem == 0) { s->have_bfaces = true; return PFEM_OK; }
+    const int64_t n = static_cast<int64_t>(m.npe) * m.nElem, nslot = 4 * m.nElem;
+    int nbits = 1;
+    while (nbits < 32 && (1LL << nbits) < m.nNode) ++nbits;
+    DevBuf<unsigned long long> keys, skeys, vals, svals;
+    DevBuf<uint8_t> flags;
+    DevBuf<int32_t> ids;
+    DevBuf<int> d_num;
+    DevBuf<char> temp;
+    PFEM_TRY(keys.alloc(static_cast<size_t>(n)));
+    PFEM_TRY(skeys.alloc(static_cast<size_t>(n)));
+    PFEM_TRY(vals.alloc(static_cast<size_t>(n)));
+    PFEM_TRY(svals.alloc(static_cast<size_t>(n)));
+    PFEM_TRY(flags.alloc(static_cast<size_t>(nslot)));
+    PFEM_TRY(d_num.alloc(1));
+    PFEM_HIP(hipMemsetAsync(flags.p, 0, static_cast<size_t>(nslot), s->stream));
+    if (m.npe == 4) hipLaunchKernelGGL(k_side_keys<4>, dim3(grid_for(m.nElem)), dim3(kBlock), 0, s->stream, m, nbits, keys.p, vals.p);
+    else hipLaunchKernelGGL(k_side_keys<3>, dim3(grid_for(m.nElem)), dim3(kBlock), 0, s->stream, m, nbits, keys.p, vals.p);
+    PFEM_TRY(check_kernel("k_side_keys"));
+    size_t tb = 0;
+    const int ni = static_cast<int>(n);
+    PFEM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys.p, skeys.p, vals.p, svals.p, ni, 0, 2 * nbits, s->stream));
+    PFEM_TRY(temp.alloc(tb));
+    PFEM_HIP(hipcub::DeviceRadixSort::SortPairs(temp.p, tb, keys.p, skeys.p, vals.p, svals.p, ni, 0, 2 * nbits, s->stream));
+    hipLaunchKernelGGL(k_side_match, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, n, static_cast<const unsigned long long *>(skeys.p),
+                       static_cast<const unsigned long long *>(svals.p), flags.p);
+    PFEM_TRY(check_kernel("k_side_match"));
+    // the unsorted pairs are dead: their room takes the selected ids (at most nslot int32 < n 8-byte keys)
+    int32_t *out = reinterpret_cast<int32_t *>(keys.p);
+    hipcub::CountingInputIterator<int32_t> iota(0);
+    size_t tb2 = 0;
+    const int nsl = static_cast<int>(nslot);
+    PFEM_HIP(hipcub::DeviceSelect::Flagged(nullptr, tb2, iota, flags.p, out, d_num.p, nsl, s->stream));
+    if (tb2 > temp.n) { PFEM_HIP(hipStreamSynchronize(s->stream)); PFEM_TRY(temp.alloc(tb2)); }
+    PFEM_HIP(hipcub::DeviceSelect::Flagged(temp.p, tb2, iota, flags.p, out, d_num.p, nsl, s->stream));
+    int nb = 0;
+    PFEM_HIP(hipMemcpyAsync(&nb, d_num.p, sizeof(int), hipMemcpyDeviceToHost, s->stream));
+    PFEM_HIP(hipStreamSynchronize(s->stream));
+    std::vector<int32_t> h_ids(static_cast<size_t>(nb));
+    if (nb > 0) {
+        PFEM_HIP(hipMemcpyAsync(h_ids.data(), out, sizeof(int32_t) * nb, hipMemcpyDeviceToHost, s->stream));
+        PFEM_HIP(hipStreamSynchronize(s->stream));
+    }
+    s->h_bface_elem.resize(static_cast<size_t>(nb));
+    s->h_bface_side.resize(static_cast<size_t>(nb));
+    for (size_t i = 0; i < h_ids.size(); ++i) {
+        s->h_bface_elem[i] = h_ids[i] >> 2;
+        s->h_bface_side[i] = h_ids[i] & 3;
+    }
+    s->have_bfaces = true;
+    return PFEM_OK;
+}
+
+}  // namespace
+
+extern "C" int pfem_mesh_boundary_faces(pfem_solver *s, int64_t *nFace, int32_t *face_elem, int32_t *face_side)
+{
+    if (!s || !nFace) return PFEM_ERR_ARG;
+    PFEM_TRY(surface_needs_mesh(s, "pfem_mesh_boundary_faces"));
+    if (!s->have_bfaces) {
+        PFEM_TRY(use_device(s));
+        PFEM_TRY(find_boundary_faces(s));
+    }
+    *nFace = static_cast<int64_t>(s->h_bface_elem.size());
+    if (face_elem) std::copy(s->h_bface_elem.begin(), s->h_bface_elem.end(), face_elem);
+    if (face_side) std::copy(s->h_bface_side.begin(), s->h_bface_side.end(), face_side);
+    return PFEM_OK;
+}
+
+extern "C" int pfem_surface_geometry(pfem_solver *s, int64_t nFace, const int32_t *face_elem, const int32_t *face_side, double *measure,
+                                     double *normal, int32_t *face_nodes)
+{
+    if (!s || nFace < 0 || (nFace && (!face_elem || !face_side))) return PFEM_ERR_ARG;
+    PFEM_TRY(surface_needs_mesh(s, "pfem_surface_geometry"));
+    if (nFace == 0) return PFEM_OK;
+    PFEM_TRY(use_device(s));
+    const MeshDev &m = s->mesh;
+    const int ns = m.npe - 1;
+    DevBuf<int32_t> de, ds, dn;
+    DevBuf<double> dm, dnrm;
+    PFEM_TRY(surface_upload_sides(s, nFace, face_elem, face_side, de, ds));
+    if (measure) PFEM_TRY(dm.alloc(static_cast<size_t>(nFace)));
+    if (normal) PFEM_TRY(dnrm.alloc(static_cast<size_t>(nFace) * m.ndim));
+    if (face_nodes) PFEM_TRY(dn.alloc(static_cast<size_t>(nFace) * ns));
+    PFEM_HIP(hipMemsetAsync(s->d_err.p, 0, sizeof(int), s->stream));
+    const dim3 grid(grid_for(nFace)), block(kBlock);
+    const int32_t *pe = de.p, *ps = ds.p;
+    if (m.npe == 4) hipLaunchKernelGGL(k_surface_geometry<4>, grid, block, 0, s->stream, m, nFace, pe, ps, dm.p, dnrm.p, dn.p, s->d_err.p);
+    else hipLaunchKernelGGL(k_surface_geometry<3>, grid, block, 0, s->stream, m, nFace, pe, ps, dm.p, dnrm.p, dn.p, s->d_err.p);
+    PFEM_TRY(check_kernel("k_surface_geometry"));
+    if (measure) PFEM_HIP(hipMemcpyAsync(measure, dm.p, sizeof(double) * nFace, hipMemcpyDeviceToHost, s->stream));
+    if (normal) PFEM_HIP(hipMemcpyAsync(normal, dnrm.p, sizeof(double) * nFace * m.ndim, hipMemcpyDeviceToHost, s->stream));
+    if (face_nodes) PFEM_HIP(hipMemcpyAsync(face_nodes, dn.p, sizeof(int32_t) * nFace * ns, hipMemcpyDeviceToHost, s->stream));
+    int err = 0;
+    PFEM_TRY(fetch_err(s, &err));
+    if (face_nodes && !s->h_niperm.empty())          // the caller's node numbering
+        for (int64_t i = 0; i < nFace * ns; ++i) face_nodes[i] = s->h_niperm[static_cast<size_t>(face_nodes[i])];
+    return err;
+}
+
+extern "C" int pfem_rhs_add_surface_load(pfem_solver *s, int64_t nFace, const int32_t *face_elem, const int32_t *face_side, int load,
+                                         int layout, const double *values, const double *elemData)
+{
+    if (!s || nFace < 0 || (nFace && (!face_elem || !face_side))) return PFEM_ERR_ARG;
+    PFEM_TRY(surface_needs_mesh(s, "pfem_rhs_add_surface_load"));
+    if (!s->have_pattern) {
+        set_last_error("pfem_rhs_add_surface_load: build the pattern first");
+        return PFEM_ERR_STATE;
+    }
+    const MeshDev &m = s->mesh;
+    const int ncomp = side_load_components(m.kind, load), ns = m.npe - 1;
+    if (ncomp == 0) {
+        set_last_error("pfem_rhs_add_surface_load: this load does not fit the mesh's element kind");
+        return PFEM_ERR_ARG;
+    }
+    if (layout != PFEM_LOAD_UNIFORM && layout != PFEM_LOAD_PER_FACE && layout != PFEM_LOAD_PER_FACE_NODE) return PFEM_ERR_ARG;
+    if (!values || (m.kind == PFEM_ELAST_TRIA && !elemData)) return PFEM_ERR_ARG;
+    if (nFace == 0) return PFEM_OK;
+    PFEM_TRY(use_device(s));
+    DevBuf<int32_t> de, ds;
+    DevBuf<double> dv;
+    PFEM_TRY(surface_upload_sides(s, nFace, face_elem, face_side, de, ds));
+    const size_t nv = layout == PFEM_LOAD_UNIFORM ? static_cast<size_t>(ncomp)
+                                                  : static_cast<size_t>(nFace) * ncomp * (layout == PFEM_LOAD_PER_FACE_NODE ? ns : 1);
+    PFEM_TRY(dv.alloc(nv));
+    PFEM_HIP(hipMemcpyAsync(dv.p, values, sizeof(double) * nv, hipMemcpyHostToDevice, s->stream));
+    const bool mats = s->n_mat > 0 && m.kind == PFEM_ELAST_TRIA;
+    const ElemPrm prm = make_prm((mats || m.kind != PFEM_ELAST_TRIA) ? nullptr : elemData, nullptr, m.kind);
+    ElemPrmTab tab{};
+    if (mats) PFEM_TRY(make_prm_tab(s, elemData, nullptr, &tab));
+    PFEM_HIP(hipMemsetAsync(s->d_err.p, 0, sizeof(int), s->stream));
+    const dim3 grid(grid_for(nFace)), block(kBlock);
+    const int32_t *pe = de.p, *ps = ds.p;
+    const double *pv = dv.p;
+#define PFEM_SURF(KIND) hipLaunchKernelGGL((k_surface_load<KIND, ElemPrm>), grid, block, 0, s->stream, m, prm, nFace, pe, ps, load, layout, pv, s->d_rhs.p, s->d_err.p)
+    switch (m.kind) {
+    case PFEM_POISSON_TRIA: PFEM_SURF(PFEM_POISSON_TRIA); break;
+    case PFEM_POISSON_TET: PFEM_SURF(PFEM_POISSON_TET); break;
+    case PFEM_ELAST_TET: PFEM_SURF(PFEM_ELAST_TET); break;
+    case PFEM_POISSON_TRIA_INLINE: PFEM_SURF(PFEM_POISSON_TRIA_INLINE); break;
+    case PFEM_ELAST_TRIA:
+        if (mats)
+            hipLaunchKernelGGL((k_surface_load<PFEM_ELAST_TRIA, ElemPrmTab>), grid, block, 0, s->stream, m, tab, nFace, pe, ps, load, layout, pv,
+                               s->d_rhs.p, s->d_err.p);
+        else PFEM_SURF(PFEM_ELAST_TRIA);
+        break;
+    }
+#undef PFEM_SURF
+    PFEM_TRY(check_kernel("k_surface_load"));
+    int err = 0;
+    PFEM_TRY(fetch_err(s, &err));
+    return err;
 }
 
 extern "C" int pfem_eval_elems(pfem_solver *s, const double *elemData, const double *timeData,

@@ -717,4 +717,103 @@ PFEM_HD bool elem_recovery_error(int kind, const double *x, const double *y, con
     return true;
 }
 
+// ---------------------------------------------------------------------------
+// Sides of an element and the loads on them (pfem_face_load / pfem_surface_geometry / pfem_rhs_add_surface_load)
+// ---------------------------------------------------------------------------
+// Side f of an element is the face (tet) or edge (triangle) OPPOSITE local node f; its nodes are the element's other local
+// nodes in ascending local order: s[0] < s[1] (< s[2]).  Written-down order of operations, host and device the same bits:
+//   tet       e1 = P_s1 - P_s0, e2 = P_s2 - P_s0, c = e1 x e2 with c_x = e1y e2z - e1z e2y (and cyclic), len = sqrt((c_x^2 +
+//             c_y^2) + c_z^2), measure = 0.5 len, d = ((P_f - P_s0)_x c_x + (..)_y c_y) + (..)_z c_z
+//   triangle  t = P_s1 - P_s0, c = (t_y, -t_x), len = sqrt(t_x^2 + t_y^2), measure = len, d = (P_f - P_s0)_x c_x + (..)_y c_y
+//   normal    n = c / len when d < 0 (c already points away from node f), (-c) / len when d > 0
+// The orientation comes from the opposite node alone -- never from the order of the nodes, so an inverted element has
+// outward normals too.  false: a side of zero measure, or an element so flat (d == 0) that "outward" has no meaning.
+// The routines take the side's points in that order (xs[a], a < npe - 1) and the opposite node's point apart, so that no array
+// is ever indexed by the run-time side number (registers, not scratch, on the device).
+PFEM_HD void side_nodes(int npe, int f, int s[3])
+{
+    s[0] = f == 0 ? 1 : 0;
+    s[1] = f <= 1 ? 2 : 1;
+    s[2] = npe == 4 ? (f <= 2 ? 3 : 2) : 0;
+}
+
+PFEM_HD bool side_geometry(int npe, const double xs[3], const double ys[3], const double zs[3], double xo, double yo, double zo,
+                           double &measure, double nrm[3])
+{
+    double cx, cy, cz, len, d;
+    if (npe == 4) {
+        const double e1x = xs[1] - xs[0], e1y = ys[1] - ys[0], e1z = zs[1] - zs[0];
+        const double e2x = xs[2] - xs[0], e2y = ys[2] - ys[0], e2z = zs[2] - zs[0];
+        cx = e1y * e2z - e1z * e2y;
+        cy = e1z * e2x - e1x * e2z;
+        cz = e1x * e2y - e1y * e2x;
+        len = sqrt((cx * cx + cy * cy) + cz * cz);
+        measure = 0.5 * len;
+        d = ((xo - xs[0]) * cx + (yo - ys[0]) * cy) + (zo - zs[0]) * cz;
+    } else {
+        const double tx = xs[1] - xs[0], ty = ys[1] - ys[0];
+        cx = ty;
+        cy = -tx;
+        cz = 0.0;
+        len = sqrt(tx * tx + ty * ty);
+        measure = len;
+        d = (xo - xs[0]) * cx + (yo - ys[0]) * cy;
+    }
+    if (!(len > 0.0) || !(d > 0.0 || d < 0.0)) return false;
+    if (d > 0.0) { cx = -cx; cy = -cy; cz = -cz; }
+    nrm[0] = cx / len;
+    nrm[1] = cy / len;
+    nrm[2] = cz / len;
+    return true;
+}
+
+// load kinds and components of a side's nodal values (kinds of include/pfem_amd.h: PFEM_LOAD_FLUX 1, _TRACTION 2, _PRESSURE 3);
+// 0: the load does not fit the element kind
+PFEM_HD int side_load_components(int kind, int load)
+{
+    const bool elast = kind == 3 || kind == 5;
+    if (load == 1) return elast ? 0 : 1;
+    if (load == 2) return elast ? (kind == 3 ? 3 : 2) : 0;
+    if (load == 3) return elast ? 1 : 0;
+    return 0;
+}
+
+// Consistent nodal load of a P1 side from its nodal values vals[a * ncomp + c], a over the side's nodes in ascending local order:
+// the exact integral of N_a g for g linear on the side,
+//   tet       F_a = A / 12 (2 g_a + g_b + g_c)      evaluated as  (A * ((2 g_a + g_b) + g_c)) / 12
+//   triangle  F_a = L thick / 6 (2 g_a + g_b)       evaluated as  ((L * thick) * (2 g_a + g_b)) / 6
+// with b, c the side's other nodes in ascending local order.  The division comes LAST: where measure times the bracket is exact
+// and the quotient representable (the reference's Cook's-membrane forces 3.125 and 1.5625), the result is the exact one.
+// A pressure p is the traction -p n: g_a,c = -(p_a n_c), then the same expression.  A flux has one component and lands on the
+// node's single dof.  Fs[a * ndof + c]: the side's nodes only (the opposite node gets nothing).  thick: 1 except for the
+// plane-stress triangle.  measure and nrm must be side_geometry's.
+PFEM_HD void side_load(int kind, int load, double measure, const double nrm[3], const double *vals, double thick, double Fs[9])
+{
+    const int npe = (kind == 2 || kind == 3) ? 4 : 3;
+    const int ndof = kind == 3 ? 3 : (kind == 5 ? 2 : 1);
+    const int ncomp = load == 2 ? ndof : 1;
+    const double m = npe == 4 ? measure : measure * thick;
+    if (npe == 4) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (c >= ndof) break;
+            const double g0 = load == 3 ? -(vals[0] * nrm[c]) : vals[c];
+            const double g1 = load == 3 ? -(vals[1] * nrm[c]) : vals[ncomp + c];
+            const double g2 = load == 3 ? -(vals[2] * nrm[c]) : vals[2 * ncomp + c];
+            Fs[c] = (m * ((2.0 * g0 + g1) + g2)) / 12.0;
+            Fs[ndof + c] = (m * ((2.0 * g1 + g0) + g2)) / 12.0;
+            Fs[2 * ndof + c] = (m * ((2.0 * g2 + g0) + g1)) / 12.0;
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            if (c >= ndof) break;
+            const double g0 = load == 3 ? -(vals[0] * nrm[c]) : vals[c];
+            const double g1 = load == 3 ? -(vals[1] * nrm[c]) : vals[ncomp + c];
+            Fs[c] = (m * (2.0 * g0 + g1)) / 6.0;
+            Fs[ndof + c] = (m * (2.0 * g1 + g0)) / 6.0;
+        }
+    }
+}
+
 }  // namespace pfem

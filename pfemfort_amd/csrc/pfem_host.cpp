@@ -122,6 +122,42 @@ extern "C" int pfem_elem_recovery_error(int kind, const double *xNode, const dou
     return PFEM_OK;
 }
 
+// One side of one element (pfem_elem.hpp: side_geometry / side_load): measure, outward unit normal and the consistent nodal
+// load of the side's nodal values, F[nsize] with zeros at the dofs of the opposite node.  F == NULL: geometry only (load and
+// values are not looked at).
+extern "C" int pfem_face_load(int kind, const double *xNode, const double *yNode, const double *zNode, int side, int load,
+                              const double *values, const double *elemData, double *F, double *measure, double *normal)
+{
+    if (!kind_valid(kind) || !xNode || !yNode) return PFEM_ERR_ARG;
+    const int npe = kind_npelem(kind), ndof = kind_ndof(kind), ndim = kind_ndim(kind);
+    if (ndim == 3 && !zNode) return PFEM_ERR_ARG;
+    if (side < 0 || side >= npe) return PFEM_ERR_ARG;
+    if (F) {
+        if (side_load_components(kind, load) == 0 || !values) return PFEM_ERR_ARG;
+        if (kind == PFEM_ELAST_TRIA && !elemData) return PFEM_ERR_ARG;
+    }
+    int sn[3];
+    side_nodes(npe, side, sn);
+    double xs[3] = {0, 0, 0}, ys[3] = {0, 0, 0}, zs[3] = {0, 0, 0};
+    for (int a = 0; a < npe - 1; ++a) {
+        xs[a] = xNode[sn[a]];
+        ys[a] = yNode[sn[a]];
+        zs[a] = ndim == 3 ? zNode[sn[a]] : 0.0;
+    }
+    double m = 0.0, nrm[3] = {0, 0, 0};
+    if (!side_geometry(npe, xs, ys, zs, xNode[side], yNode[side], ndim == 3 ? zNode[side] : 0.0, m, nrm)) return PFEM_ERR_NEG_JAC;
+    if (measure) *measure = m;
+    if (normal) std::copy(nrm, nrm + ndim, normal);
+    if (F) {
+        double Fs[9];
+        side_load(kind, load, m, nrm, values, kind == PFEM_ELAST_TRIA ? elemData[2] : 1.0, Fs);
+        std::fill(F, F + npe * ndof, 0.0);
+        for (int a = 0; a < npe - 1; ++a)
+            for (int c = 0; c < ndof; ++c) F[sn[a] * ndof + c] = Fs[a * ndof + c];
+    }
+    return PFEM_OK;
+}
+
 // ---------------------------------------------------------------------------
 // 2. structured box mesh (genTetra.cpp)
 // ---------------------------------------------------------------------------

@@ -1976,6 +1976,140 @@ __global__ void __launch_bounds__(kBlock) k_add_values(double *rhs, const int32_
     if (i < n) add_f64(&rhs[idx[i]], v[i]);
 }
 
+// ---------------------------------------------------------------------------
+// surface loads (pfem_mesh_boundary_faces / pfem_surface_geometry / pfem_rhs_add_surface_load)
+// ---------------------------------------------------------------------------
+// Boundary sides by sorting.  One thread per element writes a (key, value) pair for each of its NPE sides: with lo < mid < hi the
+// side's node numbers, key = lo << nbits | mid (nbits = bits of a node number: the radix sort then runs over 2 nbits bits only) and
+// value = hi << 32 | (4 e + f); an edge has no hi (0).  Pairs are stored side-major (pair f of element e at f nElem + e: coalesced
+// in e); the sort does not care.
+template <int NPE>
+__global__ void __launch_bounds__(kBlock) k_side_keys(MeshDev m, int nbits, unsigned long long *__restrict__ keys,
+                                                       unsigned long long *__restrict__ vals)
+{
+    const int64_t e = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    if (e >= m.nElem) return;
+    uint32_t nd[NPE];
+#pragma unroll
+    for (int a = 0; a < NPE; ++a) nd[a] = static_cast<uint32_t>(m.conn[a * m.nElem + e]);
+#pragma unroll
+    for (int f = 0; f < NPE; ++f) {
+        // the other nodes in ascending local order (side_nodes of pfem_elem.hpp, f a compile-time constant here)
+        uint32_t a = nd[f == 0 ? 1 : 0], b = nd[f <= 1 ? 2 : 1], c = NPE == 4 ? nd[f <= 2 ? 3 : 2] : 0u;
+        if (a > b) { const uint32_t t = a; a = b; b = t; }
+        if (NPE == 4) {
+            if (b > c) { const uint32_t t = b; b = c; c = t; }
+            if (a > b) { const uint32_t t = a; a = b; b = t; }
+        }
+        keys[f * m.nElem + e] = (static_cast<unsigned long long>(a) << nbits) | b;
+        vals[f * m.nElem + e] = (static_cast<unsigned long long>(c) << 32) | static_cast<unsigned long long>(4 * e + f);
+    }
+}
+
+// One thread per sorted pair: the pairs with its key sit next to it (the sides around one mesh edge in 3-D -- a handful --, the
+// at most two triangles of an edge in 2-D).  It looks backwards and forwards through that run for another pair with its third
+// node: none means no other element has this side, and the side's flag at 4 e + f is raised (flags zeroed by the caller).
+__global__ void __launch_bounds__(kBlock) k_side_match(int64_t n, const unsigned long long *__restrict__ skeys,
+                                                        const unsigned long long *__restrict__ svals, uint8_t *__restrict__ flags)
+{
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long key = skeys[i], v = svals[i];
+    const uint32_t hi = static_cast<uint32_t>(v >> 32);
+    bool shared = false;
+    for (int64_t j = i - 1; j >= 0 && !shared && skeys[j] == key; --j) shared = static_cast<uint32_t>(svals[j] >> 32) == hi;
+    for (int64_t j = i + 1; j < n && !shared && skeys[j] == key; ++j) shared = static_cast<uint32_t>(svals[j] >> 32) == hi;
+    if (!shared) flags[static_cast<uint32_t>(v)] = 1;
+}
+
+// the side's points, the opposite node's point and the side's node numbers (local order ascending) of side f of element e
+template <int NPE>
+__device__ __forceinline__ void side_load_points(const MeshDev &m, int64_t e, int f, int sn[3], int nd[3], double xs[3], double ys[3],
+                                                 double zs[3], double &xo, double &yo, double &zo)
+{
+    side_nodes(NPE, f, sn);
+#pragma unroll
+    for (int a = 0; a < NPE - 1; ++a) {
+        nd[a] = m.conn[sn[a] * m.nElem + e];
+        xs[a] = m.xyz[nd[a]];
+        ys[a] = m.xyz[m.nNode + nd[a]];
+        zs[a] = NPE == 4 ? m.xyz[2 * m.nNode + nd[a]] : 0.0;
+    }
+    if (NPE == 3) { nd[2] = 0; xs[2] = ys[2] = zs[2] = 0.0; }
+    const int no = m.conn[f * m.nElem + e];
+    xo = m.xyz[no];
+    yo = m.xyz[m.nNode + no];
+    zo = NPE == 4 ? m.xyz[2 * m.nNode + no] : 0.0;
+}
+
+// One thread per side: measure[i], normal[c * nFace + i], nodes[a * nFace + i] (device node numbers); any output may be null.
+template <int NPE>
+__global__ void __launch_bounds__(kBlock) k_surface_geometry(MeshDev m, int64_t nFace, const int32_t *__restrict__ fe,
+                                                              const int32_t *__restrict__ fs, double *__restrict__ measure,
+                                                              double *__restrict__ normal, int32_t *__restrict__ nodes, int *err)
+{
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    if (i >= nFace) return;
+    const int64_t e = fe[i];
+    const int f = fs[i];
+    if (e < 0 || e >= m.nElem || f < 0 || f >= NPE) { atomicMax(err, PFEM_ERR_ARG); return; }
+    int sn[3], nd[3];
+    double xs[3], ys[3], zs[3], xo, yo, zo, meas = 0.0, nrm[3] = {0.0, 0.0, 0.0};
+    side_load_points<NPE>(m, e, f, sn, nd, xs, ys, zs, xo, yo, zo);
+    if (!side_geometry(NPE, xs, ys, zs, xo, yo, zo, meas, nrm)) {
+        atomicMax(err, PFEM_ERR_NEG_JAC);
+        meas = 0.0;
+        nrm[0] = nrm[1] = nrm[2] = 0.0;
+    }
+    if (measure) measure[i] = meas;
+#pragma unroll
+    for (int c = 0; c < NPE - 1; ++c) {           // NPE - 1 = the space dimension = the nodes of a side
+        if (normal) normal[c * nFace + i] = nrm[c];
+        if (nodes) nodes[c * nFace + i] = nd[c];
+    }
+}
+
+// One thread per side: side_load of pfem_elem.hpp, added to the rows of the side's free dofs.  A surface node collects a few
+// sides, nFace is the mesh's surface: atomics, in whatever order they arrive.  values by layout: 0 values[c], 1 values[i ncomp +
+// c], 2 values[(i (NPE-1) + a) ncomp + c].  The thickness of the plane-stress triangle is elemData[2] of the element's row.
+template <int KIND, class PRM = ElemPrm>
+__global__ void __launch_bounds__(kBlock) k_surface_load(MeshDev m, PRM prm, int64_t nFace, const int32_t *__restrict__ fe,
+                                                          const int32_t *__restrict__ fs, int load, int layout,
+                                                          const double *__restrict__ values, double *rhs, int *err)
+{
+    using P = PostKind<KIND>;
+    constexpr int NS = P::NPE - 1;
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    if (i >= nFace) return;
+    const int64_t e = fe[i];
+    const int f = fs[i];
+    if (e < 0 || e >= m.nElem || f < 0 || f >= P::NPE) { atomicMax(err, PFEM_ERR_ARG); return; }
+    int sn[3], nd[3];
+    double xs[3], ys[3], zs[3], xo, yo, zo, meas, nrm[3];
+    side_load_points<P::NPE>(m, e, f, sn, nd, xs, ys, zs, xo, yo, zo);
+    if (!side_geometry(P::NPE, xs, ys, zs, xo, yo, zo, meas, nrm)) { atomicMax(err, PFEM_ERR_NEG_JAC); return; }
+    double v[NS * P::NDOF], Fs[9];            // the side's values as side_load reads them: v[a * ncomp + c]
+    if (load == PFEM_LOAD_TRACTION) {
+#pragma unroll
+        for (int a = 0; a < NS; ++a)
+#pragma unroll
+            for (int c = 0; c < P::NDOF; ++c)
+                v[a * P::NDOF + c] = values[layout == PFEM_LOAD_UNIFORM ? c : (layout == PFEM_LOAD_PER_FACE ? i * P::NDOF + c : (i * NS + a) * P::NDOF + c)];
+    } else {
+#pragma unroll
+        for (int a = 0; a < NS; ++a) v[a] = values[layout == PFEM_LOAD_UNIFORM ? 0 : (layout == PFEM_LOAD_PER_FACE ? i : i * NS + a)];
+    }
+    const double thick = KIND == PFEM_ELAST_TRIA ? prm_elem(prm, e)[2] : 1.0;
+    side_load(KIND, load, meas, nrm, v, thick, Fs);
+#pragma unroll
+    for (int a = 0; a < NS; ++a)
+#pragma unroll
+        for (int c = 0; c < P::NDOF; ++c) {
+            const int r = m.edof[(sn[a] * P::NDOF + c) * m.nElem + e];
+            if (r >= 0) add_f64(&rhs[r], Fs[a * P::NDOF + c]);
+        }
+}
+
 __global__ void __launch_bounds__(kBlock) k_invert(double *d, int64_t n)
 {
     const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;

@@ -122,8 +122,10 @@ def _materials(mesh, elemData, elem_mat):
     return table, ids
 
 
-def _run(kind, mesh, elemData, timeData, mode, rtol, maxits, verbose, pc=None, elem_mat=None):
+def _run(kind, mesh, elemData, timeData, mode, rtol, maxits, verbose, pc=None, elem_mat=None, surface_loads=None):
     elemData, elem_mat = _materials(mesh, elemData, elem_mat)
+    if surface_loads and mode != "batched":
+        raise ValueError("surface_loads need mode=\"batched\": the sides are integrated on the device")
     dm, conn_new, xyz_new, edof = _setup(kind, mesh)
     N = dm.size_global
     nsize = edof.shape[0]
@@ -184,6 +186,8 @@ def _run(kind, mesh, elemData, timeData, mode, rtol, maxits, verbose, pc=None, e
         else:
             for g, v in zip(gdof, mesh.force_val):
                 solver.VecSetValues([g], [v], ADD_VALUES)
+    for sl in surface_loads or ():                                       # loads on sides (elem, side) of mesh.conn's elements:
+        solver.addSurfaceLoad(sl["elem"], sl["side"], sl["load"], sl["values"], sl.get("layout"), elemData)   # not in the reference
     t0 = time.perf_counter()                                             # :898
     its, reason, rnorm = solver.factoriseAndSolve()                      # :900
     timers["solve_s"] = time.perf_counter() - t0                         # :902
@@ -246,50 +250,54 @@ def run_parallel(kind, mesh: H.Mesh, elem_proc_id, node_proc_id, dist, torch, el
 
 
 def tetrapoissonparallelimpl1(mesh: H.Mesh | str, mode="batched", rtol=1e-5, maxits=10000, verbose=False, pc=None, elem_mat=None,
-                              elemData=None) -> Result:
+                              elemData=None, surface_loads=None) -> Result:
     """PROGRAM TetraMeshPoissonEquation (tetrapoissonparallelimpl1.F) on one rank / one GPU.  ``elemData``: another vector than
     the PROGRAM's, or -- with ``elem_mat``, one material id per element -- the ``(n_mat, stride)`` table of a body of several
-    materials (all five drivers; not part of the reference, whose drivers hard-code one material)."""
+    materials (all five drivers; not part of the reference, whose drivers hard-code one material).  ``surface_loads``: a list of
+    dicts ``{"elem", "side", "load", "values"[, "layout"]}`` handed to ``PetscSolver.addSurfaceLoad`` after the nodal forces (all
+    five drivers, ``mode="batched"`` only: ``ValueError`` with ``"compat"``; sides as ``PetscSolver.boundaryFaces`` names them,
+    elements in the order of ``mesh.conn``)."""
     if isinstance(mesh, str):
         mesh = H.read_mesh(mesh)
     ed = H.POISSON_ELEMDATA if elemData is None else elemData
-    return _run(L.POISSON_TET, mesh, ed, H.TIMEDATA, mode, rtol, maxits, verbose, pc, elem_mat)   # :822-824
+    return _run(L.POISSON_TET, mesh, ed, H.TIMEDATA, mode, rtol, maxits, verbose, pc, elem_mat, surface_loads)   # :822-824
 
 
 def tetraelasticityparallelimpl1(mesh: H.Mesh | str, mode="batched", rtol=1e-5, maxits=10000, verbose=False, pc=None, elem_mat=None,
-                                 elemData=None) -> Result:
+                                 elemData=None, surface_loads=None) -> Result:
     """PROGRAM of tetraelasticityparallelimpl1.F (body force only; DESIGN.md 'deviations')."""
     if isinstance(mesh, str):
         mesh = H.read_mesh(mesh)
     ed = H.ELAST_ELEMDATA if elemData is None else elemData
-    return _run(L.ELAST_TET, mesh, ed, H.TIMEDATA, mode, rtol, maxits, verbose, pc, elem_mat)       # :894-902
+    return _run(L.ELAST_TET, mesh, ed, H.TIMEDATA, mode, rtol, maxits, verbose, pc, elem_mat, surface_loads)       # :894-902
 
 
-def triapoissonserialimpl1(mesh: H.Mesh | str, rtol=1e-5, maxits=10000, verbose=False, pc=None, elem_mat=None, elemData=None) -> Result:
+def triapoissonserialimpl1(mesh: H.Mesh | str, rtol=1e-5, maxits=10000, verbose=False, pc=None, elem_mat=None, elemData=None,
+                           surface_loads=None) -> Result:
     """PROGRAM of triapoissonserialimpl1.F: inline Ke = area*B*B^T (:573-594), Laplace.  The inline element has no material:
     ``elem_mat`` (with its table) is the library's PFEM_ERR_ARG, ``elemData`` without it is ignored."""
     if isinstance(mesh, str):
         mesh = H.read_mesh(mesh)
     return _run(L.POISSON_TRIA_INLINE, mesh, elemData if elem_mat is not None else None, H.TIMEDATA, "batched", rtol, maxits, verbose, pc,
-                elem_mat)
+                elem_mat, surface_loads)
 
 
 def triapoissonparallelimpl1(mesh: H.Mesh | str, mode="batched", rtol=1e-5, maxits=10000, verbose=False, pc=None, elem_mat=None,
-                             elemData=None) -> Result:
+                             elemData=None, surface_loads=None) -> Result:
     """PROGRAM of triapoissonparallelimpl1.F on one rank: the module routine
     StiffnessResidualPoissonLinearTria (:862), kx = ky = 1, no source (next row 8f.1)."""
     if isinstance(mesh, str):
         mesh = H.read_mesh(mesh)
     ed = np.array([1.0, 1.0]) if elemData is None else elemData
-    return _run(L.POISSON_TRIA, mesh, ed, H.TIMEDATA, mode, rtol, maxits, verbose, pc, elem_mat)
+    return _run(L.POISSON_TRIA, mesh, ed, H.TIMEDATA, mode, rtol, maxits, verbose, pc, elem_mat, surface_loads)
 
 
 def triaelasticityparallelimpl1(mesh: H.Mesh | str, mode="batched", rtol=1e-5, maxits=10000, verbose=False, pc=None, elem_mat=None,
-                                elemData=None) -> Result:
+                                elemData=None, surface_loads=None) -> Result:
     """PROGRAM of triaelasticityparallelimpl1.F on one rank with its intended semantics (the committed
     driver USEs a module that does not exist and reads thick/bforce uninitialised: SURVEY A.3#7, 8f.1):
     plane stress, E = 240.565, nu = 0.3 (REAL(4) literals), unit thickness, nodal forces from ForceBC."""
     if isinstance(mesh, str):
         mesh = H.read_mesh(mesh)
     ed = H.ELAST2D_ELEMDATA if elemData is None else elemData
-    return _run(L.ELAST_TRIA, mesh, ed, H.TIMEDATA, mode, rtol, maxits, verbose, pc, elem_mat)
+    return _run(L.ELAST_TRIA, mesh, ed, H.TIMEDATA, mode, rtol, maxits, verbose, pc, elem_mat, surface_loads)

@@ -269,6 +269,23 @@ def ElementPost(kind, xNode, yNode, zNode, elemData, valC):
     return grad, flux, sc.value, fint
 
 
+def FaceLoad(kind, xNode, yNode, zNode, side, load=None, values=None, elemData=None):
+    """One side of one element (pfem_face_load): side ``f`` is the face / edge opposite local node ``f``.  Returns
+    ``(F[nsize], measure, normal[ndim])`` -- the consistent nodal load of ``values`` ((npe-1, ncomp), per side node in ascending
+    local order; zeros at the opposite node's dofs), the side's area / length and the element's outward unit normal.  With
+    ``load=None`` only the geometry is computed and ``F`` is None.  ``load``: ``LOAD_FLUX`` (Poisson kinds), ``LOAD_TRACTION``,
+    ``LOAD_PRESSURE`` (elasticity kinds); ``elemData`` is read for the plane-stress triangle only (thickness).  ``zNode`` is
+    None in 2-D."""
+    z = None if zNode is None else _f64(zNode)
+    ed = None if elemData is None else _f64(elemData)
+    F = None if load is None else np.empty(L.NPELEM[kind] * L.NDOF[kind])
+    v = None if values is None else _f64(values).ravel()
+    meas = C.c_double(0); nrm = np.empty(L.NDIM[kind])
+    L.check(L.lib().pfem_face_load(kind, _p(_f64(xNode)), _p(_f64(yNode)), _p(z), int(side), 0 if load is None else int(load),
+                                   _p(v), _p(ed), _p(F), C.byref(meas), _p(nrm)), "pfem_face_load")
+    return F, meas.value, nrm
+
+
 def PostScalar(kind, flux):
     """The scalar of ``ElementPost`` on any flux / stress vector(s) of the kind, ``(ng,)`` or ``(n, ng)`` in the stored Voigt
     order (pfem_post_scalar): ``|q|``, von Mises, the plane-stress form."""

@@ -464,6 +464,65 @@ class PetscSolver:
         g = np.ascontiguousarray(global_dof, dtype=np.int64); v = _f64(values)
         L.check(L.lib().pfem_rhs_add_values(self._h, len(g), _p(g), _p(v)), "pfem_rhs_add_values")
 
+    # ---- surface loads (one rank, batched path) ----------------------------------------
+    def boundaryFaces(self):
+        """``(elem, side)`` of the sides that belong to exactly one element, sorted by (element, side): side ``f`` of an element
+        is the face / edge opposite its local node ``f``, elements in the order of ``uploadMesh``'s ``conn`` (of
+        ``host.gen_box_tets`` for a generated box).  Found on the device from the mesh alone, kept until the next mesh."""
+        n = C.c_int64(0)
+        L.check(L.lib().pfem_mesh_boundary_faces(self._h, C.byref(n), None, None), "pfem_mesh_boundary_faces")
+        fe = np.empty(n.value, np.int32); fs = np.empty(n.value, np.int32)
+        L.check(L.lib().pfem_mesh_boundary_faces(self._h, C.byref(n), _p(fe), _p(fs)), "pfem_mesh_boundary_faces")
+        return fe, fs
+
+    def surfaceGeometry(self, elem, side):
+        """``(measure (nFace,), normal (ndim, nFace), nodes (npe-1, nFace))`` of any sides: area / length, the named element's
+        outward unit normal, the side's nodes in ascending local order (caller's node numbering).  ``host.FaceLoad`` is the
+        per-side mirror, bit for bit."""
+        fe = _i32(elem).ravel(); fs = _i32(side).ravel()
+        assert fe.size == fs.size
+        kind = getattr(self, "kind", None)
+        if kind is None:                       # no mesh on this handle: the library says so
+            L.check(L.lib().pfem_surface_geometry(self._h, fe.size, _p(fe), _p(fs), None, None, None), "pfem_surface_geometry")
+        n = fe.size
+        meas = np.empty(n); nrm = np.empty((L.NDIM[kind], n)); nodes = np.empty((L.NPELEM[kind] - 1, n), np.int32)
+        L.check(L.lib().pfem_surface_geometry(self._h, n, _p(fe), _p(fs), _p(meas), _p(nrm), _p(nodes)), "pfem_surface_geometry")
+        return meas, nrm, nodes
+
+    def addSurfaceLoad(self, elem, side, load, values, layout=None, elemData=None):
+        """rhs += the consistent nodal loads of ``values`` on the sides ``(elem, side)``; after ``assemble`` (which zeroes the
+        rhs), before the solve.  ``load``: "flux" (Poisson kinds; the normal flux into the body), "traction" (elasticity kinds,
+        ndof components) or "pressure" (elasticity kinds; the traction ``-p n``), or the ``LOAD_*`` code.  ``layout``: "uniform"
+        (``values (ncomp,)``), "face" (``(nFace, ncomp)``) or "face_node" (``(nFace, npe-1, ncomp)``, linear on each side);
+        ``None`` infers it from ``values.shape`` (a trailing axis of one component may be left out).  ``elemData`` is read for
+        the plane-stress triangle only (its thickness): the vector, or the table while a material map is set."""
+        fe = _i32(elem).ravel(); fs = _i32(side).ravel()
+        assert fe.size == fs.size
+        code = {"flux": L.LOAD_FLUX, "traction": L.LOAD_TRACTION, "pressure": L.LOAD_PRESSURE}.get(load, load)
+        kind = getattr(self, "kind", None)
+        v = _f64(values)
+        if kind is None:
+            L.check(L.lib().pfem_rhs_add_surface_load(self._h, fe.size, _p(fe), _p(fs), int(code), 0, _p(v.ravel()), None),
+                    "pfem_rhs_add_surface_load")
+        ncomp = L.NDOF[kind] if code == L.LOAD_TRACTION else 1
+        ns = L.NPELEM[kind] - 1
+        sizes = {L.LOAD_UNIFORM: ncomp, L.LOAD_PER_FACE: fe.size * ncomp, L.LOAD_PER_FACE_NODE: fe.size * ns * ncomp}
+        if layout is None:
+            shapes = {L.LOAD_UNIFORM: [(ncomp,)] + ([()] if ncomp == 1 else []),
+                      L.LOAD_PER_FACE: [(fe.size, ncomp)] + ([(fe.size,)] if ncomp == 1 else []),
+                      L.LOAD_PER_FACE_NODE: [(fe.size, ns, ncomp)] + ([(fe.size, ns)] if ncomp == 1 else [])}
+            fits = [k for k in (L.LOAD_UNIFORM, L.LOAD_PER_FACE, L.LOAD_PER_FACE_NODE) if v.shape in shapes[k]]
+            if not fits:
+                raise ValueError(f"values of shape {v.shape} fit no layout of {fe.size} sides with {ncomp} component(s)")
+            lay = fits[0]
+        else:
+            lay = {"uniform": L.LOAD_UNIFORM, "face": L.LOAD_PER_FACE, "face_node": L.LOAD_PER_FACE_NODE}.get(layout, layout)
+            if lay in sizes and v.size != sizes[lay]:
+                raise ValueError(f"values of size {v.size}: layout {layout!r} wants {sizes[lay]}")
+        ed = self._elem_data(elemData) if kind == L.ELAST_TRIA else None
+        L.check(L.lib().pfem_rhs_add_surface_load(self._h, fe.size, _p(fe), _p(fs), int(code), int(lay), _p(v.ravel()), _p(ed)),
+                "pfem_rhs_add_surface_load")
+
     def evalElems(self, elemData, timeData):
         ns = L.NPELEM[self.kind] * L.NDOF[self.kind]
         K = np.empty((self.nElem, ns, ns)); F = np.empty((self.nElem, ns))
