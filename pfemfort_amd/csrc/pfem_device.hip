@@ -808,12 +808,24 @@ SpmvForm spmv_form(const pfem_solver *s)
     return f;
 }
 
-// compile-time copies of a run-time flag / of the relative groups' gap mode / of an epilogue mode for the kernels' template arguments
+// compile-time copies of a run-time flag / of the mesh's element kind / of the relative groups' gap mode / of an epilogue mode
+// for the kernels' template arguments
 template <class F>
 void with_flag(bool on, F &&f)
 {
     if (on) f(std::true_type{});
     else f(std::false_type{});
+}
+template <class F>
+void with_kind(int kind, F &&f)             // (the one list of the kinds for a launch; the parameter type: with_elem_prm)
+{
+    switch (kind) {
+    case PFEM_POISSON_TRIA: f(std::integral_constant<int, PFEM_POISSON_TRIA>{}); break;
+    case PFEM_POISSON_TET: f(std::integral_constant<int, PFEM_POISSON_TET>{}); break;
+    case PFEM_ELAST_TET: f(std::integral_constant<int, PFEM_ELAST_TET>{}); break;
+    case PFEM_POISSON_TRIA_INLINE: f(std::integral_constant<int, PFEM_POISSON_TRIA_INLINE>{}); break;
+    case PFEM_ELAST_TRIA: f(std::integral_constant<int, PFEM_ELAST_TRIA>{}); break;
+    }
 }
 template <class F>
 void with_gap_mode(bool gap32, bool dict, F &&f)
@@ -869,6 +881,35 @@ int fetch_err(pfem_solver *s, int *err)
     PFEM_HIP(hipMemcpyAsync(s->h_err, s->d_err.p, sizeof(int), hipMemcpyDeviceToHost, s->stream));
     PFEM_HIP(hipStreamSynchronize(s->stream));
     *err = *s->h_err;
+    return PFEM_OK;
+}
+
+// What the surface and post-processing calls need of the handle.  One rank: they do not cover the sums over the ranks at
+// interface nodes yet.  A mesh: for a pass over the elements.  A pattern too: for a pass over the incidence lists or into the rhs.
+int needs_one_rank(const pfem_solver *s, const char *who)
+{
+    if (s->nranks > 1) {
+        set_last_error(std::string(who) + ": not available with a communication backend of more than one rank");
+        return PFEM_ERR_STATE;
+    }
+    return PFEM_OK;
+}
+int needs_mesh(const pfem_solver *s, const char *who)
+{
+    PFEM_TRY(needs_one_rank(s, who));
+    if (!s->have_mesh) {
+        set_last_error(std::string(who) + ": no mesh on the device (the MatSetValues path has none)");
+        return PFEM_ERR_STATE;
+    }
+    return PFEM_OK;
+}
+int needs_pattern(const pfem_solver *s, const char *who)
+{
+    PFEM_TRY(needs_mesh(s, who));
+    if (!s->have_pattern) {
+        set_last_error(std::string(who) + ": build the pattern first");
+        return PFEM_ERR_STATE;
+    }
     return PFEM_OK;
 }
 
@@ -2364,6 +2405,19 @@ int make_prm_tab(pfem_solver *s, const double *elemData, const double *timeData,
     return PFEM_OK;
 }
 
+// The element parameter of a call, handed to `f` in its own type: the ElemPrm of one elemData or, while a material map is set,
+// the ElemPrmTab of the caller's table.  The one place that chooses between the two (the element kind: with_kind).
+template <class F>
+int with_elem_prm(pfem_solver *s, const double *elemData, const double *timeData, F &&f)
+{
+    if (s->n_mat > 0) {
+        ElemPrmTab tab{};
+        PFEM_TRY(make_prm_tab(s, elemData, timeData, &tab));
+        return f(tab);
+    }
+    return f(make_prm(elemData, timeData, s->mesh.kind));
+}
+
 // pfem_assemble past its checks, for one elemData (PRM = ElemPrm) or a table of them (ElemPrmTab)
 template <class PRM>
 int assemble_with(pfem_solver *s, const PRM prm)
@@ -2404,11 +2458,16 @@ int assemble_with(pfem_solver *s, const PRM prm)
             if (rlds > 65536) PFEM_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(rlds)));
             return PFEM_OK;
         };
-#define PFEM_GATHER(KIND)                                                                                             \
-    if (use_lds) {                                                                                                    \
-        PFEM_TRY(allow_lds(reinterpret_cast<const void *>(&k_gather_scalar<KIND, true, PRM>)));                            \
-        hipLaunchKernelGGL((k_gather_scalar<KIND, true, PRM>), rgrid, rblock, rlds, s->stream, m, A, s->d_rhs.p, prm, ip, ic, irec, nrow, s->d_err.p); \
-    } else hipLaunchKernelGGL((k_gather_scalar<KIND, false, PRM>), grid, block, 0, s->stream, m, A, s->d_rhs.p, prm, ip, ic, irec, nrow, s->d_err.p)
+        // the 1-dof kinds without a kernel of their own
+        auto gather_scalar = [&](auto kind) -> int {
+            constexpr int KIND = decltype(kind)::value;
+            if (use_lds) {
+                PFEM_TRY(allow_lds(reinterpret_cast<const void *>(&k_gather_scalar<KIND, true, PRM>)));
+                launch(k_gather_scalar<KIND, true, PRM>, rgrid, rblock, rlds, s->stream, nullptr, nullptr, m, A, s->d_rhs.p, prm, ip, ic, irec, nrow, s->d_err.p);
+            } else launch(k_gather_scalar<KIND, false, PRM>, grid, block, 0, s->stream, nullptr, nullptr, m, A, s->d_rhs.p, prm, ip, ic, irec, nrow, s->d_err.p);
+            return PFEM_OK;
+        };
+        // (a kernel of its own per kind, with its own arguments: this switch is not with_kind's)
         switch (m.kind) {
         case PFEM_POISSON_TET:
             if (use_lds && s->d_node4.p && !std::getenv("PFEM_DEBUG_GATHER_SOA")) {
@@ -2432,43 +2491,38 @@ int assemble_with(pfem_solver *s, const PRM prm)
                     const VdState reset{s->vd_n, 0, 0, 0};
                     PFEM_HIP(hipMemcpyAsync(s->d_vstate.p, &reset, sizeof reset, hipMemcpyHostToDevice, s->stream));
                 }
-                hipLaunchKernelGGL(k_gather_poisson_tet4<PRM>, xgrid, rblock, rlds, s->stream, m.nNode, A, s->d_rhs.p, prm, ip, ic, irec, nrow,
-                                   static_cast<const double4 *>(s->d_node4.p), s->d_err.p, xcd_per,
-                                   both ? static_cast<const uint8_t *>(s->d_relk.p) : nullptr, both ? static_cast<const int64_t *>(s->d_rslice_off.p) : nullptr,
-                                   (both && !direct) ? s->d_rvals.p : nullptr, bound ? L0->dinv.p : nullptr, bound ? L0->t.p : nullptr,
-                                   direct ? static_cast<const VdHashEntry *>(s->d_vhash.p) : nullptr,
-                                   direct ? reinterpret_cast<uint16_t *>(s->d_vcodes.p) : nullptr, direct ? s->d_vstate.p : nullptr,
-                                   pats ? static_cast<const uint16_t *>(s->d_node_pat.p) : nullptr, pats ? static_cast<const int4 *>(s->d_pat_rec.p) : nullptr,
-                                   s->inc_pat_stride);
+                launch(k_gather_poisson_tet4<PRM>, xgrid, rblock, rlds, s->stream, nullptr, nullptr, m.nNode, A, s->d_rhs.p, prm, ip, ic, irec, nrow,
+                       s->d_node4.p, s->d_err.p, xcd_per, both ? s->d_relk.p : nullptr, both ? s->d_rslice_off.p : nullptr,
+                       (both && !direct) ? s->d_rvals.p : nullptr, bound ? L0->dinv.p : nullptr, bound ? L0->t.p : nullptr,
+                       direct ? s->d_vhash.p : nullptr, direct ? reinterpret_cast<uint16_t *>(s->d_vcodes.p) : nullptr,
+                       direct ? s->d_vstate.p : nullptr, pats ? s->d_node_pat.p : nullptr, pats ? s->d_pat_rec.p : nullptr, s->inc_pat_stride);
                 wrote_rel = both && !direct;
                 wrote_codes = direct;
                 wrote_bound = bound;
             } else {
-                PFEM_GATHER(PFEM_POISSON_TET);
+                PFEM_TRY(gather_scalar(std::integral_constant<int, PFEM_POISSON_TET>{}));
             }
             break;
-        case PFEM_POISSON_TRIA: PFEM_GATHER(PFEM_POISSON_TRIA); break;
-        case PFEM_POISSON_TRIA_INLINE: PFEM_GATHER(PFEM_POISSON_TRIA_INLINE); break;
+        case PFEM_POISSON_TRIA: PFEM_TRY(gather_scalar(std::integral_constant<int, PFEM_POISSON_TRIA>{})); break;
+        case PFEM_POISSON_TRIA_INLINE: PFEM_TRY(gather_scalar(std::integral_constant<int, PFEM_POISSON_TRIA_INLINE>{})); break;
         case PFEM_ELAST_TET:
             PFEM_TRY(allow_lds(reinterpret_cast<const void *>(&k_gather_elast_rows<PRM>)));
             // (plain block order: the XCD-contiguous one measured 3 % slower on the beam, 1.605 against 1.56 ms)
             {
                 const bool bothg = spmv_form(s).layout == SpmvLayout::Group3 && s->d_row_group.p && s->n_hubs == 0;
                 const bool patsf = pats && s->d_pat_flags.p;
-                hipLaunchKernelGGL(k_gather_elast_rows<PRM>, rgrid, rblock, rlds, s->stream, m, A, s->d_rhs.p, prm, ip, ic, irec, ifl, nrow, s->d_err.p, 0u,
-                                   bothg ? static_cast<const int32_t *>(s->d_row_group.p) : nullptr, bothg ? static_cast<const int32_t *>(s->d_group_row0.p) : nullptr,
-                                   bothg ? static_cast<const int64_t *>(s->d_gslice_off.p) : nullptr, bothg ? s->d_gvals.p : nullptr,
-                                   patsf ? static_cast<const uint16_t *>(s->d_node_pat.p) : nullptr, patsf ? static_cast<const int4 *>(s->d_pat_rec.p) : nullptr,
-                                   patsf ? static_cast<const uint16_t *>(s->d_pat_flags.p) : nullptr, s->inc_pat_stride);
+                launch(k_gather_elast_rows<PRM>, rgrid, rblock, rlds, s->stream, nullptr, nullptr, m, A, s->d_rhs.p, prm, ip, ic, irec, ifl, nrow, s->d_err.p, 0u,
+                       bothg ? s->d_row_group.p : nullptr, bothg ? s->d_group_row0.p : nullptr, bothg ? s->d_gslice_off.p : nullptr,
+                       bothg ? s->d_gvals.p : nullptr, patsf ? s->d_node_pat.p : nullptr, patsf ? s->d_pat_rec.p : nullptr,
+                       patsf ? s->d_pat_flags.p : nullptr, s->inc_pat_stride);
                 wrote_grp = bothg;
             }
             break;
         case PFEM_ELAST_TRIA:
             PFEM_TRY(allow_lds(reinterpret_cast<const void *>(&k_gather_elast2d_rows<PRM>)));
-            hipLaunchKernelGGL(k_gather_elast2d_rows<PRM>, rgrid, rblock, rlds, s->stream, m, A, s->d_rhs.p, prm, ip, ic, irec, ifl, nrow, s->d_err.p);
+            launch(k_gather_elast2d_rows<PRM>, rgrid, rblock, rlds, s->stream, nullptr, nullptr, m, A, s->d_rhs.p, prm, ip, ic, irec, ifl, nrow, s->d_err.p);
             break;
         }
-#undef PFEM_GATHER
         PFEM_TRY(check_kernel("k_gather"));
     }
     if (m.nElem > 0 && (!gather || s->n_hubs > 0)) {
@@ -2477,23 +2531,13 @@ int assemble_with(pfem_solver *s, const PRM prm)
         const dim3 grid(grid_for(m.nElem)), block(kBlock);
         SellDev A = s->sell();
         const uint8_t *only = gather ? s->d_node_hub.p : nullptr;
-        switch (m.kind) {
-        case PFEM_POISSON_TET:
-            hipLaunchKernelGGL((k_assemble_scalar<PFEM_POISSON_TET, PRM>), grid, block, 0, s->stream, m, A, s->d_rhs.p, prm, s->d_err.p, only);
-            break;
-        case PFEM_POISSON_TRIA:
-            hipLaunchKernelGGL((k_assemble_scalar<PFEM_POISSON_TRIA, PRM>), grid, block, 0, s->stream, m, A, s->d_rhs.p, prm, s->d_err.p, only);
-            break;
-        case PFEM_POISSON_TRIA_INLINE:
-            hipLaunchKernelGGL((k_assemble_scalar<PFEM_POISSON_TRIA_INLINE, PRM>), grid, block, 0, s->stream, m, A, s->d_rhs.p, prm, s->d_err.p, only);
-            break;
-        case PFEM_ELAST_TET:
-            hipLaunchKernelGGL(k_assemble_elast<PRM>, grid, block, 0, s->stream, m, A, s->d_rhs.p, prm, s->d_err.p, only);
-            break;
-        case PFEM_ELAST_TRIA:
-            hipLaunchKernelGGL(k_assemble_elast2d<PRM>, grid, block, 0, s->stream, m, A, s->d_rhs.p, prm, s->d_err.p, only);
-            break;
-        }
+        auto scatter = [&](auto kernel) { launch(kernel, grid, block, 0, s->stream, nullptr, nullptr, m, A, s->d_rhs.p, prm, s->d_err.p, only); };
+        with_kind(m.kind, [&](auto kind) {
+            constexpr int KIND = decltype(kind)::value;
+            if constexpr (KIND == PFEM_ELAST_TET) scatter(k_assemble_elast<PRM>);
+            else if constexpr (KIND == PFEM_ELAST_TRIA) scatter(k_assemble_elast2d<PRM>);
+            else scatter(k_assemble_scalar<KIND, PRM>);
+        });
         PFEM_TRY(check_kernel("k_assemble"));
     }
     PFEM_HIP(hipEventRecord(s->ev1, s->stream));
@@ -2527,12 +2571,7 @@ extern "C" int pfem_assemble(pfem_solver *s, const double *elemData, const doubl
         return PFEM_ERR_STATE;
     }
     PFEM_TRY(use_device(s));
-    if (s->n_mat > 0) {
-        ElemPrmTab tab{};
-        PFEM_TRY(make_prm_tab(s, elemData, timeData, &tab));
-        return assemble_with(s, tab);
-    }
-    return assemble_with(s, make_prm(elemData, timeData, m.kind));
+    return with_elem_prm(s, elemData, timeData, [&](const auto &prm) { return assemble_with(s, prm); });
 }
 
 // Specified nodal forces: VecSetValue(rhsVec, row, fact, ADD_VALUES) after the element loop
@@ -2559,8 +2598,7 @@ extern "C" int pfem_rhs_add_values(pfem_solver *s, int64_t n, const int64_t *gdo
     PFEM_TRY(dv.alloc(val.size()));
     PFEM_HIP(hipMemcpyAsync(di.p, idx.data(), sizeof(int32_t) * idx.size(), hipMemcpyHostToDevice, s->stream));
     PFEM_HIP(hipMemcpyAsync(dv.p, val.data(), sizeof(double) * val.size(), hipMemcpyHostToDevice, s->stream));
-    hipLaunchKernelGGL(k_add_values, dim3(grid_for(static_cast<int64_t>(idx.size()))), dim3(kBlock), 0, s->stream, s->d_rhs.p,
-                       static_cast<const int32_t *>(di.p), static_cast<const double *>(dv.p), static_cast<int64_t>(idx.size()));
+    launch(k_add_values, dim3(grid_for(static_cast<int64_t>(idx.size()))), dim3(kBlock), 0, s->stream, nullptr, nullptr, s->d_rhs.p, di.p, dv.p, idx.size());
     PFEM_TRY(check_kernel("k_add_values"));
     PFEM_HIP(hipStreamSynchronize(s->stream));
     return PFEM_OK;
@@ -2570,20 +2608,6 @@ extern "C" int pfem_rhs_add_values(pfem_solver *s, int64_t n, const int64_t *gdo
 // surface loads: boundary sides, their geometry, their consistent nodal loads
 // ---------------------------------------------------------------------------
 namespace {
-
-// mesh and rank count that the surface calls need
-int surface_needs_mesh(const pfem_solver *s, const char *who)
-{
-    if (s->nranks > 1) {
-        set_last_error(std::string(who) + ": not available with a communication backend of more than one rank");
-        return PFEM_ERR_STATE;
-    }
-    if (!s->have_mesh) {
-        set_last_error(std::string(who) + ": no mesh on the device (the MatSetValues path has none)");
-        return PFEM_ERR_STATE;
-    }
-    return PFEM_OK;
-}
 
 // the (element, side) lists of a call, checked on the host and copied to the device
 int surface_upload_sides(pfem_solver *s, int64_t nFace, const int32_t *fe, const int32_t *fs, DevBuf<int32_t> &de, DevBuf<int32_t> &ds)
@@ -2627,16 +2651,14 @@ int find_boundary_faces(pfem_solver *s)
     PFEM_TRY(flags.alloc(static_cast<size_t>(nslot)));
     PFEM_TRY(d_num.alloc(1));
     PFEM_HIP(hipMemsetAsync(flags.p, 0, static_cast<size_t>(nslot), s->stream));
-    if (m.npe == 4) hipLaunchKernelGGL(k_side_keys<4>, dim3(grid_for(m.nElem)), dim3(kBlock), 0, s->stream, m, nbits, keys.p, vals.p);
-    else hipLaunchKernelGGL(k_side_keys<3>, dim3(grid_for(m.nElem)), dim3(kBlock), 0, s->stream, m, nbits, keys.p, vals.p);
+    launch(m.npe == 4 ? k_side_keys<4> : k_side_keys<3>, dim3(grid_for(m.nElem)), dim3(kBlock), 0, s->stream, nullptr, nullptr, m, nbits, keys.p, vals.p);
     PFEM_TRY(check_kernel("k_side_keys"));
     size_t tb = 0;
     const int ni = static_cast<int>(n);
     PFEM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys.p, skeys.p, vals.p, svals.p, ni, 0, 2 * nbits, s->stream));
     PFEM_TRY(temp.alloc(tb));
     PFEM_HIP(hipcub::DeviceRadixSort::SortPairs(temp.p, tb, keys.p, skeys.p, vals.p, svals.p, ni, 0, 2 * nbits, s->stream));
-    hipLaunchKernelGGL(k_side_match, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, n, static_cast<const unsigned long long *>(skeys.p),
-                       static_cast<const unsigned long long *>(svals.p), flags.p);
+    launch(k_side_match, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, nullptr, nullptr, n, skeys.p, svals.p, flags.p);
     PFEM_TRY(check_kernel("k_side_match"));
     // the unsorted pairs are dead: their room takes the selected ids (at most nslot int32 < n 8-byte keys)
     int32_t *out = reinterpret_cast<int32_t *>(keys.p);
@@ -2669,7 +2691,7 @@ int find_boundary_faces(pfem_solver *s)
 extern "C" int pfem_mesh_boundary_faces(pfem_solver *s, int64_t *nFace, int32_t *face_elem, int32_t *face_side)
 {
     if (!s || !nFace) return PFEM_ERR_ARG;
-    PFEM_TRY(surface_needs_mesh(s, "pfem_mesh_boundary_faces"));
+    PFEM_TRY(needs_mesh(s, "pfem_mesh_boundary_faces"));
     if (!s->have_bfaces) {
         PFEM_TRY(use_device(s));
         PFEM_TRY(find_boundary_faces(s));
@@ -2684,7 +2706,7 @@ extern "C" int pfem_surface_geometry(pfem_solver *s, int64_t nFace, const int32_
                                      double *normal, int32_t *face_nodes)
 {
     if (!s || nFace < 0 || (nFace && (!face_elem || !face_side))) return PFEM_ERR_ARG;
-    PFEM_TRY(surface_needs_mesh(s, "pfem_surface_geometry"));
+    PFEM_TRY(needs_mesh(s, "pfem_surface_geometry"));
     if (nFace == 0) return PFEM_OK;
     PFEM_TRY(use_device(s));
     const MeshDev &m = s->mesh;
@@ -2696,10 +2718,8 @@ extern "C" int pfem_surface_geometry(pfem_solver *s, int64_t nFace, const int32_
     if (normal) PFEM_TRY(dnrm.alloc(static_cast<size_t>(nFace) * m.ndim));
     if (face_nodes) PFEM_TRY(dn.alloc(static_cast<size_t>(nFace) * ns));
     PFEM_HIP(hipMemsetAsync(s->d_err.p, 0, sizeof(int), s->stream));
-    const dim3 grid(grid_for(nFace)), block(kBlock);
-    const int32_t *pe = de.p, *ps = ds.p;
-    if (m.npe == 4) hipLaunchKernelGGL(k_surface_geometry<4>, grid, block, 0, s->stream, m, nFace, pe, ps, dm.p, dnrm.p, dn.p, s->d_err.p);
-    else hipLaunchKernelGGL(k_surface_geometry<3>, grid, block, 0, s->stream, m, nFace, pe, ps, dm.p, dnrm.p, dn.p, s->d_err.p);
+    launch(m.npe == 4 ? k_surface_geometry<4> : k_surface_geometry<3>, dim3(grid_for(nFace)), dim3(kBlock), 0, s->stream, nullptr, nullptr, m, nFace,
+           de.p, ds.p, dm.p, dnrm.p, dn.p, s->d_err.p);
     PFEM_TRY(check_kernel("k_surface_geometry"));
     if (measure) PFEM_HIP(hipMemcpyAsync(measure, dm.p, sizeof(double) * nFace, hipMemcpyDeviceToHost, s->stream));
     if (normal) PFEM_HIP(hipMemcpyAsync(normal, dnrm.p, sizeof(double) * nFace * m.ndim, hipMemcpyDeviceToHost, s->stream));
@@ -2715,11 +2735,7 @@ extern "C" int pfem_rhs_add_surface_load(pfem_solver *s, int64_t nFace, const in
                                          int layout, const double *values, const double *elemData)
 {
     if (!s || nFace < 0 || (nFace && (!face_elem || !face_side))) return PFEM_ERR_ARG;
-    PFEM_TRY(surface_needs_mesh(s, "pfem_rhs_add_surface_load"));
-    if (!s->have_pattern) {
-        set_last_error("pfem_rhs_add_surface_load: build the pattern first");
-        return PFEM_ERR_STATE;
-    }
+    PFEM_TRY(needs_pattern(s, "pfem_rhs_add_surface_load"));
     const MeshDev &m = s->mesh;
     const int ncomp = side_load_components(m.kind, load), ns = m.npe - 1;
     if (ncomp == 0) {
@@ -2737,32 +2753,23 @@ extern "C" int pfem_rhs_add_surface_load(pfem_solver *s, int64_t nFace, const in
                                                   : static_cast<size_t>(nFace) * ncomp * (layout == PFEM_LOAD_PER_FACE_NODE ? ns : 1);
     PFEM_TRY(dv.alloc(nv));
     PFEM_HIP(hipMemcpyAsync(dv.p, values, sizeof(double) * nv, hipMemcpyHostToDevice, s->stream));
-    const bool mats = s->n_mat > 0 && m.kind == PFEM_ELAST_TRIA;
-    const ElemPrm prm = make_prm((mats || m.kind != PFEM_ELAST_TRIA) ? nullptr : elemData, nullptr, m.kind);
-    ElemPrmTab tab{};
-    if (mats) PFEM_TRY(make_prm_tab(s, elemData, nullptr, &tab));
-    PFEM_HIP(hipMemsetAsync(s->d_err.p, 0, sizeof(int), s->stream));
-    const dim3 grid(grid_for(nFace)), block(kBlock);
-    const int32_t *pe = de.p, *ps = ds.p;
-    const double *pv = dv.p;
-#define PFEM_SURF(KIND) hipLaunchKernelGGL((k_surface_load<KIND, ElemPrm>), grid, block, 0, s->stream, m, prm, nFace, pe, ps, load, layout, pv, s->d_rhs.p, s->d_err.p)
-    switch (m.kind) {
-    case PFEM_POISSON_TRIA: PFEM_SURF(PFEM_POISSON_TRIA); break;
-    case PFEM_POISSON_TET: PFEM_SURF(PFEM_POISSON_TET); break;
-    case PFEM_ELAST_TET: PFEM_SURF(PFEM_ELAST_TET); break;
-    case PFEM_POISSON_TRIA_INLINE: PFEM_SURF(PFEM_POISSON_TRIA_INLINE); break;
-    case PFEM_ELAST_TRIA:
-        if (mats)
-            hipLaunchKernelGGL((k_surface_load<PFEM_ELAST_TRIA, ElemPrmTab>), grid, block, 0, s->stream, m, tab, nFace, pe, ps, load, layout, pv,
-                               s->d_rhs.p, s->d_err.p);
-        else PFEM_SURF(PFEM_ELAST_TRIA);
-        break;
-    }
-#undef PFEM_SURF
-    PFEM_TRY(check_kernel("k_surface_load"));
-    int err = 0;
-    PFEM_TRY(fetch_err(s, &err));
-    return err;
+    // the elastic triangle's pressure is the one load that reads the material; the other kinds have no kernel for a table
+    const auto add = [&](const auto &prm) -> int {
+        using PRM = std::decay_t<decltype(prm)>;
+        PFEM_HIP(hipMemsetAsync(s->d_err.p, 0, sizeof(int), s->stream));
+        with_kind(m.kind, [&](auto kind) {
+            constexpr int KIND = decltype(kind)::value;
+            if constexpr (KIND == PFEM_ELAST_TRIA || std::is_same_v<PRM, ElemPrm>)
+                launch(k_surface_load<KIND, PRM>, dim3(grid_for(nFace)), dim3(kBlock), 0, s->stream, nullptr, nullptr, m, prm, nFace, de.p, ds.p, load, layout,
+                       dv.p, s->d_rhs.p, s->d_err.p);
+        });
+        PFEM_TRY(check_kernel("k_surface_load"));
+        int err = 0;
+        PFEM_TRY(fetch_err(s, &err));
+        return err;
+    };
+    if (m.kind != PFEM_ELAST_TRIA) return add(make_prm(nullptr, nullptr, m.kind));
+    return with_elem_prm(s, elemData, nullptr, add);
 }
 
 extern "C" int pfem_eval_elems(pfem_solver *s, const double *elemData, const double *timeData,
@@ -2773,24 +2780,22 @@ extern "C" int pfem_eval_elems(pfem_solver *s, const double *elemData, const dou
     PFEM_TRY(use_device(s));
     const MeshDev &m = s->mesh;
     if (s->n_mat > 0 && !elemData) return PFEM_ERR_ARG;
-    const ElemPrm prm = make_prm(s->n_mat > 0 ? nullptr : elemData, timeData, m.kind);
-    ElemPrmTab tab{};
-    if (s->n_mat > 0) PFEM_TRY(make_prm_tab(s, elemData, timeData, &tab));
-    const size_t nk = static_cast<size_t>(m.nElem) * m.nsize * m.nsize, nf = static_cast<size_t>(m.nElem) * m.nsize;
-    DevBuf<double> dK, dF;
-    PFEM_TRY(dK.alloc(nk));
-    PFEM_TRY(dF.alloc(nf));
-    PFEM_HIP(hipMemsetAsync(s->d_err.p, 0, sizeof(int), s->stream));
-    if (m.nElem > 0) {
-        if (s->n_mat > 0) hipLaunchKernelGGL(k_eval_elems<ElemPrmTab>, dim3(grid_for(m.nElem)), dim3(kBlock), 0, s->stream, m, tab, dK.p, dF.p, s->d_err.p);
-        else hipLaunchKernelGGL(k_eval_elems<ElemPrm>, dim3(grid_for(m.nElem)), dim3(kBlock), 0, s->stream, m, prm, dK.p, dF.p, s->d_err.p);
-        PFEM_TRY(check_kernel("k_eval_elems"));
-    }
-    PFEM_HIP(hipMemcpyAsync(K_out, dK.p, nk * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    PFEM_HIP(hipMemcpyAsync(F_out, dF.p, nf * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    int err = 0;
-    PFEM_TRY(fetch_err(s, &err));
-    return err;
+    return with_elem_prm(s, elemData, timeData, [&](const auto &prm) -> int {
+        const size_t nk = static_cast<size_t>(m.nElem) * m.nsize * m.nsize, nf = static_cast<size_t>(m.nElem) * m.nsize;
+        DevBuf<double> dK, dF;
+        PFEM_TRY(dK.alloc(nk));
+        PFEM_TRY(dF.alloc(nf));
+        PFEM_HIP(hipMemsetAsync(s->d_err.p, 0, sizeof(int), s->stream));
+        if (m.nElem > 0) {
+            launch(k_eval_elems<std::decay_t<decltype(prm)>>, dim3(grid_for(m.nElem)), dim3(kBlock), 0, s->stream, nullptr, nullptr, m, prm, dK.p, dF.p, s->d_err.p);
+            PFEM_TRY(check_kernel("k_eval_elems"));
+        }
+        PFEM_HIP(hipMemcpyAsync(K_out, dK.p, nk * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        PFEM_HIP(hipMemcpyAsync(F_out, dF.p, nf * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        int err = 0;
+        PFEM_TRY(fetch_err(s, &err));
+        return err;
+    });
 }
 
 extern "C" int pfem_get_csr(pfem_solver *s, int64_t *rowptr, int32_t *cols, double *vals)
@@ -3507,16 +3512,6 @@ extern "C" int pfem_bench_spmv(pfem_solver *s, int reps, double *ms_per_launch)
 // ---------------------------------------------------------------------------
 namespace {
 
-// what the post-processing passes do not cover yet: sums over the ranks at interface nodes
-int post_one_rank(const pfem_solver *s, const char *who)
-{
-    if (s->nranks > 1) {
-        set_last_error(std::string(who) + ": not available with a communication backend of more than one rank");
-        return PFEM_ERR_STATE;
-    }
-    return PFEM_OK;
-}
-
 // The nodal field [node * ndof + d] on the device, in the DEVICE's node order: the caller's array (caller's node numbering), or
 // -- u_nodal == NULL -- the field of the last solve: x at the free dofs, solnApplied at the constrained ones.
 int post_nodal_field(pfem_solver *s, const double *u_nodal, DevBuf<double> &u, const char *who)
@@ -3542,26 +3537,10 @@ int post_nodal_field(pfem_solver *s, const double *u_nodal, DevBuf<double> &u, c
     }
     PFEM_HIP(hipMemcpyAsync(u.p, s->d_soln.p, sizeof(double) * nv, hipMemcpyDeviceToDevice, s->stream));
     if (s->have_incidence && s->n_hubs == 0 && s->d_node_row.p)
-        hipLaunchKernelGGL(k_post_nodal_by_node, dim3(grid_for(nv)), dim3(kBlock), 0, s->stream, nv, static_cast<const int32_t *>(s->d_node_row.p),
-                           static_cast<const double *>(s->d_x.p), u.p);
+        launch(k_post_nodal_by_node, dim3(grid_for(nv)), dim3(kBlock), 0, s->stream, nullptr, nullptr, nv, s->d_node_row.p, s->d_x.p, u.p);
     else if (m.nElem > 0)
-        hipLaunchKernelGGL(k_post_nodal_by_elem, dim3(grid_for(m.nElem * m.nsize)), dim3(kBlock), 0, s->stream, m, static_cast<const double *>(s->d_x.p), u.p);
+        launch(k_post_nodal_by_elem, dim3(grid_for(m.nElem * m.nsize)), dim3(kBlock), 0, s->stream, nullptr, nullptr, m, s->d_x.p, u.p);
     return check_kernel("k_post_nodal");
-}
-
-// mesh, pattern and rank count that a pass over the incidence lists needs, in the words of pfem_post_nodal_forces
-int post_needs_pattern(const pfem_solver *s, const char *who)
-{
-    PFEM_TRY(post_one_rank(s, who));
-    if (!s->have_mesh) {
-        set_last_error(std::string(who) + ": no mesh on the device (the MatSetValues path has none)");
-        return PFEM_ERR_STATE;
-    }
-    if (!s->have_pattern) {
-        set_last_error(std::string(who) + ": build the pattern first");
-        return PFEM_ERR_STATE;
-    }
-    return PFEM_OK;
 }
 
 // Launches of the nodal recovery (enqueued only): nodal[node * ng + c], weight[node] and -- nscalar != nullptr -- the scalar of the
@@ -3575,20 +3554,12 @@ int post_recovery_launch(pfem_solver *s, const PRM &prm, const double *up, int u
     const int ng = post_components(m.kind);
     const bool gather = m.nElem > 0 && s->assembly_mode == PFEM_ASSEMBLY_GATHER && s->have_incidence && s->d_inc_rec.p;
     const uint8_t *hubs = (gather && s->n_hubs > 0) ? s->d_node_hub.p : nullptr;
+    const dim3 ngrid(grid_for(nn)), egrid(grid_for(m.nElem)), block(kBlock);
     if (gather) {
-        const dim3 grid(grid_for(nn)), block(kBlock);
-        const int64_t *ip = s->d_inc_ptr.p;
-        const int32_t *ic = s->d_inc_cnt.p;
-        const int4 *irec = s->d_inc_rec.p;
-#define PFEM_POST(KIND) hipLaunchKernelGGL((k_post_recovery_gather<KIND, PRM>), grid, block, 0, s->stream, m, prm, ip, ic, irec, hubs, up, use_grad, nodal, nscalar, weight, s->d_err.p)
-        switch (m.kind) {
-        case PFEM_POISSON_TRIA: PFEM_POST(PFEM_POISSON_TRIA); break;
-        case PFEM_POISSON_TET: PFEM_POST(PFEM_POISSON_TET); break;
-        case PFEM_ELAST_TET: PFEM_POST(PFEM_ELAST_TET); break;
-        case PFEM_POISSON_TRIA_INLINE: PFEM_POST(PFEM_POISSON_TRIA_INLINE); break;
-        case PFEM_ELAST_TRIA: PFEM_POST(PFEM_ELAST_TRIA); break;
-        }
-#undef PFEM_POST
+        with_kind(m.kind, [&](auto kind) {
+            launch(k_post_recovery_gather<decltype(kind)::value, PRM>, ngrid, block, 0, s->stream, nullptr, nullptr, m, prm, s->d_inc_ptr.p, s->d_inc_cnt.p,
+                   s->d_inc_rec.p, hubs, up, use_grad, nodal, nscalar, weight, s->d_err.p);
+        });
         PFEM_TRY(check_kernel("k_post_recovery_gather"));
         if (!hubs) return PFEM_OK;
     } else {
@@ -3596,31 +3567,15 @@ int post_recovery_launch(pfem_solver *s, const PRM &prm, const double *up, int u
         PFEM_HIP(hipMemsetAsync(weight, 0, sizeof(double) * static_cast<size_t>(std::max<int64_t>(nn, 1)), s->stream));
     }
     if (m.nElem > 0) {
-        const dim3 grid(grid_for(m.nElem)), block(kBlock);
-#define PFEM_POST(KIND) hipLaunchKernelGGL((k_post_recovery_scatter<KIND, PRM>), grid, block, 0, s->stream, m, prm, hubs, up, use_grad, nodal, weight, s->d_err.p)
-        switch (m.kind) {
-        case PFEM_POISSON_TRIA: PFEM_POST(PFEM_POISSON_TRIA); break;
-        case PFEM_POISSON_TET: PFEM_POST(PFEM_POISSON_TET); break;
-        case PFEM_ELAST_TET: PFEM_POST(PFEM_ELAST_TET); break;
-        case PFEM_POISSON_TRIA_INLINE: PFEM_POST(PFEM_POISSON_TRIA_INLINE); break;
-        case PFEM_ELAST_TRIA: PFEM_POST(PFEM_ELAST_TRIA); break;
-        }
-#undef PFEM_POST
+        with_kind(m.kind, [&](auto kind) {
+            launch(k_post_recovery_scatter<decltype(kind)::value, PRM>, egrid, block, 0, s->stream, nullptr, nullptr, m, prm, hubs, up, use_grad, nodal, weight,
+                   s->d_err.p);
+        });
         PFEM_TRY(check_kernel("k_post_recovery_scatter"));
     }
-    {
-        const dim3 grid(grid_for(nn)), block(kBlock);
-        const double *w = weight;
-#define PFEM_POST(KIND) hipLaunchKernelGGL(k_post_recovery_divide<KIND>, grid, block, 0, s->stream, nn, hubs, w, nodal, nscalar)
-        switch (m.kind) {
-        case PFEM_POISSON_TRIA: PFEM_POST(PFEM_POISSON_TRIA); break;
-        case PFEM_POISSON_TET: PFEM_POST(PFEM_POISSON_TET); break;
-        case PFEM_ELAST_TET: PFEM_POST(PFEM_ELAST_TET); break;
-        case PFEM_POISSON_TRIA_INLINE: PFEM_POST(PFEM_POISSON_TRIA_INLINE); break;
-        case PFEM_ELAST_TRIA: PFEM_POST(PFEM_ELAST_TRIA); break;
-        }
-#undef PFEM_POST
-    }
+    with_kind(m.kind, [&](auto kind) {
+        launch(k_post_recovery_divide<decltype(kind)::value>, ngrid, block, 0, s->stream, nullptr, nullptr, nn, hubs, weight, nodal, nscalar);
+    });
     return check_kernel("k_post_recovery_divide");
 }
 
@@ -3642,136 +3597,92 @@ int post_nodes_to_caller(pfem_solver *s, const double *dev, int nc, double *out)
     return PFEM_OK;
 }
 
+// the two sums of `n` block partials at part[0 ..) and part[kMaxGrid ..), into part[2 kMaxGrid] and part[2 kMaxGrid + 1] (enqueued only)
+void post_reduce_partials(pfem_solver *s, double *part, unsigned n)
+{
+    launch(k_reduce_partials, dim3(1), dim3(1024), 0, s->stream, nullptr, nullptr, part, part + kMaxGrid, n, part + 2 * kMaxGrid, nullptr);
+}
+
 }  // namespace
 
 extern "C" int pfem_post_elements(pfem_solver *s, const double *elemData, const double *u_nodal, double *grad, double *flux, double *scalar)
 {
     if (!s) return PFEM_ERR_ARG;
-    PFEM_TRY(post_one_rank(s, "pfem_post_elements"));
-    if (!s->have_mesh) {
-        set_last_error("pfem_post_elements: no mesh on the device (the MatSetValues path has none)");
-        return PFEM_ERR_STATE;
-    }
+    PFEM_TRY(needs_mesh(s, "pfem_post_elements"));
     const MeshDev &m = s->mesh;
     if (m.kind != PFEM_POISSON_TRIA_INLINE && !elemData) return PFEM_ERR_ARG;
     PFEM_TRY(use_device(s));
     DevBuf<double> u, dg, df, ds;
     PFEM_TRY(post_nodal_field(s, u_nodal, u, "pfem_post_elements"));
-    const bool mats = s->n_mat > 0;
-    const ElemPrm prm = make_prm(mats ? nullptr : elemData, nullptr, m.kind);
-    ElemPrmTab tab{};
-    if (mats) PFEM_TRY(make_prm_tab(s, elemData, nullptr, &tab));
-    const int ng = post_components(m.kind);
-    const size_t ne = static_cast<size_t>(m.nElem);
-    if (grad) PFEM_TRY(dg.alloc(std::max<size_t>(ne * ng, 1)));
-    if (flux) PFEM_TRY(df.alloc(std::max<size_t>(ne * ng, 1)));
-    if (scalar) PFEM_TRY(ds.alloc(std::max<size_t>(ne, 1)));
-    PFEM_HIP(hipMemsetAsync(s->d_err.p, 0, sizeof(int), s->stream));
-    PFEM_HIP(hipEventRecord(s->ev0, s->stream));
-    if (m.nElem > 0) {
-        const dim3 grid(grid_for(m.nElem)), block(kBlock);
-        const double *up = u.p;
-#define PFEM_POST(KIND)                                                                                                          \
-    if (mats) hipLaunchKernelGGL((k_post_elements<KIND, ElemPrmTab>), grid, block, 0, s->stream, m, tab, up, dg.p, df.p, ds.p, s->d_err.p); \
-    else hipLaunchKernelGGL((k_post_elements<KIND, ElemPrm>), grid, block, 0, s->stream, m, prm, up, dg.p, df.p, ds.p, s->d_err.p)
-        switch (m.kind) {
-        case PFEM_POISSON_TRIA: PFEM_POST(PFEM_POISSON_TRIA); break;
-        case PFEM_POISSON_TET: PFEM_POST(PFEM_POISSON_TET); break;
-        case PFEM_ELAST_TET: PFEM_POST(PFEM_ELAST_TET); break;
-        case PFEM_POISSON_TRIA_INLINE: PFEM_POST(PFEM_POISSON_TRIA_INLINE); break;
-        case PFEM_ELAST_TRIA: PFEM_POST(PFEM_ELAST_TRIA); break;
+    return with_elem_prm(s, elemData, nullptr, [&](const auto &prm) -> int {
+        using PRM = std::decay_t<decltype(prm)>;
+        const int ng = post_components(m.kind);
+        const size_t ne = static_cast<size_t>(m.nElem);
+        if (grad) PFEM_TRY(dg.alloc(std::max<size_t>(ne * ng, 1)));
+        if (flux) PFEM_TRY(df.alloc(std::max<size_t>(ne * ng, 1)));
+        if (scalar) PFEM_TRY(ds.alloc(std::max<size_t>(ne, 1)));
+        PFEM_HIP(hipMemsetAsync(s->d_err.p, 0, sizeof(int), s->stream));
+        PFEM_HIP(hipEventRecord(s->ev0, s->stream));
+        if (m.nElem > 0) {
+            with_kind(m.kind, [&](auto kind) {
+                launch(k_post_elements<decltype(kind)::value, PRM>, dim3(grid_for(m.nElem)), dim3(kBlock), 0, s->stream, nullptr, nullptr, m, prm, u.p, dg.p,
+                       df.p, ds.p, s->d_err.p);
+            });
+            PFEM_TRY(check_kernel("k_post_elements"));
         }
-#undef PFEM_POST
-        PFEM_TRY(check_kernel("k_post_elements"));
-    }
-    PFEM_HIP(hipEventRecord(s->ev1, s->stream));
-    if (grad) PFEM_HIP(hipMemcpyAsync(grad, dg.p, sizeof(double) * ne * ng, hipMemcpyDeviceToHost, s->stream));
-    if (flux) PFEM_HIP(hipMemcpyAsync(flux, df.p, sizeof(double) * ne * ng, hipMemcpyDeviceToHost, s->stream));
-    if (scalar) PFEM_HIP(hipMemcpyAsync(scalar, ds.p, sizeof(double) * ne, hipMemcpyDeviceToHost, s->stream));
-    int err = 0;
-    PFEM_TRY(fetch_err(s, &err));
-    PFEM_TRY(elapsed(s, &s->post_elements_ms));
-    return err;
+        PFEM_HIP(hipEventRecord(s->ev1, s->stream));
+        if (grad) PFEM_HIP(hipMemcpyAsync(grad, dg.p, sizeof(double) * ne * ng, hipMemcpyDeviceToHost, s->stream));
+        if (flux) PFEM_HIP(hipMemcpyAsync(flux, df.p, sizeof(double) * ne * ng, hipMemcpyDeviceToHost, s->stream));
+        if (scalar) PFEM_HIP(hipMemcpyAsync(scalar, ds.p, sizeof(double) * ne, hipMemcpyDeviceToHost, s->stream));
+        int err = 0;
+        PFEM_TRY(fetch_err(s, &err));
+        PFEM_TRY(elapsed(s, &s->post_elements_ms));
+        return err;
+    });
 }
 
 extern "C" int pfem_post_nodal_forces(pfem_solver *s, const double *elemData, const double *timeData, const double *u_nodal, double *R)
 {
     if (!s || !R) return PFEM_ERR_ARG;
-    PFEM_TRY(post_one_rank(s, "pfem_post_nodal_forces"));
-    if (!s->have_mesh) {
-        set_last_error("pfem_post_nodal_forces: no mesh on the device (the MatSetValues path has none)");
-        return PFEM_ERR_STATE;
-    }
-    if (!s->have_pattern) {
-        set_last_error("pfem_post_nodal_forces: build the pattern first");
-        return PFEM_ERR_STATE;
-    }
+    PFEM_TRY(needs_pattern(s, "pfem_post_nodal_forces"));
     const MeshDev &m = s->mesh;
     if (m.kind != PFEM_POISSON_TRIA_INLINE && !elemData) return PFEM_ERR_ARG;
     PFEM_TRY(use_device(s));
     DevBuf<double> u, dR;
     PFEM_TRY(post_nodal_field(s, u_nodal, u, "pfem_post_nodal_forces"));
-    const bool mats = s->n_mat > 0;
-    const ElemPrm prm = make_prm(mats ? nullptr : elemData, timeData, m.kind);
-    ElemPrmTab tab{};
-    if (mats) PFEM_TRY(make_prm_tab(s, elemData, timeData, &tab));
-    const int64_t nn = m.nNode, nv = nn * m.ndof;
-    PFEM_TRY(dR.alloc(static_cast<size_t>(std::max<int64_t>(nv, 1))));
-    const bool gather = m.nElem > 0 && s->assembly_mode == PFEM_ASSEMBLY_GATHER && s->have_incidence && s->d_inc_rec.p;
-    const uint8_t *hubs = (gather && s->n_hubs > 0) ? s->d_node_hub.p : nullptr;
-    const double *up = u.p;
-    PFEM_HIP(hipMemsetAsync(s->d_err.p, 0, sizeof(int), s->stream));
-    PFEM_HIP(hipEventRecord(s->ev0, s->stream));
-    if (!gather) PFEM_HIP(hipMemsetAsync(dR.p, 0, sizeof(double) * static_cast<size_t>(std::max<int64_t>(nv, 1)), s->stream));
-    if (gather) {
-        // one thread per node, no atomics: every entry of R is stored by its node's thread
-        const dim3 grid(grid_for(nn)), block(kBlock);
-        const int64_t *ip = s->d_inc_ptr.p;
-        const int32_t *ic = s->d_inc_cnt.p;
-        const int4 *irec = s->d_inc_rec.p;
-#define PFEM_POST(KIND)                                                                                                          \
-    if (mats) hipLaunchKernelGGL((k_post_forces_gather<KIND, ElemPrmTab>), grid, block, 0, s->stream, m, tab, ip, ic, irec, hubs, up, dR.p, s->d_err.p); \
-    else hipLaunchKernelGGL((k_post_forces_gather<KIND, ElemPrm>), grid, block, 0, s->stream, m, prm, ip, ic, irec, hubs, up, dR.p, s->d_err.p)
-        switch (m.kind) {
-        case PFEM_POISSON_TRIA: PFEM_POST(PFEM_POISSON_TRIA); break;
-        case PFEM_POISSON_TET: PFEM_POST(PFEM_POISSON_TET); break;
-        case PFEM_ELAST_TET: PFEM_POST(PFEM_ELAST_TET); break;
-        case PFEM_POISSON_TRIA_INLINE: PFEM_POST(PFEM_POISSON_TRIA_INLINE); break;
-        case PFEM_ELAST_TRIA: PFEM_POST(PFEM_ELAST_TRIA); break;
+    return with_elem_prm(s, elemData, timeData, [&](const auto &prm) -> int {
+        using PRM = std::decay_t<decltype(prm)>;
+        const int64_t nn = m.nNode, nv = nn * m.ndof;
+        PFEM_TRY(dR.alloc(static_cast<size_t>(std::max<int64_t>(nv, 1))));
+        const bool gather = m.nElem > 0 && s->assembly_mode == PFEM_ASSEMBLY_GATHER && s->have_incidence && s->d_inc_rec.p;
+        const uint8_t *hubs = (gather && s->n_hubs > 0) ? s->d_node_hub.p : nullptr;
+        const dim3 block(kBlock);
+        PFEM_HIP(hipMemsetAsync(s->d_err.p, 0, sizeof(int), s->stream));
+        PFEM_HIP(hipEventRecord(s->ev0, s->stream));
+        if (!gather) PFEM_HIP(hipMemsetAsync(dR.p, 0, sizeof(double) * static_cast<size_t>(std::max<int64_t>(nv, 1)), s->stream));
+        if (gather) {
+            // one thread per node, no atomics: every entry of R is stored by its node's thread
+            with_kind(m.kind, [&](auto kind) {
+                launch(k_post_forces_gather<decltype(kind)::value, PRM>, dim3(grid_for(nn)), block, 0, s->stream, nullptr, nullptr, m, prm, s->d_inc_ptr.p,
+                       s->d_inc_cnt.p, s->d_inc_rec.p, hubs, u.p, dR.p, s->d_err.p);
+            });
+            PFEM_TRY(check_kernel("k_post_forces_gather"));
         }
-#undef PFEM_POST
-        PFEM_TRY(check_kernel("k_post_forces_gather"));
-    }
-    if (m.nElem > 0 && (!gather || hubs)) {
-        // one thread per element, f64 atomics: the whole mesh (scatter form, no incidence records), or the hub nodes only
-        const dim3 grid(grid_for(m.nElem)), block(kBlock);
-#define PFEM_POST(KIND)                                                                                                          \
-    if (mats) hipLaunchKernelGGL((k_post_forces_scatter<KIND, ElemPrmTab>), grid, block, 0, s->stream, m, tab, hubs, up, dR.p, s->d_err.p); \
-    else hipLaunchKernelGGL((k_post_forces_scatter<KIND, ElemPrm>), grid, block, 0, s->stream, m, prm, hubs, up, dR.p, s->d_err.p)
-        switch (m.kind) {
-        case PFEM_POISSON_TRIA: PFEM_POST(PFEM_POISSON_TRIA); break;
-        case PFEM_POISSON_TET: PFEM_POST(PFEM_POISSON_TET); break;
-        case PFEM_ELAST_TET: PFEM_POST(PFEM_ELAST_TET); break;
-        case PFEM_POISSON_TRIA_INLINE: PFEM_POST(PFEM_POISSON_TRIA_INLINE); break;
-        case PFEM_ELAST_TRIA: PFEM_POST(PFEM_ELAST_TRIA); break;
+        if (m.nElem > 0 && (!gather || hubs)) {
+            // one thread per element, f64 atomics: the whole mesh (scatter form, no incidence records), or the hub nodes only
+            with_kind(m.kind, [&](auto kind) {
+                launch(k_post_forces_scatter<decltype(kind)::value, PRM>, dim3(grid_for(m.nElem)), block, 0, s->stream, nullptr, nullptr, m, prm, hubs, u.p,
+                       dR.p, s->d_err.p);
+            });
+            PFEM_TRY(check_kernel("k_post_forces_scatter"));
         }
-#undef PFEM_POST
-        PFEM_TRY(check_kernel("k_post_forces_scatter"));
-    }
-    PFEM_HIP(hipEventRecord(s->ev1, s->stream));
-    std::vector<double> tmp;
-    double *out = R;
-    if (!s->h_niperm.empty()) { tmp.resize(static_cast<size_t>(nv)); out = tmp.data(); }
-    PFEM_HIP(hipMemcpyAsync(out, dR.p, sizeof(double) * nv, hipMemcpyDeviceToHost, s->stream));
-    int err = 0;
-    PFEM_TRY(fetch_err(s, &err));
-    PFEM_TRY(elapsed(s, &s->post_forces_ms));
-    if (err) return err;
-    if (!s->h_niperm.empty())             // the caller's node numbering
-        for (int64_t i = 0; i < nn; ++i)
-            for (int d = 0; d < m.ndof; ++d)
-                R[static_cast<int64_t>(s->h_niperm[static_cast<size_t>(i)]) * m.ndof + d] = tmp[static_cast<size_t>(i * m.ndof + d)];
-    return PFEM_OK;
+        PFEM_HIP(hipEventRecord(s->ev1, s->stream));
+        int err = 0;
+        PFEM_TRY(fetch_err(s, &err));
+        PFEM_TRY(elapsed(s, &s->post_forces_ms));
+        if (err) return err;
+        return post_nodes_to_caller(s, dR.p, m.ndof, R);
+    });
 }
 
 // Recovered nodal flux / stress (or gradient / strain): the volume-weighted average of the element values at every node
@@ -3783,34 +3694,31 @@ extern "C" int pfem_post_nodal_recovery(pfem_solver *s, const double *elemData, 
         set_last_error("pfem_post_nodal_recovery: the scalar is defined for the flux / stress only");
         return PFEM_ERR_ARG;
     }
-    PFEM_TRY(post_needs_pattern(s, "pfem_post_nodal_recovery"));
+    PFEM_TRY(needs_pattern(s, "pfem_post_nodal_recovery"));
     const MeshDev &m = s->mesh;
     if (m.kind != PFEM_POISSON_TRIA_INLINE && !elemData) return PFEM_ERR_ARG;
     PFEM_TRY(use_device(s));
     DevBuf<double> u, dn, dsc, dw;
     PFEM_TRY(post_nodal_field(s, u_nodal, u, "pfem_post_nodal_recovery"));
-    const bool mats = s->n_mat > 0;
-    const ElemPrm prm = make_prm(mats ? nullptr : elemData, nullptr, m.kind);
-    ElemPrmTab tab{};
-    if (mats) PFEM_TRY(make_prm_tab(s, elemData, nullptr, &tab));
-    const int ng = post_components(m.kind);
-    const size_t nn = static_cast<size_t>(m.nNode);
-    PFEM_TRY(dn.alloc(std::max<size_t>(nn * ng, 1)));
-    PFEM_TRY(dw.alloc(std::max<size_t>(nn, 1)));
-    if (nodal_scalar) PFEM_TRY(dsc.alloc(std::max<size_t>(nn, 1)));
-    PFEM_HIP(hipMemsetAsync(s->d_err.p, 0, sizeof(int), s->stream));
-    PFEM_HIP(hipEventRecord(s->ev0, s->stream));
-    if (mats) PFEM_TRY(post_recovery_launch(s, tab, u.p, field == PFEM_POST_GRAD, dn.p, dsc.p, dw.p));
-    else PFEM_TRY(post_recovery_launch(s, prm, u.p, field == PFEM_POST_GRAD, dn.p, dsc.p, dw.p));
-    PFEM_HIP(hipEventRecord(s->ev1, s->stream));
-    int err = 0;
-    PFEM_TRY(fetch_err(s, &err));
-    PFEM_TRY(elapsed(s, &s->post_recovery_ms));
-    if (err) return err;
-    if (nodal) PFEM_TRY(post_nodes_to_caller(s, dn.p, ng, nodal));
-    if (nodal_scalar) PFEM_TRY(post_nodes_to_caller(s, dsc.p, 1, nodal_scalar));
-    if (weight) PFEM_TRY(post_nodes_to_caller(s, dw.p, 1, weight));
-    return PFEM_OK;
+    return with_elem_prm(s, elemData, nullptr, [&](const auto &prm) -> int {
+        const int ng = post_components(m.kind);
+        const size_t nn = static_cast<size_t>(m.nNode);
+        PFEM_TRY(dn.alloc(std::max<size_t>(nn * ng, 1)));
+        PFEM_TRY(dw.alloc(std::max<size_t>(nn, 1)));
+        if (nodal_scalar) PFEM_TRY(dsc.alloc(std::max<size_t>(nn, 1)));
+        PFEM_HIP(hipMemsetAsync(s->d_err.p, 0, sizeof(int), s->stream));
+        PFEM_HIP(hipEventRecord(s->ev0, s->stream));
+        PFEM_TRY(post_recovery_launch(s, prm, u.p, field == PFEM_POST_GRAD, dn.p, dsc.p, dw.p));
+        PFEM_HIP(hipEventRecord(s->ev1, s->stream));
+        int err = 0;
+        PFEM_TRY(fetch_err(s, &err));
+        PFEM_TRY(elapsed(s, &s->post_recovery_ms));
+        if (err) return err;
+        if (nodal) PFEM_TRY(post_nodes_to_caller(s, dn.p, ng, nodal));
+        if (nodal_scalar) PFEM_TRY(post_nodes_to_caller(s, dsc.p, 1, nodal_scalar));
+        if (weight) PFEM_TRY(post_nodes_to_caller(s, dw.p, 1, weight));
+        return PFEM_OK;
+    });
 }
 
 // Zienkiewicz-Zhu indicator: the recovery above (its result stays on the device), then one pass over the elements
@@ -3818,57 +3726,43 @@ extern "C" int pfem_post_error_indicator(pfem_solver *s, const double *elemData,
                                          double *flux_norm2_total)
 {
     if (!s) return PFEM_ERR_ARG;
-    PFEM_TRY(post_needs_pattern(s, "pfem_post_error_indicator"));
+    PFEM_TRY(needs_pattern(s, "pfem_post_error_indicator"));
     const MeshDev &m = s->mesh;
     if (m.kind != PFEM_POISSON_TRIA_INLINE && !elemData) return PFEM_ERR_ARG;
     PFEM_TRY(use_device(s));
     DevBuf<double> u, dn, dw, de, part;
     PFEM_TRY(post_nodal_field(s, u_nodal, u, "pfem_post_error_indicator"));
-    const bool mats = s->n_mat > 0;
-    const ElemPrm prm = make_prm(mats ? nullptr : elemData, nullptr, m.kind);
-    ElemPrmTab tab{};
-    if (mats) PFEM_TRY(make_prm_tab(s, elemData, nullptr, &tab));
-    const int ng = post_components(m.kind);
-    const size_t nn = static_cast<size_t>(m.nNode), ne = static_cast<size_t>(m.nElem);
-    PFEM_TRY(dn.alloc(std::max<size_t>(nn * ng, 1)));
-    PFEM_TRY(dw.alloc(std::max<size_t>(nn, 1)));
-    if (eta2) PFEM_TRY(de.alloc(std::max<size_t>(ne, 1)));
-    PFEM_TRY(part.alloc(2 * kMaxGrid + 2));
-    PFEM_HIP(hipMemsetAsync(s->d_err.p, 0, sizeof(int), s->stream));
-    PFEM_HIP(hipEventRecord(s->ev0, s->stream));
-    if (mats) PFEM_TRY(post_recovery_launch(s, tab, u.p, 0, dn.p, nullptr, dw.p));
-    else PFEM_TRY(post_recovery_launch(s, prm, u.p, 0, dn.p, nullptr, dw.p));
-    {
+    return with_elem_prm(s, elemData, nullptr, [&](const auto &prm) -> int {
+        using PRM = std::decay_t<decltype(prm)>;
+        const int ng = post_components(m.kind);
+        const size_t nn = static_cast<size_t>(m.nNode), ne = static_cast<size_t>(m.nElem);
+        PFEM_TRY(dn.alloc(std::max<size_t>(nn * ng, 1)));
+        PFEM_TRY(dw.alloc(std::max<size_t>(nn, 1)));
+        if (eta2) PFEM_TRY(de.alloc(std::max<size_t>(ne, 1)));
+        PFEM_TRY(part.alloc(2 * kMaxGrid + 2));
+        PFEM_HIP(hipMemsetAsync(s->d_err.p, 0, sizeof(int), s->stream));
+        PFEM_HIP(hipEventRecord(s->ev0, s->stream));
+        PFEM_TRY(post_recovery_launch(s, prm, u.p, 0, dn.p, nullptr, dw.p));
         const unsigned gv = vec_grid(m.nElem);
-        const dim3 grid(gv), block(kBlock);
-        const double *up = u.p, *np = dn.p;
-#define PFEM_POST(KIND)                                                                                                          \
-    if (mats) hipLaunchKernelGGL((k_post_indicator<KIND, ElemPrmTab>), grid, block, 0, s->stream, m, tab, up, np, de.p, part.p, part.p + kMaxGrid, s->d_err.p); \
-    else hipLaunchKernelGGL((k_post_indicator<KIND, ElemPrm>), grid, block, 0, s->stream, m, prm, up, np, de.p, part.p, part.p + kMaxGrid, s->d_err.p)
-        switch (m.kind) {
-        case PFEM_POISSON_TRIA: PFEM_POST(PFEM_POISSON_TRIA); break;
-        case PFEM_POISSON_TET: PFEM_POST(PFEM_POISSON_TET); break;
-        case PFEM_ELAST_TET: PFEM_POST(PFEM_ELAST_TET); break;
-        case PFEM_POISSON_TRIA_INLINE: PFEM_POST(PFEM_POISSON_TRIA_INLINE); break;
-        case PFEM_ELAST_TRIA: PFEM_POST(PFEM_ELAST_TRIA); break;
-        }
-#undef PFEM_POST
+        with_kind(m.kind, [&](auto kind) {
+            launch(k_post_indicator<decltype(kind)::value, PRM>, dim3(gv), dim3(kBlock), 0, s->stream, nullptr, nullptr, m, prm, u.p, dn.p, de.p, part.p,
+                   part.p + kMaxGrid, s->d_err.p);
+        });
         PFEM_TRY(check_kernel("k_post_indicator"));
-        hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, s->stream, static_cast<const double *>(part.p),
-                           static_cast<const double *>(part.p + kMaxGrid), static_cast<int>(gv), part.p + 2 * kMaxGrid, static_cast<const CgCtl *>(nullptr));
+        post_reduce_partials(s, part.p, gv);
         PFEM_TRY(check_kernel("k_reduce_partials"));
-    }
-    PFEM_HIP(hipEventRecord(s->ev1, s->stream));
-    double h[2] = {0.0, 0.0};
-    if (eta2) PFEM_HIP(hipMemcpyAsync(eta2, de.p, sizeof(double) * ne, hipMemcpyDeviceToHost, s->stream));
-    PFEM_HIP(hipMemcpyAsync(h, part.p + 2 * kMaxGrid, 2 * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    int err = 0;
-    PFEM_TRY(fetch_err(s, &err));
-    PFEM_TRY(elapsed(s, &s->post_indicator_ms));
-    if (err) return err;
-    if (eta2_total) *eta2_total = h[0];
-    if (flux_norm2_total) *flux_norm2_total = h[1];
-    return PFEM_OK;
+        PFEM_HIP(hipEventRecord(s->ev1, s->stream));
+        double h[2] = {0.0, 0.0};
+        if (eta2) PFEM_HIP(hipMemcpyAsync(eta2, de.p, sizeof(double) * ne, hipMemcpyDeviceToHost, s->stream));
+        PFEM_HIP(hipMemcpyAsync(h, part.p + 2 * kMaxGrid, 2 * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        int err = 0;
+        PFEM_TRY(fetch_err(s, &err));
+        PFEM_TRY(elapsed(s, &s->post_indicator_ms));
+        if (err) return err;
+        if (eta2_total) *eta2_total = h[0];
+        if (flux_norm2_total) *flux_norm2_total = h[1];
+        return PFEM_OK;
+    });
 }
 
 // |b - K x|_2 and |b|_2 over the owned rows for the x of the last solve, K x by the SpMV form in effect (KSPBuildResidual /
@@ -3876,7 +3770,7 @@ extern "C" int pfem_post_error_indicator(pfem_solver *s, const double *elemData,
 extern "C" int pfem_solver_true_residual(pfem_solver *s, double *rnorm2, double *bnorm2)
 {
     if (!s) return PFEM_ERR_ARG;
-    PFEM_TRY(post_one_rank(s, "pfem_solver_true_residual"));
+    PFEM_TRY(needs_one_rank(s, "pfem_solver_true_residual"));
     if (!s->have_pattern || !s->solved) {
         set_last_error("pfem_solver_true_residual: no solve of this pattern yet");
         return PFEM_ERR_STATE;
@@ -3891,10 +3785,8 @@ extern "C" int pfem_solver_true_residual(pfem_solver *s, double *rnorm2, double 
     launch_spmv<false>(s, s->d_p.p, s->d_w.p, 0, nullptr, nullptr);
     PFEM_TRY(check_kernel("k_spmv"));
     const unsigned gv = vec_grid(s->n_owned);
-    hipLaunchKernelGGL(k_post_residual_partials, dim3(gv), dim3(kBlock), 0, s->stream, s->n_owned, static_cast<const double *>(s->d_rhs.p),
-                       static_cast<const double *>(s->d_w.p), part.p, part.p + kMaxGrid);
-    hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, s->stream, static_cast<const double *>(part.p),
-                       static_cast<const double *>(part.p + kMaxGrid), static_cast<int>(gv), part.p + 2 * kMaxGrid, static_cast<const CgCtl *>(nullptr));
+    launch(k_post_residual_partials, dim3(gv), dim3(kBlock), 0, s->stream, nullptr, nullptr, s->n_owned, s->d_rhs.p, s->d_w.p, part.p, part.p + kMaxGrid);
+    post_reduce_partials(s, part.p, gv);
     PFEM_TRY(check_kernel("k_post_residual_partials"));
     double h[2] = {0.0, 0.0};
     PFEM_HIP(hipMemcpyAsync(h, part.p + 2 * kMaxGrid, 2 * sizeof(double), hipMemcpyDeviceToHost, s->stream));
