@@ -463,6 +463,51 @@ int pfem_post_error_indicator(pfem_solver *s, const double *elemData, const doub
  * the SpMV form in effect (pfem_solver_solve's rnorm is |M^-1 r| of the CG recurrence).  PFEM_ERR_STATE before a solve.     */
 int pfem_solver_true_residual(pfem_solver *s, double *rnorm2, double *bnorm2);
 
+/* ---- explicit dynamics: lumped mass and central-difference steps ----------- */
+/* M u'' + alpha M u' + K u = lambda(t) f on the assembled system: K by the SpMV form in effect, f the assembled right-hand side
+ * (body force, nodal forces, surface loads and the Dirichlet lift, all scaled together by lambda), M the lumped mass below.  The
+ * reference's explicit drivers (tetraelasticityexplicit.F, triaelasticityexplicit.F) are this loop on the host; their Residual*
+ * routines differ from their own stiffness routines and are not reproduced: the internal force here is K u.
+ * One rank and the batched path only (PFEM_ERR_STATE otherwise).  Vectors per owned dof are in pfem_solver_get_solution's order.
+ *
+ * pfem_elem_lumped_mass: MassMatrixLinearTria / MassMatrixLinearTetra (elementutilitieselasticity2D.F:283, 3D.F:401) for any
+ * kind -- the row sums of the consistent mass at the kind's one Gauss point, ((density * dvol) * N_i) * N_j summed over j
+ * ascending, Mlocal[npe * ndof] (a scalar kind gives the wave equation's mass).  dvol and N are the stiffness routine's;
+ * density is an argument of its own (the reference reads elemData(3), which is the thickness here); elemData is read for the
+ * thickness of PFEM_ELAST_TRIA only and may be NULL otherwise.  PFEM_ERR_ARG: density not positive.                         */
+int pfem_elem_lumped_mass(int kind, const double *xNode, const double *yNode, const double *zNode /* NULL in 2-D */,
+                          const double *elemData, double density, double *Mlocal);
+/* The mass vector on the device.  density[m]: one entry per material row while a map is set, else one entry; elemData as
+ * pfem_assemble takes it (read for the thickness of PFEM_ELAST_TRIA; may be NULL for the other kinds without a map).  A node's
+ * mass is the sum of its shares of its elements' pfem_elem_lumped_mass in ascending element order (gather form: one thread per
+ * node, the same bits in every run; hub nodes and the scatter form: f64 atomics).  total_mass (may be NULL): the sum over ALL
+ * nodes.  Needs the pattern and an assembled matrix (PFEM_ERR_STATE); lives until the next pattern build; the state is set to
+ * rest at t = 0, lambda = 1, no probes.                                                                                      */
+int pfem_dynamics_setup(pfem_solver *s, const double *elemData, const double *density, double *total_mass);
+int pfem_dynamics_get_mass(pfem_solver *s, double *mass_owned);
+/* dt = 2 / sqrt(max_i sum_j |K_ij| / m_i): a Gershgorin bound on omega_max, so never above the critical step 2 / omega_max   */
+int pfem_dynamics_stable_dt(pfem_solver *s, double *dt);
+/* u(t0) = u0, u'(t0) = v0 (NULL: zeros).  The start is the standard one, a0 = (lambda(t0) f - K u0) / m and
+ * u_{-1} = u0 - dt v0 + dt^2/2 a0, formed at the next pfem_dynamics_run, where dt is known.                                 */
+int pfem_dynamics_set_state(pfem_solver *s, double t0, const double *u0, const double *v0);
+/* lambda(t): piecewise linear through (t[k], lambda[k]), t strictly ascending, constant outside the table; n = 0: lambda = 1.
+ * It scales the assembled right-hand side AS A WHOLE: a nonzero Dirichlet value enters through the lift in that vector and is
+ * scaled with the loads.                                                                                                    */
+int pfem_dynamics_set_load_curve(pfem_solver *s, int n, const double *t, const double *lambda);
+/* dofs whose u and v go into the history rows: GLOBAL free-dof ids as for pfem_rhs_add_values (PFEM_ERR_ARG: not an owned row) */
+int pfem_dynamics_set_probes(pfem_solver *s, int n, const int64_t *global_dof);
+/* n_steps steps   (1/dt^2 + alpha/2dt) m u_{n+1} = lambda(t_n) f - K u_n + m/dt^2 (2 u_n - u_{n-1}) + alpha m/(2dt) u_{n-1}:
+ * two launches a step (the product, the update), replayed from a captured graph of 48 steps with the step counter, t_n,
+ * lambda(t_n) and the sampling on the device; nothing waits for the device before the last step.  Every sample_every-th step of
+ * THIS run (0: none) writes a row  [t_{n+1}, T, S, W, u_{n+1} at the probes, v_{n+1/2} at the probes]  with
+ *   T = 1/2 sum m v_{n+1/2}^2,  S = 1/2 u_{n+1} . K u_n,  W = f . u_{n+1}      (v_{n+1/2} = (u_{n+1} - u_n) / dt)
+ * -- T + S is the exact invariant of the undamped, unloaded scheme -- summed in a fixed order (the same bits in every run);
+ * history[rows * (4 + 2 n_probe)] is copied back once, after the run; *rows = n_steps / sample_every (history may be NULL when
+ * that is 0).  A second run with the same dt continues exactly; another dt needs a new pfem_dynamics_set_state (PFEM_ERR_STATE). */
+int pfem_dynamics_run(pfem_solver *s, double dt, int64_t n_steps, double alpha, int64_t sample_every, double *history, int64_t *rows);
+/* t_n, n, u_n and v_{n-1/2} (before the first run: u0 and v0 as set); any output may be NULL                                   */
+int pfem_dynamics_get_state(pfem_solver *s, double *t, int64_t *step, double *u, double *v);
+
 /* ---- inspection / export (device -> host) -------------------------------- */
 /* global dof id of every local row (owned first, then ghosts ascending) */
 int pfem_get_local_to_global(pfem_solver *s, int64_t *gid);

@@ -169,6 +169,10 @@ int pfem_matrix_info(pfem_solver *s, int64_t *n_owned, int64_t *n_local, int64_t
 int pfem_spmv(pfem_solver *s, const double *x, double *y);
 /* time `reps` back-to-back SpMV launches with HIP events on the solver's stream */
 int pfem_bench_spmv(pfem_solver *s, int reps, double *ms_per_launch);
+/* time of one explicit step (pfem_dynamics_run's two launches) in microseconds, inside `graphs` back-to-back replays of the
+ * captured step graph between two HIP events, after a run that aligns the step counter, captures and warms up; undamped, no
+ * history.  The state advances by the steps taken.  PFEM_ERR_STATE where the stream cannot be captured.                     */
+int pfem_dynamics_bench(pfem_solver *s, double dt, int graphs, double *us_per_step, int *steps_per_graph);
 
 /* Timings of the last calls, measured with HIP events on the solver's stream [ms]. */
 typedef struct pfem_timings {

@@ -157,6 +157,16 @@ SIGNATURES = {
     "pfem_solver_true_residual": [_P, _P, _P],
     "pfem_post_timings": [_P, _P, _P],
     "pfem_post_recovery_timings": [_P, _P, _P],
+    "pfem_elem_lumped_mass": [_I, _P, _P, _P, _P, _D, _P],
+    "pfem_dynamics_setup": [_P, _P, _P, _P],
+    "pfem_dynamics_get_mass": [_P, _P],
+    "pfem_dynamics_stable_dt": [_P, _P],
+    "pfem_dynamics_set_state": [_P, _D, _P, _P],
+    "pfem_dynamics_set_load_curve": [_P, _I, _P, _P],
+    "pfem_dynamics_set_probes": [_P, _I, _P],
+    "pfem_dynamics_run": [_P, _D, _L, _D, _L, _P, _P],
+    "pfem_dynamics_get_state": [_P, _P, _P, _P, _P],
+    "pfem_dynamics_bench": [_P, _D, _I, _P, _P],
     "pfem_matrix_info": [_P, _P, _P, _P, _P],
     "pfem_get_local_to_global": [_P, _P],
     "pfem_get_csr": [_P, _P, _P, _P],

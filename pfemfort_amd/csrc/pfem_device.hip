@@ -32,6 +32,7 @@
 #include "pfem_kernels.hpp"
 #include "pfem_valdict.hpp"
 #include "pfem_amg_kernels.hpp"
+#include "pfem_dyn_kernels.hpp"
 #include "pfem_peer.hpp"
 
 using namespace pfem;
@@ -495,6 +496,27 @@ struct CommBackend {
 };
 
 // ---------------------------------------------------------------------------
+// explicit dynamics on a handle (pfem_dynamics_*, pfem_dynamics.inc): lives from pfem_dynamics_setup to the next pattern
+// ---------------------------------------------------------------------------
+struct Dyn {
+    int64_t n = 0;                         // rows (n_loc of the pattern it was set up on)
+    DevBuf<double> d_mnode, d_m, d_minv;   // mass per node (device node order), m and 1 / m per matrix row
+    DevBuf<double> d_ustore[3];            // the three displacement buffers, guarded like the SpMV's input vector
+    double *u[3] = {nullptr, nullptr, nullptr};
+    DevBuf<double> d_v0, d_part, d_hist, d_ct, d_cl;
+    DevBuf<int32_t> d_probe;
+    DevBuf<DynCtl> d_ctl;
+    int n_curve = 0, n_probe = 0;
+    double total_mass = 0.0;
+    // state: u_n in u[step % 3], u_{n-1} in u[(step + 2) % 3]; started: u_{-1} has been formed with `dt`
+    long long step = 0;
+    double t0 = 0.0, dt = 0.0;
+    bool started = false;
+    int nb = 0;                            // blocks of a step launch
+    CgGraph graph;                         // kDynGraphSteps steps: 2 launches each
+};
+
+// ---------------------------------------------------------------------------
 // the solver object
 // ---------------------------------------------------------------------------
 struct pfem_solver {
@@ -679,6 +701,7 @@ struct pfem_solver {
     } d_p;
     int pc = PFEM_PC_JACOBI;
     std::unique_ptr<Amg> amg;      // -pc_type gamg: the hierarchy (pfem_amg.inc); rebuilt when the pattern changes
+    std::unique_ptr<Dyn> dyn;      // explicit dynamics (pfem_dynamics.inc); dropped when the pattern changes
     DevBuf<double> d_binv[3];      // node-block Jacobi: row (i - r0) of the inverse diagonal block, columns 0..2
     DevBuf<double> d_r2, d_z;      // ... second residual buffer (ping-pong), z = Binv r, per-row (first row | size << 30)
     // single-reduction CG (pfem_solver_set_cg_single_reduction): z is the SpMV input (guarded), s = A z, and a second
@@ -1772,6 +1795,7 @@ int alloc_vectors(pfem_solver *s)
 {
     const size_t n = static_cast<size_t>(s->n_loc);
     s->solved = false;
+    s->dyn.reset();
     PFEM_TRY(s->d_rhs.alloc(n));
     PFEM_TRY(s->d_x.alloc(n));
     PFEM_TRY(s->d_r.alloc(n));
@@ -5550,6 +5574,8 @@ extern "C" int pfem_solver_factorise(pfem_solver *s)
     s->status = PFEM_FACTORISE_OK;
     return PFEM_OK;
 }
+
+#include "pfem_dynamics.inc"
 
 extern "C" int pfem_solver_solve(pfem_solver *s, int *its, int *reason, double *rnorm)
 {

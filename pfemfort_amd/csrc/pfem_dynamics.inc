@@ -1,0 +1,391 @@
+// pfem_dynamics.inc -- explicit central-difference dynamics on an assembled system (pfem_dynamics_*; DESIGN.md section 11).
+// Included once by pfem_device.hip, after the SpMV launch and the post-processing helpers it uses.  A path beside the solve:
+// it reads the assembled matrix (by launch_spmv in the form in effect) and right-hand side and writes only its own buffers.
+
+namespace {
+
+constexpr int kDynGraphSteps = 48;         // steps of one captured graph: a multiple of 3 (buffer rotation) and of 2 (DynCtl parity)
+
+int needs_dynamics(pfem_solver *s, const char *who)
+{
+    PFEM_TRY(needs_one_rank(s, who));
+    if (!s->dyn || !s->have_pattern) {
+        set_last_error(std::string(who) + ": pfem_dynamics_setup first (after every pattern build)");
+        return PFEM_ERR_STATE;
+    }
+    return PFEM_OK;
+}
+
+// host array of the owned rows in the caller's order (pfem_solver_get_solution's) -> device vector in the internal order
+int dyn_upload_rows(pfem_solver *s, const double *in, double *d_vec)
+{
+    const int64_t n = s->n_owned;
+    std::vector<double> tmp;
+    if (s->reordered) {
+        tmp.assign(static_cast<size_t>(n), 0.0);
+        for (int64_t i = 0; i < n; ++i) tmp[static_cast<size_t>(to_internal(s, i))] = in[i];
+    }
+    PFEM_HIP(hipMemcpyAsync(d_vec, tmp.empty() ? in : tmp.data(), sizeof(double) * static_cast<size_t>(n), hipMemcpyHostToDevice, s->stream));
+    PFEM_HIP(hipStreamSynchronize(s->stream));       // (tmp goes out of scope)
+    return PFEM_OK;
+}
+
+// the parameter block of a run's launches
+DynPar dyn_par(const pfem_solver *s, double alpha, long long sample_every)
+{
+    const Dyn &D = *s->dyn;
+    DynPar P{};
+    P.n = D.n;
+    P.t0 = D.t0;
+    P.dt = D.dt;
+    P.c0 = 1.0 / (D.dt * D.dt);
+    P.c1 = alpha / (2.0 * D.dt);
+    P.a = P.c0 + P.c1;
+    P.sample_every = sample_every;
+    P.n_curve = D.n_curve;
+    P.ct = D.d_ct.p;
+    P.cl = D.d_cl.p;
+    P.n_probe = D.n_probe;
+    P.probe = D.d_probe.p;
+    P.hist = D.d_hist.p;
+    P.nb = D.nb;
+    P.part = D.d_part.p;
+    return P;
+}
+
+inline uint64_t dyn_bits(double v)
+{
+    uint64_t b;
+    std::memcpy(&b, &v, sizeof b);
+    return b;
+}
+
+// step n -> n + 1, enqueued: w = K u_n by the SpMV form in effect, then k_dyn_step.  in_graph: the step index comes from the
+// control block (the launch is replayed), else it is an argument.
+void dyn_enqueue_step(pfem_solver *s, const DynPar &P, long long step, bool in_graph)
+{
+    Dyn &D = *s->dyn;
+    const double *u = D.u[step % 3], *up = D.u[(step + 2) % 3];
+    double *un = D.u[(step + 1) % 3];
+    launch_spmv<false>(s, u, s->d_w.p, 0, nullptr, nullptr);
+    launch(k_dyn_step, dim3(static_cast<unsigned>(D.nb)), dim3(kBlock), 0, s->stream, nullptr, nullptr, P, D.d_ctl.p, static_cast<int>(step & 1),
+           in_graph ? -1LL : step, s->d_rhs.p, D.d_m.p, D.d_minv.p, s->d_w.p, u, up, un);
+}
+
+}  // namespace
+
+// Lumped mass of the mesh on the device: m and 1 / m per matrix row, the total mass of the body (all nodes, constrained ones
+// included).  density: one entry per material row, or one entry without a map.
+extern "C" int pfem_dynamics_setup(pfem_solver *s, const double *elemData, const double *density, double *total_mass)
+{
+    if (!s || !density) return PFEM_ERR_ARG;
+    PFEM_TRY(needs_pattern(s, "pfem_dynamics_setup"));
+    if (s->status < PFEM_ASSEMBLY_OK) {
+        set_last_error("pfem_dynamics_setup: assemble the matrix first");
+        return PFEM_ERR_STATE;
+    }
+    const MeshDev &m = s->mesh;
+    if ((m.kind == PFEM_ELAST_TRIA || s->n_mat > 0) && !elemData) return PFEM_ERR_ARG;
+    for (int k = 0; k < std::max(s->n_mat, 1); ++k)
+        if (!(density[k] > 0.0) || !std::isfinite(density[k])) return PFEM_ERR_ARG;
+    PFEM_TRY(use_device(s));
+    auto D = std::make_unique<Dyn>();
+    const int64_t n = s->n_loc, nn = m.nNode;
+    D->n = n;
+    D->nb = static_cast<int>(std::max<int64_t>(1, (n + kDynBlockRows - 1) / kDynBlockRows));
+    PFEM_TRY(D->d_mnode.alloc(static_cast<size_t>(std::max<int64_t>(nn, 1))));
+    PFEM_TRY(D->d_m.alloc(static_cast<size_t>(std::max<int64_t>(n, 1))));
+    PFEM_TRY(D->d_minv.alloc(static_cast<size_t>(std::max<int64_t>(n, 1))));
+    PFEM_TRY(D->d_v0.alloc(static_cast<size_t>(std::max<int64_t>(n, 1))));
+    PFEM_TRY(D->d_part.alloc(static_cast<size_t>(std::max(6 * D->nb, kMaxGrid))));
+    PFEM_TRY(D->d_ctl.alloc(1));
+    for (int b = 0; b < 3; ++b) {
+        const size_t len = static_cast<size_t>(n) + 2 * kVecGuard;
+        PFEM_TRY(D->d_ustore[b].alloc(len));
+        PFEM_HIP(hipMemsetAsync(D->d_ustore[b].p, 0, len * sizeof(double), s->stream));
+        D->u[b] = D->d_ustore[b].p + kVecGuard;
+    }
+    PFEM_HIP(hipMemsetAsync(D->d_v0.p, 0, sizeof(double) * static_cast<size_t>(std::max<int64_t>(n, 1)), s->stream));
+    PFEM_HIP(hipMemsetAsync(D->d_m.p, 0, sizeof(double) * static_cast<size_t>(std::max<int64_t>(n, 1)), s->stream));
+    PFEM_HIP(hipMemsetAsync(D->d_minv.p, 0, sizeof(double) * static_cast<size_t>(std::max<int64_t>(n, 1)), s->stream));
+    DevBuf<double> d_dens;
+    DynDens dens{nullptr, density[0]};
+    if (s->n_mat > 0) {
+        PFEM_TRY(d_dens.alloc(static_cast<size_t>(s->n_mat)));
+        PFEM_HIP(hipMemcpyAsync(d_dens.p, density, sizeof(double) * static_cast<size_t>(s->n_mat), hipMemcpyHostToDevice, s->stream));
+        dens.tab = d_dens.p;
+    }
+    const int rc = with_elem_prm(s, elemData, nullptr, [&](const auto &prm) -> int {
+        using PRM = std::decay_t<decltype(prm)>;
+        const bool gather = m.nElem > 0 && s->assembly_mode == PFEM_ASSEMBLY_GATHER && s->have_incidence && s->d_inc_rec.p;
+        const uint8_t *hubs = (gather && s->n_hubs > 0) ? s->d_node_hub.p : nullptr;
+        const dim3 block(kBlock);
+        PFEM_HIP(hipMemsetAsync(s->d_err.p, 0, sizeof(int), s->stream));
+        if (gather) {
+            with_kind(m.kind, [&](auto kind) {
+                launch(k_dyn_mass_gather<decltype(kind)::value, PRM>, dim3(grid_for(nn)), block, 0, s->stream, nullptr, nullptr, m, prm, dens, s->d_inc_ptr.p,
+                       s->d_inc_cnt.p, s->d_inc_rec.p, hubs, D->d_mnode.p, s->d_err.p);
+            });
+            PFEM_TRY(check_kernel("k_dyn_mass_gather"));
+        } else {
+            PFEM_HIP(hipMemsetAsync(D->d_mnode.p, 0, sizeof(double) * static_cast<size_t>(std::max<int64_t>(nn, 1)), s->stream));
+        }
+        if (m.nElem > 0 && (!gather || hubs)) {
+            with_kind(m.kind, [&](auto kind) {
+                launch(k_dyn_mass_scatter<decltype(kind)::value, PRM>, dim3(grid_for(m.nElem)), block, 0, s->stream, nullptr, nullptr, m, prm, dens, hubs,
+                       D->d_mnode.p, s->d_err.p);
+            });
+            PFEM_TRY(check_kernel("k_dyn_mass_scatter"));
+        }
+        if (m.nElem > 0) {
+            launch(k_dyn_mass_rows, dim3(grid_for(m.nElem * m.nsize)), block, 0, s->stream, nullptr, nullptr, m, D->d_mnode.p, D->d_m.p, D->d_minv.p);
+            PFEM_TRY(check_kernel("k_dyn_mass_rows"));
+        }
+        const unsigned gv = vec_grid(nn);
+        launch(k_dyn_mass_total, dim3(gv), block, 0, s->stream, nullptr, nullptr, nn, D->d_mnode.p, D->d_part.p);
+        PFEM_TRY(check_kernel("k_dyn_mass_total"));
+        std::vector<double> h(gv);
+        PFEM_HIP(hipMemcpyAsync(h.data(), D->d_part.p, sizeof(double) * gv, hipMemcpyDeviceToHost, s->stream));
+        int err = 0;
+        PFEM_TRY(fetch_err(s, &err));         // (waits for the stream)
+        D->total_mass = 0.0;
+        for (double v : h) D->total_mass += v;          // the blocks' partials in block order
+        return err;
+    });
+    if (rc != PFEM_OK) return rc;
+    // the default state: at rest at t = 0
+    const DynCtl c0{{0, 0}, 0};
+    PFEM_HIP(hipMemcpyAsync(D->d_ctl.p, &c0, sizeof c0, hipMemcpyHostToDevice, s->stream));
+    PFEM_HIP(hipStreamSynchronize(s->stream));
+    if (total_mass) *total_mass = D->total_mass;
+    s->dyn = std::move(D);
+    return PFEM_OK;
+}
+
+// m per owned dof, in pfem_solver_get_solution's order
+extern "C" int pfem_dynamics_get_mass(pfem_solver *s, double *mass_owned)
+{
+    if (!s || !mass_owned) return PFEM_ERR_ARG;
+    PFEM_TRY(needs_dynamics(s, "pfem_dynamics_get_mass"));
+    PFEM_TRY(use_device(s));
+    return download_external(s, s->dyn->d_m.p, mass_owned, s->n_owned);
+}
+
+// dt = 2 / sqrt(max_i sum_j |K_ij| / m_i): Gershgorin's bound on the largest eigenvalue of M^-1 K, so never above 2 / omega_max.
+// One pass over the assembled matrix in its row form (the form every assembly writes).
+extern "C" int pfem_dynamics_stable_dt(pfem_solver *s, double *dt)
+{
+    if (!s || !dt) return PFEM_ERR_ARG;
+    PFEM_TRY(needs_dynamics(s, "pfem_dynamics_stable_dt"));
+    PFEM_TRY(use_device(s));
+    Dyn &D = *s->dyn;
+    const unsigned gv = vec_grid(D.n);
+    launch(k_dyn_gershgorin, dim3(gv), dim3(kBlock), 0, s->stream, nullptr, nullptr, s->sell(), D.n, D.d_minv.p, D.d_part.p);
+    PFEM_TRY(check_kernel("k_dyn_gershgorin"));
+    std::vector<double> h(gv);
+    PFEM_HIP(hipMemcpyAsync(h.data(), D.d_part.p, sizeof(double) * gv, hipMemcpyDeviceToHost, s->stream));
+    PFEM_HIP(hipStreamSynchronize(s->stream));
+    const double best = *std::max_element(h.begin(), h.end());
+    if (!(best > 0.0)) {
+        set_last_error("pfem_dynamics_stable_dt: the matrix has no entries (or no mass)");
+        return PFEM_ERR_STATE;
+    }
+    *dt = 2.0 / std::sqrt(best);
+    return PFEM_OK;
+}
+
+// State at t0: u0, v0 per owned dof in pfem_solver_get_solution's order (NULL: zeros).  u_{-1} is formed at the next run.
+extern "C" int pfem_dynamics_set_state(pfem_solver *s, double t0, const double *u0, const double *v0)
+{
+    if (!s || !std::isfinite(t0)) return PFEM_ERR_ARG;
+    PFEM_TRY(needs_dynamics(s, "pfem_dynamics_set_state"));
+    PFEM_TRY(use_device(s));
+    Dyn &D = *s->dyn;
+    const size_t nb = sizeof(double) * static_cast<size_t>(std::max<int64_t>(D.n, 1));
+    if (u0) PFEM_TRY(dyn_upload_rows(s, u0, D.u[0]));
+    else PFEM_HIP(hipMemsetAsync(D.u[0], 0, nb, s->stream));
+    if (v0) PFEM_TRY(dyn_upload_rows(s, v0, D.d_v0.p));
+    else PFEM_HIP(hipMemsetAsync(D.d_v0.p, 0, nb, s->stream));
+    PFEM_HIP(hipStreamSynchronize(s->stream));
+    D.t0 = t0;
+    D.step = 0;
+    D.dt = 0.0;
+    D.started = false;
+    return PFEM_OK;
+}
+
+// lambda(t): piecewise linear through (t[k], lambda[k]), t strictly ascending, constant outside; n = 0: lambda = 1.  It scales
+// the assembled right-hand side as a whole.
+extern "C" int pfem_dynamics_set_load_curve(pfem_solver *s, int n, const double *t, const double *lambda)
+{
+    if (!s || n < 0 || (n > 0 && (!t || !lambda))) return PFEM_ERR_ARG;
+    for (int k = 0; k < n; ++k)
+        if (!std::isfinite(t[k]) || !std::isfinite(lambda[k]) || (k > 0 && !(t[k] > t[k - 1]))) return PFEM_ERR_ARG;
+    PFEM_TRY(needs_dynamics(s, "pfem_dynamics_set_load_curve"));
+    PFEM_TRY(use_device(s));
+    Dyn &D = *s->dyn;
+    if (n > 0) {
+        PFEM_TRY(D.d_ct.alloc(static_cast<size_t>(n)));
+        PFEM_TRY(D.d_cl.alloc(static_cast<size_t>(n)));
+        PFEM_HIP(hipMemcpyAsync(D.d_ct.p, t, sizeof(double) * static_cast<size_t>(n), hipMemcpyHostToDevice, s->stream));
+        PFEM_HIP(hipMemcpyAsync(D.d_cl.p, lambda, sizeof(double) * static_cast<size_t>(n), hipMemcpyHostToDevice, s->stream));
+        PFEM_HIP(hipStreamSynchronize(s->stream));
+    }
+    D.n_curve = n;
+    D.graph.invalidate();          // (the table may sit where the last one sat)
+    return PFEM_OK;
+}
+
+// probes: GLOBAL free-dof ids, as pfem_rhs_add_values takes them
+extern "C" int pfem_dynamics_set_probes(pfem_solver *s, int n, const int64_t *global_dof)
+{
+    if (!s || n < 0 || (n > 0 && !global_dof)) return PFEM_ERR_ARG;
+    PFEM_TRY(needs_dynamics(s, "pfem_dynamics_set_probes"));
+    std::vector<int32_t> rows(static_cast<size_t>(n));
+    for (int k = 0; k < n; ++k) {
+        const int64_t g = global_dof[k];
+        if (g < s->row_start || g >= s->row_start + s->n_owned) return PFEM_ERR_ARG;
+        rows[static_cast<size_t>(k)] = to_internal(s, g - s->row_start);
+    }
+    PFEM_TRY(use_device(s));
+    Dyn &D = *s->dyn;
+    if (n > 0) {
+        PFEM_TRY(D.d_probe.alloc(static_cast<size_t>(n)));
+        PFEM_HIP(hipMemcpyAsync(D.d_probe.p, rows.data(), sizeof(int32_t) * static_cast<size_t>(n), hipMemcpyHostToDevice, s->stream));
+        PFEM_HIP(hipStreamSynchronize(s->stream));
+    }
+    D.n_probe = n;
+    D.graph.invalidate();
+    return PFEM_OK;
+}
+
+// n_steps central-difference steps of size dt with damping C = alpha M.  history: n_steps / sample_every rows of
+// 4 + 2 n_probe doubles (may be NULL with rows), copied back once after the last step; nothing in between waits for the device.
+extern "C" int pfem_dynamics_run(pfem_solver *s, double dt, int64_t n_steps, double alpha, int64_t sample_every, double *history, int64_t *rows)
+{
+    if (!s || !(dt > 0.0) || !std::isfinite(dt) || n_steps < 0 || !(alpha >= 0.0) || !std::isfinite(alpha) || sample_every < 0) return PFEM_ERR_ARG;
+    PFEM_TRY(needs_dynamics(s, "pfem_dynamics_run"));
+    Dyn &D = *s->dyn;
+    if (D.started && dt != D.dt) {
+        set_last_error("pfem_dynamics_run: another dt than the run before needs a new pfem_dynamics_set_state");
+        return PFEM_ERR_STATE;
+    }
+    if (s->status < PFEM_ASSEMBLY_OK) {
+        set_last_error("pfem_dynamics_run: no assembled matrix (pfem_assemble after the last pfem_solver_set_zero)");
+        return PFEM_ERR_STATE;
+    }
+    PFEM_TRY(use_device(s));
+    const long long every = sample_every > 0 ? sample_every : (1LL << 62);          // 0: no rows, ever
+    const int64_t n_rows = n_steps / every;
+    const int ncol = 4 + 2 * D.n_probe;
+    if (rows) *rows = n_rows;
+    if (n_rows > 0 && !history) return PFEM_ERR_ARG;
+    if (n_rows > 0 && D.d_hist.n < static_cast<size_t>(n_rows * ncol)) PFEM_TRY(D.d_hist.alloc(static_cast<size_t>(n_rows * ncol)));
+    D.dt = dt;
+    const DynPar P = dyn_par(s, alpha, every);
+    // the SpMV's copies of the matrix values, as every product outside a solve brings them up to date
+    mark_group_vals(s);
+    PFEM_TRY(refresh_group_vals(s));
+    const DynCtl c{{D.step, D.step}, D.step};
+    PFEM_HIP(hipMemcpyAsync(D.d_ctl.p, &c, sizeof c, hipMemcpyHostToDevice, s->stream));
+    if (!D.started) {
+        launch_spmv<false>(s, D.u[0], s->d_w.p, 0, nullptr, nullptr);
+        launch(k_dyn_start, dim3(grid_for(D.n)), dim3(kBlock), 0, s->stream, nullptr, nullptr, P, s->d_rhs.p, D.d_minv.p, s->d_w.p, D.u[0], D.d_v0.p, D.u[2]);
+        PFEM_TRY(check_kernel("k_dyn_start"));
+        D.started = true;
+    }
+    const long long end = D.step + n_steps;
+    // up to the next multiple of the graph's period by stream launches, whole graphs, the rest by stream launches
+    while (D.step < end && (D.step % kDynGraphSteps != 0 || end - D.step < kDynGraphSteps)) {
+        dyn_enqueue_step(s, P, D.step, false);
+        ++D.step;
+    }
+    PFEM_TRY(check_kernel("k_dyn_step"));
+    if (end - D.step >= kDynGraphSteps) {
+        std::vector<uint64_t> key = {
+            reinterpret_cast<uint64_t>(D.u[0]), reinterpret_cast<uint64_t>(D.u[1]), reinterpret_cast<uint64_t>(D.u[2]), reinterpret_cast<uint64_t>(s->d_w.p),
+            reinterpret_cast<uint64_t>(s->d_rhs.p), reinterpret_cast<uint64_t>(D.d_m.p), reinterpret_cast<uint64_t>(D.d_minv.p),
+            reinterpret_cast<uint64_t>(D.d_ctl.p), reinterpret_cast<uint64_t>(D.d_part.p), reinterpret_cast<uint64_t>(D.d_hist.p),
+            reinterpret_cast<uint64_t>(D.d_ct.p), reinterpret_cast<uint64_t>(D.d_cl.p), reinterpret_cast<uint64_t>(D.d_probe.p),
+            reinterpret_cast<uint64_t>(s->d_vals.p), reinterpret_cast<uint64_t>(s->d_cols.p), reinterpret_cast<uint64_t>(s->d_rvals.p),
+            reinterpret_cast<uint64_t>(s->d_gvals.p), reinterpret_cast<uint64_t>(s->d_dwords.p), reinterpret_cast<uint64_t>(s->stream),
+            static_cast<uint64_t>(D.n), static_cast<uint64_t>(D.nb), static_cast<uint64_t>(D.n_curve), static_cast<uint64_t>(D.n_probe),
+            static_cast<uint64_t>(every), dyn_bits(P.t0), dyn_bits(P.dt), dyn_bits(P.c1), spmv_key(s), spmv_form(s).kernel_id()};
+        bool use_graph = false;
+        PFEM_TRY(D.graph.ensure(s->stream, std::move(key), {}, [&](int) {
+            for (int j = 0; j < kDynGraphSteps; ++j) dyn_enqueue_step(s, P, j, true);
+            return hipGetLastError() == hipSuccess;
+        }, &use_graph));
+        while (end - D.step >= kDynGraphSteps) {
+            if (use_graph) {
+                PFEM_HIP(hipGraphLaunch(D.graph.exec[0], s->stream));
+            } else {          // a stream that cannot be captured (the legacy default stream): the same launches, one by one
+                for (int j = 0; j < kDynGraphSteps; ++j) dyn_enqueue_step(s, P, D.step + j, false);
+                PFEM_TRY(check_kernel("k_dyn_step"));
+            }
+            D.step += kDynGraphSteps;
+        }
+        while (D.step < end) {
+            dyn_enqueue_step(s, P, D.step, false);
+            ++D.step;
+        }
+        PFEM_TRY(check_kernel("k_dyn_step"));
+    }
+    if (n_rows > 0) {
+        if (n_steps % every == 0) {          // the last step was a sampled one: no later launch writes its row
+            launch(k_dyn_flush, dim3(1), dim3(kBlock), 0, s->stream, nullptr, nullptr, P, D.step, end - n_steps, static_cast<const double *>(D.u[D.step % 3]),
+                   static_cast<const double *>(D.u[(D.step + 2) % 3]));
+            PFEM_TRY(check_kernel("k_dyn_flush"));
+        }
+        PFEM_HIP(hipMemcpyAsync(history, D.d_hist.p, sizeof(double) * static_cast<size_t>(n_rows * ncol), hipMemcpyDeviceToHost, s->stream));
+    }
+    PFEM_HIP(hipStreamSynchronize(s->stream));
+    return PFEM_OK;
+}
+
+// t_n, u_n and v_{n-1/2} = (u_n - u_{n-1}) / dt per owned dof in pfem_solver_get_solution's order (before the first run: the
+// u0 and v0 of pfem_dynamics_set_state); any output may be NULL
+extern "C" int pfem_dynamics_get_state(pfem_solver *s, double *t, int64_t *step, double *u, double *v)
+{
+    if (!s) return PFEM_ERR_ARG;
+    PFEM_TRY(needs_dynamics(s, "pfem_dynamics_get_state"));
+    PFEM_TRY(use_device(s));
+    Dyn &D = *s->dyn;
+    if (t) *t = D.t0 + static_cast<double>(D.step) * D.dt;
+    if (step) *step = D.step;
+    if (u) PFEM_TRY(download_external(s, D.u[D.step % 3], u, s->n_owned));
+    if (v) {
+        if (!D.started) return download_external(s, D.d_v0.p, v, s->n_owned);
+        DevBuf<double> dv;
+        PFEM_TRY(dv.alloc(static_cast<size_t>(std::max<int64_t>(D.n, 1))));
+        launch(k_dyn_velocity, dim3(grid_for(D.n)), dim3(kBlock), 0, s->stream, nullptr, nullptr, D.n, D.dt, static_cast<const double *>(D.u[D.step % 3]),
+               static_cast<const double *>(D.u[(D.step + 2) % 3]), dv.p);
+        PFEM_TRY(check_kernel("k_dyn_velocity"));
+        PFEM_TRY(download_external(s, dv.p, v, s->n_owned));
+    }
+    return PFEM_OK;
+}
+
+// time of one step in microseconds, measured inside graph replays: `graphs` replays of kDynGraphSteps steps between two events,
+// after one replay to warm up (tools/lab/dynamics_measure.py).  The state advances like a run of as many steps without history.
+extern "C" int pfem_dynamics_bench(pfem_solver *s, double dt, int graphs, double *us_per_step, int *steps_per_graph)
+{
+    if (!s || graphs < 1 || !us_per_step) return PFEM_ERR_ARG;
+    PFEM_TRY(needs_dynamics(s, "pfem_dynamics_bench"));
+    Dyn &D = *s->dyn;
+    const long long rem = (kDynGraphSteps - D.step % kDynGraphSteps) % kDynGraphSteps;
+    PFEM_TRY(pfem_dynamics_run(s, dt, rem + kDynGraphSteps, 0.0, 0, nullptr, nullptr));          // align, capture, warm up
+    if (!D.graph.exec[0] || D.graph.off) {
+        set_last_error("pfem_dynamics_bench: the step loop could not be captured on this stream");
+        return PFEM_ERR_STATE;
+    }
+    PFEM_HIP(hipEventRecord(s->ev0, s->stream));
+    for (int g = 0; g < graphs; ++g) PFEM_HIP(hipGraphLaunch(D.graph.exec[0], s->stream));
+    PFEM_HIP(hipEventRecord(s->ev1, s->stream));
+    D.step += static_cast<long long>(graphs) * kDynGraphSteps;
+    double ms = 0.0;
+    PFEM_TRY(elapsed(s, &ms));
+    *us_per_step = 1e3 * ms / (static_cast<double>(graphs) * kDynGraphSteps);
+    if (steps_per_graph) *steps_per_graph = kDynGraphSteps;
+    return PFEM_OK;
+}

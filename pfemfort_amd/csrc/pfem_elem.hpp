@@ -718,6 +718,52 @@ PFEM_HD bool elem_recovery_error(int kind, const double *x, const double *y, con
 }
 
 // ---------------------------------------------------------------------------
+// Lumped mass (pfem_elem_lumped_mass / pfem_dynamics_setup): MassMatrixLinearTria / MassMatrixLinearTetra
+// [elementutilitieselasticity2D.F:283-362, elementutilitieselasticity3D.F:401-482] -- the row sums of the consistent mass
+// at the one Gauss point, Mn[a] for local node a (the same for each of the node's dofs):
+//     b4 = (dens * dvol) * N(a);   Mn[a] = sum over j ascending of b4 * N(j),  from 0.0
+// the reference's loop with the structural zeros of its (nsize x nsize) Klocal left out (x + 0.0 == x).  dvol and N are those of
+// the kind's stiffness routine: the tet's N = 1/4 each, the triangle's REAL(4) Gauss point (tria_shape_gp), thickness in the
+// triangle's dvol.  Density is an argument: the reference reads elemData(3), which is `thick` in the stiffness routines.
+// The tet routine's nGP = 8 over one initialised point is the stiffness routine's defect (DESIGN.md "deviations"): one point.
+// false: a negative Jacobian (not tested for the inline triangle, which has no orientation test).
+// ---------------------------------------------------------------------------
+PFEM_HD bool elem_lumped_mass(int kind, const double *x, const double *y, const double *z, const double *ed, double dens, double *Mn)
+{
+    if (kind == 2 || kind == 3) {
+        TetGeom g;
+        tet_geometry(x, y, z, g);
+        if (g.jac < 0.0) return false;
+        const double dvol = kGaussWtTet * g.jac;
+        const double N[4] = {0.25, 0.25, 1.0 - 0.25 - 0.25 - 0.25, 0.25};
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            const double b4 = (dens * dvol) * N[a];
+            double fact = 0.0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) fact = fact + b4 * N[j];
+            Mn[a] = fact;
+        }
+        return true;
+    }
+    TriaGeom g;
+    tria_geometry(x, y, g);
+    if (kind != 4 && g.jac < 0.0) return false;
+    const double dvol = kind == 5 ? 0.5 * (g.jac * ed[2]) : 0.5 * g.jac;
+    double N[3];
+    tria_shape_gp(N);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const double b4 = (dens * dvol) * N[a];
+        double fact = 0.0;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) fact = fact + b4 * N[j];
+        Mn[a] = fact;
+    }
+    return true;
+}
+
+// ---------------------------------------------------------------------------
 // Sides of an element and the loads on them (pfem_face_load / pfem_surface_geometry / pfem_rhs_add_surface_load)
 // ---------------------------------------------------------------------------
 // Side f of an element is the face (tet) or edge (triangle) OPPOSITE local node f; its nodes are the element's other local

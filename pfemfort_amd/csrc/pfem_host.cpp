@@ -122,6 +122,23 @@ extern "C" int pfem_elem_recovery_error(int kind, const double *xNode, const dou
     return PFEM_OK;
 }
 
+// Lumped mass of one element (pfem_elem.hpp: elem_lumped_mass), one entry per element dof: the node's value at each of its dofs.
+// elemData is read for the thickness of PFEM_ELAST_TRIA only.
+extern "C" int pfem_elem_lumped_mass(int kind, const double *xNode, const double *yNode, const double *zNode, const double *elemData,
+                                     double density, double *Mlocal)
+{
+    if (!kind_valid(kind) || !xNode || !yNode || !Mlocal) return PFEM_ERR_ARG;
+    if (kind_ndim(kind) == 3 && !zNode) return PFEM_ERR_ARG;
+    if (kind == PFEM_ELAST_TRIA && !elemData) return PFEM_ERR_ARG;
+    if (!(density > 0.0)) return PFEM_ERR_ARG;
+    double Mn[4];
+    if (!elem_lumped_mass(kind, xNode, yNode, zNode, elemData, density, Mn)) return PFEM_ERR_NEG_JAC;
+    const int npe = kind_npelem(kind), ndof = kind_ndof(kind);
+    for (int a = 0; a < npe; ++a)
+        for (int d = 0; d < ndof; ++d) Mlocal[a * ndof + d] = Mn[a];
+    return PFEM_OK;
+}
+
 // One side of one element (pfem_elem.hpp: side_geometry / side_load): measure, outward unit normal and the consistent nodal
 // load of the side's nodal values, F[nsize] with zeros at the dofs of the opposite node.  F == NULL: geometry only (load and
 // values are not looked at).

@@ -249,6 +249,112 @@ def run_parallel(kind, mesh: H.Mesh, elem_proc_id, node_proc_id, dist, torch, el
     return _finish(kind, mesh, dm, solver, its, reason, rnorm, timers, u, elemData)
 
 
+@dataclass
+class ExplicitResult:
+    kind: int
+    mesh: H.Mesh
+    dm: H.DofMap
+    solver: PetscSolver
+    t: float                         # time reached
+    dt: float
+    soln_free: np.ndarray            # u(t) by free dof (NEW numbering)
+    velo_free: np.ndarray            # v at t - dt/2
+    solnVTK: np.ndarray              # (nNode, ndof) by OLD node id, Dirichlet values filled in
+    history: np.ndarray              # rows [t, T, S, W, u at the probes, v at the probes] (PetscSolver.dynamicsRun)
+    total_mass: float
+    stable_dt: float
+    timers: dict = field(default_factory=dict)
+
+
+def _run_explicit(kind, mesh, elemData, density, dt, n_steps, load_curve, alpha, sample_every, probes, u0, v0, elem_mat, surface_loads,
+                  check_dt):
+    """The explicit PROGRAMs on one rank: the set-up of ``_run(mode="batched")`` up to the assembled K and load, the lumped
+    mass, then the central-difference loop on the device in place of the solve."""
+    elemData, elem_mat = _materials(mesh, elemData, elem_mat)
+    dm, conn_new, xyz_new, edof = _setup(kind, mesh)
+    N = dm.size_global
+    ndof = L.NDOF[kind]
+    timers = {}
+    solver = PetscSolver()
+    solver.initialise(N, N, np.full(N, min(50, N), np.int32), np.full(N, min(25, N), np.int32))
+    solver.uploadMesh(kind, conn_new, xyz_new, edof, dm.solnApplied)
+    if elem_mat is not None:
+        solver.setMaterials(elem_mat, n_mat=elemData.shape[0], stride=elemData.shape[1])
+    solver.buildPattern()
+    t0 = time.perf_counter()
+    solver.assemble(elemData, H.TIMEDATA)
+    if mesh.force_node is not None and ndof > 1:
+        solver.addNodalForces(dm.NodeDofArrayNew[dm.node_map_get_new[mesh.force_node], mesh.force_dof], mesh.force_val)
+    for sl in surface_loads or ():
+        solver.addSurfaceLoad(sl["elem"], sl["side"], sl["load"], sl["values"], sl.get("layout"), elemData)
+    total_mass = solver.dynamicsSetup(elemData, density)                  # MassMatrixLinear* loop (triaelasticityexplicit.F:883-922)
+    timers["assembly_s"] = time.perf_counter() - t0
+    stable = solver.stableDt()
+    if check_dt and dt > stable:
+        raise ValueError(f"dt = {dt:g} is above the stable step {stable:g} of this mesh and material (pass a smaller dt)")
+    if load_curve is not None:
+        solver.setLoadCurve(*load_curve)
+    if probes is not None:                                               # (node, dof) pairs by the mesh's node ids
+        pr = np.asarray(probes, dtype=np.int64).reshape(-1, 2)
+        g = dm.NodeDofArrayNew[dm.node_map_get_new[pr[:, 0]], pr[:, 1]]
+        if (g < 0).any():
+            raise ValueError("a probe sits on a constrained dof")
+        solver.setProbes(g)
+    solver.setDynamicsState(0.0, u0, v0)                                  # disp = velo = 0 (:951-953)
+    t0 = time.perf_counter()
+    hist = solver.dynamicsRun(dt, n_steps, alpha, sample_every)           # the time loop (:970 ff.)
+    timers["run_s"] = time.perf_counter() - t0
+    t, u, v = solver.dynamicsState()
+    r = _finish(kind, mesh, dm, solver, 0, 0, 0.0, timers, u, elemData, elem_mat)
+    return ExplicitResult(kind, mesh, dm, solver, t, dt, u, v, r.solnVTK, hist, total_mass, stable, timers)
+
+
+_EXPLICIT_NOTE = """
+    The internal force is this library's ``K u`` -- the product of the assembled stiffness, consistent with the pinned
+    element matrices and with ``PetscSolver.nodalForces`` -- and the mass is ``MassMatrixLinear*`` lumped (``density`` an
+    argument of its own).  The reference's ``Residual*`` routines are NOT reproduced: they differ from the reference's own
+    stiffness routines (tensor shear strains against a ``G`` modulus, a plane-strain ``D`` in the triangle, ``dens`` read
+    from the thickness slot), so no golden fixture of these PROGRAMs is taken.  ``load_curve=(t, lam)`` scales the whole
+    assembled load (the Dirichlet lift included); ``alpha`` is mass-proportional damping; ``probes`` are ``(node, dof)``
+    pairs; ``history`` has a row every ``sample_every`` steps.  ``dt`` above ``PetscSolver.stableDt()`` is a ``ValueError``
+    unless ``check_dt=False``.  One rank, ``mode="batched"`` only."""
+
+
+def tetraelasticityexplicit(mesh: H.Mesh | str, dt=0.01, n_steps=100, elemData=None, density=7800.0, load_curve=None, alpha=0.0,
+                            sample_every=0, probes=None, u0=None, v0=None, elem_mat=None, surface_loads=None,
+                            check_dt=True) -> ExplicitResult:
+    """PROGRAM of tetraelasticityexplicit.F on one rank: central differences on a lumped mass, E = 207e9, nu = 0.3, density
+    7800, no body force, dt = 0.01 and stepsMax = 100 steps as the PROGRAM sets them (:910-934: its loop runs while
+    ``stepsCompleted < stepsMax .OR. timeNow < 10 dt``; its dt is far above the stable step of any steel mesh of metre size:
+    give your own)."""
+    if isinstance(mesh, str):
+        mesh = H.read_mesh(mesh)
+    ed = np.array([207.0e9, H._f32(0.3), 1.0, 0.0, 0.0, 0.0]) if elemData is None else elemData
+    return _run_explicit(L.ELAST_TET, mesh, ed, density, dt, n_steps, load_curve, alpha, sample_every, probes, u0, v0, elem_mat,
+                         surface_loads, check_dt)
+
+
+def triaelasticityexplicit(mesh: H.Mesh | str, dt=0.0002, n_steps=50000, elemData=None, density=10.0, load_curve="reference", alpha=0.0,
+                           sample_every=0, probes=None, u0=None, v0=None, elem_mat=None, surface_loads=None,
+                           check_dt=True) -> ExplicitResult:
+    """PROGRAM of triaelasticityexplicit.F on one rank: E = 200, nu = 0.3, density 10, unit thickness, body force (1, 0) while
+    t <= 0.1 (:872-876, :974-977), dt = 2e-4, 50 000 steps (:958-962).  ``load_curve="reference"`` is that switch as a curve:
+    lambda = 1 up to t = 0.1, 0 from the next step on."""
+    if isinstance(mesh, str):
+        mesh = H.read_mesh(mesh)
+    ed = np.array([200.0, H._f32(0.3), 1.0, 1.0, 0.0]) if elemData is None else elemData
+    if isinstance(load_curve, str):
+        if load_curve != "reference":
+            raise ValueError(load_curve)
+        load_curve = ([0.1, 0.1 + 0.5 * dt], [1.0, 0.0])
+    return _run_explicit(L.ELAST_TRIA, mesh, ed, density, dt, n_steps, load_curve, alpha, sample_every, probes, u0, v0, elem_mat,
+                         surface_loads, check_dt)
+
+
+tetraelasticityexplicit.__doc__ += _EXPLICIT_NOTE
+triaelasticityexplicit.__doc__ += _EXPLICIT_NOTE
+
+
 def tetrapoissonparallelimpl1(mesh: H.Mesh | str, mode="batched", rtol=1e-5, maxits=10000, verbose=False, pc=None, elem_mat=None,
                               elemData=None, surface_loads=None) -> Result:
     """PROGRAM TetraMeshPoissonEquation (tetrapoissonparallelimpl1.F) on one rank / one GPU.  ``elemData``: another vector than

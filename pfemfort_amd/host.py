@@ -269,6 +269,18 @@ def ElementPost(kind, xNode, yNode, zNode, elemData, valC):
     return grad, flux, sc.value, fint
 
 
+def MassMatrixLinear(kind, xNode, yNode, zNode, elemData, density):
+    """Lumped mass of one element (pfem_elem_lumped_mass; MassMatrixLinearTria / MassMatrixLinearTetra,
+    elementutilitieselasticity2D.F:283, 3D.F:401): the row sums of the consistent mass at the one Gauss point, ``Mlocal[nsize]``.
+    ``density`` is an argument of its own; ``elemData`` gives the thickness of ``ELAST_TRIA`` and may be None otherwise."""
+    M = np.empty(L.NPELEM[kind] * L.NDOF[kind])
+    z = None if zNode is None else _f64(zNode)
+    ed = None if elemData is None else _f64(elemData)
+    L.check(L.lib().pfem_elem_lumped_mass(kind, _p(_f64(xNode)), _p(_f64(yNode)), _p(z), _p(ed), float(density), _p(M)),
+            "pfem_elem_lumped_mass")
+    return M
+
+
 def FaceLoad(kind, xNode, yNode, zNode, side, load=None, values=None, elemData=None):
     """One side of one element (pfem_face_load): side ``f`` is the face / edge opposite local node ``f``.  Returns
     ``(F[nsize], measure, normal[ndim])`` -- the consistent nodal load of ``values`` ((npe-1, ncomp), per side node in ascending

@@ -604,6 +604,84 @@ class PetscSolver:
         L.check(L.lib().pfem_solver_true_residual(self._h, C.byref(r), C.byref(b)), "pfem_solver_true_residual")
         return r.value, b.value
 
+    # ---- explicit dynamics (one rank, batched path; include/pfem_amd.h "explicit dynamics") ------------
+    def dynamicsSetup(self, elemData, density):
+        """Lumped mass on the device from ``density`` (a number, or one per material row while a map is set) and the mesh;
+        ``elemData`` as ``assemble`` takes it (the thickness of ``ELAST_TRIA``).  Needs an assembled matrix.  Returns the total
+        mass.  The state is at rest at ``t = 0`` afterwards."""
+        ed = self._elem_data(elemData)
+        dens = _f64(np.atleast_1d(density)).ravel()
+        mats = self.materials() if self._h and getattr(self, "kind", None) is not None else None
+        want = mats[1] if mats else 1
+        if dens.size != want:
+            raise ValueError(f"density of {dens.size} entries: {want} wanted (one per material row, or one without a map)")
+        tot = C.c_double(0)
+        L.check(L.lib().pfem_dynamics_setup(self._h, _p(ed), _p(dens), C.byref(tot)), "pfem_dynamics_setup")
+        self._n_probe = 0
+        return tot.value
+
+    def dynamicsMass(self):
+        """Lumped mass per free dof, in ``getSolution``'s order."""
+        m = np.empty(self.size_local)
+        L.check(L.lib().pfem_dynamics_get_mass(self._h, _p(m)), "pfem_dynamics_get_mass")
+        return m
+
+    def stableDt(self):
+        """``2 / sqrt(max_i sum_j |K_ij| / m_i)``: never above the critical step of the central-difference scheme."""
+        dt = C.c_double(0)
+        L.check(L.lib().pfem_dynamics_stable_dt(self._h, C.byref(dt)), "pfem_dynamics_stable_dt")
+        return dt.value
+
+    def setDynamicsState(self, t0=0.0, u0=None, v0=None):
+        """``u(t0)``, ``u'(t0)`` per free dof in ``getSolution``'s order (``None``: zeros)."""
+        u = None if u0 is None else _f64(u0).ravel()
+        v = None if v0 is None else _f64(v0).ravel()
+        for a in (u, v):
+            if a is not None and a.size != self.size_local:
+                raise ValueError("state vectors have one entry per free dof")
+        L.check(L.lib().pfem_dynamics_set_state(self._h, float(t0), _p(u), _p(v)), "pfem_dynamics_set_state")
+
+    def setLoadCurve(self, t=None, lam=None):
+        """``lambda(t)`` piecewise linear through ``(t[k], lam[k])``, constant outside; no arguments: ``lambda = 1``.  It scales
+        the assembled right-hand side as a whole, the Dirichlet lift included."""
+        if t is None:
+            L.check(L.lib().pfem_dynamics_set_load_curve(self._h, 0, None, None), "pfem_dynamics_set_load_curve")
+            return
+        tt, ll = _f64(t).ravel(), _f64(lam).ravel()
+        if tt.size != ll.size:
+            raise ValueError("t and lam differ in length")
+        L.check(L.lib().pfem_dynamics_set_load_curve(self._h, tt.size, _p(tt), _p(ll)), "pfem_dynamics_set_load_curve")
+
+    def setProbes(self, global_dof=()):
+        """Free dofs (global ids, as ``addNodalForces`` takes them) whose ``u`` and ``v`` go into the history rows."""
+        g = np.ascontiguousarray(global_dof, dtype=np.int64).ravel()
+        L.check(L.lib().pfem_dynamics_set_probes(self._h, g.size, _p(g)), "pfem_dynamics_set_probes")
+        self._n_probe = g.size
+
+    def dynamicsRun(self, dt, n_steps, alpha=0.0, sample_every=0):
+        """``n_steps`` central-difference steps with damping ``alpha M``.  Returns the history, ``(n_steps // sample_every,
+        4 + 2 n_probe)``: ``[t, T, S, W, u at the probes, v at the probes]`` after every ``sample_every``-th step of this run."""
+        rows = C.c_int64(0)
+        n_rows = n_steps // sample_every if sample_every > 0 else 0
+        hist = np.empty((n_rows, 4 + 2 * getattr(self, "_n_probe", 0)))
+        L.check(L.lib().pfem_dynamics_run(self._h, float(dt), int(n_steps), float(alpha), int(sample_every), _p(hist) if n_rows else None,
+                                          C.byref(rows)), "pfem_dynamics_run")
+        assert rows.value == n_rows
+        return hist
+
+    def dynamicsState(self):
+        """``(t_n, u_n, v_{n-1/2})`` per free dof in ``getSolution``'s order (before the first run: ``u0``, ``v0`` as set)."""
+        t = C.c_double(0); st = C.c_int64(0)
+        u = np.empty(self.size_local); v = np.empty(self.size_local)
+        L.check(L.lib().pfem_dynamics_get_state(self._h, C.byref(t), C.byref(st), _p(u), _p(v)), "pfem_dynamics_get_state")
+        return t.value, u, v
+
+    def benchDynamics(self, dt, graphs=64):
+        """Microseconds per explicit step inside ``graphs`` replays of the captured step graph (``pfem_dynamics_bench``)."""
+        us = C.c_double(0); per = C.c_int(0)
+        L.check(L.lib().pfem_dynamics_bench(self._h, float(dt), int(graphs), C.byref(us), C.byref(per)), "pfem_dynamics_bench")
+        return us.value
+
     def postTimings(self):
         """Kernel milliseconds of the last ``elementFields`` / ``nodalForces`` call (HIP events, host copies excluded)."""
         a = C.c_double(0); b = C.c_double(0)
