@@ -505,8 +505,47 @@ int pfem_dynamics_set_probes(pfem_solver *s, int n, const int64_t *global_dof);
  * history[rows * (4 + 2 n_probe)] is copied back once, after the run; *rows = n_steps / sample_every (history may be NULL when
  * that is 0).  A second run with the same dt continues exactly; another dt needs a new pfem_dynamics_set_state (PFEM_ERR_STATE). */
 int pfem_dynamics_run(pfem_solver *s, double dt, int64_t n_steps, double alpha, int64_t sample_every, double *history, int64_t *rows);
-/* t_n, n, u_n and v_{n-1/2} (before the first run: u0 and v0 as set); any output may be NULL                                   */
+/* t_n, n, u_n and v_{n-1/2} (before the first run: u0 and v0 as set; after pfem_dynamics_run_implicit: v_n, at the integer
+ * step); any output may be NULL                                                                                            */
 int pfem_dynamics_get_state(pfem_solver *s, double *t, int64_t *step, double *u, double *v);
+
+/* ---- implicit time stepping on the lumped mass: Newmark and the theta-method ---- */
+/* Unconditionally stable steps on the same K, f, m, load curve, probes and state as above.  With a lumped
+ * mass every step is ONE solve with a shifted operator,  (K + sigma diag(m)) d = b,  sigma > 0 a scalar of the step size; nothing
+ * is assembled and no matrix value is rewritten.  t_n = t0 + n dt is formed from n.  A row without mass stays put (d = 0).
+ *
+ * PFEM_SCHEME_NEWMARK (p0 = beta > 0, p1 = gamma >= 1/2; M u'' + alpha M u' + K u = lambda f), in increment form:
+ *     ut = u_n + dt v_n + dt^2 (1/2 - beta) a_n,   vt = v_n + dt (1 - gamma) a_n,   sigma = (1 + gamma dt alpha) / (beta dt^2),
+ *     b = lambda(t_{n+1}) f - alpha m vt - K ut,   u_{n+1} = ut + d,   a_{n+1} = d / (beta dt^2),   v_{n+1} = vt + gamma dt a_{n+1},
+ *   started from a_0 = (lambda(t0) f - alpha m v0 - K u0) / m.
+ * PFEM_SCHEME_THETA (p0 = theta in (0, 1], p1 unused; M u' + K u = lambda f; alpha must be 0, the state's v0 is ignored):
+ *     sigma = 1 / (theta dt),   b = [theta lambda(t_{n+1}) + (1 - theta) lambda(t_n)] f - K u_n,   u_{n+1} = u_n + d / theta,
+ *   and the reported v is (u_{n+1} - u_n) / dt.  For a scalar kind the `density` of pfem_dynamics_setup is then rho c.
+ *
+ * The solve: the two-reduction KSPCG iteration of pfem_solver_solve from d = 0 with the solver's rtol, abstol, dtol and maxits
+ * (||z|| relative to ||z_0||).  Its preconditioner is ALWAYS the point Jacobi of the shifted operator, 1 / (K_ii + sigma m_i),
+ * also when the solver's preconditioner is gamg or node-block Jacobi: neither is used or touched.  ||z_0|| <= abstol: zero
+ * iterations, d = 0.  A solve that ends with a negative reason stops the run with PFEM_ERR_DIVERGED: the state stays at the last
+ * completed step, *steps_done (may be NULL) says how many there were, and their rows and iteration counts are returned.
+ * iterations[n_steps] (may be NULL): the CG iterations of every step.
+ *
+ * Rows as pfem_dynamics_run's, [t_{n+1}, T, S, W, u_{n+1} at the probes, v_{n+1} at the probes], with  S = 1/2 u_{n+1} . K u_{n+1},
+ * W = f . u_{n+1}  and  T = 1/2 sum m v_{n+1}^2  (theta-method: 1/2 sum m u_{n+1}^2), summed in a fixed order; a sampled step
+ * costs one product more.  *rows (may be NULL): the rows written.
+ *
+ * The run leaves the solve alone: the solution vector, the solver's inverse diagonal, control block, residual history, last
+ * iteration count / reason / norm, timings and CG graphs are not written; its own vectors are allocated at the first call.
+ * Afterwards pfem_dynamics_get_state returns (t_n, u_n, v_n) -- v AT the step, not the explicit scheme's v_{n-1/2}.  Implicit runs
+ * of one scheme continue from one another, also with another dt or other parameters.  After an explicit run an implicit one
+ * needs a new pfem_dynamics_set_state, and the other way round, and so does a Newmark run after a theta run (PFEM_ERR_STATE).
+ * Preconditions as pfem_dynamics_run: one rank, the batched path, pfem_dynamics_setup after the pattern build (PFEM_ERR_STATE).
+ * PFEM_ERR_ARG, before the device is touched: dt <= 0 or not finite, n_steps < 0, an unknown scheme, parameters out of range.
+ * PFEM_ERR_NOGPU without a device.                                                                                           */
+#define PFEM_SCHEME_NEWMARK 1      /* p0 = beta, p1 = gamma */
+#define PFEM_SCHEME_THETA   2      /* p0 = theta, p1 unused (0) */
+int pfem_dynamics_run_implicit(pfem_solver *s, int scheme, double dt, int64_t n_steps, double p0, double p1, double alpha,
+                               int64_t sample_every, double *history, int64_t *rows,
+                               int32_t *iterations /* n_steps, or NULL */, int64_t *steps_done);
 
 /* ---- inspection / export (device -> host) -------------------------------- */
 /* global dof id of every local row (owned first, then ghosts ascending) */

@@ -173,6 +173,10 @@ int pfem_bench_spmv(pfem_solver *s, int reps, double *ms_per_launch);
  * captured step graph between two HIP events, after a run that aligns the step counter, captures and warms up; undamped, no
  * history.  The state advances by the steps taken.  PFEM_ERR_STATE where the stream cannot be captured.                     */
 int pfem_dynamics_bench(pfem_solver *s, double dt, int graphs, double *us_per_step, int *steps_per_graph);
+/* time of one iteration of pfem_dynamics_run_implicit's shifted CG loop (three launches) in microseconds: `iterations`
+ * iterations of the first step from the state at hand between two HIP events, with no convergence exit (rtol = 0), after one
+ * graph unit to warm up.  The state does not advance.  PFEM_ERR_STATE when the loop ended early (zero load and state).      */
+int pfem_dynamics_bench_implicit(pfem_solver *s, int scheme, double dt, double p0, double p1, int iterations, double *us_per_iteration);
 
 /* Timings of the last calls, measured with HIP events on the solver's stream [ms]. */
 typedef struct pfem_timings {

@@ -23,6 +23,8 @@ INSERT_VALUES, ADD_VALUES = 1, 2
 # loads on a side of an element and the layouts of their values (pfem_face_load / pfem_rhs_add_surface_load)
 LOAD_FLUX, LOAD_TRACTION, LOAD_PRESSURE = 1, 2, 3
 LOAD_UNIFORM, LOAD_PER_FACE, LOAD_PER_FACE_NODE = 0, 1, 2
+# implicit time-stepping schemes (pfem_dynamics_run_implicit)
+SCHEME_NEWMARK, SCHEME_THETA = 1, 2
 
 NPELEM = {POISSON_TRIA: 3, POISSON_TET: 4, ELAST_TET: 4, POISSON_TRIA_INLINE: 3, ELAST_TRIA: 3}
 NDOF = {POISSON_TRIA: 1, POISSON_TET: 1, ELAST_TET: 3, POISSON_TRIA_INLINE: 1, ELAST_TRIA: 2}
@@ -167,6 +169,8 @@ SIGNATURES = {
     "pfem_dynamics_run": [_P, _D, _L, _D, _L, _P, _P],
     "pfem_dynamics_get_state": [_P, _P, _P, _P, _P],
     "pfem_dynamics_bench": [_P, _D, _I, _P, _P],
+    "pfem_dynamics_run_implicit": [_P, _I, _D, _L, _D, _D, _D, _L, _P, _P, _P, _P],
+    "pfem_dynamics_bench_implicit": [_P, _I, _D, _D, _D, _I, _P],
     "pfem_matrix_info": [_P, _P, _P, _P, _P],
     "pfem_get_local_to_global": [_P, _P],
     "pfem_get_csr": [_P, _P, _P, _P],

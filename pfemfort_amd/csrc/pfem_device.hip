@@ -33,6 +33,7 @@
 #include "pfem_valdict.hpp"
 #include "pfem_amg_kernels.hpp"
 #include "pfem_dyn_kernels.hpp"
+#include "pfem_imp_kernels.hpp"
 #include "pfem_peer.hpp"
 
 using namespace pfem;
@@ -498,7 +499,24 @@ struct CommBackend {
 // ---------------------------------------------------------------------------
 // explicit dynamics on a handle (pfem_dynamics_*, pfem_dynamics.inc): lives from pfem_dynamics_setup to the next pattern
 // ---------------------------------------------------------------------------
+// implicit stepping on the same handle (pfem_dynamics_run_implicit, pfem_implicit.inc): its own vectors, control block, partials
+// and graph cache, allocated at the first implicit run
+struct Imp {
+    int64_t n = 0;
+    DevBuf<double> s_u, s_ut, s_p;         // SpMV inputs, guarded like Dyn::d_ustore
+    double *u = nullptr, *ut = nullptr, *p = nullptr;
+    DevBuf<double> v, a, vt, d, r, w, dinv, part, part_pw, hist0;
+    DevBuf<CgCtl> ctl;
+    CgGraph graph;                         // kImpGraphIters iterations: 3 launches each, one stream
+    double t_base = 0.0, dt = 0.0;         // t_n = t_base + n_since dt
+    long long n_since = 0;
+};
+
+enum { kDynFresh = 0, kDynExplicit = 1 };  // Dyn::mode; an implicit run leaves its PFEM_SCHEME_* + 1
+
 struct Dyn {
+    std::unique_ptr<Imp> imp;
+    int mode = kDynFresh;                  // which stepper has advanced the state since pfem_dynamics_set_state
     int64_t n = 0;                         // rows (n_loc of the pattern it was set up on)
     DevBuf<double> d_mnode, d_m, d_minv;   // mass per node (device node order), m and 1 / m per matrix row
     DevBuf<double> d_ustore[3];            // the three displacement buffers, guarded like the SpMV's input vector
@@ -5576,6 +5594,7 @@ extern "C" int pfem_solver_factorise(pfem_solver *s)
 }
 
 #include "pfem_dynamics.inc"
+#include "pfem_implicit.inc"
 
 extern "C" int pfem_solver_solve(pfem_solver *s, int *its, int *reason, double *rnorm)
 {

@@ -211,6 +211,7 @@ extern "C" int pfem_dynamics_set_state(pfem_solver *s, double t0, const double *
     D.step = 0;
     D.dt = 0.0;
     D.started = false;
+    D.mode = kDynFresh;
     return PFEM_OK;
 }
 
@@ -266,6 +267,10 @@ extern "C" int pfem_dynamics_run(pfem_solver *s, double dt, int64_t n_steps, dou
     if (!s || !(dt > 0.0) || !std::isfinite(dt) || n_steps < 0 || !(alpha >= 0.0) || !std::isfinite(alpha) || sample_every < 0) return PFEM_ERR_ARG;
     PFEM_TRY(needs_dynamics(s, "pfem_dynamics_run"));
     Dyn &D = *s->dyn;
+    if (D.mode > kDynExplicit) {
+        set_last_error("pfem_dynamics_run: an explicit run after an implicit one needs a new pfem_dynamics_set_state");
+        return PFEM_ERR_STATE;
+    }
     if (D.started && dt != D.dt) {
         set_last_error("pfem_dynamics_run: another dt than the run before needs a new pfem_dynamics_set_state");
         return PFEM_ERR_STATE;
@@ -282,6 +287,7 @@ extern "C" int pfem_dynamics_run(pfem_solver *s, double dt, int64_t n_steps, dou
     if (n_rows > 0 && !history) return PFEM_ERR_ARG;
     if (n_rows > 0 && D.d_hist.n < static_cast<size_t>(n_rows * ncol)) PFEM_TRY(D.d_hist.alloc(static_cast<size_t>(n_rows * ncol)));
     D.dt = dt;
+    D.mode = kDynExplicit;
     const DynPar P = dyn_par(s, alpha, every);
     // the SpMV's copies of the matrix values, as every product outside a solve brings them up to date
     mark_group_vals(s);
@@ -351,6 +357,14 @@ extern "C" int pfem_dynamics_get_state(pfem_solver *s, double *t, int64_t *step,
     PFEM_TRY(needs_dynamics(s, "pfem_dynamics_get_state"));
     PFEM_TRY(use_device(s));
     Dyn &D = *s->dyn;
+    if (D.mode > kDynExplicit) {          // after an implicit run: (t_n, u_n, v_n), v at the integer step
+        const Imp &I = *D.imp;
+        if (t) *t = I.t_base + static_cast<double>(I.n_since) * I.dt;
+        if (step) *step = D.step;
+        if (u) PFEM_TRY(download_external(s, I.u, u, s->n_owned));
+        if (v) PFEM_TRY(download_external(s, I.v.p, v, s->n_owned));
+        return PFEM_OK;
+    }
     if (t) *t = D.t0 + static_cast<double>(D.step) * D.dt;
     if (step) *step = D.step;
     if (u) PFEM_TRY(download_external(s, D.u[D.step % 3], u, s->n_owned));

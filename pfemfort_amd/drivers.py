@@ -264,12 +264,17 @@ class ExplicitResult:
     total_mass: float
     stable_dt: float
     timers: dict = field(default_factory=dict)
+    iterations: np.ndarray | None = None   # CG iterations of every implicit step; None for central differences
 
 
 def _run_explicit(kind, mesh, elemData, density, dt, n_steps, load_curve, alpha, sample_every, probes, u0, v0, elem_mat, surface_loads,
-                  check_dt):
+                  check_dt, integrator="central", implicit=None, rtol=1e-5, maxits=10000):
     """The explicit PROGRAMs on one rank: the set-up of ``_run(mode="batched")`` up to the assembled K and load, the lumped
-    mass, then the central-difference loop on the device in place of the solve."""
+    mass, then the time loop on the device in place of the solve: central differences, or -- ``integrator`` "newmark" /
+    "theta" with the keywords of ``PetscSolver.implicitRun`` in ``implicit`` -- implicit steps, to which ``check_dt`` does not
+    apply."""
+    if integrator not in ("central", "newmark", "theta"):
+        raise ValueError(f"integrator {integrator!r}: 'central', 'newmark' or 'theta'")
     elemData, elem_mat = _materials(mesh, elemData, elem_mat)
     dm, conn_new, xyz_new, edof = _setup(kind, mesh)
     N = dm.size_global
@@ -290,7 +295,7 @@ def _run_explicit(kind, mesh, elemData, density, dt, n_steps, load_curve, alpha,
     total_mass = solver.dynamicsSetup(elemData, density)                  # MassMatrixLinear* loop (triaelasticityexplicit.F:883-922)
     timers["assembly_s"] = time.perf_counter() - t0
     stable = solver.stableDt()
-    if check_dt and dt > stable:
+    if integrator == "central" and check_dt and dt > stable:
         raise ValueError(f"dt = {dt:g} is above the stable step {stable:g} of this mesh and material (pass a smaller dt)")
     if load_curve is not None:
         solver.setLoadCurve(*load_curve)
@@ -302,11 +307,16 @@ def _run_explicit(kind, mesh, elemData, density, dt, n_steps, load_curve, alpha,
         solver.setProbes(g)
     solver.setDynamicsState(0.0, u0, v0)                                  # disp = velo = 0 (:951-953)
     t0 = time.perf_counter()
-    hist = solver.dynamicsRun(dt, n_steps, alpha, sample_every)           # the time loop (:970 ff.)
+    its = None
+    if integrator == "central":
+        hist = solver.dynamicsRun(dt, n_steps, alpha, sample_every)       # the time loop (:970 ff.)
+    else:
+        solver.setTolerances(rtol=rtol, maxits=maxits)
+        hist, its = solver.implicitRun(dt, n_steps, scheme=integrator, alpha=alpha, sample_every=sample_every, **(implicit or {}))
     timers["run_s"] = time.perf_counter() - t0
     t, u, v = solver.dynamicsState()
     r = _finish(kind, mesh, dm, solver, 0, 0, 0.0, timers, u, elemData, elem_mat)
-    return ExplicitResult(kind, mesh, dm, solver, t, dt, u, v, r.solnVTK, hist, total_mass, stable, timers)
+    return ExplicitResult(kind, mesh, dm, solver, t, dt, u, v, r.solnVTK, hist, total_mass, stable, timers, its)
 
 
 _EXPLICIT_NOTE = """
@@ -317,12 +327,19 @@ _EXPLICIT_NOTE = """
     from the thickness slot), so no golden fixture of these PROGRAMs is taken.  ``load_curve=(t, lam)`` scales the whole
     assembled load (the Dirichlet lift included); ``alpha`` is mass-proportional damping; ``probes`` are ``(node, dof)``
     pairs; ``history`` has a row every ``sample_every`` steps.  ``dt`` above ``PetscSolver.stableDt()`` is a ``ValueError``
-    unless ``check_dt=False``.  One rank, ``mode="batched"`` only."""
+    unless ``check_dt=False``.  One rank, ``mode="batched"`` only.
+
+    ``integrator="central"`` (the default) is the PROGRAM's scheme.  ``integrator="newmark"`` takes the same steps with Newmark
+    (``beta``, ``gamma``; ``PetscSolver.implicitRun``): unconditionally stable for ``gamma >= 1/2``, ``beta >= (gamma + 1/2)^2 / 4``,
+    so ``check_dt`` does not apply and the PROGRAM's own ``dt`` runs; every step is a Jacobi-PCG solve to ``rtol`` within
+    ``maxits`` iterations, ``iterations`` of the result holds their counts (``None`` for central differences) and ``velo_free``
+    is then v at ``t``, not at ``t - dt/2``."""
 
 
 def tetraelasticityexplicit(mesh: H.Mesh | str, dt=0.01, n_steps=100, elemData=None, density=7800.0, load_curve=None, alpha=0.0,
                             sample_every=0, probes=None, u0=None, v0=None, elem_mat=None, surface_loads=None,
-                            check_dt=True) -> ExplicitResult:
+                            check_dt=True, integrator="central", beta=0.25, gamma=0.5,
+                            rtol=1e-5, maxits=10000) -> ExplicitResult:
     """PROGRAM of tetraelasticityexplicit.F on one rank: central differences on a lumped mass, E = 207e9, nu = 0.3, density
     7800, no body force, dt = 0.01 and stepsMax = 100 steps as the PROGRAM sets them (:910-934: its loop runs while
     ``stepsCompleted < stepsMax .OR. timeNow < 10 dt``; its dt is far above the stable step of any steel mesh of metre size:
@@ -331,12 +348,13 @@ def tetraelasticityexplicit(mesh: H.Mesh | str, dt=0.01, n_steps=100, elemData=N
         mesh = H.read_mesh(mesh)
     ed = np.array([207.0e9, H._f32(0.3), 1.0, 0.0, 0.0, 0.0]) if elemData is None else elemData
     return _run_explicit(L.ELAST_TET, mesh, ed, density, dt, n_steps, load_curve, alpha, sample_every, probes, u0, v0, elem_mat,
-                         surface_loads, check_dt)
+                         surface_loads, check_dt, integrator, {"beta": beta, "gamma": gamma} if integrator == "newmark" else None, rtol, maxits)
 
 
 def triaelasticityexplicit(mesh: H.Mesh | str, dt=0.0002, n_steps=50000, elemData=None, density=10.0, load_curve="reference", alpha=0.0,
                            sample_every=0, probes=None, u0=None, v0=None, elem_mat=None, surface_loads=None,
-                           check_dt=True) -> ExplicitResult:
+                           check_dt=True, integrator="central", beta=0.25, gamma=0.5,
+                           rtol=1e-5, maxits=10000) -> ExplicitResult:
     """PROGRAM of triaelasticityexplicit.F on one rank: E = 200, nu = 0.3, density 10, unit thickness, body force (1, 0) while
     t <= 0.1 (:872-876, :974-977), dt = 2e-4, 50 000 steps (:958-962).  ``load_curve="reference"`` is that switch as a curve:
     lambda = 1 up to t = 0.1, 0 from the next step on."""
@@ -348,11 +366,31 @@ def triaelasticityexplicit(mesh: H.Mesh | str, dt=0.0002, n_steps=50000, elemDat
             raise ValueError(load_curve)
         load_curve = ([0.1, 0.1 + 0.5 * dt], [1.0, 0.0])
     return _run_explicit(L.ELAST_TRIA, mesh, ed, density, dt, n_steps, load_curve, alpha, sample_every, probes, u0, v0, elem_mat,
-                         surface_loads, check_dt)
+                         surface_loads, check_dt, integrator, {"beta": beta, "gamma": gamma} if integrator == "newmark" else None, rtol, maxits)
 
 
 tetraelasticityexplicit.__doc__ += _EXPLICIT_NOTE
 triaelasticityexplicit.__doc__ += _EXPLICIT_NOTE
+
+
+def poissontransient(mesh: H.Mesh | str, dt, n_steps, theta=1.0, capacity=1.0, u0=None, elemData=None, load_curve=None, sample_every=0,
+                     probes=None, elem_mat=None, surface_loads=None, rtol=1e-5, maxits=10000) -> ExplicitResult:
+    """Transient heat conduction ``capacity u' + K u = lambda(t) f`` on a triangle or tet Poisson mesh by the theta-method
+    (``PetscSolver.implicitRun(scheme="theta")``; ``theta = 1`` backward Euler, ``1/2`` Crank-Nicolson) on the lumped capacity:
+    K and f are those of ``triapoissonparallelimpl1`` / ``tetrapoissonparallelimpl1`` (the Dirichlet lift in f), ``capacity`` is
+    rho c -- a number, or one per material row with ``elem_mat`` --, ``u0`` the initial field by free dof (zeros).  Not part of
+    the reference, which has no diffusion stepper.  ``elem_mat`` / ``surface_loads`` / ``probes`` / ``load_curve`` /
+    ``sample_every`` as the explicit drivers take them; every step is a Jacobi-PCG solve to ``rtol``.  Returns an
+    ``ExplicitResult``: ``velo_free`` is ``(u_n - u_{n-1}) / dt``, the T column of ``history`` is ``1/2 sum m u^2``."""
+    if isinstance(mesh, str):
+        mesh = H.read_mesh(mesh)
+    npe = mesh.conn.shape[0]
+    if npe not in (3, 4):
+        raise ValueError("poissontransient takes triangle and tet meshes")
+    kind = L.POISSON_TET if npe == 4 else L.POISSON_TRIA
+    ed = (H.POISSON_ELEMDATA if npe == 4 else np.array([1.0, 1.0])) if elemData is None else elemData
+    return _run_explicit(kind, mesh, ed, capacity, dt, n_steps, load_curve, 0.0, sample_every, probes, u0, None, elem_mat, surface_loads,
+                         False, "theta", {"theta": theta}, rtol, maxits)
 
 
 def tetrapoissonparallelimpl1(mesh: H.Mesh | str, mode="batched", rtol=1e-5, maxits=10000, verbose=False, pc=None, elem_mat=None,

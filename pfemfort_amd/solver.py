@@ -682,6 +682,46 @@ class PetscSolver:
         L.check(L.lib().pfem_dynamics_bench(self._h, float(dt), int(graphs), C.byref(us), C.byref(per)), "pfem_dynamics_bench")
         return us.value
 
+    def implicitRun(self, dt, n_steps, scheme="newmark", beta=0.25, gamma=0.5, theta=None, alpha=0.0, sample_every=0):
+        """``n_steps`` implicit steps on the lumped mass (``pfem_dynamics_run_implicit``): ``scheme="newmark"`` with ``beta``,
+        ``gamma`` and damping ``alpha M``, or ``scheme="theta"`` (first order in time; ``theta`` in (0, 1], default 1: backward
+        Euler; ``alpha`` must be 0).  Every step is one Jacobi-PCG solve of ``(K + sigma diag(m)) d = b`` from ``d = 0`` with the
+        tolerances of ``setTolerances``; the preconditioner is always the point Jacobi of the shifted operator, also when the
+        solver's is gamg or node-block Jacobi, which are neither used nor touched.  Returns ``(history, iterations)``: the rows
+        ``[t, T, S, W, u at the probes, v at the probes]`` of every ``sample_every``-th step and the CG iterations of every
+        step.  ``dynamicsState`` afterwards gives ``(t_n, u_n, v_n)``, v at the integer step.  A step whose solve diverges
+        raises ``PfemError`` (``ERR_DIVERGED``) with ``steps_done``, ``history`` and ``iterations`` of the completed steps
+        as attributes; the state is that of the last completed step."""
+        if scheme == "newmark":
+            code, p0, p1 = L.SCHEME_NEWMARK, float(beta), float(gamma)
+        elif scheme == "theta":
+            code, p0, p1 = L.SCHEME_THETA, 1.0 if theta is None else float(theta), 0.0
+        else:
+            raise ValueError(f"scheme {scheme!r}: 'newmark' or 'theta'")
+        n_steps = int(n_steps)
+        rows = C.c_int64(0); done = C.c_int64(0)
+        n_rows = n_steps // sample_every if sample_every > 0 and n_steps > 0 else 0
+        hist = np.empty((n_rows, 4 + 2 * getattr(self, "_n_probe", 0)))
+        its = np.zeros(max(n_steps, 0), np.int32)
+        rc = L.lib().pfem_dynamics_run_implicit(self._h, code, float(dt), n_steps, p0, p1, float(alpha), int(sample_every),
+                                                _p(hist) if n_rows else None, C.byref(rows), _p(its) if n_steps > 0 else None, C.byref(done))
+        if rc == L.ERR_DIVERGED:
+            e = L.PfemError(rc, "pfem_dynamics_run_implicit", L.lib().pfem_last_error_string().decode())
+            e.steps_done, e.history, e.iterations = done.value, hist[:rows.value], its[:done.value]
+            raise e
+        L.check(rc, "pfem_dynamics_run_implicit")
+        assert rows.value == n_rows and done.value == n_steps
+        return hist, its
+
+    def benchImplicit(self, dt, iterations=200, scheme="newmark", beta=0.25, gamma=0.5, theta=1.0):
+        """Microseconds per iteration of the shifted CG loop of ``implicitRun``, ``iterations`` of them between two events with
+        no convergence exit (``pfem_dynamics_bench_implicit``).  The state does not advance."""
+        code, p0, p1 = (L.SCHEME_NEWMARK, beta, gamma) if scheme == "newmark" else (L.SCHEME_THETA, theta, 0.0)
+        us = C.c_double(0)
+        L.check(L.lib().pfem_dynamics_bench_implicit(self._h, code, float(dt), float(p0), float(p1), int(iterations), C.byref(us)),
+                "pfem_dynamics_bench_implicit")
+        return us.value
+
     def postTimings(self):
         """Kernel milliseconds of the last ``elementFields`` / ``nodalForces`` call (HIP events, host copies excluded)."""
         a = C.c_double(0); b = C.c_double(0)
