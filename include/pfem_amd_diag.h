@@ -125,6 +125,12 @@ int pfem_solver_amg_level0_epilogue(pfem_solver *s, int *taken);
  * numeric phase took from the Galerkin product that formed them instead of k_amg_max_rows / k_amg_max (0 in a pattern's first
  * solve, whose products run in the symbolic phase)                                                                       */
 int pfem_solver_amg_tail_from(pfem_solver *s, int *tail_from, int *tail_build, int *bounds_by_products);
+/* the side chain of the last gamg solve's numeric phase: *used = 1 when the products that form the levels from *first_level on and
+ * the dense inverse ran on a stream of their own beside the first cycle's upper levels (one rank, plain transfers, fused kernels, a
+ * warm step of at least two levels one of which lies below every level that takes the value dictionary; PFEM_AMG_SIDE_STREAM not 0),
+ * and *ms = that chain's span on its stream (pfem_solver_amg_info's numeric_ms then covers the solver's own stream only); 0, 0, 0
+ * when everything ran on the solver's stream (always so in a pattern's first solve).  Same bits either way.                    */
+int pfem_solver_amg_side_stream(pfem_solver *s, int *used, int *first_level, double *ms);
 /* 1 when the numeric phase of the last gamg solve formed level 1 from the SpMV's 16-bit value codes (one rank, a scalar brick
  * level 0 whose 4-row relative-group form streams codes that hold the current values; PFEM_AMG_GALERKIN_CODES not 0); 0 when it
  * read the fp64 row form (the first step of a pattern forms the level in the symbolic phase: 0 as well).  Same bits either way. */

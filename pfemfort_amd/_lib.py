@@ -141,6 +141,7 @@ SIGNATURES = {
     "pfem_solver_amg_cycle": [_P, _P, _P],
     "pfem_solver_amg_level0_epilogue": [_P, _P],
     "pfem_solver_amg_tail_from": [_P, _P, _P, _P],
+    "pfem_solver_amg_side_stream": [_P, _P, _P, _P],
     "pfem_solver_amg_galerkin_from_codes": [_P, _P],
     "pfem_solver_amg_level_values": [_P, _I, _L, _P, _P],
     "pfem_solver_amg_column_codes": [_P, _I, _P, _P, _P],

@@ -773,8 +773,9 @@ inline bool amg_galerkin_by_entry()
 // `from_codes` (level 0, amg_level0_codes said yes): the values are read as the SpMV's 16-bit codes instead of the row form's doubles
 // `bound` (with extras; a word some kernel before this one has zeroed): the product also leaves the maximum of the ratios there --
 // C's Gershgorin bound, C.bound_done -- and zeroes `zero` for the product after it.  Returns whether it did.
-inline bool amg_galerkin(pfem_solver *s, const AmgLevel &L, AmgLevel &C, const SellDev &A, bool extras = false, VdState *vstate = nullptr,
-                         bool from_codes = false, double *bound = nullptr, double *zero = nullptr)
+// `st`: the stream the product goes to (amg_galerkin: the solver's own)
+inline bool amg_galerkin_on(hipStream_t st, pfem_solver *s, const AmgLevel &L, AmgLevel &C, const SellDev &A, bool extras = false, VdState *vstate = nullptr,
+                            bool from_codes = false, double *bound = nullptr, double *zero = nullptr)
 {
     C.bound_fresh = C.vd_direct = C.bound_done = false;
     if (L.code_of.p && !amg_galerkin_by_entry()) {
@@ -787,7 +788,7 @@ inline bool amg_galerkin(pfem_solver *s, const AmgLevel &L, AmgLevel &C, const S
             if (bound) { X.bound = bound; X.zero = zero; C.bound_done = true; }
             if (vstate && C.vd_have_dict && C.vd_hash_ok && C.vhash.p && C.vcodes.p && C.vcodes.n >= static_cast<size_t>(C.stored) && !C.vd_refused) {
                 const VdState reset{C.vd_n, 0, 0, 0};
-                (void)hipMemcpyAsync(vstate, &reset, sizeof reset, hipMemcpyHostToDevice, s->stream);
+                (void)hipMemcpyAsync(vstate, &reset, sizeof reset, hipMemcpyHostToDevice, st);
                 X.vhash = C.vhash.p;
                 X.codes = C.vcodes.p;
                 X.vstate = vstate;
@@ -796,22 +797,27 @@ inline bool amg_galerkin(pfem_solver *s, const AmgLevel &L, AmgLevel &C, const S
         }
         if (from_codes) {
             hipLaunchKernelGGL(k_lat_galerkin_codes, dim3(static_cast<unsigned>((C.n_loc + kLatGalThreads - 1) / kLatGalThreads)), dim3(kLatGalThreads),
-                               sizeof(double) * static_cast<size_t>(std::max(s->vd_n, 1)), s->stream, C.n_loc, static_cast<const int32_t *>(L.mem_ptr.p),
+                               sizeof(double) * static_cast<size_t>(std::max(s->vd_n, 1)), st, C.n_loc, static_cast<const int32_t *>(L.mem_ptr.p),
                                static_cast<const int32_t *>(L.mem_idx.p), static_cast<const int64_t *>(s->d_rslice_off.p),
                                static_cast<const unsigned long long *>(s->d_vcodes.p), static_cast<const uint32_t *>(L.glat.p),
                                static_cast<const double *>(s->d_vdict.p), s->vd_n, static_cast<const uint32_t *>(L.code_mask.p),
                                static_cast<const int64_t *>(C.slice_off.p), C.vals.p, X);
             return C.bound_done;
         }
-        hipLaunchKernelGGL(k_lat_galerkin, dim3(static_cast<unsigned>((C.n_loc + kLatGalThreads - 1) / kLatGalThreads)), dim3(kLatGalThreads), 0, s->stream, A, C.n_loc,
+        hipLaunchKernelGGL(k_lat_galerkin, dim3(static_cast<unsigned>((C.n_loc + kLatGalThreads - 1) / kLatGalThreads)), dim3(kLatGalThreads), 0, st, A, C.n_loc,
                            static_cast<const int32_t *>(L.mem_ptr.p), static_cast<const int32_t *>(L.mem_idx.p), static_cast<const uint8_t *>(L.code_of.p),
                            static_cast<const uint32_t *>(L.code_mask.p), static_cast<const int64_t *>(C.slice_off.p), C.vals.p, X);
         return C.bound_done;
     }
-    hipLaunchKernelGGL(k_amg_galerkin, dim3(grid_for(L.nnz_c)), dim3(kBlock), 0, s->stream, L.nnz_c, static_cast<const int64_t *>(L.src_ptr.p),
+    hipLaunchKernelGGL(k_amg_galerkin, dim3(grid_for(L.nnz_c)), dim3(kBlock), 0, st, L.nnz_c, static_cast<const int64_t *>(L.src_ptr.p),
                        static_cast<const int32_t *>(L.src_slot.p), static_cast<const int64_t *>(L.dst_slot.p),
                        static_cast<const double *>(A.vals), C.vals.p);
     return false;
+}
+inline bool amg_galerkin(pfem_solver *s, const AmgLevel &L, AmgLevel &C, const SellDev &A, bool extras = false, VdState *vstate = nullptr,
+                         bool from_codes = false, double *bound = nullptr, double *zero = nullptr)
+{
+    return amg_galerkin_on(s->stream, s, L, C, A, extras, vstate, from_codes, bound, zero);
 }
 
 // Coupled hierarchy, one level (collective): the ghosts of level L learn their aggregates from the owners; the coarse
@@ -2939,19 +2945,23 @@ void amg_column_codes_verdict(Amg &M, int l, const CcState &v)
                      L.cc_ok ? "" : (v.mismatch ? " -- the check failed, the level keeps its int32 columns" : " -- the level keeps its int32 columns"));
 }
 
+// Is level l (1 .. last - 1) a candidate for the value dictionary in this solve?  Known before the numeric phase enqueues anything.
+// (a hierarchy across ranks, round 6: its distributed levels too -- k_amg_spmv_pack_vd; every rank has its own dictionaries
+// and its own verdicts: the product is the same product either way, and no collective depends on which kernel ran)
+inline bool amg_vd_candidate(const Amg &M, int l)
+{
+    const AmgLevel &L = *M.lev[static_cast<size_t>(l)];
+    return valdict_enabled() && (M.coupled || (M.fused && M.cheb_degree == 2)) && !L.fine && L.bs == 1 && !L.gptr.p && L.stored >= kAmgVdMinSlots &&
+           !L.vd_refused && (M.tail_from < 0 || l < M.tail_from);
+}
+
 int amg_value_codes(pfem_solver *s, Amg &M)
 {
-    const bool enabled = valdict_enabled();
     const int nl = static_cast<int>(M.lev.size());
     std::vector<int> cand;
     for (int l = 1; l + 1 < nl; ++l) {
-        AmgLevel &L = *M.lev[static_cast<size_t>(l)];
-        // (a hierarchy across ranks, round 6: its distributed levels too -- k_amg_spmv_pack_vd; every rank has its own dictionaries
-        // and its own verdicts: the product is the same product either way, and no collective depends on which kernel ran)
-        const bool takes = enabled && (M.coupled || (M.fused && M.cheb_degree == 2)) && !L.fine && L.bs == 1 && !L.gptr.p && L.stored >= kAmgVdMinSlots &&
-                           !L.vd_refused && (M.tail_from < 0 || l < M.tail_from);
-        if (takes) cand.push_back(l);
-        else L.vd_ok = false;
+        if (amg_vd_candidate(M, l)) cand.push_back(l);
+        else M.lev[static_cast<size_t>(l)]->vd_ok = false;
     }
     if (cand.empty()) return PFEM_OK;
     if (M.vd_states.n < static_cast<size_t>(nl)) PFEM_TRY(M.vd_states.alloc(static_cast<size_t>(nl)));
@@ -3092,9 +3102,41 @@ int amg_numeric(pfem_solver *s, Amg &M, bool overlap)
     const bool own_bounds = M.fused && !M.rbm && !fresh && M.lev.size() > 1;
     size_t zeroed = 0;
     M.bounds_by_products = 0;
+    // The tail of this chain on a stream of its own (one rank, the conditions of own_bounds; PFEM_AMG_SIDE_STREAM=0: off).  The
+    // products from a few thousand rows down and the dense inverse are latency chains of a few workgroups each; the first cycle's
+    // upper levels, which stream the large matrices, need nothing of what they write.  side_from = the first level no kernel form of
+    // which is decided by a verdict (amg_value_codes: no dictionary, no column codes from there on), at least 2 -- level 1 is what the
+    // cycle wants first, and the product that forms it fills the chip.  From the product that forms level side_from on, everything
+    // here goes to M.side_stream, forked off the solver's stream behind the product that formed level side_from - 1: the chain in
+    // which each product zeroes the next level's lam stays on one stream from there.  amg_apply waits for ev_side1 in front of the
+    // first kernel that touches such a level; run_pcg_amg makes sure no return leaves the chain unjoined.
+    M.side_used = false;
+    M.side_first = 0;
+    size_t side_from = 0;
+    if (own_bounds && M.side_on && &M == s->amg.get() && !cg_multi(s)) {
+        size_t k = 2;
+        for (size_t l = 1; l + 1 < M.lev.size(); ++l)
+            if (amg_vd_candidate(M, static_cast<int>(l))) k = l + 1;
+        if (k < M.lev.size()) side_from = k;
+    }
+    // where the kernels that write level l go
+    auto stream_of = [&](size_t l) { return M.side_used && l >= side_from ? M.side_stream : s->stream; };
+    auto fork = [&]() -> int {
+        if (!M.side_stream) PFEM_HIP(hipStreamCreateWithFlags(&M.side_stream, hipStreamNonBlocking));
+        if (!M.ev_fork) PFEM_HIP(hipEventCreateWithFlags(&M.ev_fork, hipEventDisableTiming));
+        if (!M.ev_side0) PFEM_HIP(hipEventCreate(&M.ev_side0));
+        if (!M.ev_side1) PFEM_HIP(hipEventCreate(&M.ev_side1));
+        PFEM_HIP(hipEventRecord(M.ev_fork, s->stream));
+        PFEM_HIP(hipStreamWaitEvent(M.side_stream, M.ev_fork, 0));
+        PFEM_HIP(hipEventRecord(M.ev_side0, M.side_stream));
+        M.side_used = M.side_pending = true;
+        M.side_first = static_cast<int>(side_from);
+        return PFEM_OK;
+    };
     // level l's bound from its stored matrix, or from what the assembly (level 0) / the Galerkin product left in L.t
     auto level_bound = [&](size_t l, double *zero) -> int {
         AmgLevel &L = *M.lev[l];
+        const hipStream_t st = stream_of(l);
         const SellDev A = amg_sell(s, L);
         const unsigned g = grid_for(A.n_slices * 64);
         if (!L.fine && L.bound_fresh && !fresh) {
@@ -3103,10 +3145,10 @@ int amg_numeric(pfem_solver *s, Amg &M, bool overlap)
             if (L.bound_done) { ++M.bounds_by_products; return PFEM_OK; }          // ... and their maximum in L.lam
             if (L.n > 65536) {
                 const unsigned gm = std::min<unsigned>(g, 512u);
-                hipLaunchKernelGGL(k_amg_max_rows, dim3(gm), dim3(kBlock), 0, s->stream, static_cast<const double *>(L.t.p), L.n, L.part_max.p);
-                hipLaunchKernelGGL(k_amg_max, dim3(1), dim3(1024), 0, s->stream, static_cast<const double *>(L.part_max.p), static_cast<int64_t>(gm), L.lam.p, zero);
+                hipLaunchKernelGGL(k_amg_max_rows, dim3(gm), dim3(kBlock), 0, st, static_cast<const double *>(L.t.p), L.n, L.part_max.p);
+                hipLaunchKernelGGL(k_amg_max, dim3(1), dim3(1024), 0, st, static_cast<const double *>(L.part_max.p), static_cast<int64_t>(gm), L.lam.p, zero);
             } else {
-                hipLaunchKernelGGL(k_amg_max, dim3(1), dim3(1024), 0, s->stream, static_cast<const double *>(L.t.p), L.n, L.lam.p, zero);
+                hipLaunchKernelGGL(k_amg_max, dim3(1), dim3(1024), 0, st, static_cast<const double *>(L.t.p), L.n, L.lam.p, zero);
             }
             return PFEM_OK;
         }
@@ -3114,19 +3156,19 @@ int amg_numeric(pfem_solver *s, Amg &M, bool overlap)
             // the assembly kernel left the inverse diagonal in L.dinv and every row's sum |a_ij| / a_ii in L.t while the rows were in
             // LDS (k_gather_poisson_tet4): the maximum of the ratios is all that is left to do -- no pass over the assembled matrix
             const unsigned gm = std::min<unsigned>(g, 2048u);
-            hipLaunchKernelGGL(k_amg_max_rows, dim3(gm), dim3(kBlock), 0, s->stream, static_cast<const double *>(L.t.p), L.n, L.part_max.p);
-            hipLaunchKernelGGL(k_amg_max, dim3(1), dim3(1024), 0, s->stream, static_cast<const double *>(L.part_max.p), static_cast<int64_t>(gm), L.lam.p, zero);
+            hipLaunchKernelGGL(k_amg_max_rows, dim3(gm), dim3(kBlock), 0, st, static_cast<const double *>(L.t.p), L.n, L.part_max.p);
+            hipLaunchKernelGGL(k_amg_max, dim3(1), dim3(1024), 0, st, static_cast<const double *>(L.part_max.p), static_cast<int64_t>(gm), L.lam.p, zero);
             s->asm_bound_fresh = false;
         } else {
-            hipLaunchKernelGGL(k_amg_diag_bound, dim3(g), dim3(kBlock), 0, s->stream, A, static_cast<int32_t>(L.n), L.dinv.p, L.part_max.p);
-            hipLaunchKernelGGL(k_amg_max, dim3(1), dim3(1024), 0, s->stream, static_cast<const double *>(L.part_max.p), static_cast<int64_t>(g), L.lam.p, zero);
+            hipLaunchKernelGGL(k_amg_diag_bound, dim3(g), dim3(kBlock), 0, st, A, static_cast<int32_t>(L.n), L.dinv.p, L.part_max.p);
+            hipLaunchKernelGGL(k_amg_max, dim3(1), dim3(1024), 0, st, static_cast<const double *>(L.part_max.p), static_cast<int64_t>(g), L.lam.p, zero);
         }
         if (M.rbm) {            // the bound on the symmetrically scaled operator; the smaller of the two is taken (k_rbm_bound_sym)
             if (!M.lam2.p) PFEM_TRY(M.lam2.alloc(1));
-            hipLaunchKernelGGL(k_rbm_bound_sym, dim3(g), dim3(kBlock), 0, s->stream, A, static_cast<int32_t>(L.n), static_cast<const double *>(L.dinv.p),
+            hipLaunchKernelGGL(k_rbm_bound_sym, dim3(g), dim3(kBlock), 0, st, A, static_cast<int32_t>(L.n), static_cast<const double *>(L.dinv.p),
                                static_cast<double *>(nullptr), L.part_max.p);
-            hipLaunchKernelGGL(k_amg_max, dim3(1), dim3(1024), 0, s->stream, static_cast<const double *>(L.part_max.p), static_cast<int64_t>(g), M.lam2.p);
-            hipLaunchKernelGGL(k_rbm_min2, dim3(1), dim3(64), 0, s->stream, static_cast<const double *>(M.lam2.p), L.lam.p);
+            hipLaunchKernelGGL(k_amg_max, dim3(1), dim3(1024), 0, st, static_cast<const double *>(L.part_max.p), static_cast<int64_t>(g), M.lam2.p);
+            hipLaunchKernelGGL(k_rbm_min2, dim3(1), dim3(64), 0, st, static_cast<const double *>(M.lam2.p), L.lam.p);
         }
         return PFEM_OK;
     };
@@ -3146,7 +3188,8 @@ int amg_numeric(pfem_solver *s, Amg &M, bool overlap)
                 if (l == 0) PFEM_TRY(amg_level0_codes(s, M, L, &from_codes));
                 const bool mine = own_bounds && zeroed == l + 1;
                 double *next = mine && l + 2 < M.lev.size() ? M.lev[l + 2]->lam.p : nullptr;
-                if (amg_galerkin(s, L, C, A, !M.rbm && !M.coupled, M.vd_states.p ? M.vd_states.p + (l + 1) : nullptr, from_codes, mine ? C.lam.p : nullptr, next) && next)
+                if (side_from && l + 1 == side_from) PFEM_TRY(fork());
+                if (amg_galerkin_on(stream_of(l + 1), s, L, C, A, !M.rbm && !M.coupled, M.vd_states.p ? M.vd_states.p + (l + 1) : nullptr, from_codes, mine ? C.lam.p : nullptr, next) && next)
                     zeroed = l + 2;
                 if (from_codes) M.galerkin_from_codes = true;
                 if (l == 0 && std::getenv("PFEM_VD_VERBOSE"))
@@ -3158,10 +3201,11 @@ int amg_numeric(pfem_solver *s, Amg &M, bool overlap)
     PFEM_TRY(check_kernel("gamg numeric"));
     if (M.dense) {
         AmgLevel &L = *M.lev.back();
-        hipLaunchKernelGGL(k_amg_dense_inverse, dim3(1), dim3(1024), static_cast<size_t>(L.n * L.n) * sizeof(double), s->stream, amg_sell(s, L),
-                           M.dense_inv.p);
+        hipLaunchKernelGGL(k_amg_dense_inverse, dim3(1), dim3(1024), static_cast<size_t>(L.n * L.n) * sizeof(double), stream_of(M.lev.size() - 1),
+                           amg_sell(s, L), M.dense_inv.p);
         PFEM_TRY(check_kernel("k_amg_dense_inverse"));
     }
+    if (M.side_used) PFEM_HIP(hipEventRecord(M.ev_side1, M.side_stream));          // the chain's end: what the first cycle waits for
     return amg_value_codes(s, M);
 }
 
@@ -3248,7 +3292,8 @@ int amg_smooth(pfem_solver *s, const Amg &M, AmgLevel &L, const double *b, bool 
 // what amg_apply leaves of level 0's last post-smoothing step to its caller (fine degree 1): nothing; the step itself, t = A x
 // being in L0.t (k_pc_post_dots); or the product runs with the step and the CG's sums as its epilogue (Level0Ep: z in L0.t)
 enum { kLast0Smooth = 0, kLast0Product = 1, kLast0Epilogue = 2 };
-double *amg_apply(pfem_solver *s, Amg &M, const double *r, const CgCtl *ctl, bool first0_done = false, int last0 = kLast0Smooth);
+double *amg_apply(pfem_solver *s, Amg &M, const double *r, const CgCtl *ctl, bool first0_done = false, int last0 = kLast0Smooth, int join_level = 0,
+                  hipEvent_t join_ev = nullptr);
 double *amg_apply_coupled(pfem_solver *s, Amg &M, const double *r, const CgCtl *ctl, bool overlap)
 {
     const int nl = static_cast<int>(M.lev.size());
@@ -3351,9 +3396,18 @@ double *amg_apply_coupled(pfem_solver *s, Amg &M, const double *r, const CgCtl *
 //   * levels 1 .. tail_from-1: the SpMV with the vector step as its epilogue (k_amg_spmv_ep), step 0 of the pre-smoothing
 //     done by the restriction kernel of the level above: 6 launches per level instead of 10;
 //   * levels tail_from .. last (at most kAmgTailRows rows each): one workgroup walks them all in one launch (k_amg_tail).
-double *amg_apply(pfem_solver *s, Amg &M, const double *r, const CgCtl *ctl, bool first0_done, int last0)
+// join_ev (the first cycle behind a numeric phase that forked its side chain, never a captured cycle): the stream waits for it
+// once, in front of the first kernel that reads or writes anything of a level >= join_level.
+double *amg_apply(pfem_solver *s, Amg &M, const double *r, const CgCtl *ctl, bool first0_done, int last0, int join_level, hipEvent_t join_ev)
 {
     const int nl = static_cast<int>(M.lev.size());
+    bool joined = join_ev == nullptr;
+    // called in front of every kernel that touches level l (and, the tail: the last level)
+    auto touches = [&](int l) {
+        if (joined || l < join_level) return;
+        joined = true;
+        if (hipStreamWaitEvent(s->stream, join_ev, 0) == hipSuccess) M.side_pending = false;
+    };
     // several ranks: the ghost part of z holds the owners' values after the exchange of the previous cycle; as an SpMV
     // input of THIS rank's block it has to be zero again
     if (M.lev[0]->fine && s->n_ghost > 0) (void)hipMemsetAsync(M.lev[0]->x + s->n_owned, 0, sizeof(double) * static_cast<size_t>(s->n_ghost), s->stream);
@@ -3428,7 +3482,8 @@ double *amg_apply(pfem_solver *s, Amg &M, const double *r, const CgCtl *ctl, boo
     std::function<void(int)> visit = [&](int l) {
         AmgLevel &L = *M.lev[static_cast<size_t>(l)];
         const double *b = l == 0 ? r : L.b.p;
-        if (l == tail) { run_tail(); return; }
+        if (l == tail) { touches(nl - 1); run_tail(); return; }
+        touches(l);
         if (l == nl - 1) {                      // the last level, outside a tail
             if (M.dense) {
                 hipLaunchKernelGGL(k_amg_dense_apply, dim3(1), dim3(kAmgDense), 0, s->stream, static_cast<int>(L.n),
@@ -3453,6 +3508,7 @@ double *amg_apply(pfem_solver *s, Amg &M, const double *r, const CgCtl *ctl, boo
             res_t = L.t.p;
         }
         const bool first_below = fused_level(l + 1);              // the next level wants its step 0 from this launch
+        touches(l + 1);                                           // (the restriction writes the next level's right-hand side and reads its dinv and lam)
         if (L.rbm) {
             amg_rbm_restrict_launch(s, L, C, C.n_nodes, L.n_nodes, res, res_t, M.eig_ratio, first_below ? C.dd : static_cast<double *>(nullptr),
                                     first_below ? C.x : static_cast<double *>(nullptr), ctl, L.n_nodes);
@@ -3562,6 +3618,10 @@ int run_pcg_amg(pfem_solver *s)
     PFEM_TRY(amg_cycle_shape(s, M));
     M.coupled_fused = [] { const char *e = std::getenv("PFEM_AMG_COUPLED_FUSED"); return e ? std::atoi(e) != 0 : true; }();
     M.col_codes = [] { const char *e = std::getenv("PFEM_AMG_COL_CODES"); return e ? std::atoi(e) != 0 : true; }();      // (read at every solve)
+    M.side_on = [] { const char *e = std::getenv("PFEM_AMG_SIDE_STREAM"); return e ? std::atoi(e) != 0 : true; }();      // (likewise)
+    M.side_used = false;
+    M.side_first = 0;
+    M.side_ms = 0.0;
     if (M.coupled && M.coupled_fused && !s->d_row_sh.p && s->n_loc > 0) {        // level 0's dof -> shared index table (the coarse levels got theirs with their plans)
         PFEM_TRY(s->d_row_sh.alloc(static_cast<size_t>(s->n_loc)));
         PFEM_HIP(hipMemsetAsync(s->d_row_sh.p, 0xff, sizeof(int32_t) * static_cast<size_t>(s->n_loc), s->stream));
@@ -3575,8 +3635,21 @@ int run_pcg_amg(pfem_solver *s)
     PFEM_HIP(hipEventRecord(ea, s->stream));
     M.galerkin_fresh = did_symbolic;              // (only the phase that ran a moment ago, in THIS call, vouches for the coarse operators)
     if (M.rep) M.rep->galerkin_fresh = did_symbolic;
+    // Between the fork of the numeric phase's side chain (amg_numeric) and the first cycle's wait for it (amg_apply) no way out of this
+    // function may leave the chain running beside what the caller enqueues next: the solver's stream follows the side stream first.
+    struct SideJoin {
+        pfem_solver *s;
+        Amg &M;
+        ~SideJoin()
+        {
+            if (!M.side_pending || !M.side_stream || !M.ev_fork) return;
+            if (hipEventRecord(M.ev_fork, M.side_stream) != hipSuccess || hipStreamWaitEvent(s->stream, M.ev_fork, 0) != hipSuccess)
+                (void)hipStreamSynchronize(M.side_stream);
+            M.side_pending = false;
+        }
+    } side_join{s, M};
     PFEM_TRY(amg_numeric(s, M, overlap));
-    PFEM_HIP(hipEventRecord(eb, s->stream));
+    PFEM_HIP(hipEventRecord(eb, s->stream));          // (the solver's stream: the side chain has its own pair, ev_side0 .. ev_side1)
     M.cc_used.clear();              // (pfem_solver_amg_column_codes: what this solve's cycles run)
     for (size_t l = 1; l + 1 < M.lev.size(); ++l)
         if (amg_level_col_codes(M, *M.lev[l])) M.cc_used.push_back(static_cast<int>(l));
@@ -3652,7 +3725,9 @@ int run_pcg_amg(pfem_solver *s)
             return ep0 ? M.lev[0]->t.p : M.lev[0]->x;
         }
         if (M.coupled) return amg_apply_coupled(s, M, s->d_r.p, c, overlap);      // z is the same on every holder already
-        double *z = amg_apply(s, M, s->d_r.p, c, c == ctl && fuse_first0, c == ctl ? last0 : kLast0Smooth);
+        // (the first cycle, c == nullptr, is the one that joins the numeric phase's side chain)
+        const bool join = c == nullptr && M.side_pending;
+        double *z = amg_apply(s, M, s->d_r.p, c, c == ctl && fuse_first0, c == ctl ? last0 : kLast0Smooth, join ? M.side_first : 0, join ? M.ev_side1 : nullptr);
         if (c == ctl && fuse_last0) return z;            // the exchange follows the fused last step (dots lambda)
         if (multi && exchange_sum(s, z, overlap) != PFEM_OK) return nullptr;
         return z;
@@ -3791,5 +3866,9 @@ int run_pcg_amg(pfem_solver *s)
     float f = 0.f;
     PFEM_HIP(hipEventElapsedTime(&f, ea, eb));
     M.numeric_ms = f;
+    if (M.side_used) {
+        PFEM_HIP(hipEventElapsedTime(&f, M.ev_side0, M.ev_side1));
+        M.side_ms = f;
+    }
     return PFEM_OK;
 }

@@ -160,10 +160,25 @@ struct Amg {
     // the V-cycle as a hipGraph (one rank): ~100 dependent launches, most of them on levels too small to fill the chip
     CgGraph graph;
     hipEvent_t ev_num0 = nullptr, ev_num1 = nullptr;   // around the numeric phase of a solve (created once)
+    // One rank, plain transfers, a warm step (amg_numeric): the products that form the levels from side_first on and the dense inverse
+    // run on a stream of their own beside the first cycle's upper levels; ev_side0 .. ev_side1 are that chain's span, and ev_side1 is
+    // what the first cycle waits for in front of its first kernel that touches such a level (amg_apply).  Created at the first use.
+    hipStream_t side_stream = nullptr;
+    hipEvent_t ev_side0 = nullptr, ev_side1 = nullptr;
+    hipEvent_t ev_fork = nullptr;                    // where the main stream stood when the chain was forked off it (no timing)
+    bool side_on = true;                             // PFEM_AMG_SIDE_STREAM (read at every solve)
+    bool side_used = false;                          // the last numeric phase forked the chain
+    bool side_pending = false;                       // ... and the main stream has not waited for its end yet
+    int side_first = 0;                              // first level the chain formed (0: none)
+    double side_ms = 0.0;                            // the chain's span in the last solve
     ~Amg()
     {
         if (ev_num0) (void)hipEventDestroy(ev_num0);
         if (ev_num1) (void)hipEventDestroy(ev_num1);
+        if (ev_side0) (void)hipEventDestroy(ev_side0);
+        if (ev_side1) (void)hipEventDestroy(ev_side1);
+        if (ev_fork) (void)hipEventDestroy(ev_fork);
+        if (side_stream) (void)hipStreamDestroy(side_stream);
     }
     int tail_from = -1;                              // first level of the single-launch tail of the cycle (-1: none)
     size_t tail_lds_allowed = 0;                     // dynamic LDS bytes k_amg_tail<true, true> has been allowed beyond 64 KB (hipFuncSetAttribute)

@@ -6081,6 +6081,17 @@ extern "C" int pfem_solver_amg_cycle(pfem_solver *s, int *cycle, int *last_level
     *last_level_visited_twice = M.cycle_gamma > 1 ? std::min(M.w_to, static_cast<int>(M.lev.size()) - 2) : 0;
     return PFEM_OK;
 }
+// the side chain of the last gamg solve's numeric phase (amg_numeric): forked?  from which level on?  its span on its own stream
+extern "C" int pfem_solver_amg_side_stream(pfem_solver *s, int *used, int *first_level, double *ms)
+{
+    if (!s || !used || !first_level || !ms) return PFEM_ERR_ARG;
+    if (!s->amg || !s->amg->symbolic_ok) return PFEM_ERR_STATE;
+    const Amg &M = *s->amg;
+    *used = M.side_used ? 1 : 0;
+    *first_level = M.side_used ? M.side_first : 0;
+    *ms = M.side_used ? M.side_ms : 0.0;
+    return PFEM_OK;
+}
 // the level from which the cycle runs in one launch (amg_apply's `tail`), -1: level by level to the bottom
 extern "C" int pfem_solver_amg_tail_from(pfem_solver *s, int *tail_from, int *tail_build, int *bounds_by_products)
 {

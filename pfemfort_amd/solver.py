@@ -328,6 +328,15 @@ class PetscSolver:
         L.check(L.lib().pfem_solver_amg_tail_from(self._h, C.byref(t), C.byref(tb), C.byref(bp)), "pfem_solver_amg_tail_from")
         return bp.value
 
+    def amgSideStream(self):
+        """The side chain of the last gamg solve's numeric set-up: {"used": the products that form the levels from "first_level" on
+        and the dense inverse ran on a stream of their own beside the first cycle's upper levels, "first_level": that level (0: none),
+        "ms": the chain's span on its stream -- amgInfo()["numeric_ms"] then covers the solver's own stream only}.  Never used in a
+        pattern's first solve, whose products run in the symbolic phase: a property of the solver's history, unlike amgCycle()."""
+        u, k, ms = C.c_int(0), C.c_int(0), C.c_double(0)
+        L.check(L.lib().pfem_solver_amg_side_stream(self._h, C.byref(u), C.byref(k), C.byref(ms)), "pfem_solver_amg_side_stream")
+        return {"used": bool(u.value), "first_level": k.value, "ms": ms.value}
+
     def amgTransfer(self, level, xyz=False):
         """The transfer from ``level`` to the next: {"rbm": carries rotations?, "fine_bs", "coarse_bs", "dim", "n_nodes"} and, with
         ``xyz``, the level's node coordinates [3, n_nodes]."""
