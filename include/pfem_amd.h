@@ -547,6 +547,52 @@ int pfem_dynamics_run_implicit(pfem_solver *s, int scheme, double dt, int64_t n_
                                int64_t sample_every, double *history, int64_t *rows,
                                int32_t *iterations /* n_steps, or NULL */, int64_t *steps_done);
 
+/* ---- modal analysis: the lowest modes of (K, lumped M) --------------------- */
+/* The lowest n_modes pairs of  K phi = omega^2 M phi,  M = diag(m) the lumped mass of pfem_dynamics_setup, by LOBPCG (no soft
+ * locking) on a block X of MB columns, n x MB row-major on the device:  n_modes <= 2: MB = 4,  <= 6: 8,  <= 12: 16;  `block`
+ * (0: that choice) may force a larger one of the three.  tests/modal_reference.py is the scheme in numpy:
+ *   start   X0 = x0, or entry (i, j) = (splitmix64(i MB + j) >> 11) 2^-52 - 1 with i the GLOBAL free dof: no generator state,
+ *           the same block in every run.  K X0, then one Rayleigh-Ritz on X0 alone.
+ *   then    R = K X - (m o X) diag(theta);  res_j = ||R_j|| / (||K X_j|| + |theta_j| ||m o X_j||);  stop when res_j <= tol for
+ *           all j < n_modes.  W = T R;  K W in one pass over the matrix for all MB columns;  S = [X W P];  the upper triangles of
+ *           S^T K S and S^T (m o S), summed in a fixed order, go to the host;  pfem_dense_sym_geneig gives the lowest MB pairs and
+ *           the coefficients C, which come back;  P' = W C_W + P C_P,  X' = X C_X + P',  and the same on K X, K W, K P.
+ *           When the Gram matrix of the masses is singular to working precision P is dropped for that iteration (a restart,
+ *           counted in *restarts); when it is without P as well, the run ends with reason -2.  Every 10th iteration K X is
+ *           formed by a product instead of the recurrence.
+ *   T       pc = -1: the solver's preconditioner -- when that is gamg (one rank's own hierarchy) and its numeric set-up is
+ *           current, i.e. a gamg solve has run since the last assemble, W's columns are the multigrid cycle of that solve
+ *           applied to R's columns one at a time (the cycle and its set-up are used as they stand and left as they are);
+ *           otherwise the point Jacobi 1 / K_ii, in the run's own buffer.  pc = PFEM_PC_JACOBI / PFEM_PC_NODE_BLOCK_JACOBI: the
+ *           point Jacobi.  pc = PFEM_PC_GAMG: the cycle, or PFEM_ERR_STATE where it is not current.
+ *   end     pairs in ascending theta;  phi^T M phi = 1;  the entry of largest magnitude positive (the lowest index on ties);
+ *           residuals from an explicit K X.
+ * omega2[n_modes];  modes[n_modes x n_owned], mode-major, in pfem_solver_get_solution's order (may be NULL);  residuals[n_modes];
+ * *reason: 1 converged, -1 max_iterations, -2 breakdown -- a negative reason still returns the current pairs with PFEM_OK.
+ * x0: n_owned x MB row-major in the caller's dof order, or NULL.
+ * The run leaves the solve and the steppers alone: it reads the matrix in its row form, m and the diagonal, and writes only its
+ * own buffers (under gamg also the cycle's work vectors, which every solve fills before it reads them, and the SpMV's copies of
+ * the values, as every product outside a solve) -- not the solution, the right-hand side, the last iteration count / reason /
+ * norm, the residual history, the timings, the CG graphs or the state of pfem_dynamics_run / pfem_dynamics_run_implicit.  One
+ * stream, no graph; per iteration one device -> host copy (Gram matrices and norms) and one host -> device copy (C, theta), both
+ * through pinned buffers.
+ * Preconditions as pfem_dynamics_run: one rank, the batched path, pfem_dynamics_setup after the pattern build, an assembled
+ * matrix; and every m_i > 0 (PFEM_ERR_STATE).  PFEM_ERR_ARG, before the device is touched: n_modes < 1 or > 12, a block that is
+ * not 0 / 4 / 8 / 16 or too small for n_modes, tol <= 0 or not finite, max_iterations < 1, an unknown pc; and MB > n_owned.
+ * PFEM_ERR_NOGPU without a device.                                                                                            */
+#define PFEM_MODAL_MAX_MODES 12
+int pfem_modal_solve(pfem_solver *s, int n_modes, int block /*0: auto*/, double tol, int max_iterations, int pc /*-1: the solver's*/,
+                     const double *x0 /* n_owned x MB row-major, or NULL */, double *omega2 /* n_modes */,
+                     double *modes /* n_modes x n_owned, mode-major; may be NULL */, double *residuals, int *iterations,
+                     int *restarts, int *reason /* 1 converged, -1 max_iterations, -2 breakdown */);
+/* Host only, no device, no allocation: A c = w B c for symmetric A, B of order n <= PFEM_GENEIG_MAX (row-major, the upper
+ * triangles are read) by scaling with diag(B)^-1/2, a Cholesky factor of the scaled B and cyclic Jacobi rotations on the
+ * standard problem.  w[n] ascending, C[i * n + k] = entry i of vector k, C^T B C = I.  *status: 0, or 1 = singular (a diagonal
+ * entry of B or a pivot not positive, or a squared pivot of the scaled factor below `floor`): w and C are then not written.
+ * PFEM_ERR_ARG: n < 1 or > PFEM_GENEIG_MAX, a NULL pointer, floor negative or not finite.                                      */
+#define PFEM_GENEIG_MAX 48
+int pfem_dense_sym_geneig(int n, const double *A, const double *B, double floor, double *w, double *C, int *status);
+
 /* ---- inspection / export (device -> host) -------------------------------- */
 /* global dof id of every local row (owned first, then ghosts ascending) */
 int pfem_get_local_to_global(pfem_solver *s, int64_t *gid);

@@ -183,6 +183,17 @@ int pfem_dynamics_bench(pfem_solver *s, double dt, int graphs, double *us_per_st
  * iterations of the first step from the state at hand between two HIP events, with no convergence exit (rtol = 0), after one
  * graph unit to warm up.  The state does not advance.  PFEM_ERR_STATE when the loop ended early (zero load and state).      */
 int pfem_dynamics_bench_implicit(pfem_solver *s, int scheme, double dt, double p0, double p1, int iterations, double *us_per_iteration);
+/* Y = K X by the block product of pfem_modal_solve (k_spmm<mb> on the row form; mb = 4, 8 or 16): x and y are host blocks of
+ * n_local x mb doubles, row-major (the mb values of a dof contiguous), in the caller's dof order.  One rank, an assembled
+ * matrix (PFEM_ERR_STATE); writes no state of the handle.                                                                     */
+int pfem_modal_spmm(pfem_solver *s, int mb, const double *x, double *y);
+/* the preconditioner T the last pfem_modal_solve on this handle ran with: PFEM_PC_JACOBI or PFEM_PC_GAMG.  PFEM_ERR_STATE before
+ * the first run on the current pattern.                                                                                        */
+int pfem_modal_last_pc(pfem_solver *s, int *pc);
+/* microseconds of one k_spmm<mb> launch and of mb launches of the SpMV form in effect (what the block product replaces): `reps`
+ * of each between two HIP events, each series after one warm-up launch, on the same handle.  Like pfem_bench_spmv it uses the
+ * solve's SpMV input and output vectors.                                                                                      */
+int pfem_modal_bench_spmm(pfem_solver *s, int mb, int reps, double *us_spmm, double *us_mb_spmv);
 
 /* Timings of the last calls, measured with HIP events on the solver's stream [ms]. */
 typedef struct pfem_timings {

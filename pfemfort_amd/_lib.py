@@ -172,6 +172,11 @@ SIGNATURES = {
     "pfem_dynamics_bench": [_P, _D, _I, _P, _P],
     "pfem_dynamics_run_implicit": [_P, _I, _D, _L, _D, _D, _D, _L, _P, _P, _P, _P],
     "pfem_dynamics_bench_implicit": [_P, _I, _D, _D, _D, _I, _P],
+    "pfem_modal_solve": [_P, _I, _I, _D, _I, _I, _P, _P, _P, _P, _P, _P, _P],
+    "pfem_dense_sym_geneig": [_I, _P, _P, _D, _P, _P, _P],
+    "pfem_modal_spmm": [_P, _I, _P, _P],
+    "pfem_modal_last_pc": [_P, _P],
+    "pfem_modal_bench_spmm": [_P, _I, _I, _P, _P],
     "pfem_matrix_info": [_P, _P, _P, _P, _P],
     "pfem_get_local_to_global": [_P, _P],
     "pfem_get_csr": [_P, _P, _P, _P],

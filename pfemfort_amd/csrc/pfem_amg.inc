@@ -3649,6 +3649,7 @@ int run_pcg_amg(pfem_solver *s)
         }
     } side_join{s, M};
     PFEM_TRY(amg_numeric(s, M, overlap));
+    M.numeric_epoch = s->values_epoch;
     PFEM_HIP(hipEventRecord(eb, s->stream));          // (the solver's stream: the side chain has its own pair, ev_side0 .. ev_side1)
     M.cc_used.clear();              // (pfem_solver_amg_column_codes: what this solve's cycles run)
     for (size_t l = 1; l + 1 < M.lev.size(); ++l)

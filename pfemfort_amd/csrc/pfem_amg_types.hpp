@@ -140,6 +140,7 @@ struct Amg {
     DevBuf<double> dense_inv;                        // inverse of the coarsest operator (n <= kAmgDense)
     bool dense = false;
     bool symbolic_ok = false;
+    uint64_t numeric_epoch = ~0ull;                  // pfem_solver::values_epoch of the matrix the last numeric phase was made for
     bool galerkin_fresh = false;                     // the symbolic phase has just formed every coarse operator from the CURRENT values (it needs them level
                                                      // by level): the numeric phase of the same solve does not form them again
     double symbolic_ms = 0.0, numeric_ms = 0.0;

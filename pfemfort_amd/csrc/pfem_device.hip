@@ -34,6 +34,7 @@
 #include "pfem_amg_kernels.hpp"
 #include "pfem_dyn_kernels.hpp"
 #include "pfem_imp_kernels.hpp"
+#include "pfem_modal_kernels.hpp"
 #include "pfem_peer.hpp"
 
 using namespace pfem;
@@ -512,10 +513,29 @@ struct Imp {
     long long n_since = 0;
 };
 
+// modal analysis on the same handle (pfem_modal_solve, pfem_modal.inc): the six blocks, the inverse diagonal, the vector gamg's cycle reads
+// a column from, the partials and the two pinned host buffers of the per-iteration copies, allocated at the first run and again when the block size changes
+struct Modal {
+    int mb = 0;
+    int64_t n = 0;
+    int pc_used = PFEM_PC_JACOBI;          // the T of the last run (pfem_modal_last_pc)
+    DevBuf<double> X, W, P, KX, KW, KP, dinv, vec, part_gram, part_res, out, coef;
+    double *h_out = nullptr, *h_coef = nullptr;          // pinned: modal_out_len(mb) / modal_coef_len(mb) doubles
+    Modal() = default;
+    Modal(const Modal &) = delete;
+    Modal &operator=(const Modal &) = delete;
+    ~Modal()
+    {
+        if (h_out) (void)hipHostFree(h_out);
+        if (h_coef) (void)hipHostFree(h_coef);
+    }
+};
+
 enum { kDynFresh = 0, kDynExplicit = 1 };  // Dyn::mode; an implicit run leaves its PFEM_SCHEME_* + 1
 
 struct Dyn {
     std::unique_ptr<Imp> imp;
+    std::unique_ptr<Modal> modal;
     int mode = kDynFresh;                  // which stepper has advanced the state since pfem_dynamics_set_state
     int64_t n = 0;                         // rows (n_loc of the pattern it was set up on)
     DevBuf<double> d_mnode, d_m, d_minv;   // mass per node (device node order), m and 1 / m per matrix row
@@ -652,6 +672,8 @@ struct pfem_solver {
     // ... and (one rank, -pc_type gamg with its hierarchy in place) the inverse diagonal and the rows' Gershgorin ratios of level 0,
     // straight into the hierarchy's vectors: amg_numeric then skips its pass over the assembled matrix (k_amg_diag_bound)
     bool asm_bound_fresh = false;
+    uint64_t values_epoch = 0;     // counts the times the matrix values were zeroed for a new assembly (zero_values): what a numeric
+                                   // set-up was made for (Amg::numeric_epoch; read by pfem_modal_solve)
     DevBuf<int32_t> d_row_group;   // [n_loc] node group of every row (k_spmvg's copy written by the elasticity gather kernel itself)
     bool grp_vals_current = false;
     // the group form's values as 16-bit codes into a dictionary of the distinct values (pfem_valdict.hpp): which form the
@@ -2420,6 +2442,7 @@ ElemPrm make_prm(const double *elemData, const double *timeData, int kind)
 // kernel ever writes them
 int zero_values(pfem_solver *s, bool rows_overwritten = false)
 {
+    ++s->values_epoch;
     if (!rows_overwritten)
         PFEM_HIP(hipMemsetAsync(s->d_vals.p, 0, sizeof(double) * static_cast<size_t>(std::max<int64_t>(s->stored, 1)), s->stream));
     PFEM_HIP(hipMemsetAsync(s->d_rhs.p, 0, sizeof(double) * static_cast<size_t>(std::max<int64_t>(s->n_loc, 1)), s->stream));
@@ -5595,6 +5618,7 @@ extern "C" int pfem_solver_factorise(pfem_solver *s)
 
 #include "pfem_dynamics.inc"
 #include "pfem_implicit.inc"
+#include "pfem_modal.inc"
 
 extern "C" int pfem_solver_solve(pfem_solver *s, int *its, int *reason, double *rnorm)
 {

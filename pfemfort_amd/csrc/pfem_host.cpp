@@ -1011,3 +1011,111 @@ extern "C" int pfem_text_table_parse(const char *buf, int64_t len, int64_t rows,
     }
     return bad ? PFEM_ERR_ARG : PFEM_OK;
 }
+
+// ---------------------------------------------------------------------------
+// the Rayleigh-Ritz step of the modal analysis (pfem_modal_solve)
+// ---------------------------------------------------------------------------
+// A c = w B c for symmetric A and B of order n <= PFEM_GENEIG_MAX, both row-major, the UPPER triangles read: scale both by
+// D = diag(B)^-1/2, Cholesky factor L of D B D, the standard problem L^-1 (D A D) L^-T by cyclic Jacobi rotations, C = D L^-T Z.
+// w ascending, column k of C (C[i * n + k]) its vector, C^T B C = I.  *status: 0, or 1 = "singular": a diagonal entry of B that
+// is not positive and finite, a pivot that is not, or a squared pivot of the scaled factor below `floor` -- then w and C are
+// not written.  Fixed arrays only.
+extern "C" int pfem_dense_sym_geneig(int n, const double *A, const double *B, double floor, double *w, double *C, int *status)
+{
+    constexpr int N = PFEM_GENEIG_MAX;
+    if (n < 1 || n > N || !A || !B || !w || !C || !status || !(floor >= 0.0) || !std::isfinite(floor)) return PFEM_ERR_ARG;
+    static_assert(N == 48, "the fixed arrays below");
+    double d[N], L[N][N], S[N][N], Z[N][N], t[N];
+    auto up = [n](const double *M, int i, int j) { return i <= j ? M[i * n + j] : M[j * n + i]; };
+    *status = 1;
+    for (int i = 0; i < n; ++i) {
+        const double b = B[i * n + i];
+        if (!(b > 0.0) || !std::isfinite(b)) return PFEM_OK;
+        d[i] = 1.0 / std::sqrt(b);
+    }
+    // L L^T = D B D, row by row
+    for (int i = 0; i < n; ++i) {
+        for (int j = 0; j <= i; ++j) {
+            double a = d[i] * up(B, i, j) * d[j];
+            for (int k = 0; k < j; ++k) a -= L[i][k] * L[j][k];
+            if (j < i) {
+                L[i][j] = a / L[j][j];
+            } else {
+                if (!(a > 0.0) || !std::isfinite(a) || a < floor) return PFEM_OK;
+                L[i][i] = std::sqrt(a);
+            }
+        }
+    }
+    // S = L^-1 (D A D) L^-T: Y = L^-1 (D A D) column by column, then S = L^-1 Y^T; the upper triangle is kept and mirrored
+    for (int j = 0; j < n; ++j) {
+        for (int i = 0; i < n; ++i) {
+            double a = d[i] * up(A, i, j) * d[j];
+            for (int k = 0; k < i; ++k) a -= L[i][k] * Z[k][j];
+            Z[i][j] = a / L[i][i];
+        }
+    }
+    for (int j = 0; j < n; ++j) {           // column j of S: L^-1 (row j of Y)^T
+        for (int i = 0; i < n; ++i) {
+            double a = Z[j][i];
+            for (int k = 0; k < i; ++k) a -= L[i][k] * t[k];
+            t[i] = a / L[i][i];
+        }
+        for (int i = 0; i < n; ++i) S[i][j] = t[i];
+    }
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < i; ++j) S[i][j] = S[j][i];
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) Z[i][j] = i == j ? 1.0 : 0.0;
+    // cyclic Jacobi, row by row, until the off-diagonal part is below eps x the diagonal's norm (at most 60 sweeps)
+    const double eps = 2.220446049250313e-16;
+    for (int sweep = 0; sweep < 60; ++sweep) {
+        double off = 0.0, dia = 0.0;
+        for (int i = 0; i < n; ++i) {
+            dia += S[i][i] * S[i][i];
+            for (int j = i + 1; j < n; ++j) off += S[i][j] * S[i][j];
+        }
+        if (off == 0.0 || std::sqrt(off) <= eps * std::sqrt(dia)) break;
+        for (int p = 0; p < n - 1; ++p) {
+            for (int q = p + 1; q < n; ++q) {
+                const double apq = S[p][q];
+                if (apq == 0.0) continue;
+                const double tau = (S[q][q] - S[p][p]) / (2.0 * apq);
+                const double tn = (tau >= 0.0 ? 1.0 : -1.0) / (std::fabs(tau) + std::sqrt(1.0 + tau * tau));
+                const double c = 1.0 / std::sqrt(1.0 + tn * tn), sn = tn * c;
+                for (int k = 0; k < n; ++k) {           // rows p, q
+                    const double a = S[p][k], b = S[q][k];
+                    S[p][k] = c * a - sn * b;
+                    S[q][k] = sn * a + c * b;
+                }
+                for (int k = 0; k < n; ++k) {           // columns p, q, of S and of the vectors
+                    const double a = S[k][p], b = S[k][q];
+                    S[k][p] = c * a - sn * b;
+                    S[k][q] = sn * a + c * b;
+                    const double za = Z[k][p], zb = Z[k][q];
+                    Z[k][p] = c * za - sn * zb;
+                    Z[k][q] = sn * za + c * zb;
+                }
+                S[p][q] = S[q][p] = 0.0;
+            }
+        }
+    }
+    // ascending, equal values in their order of appearance
+    int order[N];
+    for (int i = 0; i < n; ++i) {           // (insertion sort: no temporary buffer)
+        int k = i;
+        for (; k > 0 && S[order[k - 1]][order[k - 1]] > S[i][i]; --k) order[k] = order[k - 1];
+        order[k] = i;
+    }
+    for (int k = 0; k < n; ++k) {
+        const int src = order[k];
+        w[k] = S[src][src];
+        for (int i = n - 1; i >= 0; --i) {  // L^T x = z
+            double a = Z[i][src];
+            for (int j = i + 1; j < n; ++j) a -= L[j][i] * t[j];
+            t[i] = a / L[i][i];
+        }
+        for (int i = 0; i < n; ++i) C[i * n + k] = d[i] * t[i];
+    }
+    *status = 0;
+    return PFEM_OK;
+}

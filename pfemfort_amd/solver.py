@@ -6,6 +6,7 @@ There is no CPU fallback: constructing the device object without a GPU raises.
 from __future__ import annotations
 
 import ctypes as C
+from collections import namedtuple
 
 import numpy as np
 
@@ -24,6 +25,9 @@ def _f64(a):
 
 def _i32(a):
     return np.ascontiguousarray(a, dtype=np.int32)
+
+
+ModalResult = namedtuple("ModalResult", "omega omega2 modes residuals iterations restarts reason block pc")
 
 
 class PetscSolver:
@@ -730,6 +734,51 @@ class PetscSolver:
         L.check(L.lib().pfem_dynamics_bench_implicit(self._h, code, float(dt), float(p0), float(p1), int(iterations), C.byref(us)),
                 "pfem_dynamics_bench_implicit")
         return us.value
+
+    def modalSolve(self, n_modes, tol=1e-6, max_iterations=1000, block=0, pc=None, x0=None, modes=True):
+        """The lowest ``n_modes`` (1..12) modes of ``K phi = omega^2 M phi`` with the lumped mass of ``dynamicsSetup``
+        (``pfem_modal_solve``): LOBPCG on a block of 4, 8 or 16 vectors (``block=0``: chosen from ``n_modes``), started from
+        ``x0`` (``N x block``, row-major) or from a fixed hash of the dof numbers, so that two runs give the same bits.  The
+        preconditioner ``pc``: None takes the solver's -- the cycle of the last gamg solve when ``setPreconditioner("gamg")`` is
+        in effect and a solve has run since the last assemble, else the point Jacobi ``1 / K_ii``; ``"jacobi"`` forces the
+        point Jacobi, ``"gamg"`` raises ``ERR_STATE`` where the cycle is not current.  The result's ``pc`` names what ran.
+        Returns a ``ModalResult``: ``omega`` (rad per time unit, ascending), ``omega2``,
+        ``modes`` (``N x n_modes``, ``phi^T M phi = 1``, the largest entry positive; None with ``modes=False``),
+        ``residuals`` (``||K phi - omega^2 M phi||`` relative to ``||K phi|| + omega^2 ||M phi||``), ``iterations``,
+        ``restarts``, ``reason`` (1 converged, -1 ``max_iterations``, -2 breakdown) and ``block``.  The solve, its
+        preconditioner and the steppers' state are left as they are."""
+        n_modes = int(n_modes)
+        mb = max(int(block), 4 if n_modes <= 2 else 8 if n_modes <= 6 else 16)
+        N = self.matrixInfo()["n_owned"]
+        k = max(n_modes, 1)
+        om2 = np.zeros(k); res = np.zeros(k)
+        phi = np.zeros((k, N)) if modes else None
+        if x0 is not None:
+            x0 = _f64(x0)
+            if x0.shape != (N, mb):
+                raise ValueError(f"x0 must be {N} x {mb}")
+        its = C.c_int(0); restarts = C.c_int(0); reason = C.c_int(0)
+        L.check(L.lib().pfem_modal_solve(self._h, n_modes, int(block), float(tol), int(max_iterations), {None: -1, "jacobi": 0, "pbjacobi": 1, "gamg": 2}.get(pc, pc),
+                                         _p(x0) if x0 is not None else None, _p(om2), _p(phi) if modes else None, _p(res),
+                                         C.byref(its), C.byref(restarts), C.byref(reason)), "pfem_modal_solve")
+        used = C.c_int(0)
+        L.check(L.lib().pfem_modal_last_pc(self._h, C.byref(used)), "pfem_modal_last_pc")
+        return ModalResult(omega=np.sqrt(np.maximum(om2, 0.0)), omega2=om2, modes=np.ascontiguousarray(phi.T) if modes else None,
+                           residuals=res, iterations=its.value, restarts=restarts.value, reason=reason.value, block=mb,
+                           pc={0: "jacobi", 2: "gamg"}[used.value])
+
+    def modalSpmm(self, X):
+        """``K X`` for a block ``X`` (``n_local x 4 / 8 / 16``) by the block product of ``modalSolve`` (``pfem_modal_spmm``)."""
+        X = _f64(X)
+        Y = np.empty_like(X)
+        L.check(L.lib().pfem_modal_spmm(self._h, X.shape[1], _p(X), _p(Y)), "pfem_modal_spmm")
+        return Y
+
+    def benchModalSpmm(self, mb, reps=50):
+        """Microseconds of one block product of ``mb`` vectors and of ``mb`` single products (``pfem_modal_bench_spmm``)."""
+        a = C.c_double(0); b = C.c_double(0)
+        L.check(L.lib().pfem_modal_bench_spmm(self._h, int(mb), int(reps), C.byref(a), C.byref(b)), "pfem_modal_bench_spmm")
+        return a.value, b.value
 
     def postTimings(self):
         """Kernel milliseconds of the last ``elementFields`` / ``nodalForces`` call (HIP events, host copies excluded)."""
