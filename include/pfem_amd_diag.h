@@ -187,6 +187,28 @@ int pfem_dynamics_bench_implicit(pfem_solver *s, int scheme, double dt, double p
  * n_local x mb doubles, row-major (the mb values of a dof contiguous), in the caller's dof order.  One rank, an assembled
  * matrix (PFEM_ERR_STATE); writes no state of the handle.                                                                     */
 int pfem_modal_spmm(pfem_solver *s, int mb, const double *x, double *y);
+/* One launch of a kernel of pfem_modal_solve on blocks of the caller's, through the grid function and the launch code of the
+ * solve itself: what the tests compare with an exact or extended-precision evaluation at row counts beyond one pass of the
+ * capped grids.  Every block is a host array of n x mb doubles, row-major, in plain row order (rows of a block, not dofs: no
+ * renumbering applies); m and dinv hold n doubles; n >= 1, mb = 4, 8 or 16 (PFEM_ERR_ARG).  An initialised handle is all they
+ * need -- no mesh, pattern or mass -- and they write no state of it.  On the device every block is followed by one tile of rows
+ * of quiet NaNs: a read behind row n poisons the sums, and a write there is found after the launch -- PFEM_ERR_HIP, with the
+ * block's name in pfem_last_error_string.
+ *   gram:     k_modal_gram<mb> on its grid for n rows, then k_modal_sum; out: the 2 NS NS doubles (NS = 3 mb) of S^T K S and
+ *             S^T (m o S), S = [X W P], as the solve's Rayleigh-Ritz step reads them (upper block triangles, zeros below).
+ *   residual: k_modal_residual<mb> on its grid for n mb entries, then k_modal_sum; W_out = dinv o (KX - (m o X) diag(theta))
+ *             (dinv == NULL: without dinv), norms_out: the 3 mb sums ||R_j||^2, ||KX_j||^2, ||m o X_j||^2.  theta: mb doubles.
+ *   update:   k_modal_update<mb> on its grid for n rows with coef = C (3 mb x mb, row-major: rows of X, of W, of P); X, P, KX
+ *             and KP come back updated, W and KW as they stood on the device after the launch.                              */
+int pfem_modal_probe_gram(pfem_solver *s, int mb, int64_t n, const double *X, const double *W, const double *P, const double *KX,
+                          const double *KW, const double *KP, const double *m, double *out);
+int pfem_modal_probe_residual(pfem_solver *s, int mb, int64_t n, const double *KX, const double *X, const double *m, const double *dinv,
+                              const double *theta, double *W_out, double *norms_out);
+int pfem_modal_probe_update(pfem_solver *s, int mb, int64_t n, const double *coef, double *X, double *W, double *P, double *KX,
+                            double *KW, double *KP);
+/* *in_effect = 1 when the mesh on the device is held under the internal renumbering (a numbering without locality from 4 096
+ * owned dofs, or PFEM_REORDER=1 at the upload), else 0: the tests of the translations assert it.                            */
+int pfem_solver_reordered(pfem_solver *s, int *in_effect);
 /* the preconditioner T the last pfem_modal_solve on this handle ran with: PFEM_PC_JACOBI or PFEM_PC_GAMG.  PFEM_ERR_STATE before
  * the first run on the current pattern.                                                                                        */
 int pfem_modal_last_pc(pfem_solver *s, int *pc);

@@ -175,6 +175,10 @@ SIGNATURES = {
     "pfem_modal_solve": [_P, _I, _I, _D, _I, _I, _P, _P, _P, _P, _P, _P, _P],
     "pfem_dense_sym_geneig": [_I, _P, _P, _D, _P, _P, _P],
     "pfem_modal_spmm": [_P, _I, _P, _P],
+    "pfem_modal_probe_gram": [_P, _I, _L] + [_P] * 8,
+    "pfem_modal_probe_residual": [_P, _I, _L] + [_P] * 7,
+    "pfem_modal_probe_update": [_P, _I, _L] + [_P] * 7,
+    "pfem_solver_reordered": [_P, _P],
     "pfem_modal_last_pc": [_P, _P],
     "pfem_modal_bench_spmm": [_P, _I, _I, _P, _P],
     "pfem_matrix_info": [_P, _P, _P, _P, _P],

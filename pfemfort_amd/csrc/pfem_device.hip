@@ -1094,7 +1094,8 @@ namespace {
 // renumbered INTERNALLY along a Morton curve through the node coordinates (dofs of a node stay together); every entry point
 // that takes or returns dof-indexed data translates, so the ABI keeps the caller's numbering, and K, F (summed per row in
 // element order, whatever the row is called) keep their bits.  PFEM_REORDER=0 / 1 forces it off / on; otherwise it is
-// taken when most elements have no two nodes whose dofs lie within a few thousand places of each other.  The generated boxes
+// taken when most elements have no two nodes whose dofs lie within a few thousand places of each other -- or, on a vector too
+// short for that, half as many as a random numbering would leave (below).  The generated boxes
 // (pfem_mesh_generate_box) and the reference's partition renumbering are line-by-line numberings and are left alone: the
 // fastest SpMV forms live on them.
 int maybe_reorder(pfem_solver *s, const int32_t *edof_global, const double *xyz)
@@ -1131,6 +1132,18 @@ int maybe_reorder(pfem_solver *s, const int32_t *edof_global, const double *xyz)
             if (owned >= 2) { ++cnt; far_elems += best > near; }
         }
         want = (cnt > 0 && 2 * far_elems > cnt) ? 1 : 0;
+        // On a vector of a few times `near` places even a random numbering leaves most elements a near pair: two random places
+        // are near with probability p = 2 near / n, an element of k nodes is far with probability q = (1 - p)^(k (k - 1) / 2)
+        // (0.25 for tetrahedra on 19 656 dofs, 0.78 on 100 000), and "more than half" is out of reach.  So the count is also
+        // held against q: at least half of what a random numbering would give, where q >= 0.1 leaves a count to judge by (a
+        // line-by-line numbering has next to none; from about 12 900 dofs for tetrahedra of one component).  Below that the
+        // whole vector is a few spans of `near` places long and stays as it is.
+        if (!want && cnt > 0) {
+            const double p = std::min(1.0, 2.0 * static_cast<double>(near) / static_cast<double>(no));
+            const int k = std::min<int>(m.npe, 8);
+            const double q = std::pow(1.0 - p, 0.5 * k * (k - 1));
+            if (q >= 0.1 && static_cast<double>(far_elems) >= 0.5 * q * static_cast<double>(cnt)) want = 1;
+        }
     }
     if (!want) return PFEM_OK;
     double lo[3] = {0, 0, 0}, hi[3] = {1, 1, 1};
@@ -2410,6 +2423,14 @@ extern "C" int pfem_matrix_info(pfem_solver *s, int64_t *n_owned, int64_t *n_loc
     if (n_local) *n_local = s->n_loc;
     if (nnz) *nnz = s->have_pattern ? s->nnz : 0;
     if (stored_entries) *stored_entries = s->have_pattern ? s->stored : 0;
+    return PFEM_OK;
+}
+
+// whether the mesh on the device is held under the internal renumbering (maybe_reorder; pfem_amd_diag.h)
+extern "C" int pfem_solver_reordered(pfem_solver *s, int *in_effect)
+{
+    if (!s || !in_effect) return PFEM_ERR_ARG;
+    *in_effect = s->reordered ? 1 : 0;
     return PFEM_OK;
 }
 

@@ -38,6 +38,34 @@ unsigned modal_update_grid(int64_t n, int mb)
     return static_cast<unsigned>(std::min<int64_t>(kModalVecBlocks, std::max<int64_t>(1, (n + tr - 1) / tr)));
 }
 
+// What one launch of the Gram, residual and update kernels reads and writes: the six blocks of n rows x mb columns, the mass and
+// the inverse diagonal by row, the coefficient block, the partials and the summed output on the device and its host copy.  The
+// solve fills it from the buffers of Modal (modal_view), a probe (pfem_modal_probe_*) from blocks of its own: both launch
+// through the three functions below.
+struct ModalView {
+    int mb = 0;
+    int64_t n = 0;
+    double *X = nullptr, *W = nullptr, *P = nullptr, *KX = nullptr, *KW = nullptr, *KP = nullptr;
+    const double *m = nullptr, *dinv = nullptr;
+    double *vec = nullptr;                 // n doubles: a column of W on its way through gamg's cycle
+    double *coef = nullptr, *part_gram = nullptr, *part_res = nullptr, *out = nullptr;
+    double *h_out = nullptr;               // modal_out_len(mb) doubles on the host
+};
+
+ModalView modal_view(const pfem_solver *s, Modal &M)
+{
+    ModalView V;
+    V.mb = M.mb;
+    V.n = M.n;
+    V.X = M.X.p; V.W = M.W.p; V.P = M.P.p; V.KX = M.KX.p; V.KW = M.KW.p; V.KP = M.KP.p;
+    V.m = s->dyn->d_m.p;
+    V.dinv = M.dinv.p;
+    V.vec = M.vec.p;
+    V.coef = M.coef.p; V.part_gram = M.part_gram.p; V.part_res = M.part_res.p; V.out = M.out.p;
+    V.h_out = M.h_out;
+    return V;
+}
+
 // the run's own buffers for blocks of mb columns
 int modal_ensure(pfem_solver *s, int mb)
 {
@@ -73,44 +101,43 @@ void modal_spmm(pfem_solver *s, int mb, const double *X, double *Y)
 }
 
 // the Gram pass over the six blocks and the sums of its partials and (with_res) of the residual kernel's; then the copy to the
-// pinned buffer and the wait for it
-int modal_gram_to_host(pfem_solver *s, Modal &M, bool with_gram, unsigned res_blocks)
+// host buffer and the wait for it
+int modal_gram_to_host(pfem_solver *s, const ModalView &V, bool with_gram, unsigned res_blocks)
 {
-    const int mb = M.mb, n_gram = modal_gram_len(mb), n_res = 3 * mb;
-    const unsigned gg = modal_gram_grid(M.n);
+    const int mb = V.mb, n_gram = modal_gram_len(mb), n_res = 3 * mb;
+    const unsigned gg = modal_gram_grid(V.n);
     if (with_gram)
         with_mb(mb, [&](auto MB) {
-            launch(k_modal_gram<decltype(MB)::value>, dim3(gg), dim3(kBlock), 0, s->stream, nullptr, nullptr, M.n, M.X.p, M.W.p, M.P.p, M.KX.p, M.KW.p, M.KP.p,
-                   s->dyn->d_m.p, M.part_gram.p);
+            launch(k_modal_gram<decltype(MB)::value>, dim3(gg), dim3(kBlock), 0, s->stream, nullptr, nullptr, V.n, V.X, V.W, V.P, V.KX, V.KW, V.KP, V.m, V.part_gram);
         });
-    launch(k_modal_sum, dim3(grid_for(n_gram + n_res)), dim3(kBlock), 0, s->stream, nullptr, nullptr, n_gram, with_gram ? static_cast<int>(gg) : 0, M.part_gram.p,
-           n_res, static_cast<int>(res_blocks), M.part_res.p, M.out.p);
+    launch(k_modal_sum, dim3(grid_for(n_gram + n_res)), dim3(kBlock), 0, s->stream, nullptr, nullptr, n_gram, with_gram ? static_cast<int>(gg) : 0, V.part_gram,
+           n_res, static_cast<int>(res_blocks), V.part_res, V.out);
     PFEM_TRY(check_kernel("k_modal_gram"));
-    PFEM_HIP(hipMemcpyAsync(M.h_out, M.out.p, sizeof(double) * modal_out_len(mb), hipMemcpyDeviceToHost, s->stream));
+    PFEM_HIP(hipMemcpyAsync(V.h_out, V.out, sizeof(double) * modal_out_len(mb), hipMemcpyDeviceToHost, s->stream));
     PFEM_HIP(hipStreamSynchronize(s->stream));
     return PFEM_OK;
 }
 
 // R, the norms' partials and W = T R: the point Jacobi inside the residual kernel, or (gamg) the cycle of the last gamg solve on
-// every column in turn -- amg_apply as it stands, through the contiguous vector M.vec and the cycle's own output vector
-unsigned modal_residual(pfem_solver *s, Modal &M, bool gamg)
+// every column in turn -- amg_apply as it stands, through the contiguous vector V.vec and the cycle's own output vector
+unsigned modal_residual(pfem_solver *s, const ModalView &V, bool gamg)
 {
-    const unsigned gr = modal_vec_grid(M.n * M.mb);
-    with_mb(M.mb, [&](auto MB) {
-        launch(k_modal_residual<decltype(MB)::value>, dim3(gr), dim3(kBlock), 0, s->stream, nullptr, nullptr, M.n, M.KX.p, M.X.p, s->dyn->d_m.p,
-               gamg ? nullptr : M.dinv.p, M.coef.p + 3 * M.mb * M.mb, M.W.p, M.part_res.p);
+    const unsigned gr = modal_vec_grid(V.n * V.mb);
+    with_mb(V.mb, [&](auto MB) {
+        launch(k_modal_residual<decltype(MB)::value>, dim3(gr), dim3(kBlock), 0, s->stream, nullptr, nullptr, V.n, V.KX, V.X, V.m, gamg ? nullptr : V.dinv,
+               V.coef + 3 * V.mb * V.mb, V.W, V.part_res);
     });
     if (gamg) {
         Amg &A = *s->amg;
         const int tail_build = A.tail_build;
-        for (int j = 0; j < M.mb; ++j) {
-            with_mb(M.mb, [&](auto MB) {
-                launch(k_modal_pack<decltype(MB)::value>, dim3(grid_for(M.n)), dim3(kBlock), 0, s->stream, nullptr, nullptr, M.n, M.W.p, j, M.vec.p);
+        for (int j = 0; j < V.mb; ++j) {
+            with_mb(V.mb, [&](auto MB) {
+                launch(k_modal_pack<decltype(MB)::value>, dim3(grid_for(V.n)), dim3(kBlock), 0, s->stream, nullptr, nullptr, V.n, V.W, j, V.vec);
             });
-            const double *z = amg_apply(s, A, M.vec.p, nullptr);
+            const double *z = amg_apply(s, A, V.vec, nullptr);
             if (!z) return 0;
-            with_mb(M.mb, [&](auto MB) {
-                launch(k_modal_unpack<decltype(MB)::value>, dim3(grid_for(M.n)), dim3(kBlock), 0, s->stream, nullptr, nullptr, M.n, z, j, M.W.p);
+            with_mb(V.mb, [&](auto MB) {
+                launch(k_modal_unpack<decltype(MB)::value>, dim3(grid_for(V.n)), dim3(kBlock), 0, s->stream, nullptr, nullptr, V.n, z, j, V.W);
             });
         }
         A.tail_build = tail_build;         // (what the last SOLVE's cycle launched, pfem_solver_amg_tail_from)
@@ -146,12 +173,13 @@ int modal_rayleigh_ritz(Modal &M, int ns, int *singular)
     return PFEM_OK;
 }
 
-int modal_update(pfem_solver *s, Modal &M)
+// h_coef (modal_coef_len(mb) doubles on the host: C, then theta) to the device, then the update of the six blocks in place
+int modal_update(pfem_solver *s, const ModalView &V, const double *h_coef)
 {
-    PFEM_HIP(hipMemcpyAsync(M.coef.p, M.h_coef, sizeof(double) * modal_coef_len(M.mb), hipMemcpyHostToDevice, s->stream));
-    with_mb(M.mb, [&](auto MB) {
-        launch(k_modal_update<decltype(MB)::value>, dim3(modal_update_grid(M.n, M.mb)), dim3(kBlock), 0, s->stream, nullptr, nullptr, M.n, M.coef.p, M.X.p, M.W.p,
-               M.P.p, M.KX.p, M.KW.p, M.KP.p);
+    PFEM_HIP(hipMemcpyAsync(V.coef, h_coef, sizeof(double) * modal_coef_len(V.mb), hipMemcpyHostToDevice, s->stream));
+    with_mb(V.mb, [&](auto MB) {
+        launch(k_modal_update<decltype(MB)::value>, dim3(modal_update_grid(V.n, V.mb)), dim3(kBlock), 0, s->stream, nullptr, nullptr, V.n, V.coef, V.X, V.W, V.P,
+               V.KX, V.KW, V.KP);
     });
     return check_kernel("k_modal_update");
 }
@@ -214,6 +242,7 @@ extern "C" int pfem_modal_solve(pfem_solver *s, int n_modes, int block, double t
         }
     PFEM_TRY(modal_ensure(s, mb));
     Modal &M = *D.modal;
+    const ModalView V = modal_view(s, M);
     M.pc_used = gamg ? PFEM_PC_GAMG : PFEM_PC_JACOBI;
     if (gamg) {                            // the cycle's fine-level products run in the SpMV form in effect: its copies of the values
         mark_group_vals(s);
@@ -237,7 +266,7 @@ extern "C" int pfem_modal_solve(pfem_solver *s, int n_modes, int block, double t
     for (DevBuf<double> *g : {&M.W, &M.P, &M.KW, &M.KP}) PFEM_HIP(hipMemsetAsync(g->p, 0, block_bytes, s->stream));
     PFEM_HIP(hipMemsetAsync(M.out.p, 0, sizeof(double) * modal_out_len(mb), s->stream));
     modal_spmm(s, mb, M.X.p, M.KX.p);
-    PFEM_TRY(modal_gram_to_host(s, M, true, 0));
+    PFEM_TRY(modal_gram_to_host(s, V, true, 0));
     double theta[16];
     int its = 0, n_restarts = 0, why = 0, singular = 0;
     bool have_p = false;
@@ -250,13 +279,13 @@ extern "C" int pfem_modal_solve(pfem_solver *s, int n_modes, int block, double t
     } else {
         for (int j = 0; j < mb; ++j) theta[j] = M.h_coef[NS * mb + j];
     }
-    PFEM_TRY(modal_update(s, M));
+    PFEM_TRY(modal_update(s, V, M.h_coef));
     while (why == 0) {
         // R, W = T R and the norms; K W; the Gram matrices of [X W P]; one copy back
-        const unsigned gr = modal_residual(s, M, gamg);
+        const unsigned gr = modal_residual(s, V, gamg);
         if (gr == 0) return PFEM_ERR_HIP;
         modal_spmm(s, mb, M.W.p, M.KW.p);
-        PFEM_TRY(modal_gram_to_host(s, M, true, gr));
+        PFEM_TRY(modal_gram_to_host(s, V, true, gr));
         bool done = true;
         for (int j = 0; j < n_modes; ++j) done = done && modal_res(M, j, theta[j]) <= tol;
         if (done) { why = 1; break; }
@@ -269,14 +298,14 @@ extern "C" int pfem_modal_solve(pfem_solver *s, int n_modes, int block, double t
         }
         if (singular) { why = -2; break; }
         for (int j = 0; j < mb; ++j) theta[j] = M.h_coef[NS * mb + j];
-        PFEM_TRY(modal_update(s, M));
+        PFEM_TRY(modal_update(s, V, M.h_coef));
         have_p = true;
         if (its % kModalRefresh == 0) modal_spmm(s, mb, M.X.p, M.KX.p);
     }
     // the end: residuals from an explicit K X (theta is ascending as the Rayleigh-Ritz step left it)
     modal_spmm(s, mb, M.X.p, M.KX.p);
-    const unsigned gr = modal_residual(s, M, false);
-    PFEM_TRY(modal_gram_to_host(s, M, false, gr));
+    const unsigned gr = modal_residual(s, V, false);
+    PFEM_TRY(modal_gram_to_host(s, V, false, gr));
     for (int j = 0; j < n_modes; ++j) {
         omega2[j] = theta[j];
         residuals[j] = modal_res(M, j, theta[j]);
@@ -334,6 +363,152 @@ extern "C" int pfem_modal_spmm(pfem_solver *s, int mb, const double *x, double *
     PFEM_HIP(hipMemcpyAsync(h.data(), dy.p, sizeof(double) * len, hipMemcpyDeviceToHost, s->stream));
     PFEM_HIP(hipStreamSynchronize(s->stream));
     for (int64_t i = 0; i < n; ++i) std::memcpy(y + i * mb, &h[static_cast<size_t>(to_internal(s, i)) * mb], sizeof(double) * mb);
+    return PFEM_OK;
+}
+
+// ---- one launch of a modal kernel on blocks of the caller's (pfem_amd_diag.h) ---------------------------------------------------
+namespace {
+
+// A block of a probe on the device: `len` doubles, then a tile of quiet NaNs that no launch may read -- a read poisons the sums
+// -- or write: probe_download compares the fill's bits.
+struct ProbeBlock {
+    DevBuf<double> d;
+    const char *name = "";
+    size_t len = 0, guard = 0;
+};
+
+// host == nullptr: an output, NaN throughout, so that an entry the launch skips shows as well
+int probe_upload(pfem_solver *s, ProbeBlock &B, const char *name, const double *host, size_t len, size_t guard)
+{
+    B.name = name;
+    B.len = len;
+    B.guard = guard;
+    PFEM_TRY(B.d.alloc(len + guard));
+    std::vector<double> h(len + guard, std::numeric_limits<double>::quiet_NaN());
+    if (host) std::memcpy(h.data(), host, sizeof(double) * len);
+    PFEM_HIP(hipMemcpyAsync(B.d.p, h.data(), sizeof(double) * (len + guard), hipMemcpyHostToDevice, s->stream));
+    PFEM_HIP(hipStreamSynchronize(s->stream));       // (h goes out of scope)
+    return PFEM_OK;
+}
+
+// the block back (out may be nullptr) and the check of its guard tile
+int probe_download(pfem_solver *s, const ProbeBlock &B, double *out, const char *who)
+{
+    std::vector<double> h(B.len + B.guard);
+    PFEM_HIP(hipMemcpyAsync(h.data(), B.d.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, s->stream));
+    PFEM_HIP(hipStreamSynchronize(s->stream));
+    const double fill = std::numeric_limits<double>::quiet_NaN();
+    for (size_t i = B.len; i < h.size(); ++i)
+        if (std::memcmp(&h[i], &fill, sizeof(double)) != 0) {
+            set_last_error(std::string(who) + ": the launch wrote behind the last row of block " + B.name + " (guard entry " + std::to_string(i - B.len) + ")");
+            return PFEM_ERR_HIP;
+        }
+    if (out) std::memcpy(out, h.data(), sizeof(double) * B.len);
+    return PFEM_OK;
+}
+
+bool probe_args(const pfem_solver *s, int mb, int64_t n) { return s && n >= 1 && (mb == 4 || mb == 8 || mb == 16); }
+
+}  // namespace
+
+// k_modal_gram<mb> on modal_gram_grid(n) blocks, then k_modal_sum: out = the 2 NS NS doubles of h_out (pfem_amd_diag.h)
+extern "C" int pfem_modal_probe_gram(pfem_solver *s, int mb, int64_t n, const double *X, const double *W, const double *P, const double *KX, const double *KW,
+                                     const double *KP, const double *m, double *out)
+{
+    if (!probe_args(s, mb, n) || !X || !W || !P || !KX || !KW || !KP || !m || !out) return PFEM_ERR_ARG;
+    PFEM_TRY(use_device(s));
+    const char *who = "pfem_modal_probe_gram";
+    const size_t rows = static_cast<size_t>(n), tile = kModalGramTile;
+    ProbeBlock B[6], bm;
+    const double *in[6] = {X, W, P, KX, KW, KP};
+    const char *names[6] = {"X", "W", "P", "KX", "KW", "KP"};
+    for (int k = 0; k < 6; ++k) PFEM_TRY(probe_upload(s, B[k], names[k], in[k], rows * mb, tile * mb));
+    PFEM_TRY(probe_upload(s, bm, "m", m, rows, tile));
+    DevBuf<double> part_gram, part_res, d_out;
+    PFEM_TRY(part_gram.alloc(static_cast<size_t>(kModalGramBlocks) * modal_gram_len(mb)));
+    PFEM_TRY(part_res.alloc(1));
+    PFEM_TRY(d_out.alloc(static_cast<size_t>(modal_out_len(mb))));
+    PFEM_HIP(hipMemsetAsync(d_out.p, 0, sizeof(double) * modal_out_len(mb), s->stream));
+    std::vector<double> h_out(static_cast<size_t>(modal_out_len(mb)));
+    ModalView V;
+    V.mb = mb;
+    V.n = n;
+    V.X = B[0].d.p; V.W = B[1].d.p; V.P = B[2].d.p; V.KX = B[3].d.p; V.KW = B[4].d.p; V.KP = B[5].d.p;
+    V.m = bm.d.p;
+    V.part_gram = part_gram.p; V.part_res = part_res.p; V.out = d_out.p;
+    V.h_out = h_out.data();
+    PFEM_TRY(modal_gram_to_host(s, V, true, 0));
+    for (int k = 0; k < 6; ++k) PFEM_TRY(probe_download(s, B[k], nullptr, who));
+    PFEM_TRY(probe_download(s, bm, nullptr, who));
+    std::memcpy(out, h_out.data(), sizeof(double) * modal_gram_len(mb));
+    return PFEM_OK;
+}
+
+// k_modal_residual<mb> on modal_vec_grid(n mb) blocks, then k_modal_sum: W and the 3 mb norms^2 (pfem_amd_diag.h)
+extern "C" int pfem_modal_probe_residual(pfem_solver *s, int mb, int64_t n, const double *KX, const double *X, const double *m, const double *dinv,
+                                         const double *theta, double *W_out, double *norms_out)
+{
+    if (!probe_args(s, mb, n) || !KX || !X || !m || !theta || !W_out || !norms_out) return PFEM_ERR_ARG;
+    PFEM_TRY(use_device(s));
+    const char *who = "pfem_modal_probe_residual";
+    const size_t rows = static_cast<size_t>(n), tile = kBlock / mb;
+    ProbeBlock bkx, bx, bw, bm, bd;
+    PFEM_TRY(probe_upload(s, bkx, "KX", KX, rows * mb, tile * mb));
+    PFEM_TRY(probe_upload(s, bx, "X", X, rows * mb, tile * mb));
+    PFEM_TRY(probe_upload(s, bw, "W", nullptr, rows * mb, tile * mb));
+    PFEM_TRY(probe_upload(s, bm, "m", m, rows, tile));
+    if (dinv) PFEM_TRY(probe_upload(s, bd, "dinv", dinv, rows, tile));
+    std::vector<double> h_coef(static_cast<size_t>(modal_coef_len(mb)), 0.0), h_out(static_cast<size_t>(modal_out_len(mb)));
+    std::memcpy(&h_coef[static_cast<size_t>(3 * mb * mb)], theta, sizeof(double) * mb);
+    DevBuf<double> coef, part_gram, part_res, d_out;
+    PFEM_TRY(coef.alloc(h_coef.size()));
+    PFEM_TRY(part_gram.alloc(1));
+    PFEM_TRY(part_res.alloc(static_cast<size_t>(kModalVecBlocks) * 3 * mb));
+    PFEM_TRY(d_out.alloc(h_out.size()));
+    PFEM_HIP(hipMemcpyAsync(coef.p, h_coef.data(), sizeof(double) * h_coef.size(), hipMemcpyHostToDevice, s->stream));
+    PFEM_HIP(hipMemsetAsync(d_out.p, 0, sizeof(double) * h_out.size(), s->stream));
+    ModalView V;
+    V.mb = mb;
+    V.n = n;
+    V.KX = bkx.d.p; V.X = bx.d.p; V.W = bw.d.p;
+    V.m = bm.d.p;
+    V.dinv = dinv ? bd.d.p : nullptr;
+    V.coef = coef.p; V.part_gram = part_gram.p; V.part_res = part_res.p; V.out = d_out.p;
+    V.h_out = h_out.data();
+    const unsigned gr = modal_residual(s, V, false);
+    PFEM_TRY(check_kernel("k_modal_residual"));
+    PFEM_TRY(modal_gram_to_host(s, V, false, gr));   // (waits for the stream: h_coef has been read)
+    PFEM_TRY(probe_download(s, bkx, nullptr, who));
+    PFEM_TRY(probe_download(s, bx, nullptr, who));
+    PFEM_TRY(probe_download(s, bw, W_out, who));
+    PFEM_TRY(probe_download(s, bm, nullptr, who));
+    if (dinv) PFEM_TRY(probe_download(s, bd, nullptr, who));
+    std::memcpy(norms_out, h_out.data() + modal_gram_len(mb), sizeof(double) * 3 * mb);
+    return PFEM_OK;
+}
+
+// k_modal_update<mb> on modal_update_grid(n, mb) blocks: the six blocks as the launch left them (pfem_amd_diag.h)
+extern "C" int pfem_modal_probe_update(pfem_solver *s, int mb, int64_t n, const double *coef, double *X, double *W, double *P, double *KX, double *KW, double *KP)
+{
+    if (!probe_args(s, mb, n) || !coef || !X || !W || !P || !KX || !KW || !KP) return PFEM_ERR_ARG;
+    PFEM_TRY(use_device(s));
+    const char *who = "pfem_modal_probe_update";
+    const size_t rows = static_cast<size_t>(n), tile = kBlock / mb;
+    ProbeBlock B[6];
+    double *io[6] = {X, W, P, KX, KW, KP};
+    const char *names[6] = {"X", "W", "P", "KX", "KW", "KP"};
+    for (int k = 0; k < 6; ++k) PFEM_TRY(probe_upload(s, B[k], names[k], io[k], rows * mb, tile * mb));
+    std::vector<double> h_coef(static_cast<size_t>(modal_coef_len(mb)), 0.0);
+    std::memcpy(h_coef.data(), coef, sizeof(double) * 3 * mb * mb);
+    DevBuf<double> d_coef;
+    PFEM_TRY(d_coef.alloc(h_coef.size()));
+    ModalView V;
+    V.mb = mb;
+    V.n = n;
+    V.X = B[0].d.p; V.W = B[1].d.p; V.P = B[2].d.p; V.KX = B[3].d.p; V.KW = B[4].d.p; V.KP = B[5].d.p;
+    V.coef = d_coef.p;
+    PFEM_TRY(modal_update(s, V, h_coef.data()));
+    for (int k = 0; k < 6; ++k) PFEM_TRY(probe_download(s, B[k], io[k], who));       // (each waits for the stream)
     return PFEM_OK;
 }
 

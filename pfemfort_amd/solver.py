@@ -774,6 +774,59 @@ class PetscSolver:
         L.check(L.lib().pfem_modal_spmm(self._h, X.shape[1], _p(X), _p(Y)), "pfem_modal_spmm")
         return Y
 
+    @staticmethod
+    def _blocks(blocks):
+        """contiguous float64 copies of blocks of one shape ``n x mb``, ``mb`` 4, 8 or 16"""
+        out = [np.array(b, dtype=np.float64, order="C", ndmin=2) for b in blocks]
+        n, mb = out[0].shape
+        if mb not in (4, 8, 16) or n < 1 or any(b.shape != (n, mb) for b in out):
+            raise ValueError(f"blocks of one shape n x 4 / 8 / 16 with n >= 1, not {[b.shape for b in out]}")
+        return out, n, mb
+
+    def modalProbeGram(self, X, W, P, KX, KW, KP, m):
+        """One launch of ``modalSolve``'s Gram kernel and of the sum of its partials on the six ``n x mb`` blocks and the ``n``
+        masses (``pfem_modal_probe_gram``): ``(G_K, G_M)``, ``3 mb x 3 mb`` each, ``S^T K S`` and ``S^T (m o S)`` for
+        ``S = [X W P]`` -- the upper block triangles, zeros below them."""
+        B, n, mb = self._blocks((X, W, P, KX, KW, KP))
+        m = _f64(m)
+        if m.shape != (n,):
+            raise ValueError(f"m must hold {n} doubles")
+        ns = 3 * mb
+        out = np.empty((2, ns, ns))
+        L.check(L.lib().pfem_modal_probe_gram(self._h, mb, n, *[_p(b) for b in B], _p(m), _p(out)), "pfem_modal_probe_gram")
+        return out[0], out[1]
+
+    def modalProbeResidual(self, KX, X, m, theta, dinv=None):
+        """One launch of ``modalSolve``'s residual kernel and of the sum of its partials (``pfem_modal_probe_residual``):
+        ``(W, norms)`` with ``W = dinv o (KX - (m o X) diag(theta))`` (without ``dinv``: the residual itself) and ``norms``
+        (``3 x mb``) the squared column norms of the residual, of ``KX`` and of ``m o X``."""
+        (KX, X), n, mb = self._blocks((KX, X))
+        m, theta = _f64(m), _f64(theta)
+        dinv = None if dinv is None else _f64(dinv)
+        if m.shape != (n,) or theta.shape != (mb,) or (dinv is not None and dinv.shape != (n,)):
+            raise ValueError(f"m and dinv must hold {n} doubles, theta {mb}")
+        W, norms = np.empty((n, mb)), np.empty((3, mb))
+        L.check(L.lib().pfem_modal_probe_residual(self._h, mb, n, _p(KX), _p(X), _p(m), _p(dinv), _p(theta), _p(W), _p(norms)),
+                "pfem_modal_probe_residual")
+        return W, norms
+
+    def modalProbeUpdate(self, coef, X, W, P, KX, KW, KP):
+        """One launch of ``modalSolve``'s update kernel with the coefficients ``coef`` (``3 mb x mb``: rows of X, of W, of P) on
+        copies of the six blocks (``pfem_modal_probe_update``): the six as the launch left them -- ``X, P, KX, KP`` updated,
+        ``W, KW`` as they stood on the device."""
+        B, n, mb = self._blocks((X, W, P, KX, KW, KP))
+        coef = _f64(coef)
+        if coef.shape != (3 * mb, mb):
+            raise ValueError(f"coef must be {3 * mb} x {mb}")
+        L.check(L.lib().pfem_modal_probe_update(self._h, mb, n, _p(coef), *[_p(b) for b in B]), "pfem_modal_probe_update")
+        return tuple(B)
+
+    def reordered(self):
+        """Whether the mesh on the device is held under the internal renumbering (``pfem_solver_reordered``)."""
+        v = C.c_int(0)
+        L.check(L.lib().pfem_solver_reordered(self._h, C.byref(v)), "pfem_solver_reordered")
+        return bool(v.value)
+
     def benchModalSpmm(self, mb, reps=50):
         """Microseconds of one block product of ``mb`` vectors and of ``mb`` single products (``pfem_modal_bench_spmm``)."""
         a = C.c_double(0); b = C.c_double(0)

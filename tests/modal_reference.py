@@ -174,6 +174,18 @@ def _lobpcg(A, m, n_modes, tol=1e-6, max_iterations=1000, block=0, x0=None, T=No
 
 
 # ---- what the tests measure, on both sides ---------------------------------------------------------------------------------------
+def lowest_modes(A, m, k):
+    """The lowest k pairs of (A, diag(m)) by shift-invert Lanczos about 0 (scipy's eigsh on a sparse LU of A, to its full
+    accuracy, from a fixed start vector): eigenvalues ascending and M-orthonormal vectors.  The reference where the dense eigh
+    of dynamics_reference.modes is out of reach."""
+    import scipy.sparse as sp
+    import scipy.sparse.linalg as spl
+    lam, V = spl.eigsh(sp.csc_matrix(A), k=k, M=sp.diags(m).tocsc(), sigma=0, which="LM", v0=np.ones(A.shape[0]))
+    order = np.argsort(lam)
+    lam, V = lam[order], V[:, order]
+    return lam, V / np.sqrt((m[:, None] * V * V).sum(0))[None, :]
+
+
 def eig_error(omega2, lam):
     """largest relative error of the eigenvalues against the dense ones"""
     k = len(omega2)

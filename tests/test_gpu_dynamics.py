@@ -6,6 +6,8 @@ The mirror runs on the K and the load the device holds (getCSR / getRHS, pinned 
 bound is computed here, for the mesh at hand: 16 x the figure the mirror itself reaches -- against the closed form, or, for a
 trajectory, against itself with every row's products added in reverse order.  The factor covers the one thing the device does
 differently: the SpMV adds a row in slices, with fma."""
+import os
+from contextlib import contextmanager
 from types import SimpleNamespace
 
 import numpy as np
@@ -13,11 +15,12 @@ import pytest
 import scipy.sparse as sp
 
 import dynamics_reference as DR
+import modal_reference as MO
 import pfemfort_amd as pf
 from pfemfort_amd import _lib as L
 from pfemfort_amd import drivers as D
 from pfemfort_amd import host as H
-from test_gpu_parity import _hub_mesh
+from test_gpu_parity import _hub_mesh, _shuffled
 
 pytestmark = pytest.mark.gpu
 
@@ -29,13 +32,34 @@ NAMES = ["tet10", "cook", "beam2", "hub", "hub_elast"]
 PLAIN = ["tet10", "cook", "beam2"]
 
 
+@contextmanager
+def reorder_env(value):
+    """PFEM_REORDER = value (None: unset) inside the block, as it was afterwards"""
+    old = os.environ.pop("PFEM_REORDER", None)
+    if value is not None:
+        os.environ["PFEM_REORDER"] = value
+    try:
+        yield
+    finally:
+        os.environ.pop("PFEM_REORDER", None)
+        if old is not None:
+            os.environ["PFEM_REORDER"] = old
+
+
 class Case:
-    """One mesh on the device, assembled, with its mass; the mirror's matrix, load, mass and modes -- made once."""
+    """One mesh on the device, assembled, with its mass; the mirror's matrix, load, mass and modes -- made once.  A name that
+    ends in _r: the mesh of that name under a random node numbering (test_gpu_parity._shuffled, seed 7), uploaded with
+    PFEM_REORDER=1, so that the library holds it renumbered; in _s: the same numbering with PFEM_REORDER unset, the
+    renumbering left to the library's own test."""
 
     def __init__(self, name, golden_dir):
         self.name = name
         self.table = self.ids = None
         self.density = 2.5
+        self.reorder = {"_r": "1", "_s": None}.get(name[-2:], False)       # False: the environment as it stands
+        if self.reorder is not False:
+            name = name[:-2]
+        self.base = name
         if name == "tet10":
             self.kind, self.ed, self.mesh = pf.POISSON_TET, ANISO, H.read_mesh(f"{golden_dir}/input/tet10")
         elif name == "cook":
@@ -45,20 +69,28 @@ class Case:
             self.ed = self.table = BEAM_TABLE
             self.ids = (self.mesh.xyz[1][self.mesh.conn].mean(0) > 2.0).astype(np.int32)
             self.density = np.array([3.0, 11.0])
+        elif name == "box19k":               # 19 656 dofs: beyond one pass of the modal kernels' capped grids (test_gpu_modal.py)
+            self.kind, self.ed, self.mesh = pf.POISSON_TET, ANISO, H.gen_box_tets(-1, 1, 28, -0.9, 0.9, 27, -0.8, 0.8, 29)
         elif name == "hub":
             self.kind, self.ed, self.mesh = pf.POISSON_TET, ANISO, _hub_mesh(300, 1)
         else:
             self.kind, self.ed, self.mesh = pf.ELAST_TET, H.ELAST_ELEMDATA, _hub_mesh(100, 3)
+        if self.reorder is not False:
+            self.plain_mesh, self.mesh = self.mesh, _shuffled(self.mesh, seed=7)
         self.ndof = L.NDOF[self.kind]
         self.dm, self.conn, self.xyz, edof = D._setup(self.kind, self.mesh)
         self.N = self.dm.size_global
         s = self.s = pf.PetscSolver().initialise(self.N, self.N)
-        s.uploadMesh(self.kind, self.conn, self.xyz, edof, self.dm.solnApplied)
+        if self.reorder is False:
+            s.uploadMesh(self.kind, self.conn, self.xyz, edof, self.dm.solnApplied)
+        else:
+            with reorder_env(self.reorder):
+                s.uploadMesh(self.kind, self.conn, self.xyz, edof, self.dm.solnApplied)
         if self.ids is not None:
             s.setMaterials(self.ids, n_mat=2, stride=6)
         s.buildPattern()
         s.assemble(self.ed, H.TIMEDATA)
-        if name == "cook":                   # a surface load and the nodal forces of the mesh's force file
+        if self.base == "cook":              # a surface load and the nodal forces of the mesh's force file
             fe, fs = s.boundaryFaces()
             on = np.all(self.xyz[0][s.surfaceGeometry(fe, fs)[2]] == 48.0, axis=0)
             s.addSurfaceLoad(fe[on], fs[on], "traction", [0.5, 6.25], elemData=self.ed)
@@ -76,8 +108,13 @@ class Case:
         self._modes = None
 
     def modes(self):
+        """(omega ascending, M-orthonormal vectors): all of them by dense eigh; of box19k the lowest 13 by shift-invert Lanczos"""
         if self._modes is None:
-            self._modes = DR.modes(self.A, self.m)
+            if self.base == "box19k":
+                lam, phi = MO.lowest_modes(self.A, self.m, 13)
+                self._modes = (np.sqrt(lam), phi)
+            else:
+                self._modes = DR.modes(self.A, self.m)
         return self._modes
 
     def mirror(self, A=None, **kw):
@@ -93,12 +130,15 @@ class Case:
 _CASES = {}
 
 
-@pytest.fixture
-def case(request, golden_dir):
-    name = request.param
+def get_case(name, golden_dir):
     if name not in _CASES:
         _CASES[name] = Case(name, golden_dir)
     return _CASES[name]
+
+
+@pytest.fixture
+def case(request, golden_dir):
+    return get_case(request.param, golden_dir)
 
 
 def rel(a, b):

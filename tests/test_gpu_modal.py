@@ -7,7 +7,11 @@ fma.  The eigenpairs: 16 x the figure the numpy mirror (tests/modal_reference.py
 tests/test_modal_reference.py) reaches at the same settings on the same K and m, with a floor of 1e-12 where the mirror's own
 figure is the rounding of the dense reference.  The factor covers what the device does differently: the order of its sums
 (fma, slices, blocks) and Jacobi sweeps where the mirror calls eigh, which also move the stopping iteration by one or two.
-max_iterations is 4 x the mirror's count: it only catches a stall."""
+max_iterations is 4 x the mirror's count: it only catches a stall.
+
+box19k (19 656 dofs; its reference is the lowest 13 pairs by eigsh, Case.modes) is the one mesh beyond one pass of the capped
+grids of k_modal_gram (8 192 rows), and at MB 16 of k_modal_update and k_modal_residual (16 384 rows): the solve there takes
+the later trips of their loops, which tests/test_gpu_modal_kernels.py checks a launch at a time."""
 import numpy as np
 import pytest
 
@@ -26,7 +30,7 @@ EPS = np.finfo(np.float64).eps
 FLOOR = 1e-12
 # fixture -> (n_modes, tol) of the eigenpair checks
 SETTINGS = [("tet10", 2, 1e-9), ("tet10", 6, 1e-9), ("tet10", 12, 1e-9), ("cook", 6, 1e-6), ("beam2", 6, 1e-6), ("hub", 2, 1e-6),
-            ("hub_elast", 2, 1e-6)]
+            ("hub_elast", 2, 1e-6), ("box19k", 12, 1e-6), ("box19k", 2, 1e-6)]
 
 _MIRROR, _DEVICE = {}, {}
 
@@ -54,12 +58,7 @@ def device_of(c, n_modes, tol):
 
 
 # ---- the block product -------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("mb", [4, 8, 16])
-@pytest.mark.parametrize("case", NAMES, indirect=True)
-def test_block_product_against_the_csr(case, mb):
-    c = case
-    if c.name in ("tet10", "hub"):          # a partial last slice (cook, beam2 and hub_elast have 33, 9 and 4 full ones)
-        assert c.N % 64 != 0
+def check_block_product(c, mb):
     rng = np.random.default_rng(40 + mb)
     X = rng.standard_normal((c.N, mb))
     got = c.s.modalSpmm(X)
@@ -75,10 +74,18 @@ def test_block_product_against_the_csr(case, mb):
     assert (np.abs(Y0 - c.A @ X0) <= (rowlen * EPS)[:, None] * (abs(c.A) @ np.abs(X0))).all()
 
 
-# ---- eigenpairs ----------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case,n_modes,tol", SETTINGS, indirect=["case"])
-def test_lowest_modes_against_dense_eigh(case, n_modes, tol):
+@pytest.mark.parametrize("mb", [4, 8, 16])
+@pytest.mark.parametrize("case", NAMES + ["box19k"], indirect=True)
+def test_block_product_against_the_csr(case, mb):
     c = case
+    if c.name in ("tet10", "hub"):          # a partial last slice (cook, beam2 and hub_elast have 33, 9 and 4 full ones)
+        assert c.N % 64 != 0
+    check_block_product(c, mb)
+
+
+# ---- eigenpairs ----------------------------------------------------------------------------------------------------------------------
+def check_lowest_modes(c, n_modes, tol):
+    """the device's run at these settings against the reference pairs of its own K and m, within the bounds of the docstring"""
     om, phi = c.modes()
     mir = mirror_of(c, n_modes, tol)
     r = device_of(c, n_modes, tol)
@@ -100,6 +107,12 @@ def test_lowest_modes_against_dense_eigh(case, n_modes, tol):
     # the residuals are those of the returned pairs (an explicit product on the host)
     _, res = MO.residuals(c.A @ r.modes, r.modes, c.m, r.omega2)
     assert np.abs(res - r.residuals).max() <= 1e-3 * tol + 64 * c.N * EPS
+    return r
+
+
+@pytest.mark.parametrize("case,n_modes,tol", SETTINGS, indirect=["case"])
+def test_lowest_modes_against_dense_eigh(case, n_modes, tol):
+    check_lowest_modes(case, n_modes, tol)
 
 
 # ---- reproducibility -------------------------------------------------------------------------------------------------------------------
