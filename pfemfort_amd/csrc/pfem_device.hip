@@ -3598,6 +3598,38 @@ extern "C" int pfem_bench_spmv(pfem_solver *s, int reps, double *ms_per_launch)
 // ---------------------------------------------------------------------------
 namespace {
 
+// The one pass that sums a per-element quantity onto the nodes (nodal forces, nodal recovery, lumped mass), enqueued only.
+// Gather form -- incidence records exist: `gather_launch(kind, grid, hubs)` launches the feature's one-thread-per-node kernel;
+// then the hub nodes, which have no records, are summed by `scatter_launch(kind, grid, hubs)`, the feature's element pass
+// restricted to them.  Scatter form: `zero` (the output arrays with their lengths) is cleared and
+// `scatter_launch(kind, grid, nullptr)` adds to every node.  `what` names the feature in a launch error.
+struct NodePass {
+    bool gather;                // the nodes' own threads stored their sums
+    const uint8_t *hubs;        // the flags of the nodes the element pass summed after a gather; nullptr: none, or (scatter) all
+};
+template <class G, class S>
+int node_accumulate(pfem_solver *s, const char *what, std::initializer_list<std::pair<double *, int64_t>> zero, G &&gather_launch,
+                    S &&scatter_launch, NodePass *done = nullptr)
+{
+    const MeshDev &m = s->mesh;
+    const bool gather = m.nElem > 0 && s->assembly_mode == PFEM_ASSEMBLY_GATHER && s->have_incidence && s->d_inc_rec.p;
+    const uint8_t *hubs = (gather && s->n_hubs > 0) ? s->d_node_hub.p : nullptr;
+    if (done) *done = NodePass{gather, hubs};
+    if (gather) {
+        // one writer per entry, no atomics
+        with_kind(m.kind, [&](auto kind) { gather_launch(kind, dim3(grid_for(m.nNode)), hubs); });
+        PFEM_TRY(check_kernel((std::string(what) + "_gather").c_str()));
+    } else {
+        for (const auto &z : zero) PFEM_HIP(hipMemsetAsync(z.first, 0, sizeof(double) * static_cast<size_t>(std::max<int64_t>(z.second, 1)), s->stream));
+    }
+    if (m.nElem > 0 && (!gather || hubs)) {
+        // f64 atomics: the whole mesh, or the hub nodes only
+        with_kind(m.kind, [&](auto kind) { scatter_launch(kind, dim3(grid_for(m.nElem)), hubs); });
+        PFEM_TRY(check_kernel((std::string(what) + "_scatter").c_str()));
+    }
+    return PFEM_OK;
+}
+
 // The nodal field [node * ndof + d] on the device, in the DEVICE's node order: the caller's array (caller's node numbering), or
 // -- u_nodal == NULL -- the field of the last solve: x at the free dofs, solnApplied at the constrained ones.
 int post_nodal_field(pfem_solver *s, const double *u_nodal, DevBuf<double> &u, const char *who)
@@ -3637,30 +3669,22 @@ int post_recovery_launch(pfem_solver *s, const PRM &prm, const double *up, int u
 {
     const MeshDev &m = s->mesh;
     const int64_t nn = m.nNode;
-    const int ng = post_components(m.kind);
-    const bool gather = m.nElem > 0 && s->assembly_mode == PFEM_ASSEMBLY_GATHER && s->have_incidence && s->d_inc_rec.p;
-    const uint8_t *hubs = (gather && s->n_hubs > 0) ? s->d_node_hub.p : nullptr;
-    const dim3 ngrid(grid_for(nn)), egrid(grid_for(m.nElem)), block(kBlock);
-    if (gather) {
-        with_kind(m.kind, [&](auto kind) {
-            launch(k_post_recovery_gather<decltype(kind)::value, PRM>, ngrid, block, 0, s->stream, nullptr, nullptr, m, prm, s->d_inc_ptr.p, s->d_inc_cnt.p,
+    const dim3 block(kBlock);
+    NodePass pass;
+    PFEM_TRY(node_accumulate(
+        s, "k_post_recovery", {{nodal, nn * post_components(m.kind)}, {weight, nn}},
+        [&](auto kind, dim3 grid, const uint8_t *hubs) {
+            launch(k_post_recovery_gather<decltype(kind)::value, PRM>, grid, block, 0, s->stream, nullptr, nullptr, m, prm, s->d_inc_ptr.p, s->d_inc_cnt.p,
                    s->d_inc_rec.p, hubs, up, use_grad, nodal, nscalar, weight, s->d_err.p);
-        });
-        PFEM_TRY(check_kernel("k_post_recovery_gather"));
-        if (!hubs) return PFEM_OK;
-    } else {
-        PFEM_HIP(hipMemsetAsync(nodal, 0, sizeof(double) * static_cast<size_t>(std::max<int64_t>(nn * ng, 1)), s->stream));
-        PFEM_HIP(hipMemsetAsync(weight, 0, sizeof(double) * static_cast<size_t>(std::max<int64_t>(nn, 1)), s->stream));
-    }
-    if (m.nElem > 0) {
-        with_kind(m.kind, [&](auto kind) {
-            launch(k_post_recovery_scatter<decltype(kind)::value, PRM>, egrid, block, 0, s->stream, nullptr, nullptr, m, prm, hubs, up, use_grad, nodal, weight,
+        },
+        [&](auto kind, dim3 grid, const uint8_t *hubs) {
+            launch(k_post_recovery_scatter<decltype(kind)::value, PRM>, grid, block, 0, s->stream, nullptr, nullptr, m, prm, hubs, up, use_grad, nodal, weight,
                    s->d_err.p);
-        });
-        PFEM_TRY(check_kernel("k_post_recovery_scatter"));
-    }
+        },
+        &pass));
+    if (pass.gather && !pass.hubs) return PFEM_OK;      // every node's thread has divided
     with_kind(m.kind, [&](auto kind) {
-        launch(k_post_recovery_divide<decltype(kind)::value>, ngrid, block, 0, s->stream, nullptr, nullptr, nn, hubs, weight, nodal, nscalar);
+        launch(k_post_recovery_divide<decltype(kind)::value>, dim3(grid_for(nn)), block, 0, s->stream, nullptr, nullptr, nn, pass.hubs, weight, nodal, nscalar);
     });
     return check_kernel("k_post_recovery_divide");
 }
@@ -3738,30 +3762,20 @@ extern "C" int pfem_post_nodal_forces(pfem_solver *s, const double *elemData, co
     PFEM_TRY(post_nodal_field(s, u_nodal, u, "pfem_post_nodal_forces"));
     return with_elem_prm(s, elemData, timeData, [&](const auto &prm) -> int {
         using PRM = std::decay_t<decltype(prm)>;
-        const int64_t nn = m.nNode, nv = nn * m.ndof;
-        PFEM_TRY(dR.alloc(static_cast<size_t>(std::max<int64_t>(nv, 1))));
-        const bool gather = m.nElem > 0 && s->assembly_mode == PFEM_ASSEMBLY_GATHER && s->have_incidence && s->d_inc_rec.p;
-        const uint8_t *hubs = (gather && s->n_hubs > 0) ? s->d_node_hub.p : nullptr;
+        const int64_t nv = m.nNode * m.ndof;
         const dim3 block(kBlock);
+        PFEM_TRY(dR.alloc(static_cast<size_t>(std::max<int64_t>(nv, 1))));
         PFEM_HIP(hipMemsetAsync(s->d_err.p, 0, sizeof(int), s->stream));
         PFEM_HIP(hipEventRecord(s->ev0, s->stream));
-        if (!gather) PFEM_HIP(hipMemsetAsync(dR.p, 0, sizeof(double) * static_cast<size_t>(std::max<int64_t>(nv, 1)), s->stream));
-        if (gather) {
-            // one thread per node, no atomics: every entry of R is stored by its node's thread
-            with_kind(m.kind, [&](auto kind) {
-                launch(k_post_forces_gather<decltype(kind)::value, PRM>, dim3(grid_for(nn)), block, 0, s->stream, nullptr, nullptr, m, prm, s->d_inc_ptr.p,
-                       s->d_inc_cnt.p, s->d_inc_rec.p, hubs, u.p, dR.p, s->d_err.p);
-            });
-            PFEM_TRY(check_kernel("k_post_forces_gather"));
-        }
-        if (m.nElem > 0 && (!gather || hubs)) {
-            // one thread per element, f64 atomics: the whole mesh (scatter form, no incidence records), or the hub nodes only
-            with_kind(m.kind, [&](auto kind) {
-                launch(k_post_forces_scatter<decltype(kind)::value, PRM>, dim3(grid_for(m.nElem)), block, 0, s->stream, nullptr, nullptr, m, prm, hubs, u.p,
-                       dR.p, s->d_err.p);
-            });
-            PFEM_TRY(check_kernel("k_post_forces_scatter"));
-        }
+        PFEM_TRY(node_accumulate(
+            s, "k_post_forces", {{dR.p, nv}},
+            [&](auto kind, dim3 grid, const uint8_t *hubs) {
+                launch(k_post_forces_gather<decltype(kind)::value, PRM>, grid, block, 0, s->stream, nullptr, nullptr, m, prm, s->d_inc_ptr.p, s->d_inc_cnt.p,
+                       s->d_inc_rec.p, hubs, u.p, dR.p, s->d_err.p);
+            },
+            [&](auto kind, dim3 grid, const uint8_t *hubs) {
+                launch(k_post_forces_scatter<decltype(kind)::value, PRM>, grid, block, 0, s->stream, nullptr, nullptr, m, prm, hubs, u.p, dR.p, s->d_err.p);
+            }));
         PFEM_HIP(hipEventRecord(s->ev1, s->stream));
         int err = 0;
         PFEM_TRY(fetch_err(s, &err));

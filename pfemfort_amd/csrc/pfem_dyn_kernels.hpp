@@ -12,15 +12,13 @@ namespace pfem {
 // ---------------------------------------------------------------------------
 // lumped mass per node, in the device's node order
 // ---------------------------------------------------------------------------
-// density of element e / of the visit at position t of the incidence records: one value, or one per material row
+// density at an element or a visit (AtElem / AtVisit): one value, or one per material row
 struct DynDens {
     const double *tab;          // [n_mat] on the device, nullptr: `one`
     double one;
 };
-__device__ __forceinline__ double dens_elem(const ElemPrm &, const DynDens &d, int64_t) { return d.one; }
-__device__ __forceinline__ double dens_elem(const ElemPrmTab &p, const DynDens &d, int64_t e) { return d.tab[p.elem_mat[e]]; }
-__device__ __forceinline__ double dens_visit(const ElemPrm &, const DynDens &d, int64_t) { return d.one; }
-__device__ __forceinline__ double dens_visit(const ElemPrmTab &p, const DynDens &d, int64_t t) { return d.tab[p.inc_mat[t]]; }
+template <class AT> __device__ __forceinline__ double dens_at(const ElemPrm &, const DynDens &d, AT) { return d.one; }
+template <class AT> __device__ __forceinline__ double dens_at(const ElemPrmTab &p, const DynDens &d, AT at) { return d.tab[prm_mat(p, at)]; }
 
 template <int KIND>
 __device__ __forceinline__ void dyn_load_xyz(const MeshDev &m, const int nd[4], double x[4], double y[4], double z[4])
@@ -60,7 +58,7 @@ __global__ void __launch_bounds__(kBlock) k_dyn_mass_gather(MeshDev m, PRM prm, 
         }
         double x[4], y[4], z[4], Mn[4];
         dyn_load_xyz<KIND>(m, nd, x, y, z);
-        if (!elem_lumped_mass(KIND, x, y, z, prm_visit(prm, t), dens_visit(prm, dens, t), Mn)) { atomicMax(err, PFEM_ERR_NEG_JAC); continue; }
+        if (!elem_lumped_mass(KIND, x, y, z, prm_at(prm, AtVisit{t}), dens_at(prm, dens, AtVisit{t}), Mn)) { atomicMax(err, PFEM_ERR_NEG_JAC); continue; }
 #pragma unroll
         for (int i = 0; i < P::NPE; ++i)
             if (i == a) acc += Mn[i];
@@ -87,7 +85,7 @@ __global__ void __launch_bounds__(kBlock) k_dyn_mass_scatter(MeshDev m, PRM prm,
     if (!any) return;
     double x[4], y[4], z[4], Mn[4];
     dyn_load_xyz<KIND>(m, nd, x, y, z);
-    if (!elem_lumped_mass(KIND, x, y, z, prm_elem(prm, e), dens_elem(prm, dens, e), Mn)) { atomicMax(err, PFEM_ERR_NEG_JAC); return; }
+    if (!elem_lumped_mass(KIND, x, y, z, prm_at(prm, AtElem{e}), dens_at(prm, dens, AtElem{e}), Mn)) { atomicMax(err, PFEM_ERR_NEG_JAC); return; }
 #pragma unroll
     for (int a = 0; a < P::NPE; ++a) {
         if (only_nodes && !only_nodes[nd[a]]) continue;

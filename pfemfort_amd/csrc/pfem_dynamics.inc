@@ -117,26 +117,18 @@ extern "C" int pfem_dynamics_setup(pfem_solver *s, const double *elemData, const
     }
     const int rc = with_elem_prm(s, elemData, nullptr, [&](const auto &prm) -> int {
         using PRM = std::decay_t<decltype(prm)>;
-        const bool gather = m.nElem > 0 && s->assembly_mode == PFEM_ASSEMBLY_GATHER && s->have_incidence && s->d_inc_rec.p;
-        const uint8_t *hubs = (gather && s->n_hubs > 0) ? s->d_node_hub.p : nullptr;
         const dim3 block(kBlock);
         PFEM_HIP(hipMemsetAsync(s->d_err.p, 0, sizeof(int), s->stream));
-        if (gather) {
-            with_kind(m.kind, [&](auto kind) {
-                launch(k_dyn_mass_gather<decltype(kind)::value, PRM>, dim3(grid_for(nn)), block, 0, s->stream, nullptr, nullptr, m, prm, dens, s->d_inc_ptr.p,
-                       s->d_inc_cnt.p, s->d_inc_rec.p, hubs, D->d_mnode.p, s->d_err.p);
-            });
-            PFEM_TRY(check_kernel("k_dyn_mass_gather"));
-        } else {
-            PFEM_HIP(hipMemsetAsync(D->d_mnode.p, 0, sizeof(double) * static_cast<size_t>(std::max<int64_t>(nn, 1)), s->stream));
-        }
-        if (m.nElem > 0 && (!gather || hubs)) {
-            with_kind(m.kind, [&](auto kind) {
-                launch(k_dyn_mass_scatter<decltype(kind)::value, PRM>, dim3(grid_for(m.nElem)), block, 0, s->stream, nullptr, nullptr, m, prm, dens, hubs,
-                       D->d_mnode.p, s->d_err.p);
-            });
-            PFEM_TRY(check_kernel("k_dyn_mass_scatter"));
-        }
+        PFEM_TRY(node_accumulate(
+            s, "k_dyn_mass", {{D->d_mnode.p, nn}},
+            [&](auto kind, dim3 grid, const uint8_t *hubs) {
+                launch(k_dyn_mass_gather<decltype(kind)::value, PRM>, grid, block, 0, s->stream, nullptr, nullptr, m, prm, dens, s->d_inc_ptr.p, s->d_inc_cnt.p,
+                       s->d_inc_rec.p, hubs, D->d_mnode.p, s->d_err.p);
+            },
+            [&](auto kind, dim3 grid, const uint8_t *hubs) {
+                launch(k_dyn_mass_scatter<decltype(kind)::value, PRM>, grid, block, 0, s->stream, nullptr, nullptr, m, prm, dens, hubs, D->d_mnode.p,
+                       s->d_err.p);
+            }));
         if (m.nElem > 0) {
             launch(k_dyn_mass_rows, dim3(grid_for(m.nElem * m.nsize)), block, 0, s->stream, nullptr, nullptr, m, D->d_mnode.p, D->d_m.p, D->d_minv.p);
             PFEM_TRY(check_kernel("k_dyn_mass_rows"));

@@ -62,11 +62,33 @@ struct ElemPrmTab {
 };
 template <class PRM> struct PrmTraits { static constexpr bool kTab = false; };
 template <> struct PrmTraits<ElemPrmTab> { static constexpr bool kTab = true; };
-// elemData of element e / of the visit at position t of the incidence records
-__device__ __forceinline__ const double *prm_elem(const ElemPrm &p, int64_t) { return p.ed; }
-__device__ __forceinline__ const double *prm_elem(const ElemPrmTab &p, int64_t e) { return p.tab + p.stride * static_cast<int>(p.elem_mat[e]); }
-__device__ __forceinline__ const double *prm_visit(const ElemPrm &p, int64_t) { return p.ed; }
-__device__ __forceinline__ const double *prm_visit(const ElemPrmTab &p, int64_t t) { return p.tab + p.stride * static_cast<int>(p.inc_mat[t]); }
+// Where a kernel evaluates an element from: element e of the mesh, or the visit at position t of the incidence records
+struct AtElem { int64_t e; };
+struct AtVisit { int64_t t; };
+__device__ __forceinline__ uint8_t prm_mat(const ElemPrmTab &p, AtElem at) { return p.elem_mat[at.e]; }
+__device__ __forceinline__ uint8_t prm_mat(const ElemPrmTab &p, AtVisit at) { return p.inc_mat[at.t]; }
+// elemData there
+template <class AT> __device__ __forceinline__ const double *prm_at(const ElemPrm &p, AT) { return p.ed; }
+template <class AT> __device__ __forceinline__ const double *prm_at(const ElemPrmTab &p, AT at) { return p.tab + p.stride * static_cast<int>(prm_mat(p, at)); }
+
+// The node numbers of one visit of node n from its 16-byte incidence record: rc.x, rc.y, rc.z are the element's other nodes in
+// the element's order, and the sign bits of rc.x and rc.y spell the place a that n itself has there (k_build_inc_rec).
+__device__ __forceinline__ int inc_rec_place(const int4 &rc)
+{
+    return static_cast<int>((static_cast<uint32_t>(rc.x) >> 31) | ((static_cast<uint32_t>(rc.y) >> 31) << 1));
+}
+template <int NPE>
+__device__ __forceinline__ int inc_rec_nodes(const int4 &rc, int64_t n, int nd[NPE])
+{
+    const int a = inc_rec_place(rc);
+    const int o[3] = {rc.x & 0x7fffffff, rc.y & 0x7fffffff, rc.z};
+#pragma unroll
+    for (int i = 0; i < NPE; ++i) {
+        const int q = i < a ? i : (i > 0 ? i - 1 : 0);
+        nd[i] = (i == a) ? static_cast<int>(n) : o[q];
+    }
+    return a;
+}
 
 // ---------------------------------------------------------------------------
 // wave / block reductions (wave = 64 lanes)
@@ -441,7 +463,7 @@ __global__ void __launch_bounds__(kBlock) k_assemble_scalar(MeshDev m, SellDev A
     }
     double K[NPE * NPE], F[NPE];
     const double valC[4] = {0.0, 0.0, 0.0, 0.0};   // drivers pass valC = 0 (:824)
-    const double *ed = prm_elem(prm, e);
+    const double *ed = prm_at(prm, AtElem{e});
     bool ok;
     if constexpr (KIND == PFEM_POISSON_TET)
         ok = poisson_tet(x, y, z, ed[0], ed[1], ed[2], prm.af, valC, K, F);
@@ -501,7 +523,7 @@ __global__ void __launch_bounds__(kBlock) k_assemble_elast(MeshDev m, SellDev A,
     tet_geometry(x, y, z, g);
     if (g.jac < 0.0) { atomicMax(err, PFEM_ERR_NEG_JAC); return; }
     const double dvol = kGaussWtTet * g.jac;
-    const double *ed = prm_elem(prm, e);
+    const double *ed = prm_at(prm, AtElem{e});
     const ElastMat mat = elast_material(ed[0], ed[1]);
     double F[12];
 #pragma unroll
@@ -1069,7 +1091,7 @@ __global__ void __launch_bounds__(kBlock) k_gather_scalar(MeshDev m, SellDev A, 
     for (int64_t t = beg; t < end; t += 64) {
         const int4 rc = inc_rec[t];
         const uint32_t slots = static_cast<uint32_t>(rc.w);
-        const int a = static_cast<int>((static_cast<uint32_t>(rc.x) >> 31) | ((static_cast<uint32_t>(rc.y) >> 31) << 1));
+        const int a = inc_rec_place(rc);
         const int o[3] = {rc.x & 0x7fffffff, rc.y & 0x7fffffff, rc.z};
         int nd[NPE];
         bool fixed[NPE];
@@ -1088,7 +1110,7 @@ __global__ void __launch_bounds__(kBlock) k_gather_scalar(MeshDev m, SellDev A, 
         }
         // this node's entries of the element: Klocal(a,:) for the lifting, Klocal(:,a) for the row
         double Krow[NPE], Kcol[NPE], f = 0.0;
-        const double *ed = prm_visit(prm, t);
+        const double *ed = prm_at(prm, AtVisit{t});
         bool ok;
         if constexpr (KIND == PFEM_POISSON_TET) {
             bool any_fixed = false;
@@ -1386,7 +1408,7 @@ __global__ void __launch_bounds__(kBlock) k_gather_elast_rows(MeshDev m, SellDev
         const int4 rc = rp[static_cast<int64_t>(v) * rstep];
         const uint32_t flags = fp[static_cast<int64_t>(v) * rstep];
         const uint32_t slots = static_cast<uint32_t>(rc.w);
-        const int a = static_cast<int>((static_cast<uint32_t>(rc.x) >> 31) | ((static_cast<uint32_t>(rc.y) >> 31) << 1));
+        const int a = inc_rec_place(rc);
         const int o[3] = {rel ? incpat_node(rc.x, static_cast<int>(n)) : (rc.x & 0x7fffffff),
                           rel ? incpat_node(rc.y, static_cast<int>(n)) : (rc.y & 0x7fffffff), rel ? static_cast<int>(n) + rc.z : rc.z};
         int nd[4];
@@ -1473,7 +1495,7 @@ __global__ void __launch_bounds__(kBlock) k_assemble_elast2d(MeshDev m, SellDev 
     TriaGeom g;
     tria_geometry(x, y, g);
     if (g.jac < 0.0) { atomicMax(err, PFEM_ERR_NEG_JAC); return; }
-    const double *ed = prm_elem(prm, e);
+    const double *ed = prm_at(prm, AtElem{e});
     const double dvol = 0.5 * (g.jac * ed[2]);
     const Elast2dMat mat = elast2d_material(ed[0], ed[1]);
     double N[3], F[6], fact[6];
@@ -1558,7 +1580,7 @@ __global__ void __launch_bounds__(kBlock) k_gather_elast2d_rows(MeshDev m, SellD
     double facc = 0.0;
     for (int64_t t = beg; t < end; t += 64) {
         if constexpr (PrmTraits<PRM>::kTab) {
-            const double *ed = prm_visit(prm, t);
+            const double *ed = prm_at(prm, AtVisit{t});
             mat = elast2d_material(ed[0], ed[1]);
             bf = p == 0 ? ed[3] : ed[4];
             thick = ed[2];
@@ -1566,7 +1588,7 @@ __global__ void __launch_bounds__(kBlock) k_gather_elast2d_rows(MeshDev m, SellD
         const int4 rc = inc_rec[t];
         const uint32_t flags = inc_flags[t];
         const uint32_t slots = static_cast<uint32_t>(rc.w);
-        const int a = static_cast<int>((static_cast<uint32_t>(rc.x) >> 31) | ((static_cast<uint32_t>(rc.y) >> 31) << 1));
+        const int a = inc_rec_place(rc);
         const int o0 = rc.x & 0x7fffffff, o1 = rc.y & 0x7fffffff, me = static_cast<int>(n);
         const int nd[3] = {a == 0 ? me : o0, a == 0 ? o0 : (a == 1 ? me : o1), a == 2 ? me : o1};
         double x[3], y[3];
@@ -1627,7 +1649,7 @@ __global__ void __launch_bounds__(kBlock) k_eval_elems(MeshDev m, PRM prm, doubl
     }
     const double valC[4] = {0.0, 0.0, 0.0, 0.0};
     double *K = Kout + e * m.nsize * m.nsize, *F = Fout + e * m.nsize;
-    const double *ed = prm_elem(prm, e);
+    const double *ed = prm_at(prm, AtElem{e});
     bool ok = false;
     switch (m.kind) {
     case PFEM_POISSON_TET: ok = poisson_tet(x, y, z, ed[0], ed[1], ed[2], prm.af, valC, K, F); break;
@@ -1711,7 +1733,7 @@ __global__ void __launch_bounds__(kBlock) k_post_elements(MeshDev m, PRM prm, co
     for (int a = 0; a < P::NPE; ++a) nd[a] = m.conn[a * m.nElem + e];
     double x[4], y[4], z[4], valC[12], g[6], f[6], fint[12], sc, dvol;
     post_load_elem<KIND>(m, nd, u, x, y, z, valC);
-    if (!elem_post(KIND, x, y, z, prm_elem(prm, e), valC, g, f, sc, fint, dvol)) { atomicMax(err, PFEM_ERR_NEG_JAC); return; }
+    if (!elem_post(KIND, x, y, z, prm_at(prm, AtElem{e}), valC, g, f, sc, fint, dvol)) { atomicMax(err, PFEM_ERR_NEG_JAC); return; }
 #pragma unroll
     for (int c = 0; c < P::NG; ++c) {
         if (grad) grad[c * m.nElem + e] = g[c];
@@ -1741,18 +1763,11 @@ __global__ void __launch_bounds__(kBlock) k_post_forces_gather(MeshDev m, PRM pr
     const int cnt = (node_hub && node_hub[n]) ? 0 : inc_cnt[n];
     const int64_t beg = inc_ptr[n >> 6] + (n & 63), end = beg + 64LL * cnt;
     for (int64_t t = beg; t < end; t += 64) {
-        const int4 rc = inc_rec[t];
-        const int a = static_cast<int>((static_cast<uint32_t>(rc.x) >> 31) | ((static_cast<uint32_t>(rc.y) >> 31) << 1));
-        const int o[3] = {rc.x & 0x7fffffff, rc.y & 0x7fffffff, rc.z};
         int nd[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (int i = 0; i < P::NPE; ++i) {
-            const int q = i < a ? i : (i > 0 ? i - 1 : 0);
-            nd[i] = (i == a) ? static_cast<int>(n) : o[q];
-        }
+        const int a = inc_rec_nodes<P::NPE>(inc_rec[t], n, nd);
         double x[4], y[4], z[4], valC[12], r[12];
         post_load_elem<KIND>(m, nd, u, x, y, z, valC);
-        if (!elem_nodal_forces(KIND, x, y, z, prm_visit(prm, t), prm.af, valC, r)) { atomicMax(err, PFEM_ERR_NEG_JAC); continue; }
+        if (!elem_nodal_forces(KIND, x, y, z, prm_at(prm, AtVisit{t}), prm.af, valC, r)) { atomicMax(err, PFEM_ERR_NEG_JAC); continue; }
 #pragma unroll
         for (int i = 0; i < P::NPE; ++i)
             if (i == a) {
@@ -1783,7 +1798,7 @@ __global__ void __launch_bounds__(kBlock) k_post_forces_scatter(MeshDev m, PRM p
     if (!any) return;
     double x[4], y[4], z[4], valC[12], r[12];
     post_load_elem<KIND>(m, nd, u, x, y, z, valC);
-    if (!elem_nodal_forces(KIND, x, y, z, prm_elem(prm, e), prm.af, valC, r)) { atomicMax(err, PFEM_ERR_NEG_JAC); return; }
+    if (!elem_nodal_forces(KIND, x, y, z, prm_at(prm, AtElem{e}), prm.af, valC, r)) { atomicMax(err, PFEM_ERR_NEG_JAC); return; }
 #pragma unroll
     for (int a = 0; a < P::NPE; ++a) {
         if (only_nodes && !only_nodes[nd[a]]) continue;
@@ -1814,18 +1829,11 @@ __global__ void __launch_bounds__(kBlock) k_post_recovery_gather(MeshDev m, PRM 
     const int cnt = (node_hub && node_hub[n]) ? 0 : inc_cnt[n];
     const int64_t beg = inc_ptr[n >> 6] + (n & 63), end = beg + 64LL * cnt;
     for (int64_t t = beg; t < end; t += 64) {
-        const int4 rc = inc_rec[t];
-        const int a = static_cast<int>((static_cast<uint32_t>(rc.x) >> 31) | ((static_cast<uint32_t>(rc.y) >> 31) << 1));
-        const int o[3] = {rc.x & 0x7fffffff, rc.y & 0x7fffffff, rc.z};
         int nd[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (int i = 0; i < P::NPE; ++i) {
-            const int q = i < a ? i : (i > 0 ? i - 1 : 0);
-            nd[i] = (i == a) ? static_cast<int>(n) : o[q];
-        }
+        inc_rec_nodes<P::NPE>(inc_rec[t], n, nd);
         double x[4], y[4], z[4], valC[12], g[6], f[6], fint[12], sc, dvol;
         post_load_elem<KIND>(m, nd, u, x, y, z, valC);
-        if (!elem_post(KIND, x, y, z, prm_visit(prm, t), valC, g, f, sc, fint, dvol)) { atomicMax(err, PFEM_ERR_NEG_JAC); continue; }
+        if (!elem_post(KIND, x, y, z, prm_at(prm, AtVisit{t}), valC, g, f, sc, fint, dvol)) { atomicMax(err, PFEM_ERR_NEG_JAC); continue; }
 #pragma unroll
         for (int c = 0; c < P::NG; ++c) acc[c] += dvol * (use_grad ? g[c] : f[c]);
         wsum += dvol;
@@ -1861,7 +1869,7 @@ __global__ void __launch_bounds__(kBlock) k_post_recovery_scatter(MeshDev m, PRM
     if (!any) return;
     double x[4], y[4], z[4], valC[12], g[6], f[6], fint[12], sc, dvol;
     post_load_elem<KIND>(m, nd, u, x, y, z, valC);
-    if (!elem_post(KIND, x, y, z, prm_elem(prm, e), valC, g, f, sc, fint, dvol)) { atomicMax(err, PFEM_ERR_NEG_JAC); return; }
+    if (!elem_post(KIND, x, y, z, prm_at(prm, AtElem{e}), valC, g, f, sc, fint, dvol)) { atomicMax(err, PFEM_ERR_NEG_JAC); return; }
 #pragma unroll
     for (int a = 0; a < P::NPE; ++a) {
         if (only_nodes && !only_nodes[nd[a]]) continue;
@@ -1911,7 +1919,7 @@ __global__ void __launch_bounds__(kBlock) k_post_indicator(MeshDev m, PRM prm, c
         for (int a = 0; a < P::NPE; ++a)
 #pragma unroll
             for (int c = 0; c < P::NG; ++c) nf[a * P::NG + c] = nodal[static_cast<int64_t>(nd[a]) * P::NG + c];
-        if (!elem_recovery_error(KIND, x, y, z, prm_elem(prm, e), valC, nf, e2, f2)) { atomicMax(err, PFEM_ERR_NEG_JAC); continue; }
+        if (!elem_recovery_error(KIND, x, y, z, prm_at(prm, AtElem{e}), valC, nf, e2, f2)) { atomicMax(err, PFEM_ERR_NEG_JAC); continue; }
         if (eta2) eta2[e] = e2;
         se += e2;
         sf += f2;
@@ -2099,7 +2107,7 @@ __global__ void __launch_bounds__(kBlock) k_surface_load(MeshDev m, PRM prm, int
 #pragma unroll
         for (int a = 0; a < NS; ++a) v[a] = values[layout == PFEM_LOAD_UNIFORM ? 0 : (layout == PFEM_LOAD_PER_FACE ? i : i * NS + a)];
     }
-    const double thick = KIND == PFEM_ELAST_TRIA ? prm_elem(prm, e)[2] : 1.0;
+    const double thick = KIND == PFEM_ELAST_TRIA ? prm_at(prm, AtElem{e})[2] : 1.0;
     side_load(KIND, load, meas, nrm, v, thick, Fs);
 #pragma unroll
     for (int a = 0; a < NS; ++a)

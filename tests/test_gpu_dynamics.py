@@ -172,6 +172,33 @@ def test_mass_equals_the_mirror(case):
 
 
 @pytest.mark.parametrize("case", NAMES, indirect=True)
+def test_mass_in_the_scatter_form(case):
+    """The assembly mode "scatter", set before the pattern is built: the element pass sums every node by f64 atomics (the default
+    mode runs that pass for hub nodes only).  The element shares are the mirror's bit for bit (test_mass_equals_the_mirror's
+    array_equal); only the order of a sum of k positive terms differs, and every order lies within (k - 1) eps / 2 relative of
+    the exact sum: (k - 1) eps between two of them.  A solver of its own: the cached case keeps its mode."""
+    c = case
+    s = pf.PetscSolver().initialise(c.N, c.N)
+    try:
+        s.uploadMesh(c.kind, c.conn, c.xyz, D._setup(c.kind, c.mesh)[3], c.dm.solnApplied)
+        if c.ids is not None:
+            s.setMaterials(c.ids, n_mat=2, stride=6)
+        s.setAssemblyMode("scatter")
+        s.buildPattern()
+        assert not s.assemblyInfo()["gather"]         # (the mode took: the element pass sums every node)
+        s.assemble(c.ed, H.TIMEDATA)
+        total = s.dynamicsSetup(c.ed, c.density)
+        got, want = s.dynamicsMass(), c.m_mirror
+    finally:
+        s.free(collective=False)
+    assert got.shape == want.shape and (got > 0).all()
+    print(f"{c.name}: largest mass deviation {np.abs(got / want - 1).max():.3e}, most elements at a node {c.k.max()}")
+    assert (np.abs(got - want) <= (c.k - 1) * EPS * want).all()
+    n = len(c.mnode)
+    assert abs(total - c.mnode.sum()) <= n * EPS * c.mnode.sum()
+
+
+@pytest.mark.parametrize("case", NAMES, indirect=True)
 def test_stable_step_is_the_mirrors_gershgorin_step(case):
     """The same sums in the same order on non-hub rows; a square root and two divisions, each correctly rounded on both sides,
     leave an ulp or two.  Hub rows were assembled by atomics: their row sums are the device's own matrix, which the mirror reads."""
