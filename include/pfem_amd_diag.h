@@ -206,6 +206,54 @@ int pfem_modal_probe_residual(pfem_solver *s, int mb, int64_t n, const double *K
                               const double *theta, double *W_out, double *norms_out);
 int pfem_modal_probe_update(pfem_solver *s, int mb, int64_t n, const double *coef, double *X, double *W, double *P, double *KX,
                             double *KW, double *KP);
+/* One launch of a kernel of the steppers (pfem_dynamics_run_implicit, pfem_dynamics_run) on vectors of the caller's, through the
+ * grid function, the parameter block and the launch code of the run itself: what the tests compare with an exact or an
+ * extended-precision evaluation at row counts beyond one trip of the capped grid (2 048 blocks of 1 024 rows).  Every vector is
+ * a host array of n >= 1 doubles in plain row order.  An initialised handle is all they need, and they read and write no state
+ * of it.  On the device every vector is an allocation of its own with 8 quiet NaNs in front and 1 024 behind; outputs start as
+ * quiet NaNs throughout.  After the launch the guards must hold their bits and so must every vector the kernel takes as const:
+ * else PFEM_ERR_HIP with the vector's name in pfem_last_error_string.  scheme, dt, p0, p1, alpha: as pfem_dynamics_run_implicit
+ * takes them (PFEM_ERR_ARG likewise); the curve as pfem_dynamics_set_load_curve (n_curve = 0: none).  Partial arrays that come
+ * back hold 2 048 doubles, those behind the launch's gv (or nb) blocks still NaN; partial arrays that go in hold exactly
+ * gv = min(2 048, ceil(n / 1 024)) doubles (PFEM_ERR_ARG otherwise).
+ *   predict:   k_imp_predict: ut, vt from u, v, a.
+ *   rhs:       k_imp_rhs with the times and weights of step `step` from t_base, then k_cg_start with rtol, abstol, dtol: d, r,
+ *              p, the partials of (r,z), (z,z), sigma m p^2, their count *gv and the control block.  vt: Newmark only.
+ *   update:    k_imp_update on the control block *ctl (in and out) with it_arg >= 0 or -1 (the graph's form: ctl->its), the
+ *              n_pw partials of (p,Kp) and the n_mp = gv of sigma m p^2: r in place, the partials of (r,z) and (z,z).
+ *   direction: k_imp_direction on *ctl (in and out; it_arg = -1: ctl->its_dir) and the n_parts = gv partials of (r,z), (z,z):
+ *              p and d in place, the partials of sigma m p^2.
+ *   correct:   k_imp_correct: Newmark u, v, a from ut, vt, d; theta-method u in place and v from d (a stays NaN; ut, vt unused).
+ *   energy:    k_imp_energy, then k_imp_row at time t: row = [t, T, S, W, u at the probes, v at the probes] (4 + 2 n_probe
+ *              doubles; probe: rows in [0, n)), part = the [3][gv] partials (3 x 2 048 doubles of room).
+ *   step:      k_dyn_step for step -> step + 1 of a run that began at state run_start <= step, the step index as an argument
+ *              (use_ctl = 0) or from the control block (ctl_step[step & 1]); then, after a sampled step, k_dyn_flush.
+ *              ctl_step[2] goes in and comes back; un; *have_row and row (4 + 2 n_probe doubles) of a sampled step; part: the
+ *              [3][*nb] partials of parity step & 1 (room for 3 ceil(n / 1 024)), NaN after a step that is not sampled.       */
+typedef struct pfem_cg_ctl {
+    double beta[2], rn0, ttol, rn, dtol, alpha;
+    int flag, its, its_dir;
+} pfem_cg_ctl;
+int pfem_imp_probe_predict(pfem_solver *s, int64_t n, double dt, double beta, double gamma, const double *u, const double *v, const double *a,
+                           double *ut, double *vt);
+int pfem_imp_probe_rhs(pfem_solver *s, int scheme, int64_t n, double dt, double p0, double p1, double alpha, int n_curve, const double *ct,
+                       const double *cl, double t_base, int64_t step, double rtol, double abstol, double dtol, const double *f, const double *m,
+                       const double *vt, const double *w, const double *dinv, double *d, double *r, double *p, double *part_rz, double *part_zz,
+                       double *part_mp, int *gv, pfem_cg_ctl *ctl);
+int pfem_imp_probe_update(pfem_solver *s, int scheme, int64_t n, double dt, double p0, double p1, double alpha, pfem_cg_ctl *ctl, int it_arg,
+                          int n_pw, const double *part_pw, int n_mp, const double *part_mp, const double *p, const double *w, const double *m,
+                          const double *dinv, double *r, double *part_rz, double *part_zz);
+int pfem_imp_probe_direction(pfem_solver *s, int scheme, int64_t n, double dt, double p0, double p1, double alpha, pfem_cg_ctl *ctl, int it_arg,
+                             int n_parts, const double *part_rz, const double *part_zz, const double *r, const double *dinv, const double *m,
+                             double *p, double *d, int maxits, double *part_mp);
+int pfem_imp_probe_correct(pfem_solver *s, int scheme, int64_t n, double dt, double p0, double p1, double alpha, const double *ut, const double *vt,
+                           const double *d, double *u, double *v, double *a);
+int pfem_imp_probe_energy(pfem_solver *s, int scheme, int64_t n, const double *f, const double *m, const double *u, const double *v, const double *w,
+                          int n_probe, const int32_t *probe, double t, double *row, double *part, int *gv);
+int pfem_dyn_probe_step(pfem_solver *s, int64_t n, double dt, double alpha, double t0, int n_curve, const double *ct, const double *cl,
+                        int64_t step, int64_t run_start, int64_t sample_every, int n_probe, const int32_t *probe, int use_ctl,
+                        const double *f, const double *m, const double *minv, const double *w, const double *u, const double *up, double *un,
+                        double *row, int *have_row, double *part, int *nb, int64_t *ctl_step);
 /* *in_effect = 1 when the mesh on the device is held under the internal renumbering (a numbering without locality from 4 096
  * owned dofs, or PFEM_REORDER=1 at the upload), else 0: the tests of the translations assert it.                            */
 int pfem_solver_reordered(pfem_solver *s, int *in_effect);

@@ -51,6 +51,12 @@ class Timings(C.Structure):
                 ("host_comm_ms", C.c_double)]
 
 
+class CgCtl(C.Structure):
+    """the control block of the implicit stepper's CG as the probes exchange it (pfem_cg_ctl, include/pfem_amd_diag.h)"""
+    _fields_ = [("beta", C.c_double * 2), ("rn0", C.c_double), ("ttol", C.c_double), ("rn", C.c_double), ("dtol", C.c_double),
+                ("alpha", C.c_double), ("flag", C.c_int), ("its", C.c_int), ("its_dir", C.c_int)]
+
+
 # host hooks of the communication backend (include/pfem_amd.h, section 5)
 HOST_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int64)
 HOST_EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64),
@@ -178,6 +184,13 @@ SIGNATURES = {
     "pfem_modal_probe_gram": [_P, _I, _L] + [_P] * 8,
     "pfem_modal_probe_residual": [_P, _I, _L] + [_P] * 7,
     "pfem_modal_probe_update": [_P, _I, _L] + [_P] * 7,
+    "pfem_imp_probe_predict": [_P, _L, _D, _D, _D] + [_P] * 5,
+    "pfem_imp_probe_rhs": [_P, _I, _L, _D, _D, _D, _D, _I, _P, _P, _D, _L, _D, _D, _D] + [_P] * 13,
+    "pfem_imp_probe_update": [_P, _I, _L, _D, _D, _D, _D, _P, _I, _I, _P, _I] + [_P] * 8,
+    "pfem_imp_probe_direction": [_P, _I, _L, _D, _D, _D, _D, _P, _I, _I] + [_P] * 7 + [_I, _P],
+    "pfem_imp_probe_correct": [_P, _I, _L, _D, _D, _D, _D] + [_P] * 6,
+    "pfem_imp_probe_energy": [_P, _I, _L] + [_P] * 5 + [_I, _P, _D, _P, _P, _P],
+    "pfem_dyn_probe_step": [_P, _L, _D, _D, _D, _I, _P, _P, _L, _L, _L, _I, _P, _I] + [_P] * 12,
     "pfem_solver_reordered": [_P, _P],
     "pfem_modal_last_pc": [_P, _P],
     "pfem_modal_bench_spmm": [_P, _I, _I, _P, _P],

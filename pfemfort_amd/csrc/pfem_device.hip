@@ -5651,6 +5651,7 @@ extern "C" int pfem_solver_factorise(pfem_solver *s)
     return PFEM_OK;
 }
 
+#include "pfem_probe.inc"
 #include "pfem_dynamics.inc"
 #include "pfem_implicit.inc"
 #include "pfem_modal.inc"

@@ -30,26 +30,72 @@ int dyn_upload_rows(pfem_solver *s, const double *in, double *d_vec)
     return PFEM_OK;
 }
 
-// the parameter block of a run's launches
-DynPar dyn_par(const pfem_solver *s, double alpha, long long sample_every)
+// blocks of a step launch = partial sums per quantity, and the doubles its [2][3][nb] partials need (never fewer than kMaxGrid:
+// the mass total and the Gershgorin bound leave up to that many partials in the same buffer)
+int dyn_blocks(int64_t n) { return static_cast<int>(std::max<int64_t>(1, (n + kDynBlockRows - 1) / kDynBlockRows)); }
+size_t dyn_part_len(int nb) { return static_cast<size_t>(std::max(6 * nb, kMaxGrid)); }
+// sample_every as the kernels take it (0: no rows, ever)
+long long dyn_every(int64_t sample_every) { return sample_every > 0 ? sample_every : (1LL << 62); }
+
+// What the launches of a step read and write: the run fills it from the buffers of Dyn and of the solver (dyn_view), a probe
+// (pfem_dyn_probe_step) from vectors of its own; both launch through dyn_par, dyn_launch_step and dyn_launch_flush.
+struct DynView {
+    int64_t n = 0;
+    int nb = 0;
+    double t0 = 0.0, dt = 0.0;
+    int n_curve = 0;
+    const double *ct = nullptr, *cl = nullptr;
+    int n_probe = 0;
+    const int32_t *probe = nullptr;
+    double *hist = nullptr, *part = nullptr;
+    DynCtl *ctl = nullptr;
+    const double *f = nullptr, *m = nullptr, *minv = nullptr, *w = nullptr;
+    double *u[3] = {nullptr, nullptr, nullptr};          // u_n in u[n % 3], u_{n-1} in u[(n + 2) % 3]
+};
+
+DynView dyn_view(const pfem_solver *s)
 {
     const Dyn &D = *s->dyn;
+    DynView V;
+    V.n = D.n;
+    V.nb = D.nb;
+    V.t0 = D.t0;
+    V.dt = D.dt;
+    V.n_curve = D.n_curve;
+    V.ct = D.d_ct.p;
+    V.cl = D.d_cl.p;
+    V.n_probe = D.n_probe;
+    V.probe = D.d_probe.p;
+    V.hist = D.d_hist.p;
+    V.part = D.d_part.p;
+    V.ctl = D.d_ctl.p;
+    V.f = s->d_rhs.p;
+    V.m = D.d_m.p;
+    V.minv = D.d_minv.p;
+    V.w = s->d_w.p;
+    for (int b = 0; b < 3; ++b) V.u[b] = D.u[b];
+    return V;
+}
+
+// the parameter block of a run's launches
+DynPar dyn_par(const DynView &V, double alpha, long long sample_every)
+{
     DynPar P{};
-    P.n = D.n;
-    P.t0 = D.t0;
-    P.dt = D.dt;
-    P.c0 = 1.0 / (D.dt * D.dt);
-    P.c1 = alpha / (2.0 * D.dt);
+    P.n = V.n;
+    P.t0 = V.t0;
+    P.dt = V.dt;
+    P.c0 = 1.0 / (V.dt * V.dt);
+    P.c1 = alpha / (2.0 * V.dt);
     P.a = P.c0 + P.c1;
     P.sample_every = sample_every;
-    P.n_curve = D.n_curve;
-    P.ct = D.d_ct.p;
-    P.cl = D.d_cl.p;
-    P.n_probe = D.n_probe;
-    P.probe = D.d_probe.p;
-    P.hist = D.d_hist.p;
-    P.nb = D.nb;
-    P.part = D.d_part.p;
+    P.n_curve = V.n_curve;
+    P.ct = V.ct;
+    P.cl = V.cl;
+    P.n_probe = V.n_probe;
+    P.probe = V.probe;
+    P.hist = V.hist;
+    P.nb = V.nb;
+    P.part = V.part;
     return P;
 }
 
@@ -60,16 +106,28 @@ inline uint64_t dyn_bits(double v)
     return b;
 }
 
-// step n -> n + 1, enqueued: w = K u_n by the SpMV form in effect, then k_dyn_step.  in_graph: the step index comes from the
-// control block (the launch is replayed), else it is an argument.
-void dyn_enqueue_step(pfem_solver *s, const DynPar &P, long long step, bool in_graph)
+// k_dyn_step for n -> n + 1 on w = K u_n.  in_graph: the step index comes from the control block (the launch is replayed), else
+// it is an argument.
+void dyn_launch_step(pfem_solver *s, const DynView &V, const DynPar &P, long long step, bool in_graph)
 {
-    Dyn &D = *s->dyn;
-    const double *u = D.u[step % 3], *up = D.u[(step + 2) % 3];
-    double *un = D.u[(step + 1) % 3];
-    launch_spmv<false>(s, u, s->d_w.p, 0, nullptr, nullptr);
-    launch(k_dyn_step, dim3(static_cast<unsigned>(D.nb)), dim3(kBlock), 0, s->stream, nullptr, nullptr, P, D.d_ctl.p, static_cast<int>(step & 1),
-           in_graph ? -1LL : step, s->d_rhs.p, D.d_m.p, D.d_minv.p, s->d_w.p, u, up, un);
+    const double *u = V.u[step % 3], *up = V.u[(step + 2) % 3];
+    double *un = V.u[(step + 1) % 3];
+    launch(k_dyn_step, dim3(static_cast<unsigned>(V.nb)), dim3(kBlock), 0, s->stream, nullptr, nullptr, P, V.ctl, static_cast<int>(step & 1),
+           in_graph ? -1LL : step, V.f, V.m, V.minv, V.w, u, up, un);
+}
+
+// the history row of a run's last step n - 1 -> n = `step`, when that was a sampled one: no later launch writes it
+void dyn_launch_flush(pfem_solver *s, const DynView &V, const DynPar &P, long long step, long long run_start)
+{
+    launch(k_dyn_flush, dim3(1), dim3(kBlock), 0, s->stream, nullptr, nullptr, P, step, run_start, static_cast<const double *>(V.u[step % 3]),
+           static_cast<const double *>(V.u[(step + 2) % 3]));
+}
+
+// step n -> n + 1, enqueued: w = K u_n by the SpMV form in effect, then k_dyn_step
+void dyn_enqueue_step(pfem_solver *s, const DynView &V, const DynPar &P, long long step, bool in_graph)
+{
+    launch_spmv<false>(s, V.u[step % 3], s->d_w.p, 0, nullptr, nullptr);
+    dyn_launch_step(s, V, P, step, in_graph);
 }
 
 }  // namespace
@@ -92,12 +150,12 @@ extern "C" int pfem_dynamics_setup(pfem_solver *s, const double *elemData, const
     auto D = std::make_unique<Dyn>();
     const int64_t n = s->n_loc, nn = m.nNode;
     D->n = n;
-    D->nb = static_cast<int>(std::max<int64_t>(1, (n + kDynBlockRows - 1) / kDynBlockRows));
+    D->nb = dyn_blocks(n);
     PFEM_TRY(D->d_mnode.alloc(static_cast<size_t>(std::max<int64_t>(nn, 1))));
     PFEM_TRY(D->d_m.alloc(static_cast<size_t>(std::max<int64_t>(n, 1))));
     PFEM_TRY(D->d_minv.alloc(static_cast<size_t>(std::max<int64_t>(n, 1))));
     PFEM_TRY(D->d_v0.alloc(static_cast<size_t>(std::max<int64_t>(n, 1))));
-    PFEM_TRY(D->d_part.alloc(static_cast<size_t>(std::max(6 * D->nb, kMaxGrid))));
+    PFEM_TRY(D->d_part.alloc(dyn_part_len(D->nb)));
     PFEM_TRY(D->d_ctl.alloc(1));
     for (int b = 0; b < 3; ++b) {
         const size_t len = static_cast<size_t>(n) + 2 * kVecGuard;
@@ -272,7 +330,7 @@ extern "C" int pfem_dynamics_run(pfem_solver *s, double dt, int64_t n_steps, dou
         return PFEM_ERR_STATE;
     }
     PFEM_TRY(use_device(s));
-    const long long every = sample_every > 0 ? sample_every : (1LL << 62);          // 0: no rows, ever
+    const long long every = dyn_every(sample_every);
     const int64_t n_rows = n_steps / every;
     const int ncol = 4 + 2 * D.n_probe;
     if (rows) *rows = n_rows;
@@ -280,7 +338,8 @@ extern "C" int pfem_dynamics_run(pfem_solver *s, double dt, int64_t n_steps, dou
     if (n_rows > 0 && D.d_hist.n < static_cast<size_t>(n_rows * ncol)) PFEM_TRY(D.d_hist.alloc(static_cast<size_t>(n_rows * ncol)));
     D.dt = dt;
     D.mode = kDynExplicit;
-    const DynPar P = dyn_par(s, alpha, every);
+    const DynView V = dyn_view(s);          // (after d_hist has its size and D.dt its value)
+    const DynPar P = dyn_par(V, alpha, every);
     // the SpMV's copies of the matrix values, as every product outside a solve brings them up to date
     mark_group_vals(s);
     PFEM_TRY(refresh_group_vals(s));
@@ -295,7 +354,7 @@ extern "C" int pfem_dynamics_run(pfem_solver *s, double dt, int64_t n_steps, dou
     const long long end = D.step + n_steps;
     // up to the next multiple of the graph's period by stream launches, whole graphs, the rest by stream launches
     while (D.step < end && (D.step % kDynGraphSteps != 0 || end - D.step < kDynGraphSteps)) {
-        dyn_enqueue_step(s, P, D.step, false);
+        dyn_enqueue_step(s, V, P, D.step, false);
         ++D.step;
     }
     PFEM_TRY(check_kernel("k_dyn_step"));
@@ -311,28 +370,27 @@ extern "C" int pfem_dynamics_run(pfem_solver *s, double dt, int64_t n_steps, dou
             static_cast<uint64_t>(every), dyn_bits(P.t0), dyn_bits(P.dt), dyn_bits(P.c1), spmv_key(s), spmv_form(s).kernel_id()};
         bool use_graph = false;
         PFEM_TRY(D.graph.ensure(s->stream, std::move(key), {}, [&](int) {
-            for (int j = 0; j < kDynGraphSteps; ++j) dyn_enqueue_step(s, P, j, true);
+            for (int j = 0; j < kDynGraphSteps; ++j) dyn_enqueue_step(s, V, P, j, true);
             return hipGetLastError() == hipSuccess;
         }, &use_graph));
         while (end - D.step >= kDynGraphSteps) {
             if (use_graph) {
                 PFEM_HIP(hipGraphLaunch(D.graph.exec[0], s->stream));
             } else {          // a stream that cannot be captured (the legacy default stream): the same launches, one by one
-                for (int j = 0; j < kDynGraphSteps; ++j) dyn_enqueue_step(s, P, D.step + j, false);
+                for (int j = 0; j < kDynGraphSteps; ++j) dyn_enqueue_step(s, V, P, D.step + j, false);
                 PFEM_TRY(check_kernel("k_dyn_step"));
             }
             D.step += kDynGraphSteps;
         }
         while (D.step < end) {
-            dyn_enqueue_step(s, P, D.step, false);
+            dyn_enqueue_step(s, V, P, D.step, false);
             ++D.step;
         }
         PFEM_TRY(check_kernel("k_dyn_step"));
     }
     if (n_rows > 0) {
         if (n_steps % every == 0) {          // the last step was a sampled one: no later launch writes its row
-            launch(k_dyn_flush, dim3(1), dim3(kBlock), 0, s->stream, nullptr, nullptr, P, D.step, end - n_steps, static_cast<const double *>(D.u[D.step % 3]),
-                   static_cast<const double *>(D.u[(D.step + 2) % 3]));
+            dyn_launch_flush(s, V, P, D.step, end - n_steps);
             PFEM_TRY(check_kernel("k_dyn_flush"));
         }
         PFEM_HIP(hipMemcpyAsync(history, D.d_hist.p, sizeof(double) * static_cast<size_t>(n_rows * ncol), hipMemcpyDeviceToHost, s->stream));
@@ -393,5 +451,102 @@ extern "C" int pfem_dynamics_bench(pfem_solver *s, double dt, int graphs, double
     PFEM_TRY(elapsed(s, &ms));
     *us_per_step = 1e3 * ms / (static_cast<double>(graphs) * kDynGraphSteps);
     if (steps_per_graph) *steps_per_graph = kDynGraphSteps;
+    return PFEM_OK;
+}
+
+// ---- one launch of the step kernel on vectors of the caller's (pfem_amd_diag.h) ---------------------------------------------------
+namespace {
+constexpr size_t kProbeFront = 8, kProbeBack = kDynBlockRows;          // quiet NaNs before and behind every vector of a stepper probe
+constexpr int64_t kProbeMaxRows = 64;                                  // history rows a step probe allocates at most
+}  // namespace
+
+extern "C" int pfem_dyn_probe_step(pfem_solver *s, int64_t n, double dt, double alpha, double t0, int n_curve, const double *ct, const double *cl,
+                                   int64_t step, int64_t run_start, int64_t sample_every, int n_probe, const int32_t *probe, int use_ctl,
+                                   const double *f, const double *m, const double *minv, const double *w, const double *u, const double *up, double *un,
+                                   double *row, int *have_row, double *part, int *nb_out, int64_t *ctl_step)
+{
+    if (!s || n < 1 || !(dt > 0.0) || !std::isfinite(dt) || !(alpha >= 0.0) || !std::isfinite(alpha) || !std::isfinite(t0)) return PFEM_ERR_ARG;
+    if (n_curve < 0 || (n_curve > 0 && (!ct || !cl)) || n_probe < 0 || (n_probe > 0 && !probe) || sample_every < 0) return PFEM_ERR_ARG;
+    if (step < 0 || run_start < 0 || run_start > step) return PFEM_ERR_ARG;
+    if (!f || !m || !minv || !w || !u || !up || !un || !row || !have_row || !part || !nb_out || !ctl_step) return PFEM_ERR_ARG;
+    for (int k = 0; k < n_probe; ++k)
+        if (probe[k] < 0 || probe[k] >= n) return PFEM_ERR_ARG;
+    const long long every = dyn_every(sample_every);
+    const int64_t n_rows = (step + 1 - run_start) / every;             // rows of a run from run_start up to the state step + 1
+    if (n_rows > kProbeMaxRows) return PFEM_ERR_ARG;
+    PFEM_TRY(use_device(s));
+    const char *who = "pfem_dyn_probe_step";
+    const size_t rows = static_cast<size_t>(n), ncol = static_cast<size_t>(4 + 2 * n_probe);
+    const int nb = dyn_blocks(n);
+    ProbeBlock bf, bm, bq, bw, bu, bp, bn, bpart, bhist, bct, bcl;
+    PFEM_TRY(probe_upload(s, bf, "f", f, rows, kProbeBack, kProbeFront, true));
+    PFEM_TRY(probe_upload(s, bm, "m", m, rows, kProbeBack, kProbeFront, true));
+    PFEM_TRY(probe_upload(s, bq, "minv", minv, rows, kProbeBack, kProbeFront, true));
+    PFEM_TRY(probe_upload(s, bw, "w", w, rows, kProbeBack, kProbeFront, true));
+    PFEM_TRY(probe_upload(s, bu, "u", u, rows, kProbeBack, kProbeFront, true));
+    PFEM_TRY(probe_upload(s, bp, "up", up, rows, kProbeBack, kProbeFront, true));
+    PFEM_TRY(probe_upload(s, bn, "un", nullptr, rows, kProbeBack, kProbeFront));
+    PFEM_TRY(probe_upload(s, bpart, "part", nullptr, dyn_part_len(nb), kProbeBack, kProbeFront));
+    PFEM_TRY(probe_upload(s, bhist, "hist", nullptr, static_cast<size_t>(std::max<int64_t>(n_rows, 1)) * ncol, kProbeBack, kProbeFront));
+    if (n_curve > 0) {
+        PFEM_TRY(probe_upload(s, bct, "ct", ct, static_cast<size_t>(n_curve), kProbeFront, kProbeFront, true));
+        PFEM_TRY(probe_upload(s, bcl, "cl", cl, static_cast<size_t>(n_curve), kProbeFront, kProbeFront, true));
+    }
+    DevBuf<int32_t> d_probe;
+    DevBuf<DynCtl> d_ctl;
+    PFEM_TRY(d_probe.alloc(static_cast<size_t>(std::max(n_probe, 1))));
+    PFEM_TRY(d_ctl.alloc(1));
+    DynCtl c{{ctl_step[0], ctl_step[1]}, run_start};
+    if (n_probe > 0) PFEM_HIP(hipMemcpyAsync(d_probe.p, probe, sizeof(int32_t) * static_cast<size_t>(n_probe), hipMemcpyHostToDevice, s->stream));
+    PFEM_HIP(hipMemcpyAsync(d_ctl.p, &c, sizeof c, hipMemcpyHostToDevice, s->stream));
+    DynView V;
+    V.n = n;
+    V.nb = nb;
+    V.t0 = t0;
+    V.dt = dt;
+    V.n_curve = n_curve;
+    V.ct = n_curve > 0 ? bct.p() : nullptr;
+    V.cl = n_curve > 0 ? bcl.p() : nullptr;
+    V.n_probe = n_probe;
+    V.probe = d_probe.p;
+    V.hist = bhist.p();
+    V.part = bpart.p();
+    V.ctl = d_ctl.p;
+    V.f = bf.p(); V.m = bm.p(); V.minv = bq.p(); V.w = bw.p();
+    V.u[step % 3] = bu.p();
+    V.u[(step + 2) % 3] = bp.p();
+    V.u[(step + 1) % 3] = bn.p();
+    const DynPar P = dyn_par(V, alpha, every);
+    dyn_launch_step(s, V, P, step, use_ctl != 0);
+    PFEM_TRY(check_kernel("k_dyn_step"));
+    const bool sampled = (step + 1 - run_start) % every == 0;
+    if (sampled) {                         // as at the end of a run whose last step was a sampled one
+        dyn_launch_flush(s, V, P, step + 1, run_start);
+        PFEM_TRY(check_kernel("k_dyn_flush"));
+    }
+    PFEM_HIP(hipMemcpyAsync(&c, d_ctl.p, sizeof c, hipMemcpyDeviceToHost, s->stream));
+    PFEM_HIP(hipStreamSynchronize(s->stream));
+    for (const ProbeBlock *B : {&bf, &bm, &bq, &bw, &bu, &bp}) PFEM_TRY(probe_download(s, *B, nullptr, who));
+    if (n_curve > 0) {
+        PFEM_TRY(probe_download(s, bct, nullptr, who));
+        PFEM_TRY(probe_download(s, bcl, nullptr, who));
+    }
+    PFEM_TRY(probe_download(s, bn, un, who));
+    std::vector<double> h_part(bpart.len), h_hist(bhist.len);
+    PFEM_TRY(probe_download(s, bpart, h_part.data(), who));
+    PFEM_TRY(probe_download(s, bhist, h_hist.data(), who));
+    // the partials of the step's parity come back; those of the other parity and what lies behind both must be as they were
+    const size_t mine = static_cast<size_t>(step & 1) * 3 * static_cast<size_t>(nb);
+    for (size_t i = 0; i < h_part.size(); ++i)
+        if ((i < mine || i >= mine + 3 * static_cast<size_t>(nb)) && !std::isnan(h_part[i])) {
+            set_last_error(std::string(who) + ": the launch wrote partial " + std::to_string(i) + " outside the [3][nb] of the step's parity");
+            return PFEM_ERR_HIP;
+        }
+    std::memcpy(part, h_part.data() + mine, sizeof(double) * 3 * static_cast<size_t>(nb));
+    *have_row = sampled ? 1 : 0;
+    if (sampled) std::memcpy(row, h_hist.data() + static_cast<size_t>(n_rows - 1) * ncol, sizeof(double) * ncol);
+    *nb_out = nb;
+    ctl_step[0] = c.step[0];
+    ctl_step[1] = c.step[1];
     return PFEM_OK;
 }

@@ -90,27 +90,63 @@ int imp_ensure(pfem_solver *s)
     return PFEM_OK;
 }
 
+// What the launches of a step read and write: the vectors, the partials, the control block and the load curve.  The run fills it
+// from the buffers of Imp, Dyn and the solver (imp_view), a probe (pfem_imp_probe_*) from vectors of its own; both launch through
+// imp_run_of and the imp_launch_* functions below.
+struct ImpView {
+    int64_t n = 0;
+    const double *f = nullptr, *m = nullptr;
+    double *u = nullptr, *v = nullptr, *a = nullptr, *ut = nullptr, *vt = nullptr, *d = nullptr, *r = nullptr, *p = nullptr, *w = nullptr, *dinv = nullptr;
+    double *part_rz = nullptr, *part_zz = nullptr, *part_mp = nullptr, *scal_pw = nullptr, *part_e = nullptr;          // part_e: [3][gv]
+    CgCtl *ctl = nullptr;
+    double *hist0 = nullptr;
+    int n_curve = 0;
+    const double *ct = nullptr, *cl = nullptr;
+    int n_probe = 0;
+    const int32_t *probe = nullptr;
+};
+
+ImpView imp_view(const pfem_solver *s)
+{
+    const Dyn &D = *s->dyn;
+    const Imp &I = *D.imp;
+    ImpView V;
+    V.n = D.n;
+    V.f = s->d_rhs.p;
+    V.m = D.d_m.p;
+    V.u = I.u; V.v = I.v.p; V.a = I.a.p; V.ut = I.ut; V.vt = I.vt.p; V.d = I.d.p; V.r = I.r.p; V.p = I.p; V.w = I.w.p; V.dinv = I.dinv.p;
+    double *part = I.part.p;               // (r,z) | (z,z) | sigma m p^2 | folded (p,Kp) | T, S, W
+    V.part_rz = part; V.part_zz = part + kMaxGrid; V.part_mp = part + 2 * kMaxGrid; V.scal_pw = part + 3 * kMaxGrid; V.part_e = part + 4 * kMaxGrid;
+    V.ctl = I.ctl.p;
+    V.hist0 = I.hist0.p;
+    V.n_curve = D.n_curve;
+    V.ct = D.d_ct.p;
+    V.cl = D.d_cl.p;
+    V.n_probe = D.n_probe;
+    V.probe = D.d_probe.p;
+    return V;
+}
+
 struct ImpRun {
     pfem_solver *s;
-    Imp &I;
+    ImpView V;
     ImpPar P;
     DynPar C;                // the load curve (dyn_lambda reads n_curve, ct, cl)
     unsigned gv, gs;
-    double *part_rz, *part_zz, *part_mp, *scal_pw, *part_e;
     int maxits;
 };
 
-ImpRun imp_run_setup(pfem_solver *s, const ImpPar &P, int maxits)
+// the grid of the vector kernels and the curve's block for a view; gs: the blocks of the SpMV whose partials cg_fold folds
+ImpRun imp_run_of(pfem_solver *s, const ImpView &V, const ImpPar &P, unsigned gs, int maxits)
 {
-    Dyn &D = *s->dyn;
-    Imp &I = *D.imp;
     DynPar C{};
-    C.n_curve = D.n_curve;
-    C.ct = D.d_ct.p;
-    C.cl = D.d_cl.p;
-    double *part = I.part.p;
-    return ImpRun{s, I, P, C, imp_grid(D.n), spmv_blocks(s), part, part + kMaxGrid, part + 2 * kMaxGrid, part + 3 * kMaxGrid, part + 4 * kMaxGrid, maxits};
+    C.n_curve = V.n_curve;
+    C.ct = V.ct;
+    C.cl = V.cl;
+    return ImpRun{s, V, P, C, imp_grid(V.n), gs, maxits};
 }
+
+ImpRun imp_run_setup(pfem_solver *s, const ImpPar &P, int maxits) { return imp_run_of(s, imp_view(s), P, spmv_blocks(s), maxits); }
 
 // dinv of the shifted operator: the diagonal of the row form, then 1 / (K_ii + sigma m_i)
 int imp_form_dinv(const ImpRun &R)
@@ -118,50 +154,89 @@ int imp_form_dinv(const ImpRun &R)
     pfem_solver *s = R.s;
     const int64_t n = R.P.n;
     if (n > 0) {
-        launch(k_extract_diag, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, nullptr, nullptr, s->sell(), R.I.dinv.p);
-        launch(k_imp_dinv, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, nullptr, nullptr, n, R.P.sigma, s->dyn->d_m.p, R.I.dinv.p);
+        launch(k_extract_diag, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, nullptr, nullptr, s->sell(), R.V.dinv);
+        launch(k_imp_dinv, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, nullptr, nullptr, n, R.P.sigma, R.V.m, R.V.dinv);
     }
     return check_kernel("k_imp_dinv");
+}
+
+// the update of iteration `it` on w = K p, whose (p, Kp) is the sum of the pw_n doubles at pw_parts.  it < 0: inside a graph
+void imp_launch_update(const ImpRun &R, int it, const double *pw_parts, int pw_n)
+{
+    const ImpView &V = R.V;
+    launch(k_imp_update, dim3(R.gv), dim3(kBlock), 0, R.s->stream, nullptr, nullptr, V.ctl, it, R.P, pw_parts, pw_n, V.part_mp, static_cast<int>(R.gv), V.p, V.w,
+           V.m, V.dinv, V.r, V.part_rz, V.part_zz);
+}
+
+void imp_launch_direction(const ImpRun &R, int it)
+{
+    const ImpView &V = R.V;
+    launch(k_imp_direction, dim3(R.gv), dim3(kBlock), 0, R.s->stream, nullptr, nullptr, V.ctl, it, R.P, V.part_rz, V.part_zz, static_cast<int>(R.gv), V.r, V.dinv,
+           V.m, V.p, V.d, R.maxits, V.part_mp);
 }
 
 // one iteration, enqueued: w = K p with the (p, Kp) partials, update, direction.  it < 0: inside a graph
 void imp_enqueue_iteration(const ImpRun &R, int it)
 {
     pfem_solver *s = R.s;
-    Imp &I = R.I;
-    const double *m = s->dyn->d_m.p;
-    launch_spmv<true>(s, I.p, I.w.p, R.P.n, I.part_pw.p, I.ctl.p);
+    Imp &I = *s->dyn->imp;
+    launch_spmv<true>(s, R.V.p, R.V.w, R.P.n, I.part_pw.p, R.V.ctl);
     const double *pw_parts;
     int pw_n;
-    cg_fold(s, I.part_pw.p, R.gs, R.scal_pw, I.ctl.p, &pw_parts, &pw_n);
-    launch(k_imp_update, dim3(R.gv), dim3(kBlock), 0, s->stream, nullptr, nullptr, I.ctl.p, it, R.P, pw_parts, pw_n, R.part_mp, static_cast<int>(R.gv), I.p,
-           I.w.p, m, I.dinv.p, I.r.p, R.part_rz, R.part_zz);
-    launch(k_imp_direction, dim3(R.gv), dim3(kBlock), 0, s->stream, nullptr, nullptr, I.ctl.p, it, R.P, R.part_rz, R.part_zz, static_cast<int>(R.gv), I.r.p,
-           I.dinv.p, m, I.p, I.d.p, R.maxits, R.part_mp);
+    cg_fold(s, I.part_pw.p, R.gs, R.V.scal_pw, R.V.ctl, &pw_parts, &pw_n);
+    imp_launch_update(R, it, pw_parts, pw_n);
+    imp_launch_direction(R, it);
 }
 
-// predictor, K ut, right-hand side and the start of the CG for the step n -> n + 1 (rtol / abstol / dtol: the stopping rule)
-void imp_enqueue_start(const ImpRun &R, long long n, double t_base, double rtol, double abstol, double dtol)
+// Newmark's predictor for the step from (u, v, a)
+void imp_launch_predict(const ImpRun &R)
 {
-    pfem_solver *s = R.s;
-    Imp &I = R.I;
-    const Dyn &D = *s->dyn;
+    const ImpView &V = R.V;
+    launch(k_imp_predict, dim3(R.gv), dim3(kBlock), 0, R.s->stream, nullptr, nullptr, R.P, V.u, V.v, V.a, V.ut, V.vt);
+}
+
+// right-hand side and the start of the CG for the step n -> n + 1 on w = K ut (theta-method: K u_n); rtol / abstol / dtol: the
+// stopping rule
+void imp_launch_rhs(const ImpRun &R, long long n, double t_base, double rtol, double abstol, double dtol)
+{
+    const ImpView &V = R.V;
     const bool nm = R.P.scheme == PFEM_SCHEME_NEWMARK;
     const double tn0 = t_base + static_cast<double>(n) * R.P.dt, tn1 = t_base + static_cast<double>(n + 1) * R.P.dt;
-    if (nm) launch(k_imp_predict, dim3(R.gv), dim3(kBlock), 0, s->stream, nullptr, nullptr, R.P, I.u, I.v.p, I.a.p, I.ut, I.vt.p);
-    launch_spmv<false>(s, nm ? I.ut : I.u, I.w.p, 0, nullptr, nullptr);
-    launch(k_imp_rhs, dim3(R.gv), dim3(kBlock), 0, s->stream, nullptr, nullptr, R.P, R.C, tn0, nm ? 0.0 : 1.0 - R.P.theta, tn1, nm ? 1.0 : R.P.theta, s->d_rhs.p,
-           D.d_m.p, nm ? I.vt.p : nullptr, I.w.p, I.dinv.p, I.d.p, I.r.p, I.p, R.part_rz, R.part_zz, R.part_mp);
-    launch(k_cg_start, dim3(1), dim3(kBlock), 0, s->stream, nullptr, nullptr, I.ctl.p, R.part_rz, R.part_zz, static_cast<int>(R.gv), nullptr, rtol, abstol, dtol,
-           I.hist0.p);
+    launch(k_imp_rhs, dim3(R.gv), dim3(kBlock), 0, R.s->stream, nullptr, nullptr, R.P, R.C, tn0, nm ? 0.0 : 1.0 - R.P.theta, tn1, nm ? 1.0 : R.P.theta, V.f, V.m,
+           nm ? V.vt : nullptr, V.w, V.dinv, V.d, V.r, V.p, V.part_rz, V.part_zz, V.part_mp);
+    launch(k_cg_start, dim3(1), dim3(kBlock), 0, R.s->stream, nullptr, nullptr, V.ctl, V.part_rz, V.part_zz, static_cast<int>(R.gv), nullptr, rtol, abstol, dtol,
+           V.hist0);
+}
+
+// predictor, K ut, right-hand side and the start of the CG for the step n -> n + 1
+void imp_enqueue_start(const ImpRun &R, long long n, double t_base, double rtol, double abstol, double dtol)
+{
+    const bool nm = R.P.scheme == PFEM_SCHEME_NEWMARK;
+    if (nm) imp_launch_predict(R);
+    launch_spmv<false>(R.s, nm ? R.V.ut : R.V.u, R.V.w, 0, nullptr, nullptr);
+    imp_launch_rhs(R, n, t_base, rtol, abstol, dtol);
+}
+
+void imp_launch_correct(const ImpRun &R)
+{
+    const ImpView &V = R.V;
+    launch(k_imp_correct, dim3(R.gv), dim3(kBlock), 0, R.s->stream, nullptr, nullptr, R.P, V.ut, V.vt, V.d, V.u, V.v, V.a);
+}
+
+// the history row of the state (u, v) at time t on w = K u: the partials of the sums, then the one block that adds them
+void imp_launch_row(const ImpRun &R, double t, double *row)
+{
+    const ImpView &V = R.V;
+    launch(k_imp_energy, dim3(R.gv), dim3(kBlock), 0, R.s->stream, nullptr, nullptr, R.P, V.f, V.m, V.u, V.v, V.w, V.part_e);
+    launch(k_imp_row, dim3(1), dim3(kBlock), 0, R.s->stream, nullptr, nullptr, t, V.part_e, static_cast<int>(R.gv), V.n_probe, V.probe, V.u, V.v, row);
 }
 
 std::vector<uint64_t> imp_graph_key(const ImpRun &R)
 {
     const pfem_solver *s = R.s;
-    const Imp &I = R.I;
+    const ImpView &V = R.V;
     auto ptr = [](const void *p) { return reinterpret_cast<uint64_t>(p); };
-    return {ptr(I.p), ptr(I.w.p), ptr(I.r.p), ptr(I.d.p), ptr(I.dinv.p), ptr(I.part.p), ptr(I.part_pw.p), ptr(I.ctl.p), ptr(s->dyn->d_m.p),
+    return {ptr(V.p), ptr(V.w), ptr(V.r), ptr(V.d), ptr(V.dinv), ptr(V.part_rz), ptr(s->dyn->imp->part_pw.p), ptr(V.ctl), ptr(V.m),
             ptr(s->d_vals.p), ptr(s->d_cols.p), ptr(s->d_rvals.p), ptr(s->d_gvals.p), ptr(s->d_dwords.p), ptr(s->stream),
             static_cast<uint64_t>(R.P.n), static_cast<uint64_t>(R.gv), static_cast<uint64_t>(R.gs), static_cast<uint64_t>(R.maxits),
             dyn_bits(R.P.sigma), spmv_key(s), spmv_form(s).kernel_id()};
@@ -176,7 +251,7 @@ int imp_iterate(const ImpRun &R, bool use_graph, CgCtl *h)
         const int it_end = std::min(it + kImpChunk, R.maxits);
         while (it < it_end) {
             if (use_graph && it + kImpGraphIters <= it_end) {
-                PFEM_HIP(hipGraphLaunch(R.I.graph.exec[0], s->stream));
+                PFEM_HIP(hipGraphLaunch(s->dyn->imp->graph.exec[0], s->stream));
                 it += kImpGraphIters;
             } else {
                 imp_enqueue_iteration(R, it);
@@ -184,7 +259,7 @@ int imp_iterate(const ImpRun &R, bool use_graph, CgCtl *h)
             }
         }
         PFEM_TRY(check_kernel("implicit pcg iteration"));
-        PFEM_HIP(hipMemcpyAsync(s->h_ctl, R.I.ctl.p, sizeof(CgCtl), hipMemcpyDeviceToHost, s->stream));
+        PFEM_HIP(hipMemcpyAsync(s->h_ctl, R.V.ctl, sizeof(CgCtl), hipMemcpyDeviceToHost, s->stream));
         PFEM_HIP(hipStreamSynchronize(s->stream));
         *h = *s->h_ctl;
         if (h->flag != 0) break;
@@ -198,7 +273,7 @@ int imp_ensure_graph(const ImpRun &R, bool *use_graph)
     pfem_solver *s = R.s;
     *use_graph = false;
     if (R.P.n <= 0 || s->stream == nullptr) return PFEM_OK;
-    return R.I.graph.ensure(s->stream, imp_graph_key(R), {}, [&](int) {
+    return s->dyn->imp->graph.ensure(s->stream, imp_graph_key(R), {}, [&](int) {
         for (int k = 0; k < kImpGraphIters; ++k) imp_enqueue_iteration(R, -1);
         return hipGetLastError() == hipSuccess;
     }, use_graph);
@@ -220,7 +295,7 @@ extern "C" int pfem_dynamics_run_implicit(pfem_solver *s, int scheme, double dt,
                                               : "pfem_dynamics_run_implicit: another scheme than the run before needs a new pfem_dynamics_set_state");
         return PFEM_ERR_STATE;
     }
-    const long long every = sample_every > 0 ? sample_every : (1LL << 62);          // 0: no rows, ever
+    const long long every = dyn_every(sample_every);
     const int64_t n_rows = n_steps / every;
     const int ncol = 4 + 2 * D.n_probe;
     if (n_rows > 0 && !history) return PFEM_ERR_ARG;
@@ -268,14 +343,12 @@ extern "C" int pfem_dynamics_run_implicit(pfem_solver *s, int scheme, double dt,
             break;
         }
         if (iterations) iterations[done] = h.its;
-        launch(k_imp_correct, dim3(R.gv), dim3(kBlock), 0, s->stream, nullptr, nullptr, R.P, I.ut, I.vt.p, I.d.p, I.u, I.v.p, I.a.p);
+        imp_launch_correct(R);
         ++I.n_since;
         ++D.step;
         if ((done + 1) % every == 0) {     // a sampled step: one more product, K u_{n+1}
             launch_spmv<false>(s, I.u, I.w.p, 0, nullptr, nullptr);
-            launch(k_imp_energy, dim3(R.gv), dim3(kBlock), 0, s->stream, nullptr, nullptr, R.P, s->d_rhs.p, D.d_m.p, I.u, I.v.p, I.w.p, R.part_e);
-            launch(k_imp_row, dim3(1), dim3(kBlock), 0, s->stream, nullptr, nullptr, I.t_base + static_cast<double>(I.n_since) * dt, R.part_e,
-                   static_cast<int>(R.gv), D.n_probe, D.d_probe.p, I.u, I.v.p, D.d_hist.p + rows_done * ncol);
+            imp_launch_row(R, I.t_base + static_cast<double>(I.n_since) * dt, D.d_hist.p + rows_done * ncol);
             ++rows_done;
         }
         PFEM_TRY(check_kernel("k_imp_correct"));
@@ -347,4 +420,232 @@ extern "C" int pfem_dynamics_bench_implicit(pfem_solver *s, int scheme, double d
     }
     *us_per_iteration = 1e3 * ms / static_cast<double>(iterations);
     return PFEM_OK;
+}
+
+// ---- one launch of a kernel of the implicit stepper on vectors of the caller's (pfem_amd_diag.h) -----------------------------------
+namespace {
+
+CgCtl imp_ctl_in(const pfem_cg_ctl &c)
+{
+    CgCtl k{};
+    k.beta[0] = c.beta[0]; k.beta[1] = c.beta[1];
+    k.rn0 = c.rn0; k.ttol = c.ttol; k.rn = c.rn; k.dtol = c.dtol; k.alpha = c.alpha;
+    k.flag = c.flag; k.its = c.its; k.its_dir = c.its_dir;
+    return k;
+}
+
+void imp_ctl_out(const CgCtl &k, pfem_cg_ctl *c)
+{
+    c->beta[0] = k.beta[0]; c->beta[1] = k.beta[1];
+    c->rn0 = k.rn0; c->ttol = k.ttol; c->rn = k.rn; c->dtol = k.dtol; c->alpha = k.alpha;
+    c->flag = k.flag; c->its = k.its; c->its_dir = k.its_dir;
+}
+
+// the vectors of one implicit probe: every one an allocation of its own between quiet NaNs
+struct ImpProbe {
+    pfem_solver *s;
+    const char *who;
+    size_t rows;
+    std::vector<std::unique_ptr<ProbeBlock>> blocks;
+    std::vector<double *> outs;
+    DevBuf<CgCtl> ctl;
+    int rc = PFEM_OK;
+    ImpProbe(pfem_solver *s, const char *who, int64_t n) : s(s), who(who), rows(static_cast<size_t>(n)) {}
+    // host == nullptr: an output (NaN throughout); keep: the launch takes it as const; out: where it comes back to
+    double *add(const char *name, const double *host, size_t len, bool keep, double *out)
+    {
+        blocks.push_back(std::make_unique<ProbeBlock>());
+        outs.push_back(out);
+        if (rc == PFEM_OK) rc = probe_upload(s, *blocks.back(), name, host, len, kProbeBack, kProbeFront, keep);
+        return rc == PFEM_OK ? blocks.back()->p() : nullptr;
+    }
+    double *in(const char *name, const double *host) { return add(name, host, rows, true, nullptr); }
+    double *io(const char *name, double *host) { return add(name, host, rows, false, host); }
+    double *out(const char *name, double *host) { return add(name, nullptr, rows, false, host); }
+    int put_ctl(const pfem_cg_ctl *c)
+    {
+        PFEM_TRY(ctl.alloc(1));
+        const CgCtl k = c ? imp_ctl_in(*c) : CgCtl{};
+        PFEM_HIP(hipMemcpyAsync(ctl.p, &k, sizeof k, hipMemcpyHostToDevice, s->stream));
+        PFEM_HIP(hipStreamSynchronize(s->stream));
+        return PFEM_OK;
+    }
+    int get_ctl(pfem_cg_ctl *c)
+    {
+        CgCtl k{};
+        PFEM_HIP(hipMemcpyAsync(&k, ctl.p, sizeof k, hipMemcpyDeviceToHost, s->stream));
+        PFEM_HIP(hipStreamSynchronize(s->stream));
+        imp_ctl_out(k, c);
+        return PFEM_OK;
+    }
+    // every block back, with the check of its guards and of what had to stay
+    int finish()
+    {
+        for (size_t k = 0; k < blocks.size(); ++k) PFEM_TRY(probe_download(s, *blocks[k], outs[k], who));
+        return PFEM_OK;
+    }
+};
+
+}  // namespace
+
+extern "C" int pfem_imp_probe_predict(pfem_solver *s, int64_t n, double dt, double beta, double gamma, const double *u, const double *v, const double *a,
+                                      double *ut, double *vt)
+{
+    if (!s || n < 1 || !u || !v || !a || !ut || !vt) return PFEM_ERR_ARG;
+    PFEM_TRY(imp_check_args(PFEM_SCHEME_NEWMARK, dt, 0, beta, gamma, 0.0, 0));
+    PFEM_TRY(use_device(s));
+    ImpProbe Q(s, "pfem_imp_probe_predict", n);
+    ImpView V;
+    V.n = n;
+    V.u = Q.in("u", u); V.v = Q.in("v", v); V.a = Q.in("a", a);
+    V.ut = Q.out("ut", ut); V.vt = Q.out("vt", vt);
+    PFEM_TRY(Q.rc);
+    const ImpRun R = imp_run_of(s, V, imp_par(n, PFEM_SCHEME_NEWMARK, dt, beta, gamma, 0.0), 0, 0);
+    imp_launch_predict(R);
+    PFEM_TRY(check_kernel("k_imp_predict"));
+    return Q.finish();
+}
+
+extern "C" int pfem_imp_probe_rhs(pfem_solver *s, int scheme, int64_t n, double dt, double p0, double p1, double alpha, int n_curve, const double *ct,
+                                  const double *cl, double t_base, int64_t step, double rtol, double abstol, double dtol, const double *f, const double *m,
+                                  const double *vt, const double *w, const double *dinv, double *d, double *r, double *p, double *part_rz, double *part_zz,
+                                  double *part_mp, int *gv, pfem_cg_ctl *ctl)
+{
+    if (!s || n < 1 || n_curve < 0 || (n_curve > 0 && (!ct || !cl)) || step < 0 || !std::isfinite(t_base)) return PFEM_ERR_ARG;
+    if (!f || !m || !w || !dinv || !d || !r || !p || !part_rz || !part_zz || !part_mp || !gv || !ctl) return PFEM_ERR_ARG;
+    PFEM_TRY(imp_check_args(scheme, dt, 0, p0, p1, alpha, 0));
+    if (scheme == PFEM_SCHEME_NEWMARK && !vt) return PFEM_ERR_ARG;
+    PFEM_TRY(use_device(s));
+    ImpProbe Q(s, "pfem_imp_probe_rhs", n);
+    ImpView V;
+    V.n = n;
+    V.f = Q.in("f", f); V.m = Q.in("m", m);
+    if (scheme == PFEM_SCHEME_NEWMARK) V.vt = Q.in("vt", vt);
+    V.w = Q.in("w", w); V.dinv = Q.in("dinv", dinv);
+    V.d = Q.out("d", d); V.r = Q.out("r", r); V.p = Q.out("p", p);
+    V.part_rz = Q.add("part_rz", nullptr, kMaxGrid, false, part_rz);
+    V.part_zz = Q.add("part_zz", nullptr, kMaxGrid, false, part_zz);
+    V.part_mp = Q.add("part_mp", nullptr, kMaxGrid, false, part_mp);
+    V.hist0 = Q.add("hist0", nullptr, 1, false, nullptr);
+    V.n_curve = n_curve;
+    if (n_curve > 0) {
+        V.ct = Q.add("ct", ct, static_cast<size_t>(n_curve), true, nullptr);
+        V.cl = Q.add("cl", cl, static_cast<size_t>(n_curve), true, nullptr);
+    }
+    PFEM_TRY(Q.rc);
+    PFEM_TRY(Q.put_ctl(nullptr));
+    V.ctl = Q.ctl.p;
+    const ImpRun R = imp_run_of(s, V, imp_par(n, scheme, dt, p0, p1, alpha), 0, 0);
+    imp_launch_rhs(R, step, t_base, rtol, abstol, dtol);
+    PFEM_TRY(check_kernel("k_imp_rhs"));
+    PFEM_TRY(Q.get_ctl(ctl));
+    *gv = static_cast<int>(R.gv);
+    return Q.finish();
+}
+
+extern "C" int pfem_imp_probe_update(pfem_solver *s, int scheme, int64_t n, double dt, double p0, double p1, double alpha, pfem_cg_ctl *ctl, int it_arg,
+                                     int n_pw, const double *part_pw, int n_mp, const double *part_mp, const double *p, const double *w, const double *m,
+                                     const double *dinv, double *r, double *part_rz, double *part_zz)
+{
+    if (!s || n < 1 || !ctl || it_arg < -1 || n_pw < 1 || !part_pw || !part_mp || !p || !w || !m || !dinv || !r || !part_rz || !part_zz) return PFEM_ERR_ARG;
+    PFEM_TRY(imp_check_args(scheme, dt, 0, p0, p1, alpha, 0));
+    if (n_mp != static_cast<int>(imp_grid(n))) return PFEM_ERR_ARG;
+    PFEM_TRY(use_device(s));
+    ImpProbe Q(s, "pfem_imp_probe_update", n);
+    ImpView V;
+    V.n = n;
+    const double *d_pw = Q.add("part_pw", part_pw, static_cast<size_t>(n_pw), true, nullptr);
+    V.part_mp = Q.add("part_mp", part_mp, static_cast<size_t>(n_mp), true, nullptr);
+    V.p = Q.in("p", p); V.w = Q.in("w", w); V.m = Q.in("m", m); V.dinv = Q.in("dinv", dinv);
+    V.r = Q.io("r", r);
+    V.part_rz = Q.add("part_rz", nullptr, kMaxGrid, false, part_rz);
+    V.part_zz = Q.add("part_zz", nullptr, kMaxGrid, false, part_zz);
+    PFEM_TRY(Q.rc);
+    PFEM_TRY(Q.put_ctl(ctl));
+    V.ctl = Q.ctl.p;
+    const ImpRun R = imp_run_of(s, V, imp_par(n, scheme, dt, p0, p1, alpha), 0, 0);
+    imp_launch_update(R, it_arg, d_pw, n_pw);
+    PFEM_TRY(check_kernel("k_imp_update"));
+    PFEM_TRY(Q.get_ctl(ctl));
+    return Q.finish();
+}
+
+extern "C" int pfem_imp_probe_direction(pfem_solver *s, int scheme, int64_t n, double dt, double p0, double p1, double alpha, pfem_cg_ctl *ctl, int it_arg,
+                                        int n_parts, const double *part_rz, const double *part_zz, const double *r, const double *dinv, const double *m,
+                                        double *p, double *d, int maxits, double *part_mp)
+{
+    if (!s || n < 1 || !ctl || it_arg < -1 || !part_rz || !part_zz || !r || !dinv || !m || !p || !d || !part_mp) return PFEM_ERR_ARG;
+    PFEM_TRY(imp_check_args(scheme, dt, 0, p0, p1, alpha, 0));
+    if (n_parts != static_cast<int>(imp_grid(n))) return PFEM_ERR_ARG;
+    PFEM_TRY(use_device(s));
+    ImpProbe Q(s, "pfem_imp_probe_direction", n);
+    ImpView V;
+    V.n = n;
+    V.part_rz = Q.add("part_rz", part_rz, static_cast<size_t>(n_parts), true, nullptr);
+    V.part_zz = Q.add("part_zz", part_zz, static_cast<size_t>(n_parts), true, nullptr);
+    V.r = Q.in("r", r); V.dinv = Q.in("dinv", dinv); V.m = Q.in("m", m);
+    V.p = Q.io("p", p); V.d = Q.io("d", d);
+    V.part_mp = Q.add("part_mp", nullptr, kMaxGrid, false, part_mp);
+    PFEM_TRY(Q.rc);
+    PFEM_TRY(Q.put_ctl(ctl));
+    V.ctl = Q.ctl.p;
+    const ImpRun R = imp_run_of(s, V, imp_par(n, scheme, dt, p0, p1, alpha), 0, maxits);
+    imp_launch_direction(R, it_arg);
+    PFEM_TRY(check_kernel("k_imp_direction"));
+    PFEM_TRY(Q.get_ctl(ctl));
+    return Q.finish();
+}
+
+extern "C" int pfem_imp_probe_correct(pfem_solver *s, int scheme, int64_t n, double dt, double p0, double p1, double alpha, const double *ut, const double *vt,
+                                      const double *d, double *u, double *v, double *a)
+{
+    if (!s || n < 1 || !d || !u || !v || !a) return PFEM_ERR_ARG;
+    PFEM_TRY(imp_check_args(scheme, dt, 0, p0, p1, alpha, 0));
+    const bool nm = scheme == PFEM_SCHEME_NEWMARK;
+    if (nm && (!ut || !vt)) return PFEM_ERR_ARG;
+    PFEM_TRY(use_device(s));
+    ImpProbe Q(s, "pfem_imp_probe_correct", n);
+    ImpView V;
+    V.n = n;
+    if (nm) { V.ut = Q.in("ut", ut); V.vt = Q.in("vt", vt); }
+    V.d = Q.in("d", d);
+    V.u = nm ? Q.out("u", u) : Q.io("u", u);
+    V.v = Q.out("v", v); V.a = Q.out("a", a);
+    PFEM_TRY(Q.rc);
+    const ImpRun R = imp_run_of(s, V, imp_par(n, scheme, dt, p0, p1, alpha), 0, 0);
+    imp_launch_correct(R);
+    PFEM_TRY(check_kernel("k_imp_correct"));
+    return Q.finish();
+}
+
+extern "C" int pfem_imp_probe_energy(pfem_solver *s, int scheme, int64_t n, const double *f, const double *m, const double *u, const double *v, const double *w,
+                                     int n_probe, const int32_t *probe, double t, double *row, double *part, int *gv)
+{
+    if (!s || n < 1 || !f || !m || !u || !v || !w || n_probe < 0 || (n_probe > 0 && !probe) || !row || !part || !gv) return PFEM_ERR_ARG;
+    if (scheme != PFEM_SCHEME_NEWMARK && scheme != PFEM_SCHEME_THETA) return PFEM_ERR_ARG;
+    for (int k = 0; k < n_probe; ++k)
+        if (probe[k] < 0 || probe[k] >= n) return PFEM_ERR_ARG;
+    PFEM_TRY(use_device(s));
+    ImpProbe Q(s, "pfem_imp_probe_energy", n);
+    const unsigned g = imp_grid(n);
+    ImpView V;
+    V.n = n;
+    V.f = Q.in("f", f); V.m = Q.in("m", m); V.u = Q.in("u", u); V.v = Q.in("v", v); V.w = Q.in("w", w);
+    V.part_e = Q.add("part", nullptr, 3 * static_cast<size_t>(g), false, part);
+    double *d_row = Q.add("row", nullptr, static_cast<size_t>(4 + 2 * n_probe), false, row);
+    PFEM_TRY(Q.rc);
+    DevBuf<int32_t> d_probe;
+    PFEM_TRY(d_probe.alloc(static_cast<size_t>(std::max(n_probe, 1))));
+    if (n_probe > 0) {
+        PFEM_HIP(hipMemcpyAsync(d_probe.p, probe, sizeof(int32_t) * static_cast<size_t>(n_probe), hipMemcpyHostToDevice, s->stream));
+        PFEM_HIP(hipStreamSynchronize(s->stream));
+    }
+    V.n_probe = n_probe;
+    V.probe = d_probe.p;
+    // the two kernels read the scheme and the row count of the parameter block, nothing else of it
+    const ImpRun R = imp_run_of(s, V, scheme == PFEM_SCHEME_NEWMARK ? imp_par(n, scheme, 1.0, 0.25, 0.5, 0.0) : imp_par(n, scheme, 1.0, 1.0, 0.0, 0.0), 0, 0);
+    imp_launch_row(R, t, d_row);
+    PFEM_TRY(check_kernel("k_imp_energy"));
+    *gv = static_cast<int>(R.gv);
+    return Q.finish();
 }

@@ -369,44 +369,7 @@ extern "C" int pfem_modal_spmm(pfem_solver *s, int mb, const double *x, double *
 // ---- one launch of a modal kernel on blocks of the caller's (pfem_amd_diag.h) ---------------------------------------------------
 namespace {
 
-// A block of a probe on the device: `len` doubles, then a tile of quiet NaNs that no launch may read -- a read poisons the sums
-// -- or write: probe_download compares the fill's bits.
-struct ProbeBlock {
-    DevBuf<double> d;
-    const char *name = "";
-    size_t len = 0, guard = 0;
-};
-
-// host == nullptr: an output, NaN throughout, so that an entry the launch skips shows as well
-int probe_upload(pfem_solver *s, ProbeBlock &B, const char *name, const double *host, size_t len, size_t guard)
-{
-    B.name = name;
-    B.len = len;
-    B.guard = guard;
-    PFEM_TRY(B.d.alloc(len + guard));
-    std::vector<double> h(len + guard, std::numeric_limits<double>::quiet_NaN());
-    if (host) std::memcpy(h.data(), host, sizeof(double) * len);
-    PFEM_HIP(hipMemcpyAsync(B.d.p, h.data(), sizeof(double) * (len + guard), hipMemcpyHostToDevice, s->stream));
-    PFEM_HIP(hipStreamSynchronize(s->stream));       // (h goes out of scope)
-    return PFEM_OK;
-}
-
-// the block back (out may be nullptr) and the check of its guard tile
-int probe_download(pfem_solver *s, const ProbeBlock &B, double *out, const char *who)
-{
-    std::vector<double> h(B.len + B.guard);
-    PFEM_HIP(hipMemcpyAsync(h.data(), B.d.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, s->stream));
-    PFEM_HIP(hipStreamSynchronize(s->stream));
-    const double fill = std::numeric_limits<double>::quiet_NaN();
-    for (size_t i = B.len; i < h.size(); ++i)
-        if (std::memcmp(&h[i], &fill, sizeof(double)) != 0) {
-            set_last_error(std::string(who) + ": the launch wrote behind the last row of block " + B.name + " (guard entry " + std::to_string(i - B.len) + ")");
-            return PFEM_ERR_HIP;
-        }
-    if (out) std::memcpy(out, h.data(), sizeof(double) * B.len);
-    return PFEM_OK;
-}
-
+// (ProbeBlock, probe_upload and probe_download: pfem_probe.inc)
 bool probe_args(const pfem_solver *s, int mb, int64_t n) { return s && n >= 1 && (mb == 4 || mb == 8 || mb == 16); }
 
 }  // namespace

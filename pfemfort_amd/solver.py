@@ -821,6 +821,145 @@ class PetscSolver:
         L.check(L.lib().pfem_modal_probe_update(self._h, mb, n, _p(coef), *[_p(b) for b in B]), "pfem_modal_probe_update")
         return tuple(B)
 
+    # ---- one launch of a stepper kernel on vectors of the caller's (pfem_imp_probe_*, pfem_dyn_probe_step) ----------------------
+    MAX_GRID = 2048                  # blocks of a stepper's vector kernel at most = partials per sum
+    CTL_FIELDS = ("rn0", "ttol", "rn", "dtol", "alpha", "flag", "its", "its_dir")
+
+    @staticmethod
+    def _scheme(scheme, beta, gamma, theta):
+        if scheme == "newmark":
+            return L.SCHEME_NEWMARK, float(beta), float(gamma)
+        if scheme == "theta":
+            return L.SCHEME_THETA, 1.0 if theta is None else float(theta), 0.0
+        raise ValueError(f"scheme {scheme!r}: 'newmark' or 'theta'")
+
+    @staticmethod
+    def _vectors(vectors, n=None):
+        """contiguous float64 copies of vectors of one length ``n >= 1``"""
+        out = [np.array(v, dtype=np.float64, order="C").ravel() for v in vectors]
+        n = out[0].size if n is None else n
+        if n < 1 or any(v.size != n for v in out):
+            raise ValueError(f"vectors of one length n >= 1, not {[v.size for v in out]}")
+        return out, n
+
+    @classmethod
+    def _ctl_in(cls, ctl):
+        c = L.CgCtl()
+        c.beta[0], c.beta[1] = (float(b) for b in ctl.get("beta", (0.0, 0.0)))
+        for k in cls.CTL_FIELDS:
+            setattr(c, k, ctl.get(k, 0))
+        return c
+
+    @classmethod
+    def _ctl_out(cls, c):
+        return {"beta": (c.beta[0], c.beta[1]), **{k: getattr(c, k) for k in cls.CTL_FIELDS}}
+
+    @staticmethod
+    def _curve(curve):
+        if curve is None:
+            return 0, None, None
+        ct, cl = (_f64(a).ravel() for a in curve)
+        if ct.size != cl.size:
+            raise ValueError("t and lam differ in length")
+        return ct.size, ct, cl
+
+    def stepperProbePredict(self, dt, u, v, a, beta=0.25, gamma=0.5):
+        """One launch of Newmark's predictor (``pfem_imp_probe_predict``): ``(ut, vt)``."""
+        (u, v, a), n = self._vectors((u, v, a))
+        ut, vt = np.empty(n), np.empty(n)
+        L.check(L.lib().pfem_imp_probe_predict(self._h, n, float(dt), float(beta), float(gamma), _p(u), _p(v), _p(a), _p(ut), _p(vt)),
+                "pfem_imp_probe_predict")
+        return ut, vt
+
+    def stepperProbeRhs(self, dt, f, m, w, dinv, vt=None, scheme="newmark", beta=0.25, gamma=0.5, theta=None, alpha=0.0, curve=None, t_base=0.0,
+                        step=0, rtol=1e-5, abstol=1e-50, dtol=1e5):
+        """The right-hand side of step ``step`` and the start of its CG (``pfem_imp_probe_rhs``): a dict with ``d, r, p``, the
+        partials ``part_rz, part_zz, part_mp`` (2 048 each, NaN behind the first ``gv``), ``gv`` and the control block ``ctl``."""
+        code, p0, p1 = self._scheme(scheme, beta, gamma, theta)
+        (f, m, w, dinv), n = self._vectors((f, m, w, dinv))
+        if vt is not None:
+            (vt,), _ = self._vectors((vt,), n)
+        nc, ct, cl = self._curve(curve)
+        out = {k: np.empty(n) for k in ("d", "r", "p")}
+        out.update({k: np.empty(self.MAX_GRID) for k in ("part_rz", "part_zz", "part_mp")})
+        gv = C.c_int(0); c = L.CgCtl()
+        L.check(L.lib().pfem_imp_probe_rhs(self._h, code, n, float(dt), p0, p1, float(alpha), nc, _p(ct), _p(cl), float(t_base), int(step), float(rtol),
+                                           float(abstol), float(dtol), _p(f), _p(m), _p(vt), _p(w), _p(dinv), _p(out["d"]), _p(out["r"]), _p(out["p"]),
+                                           _p(out["part_rz"]), _p(out["part_zz"]), _p(out["part_mp"]), C.byref(gv), C.byref(c)), "pfem_imp_probe_rhs")
+        out["gv"], out["ctl"] = gv.value, self._ctl_out(c)
+        return out
+
+    def stepperProbeUpdate(self, dt, ctl, it_arg, part_pw, part_mp, p, w, m, dinv, r, scheme="newmark", beta=0.25, gamma=0.5, theta=None, alpha=0.0):
+        """One launch of the implicit CG's update kernel (``pfem_imp_probe_update``): ``(r, part_rz, part_zz, ctl)``; ``it_arg``
+        -1 is the captured graph's form."""
+        code, p0, p1 = self._scheme(scheme, beta, gamma, theta)
+        (p, w, m, dinv, r), n = self._vectors((p, w, m, dinv, r))
+        part_pw, part_mp = _f64(part_pw).ravel(), _f64(part_mp).ravel()
+        prz, pzz = np.empty(self.MAX_GRID), np.empty(self.MAX_GRID)
+        c = self._ctl_in(ctl)
+        L.check(L.lib().pfem_imp_probe_update(self._h, code, n, float(dt), p0, p1, float(alpha), C.byref(c), int(it_arg), part_pw.size, _p(part_pw),
+                                              part_mp.size, _p(part_mp), _p(p), _p(w), _p(m), _p(dinv), _p(r), _p(prz), _p(pzz)), "pfem_imp_probe_update")
+        return r, prz, pzz, self._ctl_out(c)
+
+    def stepperProbeDirection(self, dt, ctl, it_arg, part_rz, part_zz, r, dinv, m, p, d, maxits, scheme="newmark", beta=0.25, gamma=0.5, theta=None,
+                              alpha=0.0):
+        """One launch of the implicit CG's direction kernel (``pfem_imp_probe_direction``): ``(p, d, part_mp, ctl)``."""
+        code, p0, p1 = self._scheme(scheme, beta, gamma, theta)
+        (r, dinv, m, p, d), n = self._vectors((r, dinv, m, p, d))
+        part_rz, part_zz = _f64(part_rz).ravel(), _f64(part_zz).ravel()
+        if part_rz.size != part_zz.size:
+            raise ValueError("part_rz and part_zz differ in length")
+        pmp = np.empty(self.MAX_GRID)
+        c = self._ctl_in(ctl)
+        L.check(L.lib().pfem_imp_probe_direction(self._h, code, n, float(dt), p0, p1, float(alpha), C.byref(c), int(it_arg), part_rz.size, _p(part_rz),
+                                                 _p(part_zz), _p(r), _p(dinv), _p(m), _p(p), _p(d), int(maxits), _p(pmp)), "pfem_imp_probe_direction")
+        return p, d, pmp, self._ctl_out(c)
+
+    def stepperProbeCorrect(self, dt, d, u=None, ut=None, vt=None, scheme="newmark", beta=0.25, gamma=0.5, theta=None, alpha=0.0):
+        """One launch of the corrector (``pfem_imp_probe_correct``): ``(u, v, a)`` -- Newmark from ``ut, vt, d``, the
+        theta-method from ``u, d`` (``a`` comes back NaN: the kernel does not write it)."""
+        code, p0, p1 = self._scheme(scheme, beta, gamma, theta)
+        (d,), n = self._vectors((d,))
+        if scheme == "newmark":
+            (ut, vt), _ = self._vectors((ut, vt), n)
+            u = np.empty(n)
+        else:
+            (u,), _ = self._vectors((u,), n)
+            ut = vt = None
+        v, a = np.empty(n), np.empty(n)
+        L.check(L.lib().pfem_imp_probe_correct(self._h, code, n, float(dt), p0, p1, float(alpha), _p(ut), _p(vt), _p(d), _p(u), _p(v), _p(a)),
+                "pfem_imp_probe_correct")
+        return u, v, a
+
+    def stepperProbeEnergy(self, f, m, u, v, w, scheme="newmark", probes=(), t=0.0):
+        """The partials of a sampled implicit step and the history row made from them (``pfem_imp_probe_energy``):
+        ``(row, part)`` with ``part`` of shape ``3 x gv``."""
+        code = self._scheme(scheme, 0.25, 0.5, None)[0]
+        (f, m, u, v, w), n = self._vectors((f, m, u, v, w))
+        pr = np.ascontiguousarray(probes, dtype=np.int32).ravel()
+        row, part = np.empty(4 + 2 * pr.size), np.empty(3 * self.MAX_GRID)
+        gv = C.c_int(0)
+        L.check(L.lib().pfem_imp_probe_energy(self._h, code, n, _p(f), _p(m), _p(u), _p(v), _p(w), pr.size, _p(pr) if pr.size else None, float(t), _p(row),
+                                              _p(part), C.byref(gv)), "pfem_imp_probe_energy")
+        return row, part[:3 * gv.value].reshape(3, gv.value).copy()
+
+    def stepperProbeStep(self, dt, f, m, minv, w, u, up, alpha=0.0, t0=0.0, curve=None, step=0, run_start=0, sample_every=0, probes=(), use_ctl=False,
+                         ctl_step=(-7, -7)):
+        """One launch of the explicit step ``step -> step + 1`` of a run begun at ``run_start`` and, after a sampled step, of the
+        kernel that writes its history row (``pfem_dyn_probe_step``): ``(un, row or None, part, ctl_step)`` with ``part`` the
+        ``3 x nb`` partials of parity ``step & 1`` (NaN after a step that is not sampled).  ``use_ctl``: the step index comes
+        from ``ctl_step[step & 1]``, as in a replayed graph."""
+        (f, m, minv, w, u, up), n = self._vectors((f, m, minv, w, u, up))
+        nc, ct, cl = self._curve(curve)
+        pr = np.ascontiguousarray(probes, dtype=np.int32).ravel()
+        un, row, part = np.empty(n), np.empty(4 + 2 * pr.size), np.empty(3 * ((n + 1023) // 1024))
+        have, nb = C.c_int(0), C.c_int(0)
+        cs = np.array(ctl_step, dtype=np.int64)
+        L.check(L.lib().pfem_dyn_probe_step(self._h, n, float(dt), float(alpha), float(t0), nc, _p(ct), _p(cl), int(step), int(run_start), int(sample_every),
+                                            pr.size, _p(pr) if pr.size else None, int(bool(use_ctl)), _p(f), _p(m), _p(minv), _p(w), _p(u), _p(up), _p(un),
+                                            _p(row), C.byref(have), _p(part), C.byref(nb), _p(cs)), "pfem_dyn_probe_step")
+        return un, (row if have.value else None), part.reshape(3, nb.value), (int(cs[0]), int(cs[1]))
+
     def reordered(self):
         """Whether the mesh on the device is held under the internal renumbering (``pfem_solver_reordered``)."""
         v = C.c_int(0)

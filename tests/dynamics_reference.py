@@ -159,3 +159,48 @@ def poisson_box(H, n=10):
     p = MR.setup_problem(O.POISSON_TET, mesh, H.POISSON_ELEMDATA[None, :], np.zeros(mesh.nElem, np.int32))
     m, _, _ = free_dof_mass(p, 1.0)
     return mesh, p, m
+
+
+# ---- one launch of the step kernel, operation by operation (tests/test_gpu_stepper_kernels.py) --------------------------------
+BLOCK_ROWS = 1024          # rows of a block of the steppers' vector kernels: 256 threads x 4 consecutive rows
+LD = np.longdouble
+
+
+def block_sums(terms, blocks, dtype=None):
+    """The sum of ``terms`` over the rows r with (r // 1024) % blocks == b, for every b: what block b of a grid of ``blocks``
+    blocks adds up, whatever the order.  ``dtype``: the type the sums are formed in (longdouble for rounding data; integer-valued
+    float64 data below 2^53 is exact in any)."""
+    terms = np.asarray(terms)
+    dtype = terms.dtype if dtype is None else dtype
+    per = blocks * BLOCK_ROWS
+    trips = -(-terms.size // per)
+    t = np.zeros(trips * per, dtype)
+    t[:terms.size] = terms
+    return t.reshape(trips, blocks, BLOCK_ROWS).sum(axis=(0, 2))
+
+
+def step_par(dt, alpha):
+    """(c0, c1, a) of a run's parameter block: 1 / dt^2, alpha / (2 dt), c0 + c1"""
+    c0 = 1.0 / (dt * dt)
+    c1 = alpha / (2.0 * dt)
+    return c0, c1, c0 + c1
+
+
+def step_kernel(dt, alpha, lam, f, m, minv, w, u, up):
+    """k_dyn_step's rows in its written order of float64 operations: (u_{n+1}, the terms of T, of S and of W)."""
+    c0, c1, a = step_par(dt, alpha)
+    x = (((2.0 * u - up) * c0 + c1 * up) + (lam * f - w) * minv) / a
+    v = (x - u) / dt
+    return x, m * (v * v), x * w, f * x
+
+
+def step_terms_ld(dt, x, f, m, w, u):
+    """the terms of T, S, W in longdouble from the float64 u_{n+1} = x and v = (x - u) / dt the kernel formed"""
+    v = ((x - u) / dt).astype(LD)
+    return m.astype(LD) * (v * v), x.astype(LD) * w.astype(LD), f.astype(LD) * x.astype(LD)
+
+
+def step_row(t0, dt, step, T, S, W, un, u, probes):
+    """the history row of the sampled step `step` -> `step` + 1 from the totals"""
+    probes = np.asarray(probes, dtype=np.int64)
+    return np.concatenate([[t0 + float(step + 1) * dt, 0.5 * T, 0.5 * S, W], un[probes], (un[probes] - u[probes]) / dt])

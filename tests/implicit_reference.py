@@ -148,3 +148,97 @@ class ImplicitStepper:
             if sample_every and k % sample_every == 0:
                 rows.append(r + self.magnitudes if magnitudes else r)
         return np.array(rows).reshape(-1, 7 if magnitudes else 4)
+
+
+# ---- one launch of each kernel of a step, operation by operation (tests/test_gpu_stepper_kernels.py) --------------------------
+from fractions import Fraction      # noqa: E402
+
+from dynamics_reference import LD, block_sums      # noqa: E402,F401
+
+
+class Par:
+    """The parameter block of a run, by ImplicitStepper's arithmetic (which is the library's)."""
+
+    def __init__(self, scheme, dt, beta=0.25, gamma=0.5, theta=1.0, alpha=0.0):
+        self.scheme, self.dt, self.alpha, self.theta = scheme, dt, alpha, theta
+        if scheme == "newmark":
+            self.bdt2 = beta * (dt * dt)
+            self.gdt = gamma * dt
+            self.sigma = (1.0 + self.gdt * alpha) / self.bdt2
+            self.cu = (dt * dt) * (0.5 - beta)
+            self.cv = dt * (1.0 - gamma)
+        else:
+            self.sigma = 1.0 / (theta * dt)
+
+
+def predict(P, u, v, a):
+    """(ut, vt) in float64, the kernel's order"""
+    return (u + P.dt * v) + P.cu * a, v + P.cv * a
+
+
+def rhs_load_factor(P, curve, t_base, step):
+    """lambda of the right-hand side of step `step`: Newmark lambda(t_{n+1}); theta-method theta lambda(t_{n+1}) +
+    (1 - theta) lambda(t_n), the second term only where 1 - theta is not zero"""
+    tn0, tn1 = t_base + float(step) * P.dt, t_base + float(step + 1) * P.dt
+    if P.scheme == "newmark":
+        return 1.0 * load_factor(curve, tn1)
+    ln0 = 1.0 - P.theta
+    lam = P.theta * load_factor(curve, tn1)
+    return lam + ln0 * load_factor(curve, tn0) if ln0 != 0.0 else lam
+
+
+def rhs(P, lam, f, m, vt, w, dinv):
+    """(b, z) in float64: r = b, p = z, d = 0"""
+    load = lam * f - P.alpha * (m * vt) if P.scheme == "newmark" else lam * f
+    b = np.where(m > 0.0, load - w, 0.0)
+    return b, b * dinv
+
+
+def dot_terms(P, r, dinv, m, p, dtype=LD):
+    """the terms of (r, z), (z, z) with z = r dinv, and of sum sigma m p^2 with the float64 product sigma m, formed in
+    `dtype` from float64 vectors"""
+    r_, q_, p_ = r.astype(dtype), dinv.astype(dtype), p.astype(dtype)
+    z = r_ * q_
+    return r_ * z, z * z, ((P.sigma * m).astype(dtype) * p_) * p_
+
+
+def update(P, alpha, p, w, m, r, dtype=LD):
+    """r' = r - alpha ((sigma m) p + w) in `dtype`, and the magnitude |alpha| (|sigma m p| + |w|) + |r'| its rounding is
+    measured against (two fma: at most eps / 2 of each part)"""
+    sm = (P.sigma * m).astype(dtype)
+    t = sm * p.astype(dtype)
+    out = r.astype(dtype) - dtype(alpha) * (t + w.astype(dtype))
+    return out, abs(dtype(alpha)) * (np.abs(t) + np.abs(w.astype(dtype))) + np.abs(out)
+
+
+def direction(alpha, bb, r, dinv, p, d, dtype=LD):
+    """d' = d + alpha p (in longdouble: to well below eps |d'| in every row, see below); p' = bb p + (r dinv) with the float64
+    product r dinv; and the magnitude |bb p| + |r dinv| + |p'|"""
+    z = (r * dinv).astype(dtype)
+    t = dtype(bb) * p.astype(dtype)
+    ap = dtype(alpha) * p.astype(dtype)
+    d2 = d.astype(dtype) + ap
+    if dtype is LD:
+        # d' is measured against |d'| alone, and the product alpha p holds 106 bits, 64 of which longdouble keeps: where the sum
+        # cancels more than 2^8-fold the rounded product would spend the bound, so those rows are formed in exact rationals
+        for i in np.flatnonzero(np.abs(ap) > 256.0 * np.abs(d2)):
+            x = Fraction(float(alpha)) * Fraction(float(p[i])) + Fraction(float(d[i]))
+            hi = float(x)
+            d2[i] = LD(hi) + LD(float(x - Fraction(hi)))
+    p2 = t + z
+    return d2, p2, np.abs(t) + np.abs(z) + np.abs(p2)
+
+
+def correct(P, d, u=None, ut=None, vt=None):
+    """(u, v, a) in float64, the kernel's order; the theta-method has no a"""
+    if P.scheme == "newmark":
+        a = d / P.bdt2
+        return ut + d, vt + P.gdt * a, a
+    x = u + d / P.theta
+    return x, (x - u) / P.dt, None
+
+
+def energy_terms(P, f, m, u, v, w, dtype=LD):
+    """the terms of T (theta-method: m u^2), S and W"""
+    k = (v if P.scheme == "newmark" else u).astype(dtype)
+    return m.astype(dtype) * (k * k), u.astype(dtype) * w.astype(dtype), f.astype(dtype) * u.astype(dtype)

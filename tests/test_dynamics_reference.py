@@ -84,3 +84,30 @@ def test_load_curve():
     c = ([0.0, 1.0, 3.0], [0.0, 2.0, -2.0])
     assert DR.load_factor(None, 7.0) == 1.0
     assert [DR.load_factor(c, t) for t in (-1.0, 0.0, 0.5, 1.0, 2.0, 3.0, 9.0)] == [0.0, 0.0, 1.0, 2.0, 0.0, -2.0, -2.0]
+
+
+# ---- the per-operation functions of tests/test_gpu_stepper_kernels.py, chained over steps, against Stepper ----------------------
+def test_the_chained_step_kernel_is_the_stepper_bit_for_bit(box):
+    """300 damped, loaded steps under a ramp: u of every step carries Stepper's bits; T, S, W from block_sums of the terms
+    agree with Stepper's sums within (n + 3) eps x the sum of the terms' magnitudes (another order of an n-term sum)."""
+    A, m, f = box["A"], box["m"], box["p"].rhs
+    N = A.shape[0]
+    rng = np.random.default_rng(17)
+    dt, alpha, t0 = 0.9 * box["dt"], 0.3, 0.25
+    curve = ([0.0, 100.5 * dt], [0.0, 1.0])
+    st = DR.Stepper(A, f, m, dt, alpha=alpha, t0=t0, u0=rng.standard_normal(N), v0=rng.standard_normal(N), curve=curve)
+    u, up = st.u.copy(), st.up.copy()
+    for n in range(300):
+        lam = DR.load_factor(curve, t0 + float(n) * dt)
+        w = A @ u
+        x, tT, tS, tW = DR.step_kernel(dt, alpha, lam, f, m, st.minv, w, u, up)
+        t, T, S, W = st.step()
+        assert np.array_equal(x, st.u)
+        nb = -(-N // DR.BLOCK_ROWS)
+        row = DR.step_row(t0, dt, n, DR.block_sums(tT, nb).sum(), DR.block_sums(tS, nb).sum(), DR.block_sums(tW, nb).sum(), x, u, [0, N - 1])
+        assert row[0] == t and np.array_equal(row[4:6], x[[0, N - 1]]) and np.array_equal(row[6:], ((x - u) / dt)[[0, N - 1]])
+        for got, ref, mag in zip(row[1:4], (T, S, W), st.magnitudes):          # (the magnitudes carry the rows' factors 1/2)
+            assert abs(got - ref) <= (N + 3) * DR.EPS * mag
+        up, u = u, x
+    tl = DR.step_terms_ld(dt, x, f, m, w, up)
+    assert all(abs(float(a.sum()) - b.sum()) <= (N + 3) * DR.EPS * np.abs(b).sum() for a, b in zip(tl, (tT, tS, tW)))

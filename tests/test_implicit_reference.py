@@ -158,3 +158,112 @@ def test_run_implicit_refuses_bad_parameters_before_anything_else():
     for args in bad:
         assert _run(L, None, *args) == (_lib.ERR_ARG, 0, 0), args
     assert _run(L, None, N, 1e-3, 1, 0.25, 0.5, 0.0, every=-1)[0] == _lib.ERR_ARG
+
+
+# ---- the per-operation functions of tests/test_gpu_stepper_kernels.py, chained over steps, against the mirrors above -----------
+def _chain_pcg(P, A, m, dinv, b, z, rtol=1e-5, abstol=1e-50, dtol=1e5, maxits=10000):
+    """pcg_shifted's loop written with IR.update / IR.direction / IR.dot_terms in float64, the sums by np.sum"""
+    F = np.float64
+    r, p, d = b, z, np.zeros_like(b)
+    rzt, zzt, mpt = IR.dot_terms(P, r, dinv, m, p, F)
+    beta, rn0, mp = rzt.sum(), np.sqrt(zzt.sum()), mpt.sum()
+    if rn0 <= abstol:
+        return d, 0, 3
+    if beta < 0.0:
+        return d, 0, -8
+    ttol = max(rtol * rn0, abstol)
+    for it in range(maxits):
+        w = A @ p
+        pw = p @ w + mp
+        if not pw > 0.0:
+            return d, it + 1, -10
+        alpha = beta / pw
+        r, _ = IR.update(P, alpha, p, w, m, r, F)
+        rzt, zzt, _ = IR.dot_terms(P, r, dinv, m, p, F)
+        rz, rn = rzt.sum(), np.sqrt(zzt.sum())
+        flag = 2 if rn <= ttol else -4 if rn >= dtol * rn0 else -8 if rz < 0.0 else -3 if it + 1 >= maxits else 0
+        d, p2, _ = IR.direction(alpha, rz / beta, r, dinv, p, d, F)
+        if flag:
+            return d, it + 1, flag
+        p, beta = p2, rz
+        mp = IR.dot_terms(P, r, dinv, m, p, F)[2].sum()
+    return d, 0, -3
+
+
+def _chain(box, scheme, solve, steps, rtol=1e-13):
+    """`steps` steps by the per-operation functions beside the same steps of ImplicitStepper; solve: "lu" (the mirror's own
+    factorisation solves both) or "pcg" (each its own loop)"""
+    A, m, f = box["A"], box["m"], box["p"].rhs
+    N = A.shape[0]
+    rng = np.random.default_rng(21)
+    u0, v0 = rng.standard_normal(N), rng.standard_normal(N)
+    dt = 20.0 * box["dt"]
+    curve = ([0.0, 30.5 * dt], [0.0, 1.0])
+    alpha = 0.1 if scheme == "newmark" else 0.0
+    st = IR.ImplicitStepper(A, f, m, dt, scheme=scheme, theta=0.5, alpha=alpha, u0=u0, v0=v0, curve=curve, solve=solve, rtol=rtol)
+    P = IR.Par(scheme, dt, theta=0.5, alpha=alpha)
+    assert P.sigma == st.sigma
+    u, v, a = u0.copy(), v0.copy(), getattr(st, "a", None)
+    its = []
+    for n in range(steps):
+        lam = IR.rhs_load_factor(P, curve, 0.0, n)
+        if scheme == "newmark":
+            ut, vt = IR.predict(P, u, v, a)
+            b, z = IR.rhs(P, lam, f, m, vt, A @ ut, st.dinv)
+        else:
+            ut = vt = None
+            b, z = IR.rhs(P, lam, f, m, None, A @ u, st.dinv)
+        st.step()
+        if solve == "lu":
+            d = st._lu.solve(b)
+        else:
+            d, k, reason = _chain_pcg(P, A, m, st.dinv, b, z, rtol=rtol)
+            assert reason == 2
+            its.append(k)
+        u, v, a = IR.correct(P, d, u=u, ut=ut, vt=vt)
+    return st, u, v, a, its
+
+
+@pytest.mark.parametrize("scheme", ["newmark", "theta"])
+def test_the_chained_operations_are_the_mirror_bit_for_bit_around_one_solve(box, scheme):
+    """predict, rhs and correct around the mirror's own LU solve: u, v (and a) of 20 steps carry the mirror's bits"""
+    st, u, v, a, _ = _chain(box, scheme, "lu", 20)
+    assert np.array_equal(u, st.u) and np.array_equal(v, st.v)
+    if scheme == "newmark":
+        assert np.array_equal(a, st.a)
+
+
+@pytest.mark.parametrize("scheme", ["newmark", "theta"])
+def test_the_chained_cg_follows_pcg_shifted(box, scheme):
+    """the CG written with the per-operation update, direction and sums against pcg_shifted, 50 steps at rtol = 1e-13: the bound
+    of test_the_pcg_mirror_follows_the_lu_mirror (steps x rtol x kappa x magnitude), the iteration counts printed"""
+    steps = 50
+    st, u, v, a, its = _chain(box, scheme, "pcg", steps)
+    dt = 20.0 * box["dt"]
+    om_max = box["om"][-1]
+    kappa = 1.0 + (0.25 * (om_max * dt) ** 2 if scheme == "newmark" else om_max ** 2 * dt)
+    mag = np.abs(st.u).max()
+    err = np.abs(u - st.u).max()
+    diff = np.abs(np.array(its) - np.array(st.iterations)).max()
+    print(f"{scheme}: chained vs pcg_shifted {err:.3e} of {mag:.3e}, bound {steps * 1e-13 * kappa * mag:.3e}; iteration counts differ by {diff}")
+    assert err <= steps * 1e-13 * kappa * mag
+
+
+def test_block_sums_and_the_longdouble_forms():
+    """block_sums gives block b the rows r with (r // 1024) % blocks == b; the longdouble forms of update and direction are the
+    float64 ones to a rounding"""
+    rng = np.random.default_rng(3)
+    n, g = 5 * 1024 + 77, 2
+    t = rng.integers(-9, 10, n).astype(np.float64)
+    want = [t[(np.arange(n) // 1024) % g == b].sum() for b in range(g)]
+    assert np.array_equal(IR.block_sums(t, g), want) and IR.block_sums(t, g, IR.LD).dtype == IR.LD
+    assert np.finfo(IR.LD).eps <= 2.0 ** -63          # the extended type the GPU tests measure against
+    P = IR.Par("newmark", 0.5)
+    p, w, m, r, dinv, d = (rng.standard_normal(n) for _ in range(6))
+    m = np.abs(m)
+    lo, mag = IR.update(P, 0.3, p, w, m, r, np.float64)
+    hi, _ = IR.update(P, 0.3, p, w, m, r)
+    assert (np.abs(hi - lo) <= 2 * EPS * mag).all()
+    d2, p2, mag = IR.direction(0.3, 0.7, r, dinv, p, d, np.float64)
+    e2, q2, _ = IR.direction(0.3, 0.7, r, dinv, p, d)
+    assert (np.abs(q2 - p2) <= 2 * EPS * mag).all() and (np.abs(e2 - d2) <= 2 * EPS * (np.abs(d) + 0.3 * np.abs(p))).all()
