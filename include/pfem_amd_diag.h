@@ -171,6 +171,13 @@ int pfem_eval_elems(pfem_solver *s, const double *elemData, const double *timeDa
 int pfem_matrix_info(pfem_solver *s, int64_t *n_owned, int64_t *n_local, int64_t *nnz,
                      int64_t *stored_entries);
 
+/* An arbitrary CSR matrix (n = size_global rows, one rank) through the MatSetValues compat path, for tests that need a pattern
+ * or values no mesh produces: a host loop over the public calls and nothing else -- pfem_mat_set_values(INSERT_VALUES) once per
+ * row for the pattern, pfem_solver_set_zero, pfem_mat_set_values(INSERT_VALUES) once per row for the values (not ADD_VALUES: a
+ * sum with the +0.0 of set_zero loses the sign of -0.0 and the payload bit of a signalling NaN, and every bit pattern has to
+ * arrive as given).  values_only != 0: set_zero and the value loop alone, on the standing pattern.  The values are staged on
+ * the host; the next solve pushes them to the device, as for the compat calls.                                              */
+int pfem_load_csr(pfem_solver *s, int64_t n, const int64_t *rowptr, const int32_t *cols, const double *vals, int values_only);
 /* y = A_local x (both length n_local, host arrays): one launch of the CG SpMV kernel */
 int pfem_spmv(pfem_solver *s, const double *x, double *y);
 /* time `reps` back-to-back SpMV launches with HIP events on the solver's stream */

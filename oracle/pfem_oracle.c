@@ -713,6 +713,23 @@ double orc_stream_triad_gbps(int64_t n, int reps)
     return best;
 }
 
+/* y = A x in the operation order of the device's SpMV kernels (every form of them): per row, over the stored entries in
+ * ascending column order, acc = v0 * x0 rounded once, then acc = fma(v_k, x_k, acc).  fma() is libm's (one rounding); this
+ * file is compiled without contraction or reassociation, so nothing else fuses or reorders.  A row without entries gives 0. */
+void orc_spmv_chain(int64_t N, const int64_t *rowptr, const int32_t *cols, const double *vals, const double *x, double *y)
+{
+    int64_t r;
+    for (r = 0; r < N; ++r) {
+        int64_t k = rowptr[r];
+        double acc = 0.0;
+        if (k < rowptr[r + 1]) {
+            acc = vals[k] * x[cols[k]];
+            for (++k; k < rowptr[r + 1]; ++k) acc = fma(vals[k], x[cols[k]], acc);
+        }
+        y[r] = acc;
+    }
+}
+
 void orc_spmv(int64_t N, const int64_t *rowptr, const int32_t *cols, const double *vals,
               const double *x, double *y)
 {

@@ -301,6 +301,29 @@ def spmv(rowptr, cols, vals, x):
     return y
 
 
+def spmv_chain(rowptr, cols, vals, x):
+    """y = A x in the device kernels' own operation order (orc_spmv_chain): per row, ascending columns, the first product rounded,
+    every further one folded in by a correctly rounded fma.  The columns of a row must ascend."""
+    rowptr = np.ascontiguousarray(rowptr, dtype=np.int64); cols = _i32(cols); vals = _f64(vals); x = _f64(x)
+    N = len(rowptr) - 1
+    y = np.empty(N)
+    lib().orc_spmv_chain(C.c_int64(N), _p(rowptr), _p(cols), _p(vals), _p(x), _p(y))
+    return y
+
+
+def spmv_longdouble(rowptr, cols, vals, x):
+    """(A x, |A| |x|) with the products and the row sums in numpy's longdouble: the yardstick of a row's rounding-error bound."""
+    rowptr = np.asarray(rowptr, dtype=np.int64)
+    p = np.asarray(vals, dtype=np.longdouble) * np.asarray(x, dtype=np.longdouble)[np.asarray(cols)]
+    N = len(rowptr) - 1
+    y, a = np.zeros(N, np.longdouble), np.zeros(N, np.longdouble)
+    full = np.flatnonzero(rowptr[1:] > rowptr[:-1])          # (reduceat needs a non-empty segment per index)
+    if len(full):
+        y[full] = np.add.reduceat(p, rowptr[full])
+        a[full] = np.add.reduceat(np.abs(p), rowptr[full])
+    return y, a
+
+
 def pcg_jacobi(rowptr, cols, vals, b, rtol=1e-5, abstol=1e-50, dtol=1e5, maxits=10000, hist_len=0):
     N = len(rowptr) - 1
     x = np.empty(N)

@@ -198,6 +198,7 @@ SIGNATURES = {
     "pfem_get_local_to_global": [_P, _P],
     "pfem_get_csr": [_P, _P, _P, _P],
     "pfem_get_rhs": [_P, _P],
+    "pfem_load_csr": [_P, _L, _P, _P, _P, _I],
     "pfem_spmv": [_P, _P, _P],
     "pfem_bench_spmv": [_P, _I, _P],
     "pfem_get_timings": [_P, _P],

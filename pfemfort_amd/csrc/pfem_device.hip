@@ -5640,6 +5640,28 @@ extern "C" int pfem_solver_set_zero(pfem_solver *s)
     return PFEM_OK;
 }
 
+// A whole CSR matrix through the compat calls above, one row per call (include/pfem_amd_diag.h): the loop a test would
+// otherwise drive through ctypes.  Nothing here touches the device or the staging arrays itself.  The values go in with
+// INSERT_VALUES: an ADD onto the +0.0 that set_zero leaves would turn -0.0 into +0.0 and quiet a signalling NaN, and the tests
+// of the value dictionary need every bit pattern to arrive as given.
+extern "C" int pfem_load_csr(pfem_solver *s, int64_t n, const int64_t *rowptr, const int32_t *cols, const double *vals, int values_only)
+{
+    if (!s || n < 0 || n > INT_MAX || !rowptr || (n && (!cols || !vals))) return PFEM_ERR_ARG;
+    if (n != s->size_global) return PFEM_ERR_ARG;
+    for (int64_t r = 0; r < n; ++r)
+        if (rowptr[r + 1] < rowptr[r] || rowptr[r + 1] - rowptr[r] > INT_MAX) return PFEM_ERR_ARG;
+    const auto rows = [&](int mode) -> int {
+        for (int64_t r = 0; r < n; ++r) {
+            const int row = static_cast<int>(r);
+            PFEM_TRY(pfem_mat_set_values(s, 1, &row, static_cast<int>(rowptr[r + 1] - rowptr[r]), cols + rowptr[r], vals + rowptr[r], mode));
+        }
+        return PFEM_OK;
+    };
+    if (!values_only) PFEM_TRY(rows(PFEM_INSERT_VALUES));
+    PFEM_TRY(pfem_solver_set_zero(s));
+    return rows(PFEM_INSERT_VALUES);
+}
+
 extern "C" int pfem_solver_factorise(pfem_solver *s)
 {
     if (!s) return PFEM_ERR_ARG;

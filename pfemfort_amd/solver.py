@@ -996,6 +996,16 @@ class PetscSolver:
         L.check(L.lib().pfem_get_csr(self._h, _p(rowptr), _p(cols), _p(vals)), "pfem_get_csr")
         return rowptr, cols, vals
 
+    def loadCSR(self, rowptr, cols, vals, values_only=False):
+        """A whole CSR matrix through the MatSetValues compat calls, one row per call (pfem_load_csr): the INSERT_VALUES pass that
+        records the pattern, setZero, an INSERT_VALUES pass with the values (every bit pattern arrives as given); ``values_only``:
+        setZero and the value pass on the standing pattern.  The values are staged on the host like those of MatSetValues: the
+        next solve pushes them to the device."""
+        rowptr = np.ascontiguousarray(rowptr, dtype=np.int64); cols = _i32(cols); vals = _f64(vals)
+        if len(rowptr) != self.size_global + 1 or len(cols) != rowptr[-1] or len(vals) != rowptr[-1]:
+            raise ValueError("loadCSR: rowptr, cols and vals do not describe one matrix of size_global rows")
+        L.check(L.lib().pfem_load_csr(self._h, len(rowptr) - 1, _p(rowptr), _p(cols), _p(vals), int(bool(values_only))), "pfem_load_csr")
+
     def getRHS(self):
         r = np.empty(self.matrixInfo()["n_local"])
         L.check(L.lib().pfem_get_rhs(self._h, _p(r)), "pfem_get_rhs")
