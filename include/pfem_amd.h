@@ -154,6 +154,27 @@ int pfem_face_load(int kind, const double *xNode, const double *yNode, const dou
                    const double *elemData /* thickness, PFEM_ELAST_TRIA only; else may be NULL */,
                    double *F /* [nsize], zero off the side */, double *measure, double *normal /* [ndim] */);
 
+/* ---- thermal strains of one element --------------------------------------- */
+/* PFEM_ELAST_TET and PFEM_ELAST_TRIA only (PFEM_ERR_ARG for a Poisson kind).  theta[a] = T_a - T_ref at the element's nodes; the
+ * thermal strain is constant over the constant-strain element: e_th = alpha * sum_a N_a theta[a], N the Gauss-point shape values
+ * of the kind's stiffness routine, summed over a ascending.  eps_th = e_th [1,1,1,0,0,0] (tet), e_th [1,1,0] (plane stress):
+ *   F[nsize]      dvol B^T D eps_th with the D and dvol of the stiffness routine (thickness in the triangle's dvol): with one
+ *                 normal stress s = (d11 e_th + d12 e_th) + d12 e_th (tet), d11 e_th + d12 e_th (triangle),
+ *                 F[ndof*a + d] = dvol * (dN_a/dx_d * s)
+ *   sigma_th[ng]  D eps_th, each row of D in the order pfem_elem_post_thermal evaluates it (rows xx and yy are s; the tet's row
+ *                 zz is (d12 e_th + d12 e_th) + d11 e_th), zeros at the shear components: the stress of a fully restrained
+ *                 element (valC = 0) is -sigma_th bit for bit
+ * Any output may be NULL.  PFEM_ERR_NEG_JAC for an inverted element.  Shares its source (csrc/pfem_elem.hpp) with the kernels
+ * of pfem_rhs_add_thermal_load: same bits.                                                                                  */
+int pfem_elem_thermal_load(int kind, const double *xNode, const double *yNode, const double *zNode /* NULL in 2-D */,
+                           const double *elemData, double alpha, const double *theta /* [npe] */, double *F, double *sigma_th);
+/* pfem_elem_post under a thermal state: the normal strains enter D less e_th (flux = D (strain - eps_th)), scalar and fint are
+ * formed from that stress (fint = Klocal valC - F of pfem_elem_thermal_load, to rounding), grad stays the total strain B valC.
+ * With alpha = 0 or theta = 0 the outputs are pfem_elem_post's bits.  The same kinds and error codes as above.              */
+int pfem_elem_post_thermal(int kind, const double *xNode, const double *yNode, const double *zNode /* NULL in 2-D */,
+                           const double *elemData, const double *valC, double alpha, const double *theta /* [npe] */,
+                           double *grad, double *flux, double *scalar, double *fint);
+
 /* ========================================================================= */
 /* 2. driver bookkeeping, host, integer-exact (tetrapoissonparallelimpl1.F)   */
 /* ========================================================================= */
@@ -462,6 +483,38 @@ int pfem_post_error_indicator(pfem_solver *s, const double *elemData, const doub
 /* KSPBuildResidual / -ksp_monitor_true_residual: |b - K x|_2 and |b|_2 over the owned rows for the x of the last solve, K x by
  * the SpMV form in effect (pfem_solver_solve's rnorm is |M^-1 r| of the CG recurrence).  PFEM_ERR_STATE before a solve.     */
 int pfem_solver_true_residual(pfem_solver *s, double *rnorm2, double *bnorm2);
+
+/* ---- thermal strains: a temperature field that loads an elastic body ------- */
+/* PFEM_ELAST_TET and PFEM_ELAST_TRIA (PFEM_ERR_ARG on a handle of a Poisson kind), one rank and the batched path only, like the
+ * surface loads.  The state on the handle is theta = T - T_ref per node and the expansion coefficient alpha per material row; it
+ * lives until pfem_thermal_clear, the next mesh or the next pfem_pattern_build.  While it is set
+ *   pfem_post_elements        returns the stress D (strain - eps_th) and its von Mises (grad stays the total strain),
+ *   pfem_post_nodal_forces    returns sum_e (K_e u_e - F_e - F_th,e): the true reactions of a thermally loaded solution,
+ *   pfem_post_nodal_recovery (PFEM_POST_FLUX) and pfem_post_error_indicator work on that stress,
+ * with u_nodal given or NULL (pfem_elem_post_thermal per element, the element's own alpha row: same bits).  Assembly, the solve,
+ * the steppers and the modal solve do not read the state: they see the load below in the assembled right-hand side.
+ *
+ * pfem_thermal_set: theta_nodal[nNode] in the CALLER's node numbering (kept on the device in the device's node order);
+ * alpha[n_alpha], n_alpha = 1 without a material map and n_mat with one (anything else: PFEM_ERR_ARG).  Needs the pattern
+ * (PFEM_ERR_STATE before it).  Replaces a state already set.                                                                */
+int pfem_thermal_set(pfem_solver *s, int n_alpha, const double *alpha, const double *theta_nodal);
+/* The same with theta = (the nodal field of src's last solve) - T_ref, which never visits the host: src is a handle of a one-dof
+ * kind with the same nNode (else PFEM_ERR_ARG) on the same device and a solve of its pattern (else PFEM_ERR_STATE); its field is x
+ * at the free dofs and solnApplied at the constrained ones, what the post-processing calls take for u_nodal = NULL.  One kernel,
+ * one thread per node, carries it from src's device order to dst's through an index map composed on the host; dst's stream
+ * waits on an event of src's.  BOTH handles must have been given the same node numbering by the caller: only nNode is checked. */
+int pfem_thermal_set_from_solver(pfem_solver *dst, int n_alpha, const double *alpha, pfem_solver *src, double T_ref);
+/* n_alpha, alpha[n_alpha] and theta_nodal[nNode] in the caller's numbering; any output may be NULL.  PFEM_ERR_STATE: no state.  */
+int pfem_thermal_get(pfem_solver *s, int *n_alpha, double *alpha, double *theta_nodal);
+int pfem_thermal_clear(pfem_solver *s);
+/* rhs += sum_e F_th,e (pfem_elem_thermal_load) at the free dofs; constrained dofs are skipped.  Semantics of
+ * pfem_rhs_add_surface_load: after pfem_assemble (which zeroes the rhs) and before the solve, and again after every later
+ * pfem_assemble; elemData is the vector, or the table while a material map is set, exactly as pfem_assemble takes it.  With the
+ * gather form of the assembly in effect one thread per node sums its incident elements in ascending element order (no atomics,
+ * the same bits in every run) and a pass adds the node sums to the rows of the free dofs; hub nodes, and the scatter form, by an
+ * element pass with f64 atomics.  PFEM_ERR_STATE: no pattern, no thermal state, more than one rank.  PFEM_ERR_NEG_JAC: an
+ * inverted element among them (the others are added).                                                                      */
+int pfem_rhs_add_thermal_load(pfem_solver *s, const double *elemData);
 
 /* ---- explicit dynamics: lumped mass and central-difference steps ----------- */
 /* M u'' + alpha M u' + K u = lambda(t) f on the assembled system: K by the SpMV form in effect, f the assembled right-hand side

@@ -82,6 +82,8 @@ SIGNATURES = {
     "pfem_post_scalar": [_I, _P, _P],
     "pfem_elem_recovery_error": [_I] + [_P] * 8,
     "pfem_face_load": [_I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P],
+    "pfem_elem_thermal_load": [_I, _P, _P, _P, _P, _D, _P, _P, _P],
+    "pfem_elem_post_thermal": [_I, _P, _P, _P, _P, _P, _D, _P, _P, _P, _P, _P],
     "pfem_gen_box_tets": [_D, _D, _I, _D, _D, _I, _D, _D, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "pfem_dof_numbering": [_L, _I, _L, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "pfem_renumber_mesh": [_L, _I, _L, _I, _P, _P, _P, _P, _P, _P],
@@ -164,6 +166,11 @@ SIGNATURES = {
     "pfem_post_nodal_recovery": [_P, _P, _P, _I, _P, _P, _P],
     "pfem_post_error_indicator": [_P] * 6,
     "pfem_solver_true_residual": [_P, _P, _P],
+    "pfem_thermal_set": [_P, _I, _P, _P],
+    "pfem_thermal_set_from_solver": [_P, _I, _P, _P, _D],
+    "pfem_thermal_get": [_P, _P, _P, _P],
+    "pfem_thermal_clear": [_P],
+    "pfem_rhs_add_thermal_load": [_P, _P],
     "pfem_post_timings": [_P, _P, _P],
     "pfem_post_recovery_timings": [_P, _P, _P],
     "pfem_elem_lumped_mass": [_I, _P, _P, _P, _P, _D, _P],

@@ -35,6 +35,7 @@
 #include "pfem_dyn_kernels.hpp"
 #include "pfem_imp_kernels.hpp"
 #include "pfem_modal_kernels.hpp"
+#include "pfem_thermal_kernels.hpp"
 #include "pfem_peer.hpp"
 
 using namespace pfem;
@@ -554,6 +555,14 @@ struct Dyn {
     CgGraph graph;                         // kDynGraphSteps steps: 2 launches each
 };
 
+// thermal state of an elasticity handle (pfem_thermal_*, pfem_thermal.inc): lives from pfem_thermal_set / _set_from_solver to
+// pfem_thermal_clear, the next mesh or the next pattern
+struct Thermal {
+    DevBuf<double> d_theta;                // [nNode] T - T_ref, the device's node order
+    DevBuf<double> d_alpha;                // [n_mat] while a material map is set
+    std::vector<double> h_alpha;           // [1] without a map, [n_mat] with one
+};
+
 // ---------------------------------------------------------------------------
 // the solver object
 // ---------------------------------------------------------------------------
@@ -742,6 +751,7 @@ struct pfem_solver {
     int pc = PFEM_PC_JACOBI;
     std::unique_ptr<Amg> amg;      // -pc_type gamg: the hierarchy (pfem_amg.inc); rebuilt when the pattern changes
     std::unique_ptr<Dyn> dyn;      // explicit dynamics (pfem_dynamics.inc); dropped when the pattern changes
+    std::unique_ptr<Thermal> thermal;   // thermal strains (pfem_thermal.inc); dropped with the mesh and when the pattern changes
     DevBuf<double> d_binv[3];      // node-block Jacobi: row (i - r0) of the inverse diagonal block, columns 0..2
     DevBuf<double> d_r2, d_z;      // ... second residual buffer (ping-pong), z = Binv r, per-row (first row | size << 30)
     // single-reduction CG (pfem_solver_set_cg_single_reduction): z is the SpMV input (guarded), s = A z, and a second
@@ -1534,6 +1544,7 @@ extern "C" int pfem_mesh_upload(pfem_solver *s, int kind, int64_t nElem, const i
     PFEM_TRY(maybe_reorder(s, edof, xyz));
     clear_materials(s);
     clear_boundary_faces(s);
+    s->thermal.reset();
     s->have_mesh = true;
     s->have_pattern = false;
     // a neighbour plan set before this upload names dofs in the previous mesh's (internal) numbering: it has to be set again
@@ -1726,6 +1737,7 @@ extern "C" int pfem_mesh_generate_box_axis(pfem_solver *s, int kind, double x0, 
     s->h_iperm.clear();
     clear_materials(s);
     clear_boundary_faces(s);
+    s->thermal.reset();
     s->have_mesh = true;
     s->have_pattern = false;
     s->have_plan = false;
@@ -1849,6 +1861,7 @@ int alloc_vectors(pfem_solver *s)
     const size_t n = static_cast<size_t>(s->n_loc);
     s->solved = false;
     s->dyn.reset();
+    s->thermal.reset();
     PFEM_TRY(s->d_rhs.alloc(n));
     PFEM_TRY(s->d_x.alloc(n));
     PFEM_TRY(s->d_r.alloc(n));
@@ -3674,12 +3687,14 @@ int post_recovery_launch(pfem_solver *s, const PRM &prm, const double *up, int u
     PFEM_TRY(node_accumulate(
         s, "k_post_recovery", {{nodal, nn * post_components(m.kind)}, {weight, nn}},
         [&](auto kind, dim3 grid, const uint8_t *hubs) {
-            launch(k_post_recovery_gather<decltype(kind)::value, PRM>, grid, block, 0, s->stream, nullptr, nullptr, m, prm, s->d_inc_ptr.p, s->d_inc_cnt.p,
-                   s->d_inc_rec.p, hubs, up, use_grad, nodal, nscalar, weight, s->d_err.p);
+            if constexpr (prm_fits_kind<PRM>(decltype(kind)::value))
+                launch(k_post_recovery_gather<decltype(kind)::value, PRM>, grid, block, 0, s->stream, nullptr, nullptr, m, prm, s->d_inc_ptr.p, s->d_inc_cnt.p,
+                       s->d_inc_rec.p, hubs, up, use_grad, nodal, nscalar, weight, s->d_err.p);
         },
         [&](auto kind, dim3 grid, const uint8_t *hubs) {
-            launch(k_post_recovery_scatter<decltype(kind)::value, PRM>, grid, block, 0, s->stream, nullptr, nullptr, m, prm, hubs, up, use_grad, nodal, weight,
-                   s->d_err.p);
+            if constexpr (prm_fits_kind<PRM>(decltype(kind)::value))
+                launch(k_post_recovery_scatter<decltype(kind)::value, PRM>, grid, block, 0, s->stream, nullptr, nullptr, m, prm, hubs, up, use_grad, nodal, weight,
+                       s->d_err.p);
         },
         &pass));
     if (pass.gather && !pass.hubs) return PFEM_OK;      // every node's thread has divided
@@ -3707,6 +3722,28 @@ int post_nodes_to_caller(pfem_solver *s, const double *dev, int nc, double *out)
     return PFEM_OK;
 }
 
+// The element parameter of a post-processing call: with_elem_prm's, wrapped with the thermal state while one is set (a state
+// exists on the elasticity kinds only: pfem_thermal_set).  The one place that chooses between the plain and the thermal kernels.
+template <class BASE>
+ElemPrmTh<BASE> thermal_prm(const pfem_solver *s, const BASE &base)
+{
+    ElemPrmTh<BASE> p{};
+    p.base = base;
+    p.theta = s->thermal->d_theta.p;
+    p.alpha_tab = s->thermal->d_alpha.p;
+    p.alpha_one = s->thermal->h_alpha[0];
+    p.af = base.af;
+    return p;
+}
+template <class F>
+int with_post_prm(pfem_solver *s, const double *elemData, const double *timeData, F &&f)
+{
+    return with_elem_prm(s, elemData, timeData, [&](const auto &base) -> int {
+        if (s->thermal) return f(thermal_prm(s, base));
+        return f(base);
+    });
+}
+
 // the two sums of `n` block partials at part[0 ..) and part[kMaxGrid ..), into part[2 kMaxGrid] and part[2 kMaxGrid + 1] (enqueued only)
 void post_reduce_partials(pfem_solver *s, double *part, unsigned n)
 {
@@ -3724,7 +3761,7 @@ extern "C" int pfem_post_elements(pfem_solver *s, const double *elemData, const 
     PFEM_TRY(use_device(s));
     DevBuf<double> u, dg, df, ds;
     PFEM_TRY(post_nodal_field(s, u_nodal, u, "pfem_post_elements"));
-    return with_elem_prm(s, elemData, nullptr, [&](const auto &prm) -> int {
+    return with_post_prm(s, elemData, nullptr, [&](const auto &prm) -> int {
         using PRM = std::decay_t<decltype(prm)>;
         const int ng = post_components(m.kind);
         const size_t ne = static_cast<size_t>(m.nElem);
@@ -3735,8 +3772,9 @@ extern "C" int pfem_post_elements(pfem_solver *s, const double *elemData, const 
         PFEM_HIP(hipEventRecord(s->ev0, s->stream));
         if (m.nElem > 0) {
             with_kind(m.kind, [&](auto kind) {
-                launch(k_post_elements<decltype(kind)::value, PRM>, dim3(grid_for(m.nElem)), dim3(kBlock), 0, s->stream, nullptr, nullptr, m, prm, u.p, dg.p,
-                       df.p, ds.p, s->d_err.p);
+                if constexpr (prm_fits_kind<PRM>(decltype(kind)::value))
+                    launch(k_post_elements<decltype(kind)::value, PRM>, dim3(grid_for(m.nElem)), dim3(kBlock), 0, s->stream, nullptr, nullptr, m, prm, u.p, dg.p,
+                           df.p, ds.p, s->d_err.p);
             });
             PFEM_TRY(check_kernel("k_post_elements"));
         }
@@ -3760,7 +3798,7 @@ extern "C" int pfem_post_nodal_forces(pfem_solver *s, const double *elemData, co
     PFEM_TRY(use_device(s));
     DevBuf<double> u, dR;
     PFEM_TRY(post_nodal_field(s, u_nodal, u, "pfem_post_nodal_forces"));
-    return with_elem_prm(s, elemData, timeData, [&](const auto &prm) -> int {
+    return with_post_prm(s, elemData, timeData, [&](const auto &prm) -> int {
         using PRM = std::decay_t<decltype(prm)>;
         const int64_t nv = m.nNode * m.ndof;
         const dim3 block(kBlock);
@@ -3770,11 +3808,13 @@ extern "C" int pfem_post_nodal_forces(pfem_solver *s, const double *elemData, co
         PFEM_TRY(node_accumulate(
             s, "k_post_forces", {{dR.p, nv}},
             [&](auto kind, dim3 grid, const uint8_t *hubs) {
-                launch(k_post_forces_gather<decltype(kind)::value, PRM>, grid, block, 0, s->stream, nullptr, nullptr, m, prm, s->d_inc_ptr.p, s->d_inc_cnt.p,
-                       s->d_inc_rec.p, hubs, u.p, dR.p, s->d_err.p);
+                if constexpr (prm_fits_kind<PRM>(decltype(kind)::value))
+                    launch(k_post_forces_gather<decltype(kind)::value, PRM>, grid, block, 0, s->stream, nullptr, nullptr, m, prm, s->d_inc_ptr.p, s->d_inc_cnt.p,
+                           s->d_inc_rec.p, hubs, u.p, dR.p, s->d_err.p);
             },
             [&](auto kind, dim3 grid, const uint8_t *hubs) {
-                launch(k_post_forces_scatter<decltype(kind)::value, PRM>, grid, block, 0, s->stream, nullptr, nullptr, m, prm, hubs, u.p, dR.p, s->d_err.p);
+                if constexpr (prm_fits_kind<PRM>(decltype(kind)::value))
+                    launch(k_post_forces_scatter<decltype(kind)::value, PRM>, grid, block, 0, s->stream, nullptr, nullptr, m, prm, hubs, u.p, dR.p, s->d_err.p);
             }));
         PFEM_HIP(hipEventRecord(s->ev1, s->stream));
         int err = 0;
@@ -3800,7 +3840,7 @@ extern "C" int pfem_post_nodal_recovery(pfem_solver *s, const double *elemData, 
     PFEM_TRY(use_device(s));
     DevBuf<double> u, dn, dsc, dw;
     PFEM_TRY(post_nodal_field(s, u_nodal, u, "pfem_post_nodal_recovery"));
-    return with_elem_prm(s, elemData, nullptr, [&](const auto &prm) -> int {
+    return with_post_prm(s, elemData, nullptr, [&](const auto &prm) -> int {
         const int ng = post_components(m.kind);
         const size_t nn = static_cast<size_t>(m.nNode);
         PFEM_TRY(dn.alloc(std::max<size_t>(nn * ng, 1)));
@@ -3832,7 +3872,7 @@ extern "C" int pfem_post_error_indicator(pfem_solver *s, const double *elemData,
     PFEM_TRY(use_device(s));
     DevBuf<double> u, dn, dw, de, part;
     PFEM_TRY(post_nodal_field(s, u_nodal, u, "pfem_post_error_indicator"));
-    return with_elem_prm(s, elemData, nullptr, [&](const auto &prm) -> int {
+    return with_post_prm(s, elemData, nullptr, [&](const auto &prm) -> int {
         using PRM = std::decay_t<decltype(prm)>;
         const int ng = post_components(m.kind);
         const size_t nn = static_cast<size_t>(m.nNode), ne = static_cast<size_t>(m.nElem);
@@ -3845,8 +3885,9 @@ extern "C" int pfem_post_error_indicator(pfem_solver *s, const double *elemData,
         PFEM_TRY(post_recovery_launch(s, prm, u.p, 0, dn.p, nullptr, dw.p));
         const unsigned gv = vec_grid(m.nElem);
         with_kind(m.kind, [&](auto kind) {
-            launch(k_post_indicator<decltype(kind)::value, PRM>, dim3(gv), dim3(kBlock), 0, s->stream, nullptr, nullptr, m, prm, u.p, dn.p, de.p, part.p,
-                   part.p + kMaxGrid, s->d_err.p);
+            if constexpr (prm_fits_kind<PRM>(decltype(kind)::value))
+                launch(k_post_indicator<decltype(kind)::value, PRM>, dim3(gv), dim3(kBlock), 0, s->stream, nullptr, nullptr, m, prm, u.p, dn.p, de.p, part.p,
+                       part.p + kMaxGrid, s->d_err.p);
         });
         PFEM_TRY(check_kernel("k_post_indicator"));
         post_reduce_partials(s, part.p, gv);
@@ -5677,6 +5718,7 @@ extern "C" int pfem_solver_factorise(pfem_solver *s)
 #include "pfem_dynamics.inc"
 #include "pfem_implicit.inc"
 #include "pfem_modal.inc"
+#include "pfem_thermal.inc"
 
 extern "C" int pfem_solver_solve(pfem_solver *s, int *its, int *reason, double *rnorm)
 {

@@ -553,8 +553,11 @@ PFEM_HD bool poisson_tria_post(const double x[3], const double y[3], double kx, 
     return true;
 }
 
-PFEM_HD bool elast_tet_post(const double x[4], const double y[4], const double z[4], double E, double nu, const double valC[12],
-                            double grad[6], double flux[6], double &scalar, double fint[12], double &dvol)
+// TH: a thermal state is given -- the normal strains enter D less the thermal strain eth (thermal_strain below), `grad` stays
+// the total strain B valC, scalar and fint are formed from that stress.  TH = false is the routine as it always was.
+template <bool TH>
+PFEM_HD bool elast_tet_post_t(const double x[4], const double y[4], const double z[4], double E, double nu, const double valC[12],
+                              double eth, double grad[6], double flux[6], double &scalar, double fint[12], double &dvol)
 {
     TetGeom g;
     tet_geometry(x, y, z, g);
@@ -573,9 +576,10 @@ PFEM_HD bool elast_tet_post(const double x[4], const double y[4], const double z
         gyz = (gyz + g.gz[a] * v) + g.gy[a] * w;
         gzx = (gzx + g.gz[a] * u) + g.gx[a] * w;
     }
-    const double sxx = (m.d11 * exx + m.d12 * eyy) + m.d12 * ezz;
-    const double syy = (m.d12 * exx + m.d11 * eyy) + m.d12 * ezz;
-    const double szz = (m.d12 * exx + m.d12 * eyy) + m.d11 * ezz;
+    const double mxx = TH ? exx - eth : exx, myy = TH ? eyy - eth : eyy, mzz = TH ? ezz - eth : ezz;   // mechanical normal strains
+    const double sxx = (m.d11 * mxx + m.d12 * myy) + m.d12 * mzz;
+    const double syy = (m.d12 * mxx + m.d11 * myy) + m.d12 * mzz;
+    const double szz = (m.d12 * mxx + m.d12 * myy) + m.d11 * mzz;
     const double txy = m.gsh * gxy, tyz = m.gsh * gyz, tzx = m.gsh * gzx;
     grad[0] = exx;  grad[1] = eyy;  grad[2] = ezz;  grad[3] = gxy;  grad[4] = gyz;  grad[5] = gzx;
     flux[0] = sxx;  flux[1] = syy;  flux[2] = szz;  flux[3] = txy;  flux[4] = tyz;  flux[5] = tzx;
@@ -591,8 +595,15 @@ PFEM_HD bool elast_tet_post(const double x[4], const double y[4], const double z
     return true;
 }
 
-PFEM_HD bool elast_tria_post(const double x[3], const double y[3], double E, double nu, double thick, const double valC[6],
-                             double grad[3], double flux[3], double &scalar, double fint[6], double &dvol)
+PFEM_HD bool elast_tet_post(const double x[4], const double y[4], const double z[4], double E, double nu, const double valC[12],
+                            double grad[6], double flux[6], double &scalar, double fint[12], double &dvol)
+{
+    return elast_tet_post_t<false>(x, y, z, E, nu, valC, 0.0, grad, flux, scalar, fint, dvol);
+}
+
+template <bool TH>
+PFEM_HD bool elast_tria_post_t(const double x[3], const double y[3], double E, double nu, double thick, const double valC[6],
+                               double eth, double grad[3], double flux[3], double &scalar, double fint[6], double &dvol)
 {
     TriaGeom g;
     tria_geometry(x, y, g);
@@ -606,7 +617,8 @@ PFEM_HD bool elast_tria_post(const double x[3], const double y[3], double E, dou
         eyy = eyy + g.gy[a] * valC[2 * a + 1];
         gxy = (gxy + g.gy[a] * valC[2 * a]) + g.gx[a] * valC[2 * a + 1];
     }
-    const double sxx = m.d11 * exx + m.d12 * eyy, syy = m.d12 * exx + m.d11 * eyy, txy = m.d33 * gxy;
+    const double mxx = TH ? exx - eth : exx, myy = TH ? eyy - eth : eyy;       // no thermal shear: D(3,3) sees gxy as it is
+    const double sxx = m.d11 * mxx + m.d12 * myy, syy = m.d12 * mxx + m.d11 * myy, txy = m.d33 * gxy;
     grad[0] = exx;  grad[1] = eyy;  grad[2] = gxy;
     flux[0] = sxx;  flux[1] = syy;  flux[2] = txy;
     scalar = sqrt(((sxx * sxx - sxx * syy) + syy * syy) + 3.0 * (txy * txy));
@@ -616,6 +628,12 @@ PFEM_HD bool elast_tria_post(const double x[3], const double y[3], double E, dou
         fint[2 * a + 1] = dvol * (g.gy[a] * syy + g.gx[a] * txy);
     }
     return true;
+}
+
+PFEM_HD bool elast_tria_post(const double x[3], const double y[3], double E, double nu, double thick, const double valC[6],
+                             double grad[3], double flux[3], double &scalar, double fint[6], double &dvol)
+{
+    return elast_tria_post_t<false>(x, y, E, nu, thick, valC, 0.0, grad, flux, scalar, fint, dvol);
 }
 
 // components of grad / flux per kind (kinds as in include/pfem_amd.h: 1 Poisson tria, 2 Poisson tet, 3 elasticity tet,
@@ -635,14 +653,109 @@ PFEM_HD bool elem_post(int kind, const double *x, const double *y, const double 
     }
 }
 
+// ---------------------------------------------------------------------------
+// Thermal strains of the elasticity kinds (pfem_elem_thermal_load / pfem_thermal_* / pfem_rhs_add_thermal_load; DESIGN.md
+// section 14).  theta[a] = T_a - T_ref at the element's nodes.  The thermal strain is constant over a constant-strain element:
+//     thetabar = sum over a ascending of N(a) * theta[a], from 0.0, N the Gauss-point shape values of the kind's stiffness
+//                routine (the tet's literal quarters, tria_shape_gp);        e_th = alpha * thetabar
+// eps_th = e_th [1,1,1,0,0,0] (tet), e_th [1,1,0] (plane stress): no thermal shear.
+// ---------------------------------------------------------------------------
+PFEM_HD double thermal_strain(int kind, double alpha, const double *theta)
+{
+    double tb = 0.0;
+    if (kind == 3) {
+        const double N[4] = {0.25, 0.25, 1.0 - 0.25 - 0.25 - 0.25, 0.25};
+#pragma unroll
+        for (int a = 0; a < 4; ++a) tb = tb + N[a] * theta[a];
+    } else {
+        double N[3];
+        tria_shape_gp(N);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) tb = tb + N[a] * theta[a];
+    }
+    return alpha * tb;
+}
+
+// elem_post under a thermal state: the stress is D (eps - eps_th) for the elasticity kinds; the Poisson kinds have no such state
+PFEM_HD bool elem_post_th(int kind, const double *x, const double *y, const double *z, const double *ed, const double *valC, double eth,
+                          double *grad, double *flux, double &scalar, double *fint, double &dvol)
+{
+    switch (kind) {
+    case 3: return elast_tet_post_t<true>(x, y, z, ed[0], ed[1], valC, eth, grad, flux, scalar, fint, dvol);
+    case 5: return elast_tria_post_t<true>(x, y, ed[0], ed[1], ed[2], valC, eth, grad, flux, scalar, fint, dvol);
+    default: return elem_post(kind, x, y, z, ed, valC, grad, flux, scalar, fint, dvol);
+    }
+}
+
+// The thermal load F = dvol B^T D eps_th of one element and sig[ng] = D eps_th, geometry, D and dvol those of the stiffness
+// routine (thickness in the triangle's dvol).  The load takes ONE normal stress
+//     tet       s = (d11 * e_th + d12 * e_th) + d12 * e_th          F[3a + d] = dvol * (g_d[a] * s)
+//     triangle  s = d11 * e_th + d12 * e_th                         F[2a] = dvol * (gx[a] * s),  F[2a + 1] = dvol * (gy[a] * s)
+// sig[c] is row c of D on eps_th in that row's own order of elem_post_th, so that with valC = 0 the stress of elem_post_th is
+// -sig bit for bit: rows xx and yy give s (an addition commutes), the tet's row zz is (d12 * e_th + d12 * e_th) + d11 * e_th;
+// zeros at the shear components.  F and sig may be null.  false: a negative Jacobian.  Kinds 3 and 5 only (the caller checks).
+PFEM_HD bool elem_thermal_load(int kind, const double *x, const double *y, const double *z, const double *ed, double eth, double *F,
+                               double *sig)
+{
+    if (kind == 3) {
+        TetGeom g;
+        tet_geometry(x, y, z, g);
+        if (g.jac < 0.0) return false;
+        const double dvol = kGaussWtTet * g.jac;
+        const ElastMat m = elast_material(ed[0], ed[1]);
+        const double s = (m.d11 * eth + m.d12 * eth) + m.d12 * eth;
+        if (F) {
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                F[3 * a + 0] = dvol * (g.gx[a] * s);
+                F[3 * a + 1] = dvol * (g.gy[a] * s);
+                F[3 * a + 2] = dvol * (g.gz[a] * s);
+            }
+        }
+        if (sig) {
+            sig[0] = s;
+            sig[1] = (m.d12 * eth + m.d11 * eth) + m.d12 * eth;
+            sig[2] = (m.d12 * eth + m.d12 * eth) + m.d11 * eth;
+            sig[3] = sig[4] = sig[5] = 0.0;
+        }
+        return true;
+    }
+    TriaGeom g;
+    tria_geometry(x, y, g);
+    if (g.jac < 0.0) return false;
+    const double dvol = 0.5 * (g.jac * ed[2]);
+    const Elast2dMat m = elast2d_material(ed[0], ed[1]);
+    const double s = m.d11 * eth + m.d12 * eth;
+    if (F) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            F[2 * a] = dvol * (g.gx[a] * s);
+            F[2 * a + 1] = dvol * (g.gy[a] * s);
+        }
+    }
+    if (sig) {
+        sig[0] = s;
+        sig[1] = m.d12 * eth + m.d11 * eth;
+        sig[2] = 0.0;
+    }
+    return true;
+}
+
 // r = Klocal valC - Flocal for the Klocal, Flocal the assembly takes from the stiffness routine with valC = 0 (af scales the
 // Poisson matrices only; source term -6 of the Poisson tet, body force of the elasticity kinds): the element's share of the
 // nodal forces R of pfem_post_nodal_forces.
-PFEM_HD bool elem_nodal_forces(int kind, const double *x, const double *y, const double *z, const double *ed, double af,
-                               const double *valC, double *r)
+// TH: under a thermal state (elem_post_th) -- fint is then dvol B^T D (eps - eps_th) = Klocal valC - F_th, so r is the element's
+// share of sum (K_e u_e - F_e - F_th,e).
+template <bool TH>
+PFEM_HD bool elem_nodal_forces_t(int kind, const double *x, const double *y, const double *z, const double *ed, double af,
+                                 const double *valC, double eth, double *r)
 {
     double grad[6], flux[6], scalar, dvol;
-    if (!elem_post(kind, x, y, z, ed, valC, grad, flux, scalar, r, dvol)) return false;
+    if (TH) {
+        if (!elem_post_th(kind, x, y, z, ed, valC, eth, grad, flux, scalar, r, dvol)) return false;
+    } else {
+        if (!elem_post(kind, x, y, z, ed, valC, grad, flux, scalar, r, dvol)) return false;
+    }
     if (kind == 2) {
         const double N[4] = {0.25, 0.25, 1.0 - 0.25 - 0.25 - 0.25, 0.25};
 #pragma unroll
@@ -671,6 +784,12 @@ PFEM_HD bool elem_nodal_forces(int kind, const double *x, const double *y, const
     return true;
 }
 
+PFEM_HD bool elem_nodal_forces(int kind, const double *x, const double *y, const double *z, const double *ed, double af,
+                               const double *valC, double *r)
+{
+    return elem_nodal_forces_t<false>(kind, x, y, z, ed, af, valC, 0.0, r);
+}
+
 // ---------------------------------------------------------------------------
 // Nodal recovery and the Zienkiewicz-Zhu indicator (pfem_post_nodal_recovery / pfem_post_error_indicator)
 // ---------------------------------------------------------------------------
@@ -695,11 +814,17 @@ PFEM_HD double post_scalar(int kind, const double *f)
 //     eta2 = V / ((d+1)(d+2)) sum_c [ sum_a d_ac^2 + (sum_a d_ac)^2 ],        fnorm2 = V sum_c f_c^2,
 // a plain Euclidean sum over the ng stored Voigt components (no D^-1 weighting; shear components count once, as stored).  V is
 // elem_post's dvol (area x thickness for the plane-stress triangle).  nodal == flux at every node gives eta2 = 0.0 exactly.
-PFEM_HD bool elem_recovery_error(int kind, const double *x, const double *y, const double *z, const double *ed, const double *valC,
-                                 const double *nodal, double &eta2, double &fnorm2)
+// TH: sigma_h is the stress of elem_post_th.
+template <bool TH>
+PFEM_HD bool elem_recovery_error_t(int kind, const double *x, const double *y, const double *z, const double *ed, const double *valC,
+                                   double eth, const double *nodal, double &eta2, double &fnorm2)
 {
     double grad[6], flux[6], fint[12], scalar, dvol;
-    if (!elem_post(kind, x, y, z, ed, valC, grad, flux, scalar, fint, dvol)) return false;
+    if (TH) {
+        if (!elem_post_th(kind, x, y, z, ed, valC, eth, grad, flux, scalar, fint, dvol)) return false;
+    } else {
+        if (!elem_post(kind, x, y, z, ed, valC, grad, flux, scalar, fint, dvol)) return false;
+    }
     const int ng = post_components(kind), npe = (kind == 2 || kind == 3) ? 4 : 3;
     double e2 = 0.0, f2 = 0.0;
     for (int c = 0; c < ng; ++c) {
@@ -715,6 +840,12 @@ PFEM_HD bool elem_recovery_error(int kind, const double *x, const double *y, con
     eta2 = dvol / static_cast<double>(npe * (npe + 1)) * e2;
     fnorm2 = dvol * f2;
     return true;
+}
+
+PFEM_HD bool elem_recovery_error(int kind, const double *x, const double *y, const double *z, const double *ed, const double *valC,
+                                 const double *nodal, double &eta2, double &fnorm2)
+{
+    return elem_recovery_error_t<false>(kind, x, y, z, ed, valC, 0.0, nodal, eta2, fnorm2);
 }
 
 // ---------------------------------------------------------------------------

@@ -175,6 +175,40 @@ extern "C" int pfem_face_load(int kind, const double *xNode, const double *yNode
     return PFEM_OK;
 }
 
+// Thermal load of one element of an elasticity kind (pfem_elem.hpp: thermal_strain / elem_thermal_load) from theta[a] = T_a - T_ref
+// at its nodes: F = dvol B^T D eps_th and sigma_th = D eps_th; any output may be NULL.
+extern "C" int pfem_elem_thermal_load(int kind, const double *xNode, const double *yNode, const double *zNode, const double *elemData,
+                                      double alpha, const double *theta, double *F, double *sigma_th)
+{
+    if (kind != PFEM_ELAST_TET && kind != PFEM_ELAST_TRIA) return PFEM_ERR_ARG;
+    if (!xNode || !yNode || !elemData || !theta) return PFEM_ERR_ARG;
+    if (kind == PFEM_ELAST_TET && !zNode) return PFEM_ERR_ARG;
+    double f[12], sg[6];
+    if (!elem_thermal_load(kind, xNode, yNode, zNode, elemData, thermal_strain(kind, alpha, theta), f, sg)) return PFEM_ERR_NEG_JAC;
+    if (F) std::copy(f, f + kind_npelem(kind) * kind_ndof(kind), F);
+    if (sigma_th) std::copy(sg, sg + post_components(kind), sigma_th);
+    return PFEM_OK;
+}
+
+// pfem_elem_post of an elasticity kind under a thermal state (pfem_elem.hpp: elem_post_th): the stress is D (strain - eps_th),
+// scalar and fint are formed from it, grad stays the total strain.
+extern "C" int pfem_elem_post_thermal(int kind, const double *xNode, const double *yNode, const double *zNode, const double *elemData,
+                                      const double *valC, double alpha, const double *theta, double *grad, double *flux, double *scalar,
+                                      double *fint)
+{
+    if (kind != PFEM_ELAST_TET && kind != PFEM_ELAST_TRIA) return PFEM_ERR_ARG;
+    if (!xNode || !yNode || !elemData || !valC || !theta) return PFEM_ERR_ARG;
+    if (kind == PFEM_ELAST_TET && !zNode) return PFEM_ERR_ARG;
+    double g[6], f[6], sc = 0.0, fi[12], dvol = 0.0;
+    if (!elem_post_th(kind, xNode, yNode, zNode, elemData, valC, thermal_strain(kind, alpha, theta), g, f, sc, fi, dvol)) return PFEM_ERR_NEG_JAC;
+    const int ng = post_components(kind), nsize = kind_npelem(kind) * kind_ndof(kind);
+    if (grad) std::copy(g, g + ng, grad);
+    if (flux) std::copy(f, f + ng, flux);
+    if (scalar) *scalar = sc;
+    if (fint) std::copy(fi, fi + nsize, fint);
+    return PFEM_OK;
+}
+
 // ---------------------------------------------------------------------------
 // 2. structured box mesh (genTetra.cpp)
 // ---------------------------------------------------------------------------

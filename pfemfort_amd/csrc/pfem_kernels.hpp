@@ -71,6 +71,24 @@ __device__ __forceinline__ uint8_t prm_mat(const ElemPrmTab &p, AtVisit at) { re
 template <class AT> __device__ __forceinline__ const double *prm_at(const ElemPrm &p, AT) { return p.ed; }
 template <class AT> __device__ __forceinline__ const double *prm_at(const ElemPrmTab &p, AT at) { return p.tab + p.stride * static_cast<int>(prm_mat(p, at)); }
 
+// Either of the two under a thermal state (pfem_thermal_set): the base parameter, theta = T - T_ref per node
+// in the device's node order, and the expansion coefficient by material row (one value without a map).  The post-processing
+// kernels are instantiated with it for the two elasticity kinds only; with PRM = ElemPrm / ElemPrmTab they are the code they were.
+template <class BASE> struct ElemPrmTh {
+    BASE base;
+    const double *theta;       // [nNode]
+    const double *alpha_tab;   // [n_mat] on the device; nullptr with BASE = ElemPrm: `alpha_one`
+    double alpha_one;
+    double af;                 // base.af
+};
+template <class PRM> struct PrmThermal { static constexpr bool value = false; };
+template <class BASE> struct PrmThermal<ElemPrmTh<BASE>> { static constexpr bool value = true; };
+template <class BASE, class AT> __device__ __forceinline__ const double *prm_at(const ElemPrmTh<BASE> &p, AT at) { return prm_at(p.base, at); }
+template <class AT> __device__ __forceinline__ double prm_alpha(const ElemPrmTh<ElemPrm> &p, AT) { return p.alpha_one; }
+template <class AT> __device__ __forceinline__ double prm_alpha(const ElemPrmTh<ElemPrmTab> &p, AT at) { return p.alpha_tab[prm_mat(p.base, at)]; }
+// the kinds a kernel template is instantiated for with PRM
+template <class PRM> constexpr bool prm_fits_kind(int kind) { return !PrmThermal<PRM>::value || kind == PFEM_ELAST_TET || kind == PFEM_ELAST_TRIA; }
+
 // The node numbers of one visit of node n from its 16-byte incidence record: rc.x, rc.y, rc.z are the element's other nodes in
 // the element's order, and the sign bits of rc.x and rc.y spell the place a that n itself has there (k_build_inc_rec).
 __device__ __forceinline__ int inc_rec_place(const int4 &rc)
@@ -1720,6 +1738,44 @@ __device__ __forceinline__ void post_load_elem(const MeshDev &m, const int nd[4]
     }
 }
 
+// The element routines of pfem_elem.hpp for the parameter type of the kernel: elem_post / elem_nodal_forces / elem_recovery_error,
+// or -- PRM = ElemPrmTh<.> -- their forms under a thermal state, with e_th = alpha(row) * thetabar of the element's nodes nd.
+template <int KIND, class PRM, class AT>
+__device__ __forceinline__ double prm_thermal_strain(const PRM &prm, AT at, const int nd[4])
+{
+    double th[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int a = 0; a < PostKind<KIND>::NPE; ++a) th[a] = prm.theta[nd[a]];
+    return thermal_strain(KIND, prm_alpha(prm, at), th);
+}
+template <int KIND, class PRM, class AT>
+__device__ __forceinline__ bool post_elem(const PRM &prm, AT at, const int nd[4], const double *x, const double *y, const double *z,
+                                          const double *valC, double *g, double *f, double &sc, double *fint, double &dvol)
+{
+    if constexpr (PrmThermal<PRM>::value)
+        return elem_post_th(KIND, x, y, z, prm_at(prm, at), valC, prm_thermal_strain<KIND>(prm, at, nd), g, f, sc, fint, dvol);
+    else
+        return elem_post(KIND, x, y, z, prm_at(prm, at), valC, g, f, sc, fint, dvol);
+}
+template <int KIND, class PRM, class AT>
+__device__ __forceinline__ bool post_nodal_forces(const PRM &prm, AT at, const int nd[4], const double *x, const double *y, const double *z,
+                                                  const double *valC, double *r)
+{
+    if constexpr (PrmThermal<PRM>::value)
+        return elem_nodal_forces_t<true>(KIND, x, y, z, prm_at(prm, at), prm.af, valC, prm_thermal_strain<KIND>(prm, at, nd), r);
+    else
+        return elem_nodal_forces(KIND, x, y, z, prm_at(prm, at), prm.af, valC, r);
+}
+template <int KIND, class PRM, class AT>
+__device__ __forceinline__ bool post_recovery_error(const PRM &prm, AT at, const int nd[4], const double *x, const double *y, const double *z,
+                                                    const double *valC, const double *nf, double &e2, double &f2)
+{
+    if constexpr (PrmThermal<PRM>::value)
+        return elem_recovery_error_t<true>(KIND, x, y, z, prm_at(prm, at), valC, prm_thermal_strain<KIND>(prm, at, nd), nf, e2, f2);
+    else
+        return elem_recovery_error(KIND, x, y, z, prm_at(prm, at), valC, nf, e2, f2);
+}
+
 // One thread per element: gradient / strain, flux / stress, |q| / von Mises, stored SoA (component-major, coalesced in e).
 template <int KIND, class PRM = ElemPrm>
 __global__ void __launch_bounds__(kBlock) k_post_elements(MeshDev m, PRM prm, const double *__restrict__ u, double *__restrict__ grad,
@@ -1733,7 +1789,7 @@ __global__ void __launch_bounds__(kBlock) k_post_elements(MeshDev m, PRM prm, co
     for (int a = 0; a < P::NPE; ++a) nd[a] = m.conn[a * m.nElem + e];
     double x[4], y[4], z[4], valC[12], g[6], f[6], fint[12], sc, dvol;
     post_load_elem<KIND>(m, nd, u, x, y, z, valC);
-    if (!elem_post(KIND, x, y, z, prm_at(prm, AtElem{e}), valC, g, f, sc, fint, dvol)) { atomicMax(err, PFEM_ERR_NEG_JAC); return; }
+    if (!post_elem<KIND>(prm, AtElem{e}, nd, x, y, z, valC, g, f, sc, fint, dvol)) { atomicMax(err, PFEM_ERR_NEG_JAC); return; }
 #pragma unroll
     for (int c = 0; c < P::NG; ++c) {
         if (grad) grad[c * m.nElem + e] = g[c];
@@ -1767,7 +1823,10 @@ __global__ void __launch_bounds__(kBlock) k_post_forces_gather(MeshDev m, PRM pr
         const int a = inc_rec_nodes<P::NPE>(inc_rec[t], n, nd);
         double x[4], y[4], z[4], valC[12], r[12];
         post_load_elem<KIND>(m, nd, u, x, y, z, valC);
-        if (!elem_nodal_forces(KIND, x, y, z, prm_at(prm, AtVisit{t}), prm.af, valC, r)) { atomicMax(err, PFEM_ERR_NEG_JAC); continue; }
+        bool ok;             // (the choice is made here: through post_nodal_forces alone the plain instantiations' registers moved)
+        if constexpr (PrmThermal<PRM>::value) ok = post_nodal_forces<KIND>(prm, AtVisit{t}, nd, x, y, z, valC, r);
+        else ok = elem_nodal_forces(KIND, x, y, z, prm_at(prm, AtVisit{t}), prm.af, valC, r);
+        if (!ok) { atomicMax(err, PFEM_ERR_NEG_JAC); continue; }
 #pragma unroll
         for (int i = 0; i < P::NPE; ++i)
             if (i == a) {
@@ -1798,7 +1857,7 @@ __global__ void __launch_bounds__(kBlock) k_post_forces_scatter(MeshDev m, PRM p
     if (!any) return;
     double x[4], y[4], z[4], valC[12], r[12];
     post_load_elem<KIND>(m, nd, u, x, y, z, valC);
-    if (!elem_nodal_forces(KIND, x, y, z, prm_at(prm, AtElem{e}), prm.af, valC, r)) { atomicMax(err, PFEM_ERR_NEG_JAC); return; }
+    if (!post_nodal_forces<KIND>(prm, AtElem{e}, nd, x, y, z, valC, r)) { atomicMax(err, PFEM_ERR_NEG_JAC); return; }
 #pragma unroll
     for (int a = 0; a < P::NPE; ++a) {
         if (only_nodes && !only_nodes[nd[a]]) continue;
@@ -1833,7 +1892,7 @@ __global__ void __launch_bounds__(kBlock) k_post_recovery_gather(MeshDev m, PRM 
         inc_rec_nodes<P::NPE>(inc_rec[t], n, nd);
         double x[4], y[4], z[4], valC[12], g[6], f[6], fint[12], sc, dvol;
         post_load_elem<KIND>(m, nd, u, x, y, z, valC);
-        if (!elem_post(KIND, x, y, z, prm_at(prm, AtVisit{t}), valC, g, f, sc, fint, dvol)) { atomicMax(err, PFEM_ERR_NEG_JAC); continue; }
+        if (!post_elem<KIND>(prm, AtVisit{t}, nd, x, y, z, valC, g, f, sc, fint, dvol)) { atomicMax(err, PFEM_ERR_NEG_JAC); continue; }
 #pragma unroll
         for (int c = 0; c < P::NG; ++c) acc[c] += dvol * (use_grad ? g[c] : f[c]);
         wsum += dvol;
@@ -1869,7 +1928,7 @@ __global__ void __launch_bounds__(kBlock) k_post_recovery_scatter(MeshDev m, PRM
     if (!any) return;
     double x[4], y[4], z[4], valC[12], g[6], f[6], fint[12], sc, dvol;
     post_load_elem<KIND>(m, nd, u, x, y, z, valC);
-    if (!elem_post(KIND, x, y, z, prm_at(prm, AtElem{e}), valC, g, f, sc, fint, dvol)) { atomicMax(err, PFEM_ERR_NEG_JAC); return; }
+    if (!post_elem<KIND>(prm, AtElem{e}, nd, x, y, z, valC, g, f, sc, fint, dvol)) { atomicMax(err, PFEM_ERR_NEG_JAC); return; }
 #pragma unroll
     for (int a = 0; a < P::NPE; ++a) {
         if (only_nodes && !only_nodes[nd[a]]) continue;
@@ -1919,7 +1978,7 @@ __global__ void __launch_bounds__(kBlock) k_post_indicator(MeshDev m, PRM prm, c
         for (int a = 0; a < P::NPE; ++a)
 #pragma unroll
             for (int c = 0; c < P::NG; ++c) nf[a * P::NG + c] = nodal[static_cast<int64_t>(nd[a]) * P::NG + c];
-        if (!elem_recovery_error(KIND, x, y, z, prm_at(prm, AtElem{e}), valC, nf, e2, f2)) { atomicMax(err, PFEM_ERR_NEG_JAC); continue; }
+        if (!post_recovery_error<KIND>(prm, AtElem{e}, nd, x, y, z, valC, nf, e2, f2)) { atomicMax(err, PFEM_ERR_NEG_JAC); continue; }
         if (eta2) eta2[e] = e2;
         se += e2;
         sf += f2;

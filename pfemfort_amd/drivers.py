@@ -122,10 +122,23 @@ def _materials(mesh, elemData, elem_mat):
     return table, ids
 
 
-def _run(kind, mesh, elemData, timeData, mode, rtol, maxits, verbose, pc=None, elem_mat=None, surface_loads=None):
+def _thermal(solver, dm, mesh, thermal, elemData):
+    """``thermal=(alpha, theta)`` of the elastic drivers: ``theta (nNode,)`` = T - T_ref by the MESH's node ids, ``alpha`` a number
+    or one per material row.  Sets the state on the handle (the solver's nodes are the NEW ids) and adds the load to the rhs."""
+    alpha, theta = thermal
+    theta = np.asarray(theta, dtype=np.float64).ravel()
+    if theta.size != mesh.nNode:
+        raise ValueError(f"thermal: theta of {theta.size} entries, one per node ({mesh.nNode}) wanted")
+    solver.setThermal(alpha, theta[dm.node_map_get_old])
+    solver.addThermalLoad(elemData)
+
+
+def _run(kind, mesh, elemData, timeData, mode, rtol, maxits, verbose, pc=None, elem_mat=None, surface_loads=None, thermal=None):
     elemData, elem_mat = _materials(mesh, elemData, elem_mat)
     if surface_loads and mode != "batched":
         raise ValueError("surface_loads need mode=\"batched\": the sides are integrated on the device")
+    if thermal is not None and mode != "batched":
+        raise ValueError("thermal needs mode=\"batched\": the load is integrated on the device")
     dm, conn_new, xyz_new, edof = _setup(kind, mesh)
     N = dm.size_global
     nsize = edof.shape[0]
@@ -188,6 +201,8 @@ def _run(kind, mesh, elemData, timeData, mode, rtol, maxits, verbose, pc=None, e
                 solver.VecSetValues([g], [v], ADD_VALUES)
     for sl in surface_loads or ():                                       # loads on sides (elem, side) of mesh.conn's elements:
         solver.addSurfaceLoad(sl["elem"], sl["side"], sl["load"], sl["values"], sl.get("layout"), elemData)   # not in the reference
+    if thermal is not None:                                              # thermal strains: state on the handle, load on the rhs
+        _thermal(solver, dm, mesh, thermal, elemData)
     t0 = time.perf_counter()                                             # :898
     its, reason, rnorm = solver.factoriseAndSolve()                      # :900
     timers["solve_s"] = time.perf_counter() - t0                         # :902
@@ -268,7 +283,7 @@ class ExplicitResult:
 
 
 def _run_explicit(kind, mesh, elemData, density, dt, n_steps, load_curve, alpha, sample_every, probes, u0, v0, elem_mat, surface_loads,
-                  check_dt, integrator="central", implicit=None, rtol=1e-5, maxits=10000):
+                  check_dt, integrator="central", implicit=None, rtol=1e-5, maxits=10000, thermal=None):
     """The explicit PROGRAMs on one rank: the set-up of ``_run(mode="batched")`` up to the assembled K and load, the lumped
     mass, then the time loop on the device in place of the solve: central differences, or -- ``integrator`` "newmark" /
     "theta" with the keywords of ``PetscSolver.implicitRun`` in ``implicit`` -- implicit steps, to which ``check_dt`` does not
@@ -292,6 +307,8 @@ def _run_explicit(kind, mesh, elemData, density, dt, n_steps, load_curve, alpha,
         solver.addNodalForces(dm.NodeDofArrayNew[dm.node_map_get_new[mesh.force_node], mesh.force_dof], mesh.force_val)
     for sl in surface_loads or ():
         solver.addSurfaceLoad(sl["elem"], sl["side"], sl["load"], sl["values"], sl.get("layout"), elemData)
+    if thermal is not None:
+        _thermal(solver, dm, mesh, thermal, elemData)
     total_mass = solver.dynamicsSetup(elemData, density)                  # MassMatrixLinear* loop (triaelasticityexplicit.F:883-922)
     timers["assembly_s"] = time.perf_counter() - t0
     stable = solver.stableDt()
@@ -327,7 +344,9 @@ _EXPLICIT_NOTE = """
     from the thickness slot), so no golden fixture of these PROGRAMs is taken.  ``load_curve=(t, lam)`` scales the whole
     assembled load (the Dirichlet lift included); ``alpha`` is mass-proportional damping; ``probes`` are ``(node, dof)``
     pairs; ``history`` has a row every ``sample_every`` steps.  ``dt`` above ``PetscSolver.stableDt()`` is a ``ValueError``
-    unless ``check_dt=False``.  One rank, ``mode="batched"`` only.
+    unless ``check_dt=False``.  One rank, ``mode="batched"`` only.  ``thermal=(alpha, theta)`` adds the thermal load of
+    ``theta`` = T - T_ref per mesh node to the assembled load (scaled by the load curve with the rest) and leaves the state on the
+    handle for the post-processing calls.
 
     ``integrator="central"`` (the default) is the PROGRAM's scheme.  ``integrator="newmark"`` takes the same steps with Newmark
     (``beta``, ``gamma``; ``PetscSolver.implicitRun``): unconditionally stable for ``gamma >= 1/2``, ``beta >= (gamma + 1/2)^2 / 4``,
@@ -339,7 +358,7 @@ _EXPLICIT_NOTE = """
 def tetraelasticityexplicit(mesh: H.Mesh | str, dt=0.01, n_steps=100, elemData=None, density=7800.0, load_curve=None, alpha=0.0,
                             sample_every=0, probes=None, u0=None, v0=None, elem_mat=None, surface_loads=None,
                             check_dt=True, integrator="central", beta=0.25, gamma=0.5,
-                            rtol=1e-5, maxits=10000) -> ExplicitResult:
+                            rtol=1e-5, maxits=10000, thermal=None) -> ExplicitResult:
     """PROGRAM of tetraelasticityexplicit.F on one rank: central differences on a lumped mass, E = 207e9, nu = 0.3, density
     7800, no body force, dt = 0.01 and stepsMax = 100 steps as the PROGRAM sets them (:910-934: its loop runs while
     ``stepsCompleted < stepsMax .OR. timeNow < 10 dt``; its dt is far above the stable step of any steel mesh of metre size:
@@ -348,13 +367,14 @@ def tetraelasticityexplicit(mesh: H.Mesh | str, dt=0.01, n_steps=100, elemData=N
         mesh = H.read_mesh(mesh)
     ed = np.array([207.0e9, H._f32(0.3), 1.0, 0.0, 0.0, 0.0]) if elemData is None else elemData
     return _run_explicit(L.ELAST_TET, mesh, ed, density, dt, n_steps, load_curve, alpha, sample_every, probes, u0, v0, elem_mat,
-                         surface_loads, check_dt, integrator, {"beta": beta, "gamma": gamma} if integrator == "newmark" else None, rtol, maxits)
+                         surface_loads, check_dt, integrator, {"beta": beta, "gamma": gamma} if integrator == "newmark" else None, rtol, maxits,
+                         thermal)
 
 
 def triaelasticityexplicit(mesh: H.Mesh | str, dt=0.0002, n_steps=50000, elemData=None, density=10.0, load_curve="reference", alpha=0.0,
                            sample_every=0, probes=None, u0=None, v0=None, elem_mat=None, surface_loads=None,
                            check_dt=True, integrator="central", beta=0.25, gamma=0.5,
-                           rtol=1e-5, maxits=10000) -> ExplicitResult:
+                           rtol=1e-5, maxits=10000, thermal=None) -> ExplicitResult:
     """PROGRAM of triaelasticityexplicit.F on one rank: E = 200, nu = 0.3, density 10, unit thickness, body force (1, 0) while
     t <= 0.1 (:872-876, :974-977), dt = 2e-4, 50 000 steps (:958-962).  ``load_curve="reference"`` is that switch as a curve:
     lambda = 1 up to t = 0.1, 0 from the next step on."""
@@ -366,7 +386,8 @@ def triaelasticityexplicit(mesh: H.Mesh | str, dt=0.0002, n_steps=50000, elemDat
             raise ValueError(load_curve)
         load_curve = ([0.1, 0.1 + 0.5 * dt], [1.0, 0.0])
     return _run_explicit(L.ELAST_TRIA, mesh, ed, density, dt, n_steps, load_curve, alpha, sample_every, probes, u0, v0, elem_mat,
-                         surface_loads, check_dt, integrator, {"beta": beta, "gamma": gamma} if integrator == "newmark" else None, rtol, maxits)
+                         surface_loads, check_dt, integrator, {"beta": beta, "gamma": gamma} if integrator == "newmark" else None, rtol, maxits,
+                         thermal)
 
 
 tetraelasticityexplicit.__doc__ += _EXPLICIT_NOTE
@@ -408,12 +429,16 @@ def tetrapoissonparallelimpl1(mesh: H.Mesh | str, mode="batched", rtol=1e-5, max
 
 
 def tetraelasticityparallelimpl1(mesh: H.Mesh | str, mode="batched", rtol=1e-5, maxits=10000, verbose=False, pc=None, elem_mat=None,
-                                 elemData=None, surface_loads=None) -> Result:
-    """PROGRAM of tetraelasticityparallelimpl1.F (body force only; DESIGN.md 'deviations')."""
+                                 elemData=None, surface_loads=None, thermal=None) -> Result:
+    """PROGRAM of tetraelasticityparallelimpl1.F (body force only; DESIGN.md 'deviations').  ``thermal=(alpha, theta)`` (both
+    elastic drivers; not part of the reference): ``theta (nNode,)`` = T - T_ref by the mesh's node ids and the expansion
+    coefficient (one per material row with ``elem_mat``), handed to ``PetscSolver.setThermal`` / ``addThermalLoad`` after the
+    surface loads; the state stays on the handle, so ``write_outputs(fields=True)`` and the post-processing calls of the result's
+    solver give the stress ``D (strain - alpha thetabar)``."""
     if isinstance(mesh, str):
         mesh = H.read_mesh(mesh)
     ed = H.ELAST_ELEMDATA if elemData is None else elemData
-    return _run(L.ELAST_TET, mesh, ed, H.TIMEDATA, mode, rtol, maxits, verbose, pc, elem_mat, surface_loads)       # :894-902
+    return _run(L.ELAST_TET, mesh, ed, H.TIMEDATA, mode, rtol, maxits, verbose, pc, elem_mat, surface_loads, thermal)       # :894-902
 
 
 def triapoissonserialimpl1(mesh: H.Mesh | str, rtol=1e-5, maxits=10000, verbose=False, pc=None, elem_mat=None, elemData=None,
@@ -437,11 +462,11 @@ def triapoissonparallelimpl1(mesh: H.Mesh | str, mode="batched", rtol=1e-5, maxi
 
 
 def triaelasticityparallelimpl1(mesh: H.Mesh | str, mode="batched", rtol=1e-5, maxits=10000, verbose=False, pc=None, elem_mat=None,
-                                elemData=None, surface_loads=None) -> Result:
+                                elemData=None, surface_loads=None, thermal=None) -> Result:
     """PROGRAM of triaelasticityparallelimpl1.F on one rank with its intended semantics (the committed
     driver USEs a module that does not exist and reads thick/bforce uninitialised: SURVEY A.3#7, 8f.1):
     plane stress, E = 240.565, nu = 0.3 (REAL(4) literals), unit thickness, nodal forces from ForceBC."""
     if isinstance(mesh, str):
         mesh = H.read_mesh(mesh)
     ed = H.ELAST2D_ELEMDATA if elemData is None else elemData
-    return _run(L.ELAST_TRIA, mesh, ed, H.TIMEDATA, mode, rtol, maxits, verbose, pc, elem_mat, surface_loads)
+    return _run(L.ELAST_TRIA, mesh, ed, H.TIMEDATA, mode, rtol, maxits, verbose, pc, elem_mat, surface_loads, thermal)

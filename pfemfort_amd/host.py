@@ -298,6 +298,33 @@ def FaceLoad(kind, xNode, yNode, zNode, side, load=None, values=None, elemData=N
     return F, meas.value, nrm
 
 
+def ThermalLoad(kind, xNode, yNode, zNode, elemData, alpha, theta):
+    """Thermal load of one element of an elasticity kind (pfem_elem_thermal_load): ``theta (npe,)`` = T - T_ref at its nodes,
+    the thermal strain ``e_th = alpha * sum_a N_a theta_a`` constant over the element.  Returns ``(F[nsize], sigma_th[ng])`` --
+    ``dvol B^T D eps_th`` and ``D eps_th``.  ``zNode`` is None in 2-D."""
+    if kind not in L.NG:                                     # the library says so
+        L.check(L.lib().pfem_elem_thermal_load(int(kind), None, None, None, None, 0.0, None, None, None), "pfem_elem_thermal_load")
+    F = np.empty(L.NPELEM[kind] * L.NDOF[kind]); sg = np.empty(L.NG[kind])
+    z = None if zNode is None else _f64(zNode)
+    ed = None if elemData is None else _f64(elemData)
+    th = None if theta is None else _f64(theta).ravel()
+    L.check(L.lib().pfem_elem_thermal_load(kind, _p(_f64(xNode)), _p(_f64(yNode)), _p(z), _p(ed), float(alpha), _p(th), _p(F), _p(sg)),
+            "pfem_elem_thermal_load")
+    return F, sg
+
+
+def ElementPostThermal(kind, xNode, yNode, zNode, elemData, valC, alpha, theta):
+    """``ElementPost`` of an elasticity kind under a thermal state (pfem_elem_post_thermal): the stress is
+    ``D (strain - eps_th)``, von Mises and ``fint`` are formed from it, ``grad`` stays the total strain."""
+    ng = L.NG[kind]
+    grad = np.empty(ng); flux = np.empty(ng); sc = C.c_double(0); fint = np.empty(L.NPELEM[kind] * L.NDOF[kind])
+    z = None if zNode is None else _f64(zNode)
+    ed = None if elemData is None else _f64(elemData)
+    L.check(L.lib().pfem_elem_post_thermal(kind, _p(_f64(xNode)), _p(_f64(yNode)), _p(z), _p(ed), _p(_f64(valC)), float(alpha),
+                                           _p(_f64(theta).ravel()), _p(grad), _p(flux), C.byref(sc), _p(fint)), "pfem_elem_post_thermal")
+    return grad, flux, sc.value, fint
+
+
 def PostScalar(kind, flux):
     """The scalar of ``ElementPost`` on any flux / stress vector(s) of the kind, ``(ng,)`` or ``(n, ng)`` in the stored Voigt
     order (pfem_post_scalar): ``|q|``, von Mises, the plane-stress form."""

@@ -617,6 +617,43 @@ class PetscSolver:
         L.check(L.lib().pfem_solver_true_residual(self._h, C.byref(r), C.byref(b)), "pfem_solver_true_residual")
         return r.value, b.value
 
+    # ---- thermal strains (elasticity kinds, one rank, batched path; include/pfem_amd.h "thermal strains") ------------
+    def setThermal(self, alpha, theta):
+        """Thermal state of an elastic body: ``theta (nNode,)`` = T - T_ref in the caller's node numbering and the expansion
+        coefficient ``alpha`` (a number, or one per material row while a map is set).  Needs the pattern; lives until
+        ``clearThermal``, a new mesh or a new pattern.  While it is set ``elementFields``, ``nodalForces``, ``nodalRecovery``
+        and ``errorIndicator`` work on the stress ``D (strain - alpha thetabar)``; ``addThermalLoad`` puts the load on the rhs."""
+        a = _f64(np.atleast_1d(alpha)).ravel()
+        th = _f64(theta).ravel()
+        if getattr(self, "kind", None) is not None and th.size != self.nNode:
+            raise ValueError(f"theta of {th.size} entries: one per node ({self.nNode}) wanted")
+        L.check(L.lib().pfem_thermal_set(self._h, a.size, _p(a), _p(th)), "pfem_thermal_set")
+
+    def setThermalFrom(self, poisson_solver, alpha, T_ref=0.0):
+        """The same with ``theta`` = the nodal field of ``poisson_solver``'s last solve minus ``T_ref``, handed over on the device
+        (a handle of a one-dof kind with the same nodes IN THE SAME NUMBERING as this one's -- only their count is checked)."""
+        a = _f64(np.atleast_1d(alpha)).ravel()
+        L.check(L.lib().pfem_thermal_set_from_solver(self._h, a.size, _p(a), poisson_solver._h, float(T_ref)),
+                "pfem_thermal_set_from_solver")
+
+    def getThermal(self):
+        """``(alpha (n_alpha,), theta (nNode,))`` of the state in effect, theta in the caller's node numbering."""
+        n = C.c_int(0)
+        L.check(L.lib().pfem_thermal_get(self._h, C.byref(n), None, None), "pfem_thermal_get")
+        a = np.empty(n.value); th = np.empty(self.nNode)
+        L.check(L.lib().pfem_thermal_get(self._h, C.byref(n), _p(a), _p(th)), "pfem_thermal_get")
+        return a, th
+
+    def clearThermal(self):
+        L.check(L.lib().pfem_thermal_clear(self._h), "pfem_thermal_clear")
+
+    def addThermalLoad(self, elemData):
+        """rhs += the thermal load ``sum_e dvol B^T D eps_th`` of the state in effect at the free dofs; after ``assemble`` (which
+        zeroes the rhs), before the solve.  ``elemData`` as ``assemble`` takes it (``host.ThermalLoad`` is the per-element
+        mirror)."""
+        ed = self._elem_data(elemData)
+        L.check(L.lib().pfem_rhs_add_thermal_load(self._h, _p(ed)), "pfem_rhs_add_thermal_load")
+
     # ---- explicit dynamics (one rank, batched path; include/pfem_amd.h "explicit dynamics") ------------
     def dynamicsSetup(self, elemData, density):
         """Lumped mass on the device from ``density`` (a number, or one per material row while a map is set) and the mesh;
