@@ -100,9 +100,9 @@ inline void amg_spmv(pfem_solver *s, const Amg &M, AmgLevel &L, const double *x,
         launch_spmv<false>(s, x, y, 0, nullptr, nullptr);
     } else {
         const SellDev A = amg_sell(s, L, amg_rows(M, L));
-        if (M.coupled && L.vd_ok && L.vcodes.p)         // the level's values as dictionary codes (amg_value_codes): same product, 4 + 2 B a slot
-            hipLaunchKernelGGL(k_amg_spmv_pack_vd, dim3(spmv_grid(A.n_slices)), dim3(kBlock), sizeof(double) * static_cast<size_t>(L.vd_n), s->stream, A,
-                               static_cast<const uint16_t *>(L.vcodes.p), static_cast<const double *>(L.vdict.p), L.vd_n, x, y,
+        if (M.coupled && L.vd.ok && L.vcodes.p)         // the level's values as dictionary codes (amg_value_codes): same product, 4 + 2 B a slot
+            hipLaunchKernelGGL(k_amg_spmv_pack_vd, dim3(spmv_grid(A.n_slices)), dim3(kBlock), sizeof(double) * static_cast<size_t>(L.vd.n), s->stream, A,
+                               static_cast<const uint16_t *>(L.vcodes.p), static_cast<const double *>(L.vd.dict.p), L.vd.n, x, y,
                                ShareSum{nullptr, nullptr, nullptr, nullptr}, static_cast<double *>(nullptr), static_cast<const CgCtl *>(nullptr));
         else
         hipLaunchKernelGGL(k_spmv<false>, dim3(spmv_grid(A.n_slices)), dim3(kBlock), 0, s->stream, A, x, y,
@@ -786,10 +786,9 @@ inline bool amg_galerkin_on(hipStream_t st, pfem_solver *s, const AmgLevel &L, A
             X.ratio_out = C.t.p;
             C.bound_fresh = true;
             if (bound) { X.bound = bound; X.zero = zero; C.bound_done = true; }
-            if (vstate && C.vd_have_dict && C.vd_hash_ok && C.vhash.p && C.vcodes.p && C.vcodes.n >= static_cast<size_t>(C.stored) && !C.vd_refused) {
-                const VdState reset{C.vd_n, 0, 0, 0};
-                (void)hipMemcpyAsync(vstate, &reset, sizeof reset, hipMemcpyHostToDevice, st);
-                X.vhash = C.vhash.p;
+            if (vstate && C.vd.have && C.vd.hash_ok && C.vd.hash.p && C.vcodes.p && C.vcodes.n >= static_cast<size_t>(C.stored) && !C.vd.refused) {
+                (void)C.vd.enqueue_against_standing(st, vstate);
+                X.vhash = C.vd.hash.p;
                 X.codes = C.vcodes.p;
                 X.vstate = vstate;
                 C.vd_direct = true;
@@ -797,10 +796,10 @@ inline bool amg_galerkin_on(hipStream_t st, pfem_solver *s, const AmgLevel &L, A
         }
         if (from_codes) {
             hipLaunchKernelGGL(k_lat_galerkin_codes, dim3(static_cast<unsigned>((C.n_loc + kLatGalThreads - 1) / kLatGalThreads)), dim3(kLatGalThreads),
-                               sizeof(double) * static_cast<size_t>(std::max(s->vd_n, 1)), st, C.n_loc, static_cast<const int32_t *>(L.mem_ptr.p),
+                               sizeof(double) * static_cast<size_t>(std::max(s->vd.n, 1)), st, C.n_loc, static_cast<const int32_t *>(L.mem_ptr.p),
                                static_cast<const int32_t *>(L.mem_idx.p), static_cast<const int64_t *>(s->d_rslice_off.p),
                                static_cast<const unsigned long long *>(s->d_vcodes.p), static_cast<const uint32_t *>(L.glat.p),
-                               static_cast<const double *>(s->d_vdict.p), s->vd_n, static_cast<const uint32_t *>(L.code_mask.p),
+                               static_cast<const double *>(s->vd.dict.p), s->vd.n, static_cast<const uint32_t *>(L.code_mask.p),
                                static_cast<const int64_t *>(C.slice_off.p), C.vals.p, X);
             return C.bound_done;
         }
@@ -2892,7 +2891,7 @@ constexpr int64_t kAmgVdMinSlots = 1 << 20;
 // Column codes of the levels that take the value dictionary (one rank; AmgLevel::ccodes): do level l's fused products read them?
 inline bool amg_level_col_codes(const Amg &M, const AmgLevel &L)
 {
-    return M.col_codes && !M.coupled && L.vd_ok && L.vcodes.p && L.cc_ok && L.ccodes.p && L.cdelta.p && L.cd_n > 0;
+    return M.col_codes && !M.coupled && L.vd.ok && L.vcodes.p && L.cc_ok && L.ccodes.p && L.cdelta.p && L.cd_n > 0;
 }
 // Built once per hierarchy, at the first numeric phase that wants them (PFEM_AMG_COL_CODES not 0): the distinct  col - row  of the
 // level collected (k_cc_collect; more than the cap -- 256, PFEM_AMG_COL_CODES_MAX=<n> lowers it -- refuses the level), sorted, every
@@ -2940,7 +2939,7 @@ void amg_column_codes_verdict(Amg &M, int l, const CcState &v)
         L.cd_n = v.count;
         L.cc_ok = true;
     }
-    if (std::getenv("PFEM_VD_VERBOSE"))
+    if (vd_verbose())
         std::fprintf(stderr, "  column codes, level %d: %d distinct offsets among %lld slots%s\n", l, v.count, static_cast<long long>(L.stored),
                      L.cc_ok ? "" : (v.mismatch ? " -- the check failed, the level keeps its int32 columns" : " -- the level keeps its int32 columns"));
 }
@@ -2952,7 +2951,7 @@ inline bool amg_vd_candidate(const Amg &M, int l)
 {
     const AmgLevel &L = *M.lev[static_cast<size_t>(l)];
     return valdict_enabled() && (M.coupled || (M.fused && M.cheb_degree == 2)) && !L.fine && L.bs == 1 && !L.gptr.p && L.stored >= kAmgVdMinSlots &&
-           !L.vd_refused && (M.tail_from < 0 || l < M.tail_from);
+           !L.vd.refused && (M.tail_from < 0 || l < M.tail_from);
 }
 
 int amg_value_codes(pfem_solver *s, Amg &M)
@@ -2961,7 +2960,7 @@ int amg_value_codes(pfem_solver *s, Amg &M)
     std::vector<int> cand;
     for (int l = 1; l + 1 < nl; ++l) {
         if (amg_vd_candidate(M, l)) cand.push_back(l);
-        else M.lev[static_cast<size_t>(l)]->vd_ok = false;
+        else M.lev[static_cast<size_t>(l)]->vd.skip();
     }
     if (cand.empty()) return PFEM_OK;
     if (M.vd_states.n < static_cast<size_t>(nl)) PFEM_TRY(M.vd_states.alloc(static_cast<size_t>(nl)));
@@ -2976,12 +2975,7 @@ int amg_value_codes(pfem_solver *s, Amg &M)
             cc_wait.push_back(l);
         }
     std::vector<CcState> cst(cc_wait.empty() ? 0 : static_cast<size_t>(nl));
-    auto encode = [&](AmgLevel &L, int l) -> int {
-        const unsigned grid = static_cast<unsigned>(std::min<int64_t>((L.stored + kBlock - 1) / kBlock, 4096));
-        hipLaunchKernelGGL(k_vd_encode16, dim3(grid), dim3(kBlock), sizeof(uint64_t) * kVdMax, s->stream, static_cast<const double *>(L.vals.p), L.stored,
-                           static_cast<const double *>(L.vdict.p), M.vd_states.p + l, L.vcodes.p);
-        return check_kernel("k_vd_encode16");
-    };
+    auto encode = [&](AmgLevel &L, int l) -> int { return enqueue_vd_encode16(s->stream, L.vd, L.vals.p, L.stored, M.vd_states.p + l, L.vcodes.p); };
     auto read_states = [&]() -> int {
         PFEM_HIP(hipMemcpyAsync(st.data(), M.vd_states.p, sizeof(VdState) * static_cast<size_t>(nl), hipMemcpyDeviceToHost, s->stream));
         if (!cc_wait.empty())
@@ -2996,13 +2990,11 @@ int amg_value_codes(pfem_solver *s, Amg &M)
     for (int l : cand) {
         AmgLevel &L = *M.lev[static_cast<size_t>(l)];
         if (L.vcodes.n < static_cast<size_t>(L.stored)) PFEM_TRY(L.vcodes.alloc(static_cast<size_t>(L.stored)));
-        if (!L.vdict.p) PFEM_TRY(L.vdict.alloc(kVdMax));
-        if (!L.vtable.p) PFEM_TRY(L.vtable.alloc(kVdTable));
-        if (L.vd_have_dict && L.vd_direct) {
+        PFEM_TRY(L.vd.reserve(false));
+        if (L.vd.have && L.vd_direct) {
             any_old = true;               // (the Galerkin product wrote the codes itself: only its verdict is read)
-        } else if (L.vd_have_dict) {
-            const VdState reset{L.vd_n, 0, 0, 0};
-            PFEM_HIP(hipMemcpyAsync(M.vd_states.p + l, &reset, sizeof reset, hipMemcpyHostToDevice, s->stream));
+        } else if (L.vd.have) {
+            PFEM_TRY(L.vd.enqueue_against_standing(s->stream, M.vd_states.p + l));
             PFEM_TRY(encode(L, l));
             any_old = true;
         } else {
@@ -3014,9 +3006,9 @@ int amg_value_codes(pfem_solver *s, Amg &M)
         PFEM_TRY(read_states());
         for (int l : cand) {
             AmgLevel &L = *M.lev[static_cast<size_t>(l)];
-            if (!L.vd_have_dict) continue;
+            if (!L.vd.have) continue;
             if (st[static_cast<size_t>(l)].miss) build.push_back(l);
-            else { L.vd_ok = true; L.vd_hash_ok = L.vhash.p != nullptr; }
+            else L.vd.accept(st[static_cast<size_t>(l)], true);          // ({n, 0, 0, 0}: the dictionary that stood)
         }
     }
     if (build.empty()) return PFEM_OK;
@@ -3024,35 +3016,25 @@ int amg_value_codes(pfem_solver *s, Amg &M)
         AmgLevel &L = *M.lev[static_cast<size_t>(l)];
         const unsigned grid = static_cast<unsigned>(std::min<int64_t>((L.stored + kBlock - 1) / kBlock, 4096));
         // with the dictionary's hash table: from the next solve on the Galerkin product looks the codes up itself (k_lat_galerkin)
-        L.vd_hash_ok = false;
-        if (!L.vhash.p) PFEM_TRY(L.vhash.alloc(kVdHashSlots));
-        PFEM_TRY(enqueue_value_dictionary(s->stream, L.vals.p, L.stored, grid, L.vtable.p, L.vdict.p, M.vd_states.p + l));
-        PFEM_TRY(enqueue_vd_hash(s->stream, L.vdict.p, M.vd_states.p + l, L.vhash.p));
+        PFEM_TRY(L.vd.reserve(true));
+        PFEM_TRY(L.vd.enqueue_build(s->stream, L.vals.p, L.stored, grid, M.vd_states.p + l, true));
         PFEM_TRY(encode(L, l));
     }
     PFEM_TRY(read_states());
     for (int l : build) {
         AmgLevel &L = *M.lev[static_cast<size_t>(l)];
         const VdState &v = st[static_cast<size_t>(l)];
-        if (!vd_usable(v)) {
-            L.vd_ok = L.vd_have_dict = L.vd_hash_ok = false;
-            L.vd_refused = true;              // (for this hierarchy)
-        } else {
-            L.vd_n = v.count;
-            L.vd_have_dict = true;
-            L.vd_ok = true;
-            L.vd_hash_ok = L.vhash.p != nullptr;
-        }
-        if (std::getenv("PFEM_VD_VERBOSE"))
+        const bool taken = L.vd.accept(v, true);          // (or refused for this hierarchy)
+        if (vd_verbose())
             std::fprintf(stderr, "  value dictionary, level %d: %d distinct values among %lld slots%s\n", l, v.count, static_cast<long long>(L.stored),
-                         L.vd_ok ? "" : " -- the level keeps its fp64 values");
+                         taken ? "" : " -- the level keeps its fp64 values");
     }
     return PFEM_OK;
 }
 
 // May this numeric phase form level 1 from the SpMV's value codes (k_lat_galerkin_codes)?  One rank, a scalar brick level 0 without
 // hubs whose SpMV streams the 4-row relative-group form's 16-bit codes, and those codes hold THIS assembly's values against the
-// dictionary in place: vd_ok && vd_current, the very condition under which the CG's products read them (refresh_group_vals ran
+// dictionary in place: vd.ok && vd_current, the very condition under which the CG's products read them (refresh_group_vals ran
 // before this phase: the assembly kernel's verdict has been read and was clean, or k_vd_encode has encoded the fp64 copy).  A step
 // whose assembly met a value the dictionary lacked keeps the fp64 kernel (vd_miss_step), like every other case.
 // PFEM_AMG_GALERKIN_CODES=0 (read at every phase): k_lat_galerkin as before.  The form's lattice codes are built at the first yes.
@@ -3065,8 +3047,8 @@ int amg_level0_codes(pfem_solver *s, Amg &M, AmgLevel &L, bool *yes)
         s->n_hubs != 0 || L.stored != s->stored || L.glat_refused)
         return PFEM_OK;
     const SpmvForm f = spmv_form(s);
-    if (!valdict_enabled() || f.layout != SpmvLayout::Rel4 || !f.codes || !s->vd_have_dict || s->vd_miss_step ||
-        s->vd_n < 1 || s->vd_n > kVdMax || !s->d_vcodes.p || !s->d_vdict.p || !s->d_relk.p || !s->d_rslice_off.p || s->r_stored < 1 ||
+    if (!valdict_enabled() || f.layout != SpmvLayout::Rel4 || !f.codes || !s->vd.have || s->vd_miss_step ||
+        s->vd.n < 1 || s->vd.n > kVdMax || !s->d_vcodes.p || !s->vd.dict.p || !s->d_relk.p || !s->d_rslice_off.p || s->r_stored < 1 ||
         s->d_vcodes.n < static_cast<size_t>(s->r_stored))
         return PFEM_OK;
     if (!L.glat.p || L.glat_for != s->r_stored) {
@@ -3192,7 +3174,7 @@ int amg_numeric(pfem_solver *s, Amg &M, bool overlap)
                 if (amg_galerkin_on(stream_of(l + 1), s, L, C, A, !M.rbm && !M.coupled, M.vd_states.p ? M.vd_states.p + (l + 1) : nullptr, from_codes, mine ? C.lam.p : nullptr, next) && next)
                     zeroed = l + 2;
                 if (from_codes) M.galerkin_from_codes = true;
-                if (l == 0 && std::getenv("PFEM_VD_VERBOSE"))
+                if (l == 0 && vd_verbose())
                     std::fprintf(stderr, "  gamg numeric: level 1 summed from %s\n", from_codes ? "the SpMV's value codes" : "the fp64 row form");
             }
         }
@@ -3254,9 +3236,9 @@ int amg_smooth(pfem_solver *s, const Amg &M, AmgLevel &L, const double *b, bool 
                                    s->d_send.p, ctl);
         } else {
             const SellDev A = amg_sell(s, L, nv);
-            if (L.vd_ok && L.vcodes.p)
-                hipLaunchKernelGGL(k_amg_spmv_pack_vd, dim3(spmv_grid(A.n_slices)), dim3(kBlock), sizeof(double) * static_cast<size_t>(L.vd_n), s->stream, A,
-                                   static_cast<const uint16_t *>(L.vcodes.p), static_cast<const double *>(L.vdict.p), L.vd_n, x, L.t.p, S, s->d_send.p, ctl);
+            if (L.vd.ok && L.vcodes.p)
+                hipLaunchKernelGGL(k_amg_spmv_pack_vd, dim3(spmv_grid(A.n_slices)), dim3(kBlock), sizeof(double) * static_cast<size_t>(L.vd.n), s->stream, A,
+                                   static_cast<const uint16_t *>(L.vcodes.p), static_cast<const double *>(L.vd.dict.p), L.vd.n, x, L.t.p, S, s->d_send.p, ctl);
             else
             hipLaunchKernelGGL(k_amg_spmv_pack, dim3(spmv_grid(A.n_slices)), dim3(kBlock), 0, s->stream, A, x, L.t.p, S, s->d_send.p, ctl);
         }
@@ -3427,17 +3409,17 @@ double *amg_apply(pfem_solver *s, Amg &M, const double *r, const CgCtl *ctl, boo
                 const int32_t *gc = L.gcol.p;
                 if (L.bs == 6) hipLaunchKernelGGL((k_rbm_spmv_ep<MODE, 6>), grid, block, 0, st, A, gp, gc, xin, r_in, dinv, lam, M.eig_ratio, step, add_dd0, r_out, dd_out, x, ctl);
                 else hipLaunchKernelGGL((k_rbm_spmv_ep<MODE, 3>), grid, block, 0, st, A, gp, gc, xin, r_in, dinv, lam, M.eig_ratio, step, add_dd0, r_out, dd_out, x, ctl);
-            } else if (L.vd_ok && L.vcodes.p) {          // the level's values as dictionary codes (amg_value_codes)
+            } else if (L.vd.ok && L.vcodes.p) {          // the level's values as dictionary codes (amg_value_codes)
                 const uint16_t *q = L.vcodes.p;
-                const double *d = L.vdict.p;
-                const size_t lds = sizeof(double) * static_cast<size_t>(L.vd_n);
+                const double *d = L.vd.dict.p;
+                const size_t lds = sizeof(double) * static_cast<size_t>(L.vd.n);
                 if (amg_level_col_codes(M, L)) {          // ... and its columns as one-byte codes (amg_column_codes_enqueue): 1 + 2 B a slot
                     const uint32_t *cw = L.ccodes.p;
                     const int32_t *cdl = L.cdelta.p;
                     const size_t lds_cc = lds + sizeof(int32_t) * static_cast<size_t>(L.cd_n);
-                    hipLaunchKernelGGL((k_amg_spmv_ep_vd<MODE, true>), grid, block, lds_cc, st, A, q, d, L.vd_n, xin, r_in, dinv, lam, M.eig_ratio, step, add_dd0, r_out, dd_out, x, ctl, cw, cdl, L.cd_n);
+                    hipLaunchKernelGGL((k_amg_spmv_ep_vd<MODE, true>), grid, block, lds_cc, st, A, q, d, L.vd.n, xin, r_in, dinv, lam, M.eig_ratio, step, add_dd0, r_out, dd_out, x, ctl, cw, cdl, L.cd_n);
                 } else {
-                    hipLaunchKernelGGL((k_amg_spmv_ep_vd<MODE, false>), grid, block, lds, st, A, q, d, L.vd_n, xin, r_in, dinv, lam, M.eig_ratio, step, add_dd0, r_out, dd_out, x, ctl, nullptr, nullptr, 0);
+                    hipLaunchKernelGGL((k_amg_spmv_ep_vd<MODE, false>), grid, block, lds, st, A, q, d, L.vd.n, xin, r_in, dinv, lam, M.eig_ratio, step, add_dd0, r_out, dd_out, x, ctl, nullptr, nullptr, 0);
                 }
             } else {
                 hipLaunchKernelGGL(k_amg_spmv_ep<MODE>, grid, block, 0, st, A, xin, r_in, dinv, lam, M.eig_ratio, step, add_dd0, r_out, dd_out, x, ctl);
@@ -3704,7 +3686,7 @@ int run_pcg_amg(pfem_solver *s)
                                          reinterpret_cast<uint64_t>(M.lev[0]->t.p), reinterpret_cast<uint64_t>(M.lev[0]->dinv.p)};
             auto level_key = [&](const std::unique_ptr<AmgLevel> &L) {
                 key.push_back(reinterpret_cast<uint64_t>(L->x)); key.push_back(reinterpret_cast<uint64_t>(L->vals.p)); key.push_back(static_cast<uint64_t>(L->n));
-                key.push_back(L->vd_ok ? static_cast<uint64_t>(L->vd_n + 1) : 0); key.push_back(reinterpret_cast<uint64_t>(L->vcodes.p));
+                key.push_back(L->vd.ok ? static_cast<uint64_t>(L->vd.n + 1) : 0); key.push_back(reinterpret_cast<uint64_t>(L->vcodes.p));
                 // (the column codes: whether the level's products read them, and from where)
                 const bool cc = amg_level_col_codes(M, *L);
                 key.push_back(cc ? static_cast<uint64_t>(L->cd_n + 1) : 0); key.push_back(cc ? reinterpret_cast<uint64_t>(L->ccodes.p) : 0);

@@ -107,15 +107,10 @@ struct AmgLevel {
     // values as 16-bit codes into a dictionary of the distinct ones (pfem_valdict.hpp; scalar coarse levels of a one-rank hierarchy
     // whose Galerkin sums repeat -- bricks of a lattice): the fused SpMVs of the cycle stream 4 + 2 B a slot instead of 4 + 8 (1 + 2 B
     // with the column codes below)
+    ValueDict vd;                         // (refused: for this hierarchy)
     DevBuf<uint16_t> vcodes;
-    DevBuf<double> vdict;
-    DevBuf<unsigned long long> vtable;
-    int vd_n = 0;
-    bool vd_ok = false, vd_have_dict = false, vd_refused = false;
     // round 6: the Galerkin product that forms this level's values also writes their codes (k_lat_galerkin through the hash table
     // of the dictionary, pfem_vdhash.hpp) and leaves the inverse diagonal + the rows' Gershgorin ratios behind
-    DevBuf<VdHashEntry> vhash;
-    bool vd_hash_ok = false;              // vhash belongs to vdict, and every slot of vcodes carries a code of it
     bool vd_direct = false;               // this solve's codes came from the Galerkin product: verdict in Amg::vd_states, not read yet
     bool bound_fresh = false;             // dinv and t (ratios) of this level were written by the product that formed its values
     bool bound_done = false;              // ... and lam (their maximum) as well

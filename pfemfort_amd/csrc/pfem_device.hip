@@ -449,6 +449,76 @@ struct CgGraph {
     }
 };
 
+int check_kernel(const char *what);
+inline bool vd_verbose() { return std::getenv("PFEM_VD_VERBOSE") != nullptr; }          // (read per call)
+
+// The host side of one value dictionary (pfem_valdict.hpp, pfem_vdhash.hpp): what the assembled matrix, every coarse level and the
+// Jacobi loop's inverse diagonal keep alike.  It enqueues and never waits, and it owns neither the codes nor the state word (VdState)
+// its kernels report in: the owner encodes, reads the verdict when and how it likes, and hands it to accept().
+struct ValueDict {
+    DevBuf<double> dict;                  // [kVdMax] the distinct values, ascending by bit pattern
+    DevBuf<unsigned long long> table;     // [kVdTable] the collection pass's
+    DevBuf<VdHashEntry> hash;             // [kVdHashSlots] value -> code, for a kernel that writes codes itself (reserve(true) only)
+    int n = 0;                            // values in the dictionary that stands
+    bool have = false;                    // a dictionary stands: new values are encoded against it first, rebuilt on a miss
+    bool ok = false;                      // ... and the owner's codes are codes of it: its kernels may stream them (the matrix: while vd_current)
+    bool hash_ok = false;                 // hash belongs to dict, and every slot of the owner's codes carries a code of it
+    bool refused = false;                 // more than kVdMax distinct values: no more tries until reset()
+
+    void reset() { n = 0; have = ok = hash_ok = refused = false; }          // a new pattern / hierarchy (the buffers stay)
+    void skip() { ok = false; }                                             // fp64 this time; what stands, stands
+    void refuse() { ok = have = hash_ok = false; refused = true; }
+    int streaming() const { return ok ? n : 0; }                            // entries the owner's kernels are given
+    int reserve(bool with_hash)
+    {
+        if (!dict.p) PFEM_TRY(dict.alloc(kVdMax));
+        if (!table.p) PFEM_TRY(table.alloc(kVdTable));
+        if (with_hash && !hash.p) PFEM_TRY(hash.alloc(kVdHashSlots));
+        return PFEM_OK;
+    }
+    // the standing dictionary is tried on new values: the word an encode pass (or a kernel with the hash table) raises `miss` in
+    int enqueue_against_standing(hipStream_t st, VdState *word) const
+    {
+        const VdState reset{n, 0, 0, 0};
+        PFEM_HIP(hipMemcpyAsync(word, &reset, sizeof reset, hipMemcpyHostToDevice, st));
+        return PFEM_OK;
+    }
+    // a new dictionary of vals[0 .. count): table and word cleared, the distinct values collected and sorted into dict; the look-up
+    // table with it, or later (enqueue_hash), once the owner has seen the verdict
+    int enqueue_build(hipStream_t st, const double *vals, int64_t count, unsigned grid, VdState *word, bool with_hash)
+    {
+        hash_ok = false;
+        PFEM_HIP(hipMemsetAsync(table.p, 0xff, sizeof(unsigned long long) * kVdTable, st));
+        PFEM_HIP(hipMemsetAsync(word, 0, sizeof(VdState), st));
+        hipLaunchKernelGGL(k_vd_collect, dim3(grid), dim3(kBlock), 0, st, vals, count, table.p, word);
+        hipLaunchKernelGGL(k_vd_finish, dim3(1), dim3(1024), 0, st, static_cast<const unsigned long long *>(table.p), dict.p, word);
+        PFEM_TRY(check_kernel("k_vd_collect / k_vd_finish"));
+        return with_hash ? enqueue_hash(st, word) : PFEM_OK;
+    }
+    int enqueue_hash(hipStream_t st, const VdState *word)
+    {
+        PFEM_HIP(hipMemsetAsync(hash.p, 0xff, sizeof(VdHashEntry) * kVdHashSlots, st));
+        hipLaunchKernelGGL(k_vd_hash_build, dim3((kVdMax + kBlock - 1) / kBlock), dim3(kBlock), 0, st, static_cast<const double *>(dict.p), word, hash.p);
+        return check_kernel("k_vd_hash_build");
+    }
+    // the verdict of a build or of an encode pass, read by the owner: a dictionary the kernels may use, or none until reset()
+    bool accept(const VdState &v, bool hash_covers_every_slot)
+    {
+        if (v.fail || v.count < 1 || v.count > kVdMax || v.miss) { refuse(); return false; }
+        n = v.count;
+        have = ok = true;
+        hash_ok = hash_covers_every_slot && hash.p != nullptr;
+        return true;
+    }
+};
+// the coarse levels' and the inverse diagonal's encode pass (the matrix has its own: k_vd_encode, 64-bit words)
+inline int enqueue_vd_encode16(hipStream_t st, const ValueDict &vd, const double *vals, int64_t count, VdState *word, uint16_t *codes)
+{
+    const unsigned grid = static_cast<unsigned>(std::min<int64_t>((count + kBlock - 1) / kBlock, 4096));
+    hipLaunchKernelGGL(k_vd_encode16, dim3(grid), dim3(kBlock), sizeof(uint64_t) * kVdMax, st, vals, count, static_cast<const double *>(vd.dict.p), word, codes);
+    return check_kernel("k_vd_encode16");
+}
+
 #include "pfem_amg_types.hpp"
 
 constexpr size_t kMaxLdsBytes = 163840;       // LDS a single gfx950 workgroup may declare (MI355X_MICROARCH.md)
@@ -657,10 +727,9 @@ struct pfem_solver {
     // or faster up to 5120 wave slots: advisor, round 5)
     static constexpr int64_t kMinGroupsAuto = 163840;      // 2560 wave slots x 64 lanes
     static constexpr int64_t kMinGroupsAutoFp64 = 327680;  // 5120
-    bool vd_refused = false;       // pfem_valdict.hpp: more than kVdMax distinct values (decided once per pattern)
     int64_t min_groups_auto() const
     {
-        return (vd_refused || !valdict_enabled()) ? kMinGroupsAutoFp64 : kMinGroupsAuto;
+        return (vd.refused || !valdict_enabled()) ? kMinGroupsAutoFp64 : kMinGroupsAuto;
     }
     // SpMV-only relative row groups (k_spmvr): 4 consecutive rows, one relative column stream
     bool relgrouped = false;
@@ -685,33 +754,30 @@ struct pfem_solver {
                                    // set-up was made for (Amg::numeric_epoch; read by pfem_modal_solve)
     DevBuf<int32_t> d_row_group;   // [n_loc] node group of every row (k_spmvg's copy written by the elasticity gather kernel itself)
     bool grp_vals_current = false;
-    // the group form's values as 16-bit codes into a dictionary of the distinct values (pfem_valdict.hpp): which form the
-    // codes belong to (rows to the lane: kRelRows / kGroupRows, 0 = none), whether they hold the current values, whether the
-    // SpMV may stream them (vd_ok), the dictionary's size; vd_refused: this pattern's values are too many, no more tries
-    DevBuf<unsigned long long> d_vcodes, d_vtable;
-    // ... straight from the gather kernel (pfem_vdhash.hpp): the hash table of the dictionary; vd_hash_ok: it belongs to the
-    // current dictionary and every slot of d_vcodes has been encoded against that dictionary at least once (the explicit zeros of
-    // the group form keep their codes); vd_direct_pending: the last assembly wrote the codes itself, its verdict has not been read
-    DevBuf<VdHashEntry> d_vhash;
-    bool vd_hash_ok = false, vd_direct_pending = false;
+    // the group form's values as 16-bit codes into a dictionary of the distinct values (pfem_valdict.hpp): the dictionary, the code
+    // words (one per entry: 3 or 4 codes), the one state word, and what only the matrix has -- which form the codes belong to (rows
+    // to the lane: kRelRows / kGroupRows, 0 = none) and whether they hold the current values (the SpMV streams them if vd.ok too)
+    ValueDict vd;
+    DevBuf<unsigned long long> d_vcodes;
+    DevBuf<VdState> d_vstate;
+    int vd_rows = 0;
+    // ... straight from the gather kernel (pfem_vdhash.hpp; vd.hash_ok: the explicit zeros of the group form keep their codes);
+    // vd_direct_pending: the last assembly wrote the codes itself, its verdict (read with the error word) has not been looked at
+    bool vd_current = false, vd_direct_pending = false;
+    VdState vd_direct_verdict{0, 0, 1, 0};
     bool vd_miss_step = false;       // the assembly of the values in place wrote codes and met a value the dictionary lacked: the full
                                      // encode path served this step's SpMV, and gamg's set-up reads the fp64 copy (amg_level0_codes)
-    VdState vd_direct_verdict{0, 0, 1, 0};
-    DevBuf<double> d_vdict;
-    DevBuf<VdState> d_vstate;
-    int vd_rows = 0, vd_n = 0;
-    bool vd_current = false, vd_ok = false, vd_have_dict = false;
     double vd_encode_ms = 0.0;       // (host time of the last refresh incl. its wait: PFEM_VD_VERBOSE)
+    void new_pattern_codes() { vd.reset(); vd_current = vd_direct_pending = vd_miss_step = false; vd_rows = 0; }       // (new codes, a new verdict)
     // the inverse diagonal of the Jacobi loop as codes (DinvView): encoded after every k_invert of a solve whose matrix streams
-    // codes, verdict on the device
+    // codes, verdict on the device (nobody reads it: dvd's flags stay unused)
+    ValueDict dvd;
     DevBuf<uint16_t> d_dcodes;
-    DevBuf<double> d_ddict;
-    DevBuf<unsigned long long> d_dtable;
     DevBuf<VdState> d_dstate;
     bool dinv_codes = false;         // this solve's kernels are given the codes
     DinvView dinv_view() const
     {
-        return dinv_codes ? DinvView{d_dinv.p, d_dcodes.p, d_ddict.p, reinterpret_cast<const int *>(d_dstate.p)}
+        return dinv_codes ? DinvView{d_dinv.p, d_dcodes.p, dvd.dict.p, reinterpret_cast<const int *>(d_dstate.p)}
                           : DinvView{d_dinv.p, nullptr, nullptr, nullptr};
     }
     SellRDev sellr() const
@@ -877,7 +943,7 @@ SpmvForm spmv_form(const pfem_solver *s)
     SpmvForm f{layout, false, false, false};
     f.gap_table = layout == SpmvLayout::Rel4 ? s->rel_dict : ((layout == SpmvLayout::Group3 || layout == SpmvLayout::Row16) && s->row_dict);
     f.codes_fit = f.code_rows() != 0 && s->vd_rows == f.code_rows();
-    f.codes = f.codes_fit && s->vd_ok && s->vd_current;
+    f.codes = f.codes_fit && s->vd.ok && s->vd_current;
     return f;
 }
 
@@ -2584,16 +2650,13 @@ int assemble_with(pfem_solver *s, const PRM prm)
                 // (the SpMV's value CODES instead of the fp64 copy of that form when the last step left a dictionary, its hash table
                 // and a fully encoded code array behind: pfem_vdhash.hpp; else the encode pass of round 5)
                 const bool vd_on = valdict_enabled();
-                const bool direct = both && vd_on && s->vd_have_dict && s->vd_hash_ok && s->vd_ok && f.codes_fit && s->d_vhash.p &&
+                const bool direct = both && vd_on && s->vd.have && s->vd.hash_ok && s->vd.ok && f.codes_fit && s->vd.hash.p &&
                                     s->d_vcodes.p && s->d_vstate.p && s->d_vcodes.n >= static_cast<size_t>(s->r_stored);
-                if (direct) {
-                    const VdState reset{s->vd_n, 0, 0, 0};
-                    PFEM_HIP(hipMemcpyAsync(s->d_vstate.p, &reset, sizeof reset, hipMemcpyHostToDevice, s->stream));
-                }
+                if (direct) PFEM_TRY(s->vd.enqueue_against_standing(s->stream, s->d_vstate.p));
                 launch(k_gather_poisson_tet4<PRM>, xgrid, rblock, rlds, s->stream, nullptr, nullptr, m.nNode, A, s->d_rhs.p, prm, ip, ic, irec, nrow,
                        s->d_node4.p, s->d_err.p, xcd_per, both ? s->d_relk.p : nullptr, both ? s->d_rslice_off.p : nullptr,
                        (both && !direct) ? s->d_rvals.p : nullptr, bound ? L0->dinv.p : nullptr, bound ? L0->t.p : nullptr,
-                       direct ? s->d_vhash.p : nullptr, direct ? reinterpret_cast<uint16_t *>(s->d_vcodes.p) : nullptr,
+                       direct ? s->vd.hash.p : nullptr, direct ? reinterpret_cast<uint16_t *>(s->d_vcodes.p) : nullptr,
                        direct ? s->d_vstate.p : nullptr, pats ? s->d_node_pat.p : nullptr, pats ? s->d_pat_rec.p : nullptr, s->inc_pat_stride);
                 wrote_rel = both && !direct;
                 wrote_codes = direct;
@@ -3137,9 +3200,7 @@ int build_groups(pfem_solver *s)
     PFEM_HIP(hipStreamSynchronize(s->stream));
     s->grouped = miss == 0;          // a gap missing from the table: the row form stays (never wrong columns)
     s->grp_vals_current = false;
-    s->vd_current = s->vd_ok = s->vd_have_dict = s->vd_refused = false;       // (a new pattern: new codes, a new verdict)
-    s->vd_hash_ok = s->vd_direct_pending = s->vd_miss_step = false;
-    s->vd_rows = 0;
+    s->new_pattern_codes();
     s->d_row_group.release();
     if (s->grouped) {       // for an assembly that writes this copy itself; its zero padding is set here, once
         PFEM_TRY(s->d_row_group.alloc(static_cast<size_t>(n)));
@@ -3246,9 +3307,7 @@ int build_rel_groups(pfem_solver *s)
     s->rel_vals_current = false;
     s->asm_bound_fresh = false;
     s->vd_direct_pending = false;
-    s->vd_current = s->vd_ok = s->vd_have_dict = s->vd_refused = false;
-    s->vd_hash_ok = s->vd_direct_pending = s->vd_miss_step = false;
-    s->vd_rows = 0;
+    s->new_pattern_codes();
     s->d_relk.release();
     if (s->max_row_len > 0) {
         PFEM_TRY(s->d_relk.alloc(static_cast<size_t>(std::max<int64_t>(s->stored, 1))));
@@ -3275,95 +3334,63 @@ inline void mark_group_vals(pfem_solver *s)
     // (... or nobody will read that copy: the SpMV streams codes that are current -- written by the assembly itself, its verdict
     // pending, or encoded from a copy that has since been overwritten by nothing)
     const SpmvForm f = spmv_form(s);
-    const bool codes_serve = valdict_enabled() && f.rel() && f.codes_fit && (s->vd_direct_pending || (s->vd_current && s->vd_ok));
+    const bool codes_serve = valdict_enabled() && f.rel() && f.codes_fit && (s->vd_direct_pending || (s->vd_current && s->vd.ok));
     s->group_vals_stale = !((f.rel() && (s->rel_vals_current || codes_serve)) || (f.layout == SpmvLayout::Group3 && s->grp_vals_current));
 }
 
-// The dictionary of `n` values (pfem_valdict.hpp), enqueued: table and state cleared, the distinct values collected and sorted
-// into `dict`.  The verdict stays in `state` for the caller to read, or not.
-int enqueue_value_dictionary(hipStream_t st, const double *vals, int64_t n, unsigned grid, unsigned long long *table, double *dict, VdState *state)
-{
-    PFEM_HIP(hipMemsetAsync(table, 0xff, sizeof(unsigned long long) * kVdTable, st));
-    PFEM_HIP(hipMemsetAsync(state, 0, sizeof(VdState), st));
-    hipLaunchKernelGGL(k_vd_collect, dim3(grid), dim3(kBlock), 0, st, vals, n, table, state);
-    hipLaunchKernelGGL(k_vd_finish, dim3(1), dim3(1024), 0, st, static_cast<const unsigned long long *>(table), dict, state);
-    return check_kernel("k_vd_collect / k_vd_finish");
-}
-// ... and the look-up table by which a kernel finds a value's code itself (pfem_vdhash.hpp)
-int enqueue_vd_hash(hipStream_t st, const double *dict, const VdState *state, VdHashEntry *hash)
-{
-    PFEM_HIP(hipMemsetAsync(hash, 0xff, sizeof(VdHashEntry) * kVdHashSlots, st));
-    hipLaunchKernelGGL(k_vd_hash_build, dim3((kVdMax + kBlock - 1) / kBlock), dim3(kBlock), 0, st, dict, state, hash);
-    return check_kernel("k_vd_hash_build");
-}
-// ... and the verdict that makes it one the kernels may use (`miss`: of the encode pass that followed)
-inline bool vd_usable(const VdState &v) { return !v.fail && v.count >= 1 && v.count <= kVdMax && !v.miss; }
 // The SpMV's codes of the current values (pfem_valdict.hpp).  One wait for the device per call that finds new values: the
 // verdict decides which kernel the solve launches.
 int refresh_value_codes(pfem_solver *s)
 {
-    const bool enabled = valdict_enabled();     // (read per call: tests switch it)
-    const bool verbose = std::getenv("PFEM_VD_VERBOSE") != nullptr;
+    ValueDict &vd = s->vd;
+    const bool verbose = vd_verbose();
     const int rows = spmv_form(s).code_rows();
-    if (!enabled || rows == 0 || s->vd_refused) { s->vd_ok = false; return PFEM_OK; }
+    if (!valdict_enabled() || rows == 0 || vd.refused) { vd.skip(); return PFEM_OK; }     // (read per call: tests switch it)
     if (s->vd_current && s->vd_rows == rows) return PFEM_OK;
     const auto t0 = std::chrono::steady_clock::now();
     const int64_t n_entries = rows == kGroupRows ? s->g_stored : s->r_stored;
     const double *vals = rows == kGroupRows ? s->d_gvals.p : s->d_rvals.p;
-    if (n_entries < 1 || !vals) { s->vd_ok = false; return PFEM_OK; }
-    if (s->vd_rows != rows) { s->vd_have_dict = false; s->vd_rows = rows; }
+    if (n_entries < 1 || !vals) { vd.skip(); return PFEM_OK; }
+    if (s->vd_rows != rows) { vd.reset(); s->vd_rows = rows; }
     if (s->d_vcodes.n < static_cast<size_t>(n_entries)) PFEM_TRY(s->d_vcodes.alloc(static_cast<size_t>(n_entries)));
-    if (!s->d_vdict.p) PFEM_TRY(s->d_vdict.alloc(kVdMax));
-    if (!s->d_vtable.p) PFEM_TRY(s->d_vtable.alloc(kVdTable));
+    PFEM_TRY(vd.reserve(false));
     if (!s->d_vstate.p) PFEM_TRY(s->d_vstate.alloc(1));
     const unsigned grid = static_cast<unsigned>(std::min<int64_t>((n_entries + kBlock - 1) / kBlock, 8192));
     VdState st{0, 0, 0, 0};
     auto encode = [&]() -> int {
-        const size_t lds = sizeof(uint64_t) * static_cast<size_t>(std::max(s->vd_n, 1));
-        if (rows == kGroupRows) hipLaunchKernelGGL(k_vd_encode<kGroupRows>, dim3(grid), dim3(kBlock), lds, s->stream, vals, n_entries, static_cast<const double *>(s->d_vdict.p), s->d_vstate.p, s->d_vcodes.p);
-        else hipLaunchKernelGGL(k_vd_encode<kRelRows>, dim3(grid), dim3(kBlock), lds, s->stream, vals, n_entries, static_cast<const double *>(s->d_vdict.p), s->d_vstate.p, s->d_vcodes.p);
+        const size_t lds = sizeof(uint64_t) * static_cast<size_t>(std::max(vd.n, 1));
+        if (rows == kGroupRows) hipLaunchKernelGGL(k_vd_encode<kGroupRows>, dim3(grid), dim3(kBlock), lds, s->stream, vals, n_entries, static_cast<const double *>(vd.dict.p), s->d_vstate.p, s->d_vcodes.p);
+        else hipLaunchKernelGGL(k_vd_encode<kRelRows>, dim3(grid), dim3(kBlock), lds, s->stream, vals, n_entries, static_cast<const double *>(vd.dict.p), s->d_vstate.p, s->d_vcodes.p);
         PFEM_TRY(check_kernel("k_vd_encode"));
         PFEM_HIP(hipMemcpyAsync(&st, s->d_vstate.p, sizeof st, hipMemcpyDeviceToHost, s->stream));
         PFEM_HIP(hipStreamSynchronize(s->stream));
         return PFEM_OK;
     };
     bool done = false;
-    if (s->vd_have_dict) {          // the dictionary of the last assembly: it holds if every value is found in it
-        const VdState reset{s->vd_n, 0, 0, 0};
-        PFEM_HIP(hipMemcpyAsync(s->d_vstate.p, &reset, sizeof reset, hipMemcpyHostToDevice, s->stream));
+    if (vd.have) {          // the dictionary of the last assembly: it holds if every value is found in it
+        PFEM_TRY(vd.enqueue_against_standing(s->stream, s->d_vstate.p));
         PFEM_TRY(encode());
         done = st.miss == 0;
     }
     if (!done) {
-        PFEM_TRY(enqueue_value_dictionary(s->stream, vals, static_cast<int64_t>(rows) * n_entries, grid, s->d_vtable.p, s->d_vdict.p, s->d_vstate.p));
+        PFEM_TRY(vd.enqueue_build(s->stream, vals, static_cast<int64_t>(rows) * n_entries, grid, s->d_vstate.p, false));
         PFEM_HIP(hipMemcpyAsync(&st, s->d_vstate.p, sizeof st, hipMemcpyDeviceToHost, s->stream));
         PFEM_HIP(hipStreamSynchronize(s->stream));
-        if (!vd_usable(st)) {          // (miss is 0 here: nothing has been encoded yet)
-            s->vd_ok = s->vd_have_dict = s->vd_hash_ok = false;
-            s->vd_refused = true;          // (until the pattern changes: a mesh of this kind does not repeat its element matrices)
+        if (!vd.accept(st, false)) {          // (until the pattern changes: a mesh of this kind does not repeat its element matrices)
             if (verbose) std::fprintf(stderr, "  value dictionary: more than %d distinct matrix values, the SpMV keeps its fp64 copy\n", kVdMax);
             return PFEM_OK;
         }
-        s->vd_n = st.count;
-        s->vd_have_dict = true;
-        s->vd_hash_ok = false;
-        if (rows == kRelRows) {         // the look-up table the assembly kernel uses from the next step on (pfem_vdhash.hpp)
-            if (!s->d_vhash.p) PFEM_TRY(s->d_vhash.alloc(kVdHashSlots));
-            PFEM_TRY(enqueue_vd_hash(s->stream, s->d_vdict.p, s->d_vstate.p, s->d_vhash.p));
-        }
+        // the look-up table the assembly kernel uses from the next step on (pfem_vdhash.hpp)
+        if (rows == kRelRows) { PFEM_TRY(vd.reserve(true)); PFEM_TRY(vd.enqueue_hash(s->stream, s->d_vstate.p)); }
         PFEM_TRY(encode());
-        if (st.miss) {                  // (cannot happen for finite values; whatever it is, the fp64 copy is always right)
-            s->vd_ok = s->vd_have_dict = false;
-            s->vd_refused = true;
-            if (verbose) std::fprintf(stderr, "  value dictionary: a value of the collection pass is missing from its own dictionary, the SpMV keeps its fp64 copy\n");
-            return PFEM_OK;
-        }
     }
-    s->vd_ok = true;
+    if (!vd.accept(st, rows == kRelRows)) {          // (a miss cannot happen for finite values; whatever it is, the fp64 copy is always right)
+        if (verbose) std::fprintf(stderr, "  value dictionary: a value of the collection pass is missing from its own dictionary, the SpMV keeps its fp64 copy\n");
+        return PFEM_OK;
+    }
     s->vd_current = true;
-    s->vd_hash_ok = rows == kRelRows && s->d_vhash.p != nullptr;        // (every slot now carries a code of THIS dictionary)
     s->vd_encode_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (verbose) std::fprintf(stderr, "  value dictionary: %d distinct values among %lld slots, codes refreshed in %.3f ms (host, incl. the wait)\n", s->vd_n,
+    if (verbose) std::fprintf(stderr, "  value dictionary: %d distinct values among %lld slots, codes refreshed in %.3f ms (host, incl. the wait)\n", vd.n,
                               static_cast<long long>(rows * n_entries), s->vd_encode_ms);
     return PFEM_OK;
 }
@@ -3377,13 +3404,12 @@ int refresh_group_vals(pfem_solver *s)
         // verdict.  A value the dictionary lacks -- new coefficients, a moved mesh -- and the full path takes over: the fp64 copy of
         // the group form re-packed from the row form, collection, sort, encode.
         s->vd_direct_pending = false;
-        const bool enabled = valdict_enabled();
         const VdState st = s->vd_direct_verdict;          // (read with the assembly's error word)
         s->vd_miss_step = st.miss || st.fail;
-        if (enabled && !st.miss && !st.fail && f.rel() && f.codes_fit) {
-            s->vd_ok = s->vd_current = true;
+        if (valdict_enabled() && !st.miss && !st.fail && f.rel() && f.codes_fit && s->vd.accept(st, true)) {
+            s->vd_current = true;
             s->group_vals_stale = false;
-            if (std::getenv("PFEM_VD_VERBOSE")) std::fprintf(stderr, "  value dictionary: codes written by the assembly kernel (%d values)\n", s->vd_n);
+            if (vd_verbose()) std::fprintf(stderr, "  value dictionary: codes written by the assembly kernel (%d values)\n", s->vd.n);
             return PFEM_OK;
         }
         s->vd_current = false;
@@ -3410,21 +3436,17 @@ int refresh_group_vals(pfem_solver *s)
 // codes of the inverse diagonal for the Jacobi loop (DinvView), enqueued behind k_invert; nobody waits for the verdict
 int encode_dinv(pfem_solver *s, int64_t n)
 {
-    const bool enabled = valdict_enabled();
     s->dinv_codes = false;
     // (a matrix that repeats its values: so does its diagonal.  From 2^21 rows on: the encoding costs ~0.5 ms a solve -- the
     // one-workgroup sort of the dictionary most of it --, which 191 iterations at 100^3 do not earn back: 8.8 -> 10.0 ms there)
     const int64_t min_rows = [] { const char *e = std::getenv("PFEM_DINV_CODES_MIN_ROWS"); return e ? std::atoll(e) : static_cast<long long>(1 << 21); }();
-    if (!enabled || !spmv_form(s).codes || n < min_rows) return PFEM_OK;
+    if (!valdict_enabled() || !spmv_form(s).codes || n < min_rows) return PFEM_OK;
     if (s->d_dcodes.n < static_cast<size_t>(n)) PFEM_TRY(s->d_dcodes.alloc(static_cast<size_t>(n)));
-    if (!s->d_ddict.p) PFEM_TRY(s->d_ddict.alloc(kVdMax));
-    if (!s->d_dtable.p) PFEM_TRY(s->d_dtable.alloc(kVdTable));
+    PFEM_TRY(s->dvd.reserve(false));
     if (!s->d_dstate.p) PFEM_TRY(s->d_dstate.alloc(1));
     const unsigned grid = static_cast<unsigned>(std::min<int64_t>((n + kBlock - 1) / kBlock, 4096));
-    PFEM_TRY(enqueue_value_dictionary(s->stream, s->d_dinv.p, n, grid, s->d_dtable.p, s->d_ddict.p, s->d_dstate.p));
-    hipLaunchKernelGGL(k_vd_encode16, dim3(grid), dim3(kBlock), sizeof(uint64_t) * kVdMax, s->stream, static_cast<const double *>(s->d_dinv.p), n,
-                       static_cast<const double *>(s->d_ddict.p), s->d_dstate.p, s->d_dcodes.p);
-    PFEM_TRY(check_kernel("inverse diagonal: value codes"));
+    PFEM_TRY(s->dvd.enqueue_build(s->stream, s->d_dinv.p, n, grid, s->d_dstate.p, false));
+    PFEM_TRY(enqueue_vd_encode16(s->stream, s->dvd, s->d_dinv.p, n, s->d_dstate.p, s->d_dcodes.p));
     s->dinv_codes = true;
     return PFEM_OK;
 }
@@ -3444,17 +3466,17 @@ void launch_spmv(pfem_solver *s, const double *x, double *y, int64_t n_dot, doub
     const dim3 grid(spmv_grid(sel.list ? sel.count : f.slices(s))), block(kBlock);
     const hipStream_t st = s->stream;
     const unsigned long long *q = s->d_vcodes.p;          // f.codes: the value stream ...
-    const double *d = s->d_vdict.p;
-    const size_t lds = f.codes ? sizeof(double) * static_cast<size_t>(s->vd_n) : 0;          // ... and its dictionary in LDS
+    const double *d = s->vd.dict.p;
+    const size_t lds = f.codes ? sizeof(double) * static_cast<size_t>(s->vd.n) : 0;          // ... and its dictionary in LDS
     const Sell16Dev C{s->d_col0.p, s->d_dwords.p, s->d_slice_doff.p, s->d_row_gap_table.p};          // (the row forms' 16-bit gaps)
     with_flag(f.gap_table, [&](auto gap_table) {
         constexpr bool DICT = decltype(gap_table)::value;
         switch (f.layout) {
         case SpmvLayout::Group3:
-            if (f.codes) return launch(k_spmvg_vd<WITH_DOT, DICT>, grid, block, lds, st, e0, e1, s->sellg(), q, d, s->vd_n, s->n_loc, x, y, n_dot, partial, ctl, sel);
+            if (f.codes) return launch(k_spmvg_vd<WITH_DOT, DICT>, grid, block, lds, st, e0, e1, s->sellg(), q, d, s->vd.n, s->n_loc, x, y, n_dot, partial, ctl, sel);
             return launch(k_spmvg<WITH_DOT, DICT>, grid, block, 0, st, e0, e1, s->sellg(), s->n_loc, x, y, n_dot, partial, ctl, sel);
         case SpmvLayout::Rel4:
-            if (f.codes) return launch(k_spmvr_vd<WITH_DOT, DICT, EP>, grid, block, lds, st, e0, e1, s->sellr(), q, d, s->vd_n, s->n_loc, x, y, n_dot, partial, ctl, sel, E);
+            if (f.codes) return launch(k_spmvr_vd<WITH_DOT, DICT, EP>, grid, block, lds, st, e0, e1, s->sellr(), q, d, s->vd.n, s->n_loc, x, y, n_dot, partial, ctl, sel, E);
             return launch(k_spmvr<WITH_DOT, DICT, EP>, grid, block, 0, st, e0, e1, s->sellr(), s->n_loc, x, y, n_dot, partial, ctl, sel, E);
         case SpmvLayout::Rel4Gap32:
             return launch(k_spmvr32<WITH_DOT>, grid, block, 0, st, e0, e1, s->sellr(), s->n_loc, x, y, n_dot, partial, ctl, sel);
@@ -3556,7 +3578,7 @@ extern "C" int pfem_solver_get_spmv_value_dictionary(pfem_solver *s, int *entrie
 {
     if (!s || !entries) return PFEM_ERR_ARG;
     if (!s->have_pattern) return PFEM_ERR_STATE;
-    *entries = (s->vd_ok && s->vd_current) ? s->vd_n : 0;          // (as it always was: without a look at the form, see spmv_form)
+    *entries = s->vd_current ? s->vd.streaming() : 0;          // (as it always was: without a look at the form, see spmv_form)
     return PFEM_OK;
 }
 
@@ -4754,7 +4776,7 @@ int scalar_allreduce(pfem_solver *s, int at, int n)
 inline uint64_t spmv_key(const pfem_solver *s)
 {
     const SpmvForm f = spmv_form(s);
-    return f.kernel_id() | (f.codes ? (static_cast<uint64_t>(s->vd_n + 1) << 8) : 0) | (s->dinv_codes ? 1ull << 7 : 0) |
+    return f.kernel_id() | (f.codes ? (static_cast<uint64_t>(s->vd.n + 1) << 8) : 0) | (s->dinv_codes ? 1ull << 7 : 0) |
            (static_cast<uint64_t>(reinterpret_cast<uintptr_t>(s->d_vcodes.p)) << 24);
 }
 
@@ -6021,7 +6043,7 @@ extern "C" int pfem_solver_amg_value_dictionaries(pfem_solver *s, int max_levels
     if (!s->amg || !s->amg->symbolic_ok) return PFEM_OK;
     for (const AmgLevelRef &r : amg_levels_of(*s->amg)) {
         if (*n_levels >= max_levels) break;
-        entries[(*n_levels)++] = r.L->fine ? ((s->vd_ok && s->vd_current) ? s->vd_n : 0) : (r.L->vd_ok ? r.L->vd_n : 0);
+        entries[(*n_levels)++] = r.L->fine ? (s->vd_current ? s->vd.streaming() : 0) : r.L->vd.streaming();
     }
     return PFEM_OK;
 }

@@ -17,7 +17,9 @@
 //                  global atomics) -> k_vd_finish (one workgroup: gather, bitonic sort, the dictionary) -> k_vd_encode
 //   more than kVdMax distinct values (any unstructured mesh): the form is dropped for this pattern; the fp64 copy is what the
 //   SpMV streams, as before.
-// One read of the verdict (3 ints) by the host per assembly decides which kernel the solve launches.
+// One read of the verdict (3 ints) by the host per assembly decides which kernel the solve launches.  The host side of this life
+// cycle -- buffers, flags, the enqueues, the verdict test -- is struct ValueDict in pfem_device.hip, one per owner (the matrix, every
+// coarse level, the Jacobi loop's inverse diagonal).
 #pragma once
 #include "pfem_vdhash.hpp"
 

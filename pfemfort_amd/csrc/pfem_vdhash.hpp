@@ -1,5 +1,6 @@
 // pfem_vdhash.hpp -- the small pieces of the value dictionary (pfem_valdict.hpp) that the assembly kernels need too: the
-// verdict block, the hash, the look-up table of a dictionary.  Included ahead of pfem_kernels.hpp.
+// verdict block, the hash, the look-up table of a dictionary (on the host: ValueDict::hash, valid while ValueDict::hash_ok).
+// Included ahead of pfem_kernels.hpp.
 #pragma once
 
 namespace pfem {

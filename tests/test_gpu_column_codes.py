@@ -19,11 +19,13 @@ import pytest
 import pfemfort_amd as pf
 from pfemfort_amd import drivers as D
 from pfemfort_amd import host as H
+from test_gpu_parity import _moved
 
 pytestmark = pytest.mark.gpu
 
 CELLS = {"cube": (82, 82, 82), "ragged": (84, 82, 80)}
-SWITCHES = ("PFEM_AMG_COL_CODES", "PFEM_AMG_COL_CODES_MAX", "PFEM_AMG_FUSED", "PFEM_CG_GRAPH")
+MOVED = {"cube_moved": "cube"}          # the same cells, the nodes off their sites (test_gpu_parity._moved)
+SWITCHES = ("PFEM_AMG_COL_CODES", "PFEM_AMG_COL_CODES_MAX", "PFEM_AMG_FUSED", "PFEM_CG_GRAPH", "PFEM_SPMV_VALDICT")
 LEGS = {"codes": {}, "int32": {"PFEM_AMG_COL_CODES": "0"}, "unfused": {"PFEM_AMG_FUSED": "0"}}
 
 
@@ -45,13 +47,14 @@ def _env(**kw):
 
 @functools.lru_cache(maxsize=None)
 def _setup(name):
-    c = CELLS[name]
-    return D._setup(pf.POISSON_TET, H.gen_box_tets(-1, 1, c[0], -1, 1, c[1], -1, 1, c[2]))
+    c = CELLS[MOVED.get(name, name)]
+    mesh = H.gen_box_tets(-1, 1, c[0], -1, 1, c[1], -1, 1, c[2])
+    return D._setup(pf.POISSON_TET, _moved(mesh, 2.0 / max(c)) if name in MOVED else mesh)
 
 
 def _rows(name):
     """Free rows of the box and of its first brick level (bricks of two nodes per axis)."""
-    free = [c - 1 for c in CELLS[name]]
+    free = [c - 1 for c in CELLS[MOVED.get(name, name)]]
     return int(np.prod(free)), int(np.prod([(f + 1) // 2 for f in free]))
 
 
@@ -141,6 +144,37 @@ def test_too_many_offsets_keep_the_int32_kernel():
                 s.amgLevelColumns(1, True)
         finally:
             s.free()
+
+
+def test_a_level_whose_values_do_not_repeat_refuses_its_dictionary():
+    """The 82^3 box with its nodes moved inside balls of 0.2 cell edges (test_gpu_parity._moved): the numbering is still a box's, so
+    the hierarchy keeps its bricks and level 1 its 41^3 rows and 1.15 M slots -- a candidate for the dictionary --, but its 68 921 rows
+    are sums over cells that differ: more than 4096 distinct values, the verdict refuses the level for this hierarchy.  The pattern's
+    first solve and two warm steps stream fp64 values and int32 columns on level 1 (the column codes ride on the value codes), and
+    each is, bit for bit, the same solve with the dictionaries switched off."""
+    name = "cube_moved"
+
+    def three_solves(**env):
+        with _env(**env):
+            s = pf.PetscSolver()
+            try:
+                _load(s, name)
+                steps = []
+                for assemble in (False, True, True):
+                    step = _step(s, name, assemble)
+                    lat, step["vd"] = s.amgLayout()["lattice_levels"], s.amgValueDictionaries()
+                    print(name, env, "lattice_levels", lat, "value dictionaries", step["vd"])
+                    assert tuple(s.amgInfo()["rows"][:2]) == _rows(name) and lat >= 1          # (bricks, through the numbering)
+                    steps.append(step)
+                return steps
+            finally:
+                s.free()
+
+    ref = three_solves(PFEM_SPMV_VALDICT="0")
+    for what, step, off in zip(("first", "warm", "second warm"), three_solves(), ref):
+        assert step["vd"][1] == 0 and off["vd"][1] == 0, (what, step["vd"])
+        assert step["cc"] == [] and off["cc"] == [], what
+        _same_bits(step, off, what)
 
 
 def test_reused_solver_follows_the_mesh_and_the_switch():
