@@ -646,6 +646,50 @@ int pfem_modal_solve(pfem_solver *s, int n_modes, int block /*0: auto*/, double 
 #define PFEM_GENEIG_MAX 48
 int pfem_dense_sym_geneig(int n, const double *A, const double *B, double floor, double *w, double *C, int *status);
 
+/* ---- linear buckling: geometric stiffness and critical load factors -------- */
+/* (K + lambda K_g(sigma_0)) phi = 0 on the free dofs for a reference state with the stress sigma_0 per element (DESIGN.md section
+ * 15).  PFEM_ELAST_TET and PFEM_ELAST_TRIA, one rank and the batched path only.  K is SPD, so the problem is posed as
+ * K_g phi = theta K phi and the LOWEST theta are sought: lambda = -1 / theta for theta < 0 -- the most negative theta is the
+ * smallest positive load factor --, and a pair with theta >= 0 does not buckle in the load's direction: lambda = +infinity.
+ *
+ * pfem_elem_geometric: the geometric stiffness of one linear simplex couples equal displacement components only,
+ *     K_g[(a,i),(b,j)] = delta_ij g_ab,      g_ab = dvol (grad N_a . sigma grad N_b),      Kg[a + npe * b] = g_ab,
+ * with dvol and grad N of the kind's stiffness routine (the triangle's thickness elemData[2] in dvol; the tet reads no elemData,
+ * which may be NULL there).  sigma in the order pfem_post_elements stores `flux`: [xx,yy,zz,xy,yz,zx] for the tet, [xx,yy,xy] for
+ * the triangle -- and for the triangle it is that flux as returned, the reference's plane-stress shear factor included: K_g is
+ * built from the stress the library reports.  The triangle's K_g describes in-plane instability only.  The order of operations
+ * is fixed (pfem_elem.hpp: elem_geometric) and the device kernel gives the same bits.  PFEM_ERR_ARG: another kind, a NULL
+ * pointer.  PFEM_ERR_NEG_JAC: an inverted element.                                                                            */
+int pfem_elem_geometric(int kind, const double *xNode, const double *yNode, const double *zNode /* NULL in 2-D */,
+                        const double *elemData, const double *sigma, double *Kg /* npe * npe, g[a + npe * b] */);
+/* K_g on the device: a second fp64 value array on the pattern and the wave-sliced row form of K.  elem_stress: SoA
+ * [c * nElem + e] in the caller's element order, or NULL: the stresses pfem_post_elements would return for u_nodal (NULL: the
+ * last solve; a thermal state is honoured, so thermal buckling takes the thermal stress), which never leave the device.
+ * elemData is the vector, or the material table while a map is set, exactly as pfem_assemble takes it.  One thread per element
+ * adds g_ab with f64 atomics at (row = dof(b,i), col = dof(a,i)) for every component i whose two dofs are free; constrained dofs
+ * are dropped (an eigenproblem has no lifting).  The order of the sums therefore varies from run to run.  A new set-up replaces
+ * the old one; a re-assemble of K keeps K_g; the next mesh and the next pfem_pattern_build drop it.  PFEM_ERR_ARG: a handle of a
+ * Poisson kind, elemData NULL.  PFEM_ERR_STATE: no pattern, no assembled matrix, more than one rank (and, with neither
+ * elem_stress nor u_nodal, no solve).  PFEM_ERR_NEG_JAC: an inverted element.                                                */
+int pfem_buckling_setup(pfem_solver *s, const double *elemData, const double *u_nodal, const double *elem_stress);
+/* K_g's values in pfem_get_csr's layout and order (the same rowptr and cols).  PFEM_ERR_STATE without a set-up.             */
+int pfem_buckling_get_geometric(pfem_solver *s, double *vals);
+/* The lowest n_modes pairs of K_g phi = theta K phi by the LOBPCG of pfem_modal_solve with m o S replaced by K S and A = K_g:
+ * block choice, hashed start block, Rayleigh-Ritz on X0, dropping P when the K-Gram matrix is singular, reasons 1 / -1 / -2, the
+ * refresh of the recurrences (K X and K_g X) every 10th iteration, argument errors and PFEM_ERR_NOGPU are that routine's.
+ *     R = K_g X - (K X) diag(theta),     res_j = ||R_j|| / (||K_g X_j|| + |theta_j| ||K X_j||).
+ * T follows pfem_modal_solve's rule: the cycle of the last gamg solve where that is current, else the point Jacobi of K;
+ * pc = PFEM_PC_GAMG without a current set-up: PFEM_ERR_STATE.  (T is an approximate inverse of K: the natural one here.)
+ * theta[n_modes] ascending; factor[j] = -1 / theta_j for theta_j < 0, else INFINITY; modes mode-major in
+ * pfem_solver_get_solution's order (may be NULL), phi^T K phi = 1 by the final explicit K X, the entry of largest magnitude
+ * positive.  Preconditions: pfem_buckling_setup on the current pattern, an assembled matrix, one rank, the batched path.  It reads
+ * K's row form, K_g and the diagonal and writes only its own buffers (under gamg also the cycle's work vectors and the SpMV's
+ * value copies, as the modal solve): nothing of the solve, the steppers, the modal or the thermal state changes.             */
+int pfem_buckling_solve(pfem_solver *s, int n_modes, int block /*0: auto*/, double tol, int max_iterations, int pc /*-1: the solver's*/,
+                        const double *x0 /* n_owned x MB row-major, or NULL */, double *theta /* n_modes */, double *factor /* n_modes */,
+                        double *modes /* n_modes x n_owned, mode-major; may be NULL */, double *residuals, int *iterations,
+                        int *restarts, int *reason /* 1 converged, -1 max_iterations, -2 breakdown */);
+
 /* ---- inspection / export (device -> host) -------------------------------- */
 /* global dof id of every local row (owned first, then ghosts ascending) */
 int pfem_get_local_to_global(pfem_solver *s, int64_t *gid);

@@ -271,6 +271,29 @@ int pfem_modal_last_pc(pfem_solver *s, int *pc);
  * of each between two HIP events, each series after one warm-up launch, on the same handle.  Like pfem_bench_spmv it uses the
  * solve's SpMV input and output vectors.                                                                                      */
 int pfem_modal_bench_spmm(pfem_solver *s, int mb, int reps, double *us_spmm, double *us_mb_spmv);
+/* One launch of a kernel of pfem_buckling_solve on blocks of the caller's, through the grid functions and the launch code of the
+ * solve itself; blocks, n, mb, the NaN guards and the errors as the pfem_modal_probe_* above.  GX, GW, GP are the K_g-products.
+ *   gram:     k_buck_gram<mb>, then k_modal_sum; out: the 2 NS NS doubles (NS = 3 mb) of S^T (K_g S) and S^T (K S), S = [X W P]
+ *             (upper block triangles, zeros below).
+ *   residual: k_buck_residual<mb>, then k_modal_sum; W_out = dinv o (GX - KX diag(theta)) (dinv == NULL: without dinv),
+ *             norms_out: the 3 mb sums ||R_j||^2, ||GX_j||^2, ||KX_j||^2.  theta: mb doubles.
+ *   update:   k_buck_update<mb> with coef = C (3 mb x mb, row-major: rows of X, of W, of P); X, P, KX, KP, GX and GP come back
+ *             updated, W, KW and GW as they stood on the device after the launch.                                            */
+int pfem_buck_probe_gram(pfem_solver *s, int mb, int64_t n, const double *X, const double *W, const double *P, const double *KX,
+                         const double *KW, const double *KP, const double *GX, const double *GW, const double *GP, double *out);
+int pfem_buck_probe_residual(pfem_solver *s, int mb, int64_t n, const double *GX, const double *KX, const double *dinv, const double *theta,
+                             double *W_out, double *norms_out);
+int pfem_buck_probe_update(pfem_solver *s, int mb, int64_t n, const double *coef, double *X, double *W, double *P, double *KX, double *KW,
+                           double *KP, double *GX, double *GW, double *GP);
+/* the preconditioner T the last pfem_buckling_solve on this handle ran with: PFEM_PC_JACOBI or PFEM_PC_GAMG.  PFEM_ERR_STATE
+ * before the first run on the current set-up.                                                                                */
+int pfem_buckling_last_pc(pfem_solver *s, int *pc);
+/* microseconds of one launch of k_buck_gram<mb> (+ k_modal_sum), k_buck_update<mb>, k_modal_gram<mb> (+ k_modal_sum) and
+ * k_modal_update<mb> on blocks of n rows of the call's own (hashed values), `reps` of each between two HIP events after one
+ * warm-up launch: us[4] in that order.  An initialised handle is all it needs.  (tools/lab/buckling_measure.py)              */
+int pfem_buckling_bench_kernels(pfem_solver *s, int mb, int64_t n, int reps, double *us);
+/* kernel time [ms] of the last pfem_buckling_setup (HIP events around the stress pass, the zeroing and k_geo_assemble)       */
+int pfem_buckling_setup_ms(pfem_solver *s, double *ms);
 
 /* Timings of the last calls, measured with HIP events on the solver's stream [ms]. */
 typedef struct pfem_timings {

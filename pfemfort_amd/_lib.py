@@ -199,6 +199,16 @@ SIGNATURES = {
     "pfem_imp_probe_energy": [_P, _I, _L] + [_P] * 5 + [_I, _P, _D, _P, _P, _P],
     "pfem_dyn_probe_step": [_P, _L, _D, _D, _D, _I, _P, _P, _L, _L, _L, _I, _P, _I] + [_P] * 12,
     "pfem_solver_reordered": [_P, _P],
+    "pfem_elem_geometric": [_I, _P, _P, _P, _P, _P, _P],
+    "pfem_buckling_setup": [_P, _P, _P, _P],
+    "pfem_buckling_get_geometric": [_P, _P],
+    "pfem_buckling_solve": [_P, _I, _I, _D, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    "pfem_buck_probe_gram": [_P, _I, _L] + [_P] * 10,
+    "pfem_buck_probe_residual": [_P, _I, _L] + [_P] * 6,
+    "pfem_buck_probe_update": [_P, _I, _L] + [_P] * 10,
+    "pfem_buckling_last_pc": [_P, _P],
+    "pfem_buckling_bench_kernels": [_P, _I, _L, _I, _P],
+    "pfem_buckling_setup_ms": [_P, _P],
     "pfem_modal_last_pc": [_P, _P],
     "pfem_modal_bench_spmm": [_P, _I, _I, _P, _P],
     "pfem_matrix_info": [_P, _P, _P, _P, _P],

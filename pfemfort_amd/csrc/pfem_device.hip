@@ -35,6 +35,7 @@
 #include "pfem_dyn_kernels.hpp"
 #include "pfem_imp_kernels.hpp"
 #include "pfem_modal_kernels.hpp"
+#include "pfem_buckling_kernels.hpp"
 #include "pfem_thermal_kernels.hpp"
 #include "pfem_peer.hpp"
 
@@ -633,6 +634,18 @@ struct Thermal {
     std::vector<double> h_alpha;           // [1] without a map, [n_mat] with one
 };
 
+// linear buckling on an elasticity handle (pfem_buckling_*, pfem_buckling.inc): K_g's values on K's row form and the stresses
+// they were made from, from pfem_buckling_setup to the next set-up, the next mesh or the next pattern; the blocks of the solve
+// (Modal's six with its buffers, and the three K_g-products) from the first pfem_buckling_solve.  No mass: it does not depend on Dyn.
+struct Buck {
+    DevBuf<double> kg;                     // [entries of the row form], zero at the padding
+    DevBuf<double> stress;                 // [ng * nElem] SoA, the caller's element order
+    double setup_ms = 0.0;
+    std::unique_ptr<Modal> blocks;
+    DevBuf<double> GX, GW, GP;
+    bool ran = false;                      // blocks->pc_used is that of a run on this set-up (pfem_buckling_last_pc)
+};
+
 // ---------------------------------------------------------------------------
 // the solver object
 // ---------------------------------------------------------------------------
@@ -818,6 +831,7 @@ struct pfem_solver {
     std::unique_ptr<Amg> amg;      // -pc_type gamg: the hierarchy (pfem_amg.inc); rebuilt when the pattern changes
     std::unique_ptr<Dyn> dyn;      // explicit dynamics (pfem_dynamics.inc); dropped when the pattern changes
     std::unique_ptr<Thermal> thermal;   // thermal strains (pfem_thermal.inc); dropped with the mesh and when the pattern changes
+    std::unique_ptr<Buck> buck;         // linear buckling (pfem_buckling.inc); dropped with the mesh and when the pattern changes
     DevBuf<double> d_binv[3];      // node-block Jacobi: row (i - r0) of the inverse diagonal block, columns 0..2
     DevBuf<double> d_r2, d_z;      // ... second residual buffer (ping-pong), z = Binv r, per-row (first row | size << 30)
     // single-reduction CG (pfem_solver_set_cg_single_reduction): z is the SpMV input (guarded), s = A z, and a second
@@ -1611,6 +1625,7 @@ extern "C" int pfem_mesh_upload(pfem_solver *s, int kind, int64_t nElem, const i
     clear_materials(s);
     clear_boundary_faces(s);
     s->thermal.reset();
+    s->buck.reset();
     s->have_mesh = true;
     s->have_pattern = false;
     // a neighbour plan set before this upload names dofs in the previous mesh's (internal) numbering: it has to be set again
@@ -1804,6 +1819,7 @@ extern "C" int pfem_mesh_generate_box_axis(pfem_solver *s, int kind, double x0, 
     clear_materials(s);
     clear_boundary_faces(s);
     s->thermal.reset();
+    s->buck.reset();
     s->have_mesh = true;
     s->have_pattern = false;
     s->have_plan = false;
@@ -1928,6 +1944,7 @@ int alloc_vectors(pfem_solver *s)
     s->solved = false;
     s->dyn.reset();
     s->thermal.reset();
+    s->buck.reset();
     PFEM_TRY(s->d_rhs.alloc(n));
     PFEM_TRY(s->d_x.alloc(n));
     PFEM_TRY(s->d_r.alloc(n));
@@ -2960,11 +2977,11 @@ extern "C" int pfem_eval_elems(pfem_solver *s, const double *elemData, const dou
     });
 }
 
-extern "C" int pfem_get_csr(pfem_solver *s, int64_t *rowptr, int32_t *cols, double *vals)
+namespace {
+
+// CSR of the pattern with the values of `A` (the row form of K, or of another value array on it: pfem_buckling_get_geometric)
+int get_csr_of(pfem_solver *s, const SellDev &A, int64_t *rowptr, int32_t *cols, double *vals)
 {
-    if (!s) return PFEM_ERR_ARG;
-    if (!s->have_pattern) return PFEM_ERR_STATE;
-    PFEM_TRY(use_device(s));
     if (rowptr)
         PFEM_HIP(hipMemcpyAsync(rowptr, s->d_rowptr.p, sizeof(int64_t) * (s->n_loc + 1), hipMemcpyDeviceToHost, s->stream));
     if (cols || vals) {
@@ -2973,7 +2990,7 @@ extern "C" int pfem_get_csr(pfem_solver *s, int64_t *rowptr, int32_t *cols, doub
         if (cols) PFEM_TRY(dc.alloc(static_cast<size_t>(s->nnz)));
         if (vals) PFEM_TRY(dv.alloc(static_cast<size_t>(s->nnz)));
         if (s->n_loc > 0) {
-            hipLaunchKernelGGL(k_sell_to_csr, dim3(grid_for(s->n_loc)), dim3(kBlock), 0, s->stream, s->sell(), s->d_rowptr.p,
+            hipLaunchKernelGGL(k_sell_to_csr, dim3(grid_for(s->n_loc)), dim3(kBlock), 0, s->stream, A, s->d_rowptr.p,
                                cols ? dc.p : nullptr, vals ? dv.p : nullptr);
             PFEM_TRY(check_kernel("k_sell_to_csr"));
         }
@@ -2993,7 +3010,7 @@ extern "C" int pfem_get_csr(pfem_solver *s, int64_t *rowptr, int32_t *cols, doub
         if (!cols) {          // the columns are needed for the order even when the caller wants values only
             DevBuf<int32_t> dc;
             PFEM_TRY(dc.alloc(static_cast<size_t>(s->nnz)));
-            hipLaunchKernelGGL(k_sell_to_csr, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, s->sell(), s->d_rowptr.p, dc.p, static_cast<double *>(nullptr));
+            hipLaunchKernelGGL(k_sell_to_csr, dim3(grid_for(n)), dim3(kBlock), 0, s->stream, A, s->d_rowptr.p, dc.p, static_cast<double *>(nullptr));
             PFEM_HIP(hipStreamSynchronize(s->stream));       // the blocking copy below is not ordered after the solver's (non-blocking) stream
             PFEM_HIP(hipMemcpy(ic.data(), dc.p, sizeof(int32_t) * s->nnz, hipMemcpyDeviceToHost));
         } else {
@@ -3019,6 +3036,16 @@ extern "C" int pfem_get_csr(pfem_solver *s, int64_t *rowptr, int32_t *cols, doub
         if (rowptr) std::copy(ep.begin(), ep.end(), rowptr);
     }
     return PFEM_OK;
+}
+
+}  // namespace
+
+extern "C" int pfem_get_csr(pfem_solver *s, int64_t *rowptr, int32_t *cols, double *vals)
+{
+    if (!s) return PFEM_ERR_ARG;
+    if (!s->have_pattern) return PFEM_ERR_STATE;
+    PFEM_TRY(use_device(s));
+    return get_csr_of(s, s->sell(), rowptr, cols, vals);
 }
 
 extern "C" int pfem_get_rhs(pfem_solver *s, double *rhs_local)
@@ -5740,6 +5767,7 @@ extern "C" int pfem_solver_factorise(pfem_solver *s)
 #include "pfem_dynamics.inc"
 #include "pfem_implicit.inc"
 #include "pfem_modal.inc"
+#include "pfem_buckling.inc"
 #include "pfem_thermal.inc"
 
 extern "C" int pfem_solver_solve(pfem_solver *s, int *its, int *reason, double *rnorm)

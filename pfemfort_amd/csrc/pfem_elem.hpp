@@ -895,6 +895,55 @@ PFEM_HD bool elem_lumped_mass(int kind, const double *x, const double *y, const 
 }
 
 // ---------------------------------------------------------------------------
+// Geometric stiffness of the elasticity kinds (pfem_elem_geometric / pfem_buckling_setup).  With a stress
+// sig that is constant over the constant-strain element, K_g couples equal displacement components only:
+//     K_g[(a,i),(b,j)] = delta_ij g_ab,      g_ab = dvol * (grad N_a . (sig grad N_b))
+// Written-down order, host and device the same bits (no contraction):
+//   tet       sig = [xx,yy,zz,xy,yz,zx];  t = sig grad N_b:  tx = (sxx bx + sxy by) + szx bz,  ty = (sxy bx + syy by) + syz bz,
+//             tz = (szx bx + syz by) + szz bz;      g_ab = dvol * ((ax tx + ay ty) + az tz)
+//   triangle  sig = [xx,yy,xy];  tx = sxx bx + sxy by,  ty = sxy bx + syy by;      g_ab = dvol * (ax tx + ay ty)
+// sig is in the order elem_post stores `flux`, and for the triangle it IS that flux: the plane-stress shear stress as the
+// library reports it, with the reference's D(3,3) = b1 (1 - nu) (elast_tria_post_t above).  The triangle's K_g describes
+// in-plane instability only: a plane-stress element has no out-of-plane displacement to buckle into.  dvol and grad N are those
+// of the kind's stiffness routine (thickness ed[2] in the triangle's dvol).  g[a + npe * b].  Kinds 3 and 5 only (the caller
+// checks).  false: a negative Jacobian.
+// ---------------------------------------------------------------------------
+PFEM_HD bool elem_geometric(int kind, const double *x, const double *y, const double *z, const double *ed, const double *sig, double *g)
+{
+    if (kind == 3) {
+        TetGeom q;
+        tet_geometry(x, y, z, q);
+        if (q.jac < 0.0) return false;
+        const double dvol = kGaussWtTet * q.jac;
+        const double sxx = sig[0], syy = sig[1], szz = sig[2], sxy = sig[3], syz = sig[4], szx = sig[5];
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const double bx = q.gx[b], by = q.gy[b], bz = q.gz[b];
+            const double tx = (sxx * bx + sxy * by) + szx * bz;
+            const double ty = (sxy * bx + syy * by) + syz * bz;
+            const double tz = (szx * bx + syz * by) + szz * bz;
+#pragma unroll
+            for (int a = 0; a < 4; ++a) g[a + 4 * b] = dvol * ((q.gx[a] * tx + q.gy[a] * ty) + q.gz[a] * tz);
+        }
+        return true;
+    }
+    TriaGeom q;
+    tria_geometry(x, y, q);
+    if (q.jac < 0.0) return false;
+    const double dvol = 0.5 * (q.jac * ed[2]);
+    const double sxx = sig[0], syy = sig[1], sxy = sig[2];
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+        const double bx = q.gx[b], by = q.gy[b];
+        const double tx = sxx * bx + sxy * by;
+        const double ty = sxy * bx + syy * by;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) g[a + 3 * b] = dvol * (q.gx[a] * tx + q.gy[a] * ty);
+    }
+    return true;
+}
+
+// ---------------------------------------------------------------------------
 // Sides of an element and the loads on them (pfem_face_load / pfem_surface_geometry / pfem_rhs_add_surface_load)
 // ---------------------------------------------------------------------------
 // Side f of an element is the face (tet) or edge (triangle) OPPOSITE local node f; its nodes are the element's other local

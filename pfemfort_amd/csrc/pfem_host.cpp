@@ -190,6 +190,22 @@ extern "C" int pfem_elem_thermal_load(int kind, const double *xNode, const doubl
     return PFEM_OK;
 }
 
+// Geometric stiffness of one element of an elasticity kind under the stress sigma (pfem_elem.hpp: elem_geometric): the npe x npe
+// scalars g[a + npe * b]; K_g[(a,i),(b,j)] = delta_ij g_ab.
+extern "C" int pfem_elem_geometric(int kind, const double *xNode, const double *yNode, const double *zNode, const double *elemData,
+                                   const double *sigma, double *Kg)
+{
+    if (kind != PFEM_ELAST_TET && kind != PFEM_ELAST_TRIA) return PFEM_ERR_ARG;
+    if (!xNode || !yNode || !sigma || !Kg) return PFEM_ERR_ARG;
+    if (kind == PFEM_ELAST_TET && !zNode) return PFEM_ERR_ARG;
+    if (kind == PFEM_ELAST_TRIA && !elemData) return PFEM_ERR_ARG;      // (the thickness; the tet reads no elemData)
+    double g[16];
+    if (!elem_geometric(kind, xNode, yNode, zNode, elemData, sigma, g)) return PFEM_ERR_NEG_JAC;
+    const int npe = kind_npelem(kind);
+    std::copy(g, g + npe * npe, Kg);
+    return PFEM_OK;
+}
+
 // pfem_elem_post of an elasticity kind under a thermal state (pfem_elem.hpp: elem_post_th): the stress is D (strain - eps_th),
 // scalar and fint are formed from it, grad stays the total strain.
 extern "C" int pfem_elem_post_thermal(int kind, const double *xNode, const double *yNode, const double *zNode, const double *elemData,

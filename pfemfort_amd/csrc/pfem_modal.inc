@@ -118,6 +118,26 @@ int modal_gram_to_host(pfem_solver *s, const ModalView &V, bool with_gram, unsig
     return PFEM_OK;
 }
 
+// W <- the cycle of the last gamg solve on every column of W in turn: amg_apply as it stands, through the contiguous vector V.vec
+// and the cycle's own output vector (pfem_modal_solve, pfem_buckling_solve).  false: the cycle failed.
+bool modal_cycle_columns(pfem_solver *s, const ModalView &V)
+{
+    Amg &A = *s->amg;
+    const int tail_build = A.tail_build;
+    for (int j = 0; j < V.mb; ++j) {
+        with_mb(V.mb, [&](auto MB) {
+            launch(k_modal_pack<decltype(MB)::value>, dim3(grid_for(V.n)), dim3(kBlock), 0, s->stream, nullptr, nullptr, V.n, V.W, j, V.vec);
+        });
+        const double *z = amg_apply(s, A, V.vec, nullptr);
+        if (!z) return false;
+        with_mb(V.mb, [&](auto MB) {
+            launch(k_modal_unpack<decltype(MB)::value>, dim3(grid_for(V.n)), dim3(kBlock), 0, s->stream, nullptr, nullptr, V.n, z, j, V.W);
+        });
+    }
+    A.tail_build = tail_build;             // (what the last SOLVE's cycle launched, pfem_solver_amg_tail_from)
+    return true;
+}
+
 // R, the norms' partials and W = T R: the point Jacobi inside the residual kernel, or (gamg) the cycle of the last gamg solve on
 // every column in turn -- amg_apply as it stands, through the contiguous vector V.vec and the cycle's own output vector
 unsigned modal_residual(pfem_solver *s, const ModalView &V, bool gamg)
@@ -127,21 +147,7 @@ unsigned modal_residual(pfem_solver *s, const ModalView &V, bool gamg)
         launch(k_modal_residual<decltype(MB)::value>, dim3(gr), dim3(kBlock), 0, s->stream, nullptr, nullptr, V.n, V.KX, V.X, V.m, gamg ? nullptr : V.dinv,
                V.coef + 3 * V.mb * V.mb, V.W, V.part_res);
     });
-    if (gamg) {
-        Amg &A = *s->amg;
-        const int tail_build = A.tail_build;
-        for (int j = 0; j < V.mb; ++j) {
-            with_mb(V.mb, [&](auto MB) {
-                launch(k_modal_pack<decltype(MB)::value>, dim3(grid_for(V.n)), dim3(kBlock), 0, s->stream, nullptr, nullptr, V.n, V.W, j, V.vec);
-            });
-            const double *z = amg_apply(s, A, V.vec, nullptr);
-            if (!z) return 0;
-            with_mb(V.mb, [&](auto MB) {
-                launch(k_modal_unpack<decltype(MB)::value>, dim3(grid_for(V.n)), dim3(kBlock), 0, s->stream, nullptr, nullptr, V.n, z, j, V.W);
-            });
-        }
-        A.tail_build = tail_build;         // (what the last SOLVE's cycle launched, pfem_solver_amg_tail_from)
-    }
+    if (gamg && !modal_cycle_columns(s, V)) return 0;
     return gr;
 }
 

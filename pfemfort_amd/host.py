@@ -313,6 +313,19 @@ def ThermalLoad(kind, xNode, yNode, zNode, elemData, alpha, theta):
     return F, sg
 
 
+def GeometricStiffness(kind, xNode, yNode, zNode, elemData, sigma):
+    """Geometric stiffness of one element of an elasticity kind under the stress ``sigma`` (pfem_elem_geometric), in the order
+    ``ElementPost`` returns ``flux``: the ``npe x npe`` scalars ``g[a, b] = dvol (grad N_a . sigma grad N_b)``;
+    ``K_g[(a,i),(b,j)] = delta_ij g[a, b]``.  ``elemData`` gives the thickness of ``ELAST_TRIA`` and may be None for the tet."""
+    npe = L.NPELEM.get(kind, 4)
+    g = np.empty(npe * npe)
+    z = None if zNode is None else _f64(zNode)
+    ed = None if elemData is None else _f64(elemData)
+    sg = None if sigma is None else _f64(sigma).ravel()
+    L.check(L.lib().pfem_elem_geometric(int(kind), _p(_f64(xNode)), _p(_f64(yNode)), _p(z), _p(ed), _p(sg), _p(g)), "pfem_elem_geometric")
+    return g.reshape(npe, npe).T                             # (g[a + npe b])
+
+
 def ElementPostThermal(kind, xNode, yNode, zNode, elemData, valC, alpha, theta):
     """``ElementPost`` of an elasticity kind under a thermal state (pfem_elem_post_thermal): the stress is
     ``D (strain - eps_th)``, von Mises and ``fint`` are formed from it, ``grad`` stays the total strain."""

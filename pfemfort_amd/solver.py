@@ -28,6 +28,7 @@ def _i32(a):
 
 
 ModalResult = namedtuple("ModalResult", "omega omega2 modes residuals iterations restarts reason block pc")
+BucklingResult = namedtuple("BucklingResult", "theta factors modes residuals iterations restarts reason block pc")
 
 
 class PetscSolver:
@@ -803,6 +804,100 @@ class PetscSolver:
         return ModalResult(omega=np.sqrt(np.maximum(om2, 0.0)), omega2=om2, modes=np.ascontiguousarray(phi.T) if modes else None,
                            residuals=res, iterations=its.value, restarts=restarts.value, reason=reason.value, block=mb,
                            pc={0: "jacobi", 2: "gamg"}[used.value])
+
+    # ---- linear buckling (pfem_buckling_*; one rank, batched path, the elasticity kinds) ----------------------------------------
+    def bucklingSetup(self, elemData, u=None, stress=None):
+        """The geometric stiffness ``K_g(sigma_0)`` on the device, on K's pattern (``pfem_buckling_setup``).  ``stress``
+        (``(ng, nElem)``, as ``elementFields`` returns ``flux``) prescribes the reference stress; else it is the stress of ``u``
+        (``None``: the last solve's field), thermal state included, formed on the device.  ``elemData`` as ``assemble`` takes
+        it.  Lives until the next set-up, mesh or ``buildPattern``; a re-assemble of K keeps it."""
+        kind = getattr(self, "kind", None)
+        ed = self._elem_data(elemData)
+        uu = None if u is None else _f64(u).ravel()
+        st = None if stress is None else _f64(stress)
+        if kind is not None and st is not None and st.shape != (L.NG[kind], self.nElem):
+            raise ValueError(f"stress must be {L.NG[kind]} x {self.nElem}")
+        assert kind is None or uu is None or uu.size == self.nNode * L.NDOF[kind]
+        L.check(L.lib().pfem_buckling_setup(self._h, _p(ed), _p(uu), _p(st)), "pfem_buckling_setup")
+
+    def geometricStiffness(self):
+        """``K_g``'s values in ``getCSR``'s layout and order, with its ``rowptr`` and ``cols`` (``pfem_buckling_get_geometric``)."""
+        vals = np.empty(self.matrixInfo()["nnz"])
+        L.check(L.lib().pfem_buckling_get_geometric(self._h, _p(vals)), "pfem_buckling_get_geometric")
+        return vals
+
+    def bucklingSolve(self, n_modes, tol=1e-6, max_iterations=1000, block=0, pc=None, x0=None, modes=True):
+        """The lowest ``n_modes`` (1..12) pairs of ``K_g phi = theta K phi`` after ``bucklingSetup`` (``pfem_buckling_solve``):
+        the critical load factors of ``(K + lambda K_g) phi = 0`` are ``lambda = -1 / theta`` for ``theta < 0``, ``inf`` for a
+        pair that does not buckle in the load's direction.  LOBPCG as ``modalSolve`` runs it, with the same choice of block, start
+        and preconditioner ``pc`` (the cycle of the last gamg solve where current, else the point Jacobi of K).  Returns a
+        ``BucklingResult``: ``theta`` (ascending), ``factors``, ``modes`` (``N x n_modes``, ``phi^T K phi = 1``, the largest
+        entry positive; None with ``modes=False``), ``residuals`` (``||K_g phi - theta K phi||`` relative to
+        ``||K_g phi|| + |theta| ||K phi||``), ``iterations``, ``restarts``, ``reason`` (1 converged, -1 ``max_iterations``,
+        -2 breakdown), ``block`` and ``pc``.  The solve, the steppers, the modal and the thermal state are left as they are."""
+        n_modes = int(n_modes)
+        mb = max(int(block), 4 if n_modes <= 2 else 8 if n_modes <= 6 else 16)
+        N = self.matrixInfo()["n_owned"]
+        k = max(n_modes, 1)
+        th = np.zeros(k); fac = np.zeros(k); res = np.zeros(k)
+        phi = np.zeros((k, N)) if modes else None
+        if x0 is not None:
+            x0 = _f64(x0)
+            if x0.shape != (N, mb):
+                raise ValueError(f"x0 must be {N} x {mb}")
+        its = C.c_int(0); restarts = C.c_int(0); reason = C.c_int(0)
+        L.check(L.lib().pfem_buckling_solve(self._h, n_modes, int(block), float(tol), int(max_iterations),
+                                            {None: -1, "jacobi": 0, "pbjacobi": 1, "gamg": 2}.get(pc, pc), _p(x0) if x0 is not None else None, _p(th), _p(fac),
+                                            _p(phi) if modes else None, _p(res), C.byref(its), C.byref(restarts), C.byref(reason)), "pfem_buckling_solve")
+        used = C.c_int(0)
+        L.check(L.lib().pfem_buckling_last_pc(self._h, C.byref(used)), "pfem_buckling_last_pc")
+        return BucklingResult(theta=th, factors=fac, modes=np.ascontiguousarray(phi.T) if modes else None, residuals=res, iterations=its.value,
+                              restarts=restarts.value, reason=reason.value, block=mb, pc={0: "jacobi", 2: "gamg"}[used.value])
+
+    def buckProbeGram(self, X, W, P, KX, KW, KP, GX, GW, GP):
+        """One launch of ``bucklingSolve``'s Gram kernel and of the sum of its partials on nine ``n x mb`` blocks
+        (``pfem_buck_probe_gram``): ``(S^T K_g S, S^T K S)`` from the product blocks, ``3 mb x 3 mb`` each -- the upper block
+        triangles, zeros below them."""
+        B, n, mb = self._blocks((X, W, P, KX, KW, KP, GX, GW, GP))
+        ns = 3 * mb
+        out = np.empty((2, ns, ns))
+        L.check(L.lib().pfem_buck_probe_gram(self._h, mb, n, *[_p(b) for b in B], _p(out)), "pfem_buck_probe_gram")
+        return out[0], out[1]
+
+    def buckProbeResidual(self, GX, KX, theta, dinv=None):
+        """One launch of ``bucklingSolve``'s residual kernel and of the sum of its partials (``pfem_buck_probe_residual``):
+        ``(W, norms)`` with ``W = dinv o (GX - KX diag(theta))`` (without ``dinv``: the residual itself) and ``norms``
+        (``3 x mb``) the squared column norms of the residual, of ``GX`` and of ``KX``."""
+        (GX, KX), n, mb = self._blocks((GX, KX))
+        theta = _f64(theta)
+        dinv = None if dinv is None else _f64(dinv)
+        if theta.shape != (mb,) or (dinv is not None and dinv.shape != (n,)):
+            raise ValueError(f"dinv must hold {n} doubles, theta {mb}")
+        W, norms = np.empty((n, mb)), np.empty((3, mb))
+        L.check(L.lib().pfem_buck_probe_residual(self._h, mb, n, _p(GX), _p(KX), _p(dinv), _p(theta), _p(W), _p(norms)), "pfem_buck_probe_residual")
+        return W, norms
+
+    def buckProbeUpdate(self, coef, X, W, P, KX, KW, KP, GX, GW, GP):
+        """One launch of ``bucklingSolve``'s update kernel with the coefficients ``coef`` (``3 mb x mb``) on copies of the nine
+        blocks (``pfem_buck_probe_update``): the nine as the launch left them."""
+        B, n, mb = self._blocks((X, W, P, KX, KW, KP, GX, GW, GP))
+        coef = _f64(coef)
+        if coef.shape != (3 * mb, mb):
+            raise ValueError(f"coef must be {3 * mb} x {mb}")
+        L.check(L.lib().pfem_buck_probe_update(self._h, mb, n, _p(coef), *[_p(b) for b in B]), "pfem_buck_probe_update")
+        return tuple(B)
+
+    def benchBucklingKernels(self, mb, n, reps=20):
+        """Microseconds of one launch of ``k_buck_gram`` (with the sum), ``k_buck_update``, ``k_modal_gram`` (with the sum) and
+        ``k_modal_update`` on blocks of ``n`` rows (``pfem_buckling_bench_kernels``)."""
+        us = np.zeros(4)
+        L.check(L.lib().pfem_buckling_bench_kernels(self._h, int(mb), int(n), int(reps), _p(us)), "pfem_buckling_bench_kernels")
+        return dict(zip(("buck_gram", "buck_update", "modal_gram", "modal_update"), us))
+
+    def bucklingSetupMs(self):
+        ms = C.c_double(0)
+        L.check(L.lib().pfem_buckling_setup_ms(self._h, C.byref(ms)), "pfem_buckling_setup_ms")
+        return ms.value
 
     def modalSpmm(self, X):
         """``K X`` for a block ``X`` (``n_local x 4 / 8 / 16``) by the block product of ``modalSolve`` (``pfem_modal_spmm``)."""
