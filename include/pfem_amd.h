@@ -690,6 +690,52 @@ int pfem_buckling_solve(pfem_solver *s, int n_modes, int block /*0: auto*/, doub
                         double *modes /* n_modes x n_owned, mode-major; may be NULL */, double *residuals, int *iterations,
                         int *restarts, int *reason /* 1 converged, -1 max_iterations, -2 breakdown */);
 
+/* ---- several load cases in one solve: batched PCG on the block product ----- */
+/* K x_j = B_j for nrhs right-hand sides on the assembled K.  Column j is exactly the solve
+ * pfem_solver_solve would do with B_j as right-hand side: the two-reduction KSPCG recurrences from x = 0, the norm ||z|| against
+ * ttol = max(rtol ||z0||, abstol), the solver's rtol / abstol / dtol / maxits, the reasons 2, 3, -3, -4, -8 and -10 with that
+ * routine's meaning and its `its` convention.  A negative reason in some column is not an error of the call (PFEM_OK, as
+ * pfem_solver_solve).  A zero column returns reason 3, its = 0 and x = 0 exactly.
+ *
+ * The columns are independent CG iterations that share one pass over the matrix per iteration (the block product of
+ * pfem_modal_solve with the (p, Kp) sums as its epilogue) and nothing else: per-column step lengths, verdicts and iteration
+ * counts; no coupled steps, no rank questions -- this is not O'Leary's block CG.  When a column finishes, its x, r and p are
+ * never written again; the others go on.  Columns are processed in panels of 4 or 8: nrhs <= 4 takes one panel of 4, otherwise
+ * panels of 8 and a last panel of 4 where at most 4 columns remain; the panels run one after the other, padding columns are
+ * zero and finish at the start.  A column's bits depend on n and on its panel's width only -- not on its place in the panel or on
+ * what the other columns hold -- and every run gives the same bits.
+ *
+ * B and X are case-major (column j at B + j * n_owned) in pfem_solver_get_solution's order, which is pfem_get_rhs's on one rank:
+ * the caller's; the internal renumbering never shows.  A Dirichlet lift is part of a right-hand side: take each B_j from
+ * pfem_get_rhs after that case's assemble and loads.
+ *
+ * T follows pfem_modal_solve's rule.  pc = -1 takes the solver's.  Point Jacobi is 1 / K_ii extracted from the row form into the
+ * run's own buffer; PFEM_PC_NODE_BLOCK_JACOBI gets it too.  Where gamg is in effect and its numeric set-up is current -- a gamg
+ * solve has run since the last assemble -- T is the cycle of that solve, applied to the columns still running one at a time;
+ * pc = PFEM_PC_GAMG without a current set-up: PFEM_ERR_STATE.  Under gamg the cycles run one after the other: the gain is the
+ * assembly and the set-up not repeated per case.
+ *
+ * Preconditions: one rank; a pattern and an assembled matrix whose fp64 row form is current: on the batched path any time after
+ * pfem_assemble, on the MatSetValues path only after a solve has uploaded the staged values (PFEM_ERR_STATE before, with a message
+ * that says so).  PFEM_ERR_ARG before the device is touched: a NULL pointer, nrhs < 1 or > PFEM_MULTI_MAX_RHS, an unknown pc.  A
+ * non-finite entry of B is not checked.  PFEM_ERR_NOGPU without a device.
+ *
+ * It leaves the solve alone: the solution vector, the right-hand side, last_its / last_reason / last_rnorm, the residual
+ * history, the timings, the CG graphs, the status and the states of the steppers, the modal, buckling and thermal paths are not
+ * written.  Under gamg it writes what the modal solve writes: the cycle's work vectors and the SpMV's value copies.  Its own
+ * state (five panels of n x MB doubles, six under gamg: 320 B a row for a panel of 8) is allocated at the first call, again
+ * when n or the panel width changes, and dropped with the pattern.
+ *
+ * When it pays (measured on one MI355X, DESIGN.md section 16, 30 iterations under the point Jacobi): from 4 columns on the
+ * batched solve is ahead of as many single solves -- per column-iteration 0.89 of their time on the 200^3 Poisson box (0.96 for
+ * one panel of 4), 0.63 on the 50 x 300 x 50 beam, 0.45 on a jittered box without a value dictionary, 0.27 on a 20^3 box.  For ONE
+ * column it loses: the column travels in a panel of 4 and costs what 4 cost, 1.7 to 3.9 x pfem_solver_solve, which is the call
+ * for a single right-hand side.                                                                                              */
+#define PFEM_MULTI_MAX_RHS 64
+int pfem_solver_solve_multi(pfem_solver *s, int nrhs, const double *B /* nrhs x n_owned, case-major */,
+                            int pc /* -1: the solver's */, double *X /* nrhs x n_owned, case-major */,
+                            int *its /* nrhs */, int *reason /* nrhs */, double *rnorm /* nrhs */);
+
 /* ---- inspection / export (device -> host) -------------------------------- */
 /* global dof id of every local row (owned first, then ghosts ascending) */
 int pfem_get_local_to_global(pfem_solver *s, int64_t *gid);

@@ -294,6 +294,46 @@ int pfem_buckling_last_pc(pfem_solver *s, int *pc);
 int pfem_buckling_bench_kernels(pfem_solver *s, int mb, int64_t n, int reps, double *us);
 /* kernel time [ms] of the last pfem_buckling_setup (HIP events around the stress pass, the zeroing and k_geo_assemble)       */
 int pfem_buckling_setup_ms(pfem_solver *s, double *ms);
+/* One launch of a kernel of pfem_solver_solve_multi on panels of the caller's, through the grid functions and the launch code of
+ * the solve itself.  An initialised handle is all they need.  Panels are host arrays of n x mb doubles in
+ * plain row order, mb = 4 or 8; dinv: n doubles, or NULL for the form the solve launches under gamg.  Every device block has NaN
+ * guard tiles (see the pfem_modal_probe_* above); a block a kernel takes as const is compared with what went up.  pfem_mcg_ctl is
+ * the device's control block as a plain struct: per column (8 places, mb of them used) beta[2], rn0, ttol, rn, alpha, bb, flag,
+ * its and the verdict of the current step (0 idle, 1 goes on, 2 last step, 3 breakdown); the running count; the step counter.
+ * Partials of the vector kernels: part[block][2][mb] -- (r,z), then (z,z) -- for *gv blocks (room for 1 024 x 2 mb doubles).
+ *   init:      k_mcg_init<mb>: X = 0, R = B, and with dinv P = dinv o R and the partials (without: P and part come back NaN).
+ *   start:     k_mcg_start (one block) on nparts rows of partials: *ctl is written throughout.
+ *   fold:      k_mcg_fold<mb>: nb rows of mb product partials to fold_out[32][mb].
+ *   update:    k_mcg_update<mb> on *ctl (in and out) and the folded product partials fold_pw[32][mb]: R in place, the partials
+ *              (dinv == NULL: none, part_out comes back NaN).
+ *   dots:      k_mcg_dots<mb>: the partials from R and Z; ctl == NULL: every column; fold_pw == NULL: no breakdown marker.
+ *   verdict:   k_mcg_verdict (one block) on *ctl (in and out) and nparts rows of partials.
+ *   direction: k_mcg_direction<mb> on *ctl: P and X in place; Z (dinv == NULL) is the stored T R.
+ * pfem_multi_spmm_dot: k_spmm_dot<mb>, then k_mcg_fold, on the handle's assembled matrix like pfem_modal_spmm: W = K P in the
+ * caller's dof order and pw_out[mb] = the folded (p, Kp) summed in index order, as k_mcg_update reads them.                   */
+typedef struct pfem_mcg_ctl {
+    double beta[8][2], rn0[8], ttol[8], rn[8], alpha[8], bb[8];
+    int flag[8], its[8], verdict[8], running, step;
+} pfem_mcg_ctl;
+int pfem_multi_probe_init(pfem_solver *s, int mb, int64_t n, const double *B, const double *dinv, double *X_out, double *R_out, double *P_out,
+                          double *part_out, int *gv);
+int pfem_multi_probe_start(pfem_solver *s, int mb, int nparts, const double *part, double rtol, double abstol, pfem_mcg_ctl *ctl);
+int pfem_multi_probe_fold(pfem_solver *s, int mb, int nb, const double *part_pw, double *fold_out);
+int pfem_multi_probe_update(pfem_solver *s, int mb, int64_t n, pfem_mcg_ctl *ctl, const double *fold_pw, const double *W, const double *dinv,
+                            double *R, double *part_out, int *gv);
+int pfem_multi_probe_dots(pfem_solver *s, int mb, int64_t n, const pfem_mcg_ctl *ctl, const double *fold_pw, const double *R, const double *Z,
+                          double *part_out, int *gv);
+int pfem_multi_probe_verdict(pfem_solver *s, int mb, pfem_mcg_ctl *ctl, int nparts, const double *part, double dtol, int maxits);
+int pfem_multi_probe_direction(pfem_solver *s, int mb, int64_t n, pfem_mcg_ctl *ctl, const double *R, const double *dinv, const double *Z,
+                               double *P, double *X);
+int pfem_multi_spmm_dot(pfem_solver *s, int mb, const double *P, double *W_out, double *pw_out);
+/* the preconditioner T the last pfem_solver_solve_multi on this handle ran with: PFEM_PC_JACOBI or PFEM_PC_GAMG.  PFEM_ERR_STATE
+ * before the first call on the current pattern.                                                                               */
+int pfem_multi_last_pc(pfem_solver *s, int *pc);
+/* device time [ms] of `reps` multi solves of the assembled right-hand side scaled by j + 1 (column j), between two HIP events per
+ * panel -- after the panel's upload, after the last copy of its control block -- summed over the panels: ms[reps]; its[nrhs] of
+ * the last one.  Arguments and preconditions as pfem_solver_solve_multi.  (tools/lab/multirhs_measure.py)                   */
+int pfem_multi_bench(pfem_solver *s, int nrhs, int reps, int pc, double *ms, int *its);
 
 /* Timings of the last calls, measured with HIP events on the solver's stream [ms]. */
 typedef struct pfem_timings {

@@ -10,4 +10,4 @@ from ._lib import (ELAST_TET, ELAST_TRIA, POISSON_TET, POISSON_TRIA, POISSON_TRI
 from .drivers import (poissontransient, tetraelasticityexplicit, tetraelasticityparallelimpl1,  # noqa: F401
                       tetrapoissonparallelimpl1,
                       triaelasticityexplicit, triaelasticityparallelimpl1, triapoissonparallelimpl1, triapoissonserialimpl1)
-from .solver import ModalResult, PetscSolver  # noqa: F401
+from .solver import ModalResult, PetscSolver, SolveManyResult  # noqa: F401

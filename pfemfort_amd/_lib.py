@@ -57,6 +57,16 @@ class CgCtl(C.Structure):
                 ("alpha", C.c_double), ("flag", C.c_int), ("its", C.c_int), ("its_dir", C.c_int)]
 
 
+MULTI_MAX_RHS = 64
+
+
+class McgCtl(C.Structure):
+    """the control block of one panel of ``solveMany`` as the probes exchange it (pfem_mcg_ctl, include/pfem_amd_diag.h)"""
+    _fields_ = [("beta", (C.c_double * 2) * 8), ("rn0", C.c_double * 8), ("ttol", C.c_double * 8), ("rn", C.c_double * 8),
+                ("alpha", C.c_double * 8), ("bb", C.c_double * 8), ("flag", C.c_int * 8), ("its", C.c_int * 8),
+                ("verdict", C.c_int * 8), ("running", C.c_int), ("step", C.c_int)]
+
+
 # host hooks of the communication backend (include/pfem_amd.h, section 5)
 HOST_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int64)
 HOST_EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64),
@@ -211,6 +221,17 @@ SIGNATURES = {
     "pfem_buckling_setup_ms": [_P, _P],
     "pfem_modal_last_pc": [_P, _P],
     "pfem_modal_bench_spmm": [_P, _I, _I, _P, _P],
+    "pfem_solver_solve_multi": [_P, _I, _P, _I, _P, _P, _P, _P],
+    "pfem_multi_probe_init": [_P, _I, _L] + [_P] * 7,
+    "pfem_multi_probe_start": [_P, _I, _I, _P, _D, _D, _P],
+    "pfem_multi_probe_fold": [_P, _I, _I, _P, _P],
+    "pfem_multi_probe_update": [_P, _I, _L] + [_P] * 7,
+    "pfem_multi_probe_dots": [_P, _I, _L] + [_P] * 6,
+    "pfem_multi_probe_verdict": [_P, _I, _P, _I, _P, _D, _I],
+    "pfem_multi_probe_direction": [_P, _I, _L] + [_P] * 6,
+    "pfem_multi_spmm_dot": [_P, _I, _P, _P, _P],
+    "pfem_multi_last_pc": [_P, _P],
+    "pfem_multi_bench": [_P, _I, _I, _I, _P, _P],
     "pfem_matrix_info": [_P, _P, _P, _P, _P],
     "pfem_get_local_to_global": [_P, _P],
     "pfem_get_csr": [_P, _P, _P, _P],

@@ -36,6 +36,7 @@
 #include "pfem_imp_kernels.hpp"
 #include "pfem_modal_kernels.hpp"
 #include "pfem_buckling_kernels.hpp"
+#include "pfem_multi_kernels.hpp"
 #include "pfem_thermal_kernels.hpp"
 #include "pfem_peer.hpp"
 
@@ -646,6 +647,25 @@ struct Buck {
     bool ran = false;                      // blocks->pc_used is that of a run on this set-up (pfem_buckling_last_pc)
 };
 
+// several right-hand sides in one solve (pfem_solver_solve_multi, pfem_multi.inc): the panels of one run of mb columns, the
+// inverse diagonal, the vector gamg's cycle reads a column from, the partials and the control block with its pinned host copy;
+// allocated at the first call, again when n or mb changes, dropped when the pattern changes
+struct Multi {
+    int mb = 0;
+    int64_t n = 0;
+    int pc_used = PFEM_PC_JACOBI;          // the T of the last run (pfem_multi_last_pc)
+    DevBuf<double> B, X, R, P, W, Z, dinv, vec, part, part_pw, fold_pw;   // (Z: only under gamg)
+    DevBuf<McgCtl> ctl;
+    McgCtl *h_ctl = nullptr;               // pinned
+    Multi() = default;
+    Multi(const Multi &) = delete;
+    Multi &operator=(const Multi &) = delete;
+    ~Multi()
+    {
+        if (h_ctl) (void)hipHostFree(h_ctl);
+    }
+};
+
 // ---------------------------------------------------------------------------
 // the solver object
 // ---------------------------------------------------------------------------
@@ -832,6 +852,7 @@ struct pfem_solver {
     std::unique_ptr<Dyn> dyn;      // explicit dynamics (pfem_dynamics.inc); dropped when the pattern changes
     std::unique_ptr<Thermal> thermal;   // thermal strains (pfem_thermal.inc); dropped with the mesh and when the pattern changes
     std::unique_ptr<Buck> buck;         // linear buckling (pfem_buckling.inc); dropped with the mesh and when the pattern changes
+    std::unique_ptr<Multi> multi;       // several right-hand sides (pfem_multi.inc); dropped when the pattern changes
     DevBuf<double> d_binv[3];      // node-block Jacobi: row (i - r0) of the inverse diagonal block, columns 0..2
     DevBuf<double> d_r2, d_z;      // ... second residual buffer (ping-pong), z = Binv r, per-row (first row | size << 30)
     // single-reduction CG (pfem_solver_set_cg_single_reduction): z is the SpMV input (guarded), s = A z, and a second
@@ -1945,6 +1966,7 @@ int alloc_vectors(pfem_solver *s)
     s->dyn.reset();
     s->thermal.reset();
     s->buck.reset();
+    s->multi.reset();
     PFEM_TRY(s->d_rhs.alloc(n));
     PFEM_TRY(s->d_x.alloc(n));
     PFEM_TRY(s->d_r.alloc(n));
@@ -5768,6 +5790,7 @@ extern "C" int pfem_solver_factorise(pfem_solver *s)
 #include "pfem_implicit.inc"
 #include "pfem_modal.inc"
 #include "pfem_buckling.inc"
+#include "pfem_multi.inc"
 #include "pfem_thermal.inc"
 
 extern "C" int pfem_solver_solve(pfem_solver *s, int *its, int *reason, double *rnorm)

@@ -28,6 +28,7 @@ def _i32(a):
 
 
 ModalResult = namedtuple("ModalResult", "omega omega2 modes residuals iterations restarts reason block pc")
+SolveManyResult = namedtuple("SolveManyResult", "x iterations reasons rnorm pc")
 BucklingResult = namedtuple("BucklingResult", "theta factors modes residuals iterations restarts reason block pc")
 
 
@@ -952,6 +953,149 @@ class PetscSolver:
             raise ValueError(f"coef must be {3 * mb} x {mb}")
         L.check(L.lib().pfem_modal_probe_update(self._h, mb, n, _p(coef), *[_p(b) for b in B]), "pfem_modal_probe_update")
         return tuple(B)
+
+    # ---- several right-hand sides in one solve (pfem_solver_solve_multi; one rank) ----------------------------------------------
+    _PC_CODES = {None: -1, "jacobi": 0, "pbjacobi": 1, "gamg": 2}
+
+    def solveMany(self, B, pc=None):
+        """``K x_j = B_j`` for up to 64 right-hand sides on the assembled matrix (``pfem_solver_solve_multi``): every column is
+        the CG iteration ``solve`` would run with ``B_j`` as right-hand side -- from ``x = 0``, with the solver's tolerances
+        and reasons --, and the columns share one pass over the matrix per iteration, in panels of 4 or 8.  ``B``: ``nrhs x
+        N`` (one case per row, ``getRHS()``'s order) or a single vector.  ``pc`` as ``modalSolve``: None takes the solver's
+        (the cycle of the last gamg solve where that is current, else the point Jacobi), ``"jacobi"`` forces the point
+        Jacobi, ``"gamg"`` raises ``ERR_STATE`` where the cycle is not current.  Returns a ``SolveManyResult``: ``x`` (``nrhs x
+        N``), ``iterations``, ``reasons``, ``rnorm`` (arrays of ``nrhs``) and ``pc``, what ran.  A negative reason in some
+        column is not an error.  The solve's own solution, right-hand side, history and counters are left as they are."""
+        B = np.array(B, dtype=np.float64, order="C", ndmin=2)
+        N = self.matrixInfo()["n_owned"]
+        if B.ndim != 2 or B.shape[1] != N:
+            raise ValueError(f"B must be nrhs x {N} (or one vector of {N}), not {B.shape}")
+        nrhs = B.shape[0]
+        X = np.zeros((max(nrhs, 1), N))
+        its = np.zeros(max(nrhs, 1), dtype=np.int32); why = np.zeros(max(nrhs, 1), dtype=np.int32); rn = np.zeros(max(nrhs, 1))
+        L.check(L.lib().pfem_solver_solve_multi(self._h, nrhs, _p(B), self._PC_CODES.get(pc, pc), _p(X), _p(its), _p(why), _p(rn)),
+                "pfem_solver_solve_multi")
+        used = C.c_int(0)
+        L.check(L.lib().pfem_multi_last_pc(self._h, C.byref(used)), "pfem_multi_last_pc")
+        return SolveManyResult(x=X, iterations=its, reasons=why, rnorm=rn, pc={0: "jacobi", 2: "gamg"}[used.value])
+
+    def benchSolveMany(self, nrhs, reps=1, pc=None):
+        """Device milliseconds of ``reps`` ``solveMany`` runs on the assembled right-hand side scaled by ``j + 1`` and the
+        iteration counts of the last (``pfem_multi_bench``): ``(ms[reps], iterations[nrhs])``."""
+        ms = np.zeros(reps); its = np.zeros(nrhs, dtype=np.int32)
+        L.check(L.lib().pfem_multi_bench(self._h, int(nrhs), int(reps), self._PC_CODES.get(pc, pc), _p(ms), _p(its)), "pfem_multi_bench")
+        return ms, its
+
+    # one launch of a kernel of solveMany on panels of the caller's (pfem_multi_probe_*).  The control block travels as a dict
+    # of arrays over the mb columns (MCG_FIELDS) with the scalars "running" and "step".
+    MCG_BLOCKS = 1024                # blocks of a vector kernel of solveMany at most = rows of partials
+    MCG_FOLD = 32                    # rows of folded product partials
+    MCG_FIELDS = ("beta", "rn0", "ttol", "rn", "alpha", "bb", "flag", "its", "verdict")
+
+    @staticmethod
+    def _mcg_ctl(ctl, mb):
+        c = L.McgCtl()
+        if ctl is not None:
+            for f in PetscSolver.MCG_FIELDS:
+                if f in ctl:
+                    for j in range(mb):
+                        if f == "beta":
+                            c.beta[j][0], c.beta[j][1] = float(ctl[f][j][0]), float(ctl[f][j][1])
+                        elif f in ("flag", "its", "verdict"):
+                            getattr(c, f)[j] = int(ctl[f][j])
+                        else:
+                            getattr(c, f)[j] = float(ctl[f][j])
+            c.running = int(ctl.get("running", 0))
+            c.step = int(ctl.get("step", 0))
+        return c
+
+    @staticmethod
+    def _mcg_dict(c, mb):
+        d = {f: np.array([getattr(c, f)[j] for j in range(mb)]) for f in PetscSolver.MCG_FIELDS if f != "beta"}
+        d["beta"] = np.array([[c.beta[j][0], c.beta[j][1]] for j in range(mb)])
+        d["running"], d["step"] = c.running, c.step
+        return d
+
+    @staticmethod
+    def _panels(panels):
+        out = [np.array(b, dtype=np.float64, order="C", ndmin=2) for b in panels]
+        n, mb = out[0].shape
+        if mb not in (4, 8) or n < 1 or any(b.shape != (n, mb) for b in out):
+            raise ValueError(f"panels of one shape n x 4 / 8 with n >= 1, not {[b.shape for b in out]}")
+        return out, n, mb
+
+    def multiProbeInit(self, B, dinv=None):
+        """One launch of ``k_mcg_init`` (``pfem_multi_probe_init``): ``(X, R, P, part)``, ``part`` the ``gv x 2 x mb``
+        partials of (r,z) and (z,z); without ``dinv`` (the gamg form) ``P`` and ``part`` come back NaN."""
+        (B,), n, mb = self._panels((B,))
+        dinv = None if dinv is None else _f64(dinv)
+        X, R, P = np.empty((n, mb)), np.empty((n, mb)), np.empty((n, mb))
+        part = np.empty((self.MCG_BLOCKS, 2, mb)); gv = C.c_int(0)
+        L.check(L.lib().pfem_multi_probe_init(self._h, mb, n, _p(B), _p(dinv), _p(X), _p(R), _p(P), _p(part), C.byref(gv)), "pfem_multi_probe_init")
+        return X, R, P, part[:gv.value].copy()
+
+    def multiProbeStart(self, part, rtol, abstol):
+        """One launch of ``k_mcg_start`` on ``part`` (``nparts x 2 x mb``) (``pfem_multi_probe_start``): the control block."""
+        part = _f64(part)
+        nparts, _, mb = part.shape
+        c = L.McgCtl()
+        L.check(L.lib().pfem_multi_probe_start(self._h, mb, nparts, _p(part), float(rtol), float(abstol), C.byref(c)), "pfem_multi_probe_start")
+        return self._mcg_dict(c, mb)
+
+    def multiProbeFold(self, part_pw):
+        """One launch of ``k_mcg_fold`` on ``part_pw`` (``nb x mb``) (``pfem_multi_probe_fold``): the ``32 x mb`` folded sums."""
+        part_pw = _f64(part_pw)
+        nb, mb = part_pw.shape
+        out = np.empty((self.MCG_FOLD, mb))
+        L.check(L.lib().pfem_multi_probe_fold(self._h, mb, nb, _p(part_pw), _p(out)), "pfem_multi_probe_fold")
+        return out
+
+    def multiProbeUpdate(self, ctl, fold_pw, W, R, dinv=None):
+        """One launch of ``k_mcg_update`` (``pfem_multi_probe_update``): ``(ctl, R, part)``."""
+        (W, R), n, mb = self._panels((W, R))
+        fold_pw = _f64(fold_pw); dinv = None if dinv is None else _f64(dinv)
+        if fold_pw.shape != (self.MCG_FOLD, mb):
+            raise ValueError(f"fold_pw must be {self.MCG_FOLD} x {mb}")
+        c = self._mcg_ctl(ctl, mb)
+        part = np.empty((self.MCG_BLOCKS, 2, mb)); gv = C.c_int(0)
+        L.check(L.lib().pfem_multi_probe_update(self._h, mb, n, C.byref(c), _p(fold_pw), _p(W), _p(dinv), _p(R), _p(part), C.byref(gv)),
+                "pfem_multi_probe_update")
+        return self._mcg_dict(c, mb), R, part[:gv.value].copy()
+
+    def multiProbeDots(self, R, Z, ctl=None, fold_pw=None):
+        """One launch of ``k_mcg_dots`` (``pfem_multi_probe_dots``): the ``gv x 2 x mb`` partials."""
+        (R, Z), n, mb = self._panels((R, Z))
+        fold_pw = None if fold_pw is None else _f64(fold_pw)
+        c = None if ctl is None else self._mcg_ctl(ctl, mb)
+        part = np.empty((self.MCG_BLOCKS, 2, mb)); gv = C.c_int(0)
+        L.check(L.lib().pfem_multi_probe_dots(self._h, mb, n, None if c is None else C.byref(c), _p(fold_pw), _p(R), _p(Z), _p(part), C.byref(gv)),
+                "pfem_multi_probe_dots")
+        return part[:gv.value].copy()
+
+    def multiProbeVerdict(self, ctl, part, dtol, maxits):
+        """One launch of ``k_mcg_verdict`` on ``part`` (``nparts x 2 x mb``) (``pfem_multi_probe_verdict``): the control block."""
+        part = _f64(part)
+        nparts, _, mb = part.shape
+        c = self._mcg_ctl(ctl, mb)
+        L.check(L.lib().pfem_multi_probe_verdict(self._h, mb, C.byref(c), nparts, _p(part), float(dtol), int(maxits)), "pfem_multi_probe_verdict")
+        return self._mcg_dict(c, mb)
+
+    def multiProbeDirection(self, ctl, R, P, X, dinv=None, Z=None):
+        """One launch of ``k_mcg_direction`` (``pfem_multi_probe_direction``): ``(P, X)``; ``Z`` instead of ``dinv``: the gamg form."""
+        (R, P, X), n, mb = self._panels((R, P, X))
+        dinv = None if dinv is None else _f64(dinv)
+        Z = None if Z is None else self._panels((Z,))[0][0]
+        c = self._mcg_ctl(ctl, mb)
+        L.check(L.lib().pfem_multi_probe_direction(self._h, mb, n, C.byref(c), _p(R), _p(dinv), _p(Z), _p(P), _p(X)), "pfem_multi_probe_direction")
+        return P, X
+
+    def multiSpmmDot(self, P):
+        """``(K P, pw)`` for a panel ``P`` (``n_local x 4 / 8``) by the product kernel of ``solveMany`` and the fold of its
+        partials (``pfem_multi_spmm_dot``): ``pw[j]`` is ``(p_j, K p_j)`` as the update kernel reads it."""
+        (P,), n, mb = self._panels((P,))
+        W, pw = np.empty_like(P), np.empty(mb)
+        L.check(L.lib().pfem_multi_spmm_dot(self._h, mb, _p(P), _p(W), _p(pw)), "pfem_multi_spmm_dot")
+        return W, pw
 
     # ---- one launch of a stepper kernel on vectors of the caller's (pfem_imp_probe_*, pfem_dyn_probe_step) ----------------------
     MAX_GRID = 2048                  # blocks of a stepper's vector kernel at most = partials per sum
